@@ -1,7 +1,18 @@
 """bench.py — GBP iterations/s of the MI355X engine on BASELINE.json's synthetic graphs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run measures the headline and nothing else: set-up, W warm-up steps, ONE timed block of exactly K steps, the
+outputs (--dump-outputs), the line.  --full adds everything else the line can hold: `repeats` (default 15) repetitions
+of the block with device times beside them, configs[1], the submission variants, the sustained run, launch-per-segment,
+whole driver ticks, the dynamic tick, a reference scenario, the CPU baseline with its parity check, rooflines and
+launch counts.
+
+--dump-outputs DIR: what the headline's world holds after the last timed step — the beliefs a caller reads back
+(mgx_read_beliefs: eta [V][4], lam [V][4][4], mean [V][4], f64) and the global ids of the robots they belong to — as
+DIR/<name>.npy.  At N = 1 the world runs exactly the warm-up and the timed steps (the pre-heat runs on a second copy
+of it), so the same arguments give the same inputs and the same step count on every run.
 
 A "step" is ONE GBP iteration (one schedule step: internal factor + variable sweep, external factor sweep ->
 routing -> external variable sweep -> routing) over 1000 robots x 16 horizon per GPU.  Steps are
@@ -16,9 +27,9 @@ of 1000 robots' worth of graph per second, the same unit at every N.
 `configs1`: BASELINE configs[1] (the same robots without inter-robot factors; at N > 1 independent shards, no
 exchange), with its own roofline and CPU baseline.
 
-Timing protocol (declared in the line): W warm-up steps, a clock pre-heat of `preheat_ms`, then `repeats`
-repetitions of EXACTLY K steps, each bracketed by barrier + synchronize, MAX over ranks per repetition; `value`
-comes from the MEDIAN repetition (`ms_per_step`), the spread is reported beside it.
+Timing protocol (declared in the line): a clock pre-heat of `preheat_ms` (N = 1: on a second copy of the world), W
+warm-up steps, then `repeats` repetitions (plain run: 1) of EXACTLY K steps, each bracketed by barrier + synchronize,
+MAX over ranks per repetition; `value` comes from the MEDIAN repetition (`ms_per_step`), the spread is reported beside it.
 """
 import argparse
 import json
@@ -37,6 +48,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md: 8.0 TB/s peak, 
 # = half the guide's 157.3 TFLOP/s FP32 vector figure; as an issue rate: one f64 VALU wave-instruction per SIMD per 4 clocks
 F64_VALU_WAVE_INSTR_PER_S = 1024 * 2.4e9 / 4.0
 SCHEDULE_LEN = 10
+PREHEAT_CHUNK = 200  # steps per synchronised block of the pre-heat (a large K must not stretch it far past preheat_ms)
+DUMP_LIMIT_BYTES = 64 << 20  # --dump-outputs: beyond this a fixed, seeded sample of the variables is written
 PROFILE_TAG = "r05"
 
 
@@ -45,7 +58,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=15, help="repetitions of the timed K-step block (median reported)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline (see the module docstring); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline world's beliefs after the last timed step as DIR/<name>.npy")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="repetitions of the timed K-step block (median reported); default 1, 15 with --full")
     ap.add_argument("--preheat-ms", type=float, default=60.0, help="untimed work in front of the repetitions (clock ramp)")
     ap.add_argument("--robots-per-gpu", type=int, default=1000)
     ap.add_argument("--horizon", type=int, default=16)
@@ -67,7 +85,10 @@ def parse():
     ap.add_argument("--role", default="main", choices=["main", "direct-child", "rccl-child"],
                     help="*-child: one rank of an isolated measurement of the sharded workload with the exchange inside the "
                          "engine (direct: peer-mapped stores; rccl: grouped ncclSend / ncclRecv), spawned by the main role")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 15 if a.full else 1
+    return a
 
 
 def run_steps(iterate, n, steps_one_tick, batch=None, group=1):
@@ -97,19 +118,28 @@ def run_steps(iterate, n, steps_one_tick, batch=None, group=1):
     return launches
 
 
-def timed(torch, dist, iterate, steps_one_tick, a, multi, red_dev="cuda", sync=None, batch=None, group=1, flush=None):
+def timed(torch, dist, iterate, steps_one_tick, a, multi, red_dev="cuda", sync=None, batch=None, group=1, flush=None,
+          preheat=None, between=None, device=True):
     """The contract's measurement, repeated: W warm-up steps, a pre-heat, then `repeats` x [barrier + synchronize,
     EXACTLY K steps, barrier + synchronize].  Returns per-repetition (wall seconds MAX over ranks, device seconds
-    between HIP events on the launch stream MAX over ranks).
+    between HIP events on the launch stream MAX over ranks; None with device=False: no such repetitions).
     sync: the world's own synchronize (mgx_synchronize: a launch that lingers for the next schedule is told to end first — waiting
-    on the stream by other means would wait out its bound); flush: the same without the wait, in front of the closing event."""
+    on the stream by other means would wait out its bound); flush: the same without the wait, in front of the closing event.
+    preheat: (iterate, sync, batch) of a second world built like this one — the pre-heat runs there, in front of the warm-up, so
+    that this world runs the warm-up and the timed steps and nothing else; between: called after the wall-clock repetitions."""
     sync = sync or torch.cuda.synchronize
     flush = flush or (lambda: None)
-    run_steps(iterate, a.warmup, steps_one_tick, batch, group)
-    sync()
+    p_iterate, p_sync, p_batch = preheat or (iterate, sync, batch)
+    if preheat is None:
+        run_steps(iterate, a.warmup, steps_one_tick, batch, group)
+        sync()
+    chunk = max(min(a.steps, PREHEAT_CHUNK), SCHEDULE_LEN)
     t_end = time.perf_counter() + a.preheat_ms * 1e-3
     while time.perf_counter() < t_end:  # the same work, untimed: clocks ramp up in the first tens of milliseconds
-        run_steps(iterate, max(a.steps, SCHEDULE_LEN), steps_one_tick, batch, group)
+        run_steps(p_iterate, chunk, steps_one_tick, p_batch, group)
+        p_sync()
+    if preheat is not None:
+        run_steps(iterate, a.warmup, steps_one_tick, batch, group)
         sync()
     walls, devs = [], []
     for _ in range(a.repeats):  # wall clock: nothing but the K steps between the two barrier + synchronize pairs
@@ -122,6 +152,14 @@ def timed(torch, dist, iterate, steps_one_tick, a, multi, red_dev="cuda", sync=N
             dist.barrier()
         sync()
         walls.append(time.perf_counter() - t0)
+    if between is not None:
+        between()
+    if not device:
+        if multi:
+            t = torch.tensor(walls, dtype=torch.float64, device=red_dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            walls = [float(x) for x in t]
+        return walls, None
     for _ in range(a.repeats):  # device time of the same block: HIP events on the launch stream (own repetitions: recording them costs host time)
         sync()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -186,11 +224,34 @@ def settle_resident(sw, ref, steps_one_tick, agree, max_ticks=40):
 
 
 def summary(walls, devs, steps, units_per_step=1.0):
-    """median repetition -> throughput; spread of the repetitions beside it"""
-    w, d = statistics.median(walls), statistics.median(devs)
-    return {"value": units_per_step * steps / w, "ms_per_step": w / steps * 1e3, "device_ms_per_step": d / steps * 1e3,
+    """median repetition -> throughput; spread of the repetitions beside it (devs None: no device times)"""
+    w, d = statistics.median(walls), (statistics.median(devs) if devs else None)
+    return {"value": units_per_step * steps / w, "ms_per_step": w / steps * 1e3, "device_ms_per_step": d / steps * 1e3 if d is not None else None,
             "wall_s_median": w, "device_s_median": d,
             "spread": {"repeats": len(walls), "ms_per_step_min": min(walls) / steps * 1e3, "ms_per_step_max": max(walls) / steps * 1e3}}
+
+
+def dump_outputs(out_dir, got):
+    """--dump-outputs: (global robot ids, eta, lam, mean) as the world's reader returns them -> out_dir/<name>.npy, f64.  Where all
+    variables would take more than DUMP_LIMIT_BYTES, a fixed, seeded sample of them is written (their indices: sample_rows.npy).
+    Returns the names written."""
+    import numpy as np
+    ids, eta, lam, mean = got
+    arrays = {"belief_eta": np.asarray(eta, np.float64), "belief_lam": np.asarray(lam, np.float64),
+              "belief_mean": np.asarray(mean, np.float64)}
+    extra = {"robot_ids": np.asarray(ids, np.float64)}
+    rows = arrays["belief_eta"].shape[0]
+    per_row = sum(x[0].nbytes for x in arrays.values()) if rows else 0
+    budget = DUMP_LIMIT_BYTES - extra["robot_ids"].nbytes - 64 * 1024  # (room for the .npy headers)
+    if rows and rows * per_row > budget:
+        keep = np.sort(np.random.default_rng(805).choice(rows, size=budget // (per_row + 8), replace=False))
+        arrays = {k: v[keep] for k, v in arrays.items()}
+        extra["sample_rows"] = keep.astype(np.float64)
+    arrays.update(extra)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+    return sorted(arrays)
 
 
 def cpu_baseline(sc, seconds, check=None):
@@ -614,7 +675,9 @@ def main():
         "ms_per_step": None, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f64", "data": "synthetic",
         "timing": "median of `repeats` repetitions of exactly `steps` steps, each between barrier + synchronize, MAX over ranks "
-                  "per repetition, after `warmup` steps and `preheat_ms` of untimed work",
+                  "per repetition, after `warmup` steps and `preheat_ms` of untimed work" +
+                  (" (the pre-heat on a second copy of the world, in front of the warm-up)" if not multi else ""),
+        "full": a.full,
     }
 
     # who ran: what torch.distributed saw, each rank's device, the collective library — so that "RCCL saw N ranks on N
@@ -644,7 +707,7 @@ def main():
 
     # ---- configs[1]: dynamics + obstacle factors, no inter-robot factors; ranks are independent shards ------------
     sc1 = None
-    if not a.no_configs1:
+    if a.full and not a.no_configs1:
         sc1 = S.grid_scenario(n_loc, K, interrobot=False, seed=805 + rank)
         w1 = World(sc1["params"], stream=stream, fma=a.fma)
         S.populate(w1, sc1)
@@ -710,27 +773,44 @@ def main():
         dist.broadcast_object_list(flag, src=0)
         probe_ok = flag[0]
 
+    # --dump-outputs: what a timed world holds after its last timed step, read before anything else runs on it
+    outputs = {}
+
+    def snapshot(key, world):
+        return (lambda: outputs.__setitem__(key, world.read_beliefs())) if a.dump_outputs and rank == 0 else None
+
     G = a.ticks_per_submission if a.ticks_per_submission > 0 else (2 if multi else 1)
-    walls, devs = timed(torch, dist, sw.iterate, sc2["steps"], a, multi, red_dev, sync=sw.synchronize, batch=sw.batch, group=G, flush=sw.flush)
+    twin = None
+    if not multi:  # the pre-heat's world: the same scenario built once more, so that `sw` runs the warm-up and the timed steps only
+        twin = sharded.ShardedWorld(sc2, rank, world_size, lambda p: World(p, stream=stream, fma=a.fma), comm=None)
+        twin.world.sweep(0, 0, 0)
+    walls, devs = timed(torch, dist, sw.iterate, sc2["steps"], a, multi, red_dev, sync=sw.synchronize, batch=sw.batch, group=G, flush=sw.flush,
+                        preheat=(twin.iterate, twin.synchronize, twin.batch) if twin is not None else None,
+                        between=snapshot("collective", sw), device=a.full)
+    if twin is not None:
+        twin.synchronize()
+        twin.world.close()
+        del twin
     sw.iterate(sc2["steps"])
     resident = sw.world.last_launch_count() == 1  # the engine ran the 10-step schedule as ONE resident launch (or posted it into one)
     sw.synchronize()
-    # the timed block once more, counted: sweep-kernel launches (a schedule POSTED into a lingering launch is no launch)
-    res0 = int(sw.world.resident_stats()[0])
-    head_launches = run_steps(sw.iterate, a.steps, sc2["steps"], sw.batch, G)
-    sw.flush()
-    if resident:
-        head_launches = int(sw.world.resident_stats()[0]) - res0
+    head_launches = None
+    if a.full:  # the timed block once more, counted: sweep-kernel launches (a schedule POSTED into a lingering launch is no launch)
+        res0 = int(sw.world.resident_stats()[0])
+        head_launches = run_steps(sw.iterate, a.steps, sc2["steps"], sw.batch, G)
+        sw.flush()
+        if resident:
+            head_launches = int(sw.world.resident_stats()[0]) - res0
     lst = [int(x) for x in sw.world.linger_stats()] if hasattr(sw.world, "linger_stats") else None
     r2 = summary(walls, devs, a.steps, units_per_step=world_size)
     per_tick, variants = None, {}
     a_warm = argparse.Namespace(**{**vars(a), "preheat_ms": 0.0})  # (clocks are up: a second timed pass needs no pre-heat of its own)
-    if G > 1:  # the same workload, one submission per tick — always beside a batched headline
+    if a.full and G > 1:  # the same workload, one submission per tick — always beside a batched headline
         walls_t, devs_t = timed(torch, dist, sw.iterate, sc2["steps"], a_warm, multi, red_dev, sync=sw.synchronize, flush=sw.flush)
         rt = summary(walls_t, devs_t, a.steps, units_per_step=world_size)
         per_tick = {"value": round(rt["value"], 2), "ms_per_step": rt["ms_per_step"], "device_ms_per_step": rt["device_ms_per_step"],
                     "what": "the same workload without mgx_batch_*: every 10-step tick its own mgx_iterate call, nothing bracketed"}
-    elif not multi and not a.no_extras:
+    elif a.full and not multi and not a.no_extras:
         # what the two ways of keeping the graphs in LDS across ticks are worth, each against the same world: ticks bracketed two at
         # a time (mgx_batch_*: round 4's headline), and lingering switched off (every tick a launch of its own)
         walls_t, devs_t = timed(torch, dist, sw.iterate, sc2["steps"], a_warm, multi, red_dev, sync=sw.synchronize, batch=sw.batch, group=2, flush=sw.flush)
@@ -744,7 +824,7 @@ def main():
                                        "what": "mgx_set_linger(world, 0): every 10-step tick a resident launch of its own (graphs HBM -> LDS -> HBM per tick)"}
         sw.world.set_linger(None)
     sustained_head = None
-    if a.sustained_seconds > 0:
+    if a.full and a.sustained_seconds > 0:
         sustained_head = sustained(torch, dist, sw.iterate, sc2["steps"], a.sustained_seconds, r2["ms_per_step"], multi, red_dev,
                                    sync=sw.synchronize, units_per_step=world_size, batch=sw.batch, group=G)
     by_transport = {("one GPU, no exchange" if not multi else "collective"): round(r2["value"], 2)}
@@ -795,13 +875,15 @@ def main():
                 if verified:
                     try:
                         walls_i, devs_i = timed(torch, dist, sw_in.iterate, sc2["steps"], a, True, red_dev, sync=sw_in.synchronize,
-                                                batch=sw_in.batch, group=G)
+                                                batch=sw_in.batch, group=G, between=snapshot("in_engine", sw_in), device=a.full)
                         sw_in.iterate(sc2["steps"])
                         sw_in.synchronize()
                         lpt_in = sw_in.world.last_launch_count()
-                        launches_in = run_steps(sw_in.iterate, a.steps, sc2["steps"], sw_in.batch, G)
-                        sw_in.synchronize()
-                        if G > 1:  # one submission per tick, for the same wiring
+                        launches_in = None
+                        if a.full:
+                            launches_in = run_steps(sw_in.iterate, a.steps, sc2["steps"], sw_in.batch, G)
+                            sw_in.synchronize()
+                        if a.full and G > 1:  # one submission per tick, for the same wiring
                             walls_t, devs_t = timed(torch, dist, sw_in.iterate, sc2["steps"], a_warm, True, red_dev, sync=sw_in.synchronize)
                             rt = summary(walls_t, devs_t, a.steps, units_per_step=world_size)
                             per_tick = {"value": round(rt["value"], 2), "ms_per_step": rt["ms_per_step"], "device_ms_per_step": rt["device_ms_per_step"],
@@ -813,12 +895,12 @@ def main():
                     in_engine = {"transport": got, "result": ri, "launches_per_tick": lpt_in, "launches": launches_in,
                                  "resident_stats": [int(x) for x in sw_in.world.resident_stats()]}
                     try:
-                        if a.sustained_seconds > 0:
+                        if a.full and a.sustained_seconds > 0:
                             in_engine["sustained"] = sustained(torch, dist, sw_in.iterate, sc2["steps"], a.sustained_seconds, ri["ms_per_step"],
                                                                True, red_dev, sync=sw_in.synchronize, units_per_step=world_size,
                                                                batch=sw_in.batch, group=G)
                             in_engine["resident_stats"] = [int(x) for x in sw_in.world.resident_stats()]
-                        if got == "direct+resident":
+                        if a.full and got == "direct+resident":
                             # the same wiring with resident launches switched off on every rank: what the exchange costs WITHOUT the
                             # in-launch hand-off (the scaling curve's other half)
                             sw_in.world.set_resident_launches(False)
@@ -882,6 +964,9 @@ def main():
                                   "issued back to back are POSTED into the resident launch that is there (it lingers for them: the graphs stay in LDS "
                                   "across the calls, include/mgx.h); the timed block's closing synchronisation ends the launch.  Bit-identical "
                                   "(tests/test_gpu_linger.py)"}
+    if not a.full:  # (counted by running the timed block once more: --full)
+        for k in ("launches_per_timed_block", "iterations_per_launch"):
+            del line["submission"][k]
     if lst is not None and not multi:
         line["submission"]["linger_stats"] = {"launches_that_lingered": lst[0], "schedules_posted": lst[1], "posts_rerun_as_launches": lst[2],
                                               "launches_ended_by_device": lst[3]}
@@ -906,10 +991,11 @@ def main():
                                    "run in ONE resident launch (the first launches it, the others are posted into it)") +
                                   ", neighbouring workgroups hand their snapshot records over inside it" if resident else "1 GPU",
                    "ghost_robots_this_rank": len(sw.plan.ghosts)},
-        "roofline": roofline(kernel, bytes2 * it_per_launch, launches, head["device_s_median"],
-                             ("config2_resident" if resident else "config2") if full_size else "", it_per_launch,
-                             prof_note="counters of the N = 1 instantiation of the same per-GPU workload" if multi else ""),
     })
+    if a.full:
+        line["roofline"] = roofline(kernel, bytes2 * it_per_launch, launches, head["device_s_median"],
+                                    ("config2_resident" if resident else "config2") if full_size else "", it_per_launch,
+                                    prof_note="counters of the N = 1 instantiation of the same per-GPU workload" if multi else "")
     if multi and rank == 0 and children:
         line["in_engine_transports"] = children  # the probes (isolated child processes)
         for key, r in children.items():
@@ -920,7 +1006,7 @@ def main():
     # ---- N = 1: the same workload with resident launches switched off for THIS world (one launch per iteration): what a
     # rank of a sharded world would pay WITHOUT the in-launch hand-off, so that the scaling curve separates the cost of
     # the exchange from the loss of residency
-    if not multi and resident:
+    if a.full and not multi and resident:
         try:
             w_seg = World(sc2["params"], stream=stream, fma=a.fma)
             S.populate(w_seg, sc2)
@@ -938,7 +1024,7 @@ def main():
             line["launch_per_segment"] = {"error": f"{type(e).__name__}: {e}"}
 
     # ---- N = 1 extras: whole driver ticks, topology churn, a reference scenario end to end ----------------------------
-    if not multi and not a.no_extras:
+    if a.full and not multi and not a.no_extras:
         w = sw.world
         tk = S.tick_inputs(sc2)
         n_ticks = max(200, a.steps // 10)
@@ -1013,7 +1099,7 @@ def main():
             line["scenario"] = {"error": f"{type(e).__name__}: {e}"}
 
     # ---- CPU baseline: rank 0, N = 1 only ---------------------------------------------------------------------------
-    if rank == 0 and not multi and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not multi and not a.no_cpu_baseline:
         # parity of the exact path the headline ran: a fresh world, the timed block's submission, read back
         check = None
         try:
@@ -1044,6 +1130,9 @@ def main():
             line["configs1"]["cpu_baseline"] = cb1
             line["configs1"]["speedup_vs_cpu_baseline"] = round(line["configs1"]["value"] / cb1["value"], 1)
 
+    if a.dump_outputs and rank == 0:
+        line["outputs"] = {"files": dump_outputs(a.dump_outputs, outputs["in_engine" if in_engine is not None else "collective"]),
+                           "what": "the headline world's beliefs after its last timed step (robot ids, eta, lam, mean), f64 .npy"}
     if rank == 0:
         print(json.dumps(line))
     if multi:

@@ -129,7 +129,7 @@ def test_bench_two_rank_control_flow_dry_run():
     env = dict(os.environ, MGX_BENCH_BACKEND="gloo", MGX_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0",
                MGX_HALO_TIMEOUT_MS="20000", MGX_RESIDENT_CENSUS_SHARDED_US="500000")  # (both ranks share one GPU here)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", _free_port(), bench, "--gpus", "2", "--steps", "60", "--warmup", "20", "--robots-per-gpu", "144",
+           "--master-port", _free_port(), bench, "--full", "--gpus", "2", "--steps", "60", "--warmup", "20", "--robots-per-gpu", "144",
            "--horizon", "10", "--deadline", "150", "--repeats", "3"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
@@ -161,7 +161,7 @@ def test_bench_bare_launch_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MGX_BENCH_BACKEND="gloo", MGX_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", MGX_HALO_TIMEOUT_MS="20000",
                MGX_RESIDENT_CENSUS_SHARDED_US="500000")
-    cmd = [sys.executable, bench, "--gpus", "2", "--steps", "40", "--warmup", "10", "--robots-per-gpu", "144", "--horizon", "10",
+    cmd = [sys.executable, bench, "--full", "--gpus", "2", "--steps", "40", "--warmup", "10", "--robots-per-gpu", "144", "--horizon", "10",
            "--deadline", "150", "--repeats", "3", "--sustained-seconds", "0.5", "--no-configs1", "--ticks-per-submission", "2"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=400)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]
@@ -195,7 +195,7 @@ def test_bench_ranks_fall_back_together_when_one_probe_fails(n):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MGX_BENCH_BACKEND="gloo", MGX_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", MGX_HALO_TIMEOUT_MS="20000",
                MGX_TEST_FAIL_DIRECT_SETUP_RANK=str(n - 1))
-    cmd = [sys.executable, bench, "--gpus", str(n), "--steps", "20", "--warmup", "10", "--robots-per-gpu", "64", "--horizon", "10",
+    cmd = [sys.executable, bench, "--full", "--gpus", str(n), "--steps", "20", "--warmup", "10", "--robots-per-gpu", "64", "--horizon", "10",
            "--deadline", "120", "--repeats", "3", "--sustained-seconds", "0.2", "--no-configs1"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
     assert r.returncode == 0, r.stderr.decode(errors="replace")[-3000:]

@@ -14,7 +14,8 @@ from magics_amd import config, environment, hostlib, sim, spawner
 from magics_amd.prng import WyRand
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/config/scenarios"
+# the reference's config/scenarios/*/{config.toml, environment.yaml, formation.yaml}, stored unmodified
+REF = os.path.join(ROOT, "tests", "golden", "scenario_files")
 F = np.float32
 
 
@@ -29,7 +30,6 @@ def _plain(x):
 
 
 # ---- readers ----------------------------------------------------------------------------------------
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference's scenario files are not on this machine")
 def test_readers_reproduce_the_fixtures(scenarios):
     """tests/golden/scenarios.json IS what the readers make of the reference's files."""
     names = sorted(os.listdir(REF))

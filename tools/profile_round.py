@@ -67,7 +67,7 @@ def main():
     prof = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles")
     os.makedirs(prof, exist_ok=True)
     out = [f"# rocprofv3 summary — {tag}", "",
-           "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps 20 --warmup 20 --repeats 60 --preheat-ms 20 "
+           "Command: `rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps 20 --warmup 20 --repeats 60 --preheat-ms 20 "
            "--no-cpu-baseline --no-extras --sustained-seconds 0` (tools/profile_round.sh; MI355X) — the driver's block shape, repeated.  Every tick "
            "is its own mgx_iterate call: `<16, 2, true, false>`: configs[2], a timed block is ONE resident dispatch of 20 iterations (the first tick "
            "launches it, the second is posted into the lingering launch, the closing synchronisation ends it); `<16, 0, false, false>`: configs[1] "
@@ -89,7 +89,7 @@ def main():
     for k, (avg, n, med) in sorted(dur.items()):
         out.append(f"| k_robot_sweep{k} | {n} | {avg:.2f} | {med:.2f} |")
     traffic = {"_kernel_digest": kernel_digest(), "_source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE / --pmc SQ_* (separate passes, tools/profile_round.sh) on `python3 bench.py "
-                          f"--steps 20 --warmup 20 --repeats 60 --no-cpu-baseline --no-extras`, MI355X, round {tag}.  KiB per dispatch as reported; per "
+                          f"--full --steps 20 --warmup 20 --repeats 60 --no-cpu-baseline --no-extras`, MI355X, round {tag}.  KiB per dispatch as reported; per "
                           "MI355X_MICROARCH.md (HBM section) gfx950 FETCH_SIZE counts half the bytes of wide 16-B-per-lane streaming reads, so "
                           "bench.py doubles the reads (an upper bound here: part of the staging uses 8-B loads)."}
     keys = {"<16, 0, false, false>": ("config1", ""), "<16, 2, true, false>": ("config2_resident", ""), "<16, 2, false, false>": ("config2", "_np")}

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 # (the driver's own block shape — 20 steps = 2 ticks, one mgx_iterate call each: the first launches, the second is posted into the
 # lingering launch, the closing synchronisation ends it — repeated often: every dispatch of the timed blocks holds 20 iterations)
-B="python3 bench.py --steps 20 --warmup 20 --repeats 60 --preheat-ms 20 --no-cpu-baseline --no-extras --sustained-seconds 0"
+B="python3 bench.py --full --steps 20 --warmup 20 --repeats 60 --preheat-ms 20 --no-cpu-baseline --no-extras --sustained-seconds 0"
 out=gpurun_out/${tag}
 SQ="SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_LDS SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY"
 # what the VALU instructions ARE (f64 arithmetic by kind) and how many of a wave's 64 lanes they keep busy
