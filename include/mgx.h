@@ -219,9 +219,9 @@ int mgx_set_linger(mgx_world *w, int32_t microseconds /* < 0: default (environme
 int mgx_linger_stats(mgx_world *w, uint64_t *launches, uint64_t *posts, uint64_t *reruns, uint64_t *ended_by_device);
 /* Per-world switch for the above (default: on): 0 keeps every schedule of THIS world on the launch-per-segment path — what
  * MGX_PERSISTENT=0 does for the whole process.  For measuring one against the other; results are identical either way.
- * On a sharded world with resident launches agreed on (mgx_halo_resident_connect) every rank has to switch alike.
+ * On a sharded world with resident launches agreed on (mgx_halo_resident_connect_peers) every rank has to switch alike.
  * 2 (diagnostic): on, but this world DECLINES every resident launch — on a sharded world whose ranks agree on every schedule
- * it says no where the others look (mgx_halo_resident_connect), so every rank takes the fall-back; elsewhere like 0. */
+ * it says no where the others look (mgx_halo_resident_connect_peers), so every rank takes the fall-back; elsewhere like 0. */
 int mgx_set_resident_launches(mgx_world *w, int32_t enabled);
 /* Whether factors switched back on (mgx_set_enabled) are still taking their first updates from the inboxes they froze with
  * (or inter-robot factors created while their kind was off still lack inbox keys): such schedules run launch by launch.
@@ -485,23 +485,34 @@ int mgx_halo_rccl_disconnect(mgx_world *w);
  * mgx_external_factor_iteration) runs the exchange first, asynchronously on the world's stream.
  * All ranks must issue the same sequence of such launches (they do: one schedule).
  *
- * Wiring, after mgx_halo_plan (send list grouped by consumer, receive list grouped by producer):
- *   1. mgx_halo_direct_setup: allocates this rank's receive area (2 x n_recv records, fine-grained
- *      device memory) and n_sources arrival counters; returns their device addresses.
- *   2. the ranks swap these addresses — mgx_ipc_export / mgx_ipc_open across processes (hipIpc*),
- *      raw pointers inside one process — together with, per producer, the record offset of its
- *      segment in the consumer's area and the address of its counter (flag_base + 8 * index of the
- *      producer among the consumer's sources).
- *   3. mgx_halo_direct_connect with, per consumer p (send-list segment send_first[p] ..
- *      send_first[p+1]): the consumer's area, its size in records, the offset of this rank's
- *      segment in it and this rank's counter there.  Producers and consumers of a rank must be the
- *      same set of peers (inter-robot factors come in pairs, robot.rs:1490-1541).
+ * The wiring is made ONCE and outlives changes of the exchange lists (a world that follows its topology: connections across
+ * ranks come and go with robot.rs:1386-1586, mgx_update_topology + mgx_halo_plan_from_connections); a rank's PEERS are the ranks
+ * it shares a boundary with (fixed lists: those it sends to, which are those it receives from — inter-robot factors come in
+ * pairs, robot.rs:1490-1541) or every other rank (lists that change).  After mgx_halo_plan* (send list grouped by consumer,
+ * receive list grouped by producer):
+ *   1. mgx_halo_direct_setup_slots: allocates this rank's receive area — `slot_capacity` record slots per parity, one per ghost
+ *      robot of this rank, slot = the robot's place among the rank's ghosts in device order (mgx_halo_ghost_slots; capacity >=
+ *      their number, room for robots that join), fine-grained device memory — and one arrival counter per peer
+ *      (n_sources = number of peers); returns their device addresses.  Every peer is a source with or without records in an
+ *      exchange: a rank that sends nothing still publishes the exchange number, a rank that receives nothing still waits for
+ *      all of them (that wait is its flow control: nobody gets two exchanges ahead of anybody).
+ *   2. the ranks swap these addresses — mgx_ipc_export / mgx_ipc_open across processes (hipIpc*), raw pointers inside one
+ *      process — together with the area's capacity, the slot of every robot in it, and per producer the address of its counter
+ *      (flag_base + 8 * index of the producer among the consumer's peers).
+ *   3. mgx_halo_direct_connect_slots, and again after every change of the lists, (re)aims the pushes — peers in the order of the
+ *      send list's segments (send_first: one per peer, possibly empty), for every entry of the send list the slot of that robot
+ *      in its consumer's area.  Exchange numbers go on across calls.  The aim outlives a relayout that keeps the robots' device
+ *      order (new obstacles, reset variables); a robot that joins, migrates or is released takes it away, and an exchange is
+ *      refused (MGX_ERR_STATE) until the pushes are aimed again.
  * A wait that exceeds MGX_HALO_TIMEOUT_MS (default 5000) gives up, leaves the ghosts untouched
  * and is reported by mgx_halo_direct_status (never a hung GPU). */
-int mgx_halo_direct_setup(mgx_world *w, uint32_t n_sources, void **recv_base, void **flag_base);
-int mgx_halo_direct_connect(mgx_world *w, uint32_t n_peers, const uint32_t *send_first,
-                            void *const *peer_recv_base, const uint64_t *peer_recv_records,
-                            const uint64_t *peer_record_offset, void *const *peer_flag_slot);
+int mgx_halo_direct_setup_slots(mgx_world *w, uint32_t n_sources, uint32_t slot_capacity, void **recv_base, void **flag_base);
+int mgx_halo_ghost_slots(mgx_world *w, uint32_t n, const int32_t *robots, int32_t *slots);
+/* the exchange lists as they stand (robot ids, by peer rank in the order of mgx_halo_plan_from_connections' counts) */
+int mgx_halo_get_lists(mgx_world *w, int32_t *send_robots, uint32_t send_capacity, int32_t *recv_robots, uint32_t recv_capacity,
+                       uint32_t *n_send, uint32_t *n_recv);
+int mgx_halo_direct_connect_slots(mgx_world *w, uint32_t n_peers, const uint32_t *send_first, void *const *peer_recv_base,
+                                  const uint64_t *peer_slot_capacity, const uint32_t *entry_slot, void *const *peer_flag_slot);
 /* The exchange by hand: MGX_HALO_PUSH sends this rank's records for the next exchange,
  * MGX_HALO_WAIT fills the ghosts once every producer has done so; both = what the launches do by
  * themselves.  A launch that finds its exchange already pushed only waits — ranks that share one
@@ -511,23 +522,6 @@ int mgx_halo_direct_connect(mgx_world *w, uint32_t n_peers, const uint32_t *send
 int mgx_halo_direct_exchange(mgx_world *w, uint32_t what);
 int mgx_halo_direct_status(mgx_world *w, uint64_t *exchanges, uint64_t *failed_exchange);
 int mgx_halo_direct_disconnect(mgx_world *w);
-/* The same exchange for a world whose exchange lists CHANGE (one that follows its topology: connections across ranks come and
- * go with robot.rs:1386-1586, mgx_update_topology + mgx_halo_plan_from_connections), wired once:
- *   mgx_halo_direct_setup_slots: the receive area has `slot_capacity` record slots per parity — one per ghost robot of this rank,
- *      slot = the robot's place among the rank's ghosts in device order (mgx_halo_ghost_slots; capacity >= their number, room for
- *      robots that join) — and EVERY other rank is a source (n_sources = ranks - 1), with or without records in an exchange:
- *      a rank that sends nothing still publishes the exchange number, a rank that receives nothing still waits for all of them
- *      (that wait is its flow control: nobody gets two exchanges ahead of anybody).
- *   mgx_halo_direct_connect_slots: after every change of the lists, (re)aims the pushes — peers in the order of the send list's
- *      segments (one per other rank, possibly empty), and for every entry of the send list the slot of that robot in its
- *      consumer's area.  Exchange numbers go on across calls. */
-int mgx_halo_direct_setup_slots(mgx_world *w, uint32_t n_sources, uint32_t slot_capacity, void **recv_base, void **flag_base);
-int mgx_halo_ghost_slots(mgx_world *w, uint32_t n, const int32_t *robots, int32_t *slots);
-/* the exchange lists as they stand (robot ids, by peer rank in the order of mgx_halo_plan_from_connections' counts) */
-int mgx_halo_get_lists(mgx_world *w, int32_t *send_robots, uint32_t send_capacity, int32_t *recv_robots, uint32_t recv_capacity,
-                       uint32_t *n_send, uint32_t *n_recv);
-int mgx_halo_direct_connect_slots(mgx_world *w, uint32_t n_peers, const uint32_t *send_first, void *const *peer_recv_base,
-                                  const uint64_t *peer_slot_capacity, const uint32_t *entry_slot, void *const *peer_flag_slot);
 
 /* ---- resident schedule launches on sharded worlds ----------------------------------------------------------------------
  * (replaces, like the exchanges above, the serial external phase and routing of robot.rs:1803-1859 and
@@ -542,13 +536,14 @@ int mgx_halo_direct_connect_slots(mgx_world *w, uint32_t n_peers, const uint32_t
  * progress word; the workgroups there poll it like the word of a local neighbour.  One exchange per external iteration as
  * before (robot.rs:1803-1859), with no host work and no kernel boundary.  A schedule that OPENS with an external iteration
  * takes the direct exchange (above) in front of the launch, so mgx_halo_direct_* has to be connected too.
- *   1. mgx_halo_resident_setup (after mgx_halo_plan and mgx_halo_direct_setup / _connect): allocates the ghost area; returns its
+ *   1. mgx_halo_resident_setup (after mgx_halo_plan and mgx_halo_direct_setup_slots / _connect_slots): allocates the ghost area; returns its
  *      address, the number of ghost slots, this rank's buffer parity and segment count (both advance in lockstep on all ranks:
  *      every rank issues the same schedules), the slot of every entry of the receive list (recv_slots[n_recv]) and whether
- *      this rank CAN run resident launches (eligible: inter-robot factors staged in LDS, every local robot's workgroup resident
- *      at once).  The ranks agree on that — all or none.
- *   2. mgx_halo_resident_connect with one entry per (local robot of the send list, rank that receives it): that rank's area,
- *      number of ghost slots, the robot's slot there, that rank's parity and segment count as returned by ITS setup.
+ *      this rank CAN run resident launches (eligible: 1 — inter-robot factors staged in LDS, every local robot's workgroup
+ *      resident at once; 2 — everything but inter-robot factors is there: on a world that follows its topology they may come
+ *      later, and every schedule is decided where the ranks agree; 0 — no).  The ranks agree on that — all or none.
+ *   2. mgx_halo_resident_connect_peers, ONCE: every peer's area (the peers of the direct exchange), its number of ghost slots,
+ *      parity and segment count as returned by ITS setup (what translates this rank's counts into each peer's is settled here).
  *      coordinator_area / n_ranks: the area of rank 0 as this rank maps it (rank 0: its own) and the number of ranks of the
  *      world.  The first word of that area is where the ranks AGREE on every schedule: the launches of one schedule wait for
  *      each other's records, so they go ahead together or not at all.  Each rank's launch signs in there once all its own
@@ -560,29 +555,21 @@ int mgx_halo_direct_connect_slots(mgx_world *w, uint32_t n_peers, const uint32_t
  *      mgx_resident_outcome; the next few schedules skip the resident form — the same ones on every rank).
  *      coordinator_area NULL or n_ranks < 2: no agreement; a rank whose peers never start then gives up after
  *      MGX_RESIDENT_TIMEOUT_MS (default 2000) and reports MGX_ERR_STATE with the world invalid — never a hung GPU.
+ *   3. mgx_halo_resident_aim, and again after every change of the lists, on every rank, with all ranks' launches through
+ *      (synchronise, barrier): (local robot, index of the peer in connect_peers' order, the robot's ghost slot there) per
+ *      boundary robot and peer that holds it as a ghost; the progress words of this rank's own ghosts start over at "through
+ *      with everything so far" (a robot that has just become a neighbour across ranks never stored one here).
  * From then on mgx_iterate / mgx_tick run eligible schedules as one launch per rank (mgx_last_launch_count == 1); all ranks
  * must have connected.  A change of the world's layout (robots added / removed) switches the resident form off on THAT rank
  * only; the peers may still hold its area mapped and store into it, so wiring again goes: barrier, mgx_halo_resident_disconnect
- * on every rank, the peers close their mappings, barrier, then setup / connect as above.  A setup while the previous wiring
+ * on every rank, the peers close their mappings, barrier, then setup / connect_peers / aim as above.  A setup while the previous wiring
  * has not been disconnected is refused (MGX_ERR_STATE). */
 int mgx_halo_resident_setup(mgx_world *w, void **area_base, uint32_t *n_ghost_slots, uint32_t *parity, uint64_t *segment_count,
                             int32_t *recv_slots, int32_t *eligible);
-int mgx_halo_resident_connect(mgx_world *w, uint32_t n_targets, const int32_t *robots, void *const *peer_area_base,
-                              const uint32_t *peer_ghost_slots, const uint32_t *peer_slot, const uint32_t *peer_parity,
-                              const uint64_t *peer_segment_count, void *coordinator_area, uint32_t n_ranks);
-int mgx_halo_resident_disconnect(mgx_world *w);
-/* The same for a world whose exchange lists CHANGE (one that follows its topology; with mgx_halo_direct_setup_slots for the
- * exchanges in front of launches): mgx_halo_resident_setup as above — `eligible` 2 says "everything but inter-robot factors is
- * there": they may come later, and every schedule is decided where the ranks agree — then ONCE
- *   mgx_halo_resident_connect_peers: every other rank's area, number of ghost slots, parity and segment count (what translates
- *      this rank's counts into each peer's is settled here), the coordinator area and the number of ranks as above;
- * and after every change of the lists, on every rank, with all ranks' launches through (synchronise, barrier):
- *   mgx_halo_resident_aim: (local robot, index of the peer in connect_peers' order, the robot's ghost slot there) per boundary
- *      robot and rank that now holds it as a ghost; the progress words of this rank's own ghosts start over at "through with
- *      everything so far" (a robot that has just become a neighbour across ranks never stored one here). */
 int mgx_halo_resident_connect_peers(mgx_world *w, uint32_t n_peers, void *const *peer_area_base, const uint32_t *peer_ghost_slots,
                                     const uint32_t *peer_parity, const uint64_t *peer_segment_count, void *coordinator_area, uint32_t n_ranks);
 int mgx_halo_resident_aim(mgx_world *w, uint32_t n_targets, const int32_t *robots, const uint32_t *peer_index, const uint32_t *peer_slot);
+int mgx_halo_resident_disconnect(mgx_world *w);
 /* What became of the resident launch the last mgx_iterate enqueued (it decides within microseconds of its start whether it goes
  * ahead: residency census, and on sharded worlds the ranks' agreement above).  Waits for that decision.
  *   MGX_RESIDENT_NONE      nothing was pending (the call ran launch by launch, or its outcome has been taken already)
@@ -598,7 +585,7 @@ int mgx_halo_resident_aim(mgx_world *w, uint32_t n_targets, const int32_t *robot
 #define MGX_RESIDENT_DECLINED 2
 int mgx_resident_outcome(mgx_world *w, int32_t *outcome);
 /* Whether mgx_iterate(w, steps, n) would be issued as a resident launch now — on a sharded world whose ranks agree on every
- * schedule (mgx_halo_resident_connect): whether every rank takes it to that agreement (the same answer on every rank) — rather
+ * schedule (mgx_halo_resident_connect_peers): whether every rank takes it to that agreement (the same answer on every rank) — rather
  * than launch by launch.  For hosts that have to know in advance which form a schedule takes (LocalCluster, as above). */
 int mgx_resident_ready(mgx_world *w, const uint8_t *steps, uint32_t n, int32_t *ready);
 /* Resident launches of this world so far, how many of them were declined (see above; each is followed by a back-off during

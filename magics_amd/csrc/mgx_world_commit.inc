@@ -375,6 +375,8 @@ static int commit(mgx_world *w) {
     if (!sweep_supports(K) || sweep_lds_bytes(K, 0) > 60 * 1024) return fail(MGX_ERR_INVALID, "K = %d not supported (3 <= K <= 45: the robot's graph has to fit 60 KB of LDS)", K);
 
     // device robot order: locals (id order), then ghosts
+    const std::vector<int> order_before = std::move(w->robot_of);
+    const int R_local_before = w->d.R_local;
     w->robot_of.clear();
     w->dev_of.assign(w->robots.size(), -1);
     for (size_t r = 0; r < w->robots.size(); r++)
@@ -572,7 +574,9 @@ static int commit(mgx_world *w) {
     w->flag_base = 0;
     w->resident_cap = w->resident_cap_sharded = -1;
     w->xres.connected = false;  // ghost slots and progress words belonged to the old layout: the ranks wire them again
-    w->direct.aimed = false;    // ... and a slot-wired direct exchange names device indices and slots of the old layout
+    // the direct exchange's pushes name device indices and ghost slots: they stay good for as long as the robots' device order does
+    // (a relayout for new obstacles or reset variables keeps it; a robot that joins, migrates or is released does not)
+    if (w->robot_of != order_before || R_local != R_local_before) w->direct.aimed = false;
     d.gxrec[0] = d.gxrec[1] = nullptr; d.gflag = nullptr; d.xp_ptr = nullptr; d.xp_rec = nullptr;
     w->xres.agree = nullptr; d.agree = nullptr; d.n_ranks = 0;
     if (!w->sweep_err_host) {  // the word device code reports a wait that gave up in (resident launches, direct halo waits)

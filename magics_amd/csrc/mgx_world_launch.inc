@@ -255,7 +255,7 @@ static bool resident_gate(const mgx_world *w, const std::vector<Launch> &plan) {
     if (!resident_enabled() || w->resident_off || plan.size() < 2) return false;
     if (w->resident_backoff > 0) return false;  // a recent launch found the GPU shared (residency census): launch by launch for a while
     const DevWorld &d = w->d;
-    const bool sharded = w->xres.connected;  // the ranks have agreed (mgx_halo_resident_connect) that ghost records travel inside the launches
+    const bool sharded = w->xres.connected;  // the ranks have agreed (mgx_halo_resident_connect_peers) that ghost records travel inside the launches
     if ((d.R_total != d.R_local && !sharded) || !(w->p.enable_mask & 2u)) return false;
     if (((w->direct.connected || w->rccl.connected) && !sharded)) return false;
     for (const Launch &l : plan)
@@ -534,7 +534,7 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
         sp.flag_base = w->flag_base;
         sp.timeout_ticks = timeout_ticks;
         // residency census + clean abort (SegPlan); the ranks of a sharded world abort together, on the word they agree on
-        // (without one — mgx_halo_resident_connect without a coordinator — they keep the plain bound on every wait)
+        // (without one — mgx_halo_resident_connect_peers without a coordinator — they keep the plain bound on every wait)
         static const long long census_ticks = [] {
             const char *e = getenv("MGX_RESIDENT_CENSUS_US");
             const long long us = e ? atoll(e) : 200;

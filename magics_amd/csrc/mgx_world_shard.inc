@@ -299,17 +299,16 @@ static int halo_commit(mgx_world *w) {
 
 }  // extern "C" (helpers below have C++ linkage)
 
-// A slot-wired exchange (mgx_halo_direct_setup_slots) is only as good as its last aim: the push walks dst[] by the send list's
-// length and the wait indexes the receive area by ghost number, so lists or a layout newer than the aim — or more ghosts than
-// slots — are an error here, not a store to wherever the old tables point.
-static int direct_slots_ok(mgx_world *w) {
+// The direct exchange is only as good as its last aim: the push walks dst[] by the send list's length and the wait indexes the
+// receive area by ghost number, so lists or a device order newer than the aim — or more ghosts than slots — are an error here,
+// not a store to wherever the old tables point.
+static int direct_aim_ok(mgx_world *w) {
     const mgx_world::DirectHalo &dh = w->direct;
-    if (!dh.by_slot) return MGX_OK;
     const size_t NG = (size_t)(w->d.R_total - w->d.R_local);
     if (NG > dh.slot_cap)
         return fail(MGX_ERR_STATE, "%zu ghost robots but the direct exchange was wired with %zu slots: wire it again (mgx_halo_direct_setup_slots)", NG, dh.slot_cap);
     if (!dh.aimed)
-        return fail(MGX_ERR_STATE, "the exchange lists or the device layout changed since the direct exchange was aimed: "
+        return fail(MGX_ERR_STATE, "the exchange lists or the robots' device order changed since the direct exchange was aimed: "
                                    "mgx_halo_direct_connect_slots again (robots joined: mgx_halo_direct_setup_slots on every rank first)");
     return MGX_OK;
 }
@@ -319,25 +318,25 @@ static int direct_push(mgx_world *w) {
     int rc = halo_commit(w);
     if (rc != MGX_OK) return rc;
     mgx_world::DirectHalo &dh = w->direct;
-    if ((rc = direct_slots_ok(w)) != MGX_OK) return rc;
+    if ((rc = direct_aim_ok(w)) != MGX_OK) return rc;
     if (dh.push_seq != dh.seq) return fail(MGX_ERR_STATE, "exchange %llu is already pushed and not yet waited for", dh.push_seq);
     dh.push_seq += 1;
     const int par = (int)(dh.push_seq & 1ull);
     HIP_TRY(launch_halo_push(w->d, (int)w->halo_send.size(), w->halo_send_dev.p, dh.dst[par].p, dh.n_peers, dh.peer_flags.p, dh.push_seq,
-                             dh.done.p, w->stream, dh.by_slot));
+                             dh.done.p, w->stream));
     return MGX_OK;
 }
 static int direct_wait(mgx_world *w) {
     int rc = halo_commit(w);
     if (rc != MGX_OK) return rc;
     mgx_world::DirectHalo &dh = w->direct;
-    if ((rc = direct_slots_ok(w)) != MGX_OK) return rc;
+    if ((rc = direct_aim_ok(w)) != MGX_OK) return rc;
     if (dh.push_seq != dh.seq + 1) return fail(MGX_ERR_STATE, "nothing pushed for exchange %llu", dh.seq + 1);
     dh.seq += 1;
     const int par = (int)(dh.seq & 1ull);
     HIP_TRY(launch_halo_wait_unpack(w->d, (int)w->halo_recv.size(), w->halo_recv_dev.p, dh.recv + (size_t)par * dh.recv_words,
                                     dh.n_sources, dh.flags, dh.seq, dh.flags + dh.n_sources, dh.timeout_ticks, dh.ready.p, w->d.sweep_err,
-                                    w->stream, dh.by_slot));
+                                    w->stream));
     return MGX_OK;
 }
 static int direct_exchange(mgx_world *w) {
@@ -415,19 +414,25 @@ int mgx_halo_rccl_disconnect(mgx_world *w) {
 }
 
 // ---- direct halo exchange (peer-mapped stores, SURVEY §8e) ---------------------------------------------
-int mgx_halo_direct_setup(mgx_world *w, uint32_t n_sources, void **recv_base, void **flag_base) {
+// The exchange is wired ONCE (include/mgx.h) and outlives changes of the exchange lists: the receive area holds `slot_capacity` record
+// slots per parity, slot g = the g-th ghost robot of this rank in device order (mgx_halo_ghost_slots); its `n_sources` producers are
+// the ranks it shares a boundary with (fixed lists) or every other rank (a world that follows its topology) — with or without
+// records in a given exchange.
+int mgx_halo_direct_setup_slots(mgx_world *w, uint32_t n_sources, uint32_t slot_capacity, void **recv_base, void **flag_base) {
     MGX_ENTER(w);
     if (!w || !recv_base || !flag_base) return fail(MGX_ERR_INVALID, "null argument");
     int rc = halo_commit(w);
     if (rc != MGX_OK) return rc;
+    const size_t NG = (size_t)(w->d.R_total - w->d.R_local);
+    if ((size_t)slot_capacity < NG) return fail(MGX_ERR_INVALID, "%u slots for %zu ghost robots", slot_capacity, NG);
     mgx_world::DirectHalo &dh = w->direct;
     HIP_TRY(hipStreamSynchronize(w->stream));
     dh.connected = false;
-    dh.by_slot = false;
-    dh.aimed = false;
     if (dh.recv) { (void)hipFree(dh.recv); dh.recv = nullptr; }
     if (dh.flags) { (void)hipFree(dh.flags); dh.flags = nullptr; }
-    dh.recv_words = w->halo_recv.size() * (size_t)mgx_halo_words((uint32_t)w->K);
+    dh.aimed = false;
+    dh.slot_cap = slot_capacity;
+    dh.recv_words = (size_t)slot_capacity * (size_t)mgx_halo_words((uint32_t)w->K);
     dh.n_sources = (int)n_sources;
     const size_t rb = std::max<size_t>(2 * dh.recv_words, 1) * sizeof(double), fb = ((size_t)n_sources + 1) * sizeof(unsigned long long);
     // fine-grained: coherent with stores arriving from other GPUs / processes while kernels run
@@ -441,86 +446,6 @@ int mgx_halo_direct_setup(mgx_world *w, uint32_t n_sources, void **recv_base, vo
     }
     HIP_TRY(hipStreamSynchronize(w->stream));
     if (w->sweep_err_host) *w->sweep_err_host = 0ull;  // a freshly wired exchange starts clean
-    dh.seq = dh.push_seq = 0;
-    if (const char *ms = getenv("MGX_HALO_TIMEOUT_MS")) {
-        const long long v = atoll(ms);
-        if (v > 0) dh.timeout_ticks = v * 100000ll;
-    }
-    *recv_base = dh.recv;
-    *flag_base = dh.flags;
-    return MGX_OK;
-}
-
-int mgx_halo_direct_connect(mgx_world *w, uint32_t n_peers, const uint32_t *send_first, void *const *peer_recv_base,
-                            const uint64_t *peer_recv_records, const uint64_t *peer_record_offset, void *const *peer_flag_slot) {
-    MGX_ENTER(w);
-    if (!w) return fail(MGX_ERR_INVALID, "null world");
-    mgx_world::DirectHalo &dh = w->direct;
-    if (!dh.flags) return fail(MGX_ERR_STATE, "mgx_halo_direct_setup first");
-    if (n_peers && (!send_first || !peer_recv_base || !peer_recv_records || !peer_record_offset || !peer_flag_slot))
-        return fail(MGX_ERR_INVALID, "null argument");
-    if ((int)n_peers != dh.n_sources)
-        return fail(MGX_ERR_INVALID, "%u consumers but %d producers: the exchange must be symmetric (every peer both sends and receives)",
-                    n_peers, dh.n_sources);
-    const size_t n_send = w->halo_send.size(), words = (size_t)mgx_halo_words((uint32_t)w->K);
-    if (n_peers && (send_first[0] != 0 || send_first[n_peers] != n_send)) return fail(MGX_ERR_INVALID, "send_first does not cover the send list");
-    std::vector<unsigned long long> d0(std::max<size_t>(n_send, 1), 0ull), d1(std::max<size_t>(n_send, 1), 0ull), pf(std::max<size_t>(n_peers, 1), 0ull);
-    for (uint32_t p = 0; p < n_peers; p++) {
-        if (send_first[p + 1] <= send_first[p]) return fail(MGX_ERR_INVALID, "peer %u receives nothing", p);
-        if (!peer_recv_base[p] || !peer_flag_slot[p]) return fail(MGX_ERR_INVALID, "peer %u: null address", p);
-        const uint64_t cnt = send_first[p + 1] - send_first[p];
-        if (peer_record_offset[p] + cnt > peer_recv_records[p]) return fail(MGX_ERR_INVALID, "peer %u: segment exceeds its receive area", p);
-        for (uint32_t i = send_first[p]; i < send_first[p + 1]; i++) {
-            const unsigned long long base = (unsigned long long)(uintptr_t)peer_recv_base[p];
-            const unsigned long long rec = peer_record_offset[p] + (i - send_first[p]);
-            d0[i] = base + (0ull * peer_recv_records[p] + rec) * words * sizeof(double);
-            d1[i] = base + (1ull * peer_recv_records[p] + rec) * words * sizeof(double);
-        }
-        pf[p] = (unsigned long long)(uintptr_t)peer_flag_slot[p];
-    }
-    std::vector<unsigned int> zero(1, 0u);
-    HIP_TRY(dh.dst[0].upload(d0, w->stream));
-    HIP_TRY(dh.dst[1].upload(d1, w->stream));
-    HIP_TRY(dh.peer_flags.upload(pf, w->stream));
-    HIP_TRY(dh.done.upload(zero, w->stream));
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    dh.n_peers = (int)n_peers;
-    dh.seq = dh.push_seq = 0;
-    dh.connected = true;
-    return MGX_OK;
-}
-
-// The same exchange wired ONCE for a world whose exchange lists change (worlds that follow their topology, include/mgx.h): the
-// receive area holds `slot_capacity` record slots per parity, slot g = the g-th ghost robot of this rank in device order
-// (mgx_halo_ghost_slots), and EVERY other rank is a source — with or without records in a given exchange.
-int mgx_halo_direct_setup_slots(mgx_world *w, uint32_t n_sources, uint32_t slot_capacity, void **recv_base, void **flag_base) {
-    MGX_ENTER(w);
-    if (!w || !recv_base || !flag_base) return fail(MGX_ERR_INVALID, "null argument");
-    int rc = halo_commit(w);
-    if (rc != MGX_OK) return rc;
-    const size_t NG = (size_t)(w->d.R_total - w->d.R_local);
-    if ((size_t)slot_capacity < NG) return fail(MGX_ERR_INVALID, "%u slots for %zu ghost robots", slot_capacity, NG);
-    mgx_world::DirectHalo &dh = w->direct;
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    dh.connected = false;
-    if (dh.recv) { (void)hipFree(dh.recv); dh.recv = nullptr; }
-    if (dh.flags) { (void)hipFree(dh.flags); dh.flags = nullptr; }
-    dh.by_slot = true;
-    dh.aimed = false;
-    dh.slot_cap = slot_capacity;
-    dh.recv_words = (size_t)slot_capacity * (size_t)mgx_halo_words((uint32_t)w->K);
-    dh.n_sources = (int)n_sources;
-    const size_t rb = std::max<size_t>(2 * dh.recv_words, 1) * sizeof(double), fb = ((size_t)n_sources + 1) * sizeof(unsigned long long);
-    HIP_TRY(hipExtMallocWithFlags((void **)&dh.recv, rb, hipDeviceMallocFinegrained));
-    HIP_TRY(hipExtMallocWithFlags((void **)&dh.flags, fb, hipDeviceMallocFinegrained));
-    HIP_TRY(hipMemsetAsync(dh.recv, 0, rb, w->stream));
-    HIP_TRY(hipMemsetAsync(dh.flags, 0, fb, w->stream));
-    {
-        std::vector<unsigned long long> z(1, 0ull);
-        HIP_TRY(dh.ready.upload(z, w->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    if (w->sweep_err_host) *w->sweep_err_host = 0ull;
     dh.seq = dh.push_seq = 0;
     if (const char *ms = getenv("MGX_HALO_TIMEOUT_MS")) {
         const long long v = atoll(ms);
@@ -546,16 +471,18 @@ int mgx_halo_ghost_slots(mgx_world *w, uint32_t n, const int32_t *robots, int32_
 }
 
 // (Re)aim the pushes after the exchange lists changed (mgx_halo_plan / mgx_halo_plan_from_connections): peers in the order of the
-// send list's segments — every other rank, an empty segment for a rank that takes nothing now — and for every entry of the send
-// list the slot of that robot in its consumer's area.  The exchange numbers go on: both ends keep counting.
+// send list's segments — an empty segment for a peer that takes nothing now — and for every entry of the send list the slot of
+// that robot in its consumer's area.  The exchange numbers go on: both ends keep counting.
 int mgx_halo_direct_connect_slots(mgx_world *w, uint32_t n_peers, const uint32_t *send_first, void *const *peer_recv_base,
                                   const uint64_t *peer_slot_capacity, const uint32_t *entry_slot, void *const *peer_flag_slot) {
     MGX_ENTER(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     mgx_world::DirectHalo &dh = w->direct;
-    if (!dh.flags || !dh.by_slot) return fail(MGX_ERR_STATE, "mgx_halo_direct_setup_slots first");
+    if (!dh.flags) return fail(MGX_ERR_STATE, "mgx_halo_direct_setup_slots first");
     if (n_peers && (!send_first || !peer_recv_base || !peer_slot_capacity || !peer_flag_slot)) return fail(MGX_ERR_INVALID, "null argument");
-    if ((int)n_peers != dh.n_sources) return fail(MGX_ERR_INVALID, "%u consumers but %d producers: every other rank is both", n_peers, dh.n_sources);
+    if ((int)n_peers != dh.n_sources)
+        return fail(MGX_ERR_INVALID, "%u consumers but %d producers: the exchange must be symmetric (every peer both sends and receives)",
+                    n_peers, dh.n_sources);
     int rc = halo_commit(w);
     if (rc != MGX_OK) return rc;
     const size_t n_send = w->halo_send.size(), words = (size_t)mgx_halo_words((uint32_t)w->K);
@@ -691,67 +618,14 @@ int mgx_halo_resident_setup(mgx_world *w, void **area_base, uint32_t *n_ghost_sl
     return MGX_OK;
 }
 
-int mgx_halo_resident_connect(mgx_world *w, uint32_t n_targets, const int32_t *robots, void *const *peer_area_base,
-                              const uint32_t *peer_ghost_slots, const uint32_t *peer_slot, const uint32_t *peer_parity,
-                              const uint64_t *peer_segment_count, void *coordinator_area, uint32_t n_ranks) {
-    MGX_ENTER(w);
-    if (!w) return fail(MGX_ERR_INVALID, "null world");
-    if (n_ranks > 0x3fffu) return fail(MGX_ERR_INVALID, "at most %u ranks", 0x3fffu);  // (the agreement word counts them in 14 bits)
-    if (n_targets && (!robots || !peer_area_base || !peer_ghost_slots || !peer_slot || !peer_parity || !peer_segment_count))
-        return fail(MGX_ERR_INVALID, "null argument");
-    mgx_world::ResidentHalo &xr = w->xres;
-    if (!xr.area) return fail(MGX_ERR_STATE, "mgx_halo_resident_setup first");
-    if (!w->dev_valid || w->dirty) return fail(MGX_ERR_STATE, "the world's layout changed since mgx_halo_resident_setup");
-    DevWorld &d = w->d;
-    const size_t R = (size_t)d.R_local, K = (size_t)w->K;
-    std::vector<std::pair<int, XPushRec>> recs;
-    recs.reserve(n_targets);
-    for (uint32_t t = 0; t < n_targets; t++) {
-        if (robots[t] < 0 || (size_t)robots[t] >= w->robots.size() || w->robots[(size_t)robots[t]].ghost)
-            return fail(MGX_ERR_INVALID, "target %u: robot %d is not a local robot", t, robots[t]);
-        if (!peer_area_base[t] || peer_slot[t] >= peer_ghost_slots[t] || peer_parity[t] > 1u)
-            return fail(MGX_ERR_INVALID, "target %u: bad area / slot / parity", t);
-        const GhostAreaLayout L((size_t)peer_ghost_slots[t], K);
-        const unsigned long long base = (unsigned long long)(uintptr_t)peer_area_base[t];
-        const unsigned x = ((unsigned)d.cur ^ peer_parity[t]) & 1u;  // this rank's parity p is the consumer's p ^ x (both flip together)
-        XPushRec r;
-        for (unsigned p = 0; p < 2; p++) r.xrec[p] = base + L.xrec[p ^ x] + (size_t)peer_slot[t] * K * (size_t)XREC_BYTES;
-        r.flag = base + L.flag + (size_t)peer_slot[t] * sizeof(unsigned long long);
-        r.flag_delta = peer_segment_count[t] - w->flag_base;  // modulo 2^64
-        recs.emplace_back(w->dev_of[(size_t)robots[t]], r);
-    }
-    std::stable_sort(recs.begin(), recs.end(), [](const std::pair<int, XPushRec> &a, const std::pair<int, XPushRec> &b) { return a.first < b.first; });
-    std::vector<int32_t> ptr(R + 1, 0);
-    std::vector<XPushRec> flat(std::max<size_t>(recs.size(), 1));
-    for (size_t i = 0; i < recs.size(); i++) { ptr[(size_t)recs[i].first + 1]++; flat[i] = recs[i].second; }
-    for (size_t r = 0; r < R; r++) ptr[r + 1] += ptr[r];
-    HIP_TRY(xr.xp_ptr.upload(ptr, w->stream));
-    HIP_TRY(xr.xp_rec.upload(flat, w->stream));
-    HIP_TRY(hipStreamSynchronize(w->stream));
-    const GhostAreaLayout Lm((size_t)xr.n_ghosts, K);
-    for (int p = 0; p < 2; p++) d.gxrec[p] = (const unsigned char *)xr.area + Lm.xrec[p];
-    d.gflag = (const unsigned long long *)((const char *)xr.area + Lm.flag);
-    d.xp_ptr = xr.xp_ptr.p;
-    d.xp_rec = xr.xp_rec.p;
-    // the ranks' agreement word: first word of rank 0's area (zeroed by its setup; schedules are numbered from 1 on every rank)
-    xr.agree = coordinator_area && n_ranks >= 2 ? (unsigned long long *)((char *)coordinator_area + GhostAreaLayout::agree) : nullptr;
-    xr.n_ranks = xr.agree ? (int)n_ranks : 0;
-    xr.agree_seq = 0;
-    d.agree = xr.agree;
-    d.n_ranks = xr.n_ranks;
-    xr.connected = true;
-    xr.wired = true;
-    return MGX_OK;
-}
-
-// The same wiring for a world whose exchange lists change (one that follows its topology): the peers ONCE — every other rank's
-// ghost area, its number of ghost slots, its buffer parity and segment count as ITS setup returned them — and, after every change of
-// the lists, which local robot's records go into which slot of which peer (mgx_halo_resident_aim).
+// The wiring outlives the exchange lists: the peers ONCE — every peer's ghost area, its number of ghost slots, its buffer parity and
+// segment count as ITS setup returned them — and, after every change of the lists, which local robot's records go into which slot
+// of which peer (mgx_halo_resident_aim).
 int mgx_halo_resident_connect_peers(mgx_world *w, uint32_t n_peers, void *const *peer_area_base, const uint32_t *peer_ghost_slots,
                                     const uint32_t *peer_parity, const uint64_t *peer_segment_count, void *coordinator_area, uint32_t n_ranks) {
     MGX_ENTER(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    if (n_ranks > 0x3fffu) return fail(MGX_ERR_INVALID, "at most %u ranks", 0x3fffu);
+    if (n_ranks > 0x3fffu) return fail(MGX_ERR_INVALID, "at most %u ranks", 0x3fffu);  // (the agreement word counts them in 14 bits)
     if (n_peers && (!peer_area_base || !peer_ghost_slots || !peer_parity || !peer_segment_count)) return fail(MGX_ERR_INVALID, "null argument");
     mgx_world::ResidentHalo &xr = w->xres;
     if (!xr.area) return fail(MGX_ERR_STATE, "mgx_halo_resident_setup first");

@@ -57,11 +57,10 @@ hipError_t launch_var_tables(int R, int K, const int32_t *in_ptr, const int32_t 
                              hipStream_t stream);
 hipError_t launch_edge_gates(int n, const IrEdgeRec *recs, const uint8_t *antenna, const uint8_t *idle, uint8_t *gate, hipStream_t stream);
 hipError_t launch_halo_push(const DevWorld &w, int n, const int32_t *robots, const unsigned long long *dst, int n_peers,
-                            const unsigned long long *peer_flags, unsigned long long seq, unsigned int *done, hipStream_t stream, bool always);
+                            const unsigned long long *peer_flags, unsigned long long seq, unsigned int *done, hipStream_t stream);
 hipError_t launch_halo_wait_unpack(const DevWorld &w, int n, const int32_t *ghosts, const double *recv, int n_sources,
                                    const unsigned long long *flags, unsigned long long seq, unsigned long long *err,
-                                   long long timeout_ticks, unsigned long long *ready, unsigned long long *host_err, hipStream_t stream,
-                                   bool by_slot);
+                                   long long timeout_ticks, unsigned long long *ready, unsigned long long *host_err, hipStream_t stream);
 // mgx_topology.hip
 int env_red_plane(const mgx_env_desc *d, uint32_t resolution, float expansion, float blur_percent, bool with_blur, hipStream_t s,
                   std::vector<uint8_t> &red, uint32_t &W, uint32_t &H);  // mgx_env.hip
@@ -647,13 +646,12 @@ struct mgx_world {
         int n_sources = 0, n_peers = 0;
         bool connected = false;
         // a wiring that survives changes of the exchange lists (mgx_halo_direct_setup_slots): one record slot per ghost robot —
-        // slot = the robot's place among this rank's ghosts — instead of one per entry of the receive list
-        bool by_slot = false;
+        // slot = the robot's place among this rank's ghosts
         size_t slot_cap = 0;
         // ... whose push destinations (dst[], one per entry of the send list, in the consumers' slot numbering) are only as good as
-        // the lists and the device layout they were made for: any change of either (mgx_halo_plan*, a robot added or released)
-        // takes the aim away until mgx_halo_direct_connect_slots has run again — an exchange in between is refused, not run
-        // against tables of another length
+        // the lists and the robots' device order they were made for: any change of either (mgx_halo_plan*, a robot added, imported
+        // or released) takes the aim away until mgx_halo_direct_connect_slots has run again — an exchange in between is refused,
+        // not run against tables of another length
         bool aimed = false;
         unsigned long long seq = 0, push_seq = 0;  // exchanges waited for / pushed
         long long timeout_ticks = 500000000ll;  // 5 s of the 100 MHz wall clock

@@ -150,8 +150,6 @@ SYMBOLS = {
     "mgx_rccl_unique_id": (C.c_int, [C.c_char_p]),
     "mgx_halo_rccl_connect": (C.c_int, [_V, C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_halo_rccl_disconnect": (C.c_int, [_V]),
-    "mgx_halo_direct_setup": (C.c_int, [_V, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
-    "mgx_halo_direct_connect": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_halo_direct_exchange": (C.c_int, [_V, C.c_uint32]),
     "mgx_halo_direct_status": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mgx_halo_direct_disconnect": (C.c_int, [_V]),
@@ -164,8 +162,6 @@ SYMBOLS = {
     "mgx_halo_direct_connect_slots": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_halo_resident_setup": (C.c_int, [_V, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                           C.c_void_p, C.POINTER(C.c_int32)]),
-    "mgx_halo_resident_connect": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p, C.c_uint32]),
     "mgx_resident_outcome": (C.c_int, [_V, C.POINTER(C.c_int32)]),
     "mgx_resident_ready": (C.c_int, [_V, C.c_char_p, C.c_uint32, C.POINTER(C.c_int32)]),
     "mgx_resident_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),

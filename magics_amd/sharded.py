@@ -96,6 +96,16 @@ class ShardedWorld:
         self.dynamic = dynamic
         self.world = world_factory(sc["params"])
         w = self.world
+        # the in-engine transports (sharded.connect).  Peers of the direct exchange: the ranks this one shares a boundary with on
+        # fixed lists (those it sends to are those it receives from), every other rank on a world whose lists change
+        self.direct = self.rccl = self.resident = False
+        self.transport = "collective" if plan.world_size > 1 else "none"  # sharded.connect() moves it to an in-engine one
+        self.peers = [q for q in range(plan.world_size) if q != plan.rank and (dynamic or plan.send_lists[q])]
+        self._slot_wiring = self._res_wiring = None  # {peer: where this rank's records go there} while wired
+        self._opened, self._opened_areas = [], []  # the peers' areas as mapped here (hipIpc)
+        self._send_counts_robots = [0] * plan.world_size
+        self._next_key = 0
+        self._thaw_watch = False
         if dynamic:
             self._init_dynamic(sc, tensor_factory)
             return
@@ -130,9 +140,6 @@ class ShardedWorld:
         make = tensor_factory or _torch_tensor_factory
         self.send_buf = make(max(1, sum(self.send_counts)))
         self.recv_buf = make(max(1, sum(self.recv_counts)))
-
-        self.direct = False
-        self.transport = "collective" if plan.world_size > 1 else "none"  # sharded.connect() moves it to an in-engine one
         self.late_pending = bool(sc.get("ir_late"))
         if self.late_pending and (comm is not None or plan.world_size == 1):
             self.connect_late()  # (the ranks of a LocalCluster are ticked and connected by the cluster, in lockstep)
@@ -177,8 +184,6 @@ class ShardedWorld:
         self._make = tensor_factory or _torch_tensor_factory
         self.send_buf = self.recv_buf = None
         self.send_counts = self.recv_counts = [0] * plan.world_size
-        self.direct = False
-        self.transport = "collective" if plan.world_size > 1 else "none"  # sharded.connect() moves it to an in-engine one
         self.replan()
 
     def add_robot(self, mean0, prior_diag, dt, radius, path=None, owner=None, order_key=None):
@@ -191,7 +196,7 @@ class ShardedWorld:
         owner = g % plan.world_size if owner is None else int(owner)
         local = owner == plan.rank
         # order key: above every key the scenario handed out (they need not be 0 .. n-1), the same on every rank
-        self._next_key = max(getattr(self, "_next_key", 0), max((rb["order_key"] for rb in self.sc["robots"]), default=-1) + 1, g)
+        self._next_key = max(self._next_key, max((rb["order_key"] for rb in self.sc["robots"]), default=-1) + 1, g)
         if order_key is None:
             key, self._next_key = self._next_key, self._next_key + 1
         else:
@@ -204,12 +209,12 @@ class ShardedWorld:
         plan.K = np.asarray(mean0).shape[0]
         self.lid[g] = g
         self.replan()
-        if getattr(self, "_slot_wiring", None) is not None and self.comm is not None:
+        if self._slot_wiring is not None and self.comm is not None:
             # A multi-process world whose exchange lives in the engines: the robot needs a slot in every other rank's receive
             # (and ghost) area and the push tables name the old lists and device indices — the engine refuses an exchange until
             # mgx_halo_direct_connect_slots has run again.  Collective, like the call itself: nobody may still be pushing into an
             # area that is about to be closed.  (The ranks of a LocalCluster are wired again by the cluster.)
-            resident = bool(getattr(self, "resident", False))
+            resident = self.resident
             self.synchronize()
             self.comm.barrier()
             self.direct_close()
@@ -236,7 +241,6 @@ class ShardedWorld:
         for g, _, b in moves:
             plan.owner[g] = b
         plan.local = [int(g) for g in np.nonzero(plan.owner == plan.rank)[0]]  # (device order of the locals: by id)
-        self._slot_wiring = self._res_wiring = None  # device indices changed: whatever was wired names the old ones
         self.replan()
 
     def migrate(self, new_owner):
@@ -253,7 +257,7 @@ class ShardedWorld:
         moves = [(int(g), int(plan.owner[g]), int(new_owner[g])) for g in np.nonzero(new_owner != plan.owner)[0]]
         if not moves:
             return 0
-        in_engine, resident = self.direct and comm is not None, bool(getattr(self, "resident", False))
+        in_engine, resident = self.direct and comm is not None, self.resident
         if in_engine:
             self.synchronize()
             comm.barrier()  # nobody may still be pushing into an area that is about to be closed
@@ -275,10 +279,10 @@ class ShardedWorld:
         sc_, rc_ = self.world.halo_plan_from_connections(plan.owner, plan.rank, plan.world_size)
         self.send_counts, self.recv_counts = [c * words for c in sc_], [c * words for c in rc_]
         self._send_counts_robots = [int(c) for c in sc_]
-        if getattr(self, "_slot_wiring", None) is not None:
+        if self._slot_wiring is not None:
             if len(plan.owner) == self._slot_robots:
-                self._aim_slots()  # the exchange lives in the engine: only the pushes' destinations follow the lists
-                if getattr(self, "_res_wiring", None) is not None:
+                self._aim_direct()  # the exchange lives in the engine: only the pushes' destinations follow the lists
+                if self._res_wiring is not None:
                     self._aim_resident()
             # robots joined: the areas are wired again by whoever drives the ranks (add_robot over a communicator, LocalCluster);
             # until then the engine refuses every exchange over the old tables (MGX_ERR_STATE), it does not run them
@@ -295,11 +299,11 @@ class ShardedWorld:
         assert self.dynamic
         out = self.world.update_topology(positions_all, radius, next_number, method=method)
         if out[1] or out[2]:
-            if getattr(self, "_res_wiring", None) is not None and self.comm is not None:
+            if self._res_wiring is not None and self.comm is not None:
                 self.world.synchronize()  # (mgx_halo_resident_aim: with every rank's launches through)
                 self.comm.barrier()
             self.replan()
-            if getattr(self, "_res_wiring", None) is not None and self.comm is not None:
+            if self._res_wiring is not None and self.comm is not None:
                 self.comm.barrier()
             if self.comm is not None:
                 if self.direct:
@@ -357,17 +361,34 @@ class ShardedWorld:
             return None
         return self.world.message_counts(self.lid[robot])
 
-    # -- direct exchange wiring ----------------------------------------------------------------------
-    def direct_setup(self, export_ipc):
-        """Allocate this rank's receive area; returns what the peers need to know about it."""
-        plan, ws = self.plan, self.plan.world_size
-        sources = [p for p in range(ws) if plan.recv_lists[p]]
-        recv, flags = self.world.halo_direct_setup(len(sources))
-        offsets, acc = [], 0
-        for p in range(ws):
-            offsets.append(acc)
-            acc += len(plan.recv_lists[p])
-        info = dict(rank=plan.rank, n_records=acc, offsets=offsets, slot={p: j for j, p in enumerate(sources)})
+    # -- the in-engine exchange: wired once, re-aimed whenever the exchange lists change --------------------------
+    def _ghost_slots(self):
+        """the slot of every robot (global id) among this rank's ghosts — where its owner stores its records; -1: not a ghost here"""
+        ids = np.fromiter(self.lid, dtype=np.int64, count=len(self.lid))
+        slots = np.full(len(self.plan.owner), -1, dtype=np.int32)
+        slots[ids] = self.world.halo_ghost_slots(np.array([self.lid[int(g)] for g in ids], dtype=np.int32))
+        return slots
+
+    def _send_lists(self):
+        """the send list by consumer rank, in global ids — what the aims walk: the plan's on fixed lists, the engine's as the last
+        replan left them on a world that follows its topology"""
+        if not self.dynamic:
+            return self.plan.send_lists
+        send, out, k = self.world.halo_send_list(), [], 0
+        for c in self._send_counts_robots:
+            out.append(send[k:k + c])
+            k += c
+        return out
+
+    def direct_setup(self, export_ipc, spare=64):
+        """Allocate this rank's receive area — one record slot per ghost robot, + `spare` for robots that join — and an arrival
+        counter per peer; returns what the peers need: where it is, its capacity, the slot of every robot in it and the counter
+        of every peer."""
+        plan = self.plan
+        slots = self._ghost_slots()
+        cap = int((slots >= 0).sum()) + int(spare)
+        recv, flags = self.world.halo_direct_setup_slots(len(self.peers), cap)
+        info = dict(rank=plan.rank, capacity=cap, slots=slots, slot={p: j for j, p in enumerate(self.peers)})
         if export_ipc:
             info["recv_handle"], info["flags_handle"] = hostlib.ipc_export(recv), hostlib.ipc_export(flags)
         else:
@@ -375,53 +396,9 @@ class ShardedWorld:
         return info
 
     def direct_connect(self, infos):
-        """infos[q]: what rank q published in direct_setup (handles are opened here)."""
-        plan, ws = self.plan, self.plan.world_size
-        consumers = [q for q in range(ws) if plan.send_lists[q]]
-        first, base, nrec, off, slot = [0], [], [], [], []
-        self._opened = getattr(self, "_opened", [])
-        for q in consumers:
-            inf = infos[q]
-            if "recv_ptr" in inf:
-                r, f = inf["recv_ptr"], inf["flags_ptr"]
-            else:
-                r, f = hostlib.ipc_open(inf["recv_handle"]), hostlib.ipc_open(inf["flags_handle"])
-                self._opened += [r, f]
-            first.append(first[-1] + len(plan.send_lists[q]))
-            base.append(r)
-            nrec.append(inf["n_records"])
-            off.append(inf["offsets"][plan.rank])
-            slot.append(f + 8 * inf["slot"][plan.rank])
-        self.world.halo_direct_connect(first, base, nrec, off, slot)
-        self.direct = True
-
-    # -- the direct exchange of a world that FOLLOWS ITS TOPOLOGY: wired once, re-aimed when the lists change -----
-    def direct_setup_slots(self, export_ipc, spare=64):
-        """Allocate a receive area with one record slot per ghost robot (every robot another rank owns: they are all ghosts on a
-        world that follows its topology) + `spare` for robots that join; returns what the peers need: where it is, its capacity
-        and the slot of every robot in it."""
-        assert self.dynamic
-        plan, ws = self.plan, self.plan.world_size
-        n = len(plan.owner)
-        slots = self.world.halo_ghost_slots(np.arange(n, dtype=np.int32))
-        cap = int((slots >= 0).sum()) + int(spare)
-        recv, flags = self.world.halo_direct_setup_slots(ws - 1, cap)
-        sources = [p for p in range(ws) if p != plan.rank]
-        info = dict(rank=plan.rank, capacity=cap, slots=slots, slot={p: j for j, p in enumerate(sources)}, n_robots=n)
-        if export_ipc:
-            info["recv_handle"], info["flags_handle"] = hostlib.ipc_export(recv), hostlib.ipc_export(flags)
-        else:
-            info["recv_ptr"], info["flags_ptr"] = recv, flags
-        return info
-
-    def direct_connect_slots(self, infos):
-        """infos[q]: what rank q published in direct_setup_slots (handles are opened here, once)."""
-        plan = self.plan
-        self._opened = getattr(self, "_opened", [])
-        wiring = {}
-        for q in range(plan.world_size):
-            if q == plan.rank:
-                continue
+        """infos[q]: what rank q published in direct_setup (handles are opened here, once); then the pushes are aimed."""
+        plan, wiring = self.plan, {}
+        for q in self.peers:
             inf = infos[q]
             if "recv_ptr" in inf:
                 r, f = inf["recv_ptr"], inf["flags_ptr"]
@@ -429,97 +406,29 @@ class ShardedWorld:
                 r, f = hostlib.ipc_open(inf["recv_handle"]), hostlib.ipc_open(inf["flags_handle"])
                 self._opened += [r, f]
             wiring[q] = dict(recv=r, flag=f + 8 * inf["slot"][plan.rank], capacity=inf["capacity"], slots=np.asarray(inf["slots"]))
-        self._slot_wiring = wiring
-        self._slot_robots = len(plan.owner)
-        self.direct = True
-        self.transport = "direct"
-        self.replan()  # (aims the pushes)
+        self._slot_wiring, self._slot_robots = wiring, len(plan.owner)
+        self.direct, self.transport = True, "direct"
+        self._aim_direct()
 
-    def _aim_slots(self):
-        """send list -> (peer segments, slot of every entry in its consumer's area): after every change of the lists"""
-        plan, wiring = self.plan, self._slot_wiring
-        if len(plan.owner) != self._slot_robots:
-            raise hostlib.MgxError("robots joined since the direct exchange was wired: wire it again (direct_setup_slots / direct_connect_slots)")
-        peers = [q for q in range(plan.world_size) if q != plan.rank]
-        send = self.world.halo_send_list()
+    def _aim_direct(self):
+        """send lists -> (peer segments, slot of every entry in its consumer's area): after every change of the lists"""
+        wiring, lists = self._slot_wiring, self._send_lists()
         first, slot = [0], []
-        k = 0
-        for q, cnt in ((q, self._send_counts_robots[q]) for q in range(plan.world_size)):
-            if q == plan.rank:
-                assert cnt == 0
-                continue
-            for g in send[k:k + cnt]:
-                sl = int(wiring[q]["slots"][g])
-                assert sl >= 0, (g, q)
-                slot.append(sl)
-            k += cnt
-            first.append(k)
-        assert k == len(send)
-        self.world.halo_direct_connect_slots(first, [wiring[q]["recv"] for q in peers], [wiring[q]["capacity"] for q in peers], slot,
-                                             [wiring[q]["flag"] for q in peers])
-
-    def resident_setup_slots(self, export_ipc):
-        """(a world that follows its topology, behind direct_connect_slots) allocate this rank's ghost area — a slot per ghost
-        robot as it is — and say what the peers need: where, how many slots, parity, segment count, every robot's slot."""
-        assert self.dynamic and getattr(self, "_slot_wiring", None) is not None
-        plan = self.plan
-        area, ng, par, seg, _, ok = self.world.halo_resident_setup(self.world.halo_n_recv())
-        self._own_area = area
-        info = dict(rank=plan.rank, n_ghosts=ng, parity=par, segments=seg, eligible=ok,
-                    slots=self.world.halo_ghost_slots(np.arange(len(plan.owner), dtype=np.int32)))
-        if export_ipc:
-            info["area_handle"] = hostlib.ipc_export(area)
-        else:
-            info["area_ptr"] = area
-        return info
-
-    def resident_connect_peers(self, infos, agree=True):
-        """infos[q]: what rank q published in resident_setup_slots.  Every other rank is a peer, once; which records go where
-        follows the lists (_aim_resident, from replan)."""
-        plan = self.plan
-        peers = [q for q in range(plan.world_size) if q != plan.rank]
-        areas = {}
-        for q in set(peers) | {0}:
-            inf = infos[q]
-            if q == plan.rank:
-                areas[q] = self._own_area
-            elif "area_ptr" in inf:
-                areas[q] = inf["area_ptr"]
-            else:
-                areas[q] = hostlib.ipc_open(inf["area_handle"])
-                self._opened_areas = getattr(self, "_opened_areas", []) + [areas[q]]
-        self.world.halo_resident_connect_peers([areas[q] for q in peers], [infos[q]["n_ghosts"] for q in peers],
-                                               [infos[q]["parity"] for q in peers], [infos[q]["segments"] for q in peers],
-                                               coordinator_area=areas[0] if agree else None, n_ranks=plan.world_size if agree else 0)
-        self._res_wiring = {q: (j, np.asarray(infos[q]["slots"])) for j, q in enumerate(peers)}
-        self.resident = True
-        self.transport = "direct+resident"
-        self._aim_resident()
-
-    def _aim_resident(self):
-        """which local robot's exchange records go into which peer's ghost slot: from the send list as it stands"""
-        plan = self.plan
-        send = self.world.halo_send_list()
-        robots, peer, slot, k = [], [], [], 0
-        for q in range(plan.world_size):
-            cnt = self._send_counts_robots[q]
-            if q != plan.rank:
-                j, slots = self._res_wiring[q]
-                for g in send[k:k + cnt]:
-                    robots.append(self.lid[g]); peer.append(j); slot.append(int(slots[g]))
-            k += cnt
-        self.world.halo_resident_aim(robots, peer, slot)
+        for q in self.peers:
+            slot += [int(wiring[q]["slots"][g]) for g in lists[q]]
+            first.append(len(slot))
+        assert min(slot, default=0) >= 0, "a robot of the send list is no ghost of its consumer"
+        self.world.halo_direct_connect_slots(first, [wiring[q]["recv"] for q in self.peers], [wiring[q]["capacity"] for q in self.peers],
+                                             slot, [wiring[q]["flag"] for q in self.peers])
 
     # -- resident schedule launches: ghost records travel INSIDE the launches ---------------------------
     def resident_setup(self, export_ipc):
-        """Allocate this rank's ghost area (after the direct exchange is wired); returns what the peers need to know:
-        where it is, how many ghost slots it has, the slot of every robot this rank receives, this rank's buffer parity
-        and segment count, and whether this rank can run resident launches at all (the ranks go all or none)."""
-        plan = self.plan
-        flat = [g for l in plan.recv_lists for g in l]
-        area, ng, par, seg, slots, ok = self.world.halo_resident_setup(len(flat))
+        """Allocate this rank's ghost area (after the direct exchange is wired) — a slot per ghost robot as it is — and say what
+        the peers need: where, how many slots, parity, segment count, every robot's slot, and whether this rank can run resident
+        launches at all (the ranks go all or none)."""
+        area, ng, par, seg, _, ok = self.world.halo_resident_setup(self.world.halo_n_recv())
         self._own_area = area
-        info = dict(rank=plan.rank, n_ghosts=ng, parity=par, segments=seg, eligible=ok, slots=dict(zip(flat, slots)))
+        info = dict(rank=self.plan.rank, n_ghosts=ng, parity=par, segments=seg, eligible=ok, slots=self._ghost_slots())
         if export_ipc:
             info["area_handle"] = hostlib.ipc_export(area)
         else:
@@ -527,48 +436,46 @@ class ShardedWorld:
         return info
 
     def resident_connect(self, infos, agree=True):
-        """infos[q]: what rank q published in resident_setup (handles are opened here).  Rank 0's area doubles as the place
-        where the ranks agree on every schedule's launches (include/mgx.h: coordinator_area), so every rank maps it."""
-        plan = self.plan
-        self._opened = getattr(self, "_opened", [])
-        mapped = {}
+        """infos[q]: what rank q published in resident_setup (handles are opened here).  Every peer once; which records go where
+        follows the lists (_aim_resident, from replan).  Rank 0's area doubles as the place where the ranks agree on every
+        schedule's launches (include/mgx.h: coordinator_area), so every rank maps it."""
+        plan, areas = self.plan, {}
+        for q in sorted(set(self.peers) | ({0} if agree else set())):
+            if q == plan.rank:
+                areas[q] = self._own_area
+            elif "area_ptr" in infos[q]:
+                areas[q] = infos[q]["area_ptr"]
+            else:
+                areas[q] = hostlib.ipc_open(infos[q]["area_handle"])
+                self._opened_areas.append(areas[q])
+        self.world.halo_resident_connect_peers([areas[q] for q in self.peers], [infos[q]["n_ghosts"] for q in self.peers],
+                                               [infos[q]["parity"] for q in self.peers], [infos[q]["segments"] for q in self.peers],
+                                               coordinator_area=areas[0] if agree else None, n_ranks=plan.world_size if agree else 0)
+        self._res_wiring = {q: (j, np.asarray(infos[q]["slots"])) for j, q in enumerate(self.peers)}
+        self.resident, self.transport = True, "direct+resident"
+        self._aim_resident()
 
-        def area_of(q):
-            if q not in mapped:
-                inf = infos[q]
-                if "area_ptr" in inf:
-                    mapped[q] = inf["area_ptr"]
-                elif q == plan.rank:
-                    mapped[q] = self._own_area
-                else:
-                    mapped[q] = hostlib.ipc_open(inf["area_handle"])
-                    self._opened_areas = getattr(self, "_opened_areas", []) + [mapped[q]]
-            return mapped[q]
-        robots, area, ngs, slot, par, seg = [], [], [], [], [], []
-        for q in range(plan.world_size):
-            if not plan.send_lists[q]:
-                continue
-            inf = infos[q]
-            a = area_of(q)
-            for g in plan.send_lists[q]:
-                robots.append(self.lid[g]); area.append(a); ngs.append(inf["n_ghosts"]); slot.append(inf["slots"][g])
-                par.append(inf["parity"]); seg.append(inf["segments"])
-        self.world.halo_resident_connect(robots, area, ngs, slot, par, seg, coordinator_area=area_of(0) if agree else None,
-                                         n_ranks=plan.world_size if agree else 0)
-        self.resident = True
+    def _aim_resident(self):
+        """which local robot's exchange records go into which peer's ghost slot: from the send lists as they stand"""
+        lists, robots, peer, slot = self._send_lists(), [], [], []
+        for q in self.peers:
+            j, slots = self._res_wiring[q]
+            for g in lists[q]:
+                robots.append(self.lid[g]); peer.append(j); slot.append(int(slots[g]))
+        self.world.halo_resident_aim(robots, peer, slot)
 
     def direct_close(self):
         """Call on every rank, after a barrier: nobody may still be pushing into a closed area."""
-        if getattr(self, "resident", False):
+        if self.resident:
             self.world.halo_resident_disconnect()
             self.resident = False
-        if getattr(self, "rccl", False):
+        if self.rccl:
             self.world.halo_rccl_disconnect()
             self.direct = self.rccl = False
         if self.direct:
             self.world.halo_direct_disconnect()
             self.direct = False
-        for ptr in getattr(self, "_opened", []) + getattr(self, "_opened_areas", []):
+        for ptr in self._opened + self._opened_areas:
             hostlib.ipc_close(ptr)
         self._opened, self._opened_areas = [], []
         self._slot_wiring = self._res_wiring = None
@@ -576,8 +483,8 @@ class ShardedWorld:
     def resident_close(self):
         """The ghost areas only (the direct exchange stays wired).  Call on every rank, after a barrier."""
         self.world.halo_resident_disconnect()
-        self.resident = False
-        for ptr in getattr(self, "_opened_areas", []):
+        self.resident, self._res_wiring = False, None
+        for ptr in self._opened_areas:
             hostlib.ipc_close(ptr)
         self._opened_areas = []
 
@@ -623,7 +530,7 @@ class ShardedWorld:
     # -- World-like interface over global robot ids -------------------------------------------------
     def iterate(self, steps):
         if self.direct or self.plan.world_size == 1:
-            if getattr(self, "_thaw_watch", False):
+            if self._thaw_watch:
                 self._settle_resident()
             self.world.iterate(steps)  # one C call: launches (and exchanges) are sequenced by the engine
             return
@@ -670,7 +577,7 @@ class ShardedWorld:
         next to one that did not would wait for records that never come), and "factors are still thawing" depends on the flags of
         the robots a rank holds.  So after a switch of factor kinds resident launches are off everywhere until NO rank is thawing
         any more (asked over the control plane in front of every schedule while that lasts)."""
-        if not getattr(self, "resident", False):
+        if not self.resident:
             return
         mine = self.world.is_thawing()
         anyone = any(self.comm.all_gather_object(mine)) if self.comm is not None else mine
@@ -699,6 +606,17 @@ def _torch_tensor_factory(n):
     return torch.zeros(n, dtype=torch.float64, device="cuda")
 
 
+def _rccl_connect(sw, uid):
+    """mgx_halo_rccl_connect with the peers and the segments of the send / receive lists that belong to each"""
+    plan = sw.plan
+    peers = [q for q in range(plan.world_size) if plan.send_lists[q] or plan.recv_lists[q]]
+    send_first, recv_first = [0], [0]
+    for q in peers:
+        send_first.append(send_first[-1] + len(plan.send_lists[q]))
+        recv_first.append(recv_first[-1] + len(plan.recv_lists[q]))
+    sw.world.halo_rccl_connect(uid, plan.world_size, plan.rank, peers, send_first, recv_first)
+
+
 def connect_rccl(sw, comm):
     """The all-to-all-v inside the library: grouped ncclSend / ncclRecv enqueued by mgx_iterate itself
     (include/mgx.h).  `comm` is only the control plane that spreads the RCCL unique id."""
@@ -706,20 +624,14 @@ def connect_rccl(sw, comm):
     if plan.world_size == 1:
         return
     uid = hostlib.rccl_unique_id() if plan.rank == 0 else None
-    uid = comm.all_gather_object(uid)[0]
-    peers = [q for q in range(plan.world_size) if plan.send_lists[q] or plan.recv_lists[q]]
-    send_first, recv_first = [0], [0]
-    for q in peers:
-        send_first.append(send_first[-1] + len(plan.send_lists[q]))
-        recv_first.append(recv_first[-1] + len(plan.recv_lists[q]))
-    sw.world.halo_rccl_connect(uid, plan.world_size, plan.rank, peers, send_first, recv_first)
+    _rccl_connect(sw, comm.all_gather_object(uid)[0])
     sw.direct = sw.rccl = True  # same driving mode: the engine exchanges inside its launch sequence
     comm.barrier()
 
 
 def connect_direct(sw, comm):
     """Wire the direct exchange of a multi-process run: one all-gather of the (tiny) area
-    descriptions over the control-plane communicator, then every rank maps its consumers' areas."""
+    descriptions over the control-plane communicator, then every rank maps its peers' areas."""
     if sw.plan.world_size == 1:
         return
     infos = comm.all_gather_object(sw.direct_setup(export_ipc=True))
@@ -727,17 +639,26 @@ def connect_direct(sw, comm):
     comm.barrier()
 
 
+def _resident_eligible(sw, infos):
+    """whether every rank can run resident launches (None: its set-up failed).  Fixed lists want eligible 1 everywhere; a world
+    that follows its topology also takes a rank without inter-robot factors yet (eligible 2): they may come later, and every
+    schedule is decided where the ranks agree."""
+    return all(i is not None and (i["eligible"] == 1 or (sw.dynamic and i["eligible"] == 2)) for i in infos)
+
+
 def _connect_resident(sw, comm, all_ok):
     """On top of a wired direct exchange: the ghost areas for resident schedule launches.  Every rank reports whether it can
-    run them; only if ALL can (and all succeed in mapping their consumers' areas) are they switched on — a rank that ran
+    run them; only if ALL can (and all succeed in mapping their peers' areas) are they switched on — a rank that ran
     resident launches next to one that did not would wait for records that never come."""
     info = None
     try:
+        if sw.dynamic:
+            sw.world.sweep(0, 0, 0)
         info = sw.resident_setup(export_ipc=True)
     except Exception:  # noqa: BLE001
         info = None
     infos = comm.all_gather_object(info)
-    if any(i is None or i["eligible"] != 1 for i in infos):
+    if not _resident_eligible(sw, infos):
         return False
     try:
         sw.resident_connect({i["rank"]: i for i in infos})
@@ -746,39 +667,10 @@ def _connect_resident(sw, comm, all_ok):
         ok = False
     if all_ok(ok):
         comm.barrier()
-        sw.transport = "direct+resident"
         return True
     if ok:
-        sw.world.halo_resident_disconnect()
-        sw.resident = False
-    comm.barrier()
-    return False
-
-
-def _connect_resident_slots(sw, comm, all_ok):
-    """The same for a world that follows its topology (behind direct_connect_slots): every other rank is a peer once, the push
-    tables follow the exchange lists (ShardedWorld._aim_resident).  A rank without inter-robot factors yet is welcome (eligible 2):
-    every schedule is decided where the ranks agree."""
-    info = None
-    try:
-        sw.world.sweep(0, 0, 0)
-        info = sw.resident_setup_slots(export_ipc=True)
-    except Exception:  # noqa: BLE001
-        info = None
-    infos = comm.all_gather_object(info)
-    if any(i is None or i["eligible"] < 1 for i in infos):
-        return False
-    try:
-        sw.resident_connect_peers({i["rank"]: i for i in infos})
-        ok = True
-    except Exception:  # noqa: BLE001
-        ok = False
-    if all_ok(ok):
-        comm.barrier()
-        return True
-    if ok:
-        sw.world.halo_resident_disconnect()
-        sw.resident, sw._res_wiring, sw.transport = False, None, "direct"
+        sw.resident_close()
+    sw.transport = "direct"
     comm.barrier()
     return False
 
@@ -817,67 +709,53 @@ def connect(sw, comm, transport="auto", resident=True):
     for t in order:
         if t == "collective":
             break
-        try:
-            if t == "direct":
-                slots = bool(getattr(sw, "dynamic", False))  # a world that follows its topology: one slot per ghost robot
-                info, err = None, None
-                try:
-                    import os
-                    if os.environ.get("MGX_TEST_FAIL_DIRECT_SETUP_RANK") == str(sw.plan.rank):  # (fault injection for the fallback tests)
-                        raise hostlib.MgxError("injected: this rank cannot set up its receive area")
-                    info = sw.direct_setup_slots(export_ipc=True) if slots else sw.direct_setup(export_ipc=True)
-                except Exception as e:  # noqa: BLE001
-                    err = e
-                infos = comm.all_gather_object(info)
-                if any(i is None for i in infos):
-                    comm.barrier()
-                    sw.direct_close()  # the ranks whose set-up succeeded free their areas (nobody has mapped them yet)
-                    continue
-                try:
-                    if slots:
-                        sw.direct_connect_slots({i["rank"]: i for i in infos})
-                    else:
-                        sw.direct_connect({i["rank"]: i for i in infos})
-                    ok = True
-                except Exception:  # noqa: BLE001
-                    ok = False
-                if all_ok(ok):
-                    comm.barrier()
-                    sw.transport = "direct"
-                    if resident:
-                        (_connect_resident_slots if slots else _connect_resident)(sw, comm, all_ok)
-                    return sw.transport
+        if t == "direct":
+            info = None
+            try:
+                import os
+                if os.environ.get("MGX_TEST_FAIL_DIRECT_SETUP_RANK") == str(sw.plan.rank):  # (fault injection for the fallback tests)
+                    raise hostlib.MgxError("injected: this rank cannot set up its receive area")
+                info = sw.direct_setup(export_ipc=True)
+            except Exception:  # noqa: BLE001
+                info = None
+            infos = comm.all_gather_object(info)
+            if any(i is None for i in infos):
                 comm.barrier()
-                sw.direct_close()
-            else:
+                sw.direct_close()  # the ranks whose set-up succeeded free their areas (nobody has mapped them yet)
+                continue
+            try:
+                sw.direct_connect({i["rank"]: i for i in infos})
+                ok = True
+            except Exception:  # noqa: BLE001
+                ok = False
+            if all_ok(ok):
+                comm.barrier()
+                sw.transport = "direct"
+                if resident:
+                    _connect_resident(sw, comm, all_ok)
+                return sw.transport
+            comm.barrier()
+            sw.direct_close()
+        else:
+            try:
+                uid = hostlib.rccl_unique_id() if sw.plan.rank == 0 else b""
+            except Exception:  # noqa: BLE001
                 uid = None
-                try:
-                    uid = hostlib.rccl_unique_id() if sw.plan.rank == 0 else b""
-                except Exception:  # noqa: BLE001
-                    uid = None
-                uids = comm.all_gather_object(uid)
-                if uids[0] is None:
-                    continue
-                plan = sw.plan
-                peers = [q for q in range(plan.world_size) if plan.send_lists[q] or plan.recv_lists[q]]
-                send_first, recv_first = [0], [0]
-                for q in peers:
-                    send_first.append(send_first[-1] + len(plan.send_lists[q]))
-                    recv_first.append(recv_first[-1] + len(plan.recv_lists[q]))
-                try:
-                    sw.world.halo_rccl_connect(uids[0], plan.world_size, plan.rank, peers, send_first, recv_first)
-                    ok = True
-                except Exception:  # noqa: BLE001
-                    ok = False
-                if all_ok(ok):
-                    sw.direct = sw.rccl = True
-                    comm.barrier()
-                    sw.transport = "rccl"
-                    return sw.transport
-                if ok:
-                    sw.world.halo_rccl_disconnect()
-        except Exception:  # noqa: BLE001
-            raise
+            uids = comm.all_gather_object(uid)
+            if uids[0] is None:
+                continue
+            try:
+                _rccl_connect(sw, uids[0])
+                ok = True
+            except Exception:  # noqa: BLE001
+                ok = False
+            if all_ok(ok):
+                sw.direct = sw.rccl = True
+                comm.barrier()
+                sw.transport = "rccl"
+                return sw.transport
+            if ok:
+                sw.world.halo_rccl_disconnect()
     sw.transport = "collective"
     return sw.transport
 
@@ -925,13 +803,13 @@ class LocalCluster:
         self.ranks = [ShardedWorld(sc, r, world_size, world_factory, comm=None, owner=owner,
                                    tensor_factory=tensor_factory, dynamic=dynamic) for r in range(world_size)]
         self.n_robots, self.K = len(sc["robots"]), sc.get("K")
-        self.resident = False
+        self.direct = self.resident = self._thaw_watch = False
         self.agree = agree
+        self.declined = 0
         if sc.get("ir_late") and not dynamic:
             # robots that iterate on their own before they meet (ShardedWorld.connect_late): the ticks in lockstep over the
             # collective transport, the factors, THEN the in-engine transports are wired (for the exchange lists as they end up)
             from . import scenarios
-            self.direct_slots, self._want_resident = False, False
             tick = scenarios.tick_inputs(sc)
             for _ in range(sc["connect_after_ticks"]):
                 self.tick(steps=sc["steps"], **tick)
@@ -939,51 +817,35 @@ class LocalCluster:
                 self._exchange()
             for sw in self.ranks:
                 sw.connect_late(ticked=True)
-        self.direct_slots = bool(direct and dynamic and world_size > 1)
-        self._want_resident = bool(resident and self.direct_slots)
-        if self.direct_slots:
-            if self.K is not None:
-                self._wire_slots()
-        elif direct and world_size > 1:
-            infos = {sw.plan.rank: sw.direct_setup(export_ipc=False) for sw in self.ranks}
-            for sw in self.ranks:
-                sw.direct_connect(infos)
-            if resident:
-                # resident=True: every rank's workgroups have to be on the device TOGETHER (each rank a stream of its own on
-                # a hardware queue of its own, and all ranks' robots within the device's resident slots)
-                for sw in self.ranks:
-                    sw.world.sweep(0, 0, 0)
-                infos = {sw.plan.rank: sw.resident_setup(export_ipc=False) for sw in self.ranks}
-                if all(i["eligible"] == 1 for i in infos.values()):
-                    for sw in self.ranks:
-                        sw.resident_connect(infos, agree=agree)
-                    self.resident = True
-                    self.agree = agree
+        self.direct = bool(direct and world_size > 1)
+        self._want_resident = bool(resident and self.direct)
+        if self.direct and self.K is not None:
+            self._wire()
 
-    def _wire_slots(self):
-        """the direct exchange of a cluster that follows its topology: one record slot per ghost robot, aimed again by every
-        rank's replan (ShardedWorld.direct_setup_slots / direct_connect_slots); wired again when robots join"""
+    def _wire(self):
+        """the exchange in the engines (ShardedWorld.direct_setup / direct_connect), aimed again by every rank's replan, and the
+        resident launches on top if asked for and every rank can run them; wired again when robots join or change hands"""
         for sw in self.ranks:
             sw.synchronize()
         for sw in self.ranks:
-            if getattr(sw, "resident", False):
-                sw.world.halo_resident_disconnect()
-                sw.resident, sw._res_wiring = False, None
+            sw.direct_close()
         self.resident = False
-        infos = {sw.plan.rank: sw.direct_setup_slots(export_ipc=False) for sw in self.ranks}
+        infos = {sw.plan.rank: sw.direct_setup(export_ipc=False) for sw in self.ranks}
         for sw in self.ranks:
-            sw.direct_connect_slots(infos)
+            sw.direct_connect(infos)
         if self._want_resident:
+            # every rank's workgroups have to be on the device TOGETHER (each rank a stream of its own on a hardware queue of
+            # its own, and all ranks' robots within the device's resident slots)
             for sw in self.ranks:
                 sw.world.sweep(0, 0, 0)
-            infos = {sw.plan.rank: sw.resident_setup_slots(export_ipc=False) for sw in self.ranks}
-            if all(i["eligible"] >= 1 for i in infos.values()):
+            infos = {sw.plan.rank: sw.resident_setup(export_ipc=False) for sw in self.ranks}
+            if _resident_eligible(self.ranks[0], infos.values()):
                 for sw in self.ranks:
-                    sw.resident_connect_peers(infos, agree=self.agree)
+                    sw.resident_connect(infos, agree=self.agree)
                 self.resident = True
 
     def _exchange(self):
-        if self.direct_slots and self.ranks[0].direct:  # in the engines: all pushes before the first wait (one thread drives all ranks)
+        if self.ranks[0].direct:  # in the engines: all pushes before the first wait (one thread drives all ranks)
             for sw in self.ranks:
                 sw.world.halo_direct_exchange(hostlib.HALO_PUSH)
             for sw in self.ranks:
@@ -1008,11 +870,11 @@ class LocalCluster:
 
     def iterate(self, steps):
         segs = segments(steps)
-        if getattr(self, "_thaw_watch", False):
+        if self._thaw_watch:
             self._settle_resident()
         # (a schedule the engines would run launch by launch — too short, inter-robot factors off, backing off after a declined
         # launch — is driven from here, in lockstep: see below)
-        if self.resident and not getattr(self, "_thaw_watch", False) and self.ranks[0].world.resident_ready(steps):
+        if self.resident and not self._thaw_watch and self.ranks[0].world.resident_ready(steps):
             if segs[0][0]:  # a schedule that opens with an external iteration: its exchange, all pushes first
                 for sw in self.ranks:
                     sw.world.halo_direct_exchange(hostlib.HALO_PUSH)
@@ -1028,7 +890,7 @@ class LocalCluster:
             assert all(o == outcomes[0] for o in outcomes), f"the ranks' launches disagree: {outcomes}"
             if outcomes[0] != hostlib.RESIDENT_DECLINED:
                 return
-            self.declined = getattr(self, "declined", 0) + 1
+            self.declined += 1
         for k, (ext, n_int) in enumerate(segs):
             if ext and len(self.ranks) > 1:
                 if self.ranks[0].direct:
@@ -1050,8 +912,8 @@ class LocalCluster:
         ids = [sw.add_robot(mean0, prior_diag, dt, radius, path=path, owner=owner, order_key=order_key) for sw in self.ranks]
         assert all(i == ids[0] for i in ids)
         self.n_robots, self.K = ids[0] + 1, np.asarray(mean0).shape[0]
-        if self.direct_slots:
-            self._wire_slots()  # (a robot more: every rank's area has a slot more, or the robot a slot in the others')
+        if self.direct:
+            self._wire()  # (a robot more: every rank's area has a slot more, or the robot a slot in the others')
         return ids[0]
 
     def migrate(self, new_owner):
@@ -1063,13 +925,14 @@ class LocalCluster:
             return 0
         for sw in self.ranks:
             sw.synchronize()
+            sw.direct_close()  # (device indices change: whatever was wired names the old ones)
         records = {}
         for sw in self.ranks:
             records.update(sw._migrate_out(moves))
         for sw in self.ranks:
             sw._migrate_in(moves, records)
-        if self.direct_slots:
-            self._wire_slots()
+        if self.direct:
+            self._wire()
         return len(moves)
 
     def tick(self, robots, waypoints_xy, time_scale, what, max_speed, delta_t, steps):
@@ -1078,7 +941,7 @@ class LocalCluster:
 
     # -- per-tick calls of a driver, over global robot ids (dynamic clusters) ------------------------------
     def update_topology(self, positions_all, radius, next_number, method=hostlib.NEIGHBOURS_AUTO):
-        if self.resident and self.direct_slots:
+        if self.resident:
             for sw in self.ranks:
                 sw.synchronize()  # (the aims behind a pass that changed the lists: with every rank's launches through)
         outs = [sw.update_topology(positions_all, radius, next_number, method=method) for sw in self.ranks]

@@ -455,21 +455,6 @@ class World:
         self._chk(self._L.mgx_halo_rccl_disconnect(self._w))
 
     # direct halo exchange (peer-mapped stores; see include/mgx.h)
-    def halo_direct_setup(self, n_sources):
-        recv, flags = C.c_void_p(), C.c_void_p()
-        self._chk(self._L.mgx_halo_direct_setup(self._w, n_sources, C.byref(recv), C.byref(flags)))
-        return recv.value, flags.value
-
-    def halo_direct_connect(self, send_first, peer_recv_base, peer_recv_records, peer_record_offset, peer_flag_slot):
-        n = len(peer_recv_base)
-        a = np.ascontiguousarray(send_first, dtype=np.uint32)
-        b = np.ascontiguousarray(peer_recv_base, dtype=np.uint64)
-        c = np.ascontiguousarray(peer_recv_records, dtype=np.uint64)
-        d = np.ascontiguousarray(peer_record_offset, dtype=np.uint64)
-        e = np.ascontiguousarray(peer_flag_slot, dtype=np.uint64)
-        assert a.size == n + 1 and b.size == c.size == d.size == e.size == n
-        self._chk(self._L.mgx_halo_direct_connect(self._w, n, a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, e.ctypes.data))
-
     def halo_direct_setup_slots(self, n_sources, slot_capacity):
         """a receive area with one record slot per ghost robot (a wiring that outlives the exchange lists)"""
         recv, flags = C.c_void_p(), C.c_void_p()
@@ -543,6 +528,7 @@ class World:
         return nr.value
 
     def halo_resident_connect_peers(self, peer_area, peer_ghost_slots, peer_parity, peer_segment_count, coordinator_area=None, n_ranks=0):
+        """coordinator_area: rank 0's ghost area as this rank maps it — where the ranks agree on every schedule's launches"""
         n = len(peer_area)
         b = np.ascontiguousarray(peer_area, dtype=np.uint64)
         c = np.ascontiguousarray(peer_ghost_slots, dtype=np.uint32)
@@ -558,20 +544,6 @@ class World:
         c = np.ascontiguousarray(peer_slot, dtype=np.uint32)
         assert a.size == b.size == c.size
         self._chk(self._L.mgx_halo_resident_aim(self._w, a.size, a.ctypes.data, b.ctypes.data, c.ctypes.data))
-
-    def halo_resident_connect(self, robots, peer_area, peer_ghost_slots, peer_slot, peer_parity, peer_segment_count,
-                              coordinator_area=None, n_ranks=0):
-        """coordinator_area: rank 0's ghost area as this rank maps it — where the ranks agree on every schedule's launches"""
-        n = len(robots)
-        a = np.ascontiguousarray(robots, dtype=np.int32)
-        b = np.ascontiguousarray(peer_area, dtype=np.uint64)
-        c = np.ascontiguousarray(peer_ghost_slots, dtype=np.uint32)
-        d = np.ascontiguousarray(peer_slot, dtype=np.uint32)
-        e = np.ascontiguousarray(peer_parity, dtype=np.uint32)
-        f = np.ascontiguousarray(peer_segment_count, dtype=np.uint64)
-        assert b.size == c.size == d.size == e.size == f.size == n
-        self._chk(self._L.mgx_halo_resident_connect(self._w, n, a.ctypes.data, b.ctypes.data, c.ctypes.data, d.ctypes.data, e.ctypes.data,
-                                                    f.ctypes.data, coordinator_area, int(n_ranks)))
 
     def halo_resident_disconnect(self):
         self._chk(self._L.mgx_halo_resident_disconnect(self._w))

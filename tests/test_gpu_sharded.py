@@ -111,6 +111,29 @@ def test_direct_exchange_gating_and_prior_changes():
     assert_identical(cluster, ref, what="direct exchange, gating + change_prior on boundary robots")
 
 
+def test_direct_exchange_survives_a_relayout():
+    """A relayout that keeps the robots' device order (every rank takes the scenario's obstacle image again between ticks) keeps
+    the pushes of a wired exchange aimed: the run stays the oracle's bit for bit and every exchange is counted."""
+    sc = S.grid_scenario(64, 10, interrobot=True, pitch=2.5, comm_radius=5.0)
+    make, streams = _own_stream_factory()
+    cluster = sharded.LocalCluster(sc, 3, make, direct=True)
+    assert all(sw.direct for sw in cluster.ranks)
+    ref = oracle.OracleWorld(sc["params"])
+    S.populate(ref, sc)
+    steps = sc["steps"] + [1, 1, 2, 3, 2]
+    n_ext = sum(1 for s in steps if s & 2)
+    sdf = sc["sdf"]
+    for tick in range(3):
+        if tick:
+            for sw in cluster.ranks:
+                sw.world.set_sdf(sdf["rgb"], sdf["world_w"], sdf["world_h"])
+        cluster.iterate(steps)
+        ref.iterate(steps)
+        assert_identical(cluster, ref, what=f"direct exchange, relaid out before tick {tick}")
+    for sw in cluster.ranks:
+        assert sw.world.halo_direct_status() == 3 * n_ext
+
+
 def test_direct_exchange_reports_a_missing_peer(monkeypatch):
     """A producer that never shows up must end in a reported timeout, not in a hung GPU."""
     monkeypatch.setenv("MGX_HALO_TIMEOUT_MS", "200")
@@ -563,7 +586,7 @@ def test_resident_sharded_survives_a_missing_rank():
 
 
 def test_resident_sharded_without_agreement_reports_a_missing_rank(monkeypatch):
-    """Wired without a coordinator (mgx_halo_resident_connect: coordinator_area NULL) there is no agreement: a rank whose peer
+    """Wired without a coordinator (mgx_halo_resident_connect_peers: coordinator_area NULL) there is no agreement: a rank whose peer
     never launches gives up after the bound on its waits and the world says so."""
     monkeypatch.setenv("MGX_RESIDENT_TIMEOUT_MS", "300")
     from magics_amd import hostlib

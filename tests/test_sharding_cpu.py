@@ -159,14 +159,21 @@ def test_all_to_all_exchange_gloo_world_size_2():
 
 class DirectFakeWorld(FakeWorld):
     """FakeWorld + a host model of the direct halo exchange (include/mgx.h): every rank's receive
-    area is a numpy array in a shared registry keyed by a fake address; `connect` records where this
-    rank's segments go; `iterate` pushes through those addresses and unpacks from its own area."""
+    area — one record slot per ghost robot, slot = its place among the ghosts in device order — is
+    a numpy array in a shared registry keyed by a fake address; `connect` records where this rank's
+    send-list entries go; `iterate` pushes through those addresses and unpacks from its own area."""
     registry = {}
     next_addr = [1 << 20]
 
-    def halo_direct_setup(self, n_sources):
+    def halo_ghost_slots(self, robots):
+        slot = {r: j for j, r in enumerate(r for r, rb in enumerate(self.robots) if rb["ghost"])}
+        return np.array([slot.get(int(r), -1) for r in robots], dtype=np.int32)
+
+    def halo_direct_setup_slots(self, n_sources, capacity):
+        assert capacity >= sum(rb["ghost"] for rb in self.robots)
         words = self.halo_words(self.K)
-        self.area = np.full((2, max(1, len(self.recv)) * words), -1.0)
+        self.capacity = capacity
+        self.area = np.full((2, max(1, capacity) * words), -1.0)
         self.flags = np.zeros(max(1, n_sources), dtype=np.int64)
         a_recv, a_flag = self.next_addr[0], self.next_addr[0] + (1 << 16)
         self.next_addr[0] += 1 << 17
@@ -176,39 +183,42 @@ class DirectFakeWorld(FakeWorld):
         self.n_sources, self.seq = n_sources, 0
         return a_recv, a_flag
 
-    def halo_direct_connect(self, first, base, nrec, off, slot):
+    def halo_direct_connect_slots(self, first, base, capacity, entry_slot, slot):
         assert len(base) == self.n_sources, "producers and consumers of a rank must be the same peers"
-        assert first[0] == 0 and first[-1] == len(self.send)
+        assert first[0] == 0 and first[-1] == len(self.send) == len(entry_slot)
         self.peers = []
         for p in range(len(base)):
             kind, peer = self.registry[base[p]]
-            assert kind == "area" and nrec[p] == len(peer.recv)
+            assert kind == "area" and capacity[p] == peer.capacity
+            assert all(0 <= e < capacity[p] for e in entry_slot[first[p]:first[p + 1]])
             fk = self.registry[slot[p]]
             assert fk[0] == "flag" and fk[1] is peer
-            self.peers.append((peer, first[p], first[p + 1], off[p], fk[2]))
+            self.peers.append((peer, first[p], first[p + 1], fk[2]))
+        self.entry_slot = list(entry_slot)
 
     def direct_push(self):
         self.seq += 1
         w = self.halo_words(self.K)
-        for peer, lo, hi, off, fslot in self.peers:
-            for k, r in enumerate(self.send[lo:hi]):
+        for peer, lo, hi, fslot in self.peers:
+            for i in range(lo, hi):
+                r, e = self.send[i], self.entry_slot[i]
                 rec = np.full(w, float(self.robots[r]["key"]))
                 rec[1] = self.robots[r]["version"]
-                peer.area[self.seq & 1, (off + k) * w:(off + k + 1) * w] = rec
+                peer.area[self.seq & 1, e * w:(e + 1) * w] = rec
             peer.flags[fslot] = self.seq
 
     def direct_wait_unpack(self):
         assert (self.flags[:self.n_sources] >= self.seq).all(), "a producer has not pushed this exchange"
         w = self.halo_words(self.K)
-        for j, r in enumerate(self.recv):
-            rec = self.area[self.seq & 1, j * w:(j + 1) * w]
+        for r, e in zip(self.recv, self.halo_ghost_slots(self.recv)):
+            rec = self.area[self.seq & 1, e * w:(e + 1) * w]
             assert rec[0] == self.robots[r]["key"], "record landed in the wrong ghost"
             self.robots[r]["version"] = int(rec[1])
 
 
 @pytest.mark.parametrize("world_size", [2, 3, 4])
-def test_direct_exchange_wiring(world_size):
-    """ShardedWorld.direct_setup / direct_connect: segments, offsets and counter slots agree across
+def test_direct_exchange_slot_wiring(world_size):
+    """ShardedWorld.direct_setup / direct_connect: segments, record slots and counter slots agree across
     ranks, so that every ghost receives the snapshot of the right robot at the right version."""
     DirectFakeWorld.registry.clear()
     sc = _scenario()
