@@ -194,6 +194,20 @@ int mgx_batch_end(mgx_world *w, uint32_t *n_schedules, uint32_t *n_launches);
  * neighbours inside it); otherwise one launch per [external iteration] internal* segment.  MGX_PERSISTENT=0 in
  * the environment forces the latter.  Diagnostic (bench.py prices its roofline per launch with it). */
 int mgx_last_launch_count(mgx_world *w, uint32_t *n_launches);
+/* How the last mgx_iterate / mgx_tick call ran its sweeps, as the launcher that enqueued them chose: the horizon variant of the
+ * sweep kernel (K of a constant-K template, 0 / -1 for the run-time-K kernels: K <= 33 / K >= 34), its inter-robot mode
+ * (MGX_SWEEP_IR_*), its form (MGX_SWEEP_FORM_*; -1 with ir_mode -1: the call launched no sweep), and how many workgroups of
+ * this world's resident instantiation the device holds at once (0: the world's shape has no resident form).  A call that ran
+ * several forms (a resident launch the residency census declined, run again launch by launch) reports the last.  Host
+ * bookkeeping only: no synchronisation; any pointer may be NULL. */
+#define MGX_SWEEP_IR_NONE 0      /* no inter-robot factors */
+#define MGX_SWEEP_IR_UNSTAGED 1  /* inter-robot messages read from L2 in every variable sweep (too many edges to stage) */
+#define MGX_SWEEP_IR_STAGED 2    /* inter-robot messages staged in LDS */
+#define MGX_SWEEP_FORM_SEGMENTS 0  /* one launch per [external iteration] internal* segment */
+#define MGX_SWEEP_FORM_RESIDENT 1  /* one resident launch for the schedule */
+#define MGX_SWEEP_FORM_POSTED 2    /* posted into a lingering resident launch */
+#define MGX_SWEEP_FORM_SHARDED 3   /* one resident launch on a sharded world */
+int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *form, int32_t *resident_capacity);
 
 /* LINGERING resident launches — schedules issued back to back ride in ONE launch.  The reference's driver runs iterate_gbp_v2
  * tick after tick (robot.rs:85-108, a .chain() in FixedUpdate) with nothing in between but the two prior updates that mgx_tick

@@ -304,6 +304,12 @@ struct LingerBox {  // host-mapped
     LingerPlan plan[2];            // slot = number & 1; the prior-update records follow the box: double upd[2][4 * R_cap]
 };
 
+// Which instantiation of k_robot_sweep a launcher enqueued (mgx_last_sweep): written by the branch that launched it
+struct SweepRan {
+    int32_t variant = 0;   // KT of the template: a constant horizon, or 0 / -1 for the run-time-K kernels
+    int32_t ir_mode = -1;  // IR_NONE / IR_GLOBAL / IR_STAGED (mgx_sweep.h); -1: nothing launched
+};
+
 struct SegPlan {
     int32_t n;                     // segments in this launch
     uint8_t ext[MAX_SEGS];         // 1: the segment opens with an external iteration (factor + variable sweep)

@@ -652,7 +652,10 @@ size_t sweep_lds_bytes(int K, int ir_edges, bool resident) {  // resident: + the
            4 * (size_t)((resident ? 3 : 2) * ((K + 1) & ~1) + ((3 * (K + 1) + 1) & ~1));
 }
 size_t sweep_lds_bytes(int K, int ir_edges) { return sweep_lds_bytes(K, ir_edges, false); }
-bool sweep_supports(int K) { return K >= 3 && 2 * (K - 1) <= 128; }  // beyond 33 variables: two dynamic messages per lane
+// beyond 33 variables: two dynamic messages per lane.  45 is the documented bound (README.md): the LDS check at
+// commit alone lets K = 46 through (59.5 of its 60 KB), a horizon nothing was ever checked at
+constexpr int SWEEP_MAX_K = 45;
+bool sweep_supports(int K) { return K >= 3 && K <= SWEEP_MAX_K && 2 * (K - 1) <= 128; }
 int blob_words(int K) { const BlobLayout L(K); return (L.words() + 1) & ~1; }
 
 // ---- the sweep kernel's instantiations live in mgx_sweep_inst.hip (several objects, one per flavour and horizon set) ----
@@ -665,25 +668,25 @@ static int sweep_variant_of(int K) {
 }
 #define MGX_DECLARE_SET(N)                                                                                                          \
     bool sweep_plain_set##N(int kt, const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,   \
-                            int snap_out, uint32_t hints, hipStream_t stream);                                                      \
+                            int snap_out, uint32_t hints, hipStream_t stream, SweepRan *ran);                                       \
     int resident_capacity_set##N(int kt, const DevWorld &w);                                                                        \
     bool resident_launch_set##N(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream, \
-                                hipError_t *err);                                                                                   \
+                                hipError_t *err, SweepRan *ran);                                                                    \
     int sharded_capacity_set##N(int kt, const DevWorld &w);                                                                         \
     bool sharded_launch_set##N(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream,  \
-                               hipError_t *err);
+                               hipError_t *err, SweepRan *ran);
 MGX_DECLARE_SET(0)
 MGX_DECLARE_SET(1)
 MGX_DECLARE_SET(2)
 #undef MGX_DECLARE_SET
 
 hipError_t launch_robot_sweep(const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,
-                              int snap_out, uint32_t hints, hipStream_t stream) {
+                              int snap_out, uint32_t hints, hipStream_t stream, SweepRan *ran) {
     if (n_robots <= 0) return hipSuccess;
     const int kt = sweep_variant_of(w.K);
-    if (!sweep_plain_set0(kt, w, robot0, n_robots, ext_mask, int_mask, n_int, snap_out, hints, stream) &&
-        !sweep_plain_set1(kt, w, robot0, n_robots, ext_mask, int_mask, n_int, snap_out, hints, stream) &&
-        !sweep_plain_set2(kt, w, robot0, n_robots, ext_mask, int_mask, n_int, snap_out, hints, stream))
+    if (!sweep_plain_set0(kt, w, robot0, n_robots, ext_mask, int_mask, n_int, snap_out, hints, stream, ran) &&
+        !sweep_plain_set1(kt, w, robot0, n_robots, ext_mask, int_mask, n_int, snap_out, hints, stream, ran) &&
+        !sweep_plain_set2(kt, w, robot0, n_robots, ext_mask, int_mask, n_int, snap_out, hints, stream, ran))
         return hipErrorInvalidValue;
     return hipGetLastError();
 }
@@ -699,16 +702,17 @@ int sweep_resident_capacity(const DevWorld &w, bool sharded) {
     if (cap < 0) cap = sharded ? sharded_capacity_set2(kt, w) : resident_capacity_set2(kt, w);
     return cap < 0 ? 0 : cap;
 }
-hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, bool cooperative, hipStream_t stream) {
+hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, bool cooperative, hipStream_t stream,
+                                 SweepRan *ran) {
     if (n_robots <= 0 || plan.n <= 0) return hipSuccess;
     const int kt = sweep_variant_of(w.K);
     hipError_t e = hipErrorInvalidValue;
     if (sharded) {
-        if (!sharded_launch_set0(kt, w, n_robots, plan, cooperative, stream, &e) && !sharded_launch_set1(kt, w, n_robots, plan, cooperative, stream, &e))
-            (void)sharded_launch_set2(kt, w, n_robots, plan, cooperative, stream, &e);
+        if (!sharded_launch_set0(kt, w, n_robots, plan, cooperative, stream, &e, ran) && !sharded_launch_set1(kt, w, n_robots, plan, cooperative, stream, &e, ran))
+            (void)sharded_launch_set2(kt, w, n_robots, plan, cooperative, stream, &e, ran);
     } else {
-        if (!resident_launch_set0(kt, w, n_robots, plan, cooperative, stream, &e) && !resident_launch_set1(kt, w, n_robots, plan, cooperative, stream, &e))
-            (void)resident_launch_set2(kt, w, n_robots, plan, cooperative, stream, &e);
+        if (!resident_launch_set0(kt, w, n_robots, plan, cooperative, stream, &e, ran) && !resident_launch_set1(kt, w, n_robots, plan, cooperative, stream, &e, ran))
+            (void)resident_launch_set2(kt, w, n_robots, plan, cooperative, stream, &e, ran);
     }
     return e;
 }

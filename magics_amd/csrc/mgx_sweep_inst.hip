@@ -42,26 +42,32 @@ size_t sweep_resident_lds_max();
 
 template <int KT>
 static void launch_k(const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int, int snap_out,
-                     uint32_t hints, hipStream_t stream) {
+                     uint32_t hints, hipStream_t stream, SweepRan *ran) {
     // staging the inter-robot messages needs IR_STRIDE f64 per edge; beyond 64 KB of LDS fall back to
     // reading them from L2 in every variable sweep
     const size_t staged = sweep_lds_bytes(w.K, w.ir_max_edges);
     const SegPlan none{};
-    if (w.ir_max_edges == 0)
+    int mode;
+    if (w.ir_max_edges == 0) {
+        mode = IR_NONE;
         hipLaunchKernelGGL((k_robot_sweep<KT, IR_NONE, false>), dim3(n_robots), dim3(SWEEP_BLOCK), sweep_lds_bytes(w.K, 0), stream, w,
                            robot0, ext_mask, int_mask, n_int, snap_out, hints, none);
-    else if (staged <= 64 * 1024)
+    } else if (staged <= 64 * 1024) {
+        mode = IR_STAGED;
         hipLaunchKernelGGL((k_robot_sweep<KT, IR_STAGED, false>), dim3(n_robots), dim3(SWEEP_BLOCK), staged, stream, w, robot0, ext_mask,
                            int_mask, n_int, snap_out, hints, none);
-    else
+    } else {
+        mode = IR_GLOBAL;
         hipLaunchKernelGGL((k_robot_sweep<KT, IR_GLOBAL, false>), dim3(n_robots), dim3(SWEEP_BLOCK), sweep_lds_bytes(w.K, 0), stream, w,
                            robot0, ext_mask, int_mask, n_int, snap_out, hints, none);
+    }
+    if (ran) { ran->variant = KT; ran->ir_mode = mode; }
 }
 
 bool MGX_SET_NAME(sweep_plain)(int kt, const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,
-                               int snap_out, uint32_t hints, hipStream_t stream) {
+                               int snap_out, uint32_t hints, hipStream_t stream, SweepRan *ran) {
     switch (kt) {
-#define MGX_DO(KT) case KT: launch_k<KT>(w, robot0, n_robots, ext_mask, int_mask, n_int, snap_out, hints, stream); return true;
+#define MGX_DO(KT) case KT: launch_k<KT>(w, robot0, n_robots, ext_mask, int_mask, n_int, snap_out, hints, stream, ran); return true;
         MGX_K_LIST(MGX_DO)
 #undef MGX_DO
     default: return false;
@@ -101,9 +107,11 @@ static int resident_capacity_k(const DevWorld &w) {
     return per_cu * cus;
 }
 template <int KT>
-static hipError_t resident_launch_k(const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream) {
+static hipError_t resident_launch_k(const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream,
+                                    SweepRan *ran) {
     const size_t staged = sweep_lds_bytes(w.K, w.ir_max_edges, true);
     if (!resident_allow_lds<KT>(staged)) return hipErrorInvalidValue;
+    if (ran) { ran->variant = KT; ran->ir_mode = IR_STAGED; }
     const int grid = n_robots + (plan.launch_seq != 0ull ? 1 : 0);  // + the residency census' decider workgroup (mgx_sweep.h)
     if (cooperative) {  // the launch-time check of the grid against the occupancy query; same residency as a plain launch
         DevWorld wa = w;
@@ -134,9 +142,9 @@ int MGX_RES_NAME(capacity)(int kt, const DevWorld &w) {  // -1: not this set's h
     }
 }
 bool MGX_RES_NAME(launch)(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream,
-                          hipError_t *err) {
+                          hipError_t *err, SweepRan *ran) {
     switch (kt) {
-#define MGX_DO(KT) case KT: *err = resident_launch_k<KT>(w, n_robots, plan, cooperative, stream); return true;
+#define MGX_DO(KT) case KT: *err = resident_launch_k<KT>(w, n_robots, plan, cooperative, stream, ran); return true;
         MGX_K_LIST(MGX_DO)
 #undef MGX_DO
     default: return false;

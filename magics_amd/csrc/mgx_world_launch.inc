@@ -120,7 +120,8 @@ static int sweep(mgx_world *w, int32_t robot, uint32_t ext_mask, uint32_t int_ma
         }
         if (w->ir_thaw_active && (ext_mask & PH_EXT_FACTOR) && w->d.NI > 0 && !w->conns.empty())
             HIP_TRY(launch_thaw_ir(w->d, w->ir_gate.p, w->stream));
-        HIP_TRY(launch_robot_sweep(w->d, 0, w->d.R_local, ext_mask, int_mask, n_int, out, hints, w->stream));
+        HIP_TRY(launch_robot_sweep(w->d, 0, w->d.R_local, ext_mask, int_mask, n_int, out, hints, w->stream, &w->last_sweep));
+        w->last_sweep_form = MGX_SWEEP_FORM_SEGMENTS;
         w->last_sweep_launches++;
         if (w->ir_thaw_active && writes_snap) {  // once every robot has run an internal variable sweep, every owner has delivered
             bool all_take_part = true;  // ghosts count: their owners' flags are kept here too, and their records arrive by exchange
@@ -146,7 +147,9 @@ static int sweep(mgx_world *w, int32_t robot, uint32_t ext_mask, uint32_t int_ma
         // single workgroup: nobody else reads the snapshot buffer concurrently => update in place
         const bool thawing = w->thaw_kinds && (int_mask & PH_INT_FACTOR) && n_int > 0;
         if (thawing) HIP_TRY(launch_thaw(w->d, w->dev_of[(size_t)robot], 1, 0, w->stream));
-        HIP_TRY(launch_robot_sweep(w->d, w->dev_of[(size_t)robot], 1, 0, int_mask, n_int, writes_snap ? w->d.cur : -1, 0, w->stream));
+        HIP_TRY(launch_robot_sweep(w->d, w->dev_of[(size_t)robot], 1, 0, int_mask, n_int, writes_snap ? w->d.cur : -1, 0, w->stream,
+                                   &w->last_sweep));
+        w->last_sweep_form = MGX_SWEEP_FORM_SEGMENTS;
         if (w->thaw_kinds && (thawing || writes_snap)) HIP_TRY(launch_thaw_done(w->d, w->dev_of[(size_t)robot], 1, writes_snap ? 1 : 0, w->stream));
         log_launch(w, robot, 0, int_mask, n_int);
     }
@@ -463,6 +466,8 @@ static int linger_post(mgx_world *w, const std::vector<Launch> &plan, bool has_u
     w->flag_base += (unsigned long long)plan.size() - 1ull;
     w->stale_kinds |= ~w->p.enable_mask & 15u;  // disabled factors miss what these sweeps deliver
     w->last_sweep_launches++;  // (one submission: the schedule runs inside the launch that is there)
+    w->last_sweep = lg.ran;
+    w->last_sweep_form = MGX_SWEEP_FORM_POSTED;
     return MGX_OK;
 }
 static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
@@ -582,7 +587,8 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
         // time (same residency as a plain launch, +15..19 us of host time per launch: MI355X_MICROARCH.md); a grid it turns
         // down takes the launch-per-segment path from now on instead of waiting for workgroups that never become resident
         static const bool cooperative = [] { const char *e = getenv("MGX_COOPERATIVE"); return e && e[0] == '1'; }();
-        const hipError_t le = can ? launch_robot_schedule(w->d, w->d.R_local, sp, sharded, cooperative, w->stream)
+        SweepRan ran;
+        const hipError_t le = can ? launch_robot_schedule(w->d, w->d.R_local, sp, sharded, cooperative, w->stream, &ran)
                                   : launch_agree_abort(w->d, sp, w->stream);
         if (le != hipSuccess) {
             (void)hipGetLastError();
@@ -594,10 +600,15 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
         }
         w->last_sweep_launches++;
         w->resident_launches++;
+        if (can) {  // (a rank that voted no launched no sweep)
+            w->last_sweep = ran;
+            w->last_sweep_form = sharded ? MGX_SWEEP_FORM_SHARDED : MGX_SWEEP_FORM_RESIDENT;
+        }
         if (sp.linger_ticks > 0) {
             mgx_world::Linger &lg = w->linger;
             lg.open = true;
             lg.seq0 = sp.launch_seq;
+            lg.ran = ran;
             lg.taken_in_launch = 0;
             lg.un.active = false;
             lg.launches++;

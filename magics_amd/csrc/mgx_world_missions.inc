@@ -252,6 +252,8 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     const std::vector<Launch> plan = plan_launches(steps, n_steps);
     if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }  // (a declined launch is run again here: not this call's launches)
     w->last_sweep_launches = 0;
+    w->last_sweep = SweepRan{};
+    w->last_sweep_form = -1;
     const bool fuse = !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0;
     if (!fuse) {
         HIP_TRY(launch_update_priors(w->d, R, ms.robots_d.p, ms.waypoints_d.p, ms.ts_list_d.p, ms.what_d.p, max_speed, delta_t, s));

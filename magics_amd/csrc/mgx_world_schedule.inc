@@ -69,6 +69,8 @@ static int iterate_now(mgx_world *w, const uint8_t *steps, uint32_t n) {
         if (rcc != MGX_OK) return rcc;
     }
     w->last_sweep_launches = 0;
+    w->last_sweep = SweepRan{};
+    w->last_sweep_form = -1;
     w->linger.streak++;  // (every other entry point resets it: MGX_ENTER)
     const int resident = run_resident(w, plan);
     if (resident != 0) return resident < 0 ? resident : MGX_OK;
@@ -179,6 +181,8 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
         if (rcc != MGX_OK) return rcc;
     }
     w->last_sweep_launches = 0;
+    w->last_sweep = SweepRan{};
+    w->last_sweep_form = -1;
     const bool fuse = n > 0 && !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0 && w->K >= 3;
     if (!fuse) {
         const int rc = n ? mgx_update_priors(w, n, robots, waypoints_xy, time_scale, what, max_speed, delta_t) : MGX_OK;
@@ -347,6 +351,23 @@ int mgx_last_launch_count(mgx_world *w, uint32_t *n_launches) {
     if (!w || !n_launches) return fail(MGX_ERR_INVALID, "null argument");
     if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
     *n_launches = w->last_sweep_launches;
+    return MGX_OK;
+}
+int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *form, int32_t *resident_capacity) {
+    MGX_ENTER_SCHEDULE(w);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    // (a resident launch the census declined has been run again launch by launch by the time it is decided: that is what ran)
+    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    if (variant) *variant = w->last_sweep.variant;
+    if (ir_mode) *ir_mode = w->last_sweep.ir_mode;
+    if (form) *form = w->last_sweep_form;
+    if (resident_capacity) {
+        const bool sharded = w->xres.connected;
+        int cap = sharded ? w->resident_cap_sharded : w->resident_cap;
+        // (not asked by a launch yet: asked here, for the topology on the device — no commit, which would end a lingering launch)
+        if (cap < 0) cap = device_ok() ? sweep_resident_capacity(w->d, sharded) : 0;
+        *resident_capacity = cap;
+    }
     return MGX_OK;
 }
 

@@ -26,10 +26,11 @@ size_t sweep_lds_bytes(int K, int ir_edges, bool resident);
 int blob_words(int K);
 bool sweep_supports(int K);
 hipError_t launch_robot_sweep(const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,
-                              int snap_out, uint32_t hints, hipStream_t stream);
+                              int snap_out, uint32_t hints, hipStream_t stream, SweepRan *ran);
 int sweep_resident_capacity(const DevWorld &w, bool sharded);
 size_t sweep_resident_lds_max();
-hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, bool cooperative, hipStream_t stream);
+hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, bool cooperative, hipStream_t stream,
+                                 SweepRan *ran);
 hipError_t launch_agree_abort(const DevWorld &w, const SegPlan &plan, hipStream_t stream);
 hipError_t launch_change_prior(const DevWorld &w, int n, const int32_t *robots, const uint32_t *vars, const double *means,
                                hipStream_t stream);
@@ -503,6 +504,7 @@ struct mgx_world {
         size_t dev_stride = 0;
         bool open = false, hold = false;
         unsigned long long seq0 = 0;       // number of the open launch's own plan
+        SweepRan ran;                      // the open launch's instantiation (what a post runs in)
         uint32_t taken_in_launch = 0;      // posts the open launch has taken
         int useless = 0;                   // lingering launches in a row that ended without having taken a post
         uint32_t streak = 0;               // schedules issued back to back, this one included (no other call on the world in between)
@@ -625,6 +627,8 @@ struct mgx_world {
         uint32_t method = 0, M = 0;
     } mission_search;  // the coming tick's search, enqueued by mgx_mission_tick_end
     uint32_t last_sweep_launches = 0;  // sweep-kernel launches of the last mgx_iterate / mgx_tick call (mgx_last_launch_count)
+    SweepRan last_sweep;               // the sweep instantiation it launched last (mgx_last_sweep) ...
+    int32_t last_sweep_form = -1;      // ... and in which form (MGX_SWEEP_FORM_*; -1: none)
     // message counters are advanced lazily: launches and prior changes are only logged here
     struct CountEntry { uint8_t ext, in; int n_int, robot; uint64_t times; };
     std::vector<CountEntry> clog;

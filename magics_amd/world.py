@@ -243,24 +243,26 @@ class World:
         wp = _f64(waypoints_xy, (n, 2))
         ts = _f64(time_scale, (n,))
         what = np.ascontiguousarray(what, dtype=np.uint8)
+        if what.shape != (n,):
+            raise ValueError(f"expected shape {(n,)}, got {what.shape}")
         self._chk(self._L.mgx_update_priors(self._w, n, robots.ctypes.data_as(C.POINTER(C.c_int32)), _dp(wp), _dp(ts),
                                             what.ctypes.data_as(C.POINTER(C.c_uint8)), float(max_speed), float(delta_t)))
 
     def _arg(self, a, dtype, shape=None):
         """(keep-alive, address) of an array argument.  A driver hands the same arrays tick after tick: an array that is already
         what the C side reads (dtype, C-contiguous) is remembered with its address — preparing four pointers costs more host
-        time than the call they go into (15 us of a 130 us tick)."""
+        time than the call they go into (15 us of a 130 us tick).  The shape is checked on every call, remembered or not: the
+        same array may come with a different number of robots (or have been reshaped in place)."""
         e = self._args.get(id(a))
-        if e is not None and e[0] is a:
-            return e
-        b = np.ascontiguousarray(a, dtype=dtype)
-        if shape is not None and b.shape != shape:
-            raise ValueError(f"expected shape {shape}, got {b.shape}")
-        e = (b, b.ctypes.data)
-        if b is a:  # (held here: its id cannot be handed to another object, its buffer cannot be resized)
-            if len(self._args) >= 16:
-                self._args.pop(next(iter(self._args)))
-            self._args[id(a)] = e
+        if e is None or e[0] is not a:
+            b = np.ascontiguousarray(a, dtype=dtype)
+            e = (b, b.ctypes.data)
+            if b is a:  # (held here: its id cannot be handed to another object, its buffer cannot be resized)
+                if len(self._args) >= 16:
+                    self._args.pop(next(iter(self._args)))
+                self._args[id(a)] = e
+        if shape is not None and e[0].shape != shape:
+            raise ValueError(f"expected shape {shape}, got {e[0].shape}")
         return e
 
     def tick(self, robots, waypoints_xy, time_scale, what, max_speed, delta_t, steps):
@@ -270,7 +272,7 @@ class World:
         n = len(r[0])
         wp = self._arg(waypoints_xy, np.float64, (n, 2))
         ts = self._arg(time_scale, np.float64, (n,))
-        wh = self._arg(what, np.uint8)
+        wh = self._arg(what, np.uint8, (n,))
         key = steps if isinstance(steps, (bytes, tuple)) else tuple(steps)
         b = _STEP_BYTES.get(key)
         if b is None:
@@ -405,6 +407,15 @@ class World:
         n = C.c_uint32()
         self._chk(self._L.mgx_last_launch_count(self._w, C.byref(n)))
         return n.value
+
+    def last_sweep(self):
+        """how the last iterate / tick call ran its sweeps (mgx_last_sweep): (variant, ir_mode, form, resident_capacity) —
+        the sweep kernel's horizon variant (K, or 0 / -1 for the run-time-K kernels), inter-robot mode (0 none, 1 unstaged,
+        2 staged), form (0 launch per segment, 1 resident launch, 2 posted into a lingering launch, 3 sharded resident launch;
+        -1: no sweep ran) and the workgroups of this world's resident instantiation the device holds at once (0: none)"""
+        v = [C.c_int32() for _ in range(4)]
+        self._chk(self._L.mgx_last_sweep(self._w, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def note_change_priors(self, robots, var_ix):
         """counters only: prior changes another rank applied to robots that are ghosts here (mgx_note_change_priors)"""

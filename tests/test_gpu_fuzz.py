@@ -78,13 +78,16 @@ def test_random_script(K, n, seed, batched):
 
 def test_many_neighbours_falls_back_to_unstaged_messages():
     # a dense cluster gives a robot more inter-robot edges than LDS staging allows (> 64 KB per
-    # workgroup): the kernel variant that reads the messages from L2 must give the same beliefs
-    sc = S.grid_scenario(49, 16, interrobot=True, pitch=1.2, comm_radius=20.0, obstacles=False)
-    per_robot = max(sum(1 for c in sc["ir"] if c[1] == r) for r in range(49)) * 15
-    assert per_robot * 21 * 8 > 64 * 1024
+    # workgroup on the launch-per-segment path): the kernel variant that reads the messages from L2
+    # must give the same beliefs.  64 robots x K = 16, everyone in range: 63 neighbours x 15 edges
+    # (staging them takes 74 KB by sweep_lds_bytes)
+    sc = S.grid_scenario(64, 16, interrobot=True, pitch=1.2, comm_radius=20.0, obstacles=False)
+    assert max(sum(1 for c in sc["ir"] if c[1] == r) for r in range(64)) == 63
     eng, ref = make_pair(sc)
+    eng.set_resident_launches(False)
     for w in (eng, ref):
         w.iterate([3, 3, 1, 3])
+    assert eng.last_sweep()[:3] == (16, 1, 0), eng.last_sweep()  # (variant, unstaged inter-robot messages, launch per segment)
     assert_identical(eng, ref, what="unstaged inter-robot messages")
 
 
