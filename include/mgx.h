@@ -383,6 +383,44 @@ int mgx_mission_translations(mgx_world *w, float *translations, uint32_t capacit
  * at which each mission completed (-1 before) of every robot, id order; any pointer may be NULL.  Synchronises. */
 int mgx_mission_read(mgx_world *w, float *translations, int32_t *targets, int64_t *finished_tick);
 
+/* ---- robot-robot collision bookkeeping on the device -------------------------------------------------------
+ * update_robot_robot_collisions with the Free / Colliding state machine of CollisionHistory (planner/collisions.rs:72-140,
+ * 455-495), the figure the reference's export is read for next to makespan and smoothness.  One PASS looks at the robots
+ * alive at that moment (not removed, not ghosts), their Transforms (x, z) as f32 and r = (float)desc.radius:
+ *   pair (a, b), a < b by robot id, overlaps iff dx*dx + dy*dy <= (r_a + r_b)*(r_a + r_b), d = p_b - p_a, every operation
+ *   rounded to f32 on its own (the same in libmgx.so and libmgx_fma.so); a NaN anywhere: no overlap;
+ *   a pair that overlaps now and did not in the pass before (or was not looked at: one of the two was not alive, or is new)
+ *   is one collision EVENT, with mins = max(p_a - r_a, p_b - r_b), maxs = min(p_a + r_a, p_b + r_b) per axis (the
+ *   intersection of the two balls' AABBs), and counts once for robot a and once for robot b;
+ *   a pair that parts, or loses a robot, is Free again.  Events of despawned robots stay in the log.
+ * Robot-environment collisions are not computed (parry2d shape queries against the map generator's colliders).
+ * mgx_collisions_enable(w, 1, method, event_capacity): switches the bookkeeping on (default: off — no kernel, no allocation).
+ *   method: MGX_NEIGHBOURS_AUTO / _PAIRS / _GRID (all pairs below 512 alive robots, a hash grid of 2 r_max cells above; the same
+ *   events either way).  event_capacity (0: 262144) records of log and room for 65536 pairs overlapping at once are allocated
+ *   here and never grow.  Calling it again while on changes the method only; (w, 0, ..) switches off and drops the state.
+ * While on, every mgx_mission_tick_end (so every mgx_mission_tick and every tick of mgx_mission_run) enqueues one pass on the
+ *   Transforms after that tick's move and the robots alive after that tick's despawns, in front of the schedule's launches:
+ *   no synchronisation, nothing read back.
+ * mgx_collisions_update: the same pass over positions the caller keeps ([n_robots][3], x and z are read; NULL: the device's
+ *   mission Transforms as they are) — the mgx_update_topology counterpart.  Enqueued, not waited for.
+ * mgx_collisions_read: the one call that synchronises.  events [first, first + capacity) of the log in (pass, robot_a, robot_b)
+ *   order (pass: 0 for the first pass since enable / clear), *n_total = events in the log, *dropped = events that found the
+ *   log full (counted, not stored; the per-robot counts include them), per_robot [n_robots] (may be NULL) = contacts of every
+ *   robot.  Nothing is lost silently: if more pairs overlapped at once than there is room for, the call fills its outputs and
+ *   returns MGX_ERR_STATE (later passes may have missed contacts).
+ * mgx_collisions_clear: clear_robot_robot_collisions (collisions.rs:68-70): everybody Free, log and counts empty, pass 0.
+ * Unsharded worlds (MGX_ERR_STATE on a world with ghosts); MGX_ERR_STATE from _update / _read / _clear while switched off. */
+typedef struct mgx_collision_event {
+    uint64_t pass;
+    int32_t robot_a, robot_b;     /* robot_a < robot_b */
+    float mins[2], maxs[2];       /* (x, z) */
+} mgx_collision_event;
+int mgx_collisions_enable(mgx_world *w, int32_t enabled, uint32_t method, uint64_t event_capacity);
+int mgx_collisions_update(mgx_world *w, const float *positions_xyz);
+int mgx_collisions_read(mgx_world *w, uint64_t first, mgx_collision_event *events, uint64_t capacity, uint64_t *n_total,
+                        uint64_t *dropped, uint32_t *per_robot);
+int mgx_collisions_clear(mgx_world *w);
+
 /* ---- read-back ----------------------------------------------------------------------- */
 /* VariableNode.belief (variable.rs:40-54).  Any output pointer may be NULL. */
 int mgx_get_belief(mgx_world *w, int32_t robot, uint32_t var_ix, double eta[4], double lam[16],

@@ -204,6 +204,28 @@ public:
         if (n) check(mgx_read_variable_means(w_, variable_index, out[0].data()));
         return out;
     }
+    /// update_robot_robot_collisions on the device (planner/collisions.rs:72-140): while enabled every mission tick ends with one
+    /// pass; `update` is the same pass over Transforms the caller keeps; `read` is the one call that waits for the device
+    void collisions_enable(bool enabled = true, uint32_t method = MGX_NEIGHBOURS_AUTO, uint64_t event_capacity = 0) {
+        check(mgx_collisions_enable(w_, enabled ? 1 : 0, method, event_capacity));
+    }
+    void collisions_update(const std::vector<std::array<float, 3>> &translations) { check(mgx_collisions_update(w_, translations[0].data())); }
+    struct Collisions {
+        std::vector<mgx_collision_event> events;  ///< from `first` on, in (pass, robot_a, robot_b) order
+        uint64_t n_total = 0, dropped = 0;
+        std::vector<uint32_t> per_robot;
+    };
+    Collisions collisions_read(uint64_t first = 0) {
+        Collisions out;
+        uint32_t n = 0;
+        check(mgx_num_robots(w_, &n, nullptr));
+        out.per_robot.assign(n, 0u);
+        check(mgx_collisions_read(w_, first, nullptr, 0, &out.n_total, &out.dropped, nullptr));
+        out.events.resize(out.n_total > first ? (size_t)(out.n_total - first) : 0);
+        check(mgx_collisions_read(w_, first, out.events.data(), out.events.size(), &out.n_total, &out.dropped, out.per_robot.data()));
+        return out;
+    }
+    void collisions_clear() { check(mgx_collisions_clear(w_)); }
     void synchronize() { check(mgx_synchronize(w_)); }
     uint32_t K() const { return K_; }
 

@@ -248,6 +248,32 @@ struct DevMission {
     long long *finished_tick;  // [R] tick at which the last waypoint was reached, -1 before
 };
 
+// Robot-robot collision bookkeeping on the device (mgx_collisions.hip, which says what every array is for): what one pass
+// is handed.  Everything is indexed by robot id.
+struct CollEvent {  // == mgx_collision_event (include/mgx.h; mgx_collisions.hip asserts it)
+    unsigned long long pass;
+    int32_t robot_a, robot_b;
+    float mins[2], maxs[2];
+};
+struct CollDev {
+    const float *pos;          // [n][3] Transform::translation (x, height, z)
+    const uint8_t *alive;      // [n] not removed, not a ghost
+    const float *radius;       // [n] (float)desc.radius
+    int n;                     // robots of the world (ids 0 .. n-1)
+    uint32_t stride;           // of the pair bits: pair (a, b) is bit a * stride + b
+    uint32_t *bits;
+    int2 *list[2];             // the overlapping pairs, read / written in turn
+    uint32_t *cnt;             // [3] lengths of the lists, in rotation
+    uint32_t list_cap;
+    CollEvent *log;            // [log_cap]
+    unsigned long long log_cap;
+    unsigned long long *words;  // [0] log cursor (keeps counting beyond log_cap), [1] sticky: the pair list overflowed
+    uint32_t *per_robot;       // [n] contacts of every robot
+    unsigned long long *head;  // hash grid: per bucket (pass stamp << 32) | first robot
+    int32_t *next;             // [n] next robot of the same bucket, -1: none
+    unsigned long long pass;
+};
+
 __host__ __device__ constexpr int frozen_words(int K) { return 40 * (K - 1) + 8 * (K - 2); }
 
 // phases of one launch

@@ -75,6 +75,9 @@ hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, i
                            int32_t *prev = nullptr, int prev_valid = 0, bool *flagged = nullptr);
 int neighbours_prev_stride();
 int32_t neighbours_changed_bit();
+// mgx_collisions.hip
+hipError_t launch_collisions_pass(const CollDev &c, bool grid, double cell, uint32_t n_buckets, hipStream_t s);
+hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s);
 }  // namespace mgx
 
 using namespace mgx;
@@ -612,6 +615,26 @@ struct mgx_world {
         size_t tr_cap = 0, tr_n = 0;
         DevMission d{};
     } mission;
+    // robot-robot collision bookkeeping on the device (mgx_collisions_*, mgx_collisions.hip): everything is keyed by robot id, so a
+    // relayout of the world's arrays moves nothing here — robots that join only make the per-robot arrays (and the stride of the
+    // pair bits) grow
+    struct Collisions {
+        bool enabled = false;
+        uint32_t method = 0;
+        size_t n_sized = 0;      // robots the per-robot arrays were last sized and the radii uploaded for
+        uint32_t stride = 0;     // of the pair bits
+        DevBuf<uint32_t> bits, cnt, per_robot;
+        DevBuf<int2> list[2];
+        DevBuf<CollEvent> log;
+        DevBuf<unsigned long long> words, head;
+        DevBuf<int32_t> next;
+        DevBuf<float> radius, pos;  // pos: positions the caller handed in (mgx_collisions_update)
+        DevBuf<uint8_t> alive;      // ... and who was alive then
+        uint32_t n_buckets = 0;
+        uint64_t log_cap = 0, pass = 0;
+        std::vector<mgx_collision_event> host_log;  // the events fetched so far, in (pass, robot_a, robot_b) order
+        CollDev d{};
+    } coll;
     // a neighbour search that has been enqueued and not collected yet (neighbours_enqueue / neighbours_collect)
     struct PendingSearch {
         hipStream_t stream = nullptr;  // where it was enqueued

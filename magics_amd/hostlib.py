@@ -182,6 +182,10 @@ SYMBOLS = {
     "mgx_mission_finished": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_mission_translations": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_mission_read": (C.c_int, [_V, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "mgx_collisions_enable": (C.c_int, [_V, C.c_int32, C.c_uint32, C.c_uint64]),
+    "mgx_collisions_update": (C.c_int, [_V, C.c_void_p]),
+    "mgx_collisions_read": (C.c_int, [_V, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    "mgx_collisions_clear": (C.c_int, [_V]),
     "mgx_num_robots": (C.c_int, [_V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mgx_last_launch_count": (C.c_int, [_V, C.POINTER(C.c_uint32)]),
     "mgx_last_sweep": (C.c_int, [_V, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -341,6 +345,17 @@ class MissionDesc(C.Structure):
     _fields_ = [("n_waypoints", C.c_uint32), ("reserved", C.c_uint32), ("waypoints_xy", c_double_p), ("reach_var", C.c_uint32),
                 ("finish_var", C.c_uint32), ("reach_dist2", C.c_float), ("finish_dist2", C.c_float), ("translation", C.c_float * 3),
                 ("reserved2", C.c_float), ("time_scale", C.c_double)]
+
+
+class CollisionEvent(C.Structure):
+    """mgx_collision_event (include/mgx.h)"""
+    _fields_ = [("pass_", C.c_uint64), ("robot_a", C.c_int32), ("robot_b", C.c_int32), ("mins", C.c_float * 2), ("maxs", C.c_float * 2)]
+
+
+def collision_event_dtype():
+    """numpy view of an array of mgx_collision_event"""
+    import numpy as np
+    return np.dtype([("pass", np.uint64), ("robot_a", np.int32), ("robot_b", np.int32), ("mins", np.float32, 2), ("maxs", np.float32, 2)])
 
 
 def shard_partition(positions_xy, n_ranks):

@@ -14,7 +14,7 @@ by the frame's Update systems that matter to the path (the formation spawners):
 The reference runs its Update systems at the display's frame rate against virtual time, so the
 interleaving of spawns with fixed ticks is not reproducible there; here a frame is exactly one
 fixed tick long.  Rendering, picking, RRT* planning (`planning-strategy: rrt-star` is rejected),
-collision bookkeeping with parry2d and goal areas are outside the path (SURVEY §8 out of scope).
+robot-environment collision bookkeeping with parry2d and goal areas are outside the path (SURVEY §8 out of scope).
 """
 import json
 
@@ -30,14 +30,21 @@ F = np.float32
 
 
 class Simulation:
-    def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None):
+    def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None):
         """scenario: `config.load_scenario(dir)` (or a dict of the same shape); world: a fresh
         World-like object created with `config.world_params(scenario["config"])`.
         device_missions (default: whenever the world offers them, i.e. the engine): routes, reached-when rules and
         Transforms live on the device (include/mgx.h, mgx_mission_*) and a tick is two calls around the comms draws with
         ONE synchronisation and no belief read-back; otherwise this loop does all of it on the host (the CPU oracle's
-        path, and the checker of the other one: tests/test_gpu_sim.py)."""
+        path, and the checker of the other one: tests/test_gpu_sim.py).
+        device_collisions (default: whenever the missions live on the device and the world offers collisions_enable): the
+        robot-robot collision pass runs on the device at the end of every tick (mgx_collisions_*) and `collisions` is filled
+        from its event log when somebody asks; otherwise _collide below runs on the host every tick (the checker)."""
         self.dev = hasattr(world, "mission_tick_begin") if device_missions is None else bool(device_missions)
+        self._dev_coll = (self.dev and hasattr(world, "collisions_enable")) if device_collisions is None else bool(device_collisions)
+        if self._dev_coll and not self.dev:
+            raise ValueError("device_collisions needs device_missions (the pass reads the device's Transforms)")
+        self._coll_cursor = 0      # events of the device's log already taken into `collisions`
         self._pending_track = None
         self._trk_log = []  # what _track noted since _tracks last ran
         self.name = scenario.get("name", "")
@@ -62,7 +69,9 @@ class Simulation:
         self._translation = np.zeros((0, 3), dtype=F)
         self.tick_no, self.next_number, self.K = 0, 1, None
         self.events = []           # (tick, connections created, pairs deleted)
-        self.collisions = {}       # (robot a, robot b), a < b -> {"colliding": bool, "times": int, "aabbs": [...]}
+        self._collisions = {}      # (robot a, robot b), a < b -> {"colliding": bool, "times": int, "aabbs": [...]}
+        if self._dev_coll:
+            world.collisions_enable(True, method=neighbours_method)
         self.entities = spawner.EntityAllocator()  # the robots' Entity bits = their graphs' order (id.rs:19-54)
 
     # -- spawn_formation (spawner.rs:415-649) + RobotBundle::new (robot.rs:1134-1356) -------------------
@@ -184,6 +193,26 @@ class Simulation:
     # Free / Colliding state machine of CollisionHistory (:455-495): a Free -> Colliding edge is one collision, recorded with
     # the intersection of the two balls' AABBs (:113-119).  Robot - environment collisions need the colliders of the
     # reference's 3-D map generator (environment/map_generator.rs) and parry2d's shape queries: not built (counted 0).
+    @property
+    def collisions(self):
+        """(robot a, robot b), a < b -> {"colliding", "times", "aabbs"}.  With the pass on the device the new events of its log are
+        taken in first (the one read that waits for the device); "colliding" then only says that the pair has met — the
+        Free / Colliding state itself stays on the device."""
+        if getattr(self, "_dev_coll", False):
+            ev, total, dropped, _ = self.w.collisions_read(self._coll_cursor)
+            if dropped:
+                raise hostlib.MgxError(f"the device's collision log was full: {dropped} events were not stored")
+            for e in ev:
+                h = self._collisions.setdefault((int(e["robot_a"]), int(e["robot_b"])), {"colliding": True, "times": 0, "aabbs": []})
+                h["times"] += 1
+                h["aabbs"].append({"mins": [float(e["mins"][0]), float(e["mins"][1])], "maxs": [float(e["maxs"][0]), float(e["maxs"][1])]})
+            self._coll_cursor = total
+        return self._collisions
+
+    @collisions.setter
+    def collisions(self, value):
+        self._collisions = value
+
     def _collide(self, alive, translation):
         if len(alive) < 2:
             return
@@ -217,7 +246,8 @@ class Simulation:
         self._pending_track = None
         tr = self.w.mission_translations()
         self._track(moving, tr, now)
-        self._collide(alive, tr)
+        if not self._dev_coll:
+            self._collide(alive, tr)
 
     def _tick_device(self):
         w = self.w
@@ -328,7 +358,8 @@ class Simulation:
             moving = [r for r in live if not r["completed"]]
             tr = out["translations"][j]
             self._track(moving, tr, (self.tick_no + 1) * self.dt_ns * 1e-9)
-            self._collide(live, tr)
+            if not self._dev_coll:
+                self._collide(live, tr)
             self.tick_no += 1
 
     def run(self, max_ticks=None, max_time=None, chunk=256):
@@ -352,6 +383,7 @@ class Simulation:
             self._flush_trackers(synchronise=True)
         self._tracks()
         sch = self.cfg["gbp"]["iteration-schedule"]
+        collisions = self.collisions
         robots = {}
         for r in self.robots:
             sent_i, sent_e, recv_i, recv_e = self.w.message_counts(r["id"])
@@ -359,7 +391,7 @@ class Simulation:
             fin = r["finished_at"] if r["finished_at"] is not None else self.elapsed()
             robots[str(r["id"])] = {
                 "radius": float(r["radius"]), "positions": r["positions"], "velocities": r["velocities"],
-                "collisions": {"robots": sum(h["times"] for k, h in self.collisions.items() if r["id"] in k), "environment": 0},
+                "collisions": {"robots": sum(h["times"] for k, h in collisions.items() if r["id"] in k), "environment": 0},
                 "messages": {"sent": {"internal": sent_i, "external": sent_e}, "received": {"internal": recv_i, "external": recv_e}},
                 "mission": {"waypoints": [wps[0], wps[-1]], "started_at": r["started_at"], "finished_at": fin,
                             "routes": [{"waypoints": wps, "started_at": r["started_at"], "finished_at": fin}]},
@@ -367,7 +399,7 @@ class Simulation:
         return {"scenario": self.name, "makespan": self.elapsed(), "delta_t": float(self.dt32),
                 "gbp": {"iterations": {"internal": sch["internal"], "external": sch["external"]}}, "robots": robots,
                 "prng_seed": self.cfg["simulation"]["prng-seed"], "config": self.cfg, "obstacles": {},
-                "collisions": {"robots": [{"robot_a": a, "robot_b": b, "aabbs": h["aabbs"]} for (a, b), h in sorted(self.collisions.items())],
+                "collisions": {"robots": [{"robot_a": a, "robot_b": b, "aabbs": h["aabbs"]} for (a, b), h in sorted(collisions.items())],
                                "environment": []},
                 # goal_areas: the reference registers GoalAreaPlugin but its only system that SPAWNS goal areas
                 # (setup_goal_areas_for_junction_scenario, goal_area.rs:105-119) is commented out of the plugin (:8-11):

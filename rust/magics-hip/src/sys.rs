@@ -118,6 +118,17 @@ pub struct mgx_mission_run_desc {
 }
 
 /// opaque handles (include/mgx.h)
+/// one robot-robot contact (include/mgx.h, mgx_collisions_*)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_collision_event {
+    pub pass: u64,
+    pub robot_a: i32,
+    pub robot_b: i32,
+    pub mins: [f32; 2],
+    pub maxs: [f32; 2],
+}
+
 #[repr(C)]
 pub struct mgx_mvn { _private: [u8; 0] }
 #[repr(C)]
@@ -171,6 +182,10 @@ extern "C" {
     pub fn mgx_mission_run(w: *mut mgx_world, desc: *mut mgx_mission_run_desc) -> c_int;
     pub fn mgx_mission_translations(w: *mut mgx_world, translations: *mut f32, capacity_robots: u32, n_robots: *mut u32) -> c_int;
     pub fn mgx_mission_read(w: *mut mgx_world, translations: *mut f32, targets: *mut i32, finished_tick: *mut i64) -> c_int;
+    pub fn mgx_collisions_enable(w: *mut mgx_world, enabled: i32, method: u32, event_capacity: u64) -> c_int;
+    pub fn mgx_collisions_update(w: *mut mgx_world, positions_xyz: *const f32) -> c_int;
+    pub fn mgx_collisions_read(w: *mut mgx_world, first: u64, events: *mut mgx_collision_event, capacity: u64, n_total: *mut u64, dropped: *mut u64, per_robot: *mut u32) -> c_int;
+    pub fn mgx_collisions_clear(w: *mut mgx_world) -> c_int;
     pub fn mgx_get_belief(w: *mut mgx_world, robot: i32, var_ix: u32, eta: *mut f64, lam: *mut f64, mean: *mut f64, cov: *mut f64, valid: *mut i32) -> c_int;
     pub fn mgx_read_beliefs(w: *mut mgx_world, eta: *mut f64, lam: *mut f64, means: *mut f64) -> c_int;
     pub fn mgx_read_means(w: *mut mgx_world, means: *mut f64) -> c_int;

@@ -1,0 +1,75 @@
+"""What the robot-robot collision bookkeeping costs a mission tick (profiles/collisions.md):
+
+    python tools/collisions_bench.py --mode off      # mission ticks, collisions disabled
+    python tools/collisions_bench.py --mode device   # the pass on the device at the end of every tick (mgx_collisions_*)
+    python tools/collisions_bench.py --mode host     # Transforms read per tick + sim.Simulation._collide per tick (the host pass)
+
+A grid world with inter-robot factors on, driven through mgx_mission_tick_begin / _end like sim.Simulation does; `--reps`
+timings of `--ticks` ticks each, one JSON line with the median ticks/s."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np  # noqa: E402
+
+from magics_amd import World, hostlib, sim  # noqa: E402
+from magics_amd import scenarios as S  # noqa: E402
+from magics_amd.driver import DeviceDriver  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--mode", choices=["off", "device", "host"], required=True)
+ap.add_argument("--robots", type=int, default=1000)
+ap.add_argument("--K", type=int, default=16)
+ap.add_argument("--ticks", type=int, default=200)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--warmup", type=int, default=30)
+ap.add_argument("--method", type=int, default=hostlib.NEIGHBOURS_AUTO)
+a = ap.parse_args()
+
+sc = S.grid_scenario(a.robots, a.K, interrobot=True, comm_radius=8.0)
+sc["ir"] = []  # the topology pass of the ticks connects who is in range
+w = World(sc["params"])
+S.populate(w, sc)
+n = len(sc["robots"])
+d = DeviceDriver(w, n, a.K, waypoints=[[tuple(rb["goal"])] for rb in sc["robots"]], radii=[rb["radius"] for rb in sc["robots"]],
+                 t0=[rb["t0"] for rb in sc["robots"]], steps=sc["steps"], comms_radius=8.0, target_speed=sc["target_speed"])
+if a.mode == "device":
+    w.collisions_enable(True, method=a.method)
+host = sim.Simulation.__new__(sim.Simulation)
+host.collisions = {}
+robots = [{"id": r, "radius": np.float32(sc["robots"][r]["radius"])} for r in range(n)]
+alive = np.ones(n, bool)
+
+
+def tick():
+    d.next_number, _, _, fin = w.mission_tick_begin(d.comms_radius, d.next_number, despawn_finished=True)
+    if len(fin):
+        alive[np.asarray(fin, dtype=np.int64)] = False
+    if a.mode == "host" and d.tick_no:  # the pass of the tick before, on the Transforms that tick sent behind its launches
+        host._collide([robots[r] for r in np.nonzero(alive_before)[0]], w.mission_translations())
+    w.mission_tick_end(d.steps, d.max_speed, d.delta_t)
+    d.tick_no += 1
+
+
+alive_before = alive.copy()
+rates = []
+for rep in range(a.reps + 1):
+    t0 = time.perf_counter()
+    for _ in range(a.warmup if rep == 0 else a.ticks):
+        tick()
+        alive_before = alive.copy()
+    if a.mode == "device":
+        events, total, dropped, per = w.collisions_read()
+    else:
+        w.synchronize()
+    if rep:
+        rates.append(a.ticks / (time.perf_counter() - t0))
+total = int(w.collisions_read()[1]) if a.mode == "device" else sum(h["times"] for h in host.collisions.values())
+print(json.dumps({"mode": a.mode, "robots": n, "K": a.K, "ticks": a.ticks, "ticks_per_s_median": round(statistics.median(rates), 1),
+                  "ticks_per_s": [round(r, 1) for r in rates], "alive": int(alive.sum()), "collision_events": total,
+                  "last_sweep": list(w.last_sweep())}))
