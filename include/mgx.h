@@ -393,7 +393,7 @@ int mgx_mission_read(mgx_world *w, float *translations, int32_t *targets, int64_
  *   is one collision EVENT, with mins = max(p_a - r_a, p_b - r_b), maxs = min(p_a + r_a, p_b + r_b) per axis (the
  *   intersection of the two balls' AABBs), and counts once for robot a and once for robot b;
  *   a pair that parts, or loses a robot, is Free again.  Events of despawned robots stay in the log.
- * Robot-environment collisions are not computed (parry2d shape queries against the map generator's colliders).
+ * Robot-environment collisions are a pass of their own (mgx_env_collisions_*, below the environment rasteriser).
  * mgx_collisions_enable(w, 1, method, event_capacity): switches the bookkeeping on (default: off — no kernel, no allocation).
  *   method: MGX_NEIGHBOURS_AUTO / _PAIRS / _GRID (all pairs below 512 alive robots, a hash grid of 2 r_max cells above; the same
  *   events either way).  event_capacity (0: 262144) records of log and room for 65536 pairs overlapping at once are allocated
@@ -744,6 +744,92 @@ int mgx_env_to_sdf_image(const mgx_env_desc *env, uint32_t resolution, float exp
  * environment's own sdf settings and install the result as the world's obstacle image, world
  * size = tile_size * (n_cols, n_rows). */
 int mgx_world_set_environment(mgx_world *w, const mgx_env_desc *env);
+
+/* ---- robot-environment collisions: the map's colliders and the pass on the device ---------------------------
+ * update_robot_environment_collisions (planner/collisions.rs:368-438): every robot's Ball against every Collider that
+ * build_tile_grid piped into build_obstacles produced (environment/map_generator.rs:141-514, 537-1293), through the same
+ * Free / Colliding state machine as robot pairs (collisions.rs:455-493); export.rs:190-220, 379, 553 writes the count per
+ * robot and the contacts per (robot, obstacle).
+ *
+ * mgx_env_colliders (host code, no device needed): the colliders in the reference's creation order — the tile cuboids row by
+ *   row, tile by tile, in the order of each tile's vec![..], then the placeable obstacles in list order.  The index in that
+ *   order is the collider's identity everywhere below (it stands in for the reference's mesh Entity).  Everything is computed
+ *   in f32 as map_generator.rs writes it (base_dim, pos_offset with its mul_add, the grid offsets), quirks included: the
+ *   circle's z uses 1 - y and is not negated and its radius is radius * tile_size; the rectangle has w * tile_size / 4,
+ *   h * tile_size / 4 half extents and no rotation; the triangle's points are mirrored in x, rotated by
+ *   Quat::from_rotation_y(pi/2 - rot) and placed under an isometry of angle -rot on top of that; the regular polygon's points
+ *   are rotated by rot + rotation_offset, scaled by tile_size / 2 and placed under an isometry of the same angle again; the
+ *   polygon's points are scaled by tile_size and not rotated.  A Bevy Cuboid::new(x, y, z) becomes a 2-D cuboid of half
+ *   extents (x / 2, z / 2) at (translation.x, translation.z) (the conversion lives in the reference's parry fork;
+ *   tests/test_env_colliders.py pins this reading against the rasteriser).  ConvexPolygon::from_convex_hull and
+ *   Triangle::new become a convex hull computed here (monotone chain: counter-clockwise, collinear points dropped), stored as
+ *   WORLD-space vertices (isometry applied); mins / maxs of a polygon are the bounds of those vertices.
+ *   out [capacity], vertices_xz [vertex_capacity][2]: filled as far as they reach; *n / *n_vertices: the full counts (NULL
+ *   outputs with capacity 0 return the counts; MGX_ERR_INVALID if a non-zero capacity is too small).  An environment the
+ *   rasteriser rejects at any resolution and expansion (empty grid, a value the reference's Percentage /
+ *   StrictlyPositiveFinite / Angle / RelativePoint constructors reject, an unknown shape: one shared validation) returns
+ *   MGX_ERR_INVALID.
+ *
+ * SPECIFICATION OF A CONTACT.  This is the specification, not a claim about parry2d: its query::intersection_test (GJK for
+ *   the polygons) is third party and absent from the reference's tree, so there is nothing to be bit-identical to; the two
+ *   can differ only for centres within rounding of tangency, which nothing available pins.
+ *   A robot is (x, z) = Transform (x, z) and r = (float)desc.radius, alive as the robot-robot pass defines alive.  It touches
+ *   a collider iff the distance from its centre to the closed shape is <= r, in f32 with every operation rounded on its own
+ *   (the same in libmgx.so and libmgx_fma.so):
+ *     ball      dx*dx + dz*dz <= (r + R)*(r + R), d = p - t;
+ *     cuboid    (no rotation) e = max(|p - t| - h, 0) per axis, e_x*e_x + e_z*e_z <= r*r;
+ *     polygon   (world vertices v_0 .. v_{n-1}, counter-clockwise; edge i from a = v_i to b = v_{(i+1) % n}, e = b - a,
+ *               q = p - a) the centre is inside (e_x*q_z - e_z*q_x >= 0 for every edge, and r == r), or the smallest over the
+ *               edges of |q - t e|^2, t = min(max((q_x*e_x + q_z*e_z) / (e_x*e_x + e_z*e_z), 0), 1) (t = 0 for an edge of
+ *               length 0), is <= r*r;
+ *     a NaN anywhere means no contact.
+ *   A contact that was not one after the pass before (or was not looked at: the robot was not alive, or is new) is one
+ *   EVENT {pass, robot, collider, mins, maxs}: mins = max(p - r, collider.mins), maxs = min(p + r, collider.maxs) per axis
+ *   (robot_aabb intersected with Collider::aabb(), collisions.rs:417-426), and counts once for the robot.  A robot that is
+ *   not alive or has a non-finite coordinate is Free of everything.
+ *
+ * mgx_env_collisions_enable(w, env, event_capacity): builds the collider table of `env` and uploads it once, together with a
+ *   uniform grid over the world (a cell is one tile; per cell the colliders whose AABB overlaps it, built on the host: the
+ *   map is static).  event_capacity (0: 262144) records of log are allocated here and never grow.  env == NULL switches off
+ *   and drops the state.  Default: off — no kernel, no allocation, no change to anything else.  Calling it while on is
+ *   MGX_ERR_STATE (switch off first).
+ * While on, every mgx_mission_tick_end (so every mgx_mission_tick and every tick of mgx_mission_run) enqueues one pass on the
+ *   Transforms after that tick's move and the robots alive after that tick's despawns, beside the robot-robot pass: no
+ *   synchronisation, nothing read back.
+ * mgx_env_collisions_update: the same pass over positions the caller keeps ([n_robots][3], x and z are read; NULL: the
+ *   device's mission Transforms as they are).  Enqueued, not waited for.
+ * mgx_env_collisions_read: the one call that synchronises.  events [first, first + capacity) of the log in (pass, robot,
+ *   collider) order, *n_total = events in the log, *dropped = events that found the log full (counted, not stored; the
+ *   per-robot counts include them), per_robot [n_robots] (may be NULL).  The device remembers up to 8 colliders a robot
+ *   touches at the same time; if a robot ever touched more, the call fills its outputs and returns MGX_ERR_STATE (contacts
+ *   beyond the eighth may have been logged again).
+ * mgx_env_collisions_clear: everybody Free, log and counts empty, pass 0.
+ * Unsharded worlds (MGX_ERR_STATE on a world with ghosts); MGX_ERR_STATE from _update / _read / _clear while switched off. */
+#define MGX_COLLIDER_BALL 0
+#define MGX_COLLIDER_CUBOID 1
+#define MGX_COLLIDER_POLYGON 2
+typedef struct mgx_env_collider {
+    int32_t kind;                 /* MGX_COLLIDER_BALL / _CUBOID / _POLYGON (triangles and hulls)            */
+    int32_t tile_row, tile_col;   /* the tile it came from                                                   */
+    int32_t obstacle;             /* index into env->obstacles, -1 for a tile-grid cuboid                    */
+    float   tx, tz, angle;        /* the Isometry2 the reference builds                                      */
+    float   radius;               /* ball                                                                    */
+    float   half_extents[2];      /* cuboid                                                                  */
+    uint32_t first_vertex, n_vertices; /* polygon: WORLD-space vertices (isometry applied), counter-clockwise */
+    float   mins[2], maxs[2];     /* Collider::aabb() in world (x, z)                                        */
+} mgx_env_collider;
+int mgx_env_colliders(const mgx_env_desc *env, mgx_env_collider *out, uint32_t capacity, uint32_t *n,
+                      float *vertices_xz, uint32_t vertex_capacity, uint32_t *n_vertices);
+typedef struct mgx_env_collision_event {
+    uint64_t pass;
+    int32_t robot, collider;
+    float mins[2], maxs[2];       /* (x, z) */
+} mgx_env_collision_event;
+int mgx_env_collisions_enable(mgx_world *w, const mgx_env_desc *env, uint64_t event_capacity);
+int mgx_env_collisions_update(mgx_world *w, const float *positions_xyz);
+int mgx_env_collisions_read(mgx_world *w, uint64_t first, mgx_env_collision_event *events, uint64_t capacity,
+                            uint64_t *n_total, uint64_t *dropped, uint32_t *per_robot);
+int mgx_env_collisions_clear(mgx_world *w);
 
 /* ---- host helpers (no device needed) --------------------------------------------------- */
 /* gbp_schedule: fills steps[max(n_int,n_ext)] with MGX_STEP_* bits. Returns the count

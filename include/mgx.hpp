@@ -77,6 +77,21 @@ inline std::vector<uint32_t> get_variable_timesteps(uint32_t lookahead_horizon, 
     return std::vector<uint32_t>(ts, ts + n);
 }
 
+/// the map's colliders in the reference's creation order (mgx_env_colliders): tile cuboids, then the placeable obstacles
+struct EnvColliders {
+    std::vector<mgx_env_collider> colliders;
+    std::vector<std::array<float, 2>> vertices;  ///< the polygons' world (x, z) vertices, counter-clockwise
+};
+inline EnvColliders env_colliders(const mgx_env_desc &env) {
+    EnvColliders out;
+    uint32_t n = 0, nv = 0;
+    check(mgx_env_colliders(&env, nullptr, 0, &n, nullptr, 0, &nv));
+    out.colliders.resize(n);
+    out.vertices.resize(nv);
+    if (n) check(mgx_env_colliders(&env, out.colliders.data(), n, &n, nv ? out.vertices[0].data() : nullptr, nv, &nv));
+    return out;
+}
+
 class World;
 
 // The reference's `FactorGraph` component: here a handle (world, robot id).  Message routing happens
@@ -226,6 +241,28 @@ public:
         return out;
     }
     void collisions_clear() { check(mgx_collisions_clear(w_)); }
+    /// update_robot_environment_collisions on the device (planner/collisions.rs:368-438) against the colliders of `env`
+    /// (env_colliders above); nullptr switches it off.  `update` / `read` / `clear` as for the robot-robot pass.
+    void env_collisions_enable(const mgx_env_desc *env, uint64_t event_capacity = 0) { check(mgx_env_collisions_enable(w_, env, event_capacity)); }
+    void env_collisions_update(const std::vector<std::array<float, 3>> &translations) {
+        check(mgx_env_collisions_update(w_, translations.empty() ? nullptr : translations[0].data()));  // (empty: the device's Transforms)
+    }
+    struct EnvCollisions {
+        std::vector<mgx_env_collision_event> events;  ///< from `first` on, in (pass, robot, collider) order
+        uint64_t n_total = 0, dropped = 0;
+        std::vector<uint32_t> per_robot;
+    };
+    EnvCollisions env_collisions_read(uint64_t first = 0) {
+        EnvCollisions out;
+        uint32_t n = 0;
+        check(mgx_num_robots(w_, &n, nullptr));
+        out.per_robot.assign(n, 0u);
+        check(mgx_env_collisions_read(w_, first, nullptr, 0, &out.n_total, &out.dropped, nullptr));
+        out.events.resize(out.n_total > first ? (size_t)(out.n_total - first) : 0);
+        check(mgx_env_collisions_read(w_, first, out.events.data(), out.events.size(), &out.n_total, &out.dropped, out.per_robot.data()));
+        return out;
+    }
+    void env_collisions_clear() { check(mgx_env_collisions_clear(w_)); }
     void synchronize() { check(mgx_synchronize(w_)); }
     uint32_t K() const { return K_; }
 

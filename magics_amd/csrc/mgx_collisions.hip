@@ -11,9 +11,8 @@
 //     {pass, a, b, mins, maxs}: the intersection of the two balls' AABBs, mins = max(p - r), maxs = min(p + r) per axis; it
 //     counts once for robot a and once for robot b.
 //   * a pair that parts, or loses a robot, is Free again.
-// Robot-environment collisions are NOT here (exported as 0 / []): they need parry2d's shape queries against the map
-// generator's colliders (environment/map_generator.rs:141-514: quaternion-rotated triangles, convex hulls), and there is no
-// source of those queries to be bit-identical to.  The position / velocity tracker samples stay on the host as well.
+// Robot-environment collisions are the second half of this file (k_env_collisions: its own state, log and calls).  The
+// position / velocity tracker samples stay on the host.
 //
 // STATE (all keyed by robot ID, so nothing moves when the world lays its arrays out again; CollDev, mgx_dev.h):
 //   bits   one bit per ordered pair (a * stride + b): the pair overlapped after the last pass
@@ -226,6 +225,128 @@ hipError_t launch_collisions_pass(const CollDev &c, bool grid, double cell, uint
 }
 hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s) {
     hipLaunchKernelGGL(k_collisions_rebits, dim3(16), dim3(256), 0, s, c);
+    return hipGetLastError();
+}
+
+// ---- robot-environment collisions (update_robot_environment_collisions, collisions.rs:368-438) -----------------------------
+// Every alive robot's ball against the map's colliders (mgx_env_colliders: tile cuboids, then the placeable obstacles), through
+// the same Free / Colliding state machine.  include/mgx.h holds the specification of a contact; sim.py:_collide_environment
+// restates it on the host and is the checker.  The map is static, so everything about it is built on the host once
+// (mgx_env_collisions_enable): the collider records, the polygons' world vertices, and a uniform grid of one cell per tile with
+// a CSR list of the colliders whose AABB overlaps each cell.
+// One lane per robot: it walks the cells its (padded) AABB overlaps, however many; a collider listed in several of them is
+// tested in the first cell the two ranges share and nowhere else.  STATE per robot: ENV_COLL_SLOTS collider ids, the contacts
+// after the last pass (32 bytes, read and rewritten by its own lane only: no atomics, nothing to clear between passes).  A
+// contact that is not among them is a Hit: one 32-byte record under the log's atomic cursor (which keeps counting when the
+// log is full) and one count for the robot.  More simultaneous contacts than slots set the sticky word [1].
+// A few hundred bytes of collider data per lane out of L2, no LDS; the launch is latency, not throughput.
+static_assert(sizeof(mgx_env_collision_event) == 32 && sizeof(EnvCollEvent) == 32, "the log's records are 32 bytes");
+static_assert(offsetof(mgx_env_collision_event, robot) == offsetof(EnvCollEvent, robot) && offsetof(mgx_env_collision_event, collider) == offsetof(EnvCollEvent, collider) &&
+                  offsetof(mgx_env_collision_event, mins) == offsetof(EnvCollEvent, mins) && offsetof(mgx_env_collision_event, maxs) == offsetof(EnvCollEvent, maxs),
+              "EnvCollEvent is the ABI's record");
+static_assert(ENV_COLL_SLOTS == 8, "the slots travel as two int4");
+
+__device__ __forceinline__ float sq_sum(float a, float b) { return __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)); }
+
+// the contact of include/mgx.h: every operation rounded to f32 on its own; a NaN anywhere: false
+__device__ bool env_touches(const EnvCollider &k, const float *__restrict__ verts, float x, float z, float r) {
+    switch (k.kind) {
+    case MGX_COLLIDER_BALL: {
+        const float rs = __fadd_rn(r, k.radius);
+        return sq_sum(__fsub_rn(x, k.tx), __fsub_rn(z, k.tz)) <= __fmul_rn(rs, rs);
+    }
+    case MGX_COLLIDER_CUBOID: {
+        const float dx = __fsub_rn(fabsf(__fsub_rn(x, k.tx)), k.hx), dz = __fsub_rn(fabsf(__fsub_rn(z, k.tz)), k.hz);
+        if (dx != dx || dz != dz) return false;  // (fmaxf below would drop a NaN)
+        return sq_sum(fmaxf(dx, 0.f), fmaxf(dz, 0.f)) <= __fmul_rn(r, r);
+    }
+    case MGX_COLLIDER_POLYGON: {
+        const uint32_t n = k.n_vertices;
+        if (n == 0) return false;
+        const float *v = verts + 2 * (size_t)k.first_vertex;
+        bool inside = n >= 3 && r == r;
+        float best = INFINITY;
+        float ax = v[2 * (n - 1)], az = v[2 * (n - 1) + 1];  // edge n-1 first: v_{n-1} -> v_0
+        for (uint32_t i = 0; i < n; i++) {
+            const float bx = v[2 * i], bz = v[2 * i + 1];
+            const float ex = __fsub_rn(bx, ax), ez = __fsub_rn(bz, az), qx = __fsub_rn(x, ax), qz = __fsub_rn(z, az);
+            inside = inside && (__fsub_rn(__fmul_rn(ex, qz), __fmul_rn(ez, qx)) >= 0.f);
+            const float len2 = sq_sum(ex, ez);
+            float t = len2 == 0.f ? 0.f : __fdiv_rn(__fadd_rn(__fmul_rn(qx, ex), __fmul_rn(qz, ez)), len2);
+            if (t != t) return false;
+            t = fminf(fmaxf(t, 0.f), 1.f);
+            const float d2 = sq_sum(__fsub_rn(qx, __fmul_rn(t, ex)), __fsub_rn(qz, __fmul_rn(t, ez)));
+            if (d2 != d2) return false;
+            best = fminf(best, d2);
+            ax = bx; az = bz;
+        }
+        return inside || best <= __fmul_rn(r, r);
+    }
+    default: return false;
+    }
+}
+
+__device__ __forceinline__ int env_cell_of(double v, double origin, double inv_cell, int n) {  // monotone, clamped into the grid
+    const double c = floor((v - origin) * inv_cell);
+    return (int)fmin(fmax(c, 0.0), (double)(n - 1));
+}
+
+__global__ void __launch_bounds__(64) k_env_collisions(EnvCollDev c) {
+    const int i = (int)(blockIdx.x * 64 + threadIdx.x);
+    if (i >= c.n) return;
+    int4 *slots = reinterpret_cast<int4 *>(c.touching + (size_t)ENV_COLL_SLOTS * i);
+    const int4 o0 = slots[0], o1 = slots[1];
+    const int32_t old[ENV_COLL_SLOTS] = {o0.x, o0.y, o0.z, o0.w, o1.x, o1.y, o1.z, o1.w};
+    int32_t cur[ENV_COLL_SLOTS] = {-1, -1, -1, -1, -1, -1, -1, -1};
+    int n_cur = 0;
+    const float x = c.pos[3 * i], z = c.pos[3 * i + 2], r = c.radius[i];
+    if (c.alive[i] != 0 && isfinite(x) && isfinite(z) && r == r && c.n_colliders > 0) {
+        const double reach = (double)fabsf(r) * 1.001 + c.pad;
+        const int rx0 = env_cell_of((double)x - reach, c.x0, c.inv_cell, c.n_cx), rx1 = env_cell_of((double)x + reach, c.x0, c.inv_cell, c.n_cx);
+        const int rz0 = env_cell_of((double)z - reach, c.z0, c.inv_cell, c.n_cz), rz1 = env_cell_of((double)z + reach, c.z0, c.inv_cell, c.n_cz);
+        for (int cz = rz0; cz <= rz1; cz++)
+            for (int cx = rx0; cx <= rx1; cx++) {
+                const uint32_t cell = (uint32_t)cz * (uint32_t)c.n_cx + (uint32_t)cx;
+                for (uint32_t q = c.cell_ptr[cell], q1 = c.cell_ptr[cell + 1]; q < q1; q++) {
+                    const int32_t ki = c.cell_idx[q];
+                    const EnvCollider &k = c.colliders[ki];
+                    if (cx != max(rx0, k.cx0) || cz != max(rz0, k.cz0)) continue;  // met in an earlier cell, or will be
+                    if (!env_touches(k, c.verts, x, z, r)) continue;
+                    bool was = false;
+#pragma unroll
+                    for (int s = 0; s < ENV_COLL_SLOTS; s++) was = was || old[s] == ki;
+                    if (n_cur < ENV_COLL_SLOTS) {
+#pragma unroll
+                        for (int s = 0; s < ENV_COLL_SLOTS; s++)
+                            if (s == n_cur) cur[s] = ki;
+                        n_cur++;
+                    } else {
+                        atomicOr(&c.words[1], 1ull);
+                    }
+                    if (was) continue;  // Colliding -> Colliding
+                    const unsigned long long e = atomicAdd(&c.words[0], 1ull);
+                    if (e < c.log_cap) {
+                        EnvCollEvent ev;
+                        ev.pass = c.pass;
+                        ev.robot = i;
+                        ev.collider = ki;
+                        ev.mins[0] = fmaxf(__fsub_rn(x, r), k.mins[0]);
+                        ev.mins[1] = fmaxf(__fsub_rn(z, r), k.mins[1]);
+                        ev.maxs[0] = fminf(__fadd_rn(x, r), k.maxs[0]);
+                        ev.maxs[1] = fminf(__fadd_rn(z, r), k.maxs[1]);
+                        c.log[e] = ev;
+                    }
+                    c.per_robot[i] += 1u;  // (this lane's own word)
+                }
+            }
+    }
+    slots[0] = make_int4(cur[0], cur[1], cur[2], cur[3]);
+    slots[1] = make_int4(cur[4], cur[5], cur[6], cur[7]);
+}
+
+hipError_t launch_env_collisions_pass(const EnvCollDev &c, hipStream_t s) {
+    if (c.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_env_collisions, dim3((unsigned)((c.n + 63) / 64)), dim3(64), 0, s, c);
     return hipGetLastError();
 }
 

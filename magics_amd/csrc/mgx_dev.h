@@ -274,6 +274,43 @@ struct CollDev {
     unsigned long long pass;
 };
 
+// Robot-environment collision bookkeeping on the device (mgx_collisions.hip, second half): the map's colliders as the pass reads
+// them, and what one pass is handed.  Per-robot arrays are indexed by robot id.
+struct EnvCollider {
+    int32_t kind;              // MGX_COLLIDER_*
+    uint32_t first_vertex, n_vertices;  // polygon: world (x, z) pairs in `verts`, counter-clockwise
+    float radius;              // ball
+    float tx, tz, hx, hz;      // centre; cuboid half extents
+    float mins[2], maxs[2];    // Collider::aabb()
+    int32_t cx0, cz0, cx1, cz1;  // the cells its AABB overlaps (inclusive): a collider met in several cells counts in the first
+};
+struct EnvCollEvent {  // == mgx_env_collision_event (include/mgx.h; mgx_collisions.hip asserts it)
+    unsigned long long pass;
+    int32_t robot, collider;
+    float mins[2], maxs[2];
+};
+constexpr int ENV_COLL_SLOTS = 8;  // colliders a robot is remembered to touch at the same time
+struct EnvCollDev {
+    const float *pos;          // [n][3] Transform::translation (x, height, z)
+    const uint8_t *alive;      // [n] not removed, not a ghost
+    const float *radius;       // [n] (float)desc.radius
+    int n;                     // robots of the world (ids 0 .. n-1)
+    int n_colliders;
+    const EnvCollider *colliders;
+    const float *verts;
+    const uint32_t *cell_ptr;  // [n_cx * n_cz + 1] CSR over cells (cz * n_cx + cx)
+    const int32_t *cell_idx;   // collider indices
+    int n_cx, n_cz;            // a cell is one tile
+    double x0, z0, inv_cell;   // cell of a coordinate: floor((v - origin) * inv_cell), clamped into the grid
+    double pad;                // added to a robot's radius when its cells are chosen (covers the roundings of the f32 predicate)
+    int32_t *touching;         // [n][ENV_COLL_SLOTS] colliders touched after the last pass, -1: free slot
+    EnvCollEvent *log;         // [log_cap]
+    unsigned long long log_cap;
+    unsigned long long *words;  // [0] log cursor (keeps counting beyond log_cap), [1] sticky: a robot touched more than the slots hold
+    uint32_t *per_robot;       // [n] contacts of every robot
+    unsigned long long pass;
+};
+
 __host__ __device__ constexpr int frozen_words(int K) { return 40 * (K - 1) + 8 * (K - 2); }
 
 // phases of one launch

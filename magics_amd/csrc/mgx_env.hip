@@ -19,6 +19,7 @@
 // row once per tap through L2.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -265,6 +266,38 @@ namespace {
 bool percentage_ok(float v) { return v >= 0.0f && v <= 1.0f; }  // Percentage::new (lib.rs:52-57)
 bool spf(double v) { return v > 0.0 && std::isfinite(v); }      // StrictlyPositiveFinite
 
+// What is wrong with an ENVIRONMENT whatever the resolution or the expansion: the one validation env_red_plane and
+// mgx_env_colliders share (the rasteriser adds what depends on its own arguments: resolution, expansion, blur)
+int env_check(const mgx_env_desc *d) {
+    if (!d || !d->tiles || !d->n_rows || !d->n_cols) return env_fail(MGX_ERR_INVALID, "EmptyGrid: environment matrix representation is empty");
+    if (d->n_obstacles && !d->obstacles) return env_fail(MGX_ERR_INVALID, "null obstacle list");
+    if (!percentage_ok(d->path_width)) return env_fail(MGX_ERR_INVALID, "percentage outside [0, 1]");
+    for (uint32_t q = 0; q < d->n_obstacles; q++) {
+        const mgx_env_obstacle &in = d->obstacles[q];
+        if (!(in.translation_x >= 0.0 && in.translation_x <= 1.0 && in.translation_y >= 0.0 && in.translation_y <= 1.0))
+            return env_fail(MGX_ERR_INVALID, "obstacle %u: Invalid relative point", q);
+        if (!(in.rotation >= 0.0 && in.rotation <= 2.0 * 3.14159265358979323846))
+            return env_fail(MGX_ERR_INVALID, "obstacle %u: Angle value %g is not inside [0,2pi]", q, in.rotation);
+        switch (in.shape) {
+        case MGX_SHAPE_CIRCLE:
+        case MGX_SHAPE_TRIANGLE:
+            if (!spf(in.radius)) return env_fail(MGX_ERR_INVALID, "obstacle %u: radius must be strictly positive and finite", q);
+            break;
+        case MGX_SHAPE_REGULAR_POLYGON:
+            if (!spf(in.radius) || in.sides < 1) return env_fail(MGX_ERR_INVALID, "obstacle %u: bad regular polygon", q);
+            break;
+        case MGX_SHAPE_RECTANGLE:
+            if (!spf(in.width) || !spf(in.height)) return env_fail(MGX_ERR_INVALID, "obstacle %u: width / height must be strictly positive and finite", q);
+            break;
+        case MGX_SHAPE_POLYGON:
+            if (!in.n_points || !in.points_xy) return env_fail(MGX_ERR_INVALID, "obstacle %u: polygon without points", q);
+            break;
+        default: return env_fail(MGX_ERR_INVALID, "obstacle %u: unknown shape %d", q, in.shape);
+        }
+    }
+    return MGX_OK;
+}
+
 // image::imageops::sample::gaussian
 float gaussian(float x, float r) { return 1.0f / (sqrtf(2.0f * 3.14159265358979323846f) * r) * expf(-(x * x) / (2.0f * (r * r))); }
 
@@ -312,8 +345,7 @@ struct Dev {
 // Rasterises (and blurs when blur_percent * resolution >= 1) on stream `s`; returns the red plane.
 int env_red_plane(const mgx_env_desc *d, uint32_t resolution, float expansion, float blur_percent, bool with_blur, hipStream_t s,
                   std::vector<uint8_t> &red, uint32_t &W, uint32_t &H) {
-    if (!d || !d->tiles || !d->n_rows || !d->n_cols) return env_fail(MGX_ERR_INVALID, "EmptyGrid: environment matrix representation is empty");
-    if (d->n_obstacles && !d->obstacles) return env_fail(MGX_ERR_INVALID, "null obstacle list");
+    if (const int rc = env_check(d)) return rc;
     if (!resolution) return env_fail(MGX_ERR_INVALID, "Pixels per tile must be non-zero");
     if (!percentage_ok(expansion) || !percentage_ok(d->path_width) || (with_blur && !percentage_ok(blur_percent)))
         return env_fail(MGX_ERR_INVALID, "percentage outside [0, 1]");
@@ -348,10 +380,6 @@ int env_red_plane(const mgx_env_desc *d, uint32_t resolution, float expansion, f
         const mgx_env_obstacle &in = d->obstacles[q];
         EnvObstacle o{};
         o.kind = in.shape; o.row = in.tile_row; o.col = in.tile_col;
-        if (!(in.translation_x >= 0.0 && in.translation_x <= 1.0 && in.translation_y >= 0.0 && in.translation_y <= 1.0))
-            return env_fail(MGX_ERR_INVALID, "obstacle %u: Invalid relative point", q);
-        if (!(in.rotation >= 0.0 && in.rotation <= 2.0 * 3.14159265358979323846))
-            return env_fail(MGX_ERR_INVALID, "obstacle %u: Angle value %g is not inside [0,2pi]", q, in.rotation);
         o.tx = (float)in.translation_x; o.ty = (float)in.translation_y;
         float offset = HALF_PI32;  // lib.rs:299-312
         switch (in.shape) {
@@ -392,7 +420,6 @@ int env_red_plane(const mgx_env_desc *d, uint32_t resolution, float expansion, f
             break;
         }
         case MGX_SHAPE_POLYGON: {  // Polygon::expanded (lib.rs:352-380)
-            if (!in.n_points || !in.points_xy) return env_fail(MGX_ERR_INVALID, "obstacle %u: polygon without points", q);
             double ax = 0.0, ay = 0.0;
             for (uint32_t i = 0; i < in.n_points; i++) { ax = ax + in.points_xy[2 * i]; ay = ay + in.points_xy[2 * i + 1]; }
             const double cx = ax / (double)in.n_points, cy = ay / (double)in.n_points;
@@ -469,9 +496,200 @@ int env_red_plane(const mgx_env_desc *d, uint32_t resolution, float expansion, f
     return MGX_OK;
 }
 
+// ---- the map's colliders (host code, no device needed) ------------------------------------------
+// build_tile_grid piped into build_obstacles (crates/magics/src/environment/map_generator.rs:537-1293, 141-514) as plain data:
+// what update_robot_environment_collisions (planner/collisions.rs:368-438) tests every robot against.  f32 arithmetic as the
+// reference writes it (this file never contracts; its mul_add is fmaf); include/mgx.h says what is restated and how.
+namespace {
+
+struct P2 { float x, y; };
+
+// Andrew's monotone chain: counter-clockwise, collinear points dropped (the cross products of f32 points in f64)
+std::vector<P2> convex_hull(std::vector<P2> pts) {
+    std::sort(pts.begin(), pts.end(), [](const P2 &a, const P2 &b) { return a.x < b.x || (a.x == b.x && a.y < b.y); });
+    pts.erase(std::unique(pts.begin(), pts.end(), [](const P2 &a, const P2 &b) { return a.x == b.x && a.y == b.y; }), pts.end());
+    const size_t n = pts.size();
+    if (n < 3) return pts;
+    auto cross = [](const P2 &o, const P2 &a, const P2 &b) {
+        return ((double)a.x - o.x) * ((double)b.y - o.y) - ((double)a.y - o.y) * ((double)b.x - o.x);
+    };
+    std::vector<P2> h(2 * n);
+    size_t k = 0;
+    for (size_t i = 0; i < n; i++) {
+        while (k >= 2 && cross(h[k - 2], h[k - 1], pts[i]) <= 0.0) k--;
+        h[k++] = pts[i];
+    }
+    for (size_t i = n - 1, t = k + 1; i-- > 0;) {
+        while (k >= t && cross(h[k - 2], h[k - 1], pts[i]) <= 0.0) k--;
+        h[k++] = pts[i];
+    }
+    h.resize(k - 1);
+    return h;
+}
+
+struct ColliderList {
+    std::vector<mgx_env_collider> c;
+    std::vector<float> v;  // world (x, z) pairs
+    mgx_env_collider &push(int32_t kind, int32_t row, int32_t col, int32_t obstacle, float tx, float tz, float angle) {
+        mgx_env_collider e{};
+        e.kind = kind; e.tile_row = row; e.tile_col = col; e.obstacle = obstacle;
+        e.tx = tx; e.tz = tz; e.angle = angle;
+        c.push_back(e);
+        return c.back();
+    }
+    // Bevy Cuboid::new(x, _, z) at Transform (tx, _, tz): half extents (x / 2, z / 2), no rotation
+    void cuboid(int32_t row, int32_t col, int32_t obstacle, float hx, float hz, float tx, float tz) {
+        mgx_env_collider &e = push(MGX_COLLIDER_CUBOID, row, col, obstacle, tx, tz, 0.0f);
+        e.half_extents[0] = hx; e.half_extents[1] = hz;
+        e.mins[0] = tx - hx; e.mins[1] = tz - hz;
+        e.maxs[0] = tx + hx; e.maxs[1] = tz + hz;
+    }
+    // local points -> hull -> Isometry2::new((tx, tz), angle) * p (nalgebra UnitComplex: (re x - im y, im x + re y) + t)
+    void polygon(int32_t row, int32_t col, int32_t obstacle, const std::vector<P2> &local, float tx, float tz, float angle) {
+        const std::vector<P2> h = convex_hull(local);
+        mgx_env_collider &e = push(MGX_COLLIDER_POLYGON, row, col, obstacle, tx, tz, angle);
+        e.first_vertex = (uint32_t)(v.size() / 2);
+        e.n_vertices = (uint32_t)h.size();
+        const float re = cosf(angle), im = sinf(angle);
+        for (size_t i = 0; i < h.size(); i++) {
+            const float wx = (re * h[i].x - im * h[i].y) + tx, wz = (im * h[i].x + re * h[i].y) + tz;
+            v.push_back(wx); v.push_back(wz);
+            if (i == 0) { e.mins[0] = e.maxs[0] = wx; e.mins[1] = e.maxs[1] = wz; }
+            e.mins[0] = std::min(e.mins[0], wx); e.maxs[0] = std::max(e.maxs[0], wx);
+            e.mins[1] = std::min(e.mins[1], wz); e.maxs[1] = std::max(e.maxs[1], wz);
+        }
+    }
+};
+
+// build_tile_grid (map_generator.rs:537-1293)
+void tile_colliders(const mgx_env_desc *d, ColliderList &L) {
+    const float ts = d->tile_size, pw = d->path_width;
+    const float base_dim = ts * (1.0f - pw) / 2.0f;                // :559
+    const float gox = (float)d->n_cols / 2.0f - 0.5f;              // :563
+    const float goz = -((float)d->n_rows / 2.0f - 0.5f);           // :564
+    const float po = fmaf(pw, ts, base_dim) / 2.0f;                // :566
+    const float full = ts / 2.0f, base = base_dim / 2.0f;          // half extents of tile_size / base_dim
+    const float plug_long = (ts / 2.0f) / 2.0f, plug_wide = (pw * ts) / 2.0f, quarter = ts / 4.0f;
+    for (uint32_t y = 0; y < d->n_rows; y++)
+        for (uint32_t x = 0; x < d->n_cols; x++) {
+            const float ox = ((float)x - gox) * ts, oz = (-(float)y - goz) * ts;  // :574-579
+            const int32_t r = (int32_t)y, c = (int32_t)x;
+            auto wide = [&](float tz) { L.cuboid(r, c, -1, full, base, ox, tz); };   // Cuboid::new(tile_size, _, base_dim)
+            auto tall = [&](float tx) { L.cuboid(r, c, -1, base, full, tx, oz); };   // Cuboid::new(base_dim, _, tile_size)
+            auto cube = [&](float tx, float tz) { L.cuboid(r, c, -1, base, base, tx, tz); };
+            switch (d->tiles[y * d->n_cols + x]) {
+            case 0x2500: case '-': wide(oz - po); wide(oz + po); break;                                             // ─ :582-614
+            case 0x2502: case '|': tall(ox - po); tall(ox + po); break;                                             // │ :615-648
+            case 0x2574: wide(oz - po); wide(oz + po); L.cuboid(r, c, -1, plug_long, plug_wide, ox + quarter, oz); break;  // ╴ :649-699
+            case 0x2576: wide(oz - po); wide(oz + po); L.cuboid(r, c, -1, plug_long, plug_wide, ox - quarter, oz); break;  // ╶ :700-750
+            case 0x2577: tall(ox - po); tall(ox + po); L.cuboid(r, c, -1, plug_wide, plug_long, ox, oz + quarter); break;  // ╷ :751-801
+            case 0x2575: tall(ox - po); tall(ox + po); L.cuboid(r, c, -1, plug_wide, plug_long, ox, oz - quarter); break;  // ╵ :802-852
+            case 0x250C: cube(ox + po, oz - po); tall(ox - po); wide(oz + po); break;                               // ┌ :853-897
+            case 0x2510: cube(ox - po, oz - po); tall(ox + po); wide(oz + po); break;                               // ┐ :898-941
+            case 0x2514: cube(ox + po, oz + po); tall(ox - po); wide(oz - po); break;                               // └ :942-986
+            case 0x2518: cube(ox - po, oz + po); tall(ox + po); wide(oz - po); break;                               // ┘ :987-1031
+            case 0x252C: cube(ox - po, oz - po); cube(ox + po, oz - po); wide(oz + po); break;                      // ┬ :1032-1072
+            case 0x2534: cube(ox - po, oz + po); cube(ox + po, oz + po); wide(oz - po); break;                      // ┴ :1073-1113
+            case 0x251C: cube(ox + po, oz - po); cube(ox + po, oz + po); tall(ox - po); break;                      // ├ :1114-1154
+            case 0x2524: cube(ox - po, oz - po); cube(ox - po, oz + po); tall(ox + po); break;                      // ┤ :1155-1195
+            case 0x253C: cube(ox - po, oz - po); cube(ox + po, oz - po); cube(ox - po, oz + po); cube(ox + po, oz + po); break;  // ┼ :1196-1244
+            case 0x20: L.cuboid(r, c, -1, full, full, ox, oz); break;                                               // ' ' :1245-1255
+            default: break;                                                                                         // _ => None
+            }
+        }
+}
+
+// build_obstacles (map_generator.rs:141-514)
+void obstacle_colliders(const mgx_env_desc *d, ColliderList &L) {
+    const float ts = d->tile_size;
+    const float PI32 = 3.14159265358979323846f, HALF_PI32 = 1.57079632679489661923f;
+    const float gox = (float)d->n_cols / 2.0f - 0.5f, goz = (float)d->n_rows / 2.0f - 0.5f;  // :154-155
+    for (uint32_t q = 0; q < d->n_obstacles; q++) {
+        const mgx_env_obstacle &in = d->obstacles[q];
+        const int32_t row = in.tile_row, col = in.tile_col, ix = (int32_t)q;
+        const float ox = ((float)col - gox) * ts, oz = ((float)row - goz) * ts;  // :169-173
+        const float po = ts / 2.0f;                                             // :175
+        const float tx = (float)in.translation_x, ty = (float)in.translation_y, rot = (float)in.rotation;
+        const float cx = fmaf(tx, ts, ox) - po;
+        const float cz_neg = -(fmaf(ty, ts, oz) - po);  // triangle, regular polygon, rectangle
+        switch (in.shape) {
+        case MGX_SHAPE_CIRCLE: {  // :181-208
+            const float cz = fmaf(1.0f - ty, ts, oz) - po, radius = (float)in.radius * ts;
+            mgx_env_collider &e = L.push(MGX_COLLIDER_BALL, row, col, ix, cx, cz, 0.0f);
+            e.radius = radius;
+            e.mins[0] = cx - radius; e.mins[1] = cz - radius;
+            e.maxs[0] = cx + radius; e.maxs[1] = cz + radius;
+            break;
+        }
+        case MGX_SHAPE_TRIANGLE: {  // :209-276, Triangle::points (gbp_environment lib.rs:192-210)
+            const float a = (float)in.angle_a, b = (float)in.angle_b, c = PI32 - (a + b), r = (float)in.radius;
+            const float hyp[3] = {r / sinf(a), r / sinf(b), r / sinf(c)};
+            const float ang[3] = {PI32 + a / 2.0f, -b / 2.0f, PI32 - b - c / 2.0f};
+            const float rotation_angle = HALF_PI32 - rot;              // :253-254
+            const float hs = sinf(rotation_angle * 0.5f), hc = cosf(rotation_angle * 0.5f), k = hc * hc - hs * hs;
+            std::vector<P2> pts;
+            for (int v = 0; v < 3; v++) {
+                const float px = -(cosf(ang[v]) * hyp[v]) * ts, py = (sinf(ang[v]) * hyp[v]) * ts;  // :227-229
+                // glam Quat::from_rotation_y(a).mul_vec3((px, 0, py)).xz(): v (w w - b.b) + b (2 v.b) + (w (b x v)) 2, b = (0, s, 0)
+                pts.push_back({px * k + (hc * (hs * py)) * 2.0f, py * k + (hc * (0.0f - hs * px)) * 2.0f});
+            }
+            L.polygon(row, col, ix, pts, cx, cz_neg, rotation_angle - HALF_PI32);  // :257-260
+            break;
+        }
+        case MGX_SHAPE_REGULAR_POLYGON: {  // :277-379, RegularPolygon::points (lib.rs:271-294)
+            const float rotation_offset = PI32 + (in.sides == 4 ? 0.0f : (in.sides % 2 != 0 ? HALF_PI32 : -HALF_PI32));  // :323-328
+            const float rotation_angle = rot + rotation_offset;        // :342
+            const float hs = sinf(rotation_angle * 0.5f), hc = cosf(rotation_angle * 0.5f), k = hc * hc - hs * hs;
+            const float scale = ts / 2.0f;
+            std::vector<P2> pts;
+            for (uint32_t i = 0; i < in.sides; i++) {
+                const double angle = 2.0 * 3.14159265358979323846 / (double)in.sides * (double)i + 0.78539816339744830962;
+                const float px = (float)(cos(angle) * in.radius), py = (float)(sin(angle) * in.radius);
+                // Quat::from_rotation_z(a).mul_vec3((px, py, 0)), b = (0, 0, s)
+                const float rx = px * k + (hc * (0.0f - hs * py)) * 2.0f, ry = py * k + (hc * (hs * px)) * 2.0f;
+                pts.push_back({rx * scale, ry * scale});
+            }
+            L.polygon(row, col, ix, pts, cx, cz_neg, rotation_angle);  // :373-376
+            break;
+        }
+        case MGX_SHAPE_POLYGON: {  // :380-429
+            const float cz = fmaf(ty, ts, oz) - po;
+            std::vector<P2> pts;
+            for (uint32_t i = 0; i < in.n_points; i++) pts.push_back({(float)in.points_xy[2 * i] * ts, (float)in.points_xy[2 * i + 1] * ts});
+            L.polygon(row, col, ix, pts, cx, cz, 0.0f);
+            break;
+        }
+        case MGX_SHAPE_RECTANGLE:  // :430-477
+            L.cuboid(row, col, ix, (float)in.width * ts / 4.0f, (float)in.height * ts / 4.0f, cx, cz_neg);
+            break;
+        default: break;
+        }
+    }
+}
+
+}  // namespace
+
 }  // namespace mgx
 
 extern "C" {
+
+int mgx_env_colliders(const mgx_env_desc *env, mgx_env_collider *out, uint32_t capacity, uint32_t *n, float *vertices_xz, uint32_t vertex_capacity,
+                      uint32_t *n_vertices) {
+    const int rc = mgx::env_check(env);
+    if (rc != MGX_OK) return rc;
+    if ((!out && capacity) || (!vertices_xz && vertex_capacity)) return mgx::env_fail(MGX_ERR_INVALID, "null output with a capacity");
+    mgx::ColliderList L;
+    mgx::tile_colliders(env, L);
+    mgx::obstacle_colliders(env, L);
+    if (n) *n = (uint32_t)L.c.size();
+    if (n_vertices) *n_vertices = (uint32_t)(L.v.size() / 2);
+    if (!capacity && !vertex_capacity) return MGX_OK;  // the capacity query
+    if (capacity < L.c.size() || vertex_capacity < L.v.size() / 2)
+        return mgx::env_fail(MGX_ERR_INVALID, "room for %u colliders and %u vertices, the environment has %zu and %zu", capacity, vertex_capacity, L.c.size(), L.v.size() / 2);
+    std::copy(L.c.begin(), L.c.end(), out);
+    std::copy(L.v.begin(), L.v.end(), vertices_xz);
+    return MGX_OK;
+}
 
 int mgx_env_image_size(const mgx_env_desc *env, uint32_t resolution, uint32_t *width, uint32_t *height) {
     if (!env || !width || !height || !resolution) return mgx::env_fail(MGX_ERR_INVALID, "bad arguments");

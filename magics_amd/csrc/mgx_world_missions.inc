@@ -229,6 +229,8 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     // update_robot_robot_collisions (collisions.rs:72-140) on the Transforms after this tick's move and the robots alive after its
     // despawns: enqueued here, in front of the schedule's launches — no synchronisation, nothing read back (mgx_collisions_read)
     if (w->coll.enabled && (rc = collisions_pass(w, ms.translation_d.p, ms.moving_d.p, s)) != MGX_OK) return rc;
+    // update_robot_environment_collisions (collisions.rs:368-438), beside it on the same stream (mgx_env_collisions_read)
+    if (w->envcoll.enabled && (rc = env_collisions_pass(w, ms.translation_d.p, ms.moving_d.p, s)) != MGX_OK) return rc;
     // the Transforms after this tick's move travel to the host behind the launch: complete at the next synchronisation
     // (the next tick's own one), read without one by mgx_mission_translations
     if (ms.tr_cap < (size_t)R) {

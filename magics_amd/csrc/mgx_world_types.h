@@ -78,6 +78,7 @@ int32_t neighbours_changed_bit();
 // mgx_collisions.hip
 hipError_t launch_collisions_pass(const CollDev &c, bool grid, double cell, uint32_t n_buckets, hipStream_t s);
 hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s);
+hipError_t launch_env_collisions_pass(const EnvCollDev &c, hipStream_t s);
 }  // namespace mgx
 
 using namespace mgx;
@@ -635,6 +636,22 @@ struct mgx_world {
         std::vector<mgx_collision_event> host_log;  // the events fetched so far, in (pass, robot_a, robot_b) order
         CollDev d{};
     } coll;
+    // robot-environment collision bookkeeping on the device (mgx_env_collisions_*, mgx_collisions.hip): the map's side is uploaded
+    // once by _enable; the per-robot arrays are keyed by robot id and only grow
+    struct EnvCollisions {
+        bool enabled = false;
+        size_t n_sized = 0;      // robots the per-robot arrays were last sized and the radii uploaded for
+        DevBuf<EnvCollider> colliders;
+        DevBuf<float> verts, radius, pos;  // pos: positions the caller handed in (mgx_env_collisions_update)
+        DevBuf<uint32_t> cell_ptr, per_robot;
+        DevBuf<int32_t> cell_idx, touching;
+        DevBuf<EnvCollEvent> log;
+        DevBuf<unsigned long long> words;
+        DevBuf<uint8_t> alive;
+        uint64_t log_cap = 0, pass = 0;
+        std::vector<mgx_env_collision_event> host_log;  // the events fetched so far, in (pass, robot, collider) order
+        EnvCollDev d{};
+    } envcoll;
     // a neighbour search that has been enqueued and not collected yet (neighbours_enqueue / neighbours_collect)
     struct PendingSearch {
         hipStream_t stream = nullptr;  // where it was enqueued

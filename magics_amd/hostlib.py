@@ -115,6 +115,11 @@ SYMBOLS = {
     "mgx_env_to_image": (C.c_int, [C.POINTER(EnvDesc), C.c_uint32, C.c_float, C.c_void_p]),
     "mgx_env_to_sdf_image": (C.c_int, [C.POINTER(EnvDesc), C.c_uint32, C.c_float, C.c_float, C.c_void_p]),
     "mgx_world_set_environment": (C.c_int, [_V, C.POINTER(EnvDesc)]),
+    "mgx_env_colliders": (C.c_int, [C.POINTER(EnvDesc), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "mgx_env_collisions_enable": (C.c_int, [_V, C.POINTER(EnvDesc), C.c_uint64]),
+    "mgx_env_collisions_update": (C.c_int, [_V, C.c_void_p]),
+    "mgx_env_collisions_read": (C.c_int, [_V, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    "mgx_env_collisions_clear": (C.c_int, [_V]),
     "mgx_robot_add": (C.c_int, [_V, C.POINTER(RobotDesc), C.POINTER(C.c_int32)]),
     "mgx_robot_remove": (C.c_int, [_V, C.c_int32]),
     "mgx_ir_connect": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_uint64]),
@@ -356,6 +361,51 @@ def collision_event_dtype():
     """numpy view of an array of mgx_collision_event"""
     import numpy as np
     return np.dtype([("pass", np.uint64), ("robot_a", np.int32), ("robot_b", np.int32), ("mins", np.float32, 2), ("maxs", np.float32, 2)])
+
+
+COLLIDER_BALL, COLLIDER_CUBOID, COLLIDER_POLYGON = 0, 1, 2
+
+
+class EnvCollider(C.Structure):
+    """mgx_env_collider (include/mgx.h)"""
+    _fields_ = [("kind", C.c_int32), ("tile_row", C.c_int32), ("tile_col", C.c_int32), ("obstacle", C.c_int32), ("tx", C.c_float),
+                ("tz", C.c_float), ("angle", C.c_float), ("radius", C.c_float), ("half_extents", C.c_float * 2), ("first_vertex", C.c_uint32),
+                ("n_vertices", C.c_uint32), ("mins", C.c_float * 2), ("maxs", C.c_float * 2)]
+
+
+def env_collider_dtype():
+    """numpy view of an array of mgx_env_collider"""
+    import numpy as np
+    return np.dtype([("kind", np.int32), ("tile_row", np.int32), ("tile_col", np.int32), ("obstacle", np.int32), ("tx", np.float32),
+                     ("tz", np.float32), ("angle", np.float32), ("radius", np.float32), ("half_extents", np.float32, 2),
+                     ("first_vertex", np.uint32), ("n_vertices", np.uint32), ("mins", np.float32, 2), ("maxs", np.float32, 2)])
+
+
+class EnvCollisionEvent(C.Structure):
+    """mgx_env_collision_event (include/mgx.h)"""
+    _fields_ = [("pass_", C.c_uint64), ("robot", C.c_int32), ("collider", C.c_int32), ("mins", C.c_float * 2), ("maxs", C.c_float * 2)]
+
+
+def env_collision_event_dtype():
+    """numpy view of an array of mgx_env_collision_event"""
+    import numpy as np
+    return np.dtype([("pass", np.uint64), ("robot", np.int32), ("collider", np.int32), ("mins", np.float32, 2), ("maxs", np.float32, 2)])
+
+
+def env_colliders(env, fma=None):
+    """mgx_env_colliders: the map's colliders in the reference's creation order (tile cuboids, then the placeable obstacles) as
+    a structured array (env_collider_dtype) and the polygons' world vertices [n, 2] f32 (x, z).  env: an environment dict
+    (magics_amd.environment).  Host code: needs no device."""
+    import numpy as np
+    from .environment import _Desc
+    L = lib(fma)
+    d = _Desc(env)
+    n, nv = C.c_uint32(), C.c_uint32()
+    check(L.mgx_env_colliders(C.byref(d.desc), None, 0, C.byref(n), None, 0, C.byref(nv)), L)
+    cols, verts = np.zeros(n.value, env_collider_dtype()), np.zeros((nv.value, 2), np.float32)
+    if n.value:
+        check(L.mgx_env_colliders(C.byref(d.desc), cols.ctypes.data, n.value, C.byref(n), verts.ctypes.data, nv.value, C.byref(nv)), L)
+    return cols, verts
 
 
 def shard_partition(positions_xy, n_ranks):

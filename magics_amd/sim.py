@@ -13,8 +13,10 @@ by the frame's Update systems that matter to the path (the formation spawners):
 
 The reference runs its Update systems at the display's frame rate against virtual time, so the
 interleaving of spawns with fixed ticks is not reproducible there; here a frame is exactly one
-fixed tick long.  Rendering, picking, RRT* planning (`planning-strategy: rrt-star` is rejected),
-robot-environment collision bookkeeping with parry2d and goal areas are outside the path (SURVEY §8 out of scope).
+fixed tick long.  Rendering, picking, RRT* planning (`planning-strategy: rrt-star` is rejected) and goal areas are outside
+the path (SURVEY §8 out of scope).  Robot-environment collisions (planner/collisions.rs:368-438) are counted on request
+(`environment_collisions=True`) against the map's colliders (hostlib.env_colliders) with the contact include/mgx.h
+specifies: parry2d's own shape queries are third party and absent, so contacts within rounding of tangency are not pinned.
 """
 import json
 
@@ -29,8 +31,45 @@ from .scenarios import robot_initial_state
 F = np.float32
 
 
+def environment_contacts(colliders, vertices, pos, rad):
+    """The contact of include/mgx.h ("specification of a contact") in numpy f32, every operation rounded on its own: [n, m] bool,
+    robot i (pos [n, 2] = Transform (x, z), rad [n]) touches collider j of hostlib.env_colliders.  The checker of the device pass
+    (mgx_collisions.hip, env_touches)."""
+    pos, rad = np.ascontiguousarray(pos, dtype=F).reshape(-1, 2), np.ascontiguousarray(rad, dtype=F).reshape(-1)
+    out = np.zeros((len(pos), len(colliders)), dtype=bool)
+    x, z, r = pos[:, 0:1], pos[:, 1:2], rad[:, None]
+    with np.errstate(all="ignore"):
+        b = np.nonzero(colliders["kind"] == hostlib.COLLIDER_BALL)[0]
+        if len(b):
+            dx, dz, rs = x - colliders["tx"][b][None], z - colliders["tz"][b][None], r + colliders["radius"][b][None]
+            out[:, b] = dx * dx + dz * dz <= rs * rs
+        c = np.nonzero(colliders["kind"] == hostlib.COLLIDER_CUBOID)[0]
+        if len(c):
+            h = colliders["half_extents"][c]
+            ex = np.maximum(np.abs(x - colliders["tx"][c][None]) - h[None, :, 0], F(0))
+            ez = np.maximum(np.abs(z - colliders["tz"][c][None]) - h[None, :, 1], F(0))
+            out[:, c] = ex * ex + ez * ez <= r * r
+        for j in np.nonzero(colliders["kind"] == hostlib.COLLIDER_POLYGON)[0]:
+            nv = int(colliders["n_vertices"][j])
+            if nv == 0:
+                continue
+            a = vertices[int(colliders["first_vertex"][j]):int(colliders["first_vertex"][j]) + nv].astype(F)
+            e = np.roll(a, -1, axis=0) - a                                      # edge i: v_i -> v_(i+1)
+            q = pos[:, None, :] - a[None]
+            inside = (e[None, :, 0] * q[..., 1] - e[None, :, 1] * q[..., 0] >= 0).all(axis=1) & (nv >= 3) & (rad == rad)
+            len2 = (e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1])[None]
+            t = np.where(len2 == 0, F(0), (q[..., 0] * e[None, :, 0] + q[..., 1] * e[None, :, 1]) / len2).astype(F)
+            t = np.minimum(np.maximum(t, F(0)), F(1))
+            d0, d1 = q[..., 0] - t * e[None, :, 0], q[..., 1] - t * e[None, :, 1]
+            d2 = d0 * d0 + d1 * d1
+            bad = np.isnan(t).any(axis=1) | np.isnan(d2).any(axis=1)
+            out[:, j] = (inside | (d2.min(axis=1) <= rad * rad)) & ~bad
+    return out
+
+
 class Simulation:
-    def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None):
+    def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None,
+                 environment_collisions=False):
         """scenario: `config.load_scenario(dir)` (or a dict of the same shape); world: a fresh
         World-like object created with `config.world_params(scenario["config"])`.
         device_missions (default: whenever the world offers them, i.e. the engine): routes, reached-when rules and
@@ -39,12 +78,21 @@ class Simulation:
         path, and the checker of the other one: tests/test_gpu_sim.py).
         device_collisions (default: whenever the missions live on the device and the world offers collisions_enable): the
         robot-robot collision pass runs on the device at the end of every tick (mgx_collisions_*) and `collisions` is filled
-        from its event log when somebody asks; otherwise _collide below runs on the host every tick (the checker)."""
+        from its event log when somebody asks; otherwise _collide below runs on the host every tick (the checker).
+        environment_collisions (default off: the export keeps 0 / []): True — robot-environment collisions are counted, on the
+        device (mgx_env_collisions_*) whenever the missions live there, otherwise by _collide_environment on the host; "host" —
+        the host pass whatever the missions do (the checker of the device pass)."""
         self.dev = hasattr(world, "mission_tick_begin") if device_missions is None else bool(device_missions)
         self._dev_coll = (self.dev and hasattr(world, "collisions_enable")) if device_collisions is None else bool(device_collisions)
         if self._dev_coll and not self.dev:
             raise ValueError("device_collisions needs device_missions (the pass reads the device's Transforms)")
         self._coll_cursor = 0      # events of the device's log already taken into `collisions`
+        if environment_collisions not in (False, True, "host"):
+            raise ValueError('environment_collisions: False, True or "host"')
+        self._env_coll = bool(environment_collisions)
+        self._dev_env_coll = environment_collisions is True and self.dev and hasattr(world, "env_collisions_enable")
+        self._env_coll_cursor = 0
+        self._env_collisions = {}  # (robot, collider) -> {"colliding": bool, "times": int, "aabbs": [...]}
         self._pending_track = None
         self._trk_log = []  # what _track noted since _tracks last ran
         self.name = scenario.get("name", "")
@@ -72,6 +120,10 @@ class Simulation:
         self._collisions = {}      # (robot a, robot b), a < b -> {"colliding": bool, "times": int, "aabbs": [...]}
         if self._dev_coll:
             world.collisions_enable(True, method=neighbours_method)
+        if self._dev_env_coll:
+            world.env_collisions_enable(self.env)
+        elif self._env_coll:
+            self._colliders, self._collider_vertices = hostlib.env_colliders(self.env)
         self.entities = spawner.EntityAllocator()  # the robots' Entity bits = their graphs' order (id.rs:19-54)
 
     # -- spawn_formation (spawner.rs:415-649) + RobotBundle::new (robot.rs:1134-1356) -------------------
@@ -191,8 +243,7 @@ class Simulation:
     # spheres of their Ball(radius) at the Transform's (x, z) — parry2d 0.13 BoundingSphere::intersects, restated from its
     # published source (third party, absent from /root/reference): |c_b - c_a|^2 <= (r_a + r_b)^2 in f32 — through the
     # Free / Colliding state machine of CollisionHistory (:455-495): a Free -> Colliding edge is one collision, recorded with
-    # the intersection of the two balls' AABBs (:113-119).  Robot - environment collisions need the colliders of the
-    # reference's 3-D map generator (environment/map_generator.rs) and parry2d's shape queries: not built (counted 0).
+    # the intersection of the two balls' AABBs (:113-119).  Robot - environment collisions: _collide_environment below.
     @property
     def collisions(self):
         """(robot a, robot b), a < b -> {"colliding", "times", "aabbs"}.  With the pass on the device the new events of its log are
@@ -235,6 +286,46 @@ class Simulation:
                 hi = np.minimum(pos[i] + rad[i], pos[j] + rad[j])
                 h["aabbs"].append({"mins": [float(lo[0]), float(lo[1])], "maxs": [float(hi[0]), float(hi[1])]})
 
+    # update_robot_environment_collisions (planner/collisions.rs:368-438, FixedUpdate): every live robot's Ball against every
+    # collider of the map (hostlib.env_colliders), the contact of include/mgx.h, the same Free / Colliding state machine; a
+    # Free -> Colliding edge is one collision, recorded with robot_aabb intersected with the collider's AABB (:417-426)
+    @property
+    def environment_collisions(self):
+        """(robot, collider) -> {"colliding", "times", "aabbs"}; empty while the option is off.  With the pass on the device the new
+        events of its log are taken in first (the one read that waits for the device)."""
+        if self._dev_env_coll:
+            ev, total, dropped, _ = self.w.env_collisions_read(self._env_coll_cursor)
+            if dropped:
+                raise hostlib.MgxError(f"the device's environment collision log was full: {dropped} events were not stored")
+            for e in ev:
+                h = self._env_collisions.setdefault((int(e["robot"]), int(e["collider"])), {"colliding": True, "times": 0, "aabbs": []})
+                h["times"] += 1
+                h["aabbs"].append({"mins": [float(e["mins"][0]), float(e["mins"][1])], "maxs": [float(e["maxs"][0]), float(e["maxs"][1])]})
+            self._env_coll_cursor = total
+        return self._env_collisions
+
+    def _collide_environment(self, alive, translation):
+        if not self._env_coll or self._dev_env_coll:
+            return
+        seen = {}
+        if alive and len(self._colliders):
+            ids = np.array([r["id"] for r in alive])
+            rad = np.array([r["radius"] for r in alive], dtype=F)
+            pos = np.ascontiguousarray(np.asarray(translation)[ids][:, [0, 2]], dtype=F)
+            hit = environment_contacts(self._colliders, self._collider_vertices, pos, rad) & np.isfinite(pos).all(axis=1)[:, None]
+            seen = {(int(ids[i]), int(k)): i for i, k in zip(*np.nonzero(hit))}
+        for key, h in self._env_collisions.items():                 # Colliding -> Free (also: the robot is gone)
+            if h["colliding"] and key not in seen:
+                h["colliding"] = False
+        for key, i in seen.items():                                 # Free -> Colliding
+            h = self._env_collisions.setdefault(key, {"colliding": False, "times": 0, "aabbs": []})
+            if not h["colliding"]:
+                h["colliding"] = True
+                h["times"] += 1
+                col = self._colliders[key[1]]
+                lo, hi = np.maximum(pos[i] - rad[i], col["mins"]), np.minimum(pos[i] + rad[i], col["maxs"])
+                h["aabbs"].append({"mins": [float(lo[0]), float(lo[1])], "maxs": [float(hi[0]), float(hi[1])]})
+
     def _flush_trackers(self, synchronise=False):
         """device missions: the samples of the last tick, taken from the Transforms that tick sent to the host behind its
         launches (complete after the next synchronisation — the next tick's own, or an explicit one here)"""
@@ -248,6 +339,7 @@ class Simulation:
         self._track(moving, tr, now)
         if not self._dev_coll:
             self._collide(alive, tr)
+        self._collide_environment(alive, tr)
 
     def _tick_device(self):
         w = self.w
@@ -306,6 +398,7 @@ class Simulation:
                 w.iterate(self.steps)
             self._track(moving, self._translation, (self.tick_no + 1) * self.dt_ns * 1e-9)
             self._collide(live, self._translation)
+            self._collide_environment(live, self._translation)
         self.tick_no += 1
 
     def finished(self):
@@ -360,6 +453,7 @@ class Simulation:
             self._track(moving, tr, (self.tick_no + 1) * self.dt_ns * 1e-9)
             if not self._dev_coll:
                 self._collide(live, tr)
+            self._collide_environment(live, tr)
             self.tick_no += 1
 
     def run(self, max_ticks=None, max_time=None, chunk=256):
@@ -384,6 +478,10 @@ class Simulation:
         self._tracks()
         sch = self.cfg["gbp"]["iteration-schedule"]
         collisions = self.collisions
+        env_coll = self.environment_collisions if self._env_coll else {}
+        env_count = {}
+        for (rid, _), h in env_coll.items():
+            env_count[rid] = env_count.get(rid, 0) + h["times"]
         robots = {}
         for r in self.robots:
             sent_i, sent_e, recv_i, recv_e = self.w.message_counts(r["id"])
@@ -391,7 +489,8 @@ class Simulation:
             fin = r["finished_at"] if r["finished_at"] is not None else self.elapsed()
             robots[str(r["id"])] = {
                 "radius": float(r["radius"]), "positions": r["positions"], "velocities": r["velocities"],
-                "collisions": {"robots": sum(h["times"] for k, h in collisions.items() if r["id"] in k), "environment": 0},
+                "collisions": {"robots": sum(h["times"] for k, h in collisions.items() if r["id"] in k),
+                               "environment": env_count.get(r["id"], 0)},
                 "messages": {"sent": {"internal": sent_i, "external": sent_e}, "received": {"internal": recv_i, "external": recv_e}},
                 "mission": {"waypoints": [wps[0], wps[-1]], "started_at": r["started_at"], "finished_at": fin,
                             "routes": [{"waypoints": wps, "started_at": r["started_at"], "finished_at": fin}]},
@@ -400,7 +499,9 @@ class Simulation:
                 "gbp": {"iterations": {"internal": sch["internal"], "external": sch["external"]}}, "robots": robots,
                 "prng_seed": self.cfg["simulation"]["prng-seed"], "config": self.cfg, "obstacles": {},
                 "collisions": {"robots": [{"robot_a": a, "robot_b": b, "aabbs": h["aabbs"]} for (a, b), h in sorted(collisions.items())],
-                               "environment": []},
+                               # only the pairs that have at least one AABB (collisions.rs:282-291); "obstacle": the collider's index
+                               "environment": [{"robot": a, "obstacle": k, "aabbs": h["aabbs"]}
+                                               for (a, k), h in sorted(env_coll.items()) if h["aabbs"]]},
                 # goal_areas: the reference registers GoalAreaPlugin but its only system that SPAWNS goal areas
                 # (setup_goal_areas_for_junction_scenario, goal_area.rs:105-119) is commented out of the plugin (:8-11):
                 # the exported map is empty in the reference itself

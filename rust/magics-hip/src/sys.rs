@@ -129,6 +129,36 @@ pub struct mgx_collision_event {
     pub maxs: [f32; 2],
 }
 
+/// one collider of the map (include/mgx.h, mgx_env_colliders)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_env_collider {
+    pub kind: i32,
+    pub tile_row: i32,
+    pub tile_col: i32,
+    pub obstacle: i32,
+    pub tx: f32,
+    pub tz: f32,
+    pub angle: f32,
+    pub radius: f32,
+    pub half_extents: [f32; 2],
+    pub first_vertex: u32,
+    pub n_vertices: u32,
+    pub mins: [f32; 2],
+    pub maxs: [f32; 2],
+}
+
+/// one robot-environment contact (include/mgx.h, mgx_env_collisions_*)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_env_collision_event {
+    pub pass: u64,
+    pub robot: i32,
+    pub collider: i32,
+    pub mins: [f32; 2],
+    pub maxs: [f32; 2],
+}
+
 #[repr(C)]
 pub struct mgx_mvn { _private: [u8; 0] }
 #[repr(C)]
@@ -250,6 +280,11 @@ extern "C" {
     pub fn mgx_env_to_image(env: *const mgx_env_desc, resolution: u32, expansion: f32, rgb: *mut u8) -> c_int;
     pub fn mgx_env_to_sdf_image(env: *const mgx_env_desc, resolution: u32, expansion: f32, blur_percent: f32, rgb: *mut u8) -> c_int;
     pub fn mgx_world_set_environment(w: *mut mgx_world, env: *const mgx_env_desc) -> c_int;
+    pub fn mgx_env_colliders(env: *const mgx_env_desc, out: *mut mgx_env_collider, capacity: u32, n: *mut u32, vertices_xz: *mut f32, vertex_capacity: u32, n_vertices: *mut u32) -> c_int;
+    pub fn mgx_env_collisions_enable(w: *mut mgx_world, env: *const mgx_env_desc, event_capacity: u64) -> c_int;
+    pub fn mgx_env_collisions_update(w: *mut mgx_world, positions_xyz: *const f32) -> c_int;
+    pub fn mgx_env_collisions_read(w: *mut mgx_world, first: u64, events: *mut mgx_env_collision_event, capacity: u64, n_total: *mut u64, dropped: *mut u64, per_robot: *mut u32) -> c_int;
+    pub fn mgx_env_collisions_clear(w: *mut mgx_world) -> c_int;
     pub fn mgx_schedule(kind: i32, n_internal: u8, n_external: u8, steps: *mut u8, capacity: u32) -> c_int;
     pub fn mgx_variable_timesteps(lookahead_horizon: u32, lookahead_multiple: u32, timesteps: *mut u32, capacity: u32) -> c_int;
 }

@@ -1,8 +1,10 @@
-"""What the robot-robot collision bookkeeping costs a mission tick (profiles/collisions.md):
+"""What the collision bookkeeping costs a mission tick (profiles/collisions.md):
 
     python tools/collisions_bench.py --mode off      # mission ticks, collisions disabled
     python tools/collisions_bench.py --mode device   # the pass on the device at the end of every tick (mgx_collisions_*)
     python tools/collisions_bench.py --mode host     # Transforms read per tick + sim.Simulation._collide per tick (the host pass)
+    python tools/collisions_bench.py --mode env      # the robot-environment pass on the device (mgx_env_collisions_*), Junction tile
+    python tools/collisions_bench.py --mode both     # both device passes
 
 A grid world with inter-robot factors on, driven through mgx_mission_tick_begin / _end like sim.Simulation does; `--reps`
 timings of `--ticks` ticks each, one JSON line with the median ticks/s."""
@@ -17,12 +19,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
-from magics_amd import World, hostlib, sim  # noqa: E402
+from magics_amd import World, environment, hostlib, sim  # noqa: E402
 from magics_amd import scenarios as S  # noqa: E402
 from magics_amd.driver import DeviceDriver  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=["off", "device", "host"], required=True)
+ap.add_argument("--mode", choices=["off", "device", "host", "env", "both"], required=True)
 ap.add_argument("--robots", type=int, default=1000)
 ap.add_argument("--K", type=int, default=16)
 ap.add_argument("--ticks", type=int, default=200)
@@ -38,8 +40,10 @@ S.populate(w, sc)
 n = len(sc["robots"])
 d = DeviceDriver(w, n, a.K, waypoints=[[tuple(rb["goal"])] for rb in sc["robots"]], radii=[rb["radius"] for rb in sc["robots"]],
                  t0=[rb["t0"] for rb in sc["robots"]], steps=sc["steps"], comms_radius=8.0, target_speed=sc["target_speed"])
-if a.mode == "device":
+if a.mode in ("device", "both"):
     w.collisions_enable(True, method=a.method)
+if a.mode in ("env", "both"):  # the Junction scenarios' map: one crossroads tile, four corner cuboids
+    w.env_collisions_enable(environment.new(["┼"], 0.16, 2.0, 100.0))
 host = sim.Simulation.__new__(sim.Simulation)
 host.collisions = {}
 robots = [{"id": r, "radius": np.float32(sc["robots"][r]["radius"])} for r in range(n)]
@@ -63,13 +67,16 @@ for rep in range(a.reps + 1):
     for _ in range(a.warmup if rep == 0 else a.ticks):
         tick()
         alive_before = alive.copy()
-    if a.mode == "device":
+    if a.mode in ("device", "both"):
         events, total, dropped, per = w.collisions_read()
-    else:
+    if a.mode in ("env", "both"):
+        env_total = w.env_collisions_read()[1]
+    if a.mode in ("off", "host"):
         w.synchronize()
     if rep:
         rates.append(a.ticks / (time.perf_counter() - t0))
-total = int(w.collisions_read()[1]) if a.mode == "device" else sum(h["times"] for h in host.collisions.values())
+total = int(w.collisions_read()[1]) if a.mode in ("device", "both") else sum(h["times"] for h in host.collisions.values())
 print(json.dumps({"mode": a.mode, "robots": n, "K": a.K, "ticks": a.ticks, "ticks_per_s_median": round(statistics.median(rates), 1),
                   "ticks_per_s": [round(r, 1) for r in rates], "alive": int(alive.sum()), "collision_events": total,
+                  **({"env_collision_events": int(env_total)} if a.mode in ("env", "both") else {}),
                   "last_sweep": list(w.last_sweep())}))
