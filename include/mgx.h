@@ -101,7 +101,12 @@ int mgx_synchronize(mgx_world *w);
 
 /* Obstacle "SDF" image sampled by ObstacleFactor::measure (factor/obstacle.rs:141-188):
  * interleaved RGB u8, row-major, `world_w x world_h` world units (robot.rs:1259-1264).
- * Only the red channel is kept on the device. */
+ * Only the red channel is kept on the device.
+ * The obstacle factors' jacobian_delta is (world_w / width + world_h / height) / 2 (obstacle.rs:98-102).  The kernels divide by
+ * it through a reciprocal that the host checks against every numerator the image's 256 sample values can form; a delta for
+ * which that check fails — zero, not finite, or near the ends of the f64 range: no map of any use — makes the next call that
+ * commits the world (the first iterate / tick / read after a change) return MGX_ERR_INVALID, whether or not obstacle factors
+ * are enabled at that moment (mgx_set_enabled can switch them on without another commit). */
 int mgx_world_set_sdf(mgx_world *w, const uint8_t *rgb, uint32_t width, uint32_t height,
                       double world_w, double world_h);
 

@@ -17,6 +17,50 @@
 
 namespace mgx {
 
+// ---------------------------------------------------------------------------------------
+// Division by a divisor that does not change from call to call ("invariant divisors").
+// An IEEE f64 division is a dozen VALU instructions on gfx950 (scale, reciprocal, Newton steps, div_fmas, div_fixup).  With
+// y = RN(1 / b) from ONE true division, kept beside b, the quotient of any a by the same b is three:
+//     q = RN(a y);   e = a - b q  (one fma: exact);   q' = RN(q + e y)  (one fma)
+// (Markstein's correction).  q' is the correctly rounded a / b — the bits the division returns — in round-to-nearest whenever
+// nothing overflows or underflows on the way:  |y - 1/b| <= ulp(y)/2 puts a y within one ulp of a/b, so q is one of the two
+// doubles around a/b or their outer neighbours and e is exact; q + e y = a/b + (a/b - q) eps with |eps| <= 2^-54 b (b scaled into
+// [1, 2)), which is closer to a/b than a/b can be to a rounding boundary (a/b is never a midpoint of two doubles, and a - b m is
+// a non-zero multiple of ulp(b) ulp(m) for every midpoint m: where a/b comes that close to m, q is a neighbour of m and the
+// perturbation 2^-108 b stays under the distance 2^-106 / b for every b < 2).
+// What the three instructions do NOT reproduce: a = +-0 with signs (e = -0 + 0), inf and NaN, and quotients, residuals or
+// reciprocals in or near the denormal range.  So:
+//   * reciprocal_for_division(b) hands out y only for 2^-400 <= |b| <= 2^400, otherwise 0 ("no reciprocal");
+//   * divide_by_invariant(a, b, y) takes the short form only when the exponent of q = a y lies in [-500, 500] — then a is finite,
+//     non-zero and within 2^+-900, e is at least 2^-1005 or exactly zero, nothing is denormal — and divides otherwise (zeros,
+//     denormals, inf, NaN, y == 0).  The test reads the exponent field with integer instructions; the branch is uniform across
+//     a wave in practice;
+//   * divide3 is the bare form for call sites whose operands come from a finite set that has been checked value by value
+//     (sdf_value: 256 numerators; the obstacle Jacobian: obstacle_inv_delta below).
+// The library is compiled with -ffp-contract=off: the fused operations are explicit.
+// ---------------------------------------------------------------------------------------
+MGX_HD uint64_t f64_bits(double v) {
+    uint64_t u;
+    __builtin_memcpy(&u, &v, sizeof u);
+    return u;
+}
+MGX_HD double divide3(double a, double b, double y) {
+    const double q = a * y;
+    const double e = __builtin_fma(-b, q, a);
+    return __builtin_fma(e, y, q);
+}
+MGX_HD double reciprocal_for_division(double b) {
+    const double m = std::fabs(b);
+    return (m >= 0x1p-400 && m <= 0x1p400) ? 1.0 / b : 0.0;
+}
+MGX_HD double divide_by_invariant(double a, double b, double y) {
+    const double q = a * y;
+    const uint32_t ex = (uint32_t)(f64_bits(q) >> 52) & 0x7ffu;  // biased exponent of q; 0: zero / denormal, 0x7ff: inf / NaN
+    if (ex - 523u > 1000u) return a / b;
+    const double e = __builtin_fma(-b, q, a);
+    return __builtin_fma(e, y, q);
+}
+
 // 4x4 inverse by cofactor expansion — the `Option` contract of ndarray-inverse 0.1.9 `inv()` used at
 // variable.rs:153,278 and factor/marginalise_factor_distance.rs:79: `None` iff det == 0 exactly.
 //   cofactor(i, j) = (-1)^(i+j) * det3(rows != i, columns != j),
@@ -249,7 +293,26 @@ MGX_HD long long sdf_index(const SdfView &s, double x, double y) {
     if (!(xp < s.w && yp < s.h)) return -1;
     return (long long)yp * s.w + xp;
 }
-MGX_HD double sdf_value(uint8_t red) { return 1.0 - (double)red / 255.0; }
+// 1 - red / 255 (obstacle.rs:178-180).  The quotient in three instructions (divide3): all 256 numerators give the bits of the
+// division (tests/test_invariant_divisions.py checks every one).
+MGX_HD double sdf_value(uint8_t red) { return 1.0 - divide3((double)red, 255.0, 1.0 / 255.0); }
+// Every value a sample of the image can take — 1 - k/255, and 0 outside the image, which is sdf_value(255) — is one of 256, so the
+// numerators h[i] - h[0] of the forward-difference Jacobian are at most 256 x 256 doubles, never -0.  For the world's delta the host
+// tries them all ONCE (mgx_world_commit.inc): the reciprocal 1 / delta if divide3 returns the division's bits for every one of
+// them, else 0 — and then the world is not committed (no world of any use has such a delta).  No guard in the iteration.
+MGX_HD double obstacle_inv_delta(double delta) {
+    const double y = 1.0 / delta;
+    for (int i = 0; i < 256; i++)
+        for (int j = 0; j < 256; j++) {
+            const double a = sdf_value((uint8_t)i) - sdf_value((uint8_t)j);
+            if (f64_bits(divide3(a, delta, y)) != f64_bits(a / delta)) return 0.0;
+        }
+    return (f64_bits(y) << 1) ? y : 0.0;
+}
+// (h_i - h_0) / delta by the reciprocal that obstacle_inv_delta(delta) vouches for (never 0 here: a world whose delta has none
+// is turned down when it is committed, mgx_world_commit.inc — a delta that is zero, not finite or near the ends of the f64 range; so the iteration carries
+// neither a test nor a division for it)
+MGX_HD double obstacle_slope(double hi, double h0, double delta, double inv_delta) { return divide3(hi - h0, delta, inv_delta); }
 
 // The four sample positions of the forward-difference Jacobian.  The reference perturbs
 // x[i] += delta ... x[i] -= delta in place, so later columns see (x+d)-d, not x.
@@ -264,6 +327,31 @@ MGX_HD void obstacle_taps(const SdfView &s, double x, double y, double delta, lo
 
 // Message of the obstacle factor = its 4-dim potential (marginalise passthrough,
 // marginalise_factor_distance.rs:62-72): lam = J^T (1/sigma^2) J, eta = J^T (1/s^2)(J x0 + (0 - h0)).
+MGX_HD void obstacle_message_of(const double (&J)[4], double h0, double inv_sigma2, const double (&x0)[4], double (&eta)[4],
+                                double (&lam)[16]) {
+    double jl[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) jl[i] = J[i] * inv_sigma2;
+    const double jx = ((J[0] * x0[0] + J[1] * x0[1]) + J[2] * x0[2]) + J[3] * x0[3];
+    const double rhs = jx + (0.0 - h0);
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        eta[i] = jl[i] * rhs;
+#pragma unroll
+        for (int j = 0; j < 4; j++) lam[i * 4 + j] = jl[i] * J[j];
+    }
+}
+// inv_delta: obstacle_inv_delta(delta), not 0.  Columns 2 and 3 are the same quotient (same sample, see obstacle_taps).
+MGX_HD void obstacle_message(const double (&h)[4], double delta, double inv_delta, double inv_sigma2, const double (&x0)[4],
+                             double (&eta)[4], double (&lam)[16]) {
+    double J[4];
+    J[0] = obstacle_slope(h[1], h[0], delta, inv_delta);
+    J[1] = obstacle_slope(h[2], h[0], delta, inv_delta);
+    J[2] = obstacle_slope(h[3], h[0], delta, inv_delta);
+    J[3] = J[2];
+    obstacle_message_of(J, h[0], inv_sigma2, x0, eta, lam);
+}
+// the same with the divisions as the reference writes them (any delta; host code and tests)
 MGX_HD void obstacle_message(const double (&h)[4], double delta, double inv_sigma2, const double (&x0)[4],
                              double (&eta)[4], double (&lam)[16]) {
     double J[4];
@@ -271,17 +359,7 @@ MGX_HD void obstacle_message(const double (&h)[4], double delta, double inv_sigm
     J[1] = (h[2] - h[0]) / delta;
     J[2] = (h[3] - h[0]) / delta;
     J[3] = (h[3] - h[0]) / delta;
-    double jl[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) jl[i] = J[i] * inv_sigma2;
-    const double jx = ((J[0] * x0[0] + J[1] * x0[1]) + J[2] * x0[2]) + J[3] * x0[3];
-    const double rhs = jx + (0.0 - h[0]);
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        eta[i] = jl[i] * rhs;
-#pragma unroll
-        for (int j = 0; j < 4; j++) lam[i * 4 + j] = jl[i] * J[j];
-    }
+    obstacle_message_of(J, h[0], inv_sigma2, x0, eta, lam);
 }
 
 // Row-split form of the two functions above for four cooperating lanes (q = 0..3): lane q samples
@@ -293,12 +371,12 @@ MGX_HD long long obstacle_tap(const SdfView &s, double x, double y, double delta
     const double ty = (q <= 1) ? y : (q == 2 ? y + delta : yr);
     return sdf_index(s, tx, ty);
 }
-MGX_HD void obstacle_message_row(const double (&h)[4], double delta, double inv_sigma2, const double (&x0)[4], int q,
+MGX_HD void obstacle_message_row(const double (&h)[4], double delta, double inv_delta, double inv_sigma2, const double (&x0)[4], int q,
                                  double &eta_q, double (&lam_q)[4]) {
     double J[4];
-    J[0] = (h[1] - h[0]) / delta;
-    J[1] = (h[2] - h[0]) / delta;
-    J[2] = (h[3] - h[0]) / delta;
+    J[0] = obstacle_slope(h[1], h[0], delta, inv_delta);
+    J[1] = obstacle_slope(h[2], h[0], delta, inv_delta);
+    J[2] = obstacle_slope(h[3], h[0], delta, inv_delta);
     J[3] = J[2];
     const double jq = (q == 0) ? J[0] : (q == 1 ? J[1] : J[2]);
     const double jl = jq * inv_sigma2;
@@ -316,7 +394,25 @@ MGX_HD void obstacle_message_row(const double (&h)[4], double delta, double inv_
 // `dst_slot` given the other slot's variable->factor message (eo, lo) (zeros when empty).
 // Returns false for an empty message (skip, singular, inf).
 // ---------------------------------------------------------------------------------------
-MGX_HD bool interrobot_message(const double (&x_lo)[4], const double (&x_hi)[4], double d_safe, double tiny_offset,
+// The three quotients of the measurement and its Jacobian (interrobot.rs:148-160,188-200) for 0 <= r <= d_safe:
+//     h0 = 1 (1 - r / d_safe),   cl = -1 / d_safe / r,   ch = 1 / d_safe / r
+// given inv_d_safe = reciprocal_for_division(d_safe), an edge constant (made where the edge's constants are loaded).
+//   * r / d_safe: divide_by_invariant (r == 0, tiny r and a d_safe without a reciprocal — inv_d_safe == 0 — take its division).
+//   * -1 / d_safe is -(1 / d_safe) bit for bit (round-to-nearest is sign-symmetric), and so is ch = -cl: ONE division, by r.
+//     With a reciprocal d_safe and r are numbers, so cl is one (possibly infinite) and its negation is exact.  Without one
+//     (d_safe beyond 2^+-400: no world has that) the numerator is divided for and ch gets its own division: -cl would flip the
+//     sign of the NaN that 0 / 0 gives for d_safe = inf, r = 0.
+MGX_HD void interrobot_slopes(double r, double d_safe, double inv_d_safe, double &h0, double &cl, double &ch) {
+    const bool have = (f64_bits(inv_d_safe) << 1) != 0;
+    h0 = 1.0 * (1.0 - divide_by_invariant(r, d_safe, inv_d_safe));
+    double n = -inv_d_safe;
+    if (!have) n = -1.0 / d_safe;
+    cl = n / r;
+    ch = -cl;
+    if (!have) ch = 1.0 / d_safe / r;
+}
+
+MGX_HD bool interrobot_message(const double (&x_lo)[4], const double (&x_hi)[4], double d_safe, double inv_d_safe, double tiny_offset,
                                double inv_sigma2, int dst_slot, const double (&eo)[4], const double (&lo)[16],
                                double (&out_eta)[4], double (&out_lam)[16]) {
     const double dx = x_lo[0] - x_hi[0], dy = x_lo[1] - x_hi[1];
@@ -325,8 +421,8 @@ MGX_HD bool interrobot_message(const double (&x_lo)[4], const double (&x_hi)[4],
     const double r = std::sqrt(d0 * d0 + d1 * d1);
     double h0 = 0.0, jl0 = 0.0, jl1 = 0.0, jh0 = 0.0, jh1 = 0.0;
     if (r <= d_safe) {  // :148-160, :188-200
-        h0 = 1.0 * (1.0 - r / d_safe);
-        const double cl = -1.0 / d_safe / r, ch = 1.0 / d_safe / r;
+        double cl, ch;
+        interrobot_slopes(r, d_safe, inv_d_safe, h0, cl, ch);
         jl0 = cl * d0; jl1 = cl * d1; jh0 = ch * d0; jh1 = ch * d1;
     }
     // row 0 of J = [jl0 jl1 0 0 | jh0 jh1 0 0]; lam_p = (J0^T / s^2) J0 ; eta_p = (J0^T / s^2) rhs
@@ -350,6 +446,11 @@ MGX_HD bool interrobot_message(const double (&x_lo)[4], const double (&x_hi)[4],
     eb[0] = wb0 * rhs + eo[0]; eb[1] = wb1 * rhs + eo[1]; eb[2] = eo[2]; eb[3] = eo[3];
     return schur4(laa, lab, lba, lbb, ea, eb, out_eta, out_lam);
 }
+MGX_HD bool interrobot_message(const double (&x_lo)[4], const double (&x_hi)[4], double d_safe, double tiny_offset,
+                               double inv_sigma2, int dst_slot, const double (&eo)[4], const double (&lo)[16],
+                               double (&out_eta)[4], double (&out_lam)[16]) {
+    return interrobot_message(x_lo, x_hi, d_safe, reciprocal_for_division(d_safe), tiny_offset, inv_sigma2, dst_slot, eo, lo, out_eta, out_lam);
+}
 
 // The same message in the form the engine keeps it (six numbers — eta[0..1] and the position block of lam; the
 // velocity rows and columns of an inter-robot message are structural zeros): only the terms that are not products with a
@@ -360,7 +461,7 @@ MGX_HD bool interrobot_message(const double (&x_lo)[4], const double (&x_hi)[4],
 //   0 - (sums of x * 0), which is never infinite, so the `Message::empty()` test reads the four kept entries.
 // x + 0.0 * y == x for finite y: the kept numbers equal interrobot_message's unless the dense form meets inf / NaN there
 // (structural zeros).  out: eta0, eta1, lam00, lam01, lam10, lam11.
-MGX_HD bool interrobot_message_compact(const double (&x_lo)[4], const double (&x_hi)[4], double d_safe, double tiny_offset,
+MGX_HD bool interrobot_message_compact(const double (&x_lo)[4], const double (&x_hi)[4], double d_safe, double inv_d_safe, double tiny_offset,
                                        double inv_sigma2, int dst_slot, const double (&eo)[4], const double (&lo)[16],
                                        double (&out)[6]) {
     const double dx = x_lo[0] - x_hi[0], dy = x_lo[1] - x_hi[1];
@@ -369,8 +470,8 @@ MGX_HD bool interrobot_message_compact(const double (&x_lo)[4], const double (&x
     const double r = std::sqrt(d0 * d0 + d1 * d1);
     double h0 = 0.0, jl0 = 0.0, jl1 = 0.0, jh0 = 0.0, jh1 = 0.0;
     if (r <= d_safe) {
-        h0 = 1.0 * (1.0 - r / d_safe);
-        const double cl = -1.0 / d_safe / r, ch = 1.0 / d_safe / r;
+        double cl, ch;
+        interrobot_slopes(r, d_safe, inv_d_safe, h0, cl, ch);
         jl0 = cl * d0; jl1 = cl * d1; jh0 = ch * d0; jh1 = ch * d1;
     }
     const double jx = (jl0 * x_lo[0] + jh0 * x_hi[0]) + (jl1 * x_lo[1] + jh1 * x_hi[1]);

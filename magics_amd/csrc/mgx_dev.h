@@ -182,6 +182,7 @@ struct DevWorld {
     const uint8_t *sdf;
     uint32_t sdf_w, sdf_h;
     double world_w, world_h, obs_delta;
+    double obs_inv_delta;  // 1 / obs_delta once the host has checked it against every numerator the Jacobian can meet, else 0 (gbp_math.h, obstacle_inv_delta)
     int ir_max_edges;  // largest number of inter-robot edges attached to one robot (LDS staging size)
     int trk_cols;      // 0: tracking factors have never been enabled in this world (their message columns are all zero)
 

@@ -234,7 +234,7 @@ __global__ void k_thaw(DevWorld w, int robot0, int n_robots, uint32_t ext_mask) 
             double h[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) h[q] = (idx[q] >= 0) ? sdf_value(w.sdf[idx[q]]) : 0.0;
-            obstacle_message(h, w.obs_delta, w.inv_s2_obs, x0, oe, ol);
+            obstacle_message(h, w.obs_delta, w.obs_inv_delta, w.inv_s2_obs, x0, oe, ol);
         } else {
             const bool radio = (w.antenna[r] != 0) && !idle;
             const int itf = w.iter_factor[r] + (((ext_mask & PH_EXT_FACTOR) && radio) ? 1 : 0);
@@ -316,7 +316,7 @@ __global__ void k_thaw_ir(DevWorld w, uint8_t *gate) {
             x_lo[c] = dslot ? a_mu[c] : b_mu[c];
             x_hi[c] = dslot ? b_mu[c] : a_mu[c];
         }
-        const bool ok = interrobot_message_compact(x_lo, x_hi, er.d_safe, er.offset, w.inv_s2_ir, dslot, ao_eta, ao_lam, o6);
+        const bool ok = interrobot_message_compact(x_lo, x_hi, er.d_safe, reciprocal_for_division(er.d_safe), er.offset, w.inv_s2_ir, dslot, ao_eta, ao_lam, o6);
         w.ir_fv_eta[0 * (size_t)w.NI + e] = ok ? o6[0] : 0.0;
         w.ir_fv_eta[1 * (size_t)w.NI + e] = ok ? o6[1] : 0.0;
         w.ir_fv_lam[0 * (size_t)w.NI + e] = ok ? o6[2] : 0.0;

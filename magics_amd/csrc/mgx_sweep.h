@@ -73,14 +73,17 @@ extern __shared__ double lds[];
 
 // An edge's constants in registers: loaded as two 16-byte pieces and kept as five scalars, never as an aggregate — a copy of the
 // 32-byte record that is chosen between a register copy and memory ends up as a pointer choice, and the register copy in scratch.
-#define MGX_EDGE_REGS(p) int p##_src_var = 0, p##_dst = 0; uint32_t p##_created = 0u; double p##_d_safe = 0.0, p##_offset = 0.0
+// p_inv_d_safe: the reciprocal of the safety distance that the factor's quotients are made from (gbp_math.h, interrobot_slopes) —
+// one division where the constants are loaded instead of four in every evaluation of the factor.
+#define MGX_EDGE_REGS(p) int p##_src_var = 0, p##_dst = 0; uint32_t p##_created = 0u; double p##_d_safe = 0.0, p##_inv_d_safe = 0.0, p##_offset = 0.0
 #define MGX_EDGE_LOAD(p, ptr)                                                                                     \
     do {                                                                                                          \
         const int4 a_ = *reinterpret_cast<const int4 *>(ptr);                                                     \
         const double2 b_ = *reinterpret_cast<const double2 *>(reinterpret_cast<const char *>(ptr) + 16);          \
         p##_src_var = a_.x; p##_created = (uint32_t)a_.z; p##_dst = a_.w; p##_d_safe = b_.x; p##_offset = b_.y;   \
+        p##_inv_d_safe = reciprocal_for_division(b_.x);                                                           \
     } while (0)
-#define MGX_EDGE_COPY(p, q) do { p##_src_var = q##_src_var; p##_created = q##_created; p##_dst = q##_dst; p##_d_safe = q##_d_safe; p##_offset = q##_offset; } while (0)
+#define MGX_EDGE_COPY(p, q) do { p##_src_var = q##_src_var; p##_created = q##_created; p##_dst = q##_dst; p##_d_safe = q##_d_safe; p##_inv_d_safe = q##_inv_d_safe; p##_offset = q##_offset; } while (0)
 
 // In-kernel cycle stamps exist only in the diagnostic build (never in libmgx.so): they go to a
 // buffer of their own and no output value depends on them.
@@ -1077,7 +1080,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                     x_lo[c] = dslot ? a_mu[c] : b_mu[c];
                     x_hi[c] = dslot ? b_mu[c] : a_mu[c];
                 }
-                const bool live_msg = interrobot_message_compact(x_lo, x_hi, er_d_safe, er_offset, w.inv_s2_ir, dslot, ao_eta, ao_lam, o6);
+                const bool live_msg = interrobot_message_compact(x_lo, x_hi, er_d_safe, er_inv_d_safe, er_offset, w.inv_s2_ir, dslot, ao_eta, ao_lam, o6);
                 if (!live_msg) {
 #pragma unroll
                     for (int c = 0; c < 6; c++) o6[c] = 0.0;
@@ -1409,6 +1412,12 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
         asm volatile("" : "+v"(p_));
         return p_;
     };
+    // (the obstacle Jacobian's reciprocal likewise: read where it is used, not carried across the iteration in scalar registers)
+    auto obs_inv_delta_here = [&]() __attribute__((always_inline)) {
+        double p_ = w.obs_inv_delta;
+        asm volatile("" : "+s"(p_));
+        return p_;
+    };
     auto unary_messages = [&](uint32_t skip, double *s_out, int itf_gate) __attribute__((always_inline)) {
         if (obs_rows) {
             // four lanes per obstacle factor: lane q samples tap q and writes row q of the message
@@ -1424,7 +1433,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
 #pragma unroll
                 for (int t = 0; t < 4; t++) h[t] = __shfl(hq, (lane & ~3) + t, 64);
                 double eta_q, lam_q[4];
-                obstacle_message_row(h, w.obs_delta, w.inv_s2_obs, x0, q, eta_q, lam_q);
+                obstacle_message_row(h, w.obs_delta, obs_inv_delta_here(), w.inv_s2_obs, x0, q, eta_q, lam_q);
                 s_out[q * E1 + col] = eta_q;
 #pragma unroll
                 for (int c = 0; c < 4; c++) s_out[(4 + q * 4 + c) * E1 + col] = lam_q[c];
@@ -1439,7 +1448,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
             double h[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) h[q] = (idx[q] >= 0) ? sdf_value(w.sdf[idx[q]]) : 0.0;
-            obstacle_message(h, w.obs_delta, w.inv_s2_obs, x0, oe, ol);
+            obstacle_message(h, w.obs_delta, obs_inv_delta_here(), w.inv_s2_obs, x0, oe, ol);
 #pragma unroll
             for (int c = 0; c < 4; c++) s_out[c * E1 + uedge] = oe[c];
 #pragma unroll

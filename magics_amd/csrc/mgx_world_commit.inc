@@ -547,6 +547,13 @@ static int commit(mgx_world *w) {
     d.sdf = w->sdf.p; d.sdf_w = w->sdf_w; d.sdf_h = w->sdf_h; d.world_w = w->world_w; d.world_h = w->world_h;
     // ObstacleFactor::new jacobian_delta (obstacle.rs:98-102)
     d.obs_delta = (w->sdf_w && w->sdf_h) ? (w->world_w / (double)w->sdf_w + w->world_h / (double)w->sdf_h) / 2.0 : 1.0;
+    if (f64_bits(w->obs_delta_checked) != f64_bits(d.obs_delta)) {
+        w->obs_inv_delta = obstacle_inv_delta(d.obs_delta);
+        w->obs_delta_checked = d.obs_delta;
+    }
+    if (!(f64_bits(w->obs_inv_delta) << 1))
+        return fail(MGX_ERR_INVALID, "obstacle factors: jacobian delta %g (world size / image size) has no reciprocal that reproduces the division (zero, not finite, or near the ends of the f64 range)", d.obs_delta);
+    d.obs_inv_delta = w->obs_inv_delta;
     d.inv_s2_obs = 1.0 / (w->p.sigma_obstacle * w->p.sigma_obstacle);    // FactorState::new, factor/mod.rs:631-632
     d.inv_s2_ir = 1.0 / (w->p.sigma_interrobot * w->p.sigma_interrobot);
     d.inv_s2_trk = 1.0 / (w->p.sigma_tracking * w->p.sigma_tracking);

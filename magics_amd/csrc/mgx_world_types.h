@@ -425,6 +425,9 @@ struct mgx_world {
     std::vector<uint8_t> sdf_red;
     uint32_t sdf_w = 0, sdf_h = 0;
     double world_w = 1.0, world_h = 1.0;
+    // the reciprocal of the obstacle factors' jacobian_delta the kernels may divide with, and the delta it was checked for
+    // (gbp_math.h, obstacle_inv_delta: 65 536 quotients, so once per delta and not once per commit)
+    double obs_delta_checked = 0.0, obs_inv_delta = 0.0;
     int K = 0;
 
     hipStream_t stream = nullptr;
