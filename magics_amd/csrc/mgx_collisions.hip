@@ -25,7 +25,8 @@
 // counted for both robots.  The two never touch the same pair in conflicting ways (the retest only clears bits of pairs that
 // do not overlap, the search only sets bits of pairs that do), so both run in ONE launch.
 //   log    append-only, 32-byte records under an atomic cursor that keeps counting when the log is full (what did not fit is
-//          cursor - capacity: nothing is lost silently, nothing traps or spins)
+//          cursor - capacity: nothing is lost silently, nothing traps or spins): ContactLog and contact_append, shared with
+//          the robot-environment pass
 //   words  [0] the cursor, [1] sticky: the pair list overflowed (a pair's bit is set but nobody will ever clear it: later
 //          passes may miss events — mgx_collisions_read reports it as an error)
 //
@@ -48,13 +49,30 @@
 #include "../../include/mgx.h"
 #include "gbp_math.h"
 #include "mgx_dev.h"
+#include "mgx_grid.h"
 
 namespace mgx {
 
-static_assert(sizeof(mgx_collision_event) == 32 && sizeof(CollEvent) == 32, "the log's records are 32 bytes");
-static_assert(offsetof(mgx_collision_event, robot_a) == offsetof(CollEvent, robot_a) && offsetof(mgx_collision_event, mins) == offsetof(CollEvent, mins) &&
-                  offsetof(mgx_collision_event, maxs) == offsetof(CollEvent, maxs),
-              "CollEvent is the ABI's record");
+static_assert(sizeof(mgx_collision_event) == 32 && sizeof(ContactEvent) == 32, "the log's records are 32 bytes");
+static_assert(offsetof(mgx_collision_event, robot_a) == offsetof(ContactEvent, a) && offsetof(mgx_collision_event, robot_b) == offsetof(ContactEvent, b) &&
+                  offsetof(mgx_collision_event, mins) == offsetof(ContactEvent, mins) && offsetof(mgx_collision_event, maxs) == offsetof(ContactEvent, maxs),
+              "ContactEvent is the ABI's record");
+
+// one record under the log's cursor, which keeps counting when the log is full (the overflow word is the callers' business)
+__device__ __forceinline__ void contact_append(const ContactLog &log, unsigned long long pass, int a, int b, float min0, float min1, float max0, float max1) {
+    const unsigned long long e = atomicAdd(&log.words[0], 1ull);
+    if (e < log.cap) {
+        ContactEvent ev;
+        ev.pass = pass;
+        ev.a = a;
+        ev.b = b;
+        ev.mins[0] = min0;
+        ev.mins[1] = min1;
+        ev.maxs[0] = max0;
+        ev.maxs[1] = max1;
+        log.events[e] = ev;
+    }
+}
 
 __device__ __forceinline__ bool balls_overlap(float ax, float az, float ar, float bx, float bz, float br) {
     const float dx = __fsub_rn(bx, ax), dy = __fsub_rn(bz, az), rs = __fadd_rn(ar, br);
@@ -72,7 +90,7 @@ __device__ __forceinline__ void robot_ball(const CollDev &c, int i, float &x, fl
 __device__ __forceinline__ void list_append(const CollDev &c, int a, int b) {
     const uint32_t at = atomicAdd(&c.cnt[(c.pass + 1) % 3], 1u);
     if (at < c.list_cap) c.list[(c.pass + 1) & 1][at] = make_int2(a, b);
-    else atomicOr(&c.words[1], 1ull);
+    else atomicOr(&c.log.words[1], 1ull);
 }
 
 // pair (a, b), a < b, overlaps in this pass
@@ -81,18 +99,8 @@ __device__ __forceinline__ void pair_overlaps(const CollDev &c, int a, float ax,
     const uint32_t m = 1u << (bit & 31u);
     if (atomicOr(&c.bits[bit >> 5], m) & m) return;  // Colliding -> Colliding (the retest lanes carry it over)
     list_append(c, a, b);
-    const unsigned long long e = atomicAdd(&c.words[0], 1ull);
-    if (e < c.log_cap) {
-        CollEvent ev;
-        ev.pass = c.pass;
-        ev.robot_a = a;
-        ev.robot_b = b;
-        ev.mins[0] = fmaxf(__fsub_rn(ax, ar), __fsub_rn(bx, br));
-        ev.mins[1] = fmaxf(__fsub_rn(az, ar), __fsub_rn(bz, br));
-        ev.maxs[0] = fminf(__fadd_rn(ax, ar), __fadd_rn(bx, br));
-        ev.maxs[1] = fminf(__fadd_rn(az, ar), __fadd_rn(bz, br));
-        c.log[e] = ev;
-    }
+    contact_append(c.log, c.pass, a, b, fmaxf(__fsub_rn(ax, ar), __fsub_rn(bx, br)), fmaxf(__fsub_rn(az, ar), __fsub_rn(bz, br)),
+                   fminf(__fadd_rn(ax, ar), __fadd_rn(bx, br)), fminf(__fadd_rn(az, ar), __fadd_rn(bz, br)));
     atomicAdd(&c.per_robot[a], 1u);
     atomicAdd(&c.per_robot[b], 1u);
 }
@@ -146,15 +154,6 @@ __global__ void __launch_bounds__(COLL_BLOCK) k_collisions_pairs(CollDev c, int 
         if (balls_overlap(ax, az, ar, X[q], Z[q], Rr[q])) pair_overlaps(c, i, ax, az, ar, j0 + q, X[q], Z[q], Rr[q]);
 }
 
-__device__ __forceinline__ int coll_cell_of(float x, double inv_cell) {  // monotone, clamped (as mgx_topology.hip's)
-    double v = floor((double)x * inv_cell);
-    v = fmin(fmax(v, -1073741824.0), 1073741824.0);
-    return (int)v;
-}
-__device__ __forceinline__ uint32_t coll_bucket_of(int cx, int cz, uint32_t mask) {
-    return (((uint32_t)cx * 73856093u) ^ ((uint32_t)cz * 19349663u)) & mask;
-}
-
 // every alive robot with finite coordinates goes to the front of its bucket's list; a head of another pass is an empty bucket
 __global__ void __launch_bounds__(256) k_collisions_link(CollDev c, double inv_cell, uint32_t mask) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
@@ -163,7 +162,7 @@ __global__ void __launch_bounds__(256) k_collisions_link(CollDev c, double inv_c
     robot_ball(c, i, x, z, r);
     if (!isfinite(x) || !isfinite(z)) return;
     const unsigned long long stamp = (unsigned long long)(uint32_t)(c.pass + 1u) << 32;
-    const unsigned long long old = atomicExch(&c.head[coll_bucket_of(coll_cell_of(x, inv_cell), coll_cell_of(z, inv_cell), mask)], stamp | (uint32_t)i);
+    const unsigned long long old = atomicExch(&c.head[bucket_of(cell_of(x, inv_cell), cell_of(z, inv_cell), mask)], stamp | (uint32_t)i);
     c.next[i] = (old >> 32) == (stamp >> 32) ? (int32_t)(uint32_t)old : -1;
 }
 
@@ -179,18 +178,18 @@ __global__ void __launch_bounds__(COLL_BLOCK) k_collisions_grid(CollDev c, doubl
     float ax, az, ar;
     robot_ball(c, i, ax, az, ar);
     if (!isfinite(ax) || !isfinite(az)) return;
-    const int cx = coll_cell_of(ax, inv_cell), cz = coll_cell_of(az, inv_cell);
+    const int cx = cell_of(ax, inv_cell), cz = cell_of(az, inv_cell);
     const uint32_t stamp = (uint32_t)(c.pass + 1u);
     for (int ox = -1; ox <= 1; ox++)
         for (int oz = -1; oz <= 1; oz++) {
             const int qx = cx + ox, qz = cz + oz;
-            const unsigned long long h = c.head[coll_bucket_of(qx, qz, mask)];
+            const unsigned long long h = c.head[bucket_of(qx, qz, mask)];
             int j = (uint32_t)(h >> 32) == stamp ? (int)(uint32_t)h : -1;
             for (int guard = 0; j >= 0 && j < c.n && guard < c.n; guard++) {
                 if (j > i) {
                     float bx, bz, br;
                     robot_ball(c, j, bx, bz, br);
-                    if (coll_cell_of(bx, inv_cell) == qx && coll_cell_of(bz, inv_cell) == qz && balls_overlap(ax, az, ar, bx, bz, br))
+                    if (cell_of(bx, inv_cell) == qx && cell_of(bz, inv_cell) == qz && balls_overlap(ax, az, ar, bx, bz, br))
                         pair_overlaps(c, i, ax, az, ar, j, bx, bz, br);
                 }
                 j = c.next[j];
@@ -240,10 +239,10 @@ hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s) {
 // contact that is not among them is a Hit: one 32-byte record under the log's atomic cursor (which keeps counting when the
 // log is full) and one count for the robot.  More simultaneous contacts than slots set the sticky word [1].
 // A few hundred bytes of collider data per lane out of L2, no LDS; the launch is latency, not throughput.
-static_assert(sizeof(mgx_env_collision_event) == 32 && sizeof(EnvCollEvent) == 32, "the log's records are 32 bytes");
-static_assert(offsetof(mgx_env_collision_event, robot) == offsetof(EnvCollEvent, robot) && offsetof(mgx_env_collision_event, collider) == offsetof(EnvCollEvent, collider) &&
-                  offsetof(mgx_env_collision_event, mins) == offsetof(EnvCollEvent, mins) && offsetof(mgx_env_collision_event, maxs) == offsetof(EnvCollEvent, maxs),
-              "EnvCollEvent is the ABI's record");
+static_assert(sizeof(mgx_env_collision_event) == 32, "the log's records are 32 bytes");
+static_assert(offsetof(mgx_env_collision_event, robot) == offsetof(ContactEvent, a) && offsetof(mgx_env_collision_event, collider) == offsetof(ContactEvent, b) &&
+                  offsetof(mgx_env_collision_event, mins) == offsetof(ContactEvent, mins) && offsetof(mgx_env_collision_event, maxs) == offsetof(ContactEvent, maxs),
+              "ContactEvent is the ABI's record");
 static_assert(ENV_COLL_SLOTS == 8, "the slots travel as two int4");
 
 __device__ __forceinline__ float sq_sum(float a, float b) { return __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)); }
@@ -286,11 +285,6 @@ __device__ bool env_touches(const EnvCollider &k, const float *__restrict__ vert
     }
 }
 
-__device__ __forceinline__ int env_cell_of(double v, double origin, double inv_cell, int n) {  // monotone, clamped into the grid
-    const double c = floor((v - origin) * inv_cell);
-    return (int)fmin(fmax(c, 0.0), (double)(n - 1));
-}
-
 __global__ void __launch_bounds__(64) k_env_collisions(EnvCollDev c) {
     const int i = (int)(blockIdx.x * 64 + threadIdx.x);
     if (i >= c.n) return;
@@ -321,21 +315,11 @@ __global__ void __launch_bounds__(64) k_env_collisions(EnvCollDev c) {
                             if (s == n_cur) cur[s] = ki;
                         n_cur++;
                     } else {
-                        atomicOr(&c.words[1], 1ull);
+                        atomicOr(&c.log.words[1], 1ull);
                     }
                     if (was) continue;  // Colliding -> Colliding
-                    const unsigned long long e = atomicAdd(&c.words[0], 1ull);
-                    if (e < c.log_cap) {
-                        EnvCollEvent ev;
-                        ev.pass = c.pass;
-                        ev.robot = i;
-                        ev.collider = ki;
-                        ev.mins[0] = fmaxf(__fsub_rn(x, r), k.mins[0]);
-                        ev.mins[1] = fmaxf(__fsub_rn(z, r), k.mins[1]);
-                        ev.maxs[0] = fminf(__fadd_rn(x, r), k.maxs[0]);
-                        ev.maxs[1] = fminf(__fadd_rn(z, r), k.maxs[1]);
-                        c.log[e] = ev;
-                    }
+                    contact_append(c.log, c.pass, i, ki, fmaxf(__fsub_rn(x, r), k.mins[0]), fmaxf(__fsub_rn(z, r), k.mins[1]),
+                                   fminf(__fadd_rn(x, r), k.maxs[0]), fminf(__fadd_rn(z, r), k.maxs[1]));
                     c.per_robot[i] += 1u;  // (this lane's own word)
                 }
             }

@@ -249,34 +249,39 @@ struct DevMission {
     long long *finished_tick;  // [R] tick at which the last waypoint was reached, -1 before
 };
 
-// Robot-robot collision bookkeeping on the device (mgx_collisions.hip, which says what every array is for): what one pass
-// is handed.  Everything is indexed by robot id.
-struct CollEvent {  // == mgx_collision_event (include/mgx.h; mgx_collisions.hip asserts it)
+// Collision bookkeeping on the device (mgx_collisions.hip, which says what every array is for).  Both passes, robot-robot and
+// robot-environment, append the same 32-byte record to a log of the same kind and read the same per-robot inputs.
+struct ContactEvent {  // == mgx_collision_event == mgx_env_collision_event (include/mgx.h; mgx_collisions.hip asserts both)
     unsigned long long pass;
-    int32_t robot_a, robot_b;
+    int32_t a, b;              // robot_a, robot_b / robot, collider
     float mins[2], maxs[2];
 };
-struct CollDev {
+struct ContactLog {
+    ContactEvent *events;      // [cap]
+    unsigned long long cap;
+    unsigned long long *words;  // [0] cursor (keeps counting beyond cap), [1] sticky: the pass's own state overflowed (each pass says how)
+};
+struct ContactDev {            // what either pass is handed about the robots; everything is indexed by robot id
     const float *pos;          // [n][3] Transform::translation (x, height, z)
     const uint8_t *alive;      // [n] not removed, not a ghost
     const float *radius;       // [n] (float)desc.radius
+    uint32_t *per_robot;       // [n] contacts of every robot
+    ContactLog log;
+    unsigned long long pass;
+};                             // (n stays with each pass's own 32-bit fields: here it would pad a kernel's argument by 8 bytes)
+struct CollDev : ContactDev {  // robot-robot; words[1]: the pair list overflowed
     int n;                     // robots of the world (ids 0 .. n-1)
     uint32_t stride;           // of the pair bits: pair (a, b) is bit a * stride + b
     uint32_t *bits;
     int2 *list[2];             // the overlapping pairs, read / written in turn
     uint32_t *cnt;             // [3] lengths of the lists, in rotation
     uint32_t list_cap;
-    CollEvent *log;            // [log_cap]
-    unsigned long long log_cap;
-    unsigned long long *words;  // [0] log cursor (keeps counting beyond log_cap), [1] sticky: the pair list overflowed
-    uint32_t *per_robot;       // [n] contacts of every robot
     unsigned long long *head;  // hash grid: per bucket (pass stamp << 32) | first robot
     int32_t *next;             // [n] next robot of the same bucket, -1: none
-    unsigned long long pass;
 };
 
-// Robot-environment collision bookkeeping on the device (mgx_collisions.hip, second half): the map's colliders as the pass reads
-// them, and what one pass is handed.  Per-robot arrays are indexed by robot id.
+// Robot-environment collision bookkeeping (mgx_collisions.hip, second half): the map's colliders as the pass reads them, and
+// what one pass is handed.
 struct EnvCollider {
     int32_t kind;              // MGX_COLLIDER_*
     uint32_t first_vertex, n_vertices;  // polygon: world (x, z) pairs in `verts`, counter-clockwise
@@ -285,32 +290,20 @@ struct EnvCollider {
     float mins[2], maxs[2];    // Collider::aabb()
     int32_t cx0, cz0, cx1, cz1;  // the cells its AABB overlaps (inclusive): a collider met in several cells counts in the first
 };
-struct EnvCollEvent {  // == mgx_env_collision_event (include/mgx.h; mgx_collisions.hip asserts it)
-    unsigned long long pass;
-    int32_t robot, collider;
-    float mins[2], maxs[2];
-};
 constexpr int ENV_COLL_SLOTS = 8;  // colliders a robot is remembered to touch at the same time
-struct EnvCollDev {
-    const float *pos;          // [n][3] Transform::translation (x, height, z)
-    const uint8_t *alive;      // [n] not removed, not a ghost
-    const float *radius;       // [n] (float)desc.radius
+struct EnvCollDev : ContactDev {  // words[1]: a robot touched more than the slots hold
     int n;                     // robots of the world (ids 0 .. n-1)
     int n_colliders;
+    int n_cx, n_cz;            // a cell is one tile
     const EnvCollider *colliders;
     const float *verts;
     const uint32_t *cell_ptr;  // [n_cx * n_cz + 1] CSR over cells (cz * n_cx + cx)
     const int32_t *cell_idx;   // collider indices
-    int n_cx, n_cz;            // a cell is one tile
     double x0, z0, inv_cell;   // cell of a coordinate: floor((v - origin) * inv_cell), clamped into the grid
     double pad;                // added to a robot's radius when its cells are chosen (covers the roundings of the f32 predicate)
     int32_t *touching;         // [n][ENV_COLL_SLOTS] colliders touched after the last pass, -1: free slot
-    EnvCollEvent *log;         // [log_cap]
-    unsigned long long log_cap;
-    unsigned long long *words;  // [0] log cursor (keeps counting beyond log_cap), [1] sticky: a robot touched more than the slots hold
-    uint32_t *per_robot;       // [n] contacts of every robot
-    unsigned long long pass;
 };
+static_assert(sizeof(CollDev) == 128 && sizeof(EnvCollDev) == 152, "kernel arguments by value: no larger than before the fold");
 
 __host__ __device__ constexpr int frozen_words(int K) { return 40 * (K - 1) + 8 * (K - 2); }
 

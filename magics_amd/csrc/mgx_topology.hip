@@ -15,6 +15,7 @@
 #include <limits>
 
 #include "gbp_math.h"
+#include "mgx_grid.h"
 
 namespace mgx {
 
@@ -41,15 +42,38 @@ __device__ __forceinline__ bool in_comms_range_sq(float ax, float ay, float az, 
 
 __device__ __forceinline__ bool finite3(float x, float y, float z) { return isfinite(x) && isfinite(y) && isfinite(z); }
 
-// cell coordinate of one axis: floor(x / cell) in f64, clamped (monotone, so robots within one
-// radius of each other stay within one cell of each other)
-__device__ __forceinline__ int cell_of(float x, double inv_cell) {
-    double c = floor((double)x * inv_cell);
-    c = fmin(fmax(c, -1073741824.0), 1073741824.0);
-    return (int)c;
-}
-__device__ __forceinline__ uint32_t bucket_of(int cx, int cz, uint32_t mask) {
-    return (((uint32_t)cx * 73856093u) ^ ((uint32_t)cz * 19349663u)) & mask;
+// all n positions [n][3] into LDS as a structure of arrays, by the NT threads of a workgroup: 3 n floats, 16 bytes at a time, six
+// loads per lane in flight together (the block is 16-byte aligned; the last, partial group goes float by float).  The caller
+// synchronises.
+template <int NT>
+__device__ __forceinline__ void load_positions_soa(const float *__restrict__ pos, int n, float *X, float *Y, float *Z) {
+    const int n3 = 3 * n, n4 = n3 >> 2;
+    const float4 *p4 = reinterpret_cast<const float4 *>(pos);
+    constexpr int INFLIGHT = 6;
+    for (int g0 = 0; g0 < n4; g0 += NT * INFLIGHT) {
+        float4 v[INFLIGHT];
+#pragma unroll
+        for (int u = 0; u < INFLIGHT; u++) {
+            const int g = g0 + u * NT + (int)threadIdx.x;
+            v[u] = g < n4 ? p4[g] : float4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int u = 0; u < INFLIGHT; u++) {
+            const int g = g0 + u * NT + (int)threadIdx.x;
+            if (g < n4) {
+                const float c[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int e = 4 * g + q, j = e / 3, a = e - 3 * j;
+                    (a == 0 ? X : a == 1 ? Y : Z)[j] = c[q];
+                }
+            }
+        }
+    }
+    for (int e = 4 * n4 + (int)threadIdx.x; e < n3; e += NT) {
+        const int j = e / 3, a = e - 3 * j;
+        (a == 0 ? X : a == 1 ? Y : Z)[j] = pos[e];
+    }
 }
 
 // ---- all pairs ------------------------------------------------------------------------------------
@@ -106,35 +130,7 @@ __global__ void __launch_bounds__(ROWS_BLOCK) k_pairs_rows(const float *__restri
     extern __shared__ float lds_pos[];
     const int npad = (n + 3) & ~3;
     float *X = lds_pos, *Y = lds_pos + npad, *Z = lds_pos + 2 * npad;
-    {   // 3 n floats, 16 bytes at a time (the block is 16-byte aligned; the last, partial group goes float by float)
-        const int n3 = 3 * n, n4 = n3 >> 2;
-        const float4 *p4 = reinterpret_cast<const float4 *>(pos);
-        constexpr int INFLIGHT = 6;
-        for (int g0 = 0; g0 < n4; g0 += ROWS_BLOCK * INFLIGHT) {
-            float4 v[INFLIGHT];
-#pragma unroll
-            for (int u = 0; u < INFLIGHT; u++) {
-                const int g = g0 + u * ROWS_BLOCK + (int)threadIdx.x;
-                v[u] = g < n4 ? p4[g] : float4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int u = 0; u < INFLIGHT; u++) {
-                const int g = g0 + u * ROWS_BLOCK + (int)threadIdx.x;
-                if (g < n4) {
-                    const float c[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int e = 4 * g + q, j = e / 3, a = e - 3 * j;
-                        (a == 0 ? X : a == 1 ? Y : Z)[j] = c[q];
-                    }
-                }
-            }
-        }
-        for (int e = 4 * n4 + (int)threadIdx.x; e < n3; e += ROWS_BLOCK) {
-            const int j = e / 3, a = e - 3 * j;
-            (a == 0 ? X : a == 1 ? Y : Z)[j] = pos[e];
-        }
-    }
+    load_positions_soa<ROWS_BLOCK>(pos, n, X, Y, Z);
     __syncthreads();
     const int i = blockIdx.x * ROBOTS + (int)threadIdx.x / L, l = (int)threadIdx.x % L;
     const bool live = i < n;
@@ -207,35 +203,7 @@ __global__ void __launch_bounds__(GRID_BLOCK) k_grid_rows(const float *__restric
     uint16_t *hit = special + npad;                                     // [GRID_BLOCK][REG] the hits of this workgroup's robots as they are found
     __shared__ int32_t n_special;
     const int tid = (int)threadIdx.x;
-    {   // all positions, 16 bytes at a time (see k_pairs_rows)
-        const int n3 = 3 * n, n4 = n3 >> 2;
-        const float4 *p4 = reinterpret_cast<const float4 *>(pos);
-        constexpr int INFLIGHT = 6;
-        for (int g0 = 0; g0 < n4; g0 += GRID_BLOCK * INFLIGHT) {
-            float4 v[INFLIGHT];
-#pragma unroll
-            for (int u = 0; u < INFLIGHT; u++) {
-                const int g = g0 + u * GRID_BLOCK + tid;
-                v[u] = g < n4 ? p4[g] : float4{0.f, 0.f, 0.f, 0.f};
-            }
-#pragma unroll
-            for (int u = 0; u < INFLIGHT; u++) {
-                const int g = g0 + u * GRID_BLOCK + tid;
-                if (g < n4) {
-                    const float c[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-#pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const int e = 4 * g + q, j = e / 3, a = e - 3 * j;
-                        (a == 0 ? X : a == 1 ? Y : Z)[j] = c[q];
-                    }
-                }
-            }
-        }
-        for (int e = 4 * n4 + tid; e < n3; e += GRID_BLOCK) {
-            const int j = e / 3, a = e - 3 * j;
-            (a == 0 ? X : a == 1 ? Y : Z)[j] = pos[e];
-        }
-    }
+    load_positions_soa<GRID_BLOCK>(pos, n, X, Y, Z);
     for (int b = tid; b < GRID_M; b += GRID_BLOCK) fill[b] = 0;
     if (tid == 0) n_special = 0;
     __syncthreads();

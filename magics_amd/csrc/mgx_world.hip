@@ -18,7 +18,7 @@
 //   mgx_world_launch.inc — launches: confirm_resident, sweep, resident schedule launches, lingering launches (the host's side)
 //   mgx_world_abi.inc — C ABI: lifecycle, environment, robots, connections, factor kinds, flags
 //   mgx_world_topology.inc — C ABI: dynamic inter-robot topology — neighbour search, delete / create_interrobot_factors
-//   mgx_world_collisions.inc — C ABI: robot-robot collision bookkeeping on the device (the pass mgx_mission_tick_end enqueues)
+//   mgx_world_collisions.inc — C ABI: robot-robot and robot-environment collision bookkeeping on the device, one contact book under both (the passes mgx_mission_tick_end enqueues)
 //   mgx_world_missions.inc — C ABI: missions on the device, many ticks per call, fine-grained sweeps, schedules -> launches
 //   mgx_world_schedule.inc — C ABI: batches, mgx_iterate, prior changes, mgx_tick, resets, diagnostics, read-back
 //   mgx_world_shard.inc — C ABI: sharded worlds — exchange lists, migration, the in-engine transports (RCCL, direct, ghost records inside resident launches), hipIpc, pack / unpack

@@ -19,6 +19,7 @@
 #include "../../include/mgx.h"
 #include "gbp_math.h"
 #include "mgx_dev.h"
+#include "mgx_grid.h"
 
 namespace mgx {
 size_t sweep_lds_bytes(int K, int ir_edges);
@@ -619,40 +620,37 @@ struct mgx_world {
         size_t tr_cap = 0, tr_n = 0;
         DevMission d{};
     } mission;
-    // robot-robot collision bookkeeping on the device (mgx_collisions_*, mgx_collisions.hip): everything is keyed by robot id, so a
-    // relayout of the world's arrays moves nothing here — robots that join only make the per-robot arrays (and the stride of the
-    // pair bits) grow
-    struct Collisions {
+    // collision bookkeeping on the device (mgx_world_collisions.inc, mgx_collisions.hip).  What its two kinds share: the log, the
+    // contact counts and the robots' inputs — keyed by robot id, so a relayout of the world's arrays moves nothing here and
+    // robots that join only make the per-robot arrays grow
+    struct ContactBook {
         bool enabled = false;
-        uint32_t method = 0;
         size_t n_sized = 0;      // robots the per-robot arrays were last sized and the radii uploaded for
-        uint32_t stride = 0;     // of the pair bits
-        DevBuf<uint32_t> bits, cnt, per_robot;
-        DevBuf<int2> list[2];
-        DevBuf<CollEvent> log;
-        DevBuf<unsigned long long> words, head;
-        DevBuf<int32_t> next;
-        DevBuf<float> radius, pos;  // pos: positions the caller handed in (mgx_collisions_update)
+        DevBuf<ContactEvent> log;
+        DevBuf<unsigned long long> words;
+        DevBuf<uint32_t> per_robot;
+        DevBuf<float> radius, pos;  // pos: positions the caller handed in (mgx_collisions_update / mgx_env_collisions_update)
         DevBuf<uint8_t> alive;      // ... and who was alive then
-        uint32_t n_buckets = 0;
         uint64_t log_cap = 0, pass = 0;
-        std::vector<mgx_collision_event> host_log;  // the events fetched so far, in (pass, robot_a, robot_b) order
+        std::vector<ContactEvent> host_log;  // the events fetched so far, in (pass, a, b) order
+    };
+    // robot-robot (mgx_collisions_*): the pair bits (whose stride grows with the robots), the pair lists, the hash grid's links
+    struct Collisions : ContactBook {
+        uint32_t method = 0;
+        uint32_t stride = 0;     // of the pair bits
+        DevBuf<uint32_t> bits, cnt;
+        DevBuf<int2> list[2];
+        DevBuf<unsigned long long> head;
+        DevBuf<int32_t> next;
+        uint32_t n_buckets = 0;
         CollDev d{};
     } coll;
-    // robot-environment collision bookkeeping on the device (mgx_env_collisions_*, mgx_collisions.hip): the map's side is uploaded
-    // once by _enable; the per-robot arrays are keyed by robot id and only grow
-    struct EnvCollisions {
-        bool enabled = false;
-        size_t n_sized = 0;      // robots the per-robot arrays were last sized and the radii uploaded for
+    // robot-environment (mgx_env_collisions_*): the map's side, uploaded once by _enable, and the colliders every robot touches
+    struct EnvCollisions : ContactBook {
         DevBuf<EnvCollider> colliders;
-        DevBuf<float> verts, radius, pos;  // pos: positions the caller handed in (mgx_env_collisions_update)
-        DevBuf<uint32_t> cell_ptr, per_robot;
+        DevBuf<float> verts;
+        DevBuf<uint32_t> cell_ptr;
         DevBuf<int32_t> cell_idx, touching;
-        DevBuf<EnvCollEvent> log;
-        DevBuf<unsigned long long> words;
-        DevBuf<uint8_t> alive;
-        uint64_t log_cap = 0, pass = 0;
-        std::vector<mgx_env_collision_event> host_log;  // the events fetched so far, in (pass, robot, collider) order
         EnvCollDev d{};
     } envcoll;
     // a neighbour search that has been enqueued and not collected yet (neighbours_enqueue / neighbours_collect)

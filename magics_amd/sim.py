@@ -67,6 +67,36 @@ def environment_contacts(colliders, vertices, pos, rad):
     return out
 
 
+def _box(lo, hi):
+    return {"mins": [float(lo[0]), float(lo[1])], "maxs": [float(hi[0]), float(hi[1])]}
+
+
+def _edges(table, now, aabb):
+    """one step of the Free / Colliding state machine (CollisionHistory, collisions.rs:455-495) over table: key -> {"colliding",
+    "times", "aabbs"}.  now: key -> whatever aabb(key, value) needs to give (mins, maxs) of a contact that begins."""
+    for key, h in table.items():                                    # Colliding -> Free (also: a robot is gone)
+        if h["colliding"] and key not in now:
+            h["colliding"] = False
+    for key, what in now.items():                                   # Free -> Colliding: one collision, with its AABB
+        h = table.setdefault(key, {"colliding": False, "times": 0, "aabbs": []})
+        if not h["colliding"]:
+            h["colliding"] = True
+            h["times"] += 1
+            h["aabbs"].append(_box(*aabb(key, what)))
+
+
+def _take_in(table, read, a, b, what):
+    """the new events of a device log (World.collisions_read / env_collisions_read from the cursor on) into table; the new cursor"""
+    ev, total, dropped = read[:3]
+    if dropped:
+        raise hostlib.MgxError(f"the device's {what} log was full: {dropped} events were not stored")
+    for e in ev:
+        h = table.setdefault((int(e[a]), int(e[b])), {"colliding": True, "times": 0, "aabbs": []})
+        h["times"] += 1
+        h["aabbs"].append(_box(e["mins"], e["maxs"]))
+    return total
+
+
 class Simulation:
     def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None,
                  environment_collisions=False):
@@ -250,14 +280,7 @@ class Simulation:
         taken in first (the one read that waits for the device); "colliding" then only says that the pair has met — the
         Free / Colliding state itself stays on the device."""
         if getattr(self, "_dev_coll", False):
-            ev, total, dropped, _ = self.w.collisions_read(self._coll_cursor)
-            if dropped:
-                raise hostlib.MgxError(f"the device's collision log was full: {dropped} events were not stored")
-            for e in ev:
-                h = self._collisions.setdefault((int(e["robot_a"]), int(e["robot_b"])), {"colliding": True, "times": 0, "aabbs": []})
-                h["times"] += 1
-                h["aabbs"].append({"mins": [float(e["mins"][0]), float(e["mins"][1])], "maxs": [float(e["maxs"][0]), float(e["maxs"][1])]})
-            self._coll_cursor = total
+            self._coll_cursor = _take_in(self._collisions, self.w.collisions_read(self._coll_cursor), "robot_a", "robot_b", "collision")
         return self._collisions
 
     @collisions.setter
@@ -274,17 +297,8 @@ class Simulation:
         rs = rad[:, None] + rad[None, :]
         hit = np.triu(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] <= rs * rs, k=1)
         now = {(int(ids[i]), int(ids[j])): (i, j) for i, j in zip(*np.nonzero(hit))}
-        for key, h in self.collisions.items():                      # Colliding -> Free
-            if h["colliding"] and key not in now:
-                h["colliding"] = False
-        for key, (i, j) in now.items():                             # Free -> Colliding: one collision, with the AABBs' intersection
-            h = self.collisions.setdefault(key, {"colliding": False, "times": 0, "aabbs": []})
-            if not h["colliding"]:
-                h["colliding"] = True
-                h["times"] += 1
-                lo = np.maximum(pos[i] - rad[i], pos[j] - rad[j])
-                hi = np.minimum(pos[i] + rad[i], pos[j] + rad[j])
-                h["aabbs"].append({"mins": [float(lo[0]), float(lo[1])], "maxs": [float(hi[0]), float(hi[1])]})
+        _edges(self.collisions, now, lambda key, ij: (np.maximum(pos[ij[0]] - rad[ij[0]], pos[ij[1]] - rad[ij[1]]),
+                                                      np.minimum(pos[ij[0]] + rad[ij[0]], pos[ij[1]] + rad[ij[1]])))
 
     # update_robot_environment_collisions (planner/collisions.rs:368-438, FixedUpdate): every live robot's Ball against every
     # collider of the map (hostlib.env_colliders), the contact of include/mgx.h, the same Free / Colliding state machine; a
@@ -294,14 +308,8 @@ class Simulation:
         """(robot, collider) -> {"colliding", "times", "aabbs"}; empty while the option is off.  With the pass on the device the new
         events of its log are taken in first (the one read that waits for the device)."""
         if self._dev_env_coll:
-            ev, total, dropped, _ = self.w.env_collisions_read(self._env_coll_cursor)
-            if dropped:
-                raise hostlib.MgxError(f"the device's environment collision log was full: {dropped} events were not stored")
-            for e in ev:
-                h = self._env_collisions.setdefault((int(e["robot"]), int(e["collider"])), {"colliding": True, "times": 0, "aabbs": []})
-                h["times"] += 1
-                h["aabbs"].append({"mins": [float(e["mins"][0]), float(e["mins"][1])], "maxs": [float(e["maxs"][0]), float(e["maxs"][1])]})
-            self._env_coll_cursor = total
+            self._env_coll_cursor = _take_in(self._env_collisions, self.w.env_collisions_read(self._env_coll_cursor), "robot", "collider",
+                                             "environment collision")
         return self._env_collisions
 
     def _collide_environment(self, alive, translation):
@@ -314,17 +322,8 @@ class Simulation:
             pos = np.ascontiguousarray(np.asarray(translation)[ids][:, [0, 2]], dtype=F)
             hit = environment_contacts(self._colliders, self._collider_vertices, pos, rad) & np.isfinite(pos).all(axis=1)[:, None]
             seen = {(int(ids[i]), int(k)): i for i, k in zip(*np.nonzero(hit))}
-        for key, h in self._env_collisions.items():                 # Colliding -> Free (also: the robot is gone)
-            if h["colliding"] and key not in seen:
-                h["colliding"] = False
-        for key, i in seen.items():                                 # Free -> Colliding
-            h = self._env_collisions.setdefault(key, {"colliding": False, "times": 0, "aabbs": []})
-            if not h["colliding"]:
-                h["colliding"] = True
-                h["times"] += 1
-                col = self._colliders[key[1]]
-                lo, hi = np.maximum(pos[i] - rad[i], col["mins"]), np.minimum(pos[i] + rad[i], col["maxs"])
-                h["aabbs"].append({"mins": [float(lo[0]), float(lo[1])], "maxs": [float(hi[0]), float(hi[1])]})
+        _edges(self._env_collisions, seen, lambda key, i: (np.maximum(pos[i] - rad[i], self._colliders[key[1]]["mins"]),
+                                                           np.minimum(pos[i] + rad[i], self._colliders[key[1]]["maxs"])))
 
     def _flush_trackers(self, synchronise=False):
         """device missions: the samples of the last tick, taken from the Transforms that tick sent to the host behind its

@@ -374,37 +374,45 @@ class World:
         self._chk(self._L.mgx_mission_read(self._w, tr.ctypes.data, tg.ctypes.data, fin.ctypes.data))
         return tr, tg, fin
 
-    # -- robot-robot collision bookkeeping on the device (include/mgx.h, mgx_collisions_*) --------------------------
+    # -- collision bookkeeping on the device (include/mgx.h): robot-robot (mgx_collisions_*), robot-environment (mgx_env_collisions_*)
+    def _contacts_update(self, update, positions):
+        pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        if pos is not None and len(pos) != self.num_robots()[0]:
+            raise ValueError("one position per robot of the world")
+        self._chk(update(self._w, None if pos is None else pos.ctypes.data))
+
+    def _contacts_read(self, read, dtype, first, strict=True):
+        """two calls: how many events there are, then the events from `first` on.  A status may come with every output filled."""
+        n, first = self.num_robots()[0], int(first)
+        tot, drop = C.c_uint64(), C.c_uint64()
+        per = np.zeros(n, np.uint32)
+        ev = np.zeros(0, dtype)
+        rc = read(self._w, first, None, 0, C.byref(tot), C.byref(drop), per.ctypes.data)
+        if tot.value > first:
+            ev = np.zeros(tot.value - first, dtype)
+            rc = read(self._w, first, ev.ctypes.data, len(ev), C.byref(tot), C.byref(drop), per.ctypes.data)
+            ev = ev[:max(0, min(len(ev), tot.value - first))]
+        if strict:
+            self._chk(rc)
+            return ev, int(tot.value), int(drop.value), per
+        return ev, int(tot.value), int(drop.value), per, rc
+
     def collisions_enable(self, enabled=True, method=hostlib.NEIGHBOURS_AUTO, event_capacity=0):
         """while on, every mission tick ends with one pass of update_robot_robot_collisions on the device (no synchronisation)"""
         self._chk(self._L.mgx_collisions_enable(self._w, 1 if enabled else 0, int(method), int(event_capacity)))
 
     def collisions_update(self, positions=None):
         """one pass over the caller's Transforms [n, 3] f32 (None: the device's mission Transforms); enqueued, not waited for"""
-        pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
-        if pos is not None and len(pos) != self.num_robots()[0]:
-            raise ValueError("one position per robot of the world")
-        self._chk(self._L.mgx_collisions_update(self._w, None if pos is None else pos.ctypes.data))
+        self._contacts_update(self._L.mgx_collisions_update, positions)
 
     def collisions_read(self, first=0):
         """(events from `first` on in (pass, robot_a, robot_b) order — a structured array with fields pass, robot_a, robot_b,
         mins [2], maxs [2] —, events in the log, events dropped because it was full, contacts per robot).  Synchronises."""
-        n, _ = self.num_robots()
-        tot, drop = C.c_uint64(), C.c_uint64()
-        per = np.zeros(n, np.uint32)
-        ev = np.zeros(0, hostlib.collision_event_dtype())
-        rc = self._L.mgx_collisions_read(self._w, int(first), None, 0, C.byref(tot), C.byref(drop), per.ctypes.data)
-        if rc == 0 and tot.value > first:
-            ev = np.zeros(tot.value - int(first), hostlib.collision_event_dtype())
-            rc = self._L.mgx_collisions_read(self._w, int(first), ev.ctypes.data, len(ev), C.byref(tot), C.byref(drop), per.ctypes.data)
-            ev = ev[:max(0, min(len(ev), tot.value - int(first)))]
-        self._chk(rc)
-        return ev, int(tot.value), int(drop.value), per
+        return self._contacts_read(self._L.mgx_collisions_read, hostlib.collision_event_dtype(), first)
 
     def collisions_clear(self):
         self._chk(self._L.mgx_collisions_clear(self._w))
 
-    # -- robot-environment collision bookkeeping on the device (include/mgx.h, mgx_env_collisions_*) ---------------
     def env_collisions_enable(self, env, event_capacity=0):
         """env: an environment dict — its colliders (hostlib.env_colliders) go to the device once and every mission tick ends with
         one pass of update_robot_environment_collisions (no synchronisation); None: off, the state is dropped"""
@@ -417,29 +425,14 @@ class World:
 
     def env_collisions_update(self, positions=None):
         """one pass over the caller's Transforms [n, 3] f32 (None: the device's mission Transforms); enqueued, not waited for"""
-        pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
-        if pos is not None and len(pos) != self.num_robots()[0]:
-            raise ValueError("one position per robot of the world")
-        self._chk(self._L.mgx_env_collisions_update(self._w, None if pos is None else pos.ctypes.data))
+        self._contacts_update(self._L.mgx_env_collisions_update, positions)
 
     def env_collisions_read(self, first=0, strict=True):
         """(events from `first` on in (pass, robot, collider) order — a structured array with fields pass, robot, collider,
         mins [2], maxs [2] —, events in the log, events dropped because it was full, contacts per robot).  Synchronises.
         strict=False: a status that comes with filled outputs (MGX_ERR_STATE: a robot touched more colliders at once than the
         device remembers) is returned as a fifth element instead of being raised."""
-        n, _ = self.num_robots()
-        tot, drop = C.c_uint64(), C.c_uint64()
-        per = np.zeros(n, np.uint32)
-        ev = np.zeros(0, hostlib.env_collision_event_dtype())
-        rc = self._L.mgx_env_collisions_read(self._w, int(first), None, 0, C.byref(tot), C.byref(drop), per.ctypes.data)
-        if tot.value > first:
-            ev = np.zeros(tot.value - int(first), hostlib.env_collision_event_dtype())
-            rc = self._L.mgx_env_collisions_read(self._w, int(first), ev.ctypes.data, len(ev), C.byref(tot), C.byref(drop), per.ctypes.data)
-            ev = ev[:max(0, min(len(ev), tot.value - int(first)))]
-        if strict:
-            self._chk(rc)
-            return ev, int(tot.value), int(drop.value), per
-        return ev, int(tot.value), int(drop.value), per, rc
+        return self._contacts_read(self._L.mgx_env_collisions_read, hostlib.env_collision_event_dtype(), first, strict)
 
     def env_collisions_clear(self):
         self._chk(self._L.mgx_env_collisions_clear(self._w))

@@ -253,6 +253,45 @@ def test_robots_that_join_while_others_overlap():
     assert _export(dev) == _export(host)
 
 
+@pytest.mark.parametrize("method", [hostlib.NEIGHBOURS_PAIRS, hostlib.NEIGHBOURS_GRID], ids=["pairs", "grid"])
+def test_robots_join_across_the_first_sizing_while_a_pair_overlaps(method):
+    """The first sizing (for the two robots of the first pass) leaves room for R + R/4 + 64 per-robot counts
+    and a pair-bit stride of that rounded up to 32.  One robot more than the stride holds joins while pair (0, 1) overlaps:
+    the counts move to the front of a longer array and the pair's bit is set again under the new stride (k_collisions_rebits
+    with a list that is not empty) — no second event for the held pair, one for a pair with an id beyond the old stride,
+    and the state machine goes on as before."""
+    first = 2
+    room = first + first // 4 + 64                     # DevBuf::reserve: the room the first sizing leaves for the counts
+    stride = (room + 31) & ~31
+    n = stride + 1
+    assert first < room < n                            # (both growth paths are crossed)
+    radii = np.ones(n, F)
+    w, chk = _bare_world(radii[:first]), Checker()
+    w.collisions_enable(True, method=method)
+
+    def run(pos, fresh):
+        w.collisions_update(pos)
+        assert chk.step(list(range(len(pos))), radii, pos) == fresh
+        ev, total, dropped, per = w.collisions_read()
+        assert (total, dropped) == (len(chk.events), 0) and _device_events(ev) == chk.events
+        assert np.array_equal(per, chk.per_robot(len(pos)))
+    pos = np.zeros((n, 3), F)
+    pos[:, 0], pos[:, 1], pos[:, 2] = 10.0 * np.arange(n), -1.5, 100.0   # apart from everyone ...
+    pos[0], pos[1] = (0.0, -1.5, 0.0), (1.0, -1.5, 0.0)                  # ... but (0, 1), which overlap from the start
+    pos[n - 1, 0] = pos[n - 2, 0] + 0.5                                  # ... and the last two, which overlap each other
+    run(pos[:first], 1)
+    mean0, prior, dt = scenarios.robot_initial_state((0.0, 0.0, 5.0, 0.0), (10.0, 0.0, 5.0, 0.0), scenarios.timesteps_for_K(10), 1.0, 5.0, 5.0)
+    for _ in range(n - first):
+        w.add_robot(mean0, prior, dt, 1.0)
+    run(pos, 1)
+    assert chk.events[-1][:3] == (1, n - 2, n - 1) and n - 1 >= stride
+    pos[1, 0] = 5.0                                                      # (0, 1) part for a pass ...
+    run(pos, 0)
+    pos[1, 0] = 1.0                                                      # ... and meet again
+    run(pos, 1)
+    assert [e[:3] for e in chk.events] == [(0, 0, 1), (1, n - 2, n - 1), (3, 0, 1)]
+
+
 def test_off_means_off():
     L = hostlib.lib()
     sc = _scenario("Circle Experiment")

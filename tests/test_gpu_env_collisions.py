@@ -358,6 +358,42 @@ def test_a_radius_larger_than_a_tile_finds_contacts_in_every_cell():
     assert _device_events(ev) == chk.events and (total, dropped) == (10, 0) and list(per) == [10, 0]
 
 
+def test_robots_join_across_the_first_sizing_while_a_contact_is_held():
+    """The first sizing (for the two robots of the first pass) leaves room for R + R/4 + 64 per-robot
+    counts and as many sets of slots.  One robot more than that joins while robot 0 rests on a collider: counts and `touching`
+    slots move to the front of longer arrays — no second event for the held contact, one for the new robot, the earlier
+    count kept."""
+    env = _cross_grid()
+    chk = Checker(env)
+    first = 2
+    n = first + first // 4 + 64 + 1                    # DevBuf::reserve: the room the first sizing leaves for the counts; one more
+    radii = np.full(n, 0.5, F)
+    cuboids = np.nonzero(chk.cols["kind"] == CUBOID)[0]
+    held, met = int(cuboids[0]), int(cuboids[-1])
+    points = [(-95.0 + 10.0 * (i % 20), -95.0 + 10.0 * (i // 20)) for i in range(n)]   # tile centres: nothing there
+    points[0] = (float(chk.cols["tx"][held]), float(chk.cols["tz"][held]))
+    points[n - 1] = (float(chk.cols["tx"][met]), float(chk.cols["tz"][met]))
+    gap = signed_gap(chk.cols, chk.verts, points, radii)
+    assert [list(np.nonzero(g <= 0)[0]) for g in gap] == [[held]] + [[]] * (n - 2) + [[met]] and (np.abs(gap) > 0.05).all()
+    pos = _xyz(points)
+    w = _bare_world(radii[:first])
+    w.env_collisions_enable(env)
+
+    def run(pos, fresh):
+        w.env_collisions_update(pos)
+        assert chk.step(list(range(len(pos))), radii, pos) == fresh
+        ev, total, dropped, per = w.env_collisions_read()
+        assert (total, dropped) == (len(chk.events), 0) and _device_events(ev) == chk.events
+        assert np.array_equal(per, chk.per_robot(len(pos)))
+        return per
+    assert list(run(pos[:first], 1)) == [1, 0]
+    for r in radii[first:]:
+        _add(w, r)
+    per = run(pos, 1)
+    assert [e[:3] for e in chk.events] == [(0, 0, held), (1, n - 1, met)]
+    assert list(per) == [1] + [0] * (n - 2) + [1]
+
+
 def test_off_means_off():
     import torch
     L = hostlib.lib()

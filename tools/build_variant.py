@@ -24,7 +24,7 @@ if rev:
     units = [u for u in g.UNITS if os.path.exists(os.path.join(g.CSRC, u[0]))]
     if len(units) != len(g.UNITS):  # a revision from before the sweep kernel was split into several objects
         units = [(s, []) for s in ("mgx_kernels.hip", "mgx_topology.hip", "mgx_env.hip", "mgx_world.hip", "mgx_host.cpp", "mgx_linalg.cpp")]
-        g.HEADERS = [h for h in g.HEADERS if os.path.exists(os.path.join(g.CSRC, h))]
+    g.HEADERS = [h for h in g.HEADERS if os.path.exists(os.path.join(g.CSRC, h))]  # (a revision from before a header was split off: mgx_grid.h)
     g.UNITS = units
     g.SOURCES = sorted({u[0] for u in units})
 g.build_library(out, ["-ffp-contract=off"], extra_defines=defs)
