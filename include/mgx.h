@@ -213,6 +213,25 @@ int mgx_last_launch_count(mgx_world *w, uint32_t *n_launches);
 #define MGX_SWEEP_FORM_POSTED 2    /* posted into a lingering resident launch */
 #define MGX_SWEEP_FORM_SHARDED 3   /* one resident launch on a sharded world */
 int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *form, int32_t *resident_capacity);
+/* How the last neighbour search of this world (mgx_neighbours, mgx_update_topology, a mission tick's) ran, as the branch that
+ * launched it chose: the kernel it launched LAST (MGX_SEARCH_*), the row capacity it launched it with (the one-pass kernels write
+ * rows of a fixed capacity that the world doubles when a row outgrows it; 0 for the two-pass forms), and how many search launches
+ * the call made (1; 2 when a row outgrew the capacity and the search ran again with more room, or when the two-pass forms' rows
+ * outgrew the buffer their filling pass guessed and that pass ran again).  n_changed: the one-pass grid kernels of a topology
+ * pass say which robots' rows differ from the pass before, and the host's create / delete pass looks at those only — the number of
+ * robots so flagged, or -1 where no flags reached that pass (a search outside a topology pass, an all-pairs or two-pass kernel, a
+ * search that was run again, a world with removed robots, order keys that do not ascend with the robot ids).  changed (may be
+ * NULL): where flags reached it and capacity >= the number of robots, one byte per robot (1: looked at).  Host bookkeeping only:
+ * no synchronisation; any pointer may be NULL. */
+#define MGX_SEARCH_NONE -1           /* no search since the world was made */
+#define MGX_SEARCH_TWO_PASS_PAIRS 0  /* count, scan, fill: all pairs */
+#define MGX_SEARCH_TWO_PASS_GRID 1   /* count, scan, fill: hash grid in device memory */
+#define MGX_SEARCH_ROWS_PAIRS_4 2    /* one pass, all pairs, four lanes per robot, workgroups of 64 */
+#define MGX_SEARCH_ROWS_PAIRS_2 3    /* one pass, all pairs, two lanes per robot, workgroups of 128 */
+#define MGX_SEARCH_ROWS_GRID_16 4    /* one pass, hash grid in LDS, rows of up to 16 */
+#define MGX_SEARCH_ROWS_GRID_32 5    /* one pass, hash grid in LDS, rows of up to 32 */
+int mgx_last_search(mgx_world *w, int32_t *kernel, int32_t *row_cap, int32_t *n_launches, int32_t *n_changed, uint8_t *changed,
+                    uint32_t capacity);
 
 /* LINGERING resident launches — schedules issued back to back ride in ONE launch.  The reference's driver runs iterate_gbp_v2
  * tick after tick (robot.rs:85-108, a .chain() in FixedUpdate) with nothing in between but the two prior updates that mgx_tick

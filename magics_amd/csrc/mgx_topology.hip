@@ -14,6 +14,7 @@
 #include <cstdint>
 #include <limits>
 
+#include "../../include/mgx.h"
 #include "gbp_math.h"
 #include "mgx_grid.h"
 
@@ -372,9 +373,10 @@ static size_t neighbours_rows_lds(int n, int32_t cap) {
 }
 int neighbours_prev_stride() { return NEIGHBOURS_PREV_STRIDE; }
 int32_t neighbours_changed_bit() { return NEIGHBOURS_CHANGED; }
-// prev / prev_valid (may be null / 0): see k_grid_rows; *flagged says whether the kernel that ran marks the counts of changed rows
+// prev / prev_valid (may be null / 0): see k_grid_rows; *flagged says whether the kernel that ran marks the counts of changed rows;
+// *ran (may be null): the kernel launched (MGX_SEARCH_*, mgx_last_search), written by the branch that launched it
 hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, float *stage,
-                           int32_t *prev, int prev_valid, bool *flagged) {
+                           int32_t *prev, int prev_valid, bool *flagged, int32_t *ran) {
     if (flagged) *flagged = false;
     if (n <= 0) return hipSuccess;
     if (stage) {
@@ -388,15 +390,23 @@ hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, i
         const double inv_cell = 1.0 / ((double)radius * 1.001);
         const dim3 grid((unsigned)((n + GRID_ROBOTS - 1) / GRID_ROBOTS));
         if (!flagged) prev = nullptr;  // (a caller that does not ask cannot read flagged counts)
-        if (cap <= 16) hipLaunchKernelGGL(k_grid_rows<16>, grid, dim3(GRID_BLOCK), neighbours_rows_lds(n, 16), s, pos, n, s_max, inv_cell, cap, cnt, rows, prev, prev_valid);
-        else hipLaunchKernelGGL(k_grid_rows<32>, grid, dim3(GRID_BLOCK), neighbours_rows_lds(n, 32), s, pos, n, s_max, inv_cell, cap, cnt, rows, prev, prev_valid);
+        if (cap <= 16) {
+            hipLaunchKernelGGL(k_grid_rows<16>, grid, dim3(GRID_BLOCK), neighbours_rows_lds(n, 16), s, pos, n, s_max, inv_cell, cap, cnt, rows, prev, prev_valid);
+            if (ran) *ran = MGX_SEARCH_ROWS_GRID_16;
+        } else {
+            hipLaunchKernelGGL(k_grid_rows<32>, grid, dim3(GRID_BLOCK), neighbours_rows_lds(n, 32), s, pos, n, s_max, inv_cell, cap, cnt, rows, prev, prev_valid);
+            if (ran) *ran = MGX_SEARCH_ROWS_GRID_32;
+        }
         if (flagged) *flagged = prev != nullptr;
         return hipGetLastError();
     }
-    if (n > 512 && n <= 1024)
+    if (n > 512 && n <= 1024) {
         hipLaunchKernelGGL((k_pairs_rows<2, 128>), dim3((unsigned)((n + 63) / 64)), dim3(128), lds, s, pos, n, s_max, cap, cnt, rows);
-    else
+        if (ran) *ran = MGX_SEARCH_ROWS_PAIRS_2;
+    } else {
         hipLaunchKernelGGL((k_pairs_rows<4, 64>), dim3((unsigned)((n + 15) / 16)), dim3(64), lds, s, pos, n, s_max, cap, cnt, rows);
+        if (ran) *ran = MGX_SEARCH_ROWS_PAIRS_4;
+    }
     return hipGetLastError();
 }
 

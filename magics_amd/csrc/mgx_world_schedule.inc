@@ -370,6 +370,18 @@ int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *fo
     }
     return MGX_OK;
 }
+int mgx_last_search(mgx_world *w, int32_t *kernel, int32_t *row_cap, int32_t *n_launches, int32_t *n_changed, uint8_t *changed,
+                    uint32_t capacity) {
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (kernel) *kernel = w->last_search_kernel;
+    if (row_cap) *row_cap = w->last_search_cap;
+    if (n_launches) *n_launches = w->last_search_launches;
+    if (n_changed) *n_changed = w->last_search_changed;
+    // (flags reach a pass only for a world without removed robots: one byte per robot of the world)
+    if (changed && w->last_search_changed >= 0 && (size_t)capacity >= w->robots.size() && w->scratch_chg.size() >= w->robots.size())
+        memcpy(changed, w->scratch_chg.data(), w->robots.size());
+    return MGX_OK;
+}
 
 int mgx_num_robots(mgx_world *w, uint32_t *n_robots, uint32_t *n_variables) {
     MGX_ENTER(w);

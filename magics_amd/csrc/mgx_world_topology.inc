@@ -53,6 +53,8 @@ static int neighbours_enqueue(mgx_world *w, const float *pos, float radius, uint
         pos = packed.data();
     }
     const int n = (int)alive.size();
+    w->last_search_launches = 0;
+    w->last_search_changed = -1;  // (until flags reach a pass: topology_bookkeeping)
     const bool usable_radius = std::isfinite(radius) && radius > 0.f;
     bool grid = method == MGX_NEIGHBOURS_GRID || (method == MGX_NEIGHBOURS_AUTO && n >= 512);
     if (!usable_radius) grid = false;  // radius <= 0 / NaN / inf: every pair has to see the predicate
@@ -127,7 +129,9 @@ static int neighbours_enqueue(mgx_world *w, const float *pos, float radius, uint
         bool chg_written = false;
         HIP_TRY(neighbours_rows(from_missions ? w->nb_pos.p : reinterpret_cast<const float *>(dp), n, radius, cap,
                                 reinterpret_cast<int32_t *>(dp + off_cnt), reinterpret_cast<int32_t *>(dp + off_rows), s, nullptr,
-                                keep_rows ? w->nb_prev.p : nullptr, prev_valid, &chg_written));
+                                keep_rows ? w->nb_prev.p : nullptr, prev_valid, &chg_written, &w->last_search_kernel));
+        w->last_search_cap = cap;
+        w->last_search_launches++;
         ps.has_chg = chg_written;
         ps.n = n; ps.n_all = n_all; ps.compact = compact; ps.guess = 0; ps.off_ptr = off_cnt; ps.off_idx = off_rows;
         ps.radius = radius; ps.method = method; ps.grid = false; ps.M = M; ps.rows = true; ps.row_cap = cap; ps.from_missions = from_missions;
@@ -146,6 +150,11 @@ static int neighbours_enqueue(mgx_world *w, const float *pos, float radius, uint
     }
     HIP_TRY(neighbours_count(w->nb_pos.p, n, radius, grid, M, w->nb_cnt.p, w->nb_bucket_cnt.p, w->nb_bucket_ptr.p, w->nb_cursor.p,
                              w->nb_members.p, w->nb_special.p, w->nb_nspecial.p, w->nb_ptr.p, s));
+    if (n > 0) {  // (an empty query launches nothing)
+        w->last_search_kernel = grid ? MGX_SEARCH_TWO_PASS_GRID : MGX_SEARCH_TWO_PASS_PAIRS;
+        w->last_search_cap = 0;
+        w->last_search_launches++;
+    }
     // The second pass needs the total to size its output — one more host round trip.  Instead it runs right
     // away into the buffer left from the last search (the kernels leave it alone if the rows do not fit), and
     // rows and counts come back together; only a total beyond the guess costs the second trip.
@@ -197,7 +206,10 @@ static int neighbours_collect(mgx_world *w, mgx_world::PendingSearch &ps, std::v
             HIP_TRY(hipHostGetDevicePointer(&dpin, pin, 0));
             char *dp = static_cast<char *>(dpin);
             HIP_TRY(neighbours_rows(ps.from_missions ? w->nb_pos.p : reinterpret_cast<const float *>(dp), n, ps.radius, cap,
-                                    reinterpret_cast<int32_t *>(dp + ps.off_ptr), reinterpret_cast<int32_t *>(dp + off_rows), s, nullptr));
+                                    reinterpret_cast<int32_t *>(dp + ps.off_ptr), reinterpret_cast<int32_t *>(dp + off_rows), s, nullptr,
+                                    nullptr, 0, nullptr, &w->last_search_kernel));
+            w->last_search_cap = cap;
+            w->last_search_launches++;
             HIP_TRY(hipStreamSynchronize(s));
             cnt = reinterpret_cast<const int32_t *>(pin + ps.off_ptr);
         }
@@ -221,6 +233,7 @@ static int neighbours_collect(mgx_world *w, mgx_world::PendingSearch &ps, std::v
         if (total) memcpy(idx.data(), pin + ps.off_idx, sizeof(int32_t) * total);
     } else {
         idx.assign(total, 0);
+        if (n > 0 && guess > 0 && w->nb_idx.p) w->last_search_launches++;  // (the filling pass ran into the guessed buffer: once more)
         HIP_TRY(w->nb_idx.reserve(total));
         HIP_TRY(neighbours_fill(w->nb_pos.p, n, ps.radius, ps.grid, ps.M, w->nb_bucket_ptr.p, w->nb_members.p, w->nb_special.p,
                                 w->nb_nspecial.p, w->nb_ptr.p, w->nb_idx.p, (int32_t)total, s));
@@ -320,6 +333,11 @@ static int topology_bookkeeping(mgx_world *w, std::vector<int32_t> &ptr, std::ve
     int rc = MGX_OK;
     w->nb_prev_valid = false;  // (until this pass has gone through)
     const int n = (int)w->robots.size();
+    w->last_search_changed = -1;
+    if (chg) {
+        w->last_search_changed = 0;
+        for (int r = 0; r < n; r++) w->last_search_changed += chg[r] ? 1 : 0;
+    }
     uint32_t created = 0, deleted = 0;
     // a robot's row of the search and its connection set are both ascending in order key (BTreeSet<Entity>): merges
     ConnSets &cs = w->sets;

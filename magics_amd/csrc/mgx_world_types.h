@@ -73,7 +73,7 @@ hipError_t neighbours_fill(const float *pos, int n, float radius, bool grid, uin
                            const int32_t *members, const int32_t *special, const int32_t *n_special, const int32_t *ptr,
                            int32_t *idx, int32_t cap, hipStream_t s);
 hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, float *stage,
-                           int32_t *prev = nullptr, int prev_valid = 0, bool *flagged = nullptr);
+                           int32_t *prev = nullptr, int prev_valid = 0, bool *flagged = nullptr, int32_t *ran = nullptr);
 int neighbours_prev_stride();
 int32_t neighbours_changed_bit();
 // mgx_collisions.hip
@@ -670,6 +670,10 @@ struct mgx_world {
     uint32_t last_sweep_launches = 0;  // sweep-kernel launches of the last mgx_iterate / mgx_tick call (mgx_last_launch_count)
     SweepRan last_sweep;               // the sweep instantiation it launched last (mgx_last_sweep) ...
     int32_t last_sweep_form = -1;      // ... and in which form (MGX_SWEEP_FORM_*; -1: none)
+    // the last neighbour search (mgx_last_search): the kernel it launched last, written by the branch that launched it, with which
+    // row capacity, in how many launches — and how many robots' changed-row flags reached the pass behind it (-1: none did; the
+    // flags themselves are scratch_chg)
+    int32_t last_search_kernel = MGX_SEARCH_NONE, last_search_cap = 0, last_search_launches = 0, last_search_changed = -1;
     // message counters are advanced lazily: launches and prior changes are only logged here
     struct CountEntry { uint8_t ext, in; int n_int, robot; uint64_t times; };
     std::vector<CountEntry> clog;

@@ -26,6 +26,8 @@ STEP_INTERNAL = 1
 STEP_EXTERNAL = 2
 NEIGHBOURS_AUTO, NEIGHBOURS_PAIRS, NEIGHBOURS_GRID = 0, 1, 2
 RESIDENT_NONE, RESIDENT_RAN, RESIDENT_DECLINED = 0, 1, 2
+# mgx_last_search: the kernel a neighbour search launched last
+SEARCH_NONE, SEARCH_TWO_PASS_PAIRS, SEARCH_TWO_PASS_GRID, SEARCH_ROWS_PAIRS_4, SEARCH_ROWS_PAIRS_2, SEARCH_ROWS_GRID_16, SEARCH_ROWS_GRID_32 = -1, 0, 1, 2, 3, 4, 5
 HALO_PUSH, HALO_WAIT = 1, 2
 HINT_NEXT_STARTS_EXTERNAL = 1
 
@@ -194,6 +196,7 @@ SYMBOLS = {
     "mgx_num_robots": (C.c_int, [_V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mgx_last_launch_count": (C.c_int, [_V, C.POINTER(C.c_uint32)]),
     "mgx_last_sweep": (C.c_int, [_V, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mgx_last_search": (C.c_int, [_V, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _V, C.c_uint32]),
     "mgx_flush": (C.c_int, [_V]),
     "mgx_set_linger": (C.c_int, [_V, C.c_int32]),
     "mgx_linger_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),

@@ -44,6 +44,7 @@ class World:
         self._chk(self._L.mgx_world_create(C.byref(self._p), C.byref(h)))
         self._w = h
         self._next_key = 0
+        self._n_ids = 0  # robot ids handed out so far (ghosts and removed robots included)
         self._args = {}  # array arguments seen before: id -> (the array, its address), see _arg
         self.stream_handle = 0  # raw HIP stream every launch of this world goes to (0: the default stream)
         if stream is not None:
@@ -118,6 +119,7 @@ class World:
         d.ghost = 1 if ghost else 0
         rid = C.c_int32(-1)
         self._chk(self._L.mgx_robot_add(self._w, C.byref(d), C.byref(rid)))
+        self._n_ids = max(self._n_ids, rid.value + 1)
         return rid.value
 
     def ir_connect(self, owner, other, first_robot_number):
@@ -148,11 +150,17 @@ class World:
         self._chk(self._L.mgx_set_antennas(self._w, robots.size, robots.ctypes.data, active.ctypes.data))
 
     # -- dynamic inter-robot topology (robot.rs:1362-1586) --------------------------------------
-    def neighbours(self, positions, radius, method=hostlib.NEIGHBOURS_AUTO):
-        """update_robot_neighbours: CSR (row_ptr, neighbours) of robots_within_comms_range."""
+    def neighbours(self, positions, radius, method=hostlib.NEIGHBOURS_AUTO, capacity=None):
+        """update_robot_neighbours: CSR (row_ptr, neighbours) of robots_within_comms_range.  capacity: ONE search into a buffer
+        of that many entries (an error if the rows need more) instead of a sizing search and a second one."""
         pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         ptr = np.zeros(pos.shape[0] + 1, dtype=np.int32)
         need = C.c_uint64()
+        if capacity is not None:
+            idx = np.zeros(max(int(capacity), 1), dtype=np.int32)
+            self._chk(self._L.mgx_neighbours(self._w, pos.ctypes.data, float(radius), method, ptr.ctypes.data, idx.ctypes.data,
+                                             int(capacity), C.byref(need)))
+            return ptr, idx[:need.value]
         self._chk(self._L.mgx_neighbours(self._w, pos.ctypes.data, float(radius), method, ptr.ctypes.data, None, 0, C.byref(need)))
         idx = np.zeros(max(need.value, 1), dtype=np.int32)
         self._chk(self._L.mgx_neighbours(self._w, pos.ctypes.data, float(radius), method, ptr.ctypes.data, idx.ctypes.data,
@@ -479,6 +487,17 @@ class World:
         v = [C.c_int32() for _ in range(4)]
         self._chk(self._L.mgx_last_sweep(self._w, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
+
+    def last_search(self):
+        """how the last neighbour search ran (mgx_last_search): (kernel, row_cap, n_launches, n_changed, changed) — the kernel it
+        launched last (hostlib.SEARCH_*), with which row capacity (0: the two-pass forms), in how many launches, how many robots'
+        changed-row flags reached the topology pass behind it (-1: none did) and those flags, one uint8 per robot (None with -1)"""
+        v = [C.c_int32() for _ in range(4)]
+        n = self._n_ids
+        chg = np.full(max(n, 1), 255, dtype=np.uint8)  # (left as it is where no flags are copied)
+        self._chk(self._L.mgx_last_search(self._w, *[C.byref(x) for x in v], chg.ctypes.data, n))
+        k, cap, launches, n_changed = (int(x.value) for x in v)
+        return k, cap, launches, n_changed, (chg[:n] if n_changed >= 0 and (n == 0 or chg[0] != 255) else None)
 
     def note_change_priors(self, robots, var_ix):
         """counters only: prior changes another rank applied to robots that are ghosts here (mgx_note_change_priors)"""

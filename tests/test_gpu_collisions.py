@@ -310,3 +310,36 @@ def test_off_means_off():
         assert np.array_equal(x, y)
     assert np.array_equal(on.translation, off.translation)
     assert on.w.collisions_read()[2] == 0
+
+
+_LATTICE = {}
+
+
+def _tangent_lattice():
+    """1024 robots of radius 0.5 on the integer lattice [-16, 16)^2: every 4-neighbour pair exactly tangent (1 <= 1 in f32: a
+    contact), every diagonal pair apart, and with cells of 1.001 tangent pairs in different cells on both sides of zero.  Three
+    passes: the lattice, the lattice x 1.5 (everyone parts), the lattice again — and what the host pass makes of them."""
+    if not _LATTICE:
+        k = np.arange(1024)
+        pos = np.zeros((1024, 3), F)
+        pos[:, 0], pos[:, 1], pos[:, 2] = (k % 32) - 16, -1.5, (k // 32) - 16
+        passes = [pos, (pos * F(1.5)).astype(F), pos.copy()]
+        radii = np.full(1024, 0.5, F)
+        chk = Checker()
+        _LATTICE["x"] = (passes, radii, chk, [chk.step(range(1024), radii, p) for p in passes])
+    return _LATTICE["x"]
+
+
+@pytest.mark.parametrize("method", [hostlib.NEIGHBOURS_PAIRS, hostlib.NEIGHBOURS_GRID], ids=["pairs", "grid"])
+def test_tangent_lattice_on_both_sides_of_zero(method):
+    passes, radii, chk, per_pass = _tangent_lattice()
+    assert per_pass == [1984, 0, 1984] and len(chk.events) == 3968       # 2 * 32 * 31 tangent pairs, twice
+    assert {e[0] for e in chk.events} == {0, 2}
+    w = _bare_world(radii)
+    w.collisions_enable(True, method=method)
+    for pos in passes:
+        w.collisions_update(pos)
+    ev, total, dropped, per = w.collisions_read()
+    assert (total, dropped) == (3968, 0)
+    assert _device_events(ev) == chk.events
+    assert np.array_equal(per, chk.per_robot(1024))
