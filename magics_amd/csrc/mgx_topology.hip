@@ -17,6 +17,7 @@
 #include "../../include/mgx.h"
 #include "gbp_math.h"
 #include "mgx_grid.h"
+#include "mgx_search.h"
 
 namespace mgx {
 
@@ -182,9 +183,7 @@ __global__ void __launch_bounds__(ROWS_BLOCK) k_pairs_rows(const float *__restri
 // (bucket order); the first lane then takes both lists into registers, sorts them (odd-even transposition, a dozen hits per
 // robot) and writes the row; more than `cap`
 // hits are counted only (the host then repeats the search with more room — beyond 32 per row with the all-pairs kernel).
-constexpr int GRID_BLOCK = 128, GRID_ROBOTS = GRID_BLOCK / 2, GRID_M = 1024;
-constexpr int NEIGHBOURS_PREV_STRIDE = 33;  // words per robot of the kept rows: count, then up to 32 entries
-constexpr int32_t NEIGHBOURS_CHANGED = 1 << 30;  // in a robot's count: its row is not the one of the search before
+constexpr int GRID_BLOCK = 128, GRID_ROBOTS = GRID_BLOCK / 2;  // (GRID_M buckets, the kept rows and the changed bit: mgx_search.h)
 template <int REG>
 __global__ void __launch_bounds__(GRID_BLOCK) k_grid_rows(const float *__restrict__ pos, int n, float s_max, double inv_cell, int32_t cap,
                                                           int32_t *__restrict__ cnt, int32_t *__restrict__ rows, int32_t *__restrict__ prev,
@@ -359,53 +358,46 @@ static float squared_threshold(float radius) {
     }
     return s;
 }
-// positions from the callers' pinned block into device memory, by a kernel as small as the search itself (every workgroup of
-// the search reads all of them: over the host link that would be the search's whole time)
-__global__ void __launch_bounds__(64) k_stage_positions(const float *__restrict__ src, float *__restrict__ dst, int n3) {
-    const int t = blockIdx.x * 64 + threadIdx.x;
-    if (t < n3) dst[t] = src[t];
-}
 // LDS of one workgroup of the grid search (k_grid_rows) for n robots and rows of up to `cap` entries; its workgroups: one per 64 robots
 static size_t neighbours_rows_lds(int n, int32_t cap) {
     const size_t npad = (size_t)((n + 3) & ~3);
     return sizeof(float) * 3 * npad + sizeof(int32_t) * ((size_t)GRID_M + GRID_BLOCK) +
            sizeof(uint16_t) * ((size_t)GRID_M + 2 + 2 * npad + (size_t)GRID_BLOCK * (cap <= 16 ? 16 : 32));
 }
-int neighbours_prev_stride() { return NEIGHBOURS_PREV_STRIDE; }
-int32_t neighbours_changed_bit() { return NEIGHBOURS_CHANGED; }
+// One launch of the one-pass search: the kernel search_kernel_for (mgx_search.h) names for a query of this size, radius and row capacity.
 // prev / prev_valid (may be null / 0): see k_grid_rows; *flagged says whether the kernel that ran marks the counts of changed rows;
 // *ran (may be null): the kernel launched (MGX_SEARCH_*, mgx_last_search), written by the branch that launched it
-hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, float *stage,
-                           int32_t *prev, int prev_valid, bool *flagged, int32_t *ran) {
+hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, int32_t *prev,
+                           int prev_valid, bool *flagged, int32_t *ran) {
     if (flagged) *flagged = false;
     if (n <= 0) return hipSuccess;
-    if (stage) {
-        hipLaunchKernelGGL(k_stage_positions, dim3((unsigned)((3 * n + 63) / 64)), dim3(64), 0, s, pos, stage, 3 * n);
-        pos = stage;
-    }
-    const size_t npad = (size_t)((n + 3) & ~3);
-    const size_t lds = sizeof(float) * 3 * npad;  // <= 48 KB: the host takes this kernel for n <= 4096
+    const size_t lds = pairs_rows_lds(n);
     const float s_max = squared_threshold(radius);
-    if (n <= GRID_M && cap <= 32 && std::isfinite(radius) && radius > 0.f) {  // the grid in LDS (a usable radius, room for the rows in registers)
-        const double inv_cell = 1.0 / ((double)radius * 1.001);
-        const dim3 grid((unsigned)((n + GRID_ROBOTS - 1) / GRID_ROBOTS));
-        if (!flagged) prev = nullptr;  // (a caller that does not ask cannot read flagged counts)
-        if (cap <= 16) {
-            hipLaunchKernelGGL(k_grid_rows<16>, grid, dim3(GRID_BLOCK), neighbours_rows_lds(n, 16), s, pos, n, s_max, inv_cell, cap, cnt, rows, prev, prev_valid);
-            if (ran) *ran = MGX_SEARCH_ROWS_GRID_16;
-        } else {
-            hipLaunchKernelGGL(k_grid_rows<32>, grid, dim3(GRID_BLOCK), neighbours_rows_lds(n, 32), s, pos, n, s_max, inv_cell, cap, cnt, rows, prev, prev_valid);
-            if (ran) *ran = MGX_SEARCH_ROWS_GRID_32;
-        }
+    // the grid in LDS (a usable radius, room for the rows in registers)
+    const double inv_cell = 1.0 / ((double)radius * 1.001);
+    const dim3 grid((unsigned)((n + GRID_ROBOTS - 1) / GRID_ROBOTS));
+    if (!flagged) prev = nullptr;  // (a caller that does not ask cannot read flagged counts)
+    switch (search_kernel_for(n, MGX_NEIGHBOURS_AUTO, radius, cap)) {
+    case MGX_SEARCH_ROWS_GRID_16:
+        hipLaunchKernelGGL(k_grid_rows<16>, grid, dim3(GRID_BLOCK), neighbours_rows_lds(n, 16), s, pos, n, s_max, inv_cell, cap, cnt, rows, prev, prev_valid);
+        if (ran) *ran = MGX_SEARCH_ROWS_GRID_16;
         if (flagged) *flagged = prev != nullptr;
-        return hipGetLastError();
-    }
-    if (n > 512 && n <= 1024) {
+        break;
+    case MGX_SEARCH_ROWS_GRID_32:
+        hipLaunchKernelGGL(k_grid_rows<32>, grid, dim3(GRID_BLOCK), neighbours_rows_lds(n, 32), s, pos, n, s_max, inv_cell, cap, cnt, rows, prev, prev_valid);
+        if (ran) *ran = MGX_SEARCH_ROWS_GRID_32;
+        if (flagged) *flagged = prev != nullptr;
+        break;
+    case MGX_SEARCH_ROWS_PAIRS_2:
         hipLaunchKernelGGL((k_pairs_rows<2, 128>), dim3((unsigned)((n + 63) / 64)), dim3(128), lds, s, pos, n, s_max, cap, cnt, rows);
         if (ran) *ran = MGX_SEARCH_ROWS_PAIRS_2;
-    } else {
+        break;
+    case MGX_SEARCH_ROWS_PAIRS_4:
         hipLaunchKernelGGL((k_pairs_rows<4, 64>), dim3((unsigned)((n + 15) / 16)), dim3(64), lds, s, pos, n, s_max, cap, cnt, rows);
         if (ran) *ran = MGX_SEARCH_ROWS_PAIRS_4;
+        break;
+    default:  // beyond ROWS_MAX_N: no one-pass kernel holds the positions in its LDS
+        return hipErrorInvalidValue;
     }
     return hipGetLastError();
 }
@@ -538,42 +530,38 @@ __global__ void __launch_bounds__(256) k_grid_query(const float *__restrict__ po
 }
 
 // ---- host-side sequencing ---------------------------------------------------------------------------
-// Scratch (all device): cnt[n], bucket_cnt[M], bucket_ptr[M+1], cursor[M], members[n], special[n],
-// n_special[1].  `ptr` is [n+1].  Phase 1 leaves the row counts scanned in `ptr`; the caller
+// Scratch: SearchScratch (mgx_search.h).  Phase 1 leaves the row counts scanned in `ptr`; the caller
 // reads ptr[n], sizes `idx` and runs phase 2.
-hipError_t neighbours_count(const float *pos, int n, float radius, bool grid, uint32_t M, int32_t *cnt, int32_t *bucket_cnt,
-                            int32_t *bucket_ptr, int32_t *cursor, int32_t *members, int32_t *special, int32_t *n_special,
-                            int32_t *ptr, hipStream_t s) {
-    if (n <= 0) return hipMemsetAsync(ptr, 0, sizeof(int32_t), s);
+hipError_t neighbours_count(const float *pos, int n, float radius, bool grid, uint32_t M, const SearchScratch &sc, hipStream_t s) {
+    if (n <= 0) return hipMemsetAsync(sc.ptr, 0, sizeof(int32_t), s);
     const dim3 g256((unsigned)((n + 255) / 256));
     if (grid) {
         const double inv_cell = 1.0 / ((double)radius * 1.001);
-        hipError_t e = hipMemsetAsync(bucket_cnt, 0, sizeof(int32_t) * M, s);
+        hipError_t e = hipMemsetAsync(sc.bucket_cnt, 0, sizeof(int32_t) * M, s);
         if (e != hipSuccess) return e;
-        if ((e = hipMemsetAsync(cursor, 0, sizeof(int32_t) * M, s)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(n_special, 0, sizeof(int32_t), s)) != hipSuccess) return e;
-        hipLaunchKernelGGL(k_grid_hist, g256, dim3(256), 0, s, pos, n, inv_cell, M - 1, bucket_cnt, special, n_special);
-        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, bucket_cnt, (int)M, bucket_ptr);
-        hipLaunchKernelGGL(k_grid_scatter, g256, dim3(256), 0, s, pos, n, inv_cell, M - 1, bucket_ptr, cursor, members);
-        hipLaunchKernelGGL(k_grid_query<false>, dim3((unsigned)(((size_t)n * QG + 255) / 256)), dim3(256), 0, s, pos, n, radius, inv_cell, M - 1, bucket_ptr, members, special,
-                           n_special, cnt, (const int32_t *)nullptr, (int32_t *)nullptr, 0);
+        if ((e = hipMemsetAsync(sc.cursor, 0, sizeof(int32_t) * M, s)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(sc.n_special, 0, sizeof(int32_t), s)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_grid_hist, g256, dim3(256), 0, s, pos, n, inv_cell, M - 1, sc.bucket_cnt, sc.special, sc.n_special);
+        hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, sc.bucket_cnt, (int)M, sc.bucket_ptr);
+        hipLaunchKernelGGL(k_grid_scatter, g256, dim3(256), 0, s, pos, n, inv_cell, M - 1, sc.bucket_ptr, sc.cursor, sc.members);
+        hipLaunchKernelGGL(k_grid_query<false>, dim3((unsigned)(((size_t)n * QG + 255) / 256)), dim3(256), 0, s, pos, n, radius, inv_cell, M - 1, sc.bucket_ptr, sc.members,
+                           sc.special, sc.n_special, sc.cnt, (const int32_t *)nullptr, (int32_t *)nullptr, 0);
     } else {
-        hipLaunchKernelGGL(k_pairs<false>, g256, dim3(256), 0, s, pos, n, radius, cnt, (const int32_t *)nullptr, (int32_t *)nullptr, 0);
+        hipLaunchKernelGGL(k_pairs<false>, g256, dim3(256), 0, s, pos, n, radius, sc.cnt, (const int32_t *)nullptr, (int32_t *)nullptr, 0);
     }
-    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, cnt, n, ptr);
+    hipLaunchKernelGGL(k_scan, dim3(1), dim3(1024), 0, s, sc.cnt, n, sc.ptr);
     return hipGetLastError();
 }
-hipError_t neighbours_fill(const float *pos, int n, float radius, bool grid, uint32_t M, const int32_t *bucket_ptr,
-                           const int32_t *members, const int32_t *special, const int32_t *n_special, const int32_t *ptr,
-                           int32_t *idx, int32_t cap, hipStream_t s) {
+hipError_t neighbours_fill(const float *pos, int n, float radius, bool grid, uint32_t M, const SearchScratch &sc, int32_t *idx, int32_t cap,
+                           hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const dim3 g256((unsigned)((n + 255) / 256));
     if (grid) {
         const double inv_cell = 1.0 / ((double)radius * 1.001);
-        hipLaunchKernelGGL(k_grid_query<true>, dim3((unsigned)(((size_t)n * QG + 255) / 256)), dim3(256), 0, s, pos, n, radius, inv_cell, M - 1, bucket_ptr, members, special,
-                           n_special, (int32_t *)nullptr, ptr, idx, cap);
+        hipLaunchKernelGGL(k_grid_query<true>, dim3((unsigned)(((size_t)n * QG + 255) / 256)), dim3(256), 0, s, pos, n, radius, inv_cell, M - 1, sc.bucket_ptr, sc.members,
+                           sc.special, sc.n_special, (int32_t *)nullptr, sc.ptr, idx, cap);
     } else {
-        hipLaunchKernelGGL(k_pairs<true>, g256, dim3(256), 0, s, pos, n, radius, (int32_t *)nullptr, ptr, idx, cap);
+        hipLaunchKernelGGL(k_pairs<true>, g256, dim3(256), 0, s, pos, n, radius, (int32_t *)nullptr, sc.ptr, idx, cap);
     }
     return hipGetLastError();
 }

@@ -36,7 +36,7 @@ int mgx_world_destroy(mgx_world *w) {
     if (w->direct.recv) (void)hipFree(w->direct.recv);
     if (w->direct.flags) (void)hipFree(w->direct.flags);
     if (w->xres.area) (void)hipFree(w->xres.area);
-    if (w->search_stream) { (void)hipStreamSynchronize(w->search_stream); (void)hipStreamDestroy(w->search_stream); }
+    if (w->search.stream) { (void)hipStreamSynchronize(w->search.stream); (void)hipStreamDestroy(w->search.stream); }
     if (w->decision_host) (void)hipHostFree(w->decision_host);
     if (w->sweep_err_host) (void)hipHostFree(w->sweep_err_host);
     if (w->mission.ev_host) (void)hipHostFree(w->mission.ev_host);
@@ -328,7 +328,7 @@ int mgx_robot_remove(mgx_world *w, int32_t robot) {
     rb.idle = 1;
     rb.antenna = 0;
     w->sets.cnt[(size_t)robot] = 0;
-    w->nb_prev_valid = false;
+    w->search.sets_touched();
     w->flags_dirty = true;
     w->mission.alive_dirty = true;
     return MGX_OK;

@@ -119,7 +119,7 @@ int mgx_mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, ui
     if (ms.dirty || ms.has.size() != w->robots.size()) {
         if (ms.uploaded && !ms.dirty && (rc = mission_download(w)) != MGX_OK) return rc;
         if ((rc = mission_upload(w)) != MGX_OK) return rc;
-        w->mission_search.valid = false;  // the host has touched the missions: Transforms may have moved
+        w->search.mission.valid = false;  // the host has touched the missions: Transforms may have moved
     }
     const int R = (int)w->robots.size();
     hipStream_t s = w->stream;
@@ -133,7 +133,7 @@ int mgx_mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, ui
     std::vector<int32_t> ptr, idx;
     // the search itself was enqueued by the last tick's end, in front of its GBP schedule, if nothing has changed since: the same
     // radius and method, the same robots alive (this tick's despawns are taken out of the rows below either way)
-    mgx_world::PendingSearch &pf = w->mission_search;
+    NeighbourSearch::PendingSearch &pf = w->search.mission;
     bool prefetched = pf.valid && pf.radius == comms_radius && pf.method == method && pf.n_all == R;
     if (prefetched) {
         size_t a = 0;
@@ -244,7 +244,7 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     // update_robot_neighbours of the COMING tick (robot.rs:1362-1384): the Transforms it looks at are final now, so the search goes
     // in front of this tick's GBP schedule and its rows reach the host while that runs
     tm.lap("prepare");
-    if (ms.search_known && (rc = neighbours_enqueue(w, nullptr, ms.search_radius, ms.search_method, w->mission_search)) != MGX_OK) return rc;
+    if (ms.search_known && (rc = neighbours_enqueue(w, nullptr, ms.search_radius, ms.search_method, w->search.mission)) != MGX_OK) return rc;
     tm.lap("search of the coming tick enqueued");
     for (int r = 0; r < R; r++) {  // message counters: the prior changes of the robots that move (what the device decides too)
         const Robot &rb = w->robots[(size_t)r];

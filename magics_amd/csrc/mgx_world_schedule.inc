@@ -373,13 +373,14 @@ int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *fo
 int mgx_last_search(mgx_world *w, int32_t *kernel, int32_t *row_cap, int32_t *n_launches, int32_t *n_changed, uint8_t *changed,
                     uint32_t capacity) {
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    if (kernel) *kernel = w->last_search_kernel;
-    if (row_cap) *row_cap = w->last_search_cap;
-    if (n_launches) *n_launches = w->last_search_launches;
-    if (n_changed) *n_changed = w->last_search_changed;
+    const NeighbourSearch &S = w->search;
+    if (kernel) *kernel = S.last_kernel;
+    if (row_cap) *row_cap = S.last_cap;
+    if (n_launches) *n_launches = S.last_launches;
+    if (n_changed) *n_changed = S.last_changed;
     // (flags reach a pass only for a world without removed robots: one byte per robot of the world)
-    if (changed && w->last_search_changed >= 0 && (size_t)capacity >= w->robots.size() && w->scratch_chg.size() >= w->robots.size())
-        memcpy(changed, w->scratch_chg.data(), w->robots.size());
+    if (changed && S.last_changed >= 0 && (size_t)capacity >= w->robots.size() && S.chg.size() >= w->robots.size())
+        memcpy(changed, S.chg.data(), w->robots.size());
     return MGX_OK;
 }
 

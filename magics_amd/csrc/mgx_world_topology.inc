@@ -9,7 +9,7 @@ int mgx_ir_connect(mgx_world *w, int32_t owner, int32_t other, uint64_t first_ro
     MGX_ENTER(w);
     int rc = ir_connect(w, owner, other, first_robot_number);
     if (rc != MGX_OK) return rc;
-    w->nb_prev_valid = false;  // (the sets change outside a topology pass)
+    w->search.sets_touched();
     if (!w->sets.has((size_t)owner, other)) w->sets.insert_sorted((size_t)owner, other);
     return MGX_OK;
 }
@@ -17,7 +17,7 @@ int mgx_ir_disconnect(mgx_world *w, int32_t a, int32_t b) {
     MGX_ENTER(w);
     int rc = ir_disconnect(w, a, b);
     if (rc != MGX_OK) return rc;
-    w->nb_prev_valid = false;
+    w->search.sets_touched();
     w->sets.erase((size_t)a, b);
     w->sets.erase((size_t)b, a);
     return MGX_OK;
@@ -25,245 +25,241 @@ int mgx_ir_disconnect(mgx_world *w, int32_t a, int32_t b) {
 
 // device neighbour search -> host CSR, rows ascending in order key
 // pos == nullptr: the positions come from the device-resident Transforms of the missions (mgx_mission_tick)
-// Two halves: everything that is enqueued (positions up, the counting and filling kernels, rows down into pinned memory) and,
-// behind a synchronisation of the stream, the host side (a second filling pass if the rows outgrew the guess, ids and order).
+// Two halves: everything that is enqueued (neighbours_enqueue) and, behind a synchronisation of the stream, the host side
+// (neighbours_collect: once more with room if the rows outgrew it, ids and order).  Two strategies (mgx_search.h,
+// search_kernel_for): the one-pass kernels read and write a mapped pinned block in place (rows_*), the two-pass count / scan /
+// fill search works with device scratch and a guessed buffer (csr_*).
 // mgx_mission_tick enqueues the search of the NEXT tick in front of this tick's GBP schedule — the Transforms it looks at are
 // final once the prior updates have moved them — so its rows are on the host long before that tick's one synchronisation.
-// track: the search of a topology pass over the caller's positions — the kernel compares every robot's row with the one it got in
-// the pass before (mgx_world::nb_prev) and says which ones changed
-static int neighbours_enqueue(mgx_world *w, const float *pos, float radius, uint32_t method, mgx_world::PendingSearch &ps, bool track = false) {
+using PendingSearch = NeighbourSearch::PendingSearch;
+
+// the positions of a mission's search: the Transforms of the robots in the query, on the device
+static int mission_positions(mgx_world *w, PendingSearch &ps) {
+    mgx_world::Mission &ms = w->mission;
+    if (ms.alive_dirty || ms.alive_host.size() != ps.alive.size()) {
+        ms.alive_host.assign(ps.alive.begin(), ps.alive.end());
+        if (ms.alive_host.empty()) ms.alive_host.push_back(0);
+        HIP_TRY(ms.alive_d.upload(ms.alive_host, ps.stream));
+        HIP_TRY(hipStreamSynchronize(ps.stream));
+        ms.alive_host.resize(ps.alive.size());
+        ms.alive_dirty = false;
+    }
+    HIP_TRY(launch_mission_positions(ms.d, ps.n, ms.alive_d.p, w->search.pos.p, ps.stream));
+    return MGX_OK;
+}
+// what both strategies start with: who is in the query, on which stream, ordered against the search before; the positions of
+// a mission's search.  *pos: the caller's positions, compacted where robots have left the query
+static int search_front(mgx_world *w, const float **pos, float radius, uint32_t method, PendingSearch &ps) {
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
-    w->mission_search.valid = false;  // the buffers below are shared: whatever was waiting in them is gone
+    NeighbourSearch &S = w->search;
+    S.mission.valid = false;  // the buffers below are shared: whatever was waiting in them is gone
     ps.valid = false;
-    const int n_all = (int)w->robots.size();
-    const bool from_missions = pos == nullptr;
+    ps.n_all = (int)w->robots.size();
+    ps.from_missions = *pos == nullptr;
+    ps.radius = radius;
+    ps.method = method;
     std::vector<int> &alive = ps.alive;  // removed robots are in no query: search the others, map back
     alive.clear();
-    std::vector<float> packed;
-    for (int r = 0; r < n_all; r++) {
+    for (int r = 0; r < ps.n_all; r++) {
         // ghosts take part: a sharded world that follows a changing topology holds EVERY robot of the
         // scenario (its own ones and ghost copies of all others) and is handed all positions, so that
         // the connection bookkeeping below runs identically on every rank
         if (!w->sets.removed[(size_t)r]) alive.push_back(r);
     }
-    const bool compact = (int)alive.size() != n_all;
-    if (compact && !from_missions) {
-        packed.resize(3 * alive.size());
-        for (size_t a = 0; a < alive.size(); a++) memcpy(&packed[3 * a], pos + 3 * (size_t)alive[a], 3 * sizeof(float));
-        pos = packed.data();
+    const int n = ps.n = (int)alive.size();
+    ps.compact = n != ps.n_all;
+    if (ps.compact && !ps.from_missions) {
+        S.packed.resize(3 * alive.size());
+        for (size_t a = 0; a < alive.size(); a++) memcpy(&S.packed[3 * a], *pos + 3 * (size_t)alive[a], 3 * sizeof(float));
+        *pos = S.packed.data();
     }
-    const int n = (int)alive.size();
-    w->last_search_launches = 0;
-    w->last_search_changed = -1;  // (until flags reach a pass: topology_bookkeeping)
-    const bool usable_radius = std::isfinite(radius) && radius > 0.f;
-    bool grid = method == MGX_NEIGHBOURS_GRID || (method == MGX_NEIGHBOURS_AUTO && n >= 512);
-    if (!usable_radius) grid = false;  // radius <= 0 / NaN / inf: every pair has to see the predicate
-    uint32_t M = 64;
-    while (M < 2u * (uint32_t)std::max(n, 1)) M <<= 1;
+    S.last_launches = 0;
+    S.last_changed = -1;  // (until flags reach a pass: topology_bookkeeping)
     // A search over positions the CALLER hands in reads nothing of the world's device state: it runs on a stream of its own,
     // next to whatever the world's stream is still busy with (the previous tick's GBP schedule), instead of behind it.
     // (The missions' search reads the device's Transforms, which the tick's kernels move: that one stays in stream order.)
-    hipStream_t s = w->stream;
-    if (!from_missions) {
+    ps.stream = w->stream;
+    if (!ps.from_missions) {
         // Never beside a resident launch that is still getting onto the device: the search's workgroups would take slots the
         // launch's last workgroups need — the census says no and a handful of ticks run launch by launch (a thousand robots
         // leave two or three free slots per XCD; enqueued at once "when both fit" the search still cost every third launch its
         // residency: tools/dynamic_tick_bench.py, 27 of 90 launches declined, 4.2 k ticks/s against 5.9 k behind the decision).
         // Behind a DECIDED launch the search finds the holes that launch leaves (mgx_topology.hip) and runs beside it.
         if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
-        if (!w->search_stream) HIP_TRY(hipStreamCreateWithFlags(&w->search_stream, hipStreamNonBlocking));
-        s = w->search_stream;
+        if (!S.stream) HIP_TRY(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
+        ps.stream = S.stream;
     }
-    if (w->nb_last_stream_set && w->nb_last_stream != s) HIP_TRY(hipStreamSynchronize(w->nb_last_stream));  // the scratch buffers are shared
-    w->nb_last_stream = s;
-    w->nb_last_stream_set = true;
-    ps.stream = s;
-    HIP_TRY(w->nb_pos.reserve((size_t)3 * std::max(n, 1)));
-    HIP_TRY(w->nb_cnt.reserve((size_t)std::max(n, 1)));
-    HIP_TRY(w->nb_ptr.reserve((size_t)n + 1));
-    HIP_TRY(w->nb_members.reserve((size_t)std::max(n, 1)));
-    HIP_TRY(w->nb_special.reserve((size_t)std::max(n, 1)));
-    HIP_TRY(w->nb_nspecial.reserve(1));
-    HIP_TRY(w->nb_bucket_cnt.reserve(M));
-    HIP_TRY(w->nb_bucket_ptr.reserve((size_t)M + 1));
-    HIP_TRY(w->nb_cursor.reserve(M));
-    if (from_missions) {
-        mgx_world::Mission &ms = w->mission;
-        if (ms.alive_dirty || ms.alive_host.size() != alive.size()) {
-            ms.alive_host.assign(alive.begin(), alive.end());
-            if (ms.alive_host.empty()) ms.alive_host.push_back(0);
-            HIP_TRY(ms.alive_d.upload(ms.alive_host, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            ms.alive_host.resize(alive.size());
-            ms.alive_dirty = false;
+    if (S.last_stream_set && S.last_stream != ps.stream) HIP_TRY(hipStreamSynchronize(S.last_stream));  // the scratch buffers are shared
+    S.last_stream = ps.stream;
+    S.last_stream_set = true;
+    HIP_TRY(S.pos.reserve((size_t)3 * std::max(n, 1)));
+    return ps.from_missions ? mission_positions(w, ps) : MGX_OK;
+}
+
+// ---- one pass: rows of a fixed capacity, written in place (small worlds, AUTO) --------------------------------------------------
+// ONE launch of the kernel for rows of `cap` entries.  No copies at all: the kernel reads the callers' positions from the pinned
+// block and writes counts and rows into it (a copy is a launch of its own — a blit kernel too big to find room beside a resident
+// schedule launch).  host_pos (may be null): positions to put into the block first — null where they are in it already (a
+// search that runs again: what the block holds moves along when it grows) or on the device (a mission's).
+// prev (may be null): the kept rows, for the kernel to compare with and to overwrite
+static int rows_launch(mgx_world *w, PendingSearch &ps, int cap, const float *host_pos, int32_t *prev, int prev_valid) {
+    NeighbourSearch &S = w->search;
+    const RowsLayout at = rows_layout(ps.n, cap);
+    HIP_TRY(S.pin.reserve(at.bytes, host_pos || ps.from_missions ? 0 : at.off_cnt));
+    if (host_pos) memcpy(S.pin.p, host_pos, at.off_cnt);
+    void *dpin = nullptr;
+    HIP_TRY(hipHostGetDevicePointer(&dpin, S.pin.p, 0));
+    char *dp = static_cast<char *>(dpin);
+    ps.rows.cap = cap;
+    HIP_TRY(neighbours_rows(ps.from_missions ? S.pos.p : reinterpret_cast<const float *>(dp), ps.n, ps.radius, cap,
+                            reinterpret_cast<int32_t *>(dp + at.off_cnt), reinterpret_cast<int32_t *>(dp + at.off_rows), ps.stream, prev,
+                            prev_valid, &ps.rows.has_chg, &S.last_kernel));
+    S.last_cap = cap;
+    S.last_launches++;
+    return MGX_OK;
+}
+// keep_rows: the search of a topology pass over the caller's positions, by a kernel that can compare every robot's row with the
+// one it got in the pass before (NeighbourSearch::prev) and say which ones changed
+static int rows_enqueue(mgx_world *w, const float *pos, PendingSearch &ps, bool keep_rows) {
+    NeighbourSearch &S = w->search;
+    int prev_valid = 0;
+    if (keep_rows) {
+        const size_t words = (size_t)ps.n * (size_t)NEIGHBOURS_PREV_STRIDE;
+        if (S.prev.cap < words || S.prev_n != (size_t)ps.n) {  // (the world's robots are not the ones of the last pass: nothing is kept)
+            HIP_TRY(S.prev.reserve(words));
+            S.prev_n = (size_t)ps.n;
+            S.prev_valid = false;
         }
-        HIP_TRY(launch_mission_positions(ms.d, n, ms.alive_d.p, w->nb_pos.p, s));
+        prev_valid = S.prev_valid ? 1 : 0;
+        S.prev_valid = false;  // (the kernel overwrites the kept rows: they are the sets again when the pass has gone through)
     }
-    // small worlds (AUTO): ONE small kernel, rows of a fixed capacity written in place, no scans (mgx_topology.hip)
-    const bool rows_mode = method == MGX_NEIGHBOURS_AUTO && n > 0 && n <= 4096;
-    if (rows_mode) {
-        const int cap = w->nb_row_cap;
-        const size_t off_cnt = sizeof(float) * 3 * (size_t)n, off_rows = off_cnt + sizeof(int32_t) * (size_t)n;
-        HIP_TRY(w->nb_pin.reserve(off_rows + sizeof(int32_t) * (size_t)n * (size_t)cap));
-        // (the kept rows: where robots left the query, or the world's robots are not the ones of the last pass, nothing is kept)
-        const bool keep_rows = track && !compact && !from_missions && cap <= 32;
-        int prev_valid = 0;
-        if (keep_rows) {
-            const size_t words = (size_t)n * (size_t)neighbours_prev_stride();
-            if (w->nb_prev.cap < words || w->nb_prev_n != (size_t)n) {
-                HIP_TRY(w->nb_prev.reserve(words));
-                w->nb_prev_n = (size_t)n;
-                w->nb_prev_valid = false;
-            }
-            prev_valid = w->nb_prev_valid ? 1 : 0;
-            w->nb_prev_valid = false;  // (the kernel overwrites the kept rows: they are the sets again when the pass has gone through)
-        }
-        HIP_TRY(w->nb_idx.reserve((size_t)n * (size_t)cap));
-        char *pin = static_cast<char *>(w->nb_pin.p);
-        // no copies at all: the kernel reads the callers' positions from the pinned block and writes counts and rows into it
-        // (a copy is a launch of its own — a blit kernel too big to find room beside a resident schedule launch)
-        void *dpin = nullptr;
-        HIP_TRY(hipHostGetDevicePointer(&dpin, pin, 0));
-        char *dp = static_cast<char *>(dpin);
-        if (!from_missions) memcpy(pin, pos, sizeof(float) * 3 * (size_t)n);
-        bool chg_written = false;
-        HIP_TRY(neighbours_rows(from_missions ? w->nb_pos.p : reinterpret_cast<const float *>(dp), n, radius, cap,
-                                reinterpret_cast<int32_t *>(dp + off_cnt), reinterpret_cast<int32_t *>(dp + off_rows), s, nullptr,
-                                keep_rows ? w->nb_prev.p : nullptr, prev_valid, &chg_written, &w->last_search_kernel));
-        w->last_search_cap = cap;
-        w->last_search_launches++;
-        ps.has_chg = chg_written;
-        ps.n = n; ps.n_all = n_all; ps.compact = compact; ps.guess = 0; ps.off_ptr = off_cnt; ps.off_idx = off_rows;
-        ps.radius = radius; ps.method = method; ps.grid = false; ps.M = M; ps.rows = true; ps.row_cap = cap; ps.from_missions = from_missions;
-        ps.valid = true;
-        return MGX_OK;
+    HIP_TRY(S.idx.reserve((size_t)ps.n * (size_t)S.row_cap));  // (a two-pass search behind this one fills into it on a guess)
+    return rows_launch(w, ps, S.row_cap, pos, keep_rows ? S.prev.p : nullptr, prev_valid);
+}
+// chg (may be null): where to put the pointer to the rows-changed bytes of the search, or null if it has none — then only the rows
+// of robots whose byte is set are copied into idx (the others' entries are not to be read)
+static int rows_collect(mgx_world *w, PendingSearch &ps, std::vector<int32_t> &ptr, std::vector<int32_t> &idx, const uint8_t **chg) {
+    NeighbourSearch &S = w->search;
+    const int n = ps.n;
+    RowsLayout at = rows_layout(n, ps.rows.cap);
+    int32_t *cnt = reinterpret_cast<int32_t *>(static_cast<char *>(S.pin.p) + at.off_cnt);
+    if (ps.rows.has_chg) {  // the flags out of the counts (the pinned block is the host's to write)
+        S.chg.resize((size_t)n);
+        strip_changed(cnt, n, S.chg.data());
     }
-    ps.rows = false;
-    const size_t guess = std::min(w->nb_idx.cap, w->nb_last_total + w->nb_last_total / 4 + 64);
+    int32_t longest = 0;
+    for (int i = 0; i < n; i++) longest = std::max(longest, cnt[i]);
+    if (longest > ps.rows.cap) {  // a row outgrew its capacity: once more with room (the world remembers)
+        int cap = ps.rows.cap;
+        while (cap < longest) cap *= 2;
+        S.row_cap = cap;
+        // (no kept rows, no flags: they were half written by the search that did not fit — everybody counts as changed)
+        const int rc = rows_launch(w, ps, cap, nullptr, nullptr, 0);
+        if (rc != MGX_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(ps.stream));
+        at = rows_layout(n, ps.rows.cap);
+        cnt = reinterpret_cast<int32_t *>(static_cast<char *>(S.pin.p) + at.off_cnt);
+    }
+    // flags reach the pass only where it can go by them: nobody left the query, and ids ascending == keys ascending (rows that are
+    // sorted by key below are all needed)
+    const uint8_t *changed = (chg && ps.rows.has_chg && !ps.compact && w->sets.monotone()) ? S.chg.data() : nullptr;
+    static const bool check_index = getenv("MGX_CHECK_INDEX") != nullptr;  // (diagnostics: every row is there for the pass to verify)
+    rows_to_csr(cnt, reinterpret_cast<const int32_t *>(static_cast<char *>(S.pin.p) + at.off_rows), n, ps.rows.cap, check_index ? nullptr : changed,
+                ptr, idx);
+    if (chg) *chg = changed;
+    S.last_total = idx.size();
+    return MGX_OK;
+}
+
+// ---- two passes: count, scan, fill ----------------------------------------------------------------------------------------------
+static int csr_enqueue(mgx_world *w, const float *pos, PendingSearch &ps, bool grid) {
+    NeighbourSearch &S = w->search;
+    const int n = ps.n;
+    uint32_t M = 64;  // buckets of the grid: a power of two, at least two per robot
+    while (M < 2u * (uint32_t)std::max(n, 1)) M <<= 1;
+    HIP_TRY(S.cnt.reserve((size_t)std::max(n, 1)));
+    HIP_TRY(S.ptr.reserve((size_t)n + 1));
+    HIP_TRY(S.members.reserve((size_t)std::max(n, 1)));
+    HIP_TRY(S.special.reserve((size_t)std::max(n, 1)));
+    HIP_TRY(S.nspecial.reserve(1));
+    HIP_TRY(S.bucket_cnt.reserve(M));
+    HIP_TRY(S.bucket_ptr.reserve((size_t)M + 1));
+    HIP_TRY(S.cursor.reserve(M));
+    const size_t guess = std::min(S.idx.cap, S.last_total + S.last_total / 4 + 64);  // (0 while there is no buffer)
     // pinned layout: [3 n floats: positions up] [n + 1 ints: row pointers down] [guess ints: rows down]
     const size_t off_ptr = sizeof(float) * 3 * (size_t)std::max(n, 1), off_idx = off_ptr + sizeof(int32_t) * ((size_t)n + 1);
-    HIP_TRY(w->nb_pin.reserve(off_idx + sizeof(int32_t) * guess));
-    char *pin = static_cast<char *>(w->nb_pin.p);
-    if (!from_missions && n) {
+    HIP_TRY(S.pin.reserve(off_idx + sizeof(int32_t) * guess));
+    char *pin = static_cast<char *>(S.pin.p);
+    if (!ps.from_missions && n) {
         memcpy(pin, pos, sizeof(float) * 3 * (size_t)n);
-        HIP_TRY(hipMemcpyAsync(w->nb_pos.p, pin, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipMemcpyAsync(S.pos.p, pin, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, ps.stream));
     }
-    HIP_TRY(neighbours_count(w->nb_pos.p, n, radius, grid, M, w->nb_cnt.p, w->nb_bucket_cnt.p, w->nb_bucket_ptr.p, w->nb_cursor.p,
-                             w->nb_members.p, w->nb_special.p, w->nb_nspecial.p, w->nb_ptr.p, s));
+    HIP_TRY(neighbours_count(S.pos.p, n, ps.radius, grid, M, S.scratch(), ps.stream));
     if (n > 0) {  // (an empty query launches nothing)
-        w->last_search_kernel = grid ? MGX_SEARCH_TWO_PASS_GRID : MGX_SEARCH_TWO_PASS_PAIRS;
-        w->last_search_cap = 0;
-        w->last_search_launches++;
+        S.last_kernel = grid ? MGX_SEARCH_TWO_PASS_GRID : MGX_SEARCH_TWO_PASS_PAIRS;
+        S.last_cap = 0;
+        S.last_launches++;
     }
     // The second pass needs the total to size its output — one more host round trip.  Instead it runs right
     // away into the buffer left from the last search (the kernels leave it alone if the rows do not fit), and
     // rows and counts come back together; only a total beyond the guess costs the second trip.
-    if (guess > 0 && w->nb_idx.p)
-        HIP_TRY(neighbours_fill(w->nb_pos.p, n, radius, grid, M, w->nb_bucket_ptr.p, w->nb_members.p, w->nb_special.p,
-                                w->nb_nspecial.p, w->nb_ptr.p, w->nb_idx.p, (int32_t)guess, s));
-    HIP_TRY(hipMemcpyAsync(pin + off_ptr, w->nb_ptr.p, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, s));
-    if (guess > 0 && w->nb_idx.p) HIP_TRY(hipMemcpyAsync(pin + off_idx, w->nb_idx.p, sizeof(int32_t) * guess, hipMemcpyDeviceToHost, s));
-    ps.n = n; ps.n_all = n_all; ps.compact = compact; ps.guess = guess; ps.off_ptr = off_ptr; ps.off_idx = off_idx;
-    ps.radius = radius; ps.method = method; ps.grid = grid; ps.M = M;
-    ps.valid = true;
+    if (guess > 0) HIP_TRY(neighbours_fill(S.pos.p, n, ps.radius, grid, M, S.scratch(), S.idx.p, (int32_t)guess, ps.stream));
+    HIP_TRY(hipMemcpyAsync(pin + off_ptr, S.ptr.p, sizeof(int32_t) * ((size_t)n + 1), hipMemcpyDeviceToHost, ps.stream));
+    if (guess > 0) HIP_TRY(hipMemcpyAsync(pin + off_idx, S.idx.p, sizeof(int32_t) * guess, hipMemcpyDeviceToHost, ps.stream));
+    ps.csr = {guess, off_ptr, off_idx, M, grid};
     return MGX_OK;
 }
-// chg (may be null): where to put the pointer to the rows-changed bytes of the search, or null if it has none — then only the rows
-// of robots whose byte is set are copied into idx (the others' entries are not to be read)
-static int neighbours_collect(mgx_world *w, mgx_world::PendingSearch &ps, std::vector<int32_t> &ptr, std::vector<int32_t> &idx,
+static int csr_collect(mgx_world *w, PendingSearch &ps, std::vector<int32_t> &ptr, std::vector<int32_t> &idx) {
+    NeighbourSearch &S = w->search;
+    const int n = ps.n;
+    const char *pin = static_cast<const char *>(S.pin.p);
+    ptr.assign((size_t)n + 1, 0);
+    memcpy(ptr.data(), pin + ps.csr.off_ptr, sizeof(int32_t) * ((size_t)n + 1));
+    const size_t total = (size_t)ptr[(size_t)n];
+    S.last_total = total;
+    if (total <= ps.csr.guess || total == 0) {
+        idx.resize(total);
+        if (total) memcpy(idx.data(), pin + ps.csr.off_idx, sizeof(int32_t) * total);
+        return MGX_OK;
+    }
+    idx.assign(total, 0);
+    if (n > 0 && ps.csr.guess > 0) S.last_launches++;  // (the filling pass ran into the guessed buffer: once more)
+    HIP_TRY(S.idx.reserve(total));
+    HIP_TRY(neighbours_fill(S.pos.p, n, ps.radius, ps.csr.grid, ps.csr.M, S.scratch(), S.idx.p, (int32_t)total, ps.stream));
+    HIP_TRY(hipMemcpyAsync(idx.data(), S.idx.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, ps.stream));
+    HIP_TRY(hipStreamSynchronize(ps.stream));
+    return MGX_OK;
+}
+
+// track: the search of a topology pass over the caller's positions (see rows_enqueue)
+static int neighbours_enqueue(mgx_world *w, const float *pos, float radius, uint32_t method, PendingSearch &ps, bool track = false) {
+    int rc = search_front(w, &pos, radius, method, ps);
+    if (rc != MGX_OK) return rc;
+    const int32_t kernel = search_kernel_for(ps.n, method, radius, w->search.row_cap);
+    ps.in_rows = search_in_rows(kernel);
+    // (the kept rows: where robots left the query, or the positions are a mission's, nothing is kept)
+    rc = ps.in_rows ? rows_enqueue(w, pos, ps, track && !ps.compact && !ps.from_missions && search_keeps_rows(kernel))
+                    : csr_enqueue(w, pos, ps, kernel == MGX_SEARCH_TWO_PASS_GRID);
+    ps.valid = rc == MGX_OK;
+    return rc;
+}
+static int neighbours_collect(mgx_world *w, PendingSearch &ps, std::vector<int32_t> &ptr, std::vector<int32_t> &idx,
                               const uint8_t **chg = nullptr) {
     if (chg) *chg = nullptr;
-    hipStream_t s = ps.stream;
-    const int n = ps.n, n_all = ps.n_all;
-    const std::vector<int> &alive = ps.alive;
-    const size_t guess = ps.guess;
-    char *pin = static_cast<char *>(w->nb_pin.p);
     ps.valid = false;
-    HIP_TRY(hipStreamSynchronize(s));
-    if (ps.rows) {
-        int cap = ps.row_cap;
-        const int32_t *cnt = reinterpret_cast<const int32_t *>(pin + ps.off_ptr);
-        if (ps.has_chg) {  // the flags out of the counts (the pinned block is the host's to write)
-            int32_t *c = reinterpret_cast<int32_t *>(pin + ps.off_ptr);
-            const int32_t bit = neighbours_changed_bit();
-            w->scratch_chg.resize((size_t)n);
-            for (int i = 0; i < n; i++) { w->scratch_chg[(size_t)i] = (c[i] & bit) ? 1 : 0; c[i] &= ~bit; }
-        }
-        int32_t longest = 0;
-        for (int i = 0; i < n; i++) longest = std::max(longest, cnt[i]);
-        if (longest > cap) {  // a row outgrew its capacity: once more with room (the world remembers)
-            while (cap < longest) cap *= 2;
-            w->nb_row_cap = cap;
-            const size_t off_rows = ps.off_ptr + sizeof(int32_t) * (size_t)n;
-            ps.has_chg = false;  // (the kept rows were half written by the search that did not fit: everybody counts as changed)
-            // the pinned block grows: the callers' positions it holds move along (a mission's are on the device)
-            std::vector<float> keep;
-            if (!ps.from_missions) keep.assign(reinterpret_cast<const float *>(pin), reinterpret_cast<const float *>(pin) + 3 * (size_t)n);
-            HIP_TRY(w->nb_pin.reserve(off_rows + sizeof(int32_t) * (size_t)n * (size_t)cap));
-            pin = static_cast<char *>(w->nb_pin.p);
-            if (!ps.from_missions) memcpy(pin, keep.data(), sizeof(float) * keep.size());
-            void *dpin = nullptr;
-            HIP_TRY(hipHostGetDevicePointer(&dpin, pin, 0));
-            char *dp = static_cast<char *>(dpin);
-            HIP_TRY(neighbours_rows(ps.from_missions ? w->nb_pos.p : reinterpret_cast<const float *>(dp), n, ps.radius, cap,
-                                    reinterpret_cast<int32_t *>(dp + ps.off_ptr), reinterpret_cast<int32_t *>(dp + off_rows), s, nullptr,
-                                    nullptr, 0, nullptr, &w->last_search_kernel));
-            w->last_search_cap = cap;
-            w->last_search_launches++;
-            HIP_TRY(hipStreamSynchronize(s));
-            cnt = reinterpret_cast<const int32_t *>(pin + ps.off_ptr);
-        }
-        const int32_t *rows = reinterpret_cast<const int32_t *>(pin + ps.off_ptr + sizeof(int32_t) * (size_t)n);
-        ptr.assign((size_t)n + 1, 0);
-        for (int i = 0; i < n; i++) ptr[(size_t)i + 1] = ptr[(size_t)i] + cnt[i];
-        idx.resize((size_t)ptr[(size_t)n]);
-        static const bool check_index = getenv("MGX_CHECK_INDEX") != nullptr;  // (diagnostics: every row is there for the pass to verify)
-        const uint8_t *changed = (chg && ps.has_chg && !ps.compact) ? w->scratch_chg.data() : nullptr;
-        for (int i = 0; i < n; i++)
-            if (cnt[i] && (!changed || changed[i] || check_index)) memcpy(idx.data() + ptr[(size_t)i], rows + (size_t)i * (size_t)cap, sizeof(int32_t) * (size_t)cnt[i]);
-        if (chg) *chg = changed;
-        w->nb_last_total = idx.size();
-    } else {
-    ptr.assign((size_t)n + 1, 0);
-    memcpy(ptr.data(), pin + ps.off_ptr, sizeof(int32_t) * ((size_t)n + 1));
-    const size_t total = (size_t)ptr[(size_t)n];
-    w->nb_last_total = total;
-    if (total <= guess && (w->nb_idx.p || total == 0)) {
-        idx.resize(total);
-        if (total) memcpy(idx.data(), pin + ps.off_idx, sizeof(int32_t) * total);
-    } else {
-        idx.assign(total, 0);
-        if (n > 0 && guess > 0 && w->nb_idx.p) w->last_search_launches++;  // (the filling pass ran into the guessed buffer: once more)
-        HIP_TRY(w->nb_idx.reserve(total));
-        HIP_TRY(neighbours_fill(w->nb_pos.p, n, ps.radius, ps.grid, ps.M, w->nb_bucket_ptr.p, w->nb_members.p, w->nb_special.p,
-                                w->nb_nspecial.p, w->nb_ptr.p, w->nb_idx.p, (int32_t)total, s));
-        HIP_TRY(hipMemcpyAsync(idx.data(), w->nb_idx.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-    }
-    }
-    if (ps.compact) {  // back to world robot ids, empty rows for the removed ones
-        for (int32_t &j : idx) j = alive[(size_t)j];
-        std::vector<int32_t> full((size_t)n_all + 1, 0);
-        for (int a = 0; a < n; a++) full[(size_t)alive[(size_t)a] + 1] = ptr[(size_t)a + 1] - ptr[(size_t)a];
-        for (int r = 0; r < n_all; r++) full[(size_t)r + 1] += full[(size_t)r];
-        ptr.swap(full);
-    }
-    if (chg && *chg && !w->sets.monotone()) {  // (rows are re-sorted by key below: every row is needed)
-        const int32_t *cnt = reinterpret_cast<const int32_t *>(pin + ps.off_ptr);
-        const int32_t *rows = reinterpret_cast<const int32_t *>(pin + ps.off_ptr + sizeof(int32_t) * (size_t)n);
-        for (int i = 0; i < n; i++)
-            if (cnt[i]) memcpy(idx.data() + ptr[(size_t)i], rows + (size_t)i * (size_t)ps.row_cap, sizeof(int32_t) * (size_t)cnt[i]);
-        *chg = nullptr;
-    }
+    HIP_TRY(hipStreamSynchronize(ps.stream));
+    const int rc = ps.in_rows ? rows_collect(w, ps, ptr, idx, chg) : csr_collect(w, ps, ptr, idx);
+    if (rc != MGX_OK) return rc;
+    if (ps.compact) compact_to_world(ps.alive, ps.n_all, ptr, idx);  // back to world robot ids, empty rows for the removed ones
     if (!w->sets.monotone())  // ids ascending == keys ascending: nothing to do (the keys' compact copies: fixed when a robot is added)
-        for (int r = 0; r < n_all; r++)
+        for (int r = 0; r < ps.n_all; r++)
             std::sort(idx.begin() + ptr[(size_t)r], idx.begin() + ptr[(size_t)r + 1],
                       [&](int a, int b) { return w->robots[(size_t)a].order_key < w->robots[(size_t)b].order_key; });
     return MGX_OK;
 }
 static int neighbours(mgx_world *w, const float *pos, float radius, uint32_t method, std::vector<int32_t> &ptr,
                       std::vector<int32_t> &idx) {
-    mgx_world::PendingSearch ps;
+    PendingSearch ps;
     const int rc = neighbours_enqueue(w, pos, radius, method, ps);
     return rc != MGX_OK ? rc : neighbours_collect(w, ps, ptr, idx);
 }
@@ -313,7 +309,7 @@ int mgx_update_topology(mgx_world *w, const float *positions_xyz, float radius, 
     // enqueued only with the launch decided (microseconds after its start); the message counters are brought up to date
     // under it (the pass is about to change who sends to whom).  (Who owns which connection — what the deletions walk —
     // comes from the connection index, kept in step with the list: round 4 listed the connections by owner here, every tick.)
-    mgx_world::PendingSearch ps;
+    PendingSearch ps;
     int rc = neighbours_enqueue(w, positions_xyz, radius, method, ps, true);  // (waits for the launch to be decided first if it has to)
     if (rc != MGX_OK) return rc;
     tm.lap("search enqueued");
@@ -327,16 +323,16 @@ int mgx_update_topology(mgx_world *w, const float *positions_xyz, float radius, 
 }
 // delete_interrobot_factors + create_interrobot_factors on the search's result (rows per robot id, ascending)
 // chg (may be null): per robot, whether its row differs from the one of the pass before — which is its connection set (see
-// mgx_world::nb_prev): a robot whose byte is 0 has nothing out of range and nobody new, and its row was not even copied
+// NeighbourSearch::prev): a robot whose byte is 0 has nothing out of range and nobody new, and its row was not even copied
 static int topology_bookkeeping(mgx_world *w, std::vector<int32_t> &ptr, std::vector<int32_t> &idx, uint64_t *robot_number_next,
                                 uint32_t *stats, StageTimer &tm, const uint8_t *chg) {
     int rc = MGX_OK;
-    w->nb_prev_valid = false;  // (until this pass has gone through)
+    w->search.prev_valid = false;  // (until this pass has gone through)
     const int n = (int)w->robots.size();
-    w->last_search_changed = -1;
+    w->search.last_changed = -1;
     if (chg) {
-        w->last_search_changed = 0;
-        for (int r = 0; r < n; r++) w->last_search_changed += chg[r] ? 1 : 0;
+        w->search.last_changed = 0;
+        for (int r = 0; r < n; r++) w->search.last_changed += chg[r] ? 1 : 0;
     }
     uint32_t created = 0, deleted = 0;
     // a robot's row of the search and its connection set are both ascending in order key (BTreeSet<Entity>): merges
@@ -413,7 +409,7 @@ static int topology_bookkeeping(mgx_world *w, std::vector<int32_t> &ptr, std::ve
     }
     tm.lap("create");
     if (stats) { stats[0] = created; stats[1] = deleted; }
-    w->nb_prev_valid = chg != nullptr;  // (every robot's set is its row now — and where the search kept the rows, they are on the device)
+    w->search.prev_valid = chg != nullptr;  // (every robot's set is its row now — and where the search kept the rows, they are on the device)
     return MGX_OK;
 }
 

@@ -1,4 +1,4 @@
-// mgx_world_types.h — what the host side is made of: launcher prototypes of the kernel files, error text, device buffers, the pinned argument ring, the host mirror's records (Robot, IrConn), connection sets and index, the world itself, the entry hooks of the C ABI (MGX_ENTER).
+// mgx_world_types.h — what the host side is made of: launcher prototypes of the kernel files, error text, device buffers, the pinned argument ring, the neighbour search's state, the host mirror's records (Robot, IrConn), connection sets and index, the world itself, the entry hooks of the C ABI (MGX_ENTER).
 // Part of ONE translation unit (mgx_world.hip includes its parts in order); not a stand-alone header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@
 #include "gbp_math.h"
 #include "mgx_dev.h"
 #include "mgx_grid.h"
+#include "mgx_search.h"  // the neighbour search: its dispatch, its pure helpers, the launchers of mgx_topology.hip
 
 namespace mgx {
 size_t sweep_lds_bytes(int K, int ir_edges);
@@ -63,19 +64,8 @@ hipError_t launch_halo_push(const DevWorld &w, int n, const int32_t *robots, con
 hipError_t launch_halo_wait_unpack(const DevWorld &w, int n, const int32_t *ghosts, const double *recv, int n_sources,
                                    const unsigned long long *flags, unsigned long long seq, unsigned long long *err,
                                    long long timeout_ticks, unsigned long long *ready, unsigned long long *host_err, hipStream_t stream);
-// mgx_topology.hip
 int env_red_plane(const mgx_env_desc *d, uint32_t resolution, float expansion, float blur_percent, bool with_blur, hipStream_t s,
                   std::vector<uint8_t> &red, uint32_t &W, uint32_t &H);  // mgx_env.hip
-hipError_t neighbours_count(const float *pos, int n, float radius, bool grid, uint32_t M, int32_t *cnt, int32_t *bucket_cnt,
-                            int32_t *bucket_ptr, int32_t *cursor, int32_t *members, int32_t *special, int32_t *n_special,
-                            int32_t *ptr, hipStream_t s);
-hipError_t neighbours_fill(const float *pos, int n, float radius, bool grid, uint32_t M, const int32_t *bucket_ptr,
-                           const int32_t *members, const int32_t *special, const int32_t *n_special, const int32_t *ptr,
-                           int32_t *idx, int32_t cap, hipStream_t s);
-hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, float *stage,
-                           int32_t *prev = nullptr, int prev_valid = 0, bool *flagged = nullptr, int32_t *ran = nullptr);
-int neighbours_prev_stride();
-int32_t neighbours_changed_bit();
 // mgx_collisions.hip
 hipError_t launch_collisions_pass(const CollDev &c, bool grid, double cell, uint32_t n_buckets, hipStream_t s);
 hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s);
@@ -386,6 +376,67 @@ struct RcclApi {
 static RcclApi g_rccl;
 constexpr int NCCL_FLOAT64 = 8;  // ncclFloat64 (rccl.h)
 
+// Pinned, device-mapped host memory the search's positions go up from and its rows come back into: copies to and from pageable
+// memory (std::vector) are staged by the runtime, tens of microseconds each
+struct PinBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    // keep: the first bytes of the block that move along when it grows (the rest is undefined afterwards)
+    hipError_t reserve(size_t bytes, size_t keep = 0) {
+        if (bytes <= cap) return hipSuccess;
+        void *q = nullptr;
+        const size_t want = bytes + bytes / 2 + 4096;
+        const hipError_t e = hipHostMalloc(&q, want, hipHostMallocMapped);  // the one-pass search reads and writes it in place
+        if (e != hipSuccess) return e;
+        if (p) {
+            memcpy(q, p, std::min(keep, cap));
+            (void)hipHostFree(p);
+        }
+        p = q;
+        cap = want;
+        return hipSuccess;
+    }
+};
+
+// The comms-range neighbour search of a world: everything it owns between calls.  mgx_world_topology.inc drives it
+// (neighbours_enqueue / neighbours_collect), mgx_search.h says which kernel of mgx_topology.hip answers which query.
+struct NeighbourSearch {
+    DevBuf<float> pos;  // the query's positions on the device (the two-pass search's copy, a mission's Transforms)
+    DevBuf<int32_t> cnt, bucket_cnt, bucket_ptr, cursor, members, special, nspecial, ptr, idx;  // the two-pass search's scratch and rows
+    SearchScratch scratch() const { return {cnt.p, bucket_cnt.p, bucket_ptr.p, cursor.p, members.p, special.p, nspecial.p, ptr.p}; }
+    size_t last_total = 0;  // rows of the last search: sizes the speculative second pass of the next one
+    int row_cap = 16;       // one-pass searches: capacity of a row (grown to what the largest row needed)
+    // The rows of the last topology pass's search, kept on the device: after a pass a robot's connection set IS its row, so the
+    // next search can say which robots' rows changed (k_grid_rows) and the host's pass looks at those only.  prev_valid: the
+    // kept rows are the sets — false whenever the sets were touched by anything but a pass that compared against them.
+    DevBuf<int32_t> prev;
+    bool prev_valid = false;
+    size_t prev_n = 0;
+    void sets_touched() { prev_valid = false; }  // the connection sets change outside a topology pass
+    hipStream_t stream = nullptr, last_stream = nullptr;  // searches over host-supplied positions run beside the world's stream
+    bool last_stream_set = false;                         // (last_stream: the one that last used the shared buffers)
+    PinBuf pin;
+    std::vector<float> packed;  // the callers' positions without the removed robots' (scratch)
+    std::vector<uint8_t> chg;   // the rows-changed flags taken out of the counts (scratch; what mgx_last_search copies)
+    // the last search (mgx_last_search): the kernel it launched last, written by the branch that launched it, with which row
+    // capacity, in how many launches — and how many robots' changed-row flags reached the pass behind it (-1: none did)
+    int32_t last_kernel = MGX_SEARCH_NONE, last_cap = 0, last_launches = 0, last_changed = -1;
+    // a search that has been enqueued and not collected yet: what both strategies need, then one part per strategy
+    struct PendingSearch {
+        bool valid = false;
+        hipStream_t stream = nullptr;  // where it was enqueued
+        int n = 0, n_all = 0;          // robots in the query, robots of the world
+        std::vector<int> alive;        // the world ids of the robots in the query
+        bool compact = false, from_missions = false;
+        float radius = 0.f;
+        uint32_t method = 0;
+        bool in_rows = false;  // the one-pass kernel with rows of a fixed capacity (`rows`), else count / scan / fill (`csr`)
+        struct { int cap = 0; bool has_chg = false; } rows;  // has_chg: the counts carry "this robot's row changed" (see prev)
+        struct Csr { size_t guess, off_ptr, off_idx; uint32_t M; bool grid; } csr{};  // the guessed buffer, where the pinned block holds what
+    } mission;  // the coming tick's search, enqueued by mgx_mission_tick_end
+};
+
 }  // namespace
 
 // Incoming inter-robot connections of every local robot in inbox key order (graph key, node index
@@ -556,7 +607,6 @@ struct mgx_world {
     std::vector<int32_t> scratch_dead_list;
     std::vector<int> scratch_gone;
     std::vector<int> scratch_victim;      // topology_bookkeeping's scratch
-    std::vector<uint8_t> scratch_chg;     // neighbours_collect: the rows-changed flags taken out of the counts
     // storage of deleted connections' edge and node lists, handed to the connections created next (a topology pass deletes and
     // creates dozens per tick: 3 KB from the allocator and back for each was a third of the pass's bookkeeping)
     std::vector<std::vector<IrEdge>> pool_edges;
@@ -653,27 +703,9 @@ struct mgx_world {
         DevBuf<int32_t> cell_idx, touching;
         EnvCollDev d{};
     } envcoll;
-    // a neighbour search that has been enqueued and not collected yet (neighbours_enqueue / neighbours_collect)
-    struct PendingSearch {
-        hipStream_t stream = nullptr;  // where it was enqueued
-        bool valid = false, compact = false, grid = false;
-        bool rows = false;  // the one-pass kernel with rows of a fixed capacity (small worlds, AUTO)
-        bool from_missions = false;
-        int row_cap = 0;
-        int n = 0, n_all = 0;
-        std::vector<int> alive;
-        size_t guess = 0, off_ptr = 0, off_idx = 0;
-        bool has_chg = false;  // rows mode: the counts carry "this robot's row changed" (see nb_prev)
-        float radius = 0.f;
-        uint32_t method = 0, M = 0;
-    } mission_search;  // the coming tick's search, enqueued by mgx_mission_tick_end
     uint32_t last_sweep_launches = 0;  // sweep-kernel launches of the last mgx_iterate / mgx_tick call (mgx_last_launch_count)
     SweepRan last_sweep;               // the sweep instantiation it launched last (mgx_last_sweep) ...
     int32_t last_sweep_form = -1;      // ... and in which form (MGX_SWEEP_FORM_*; -1: none)
-    // the last neighbour search (mgx_last_search): the kernel it launched last, written by the branch that launched it, with which
-    // row capacity, in how many launches — and how many robots' changed-row flags reached the pass behind it (-1: none did; the
-    // flags themselves are scratch_chg)
-    int32_t last_search_kernel = MGX_SEARCH_NONE, last_search_cap = 0, last_search_launches = 0, last_search_changed = -1;
     // message counters are advanced lazily: launches and prior changes are only logged here
     struct CountEntry { uint8_t ext, in; int n_int, robot; uint64_t times; };
     std::vector<CountEntry> clog;
@@ -735,36 +767,7 @@ struct mgx_world {
         std::vector<uint32_t> send_first, recv_first;  // [n_peers + 1] into halo_send / halo_recv
         DevBuf<double> send_buf, recv_buf;
     } rccl;
-    // neighbour search scratch (mgx_topology.hip)
-    DevBuf<float> nb_pos;
-    DevBuf<int32_t> nb_cnt, nb_bucket_cnt, nb_bucket_ptr, nb_cursor, nb_members, nb_special, nb_nspecial, nb_ptr, nb_idx;
-    size_t nb_last_total = 0;  // rows of the last search: sizes the speculative second pass of the next one
-    int nb_row_cap = 16;       // one-pass searches: capacity of a row (grown to what the largest row needed)
-    // The rows of the last topology pass's search, kept on the device: after a pass a robot's connection set IS its row, so the
-    // next search can say which robots' rows changed (k_grid_rows) and the host's pass looks at those only.  nb_prev_valid: the
-    // kept rows are the sets — false whenever the sets were touched by anything but a pass that compared against them.
-    DevBuf<int32_t> nb_prev;
-    bool nb_prev_valid = false;
-    size_t nb_prev_n = 0;
-    hipStream_t search_stream = nullptr, nb_last_stream = nullptr;  // searches over host-supplied positions run beside the world's stream
-    bool nb_last_stream_set = false;
-    // pinned host memory the search's positions go up from and its rows come back into: copies to and from pageable memory
-    // (std::vector) are staged by the runtime, tens of microseconds each
-    struct PinBuf {
-        void *p = nullptr;
-        size_t cap = 0;
-        ~PinBuf() { if (p) (void)hipHostFree(p); }
-        hipError_t reserve(size_t bytes) {
-            if (bytes <= cap) return hipSuccess;
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-            cap = 0;
-            const size_t want = bytes + bytes / 2 + 4096;
-            const hipError_t e = hipHostMalloc(&p, want, hipHostMallocMapped);  // the one-pass search reads and writes it in place
-            if (e == hipSuccess) cap = want;
-            return e;
-        }
-    } nb_pin;
+    NeighbourSearch search;  // the comms-range neighbour search: its buffers, what it keeps between passes, what the last one did
 };
 
 static size_t edge_index(const std::vector<int32_t> &in_ptr, int K, int r, int j, int slot);

@@ -35,7 +35,7 @@ SIZES = [1, 2, 3, 5, 6, 7, 63, 64, 65, 127, 128, 129, 511, 512, 513, 1000, 1023,
 TALLY = collections.Counter()   # kernel code -> times a step asserted it
 
 
-# ---- the dispatch as include/mgx.h and mgx_topology.hip document it -----------------------------------------------------------
+# ---- the dispatch as include/mgx.h and mgx_search.h document it (restated here: never read from the code under test) -------------
 def usable(radius):
     return bool(np.isfinite(radius) and radius > 0)
 

@@ -311,3 +311,127 @@ def test_topology_differences_are_cross_checked():
                        stderr=subprocess.STDOUT, timeout=300)
     out = r.stdout.decode(errors="replace")
     assert r.returncode == 0 and "OK 180 robots" in out, out[-3000:]
+
+
+# ---- the branch combinations of the one-pass search that the tests above do not cross -------------------------------------------
+def hub_positions(n, spokes, seed, radius=1.0):
+    """robot ids shuffled: one hub with `spokes` others on a circle of 0.95 radii around it (a spoke reaches the hub and its three
+    neighbours on either side), everybody else on a lattice of 3 radii far to the right, out of anyone's reach.
+    -> (positions, hub id, spoke ids in circle order)"""
+    perm = np.random.default_rng(seed).permutation(n)
+    x, z = np.zeros(n), np.zeros(n)
+    ang = 0.1 + 2 * np.pi * np.arange(spokes) / spokes
+    x[1:spokes + 1], z[1:spokes + 1] = 0.95 * radius * np.cos(ang), 0.95 * radius * np.sin(ang)
+    k = np.arange(n - spokes - 1)
+    x[spokes + 1:], z[spokes + 1:] = 6.0 * radius + 3.0 * radius * (k % 8), 3.0 * radius * (k // 8) - 10.0 * radius
+    pos = np.zeros((n, 3), dtype=np.float32)
+    pos[perm, 0], pos[perm, 1], pos[perm, 2] = x, 0.5, z
+    return pos, int(perm[0]), [int(p) for p in perm[1:spokes + 1]]
+
+
+def rows_of_csr(csr):
+    return [csr[1][csr[0][r]:csr[0][r + 1]].tolist() for r in range(len(csr[0]) - 1)]
+
+
+@pytest.mark.parametrize("tracked_first", [False, True])
+def test_removed_robot_and_a_row_that_outgrows_its_capacity(tracked_first):
+    """65 robots, one of them removed (the query is compacted and mapped back to world ids), a hub with 17 others in range on a
+    fresh world (row capacity 16): the search runs again with rows of 32 — through mgx_neighbours, or inside a topology pass — and
+    no changed-row flags reach a pass.  (66 robots as well: 65 in the query, two workgroups of the grid kernel.)"""
+    GRID_32 = hostlib.SEARCH_ROWS_GRID_32
+    for n in (65, 66):
+        eng, ref, _ = bare_pair(n)
+        pos, hub, spokes = hub_positions(n, 18, seed=n)
+        gone = spokes[4]  # (a robot that WOULD be in the hub's row, and in six spokes' rows)
+        for w in (eng, ref):
+            w.remove_robot(gone)
+        want = ref.neighbours(pos, 1.0)
+        rows = rows_of_csr(want)
+        assert len(rows[hub]) == 17 and max(len(r) for r in rows) == 17 and rows[gone] == [] and all(gone not in r for r in rows)
+        if not tracked_first:
+            assert same_csr(eng.neighbours(pos, 1.0, capacity=len(want[1])), want), n   # (ONE search: no sizing call in front)
+            assert eng.last_search()[:4] == (GRID_32, 32, 2, -1), eng.last_search()
+        out_e, out_r = eng.update_topology(pos, 1.0, 1), ref.update_topology(pos, 1.0, 1)
+        assert out_e == out_r and out_e[1] == sum(len(r) for r in rows), (n, out_e, out_r)
+        assert eng.last_search()[:4] == (GRID_32, 32, 2 if tracked_first else 1, -1), eng.last_search()
+        assert eng.last_search()[4] is None
+        conns = [eng.connections(r) for r in range(n)]
+        assert conns == [ref.connections(r) for r in range(n)] == rows, n
+        if tracked_first:
+            assert same_csr(eng.neighbours(pos, 1.0), want), n
+            assert eng.last_search()[:4] == (GRID_32, 32, 1, -1), eng.last_search()
+        eng.close()
+
+
+def test_flags_with_order_keys_that_do_not_ascend():
+    """Tracked passes of the one-pass grid kernel on a world whose order keys are a permutation of the ids: the rows are sorted by
+    key on the host, so every row is needed and no changed-row flags reach the pass (include/mgx.h: n_changed == -1) — first
+    pass and second, with a few robots moved in between; events, connection sets and rows are the oracle's."""
+    n = 65
+    sc = S.grid_scenario(n, 10, interrobot=True, comm_radius=0.01, obstacles=False)
+    assert not sc["ir"]
+    keys = np.random.default_rng(4).permutation(n)
+    for rb, k in zip(sc["robots"], keys):
+        rb["order_key"] = int(k) + 100
+    eng, ref = make_pair(sc)
+    rng = np.random.default_rng(6)
+    pos = rng.uniform(-9, 9, size=(n, 3)).astype(np.float32)
+    pos[:, 1] = 0.5
+    moved = pos.copy()
+    moved[[3, 17, 40, 64], 0] += np.float32(2.5)
+    nxt_e = nxt_r = 1
+    events = []
+    for k, p in enumerate((pos, moved)):
+        want = ref.neighbours(p, 3.0)
+        deg = np.diff(want[0])
+        rows = [np.array(r) for r in rows_of_csr(want) if len(r) > 1]
+        assert 3 <= deg.max() <= 16 and all((np.diff(keys[r]) > 0).all() for r in rows) and any((np.diff(r) < 0).any() for r in rows)
+        oe, orf = eng.update_topology(p, 3.0, nxt_e), ref.update_topology(p, 3.0, nxt_r)
+        assert oe == orf, (k, oe, orf)
+        nxt_e, nxt_r = oe[0], orf[0]
+        events.append(oe[1:])
+        ran = eng.last_search()
+        assert ran[:4] == (hostlib.SEARCH_ROWS_GRID_16, 16, 1, -1) and ran[4] is None, (k, ran)
+        assert [eng.connections(r) for r in range(n)] == [ref.connections(r) for r in range(n)], k
+        assert same_csr(eng.neighbours(p, 3.0), want), k
+        for w in (eng, ref):
+            w.iterate([3, 3, 3])
+    assert events[0][0] > n and events[1][0] > 0 and events[1][1] > 0, events   # the second pass created AND deleted
+    assert_identical(eng, ref, what="two tracked passes, permuted order keys")
+    eng.close()
+
+
+def test_mission_tick_search_outgrows_its_capacity():
+    """The search of a mission tick reads the Transforms on the device; on a fresh world (row capacity 16) they put 17 robots within
+    comms range of one: the search runs again with rows of 32 from the same device positions.  Events and connection sets are
+    those of the host driver on the oracle; the search of the coming tick, enqueued by the tick's end, is what last_search reports
+    afterwards: one launch of the <32> kernel."""
+    from magics_amd.driver import DeviceDriver, Driver
+    n, K = 65, 10
+    sc = S.grid_scenario(n, K, interrobot=True, comm_radius=0.01, obstacles=False)
+    assert not sc["ir"]
+    # the comms radius under which exactly one robot has 17 others in range at the start and nobody more (f32, as the search)
+    p = np.array([rb["pos"] for rb in sc["robots"]], dtype=np.float64).astype(np.float32).astype(np.float64)
+    d = np.sqrt(((p[:, None, :] - p[None, :, :]) ** 2).sum(axis=2))
+    d17 = np.sort(d, axis=1)[:, 17]                       # (column 0 is the robot itself)
+    hub = int(np.argmin(d17))
+    beyond = np.unique(d[d > d17[hub]])[0]
+    comms = float(np.float32((d17[hub] + beyond) / 2))
+    assert beyond - d17[hub] > 1e-3
+    eng, ref = make_pair(sc)
+    kw = dict(waypoints=[[tuple(rb["goal"])] for rb in sc["robots"]], radii=[rb["radius"] for rb in sc["robots"]],
+              t0=[rb["t0"] for rb in sc["robots"]], steps=sc["steps"], comms_radius=comms, target_speed=sc["target_speed"])
+    de, dr = DeviceDriver(eng, n, K, **kw), Driver(ref, n, K, **kw)
+    deg0 = np.diff(ref.neighbours(dr.translation, comms)[0])
+    assert deg0.max() == 17 and (deg0 == 17).sum() == 1 and int(np.argmax(deg0)) == hub
+    assert eng.last_search()[:3] == (hostlib.SEARCH_NONE, 0, 0)
+    for tick in range(3):
+        ee, er = de.tick(), dr.tick()
+        assert ee == er, (tick, ee, er)
+        assert [eng.connections(r) for r in range(n)] == [ref.connections(r) for r in range(n)], tick
+        assert tick > 0 or (len(ref.connections(hub)) == 17 and ee[0] == int(deg0.sum()))   # (the row of 17 went through whole)
+        ran = eng.last_search()
+        assert ran[:4] == (hostlib.SEARCH_ROWS_GRID_32, 32, 1, -1), (tick, ran)
+    assert np.array_equal(de.state()[0], dr.translation)
+    assert_identical(eng, ref, what="mission ticks, a row of 17 on a fresh world")
+    eng.close()
