@@ -137,6 +137,15 @@ int mgx_ir_disconnect(mgx_world *w, int32_t a, int32_t b);
  * the same mask right after a halo exchange (the records inter-robot factors freeze with / thaw against
  * include the ghosts' — they have to be the owners' current ones). */
 int mgx_set_enabled(mgx_world *w, uint32_t kind_mask);
+/* FactorGraph::update_inter_robot_safety_distance_multiplier (factorgraph.rs:892-910 -> InterRobotFactor::update_safety_distance,
+ * interrobot.rs:87-89) applied to every graph and to the config entry new factors read, as the reference's only caller does
+ * (ui/settings.rs:586-590): every inter-robot factor of the world gets safety_distance = multiplier * radius(owner) — frozen
+ * and keyless ones included — and so does every connection created from now on and every later re-layout of the world.
+ * Nothing else changes (messages, response means, epochs, counters).  Applied on the device, in place: the edge records and
+ * the slot records kept there are rewritten from the robots' radii; no state is pulled, nothing is laid out again.
+ * multiplier must be finite and > 0 (StrictlyPositiveFinite): MGX_ERR_INVALID otherwise, nothing changes.  On a sharded
+ * world every rank calls this with the same value between the same two schedules (nothing that travels changes). */
+int mgx_set_safety_multiplier(mgx_world *w, double multiplier);
 int mgx_set_antenna(mgx_world *w, int32_t robot, int32_t active);
 int mgx_set_idle(mgx_world *w, int32_t robot, int32_t idle);
 
@@ -309,6 +318,15 @@ int mgx_change_priors(mgx_world *w, uint32_t n, const int32_t *robots, const uin
 int mgx_reset_variables(mgx_world *w, int32_t robot, const double *means, uint32_t n_means, double first_last_sigma,
                         double inbetween_sigma);
 int mgx_reset_tracking_factors(mgx_world *w, int32_t robot);
+/* FactorGraph::modify_tracking_factors(|t| t.set_tracking_path(path)) (factorgraph.rs:1467, tracking.rs:134-136): the first of
+ * the three calls of the path-finding completion handler (robot.rs:674-682, then reset_variables and reset_tracking_factors,
+ * robot.rs:766-769).  Every tracking factor of the robot's graph follows the new polyline from its next update on and keeps
+ * its record, its last measurement and its timeout: a factor whose record is already >= n_path - 1 is skipped from then on
+ * (tracking.rs:373-379), a robot added without a path starts tracking.  path_xy: [n_path][2] f32, 2 <= n_path <= 65535
+ * (TwoOrMore; the engine keeps a factor's record in 16 bits beside its timeout); the robot must be a live local one
+ * (MGX_ERR_INVALID otherwise, nothing changes).  Only the packed path arrays are rebuilt
+ * and uploaded: no state is pulled, nothing else is laid out again. */
+int mgx_set_tracking_path(mgx_world *w, int32_t robot, const float *path_xy, uint32_t n_path);
 
 /* The driver's per-tick prior updates, batched over robots in one launch:
  *   what[i] & 1: update_prior_of_horizon_state (robot.rs:2182-2283) — the last variable of robots[i]

@@ -110,6 +110,9 @@ public:
     MessageCount message_count() const;
     void set_antenna_active(bool active);
     void set_idle(bool idle);
+    /// modify_tracking_factors(|t| t.set_tracking_path(path)) (factorgraph.rs:1467, tracking.rs:134-136; robot.rs:674-682):
+    /// two points or more; the tracking factors keep their records and timeouts
+    void set_tracking_path(const std::vector<std::array<float, 2>> &path);
 
 private:
     friend class World;
@@ -182,6 +185,9 @@ public:
     void set_linger(int32_t microseconds) { check(mgx_set_linger(w_, microseconds)); }
     /// FactorGraph::change_factor_enabled (factorgraph.rs:1529-1539) for every graph: MGX_FACTOR_* bits
     void change_factor_enabled(uint32_t kind_mask) { check(mgx_set_enabled(w_, kind_mask)); }
+    /// FactorGraph::update_inter_robot_safety_distance_multiplier (factorgraph.rs:892-910) for every graph and for factors
+    /// created from now on, as ui/settings.rs:586-590 applies it: finite and > 0
+    void update_inter_robot_safety_distance_multiplier(double multiplier) { check(mgx_set_safety_multiplier(w_, multiplier)); }
     std::pair<uint32_t, uint32_t> update_topology(const std::vector<std::array<float, 3>> &translations, float comms_radius,
                                                   RobotNumberGenerator &numbers) {
         uint32_t stats[2] = {0, 0};
@@ -292,6 +298,9 @@ inline MessageCount FactorGraph::message_count() const {
 }
 inline void FactorGraph::set_antenna_active(bool active) { check(mgx_set_antenna(world_->raw(), robot_, active ? 1 : 0)); }
 inline void FactorGraph::set_idle(bool idle) { check(mgx_set_idle(world_->raw(), robot_, idle ? 1 : 0)); }
+inline void FactorGraph::set_tracking_path(const std::vector<std::array<float, 2>> &path) {
+    check(mgx_set_tracking_path(world_->raw(), robot_, path.empty() ? nullptr : path[0].data(), (uint32_t)path.size()));
+}
 
 // crates/gbp_multivariate_normal: errors are the variants of MultivariateNormalError, carried by
 // mgx::Error::code (MGX_MVN_ERR_*) and what()

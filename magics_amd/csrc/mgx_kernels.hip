@@ -637,6 +637,21 @@ __global__ void k_edge_gates(int n, const IrEdgeRec *__restrict__ recs, const ui
     const int a = recs[e].src_robot;
     gate[e] = (antenna[a] && !idle[a]) ? 1 : 0;
 }
+// mgx_set_safety_multiplier: safety_distance = multiplier * radius(owner) (interrobot.rs:87-89) in the edge records of the
+// consumers and in the slot records k_retopo_robots keeps (what a robot whose list does not change lays its edges out from in
+// the next topology pass) — the product the host forms for a new record, from the same two f64.  One thread per record, edges
+// first; radius: [n_robots] by device robot index.  Nothing else of a record is written.
+__global__ void k_set_safety(int n_edges, IrEdgeRec *__restrict__ recs, int n_slots, IrSlotRec *__restrict__ slots, int n_robots,
+                             const double *__restrict__ radius, double multiplier) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n_edges) {
+        const int a = recs[t].src_robot;
+        if ((unsigned)a < (unsigned)n_robots) recs[t].d_safe = multiplier * radius[a];
+    } else if (t - n_edges < n_slots) {
+        const int q = t - n_edges, a = slots[q].src_robot;
+        if ((unsigned)a < (unsigned)n_robots) slots[q].d_safe = multiplier * radius[a];
+    }
+}
 
 // small byte copy (flag tables from the pinned argument ring into their device arrays)
 __global__ void k_copy_bytes(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, size_t n) {
@@ -798,6 +813,13 @@ hipError_t launch_var_tables(int R, int K, const int32_t *in_ptr, const int32_t 
 hipError_t launch_edge_gates(int n, const IrEdgeRec *recs, const uint8_t *antenna, const uint8_t *idle, uint8_t *gate, hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_edge_gates, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, recs, antenna, idle, gate);
+    return hipGetLastError();
+}
+hipError_t launch_set_safety(int n_edges, IrEdgeRec *recs, int n_slots, IrSlotRec *slots, int n_robots, const double *radius,
+                             double multiplier, hipStream_t stream) {
+    const int n = n_edges + n_slots;
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_set_safety, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n_edges, recs, n_slots, slots, n_robots, radius, multiplier);
     return hipGetLastError();
 }
 hipError_t launch_freeze(const DevWorld &w, uint32_t kinds, hipStream_t stream) {

@@ -429,6 +429,31 @@ int mgx_set_enabled(mgx_world *w, uint32_t kind_mask) {
     return MGX_OK;
 }
 
+// FactorGraph::update_inter_robot_safety_distance_multiplier for every graph + the config entry new factors read
+// (factorgraph.rs:892-910, interrobot.rs:87-89, ui/settings.rs:586-590).  The multiplier lives in w->p: every record the host
+// forms later (ir_connect -> retopo's slot records, commit's edge records) takes it from there.  The records the DEVICE holds
+// are rewritten in place by k_set_safety: the edge records of the layout there now, and — where the next topology pass will read
+// them (rinc.all: it will not, every robot sends its piece) — the slot records.  A world whose device arrays are about to be
+// laid out again anyway (dirty, or never laid out) needs nothing but the scalar.  No pull, no commit, no upload.
+int mgx_set_safety_multiplier(mgx_world *w, double multiplier) {
+    MGX_ENTER(w);
+    if (!std::isfinite(multiplier) || !(multiplier > 0)) return fail(MGX_ERR_INVALID, "safety multiplier must be finite and > 0");
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    // (a resident launch the census declined is run again first: its schedule was issued under the old distance)
+    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    w->p.safety_multiplier = multiplier;
+    if (w->dirty || !w->dev_valid || w->dev_in_ptr.empty()) return MGX_OK;
+    const size_t n_slots = (size_t)w->dev_in_ptr.back(), n_edges = n_slots * (size_t)(w->K - 1);
+    if (n_edges == 0) return MGX_OK;
+    if (n_edges > w->ir_rec.n || (size_t)w->d.R_total > w->radius_dev.n)
+        return fail(MGX_ERR_STATE, "internal: %zu edges on the device, %zu records, %zu radii for %d robots", n_edges, w->ir_rec.n, w->radius_dev.n, w->d.R_total);
+    const bool slots_live = !w->rinc.all && n_slots <= w->slot_recs.n;
+    if (!slots_live) w->rinc.all = true;  // (no slot records there to rewrite: the next pass sends everybody's, with the new distance)
+    HIP_TRY(launch_set_safety((int)n_edges, w->ir_rec.p, slots_live ? (int)n_slots : 0, w->slot_recs.p, w->d.R_total, w->radius_dev.p,
+                              multiplier, w->stream));
+    return MGX_OK;
+}
+
 int mgx_set_antenna(mgx_world *w, int32_t robot, int32_t active) {
     MGX_ENTER(w);
     if (!w || robot < 0 || (size_t)robot >= w->robots.size()) return fail(MGX_ERR_INVALID, "bad robot id");

@@ -430,8 +430,10 @@ static int commit(mgx_world *w) {
     std::vector<int32_t> trc(NT, 0), pptr((size_t)R_local + 1, 0), itf((size_t)std::max(R_local, 1), 0);
     std::vector<uint32_t> ep(V);
     std::vector<float> tlp(2 * NT, 0.f), pxy;
+    std::vector<double> rad((size_t)R_total, 0.0);
     for (int dr = 0; dr < R_total; dr++) {
         const Robot &rb = w->robots[(size_t)w->robot_of[(size_t)dr]];
+        rad[(size_t)dr] = rb.radius;
         blob_pack(rb, &blb[(size_t)dr * BS]);
         for (int i = 0; i < K; i++) {
             const size_t v = (size_t)dr * K + i;
@@ -473,6 +475,7 @@ static int commit(mgx_world *w) {
     HIP_TRY(w->path_ptr.upload(pptr, s));
     HIP_TRY(w->path_xy.upload(pxy, s));
     HIP_TRY(w->iter_factor.upload(itf, s));
+    HIP_TRY(w->radius_dev.upload(rad, s));
     HIP_TRY(w->in_ptr_dev.upload(t.in_ptr, s));
     HIP_TRY(w->in_mid_dev.upload(t.mid, s));
     HIP_TRY(w->ir_var_ptr.reserve((size_t)R_local * K + 1));

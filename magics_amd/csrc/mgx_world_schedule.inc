@@ -315,6 +315,40 @@ int mgx_reset_tracking_factors(mgx_world *w, int32_t robot) {
     w->dev_valid = false;
     return MGX_OK;
 }
+// FactorGraph::modify_tracking_factors(|t| t.set_tracking_path(path)) (factorgraph.rs:1467, tracking.rs:134-136; the
+// completion handler's first call, robot.rs:674-682): the graph's tracking factors share the robot's polyline (Robot::path), so
+// replacing it IS the call — records, last measurements and timeouts stay where they are (on the device: nothing is pulled).
+// The packed path arrays are rebuilt from the host's per-robot paths in the device order of the layout there now and uploaded;
+// a world about to be laid out again (dirty, or never laid out) takes the new path with that layout.
+int mgx_set_tracking_path(mgx_world *w, int32_t robot, const float *path_xy, uint32_t n_path) {
+    MGX_ENTER(w);
+    if (n_path < 2) return fail(MGX_ERR_INVALID, "n_path must be >= 2 (TwoOrMore), got %u", n_path);
+    if (!path_xy) return fail(MGX_ERR_INVALID, "null path");
+    if (!w || robot < 0 || (size_t)robot >= w->robots.size()) return fail(MGX_ERR_INVALID, "bad robot id");
+    if (w->robots[(size_t)robot].ghost || w->robots[(size_t)robot].removed) return fail(MGX_ERR_INVALID, "robot %d is not a live local robot", robot);
+    if (n_path > 0xffffu) return fail(MGX_ERR_INVALID, "n_path %u: a factor's record is kept in 16 bits", n_path);
+    // (a resident launch the census declined is run again first: its schedule was issued under the old path)
+    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    w->robots[(size_t)robot].path.assign(path_xy, path_xy + 2 * (size_t)n_path);
+    if (w->dirty || !w->dev_valid) return MGX_OK;
+    const size_t RL = (size_t)w->d.R_local;
+    std::vector<int32_t> pptr(RL + 1, 0);
+    std::vector<float> pxy;
+    for (size_t dr = 0; dr < RL; dr++) {  // (as commit packs them — every robot's again: one packed array, a rare call)
+        const Robot &rb = w->robots[(size_t)w->robot_of[dr]];
+        pptr[dr] = (int32_t)(pxy.size() / 2);
+        pxy.insert(pxy.end(), rb.path.begin(), rb.path.end());
+        pptr[dr + 1] = (int32_t)(pxy.size() / 2);
+    }
+    if (pptr.size() > w->path_ptr.cap || pxy.size() > w->path_xy.cap)
+        HIP_TRY(hipStreamSynchronize(w->stream));  // (an array that has to grow is freed first: nothing may still read it)
+    HIP_TRY(w->path_ptr.upload(pptr, w->stream));
+    HIP_TRY(w->path_xy.upload(pxy, w->stream));
+    w->d.path_ptr = w->path_ptr.p;
+    w->d.path_xy = w->path_xy.p;
+    HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vectors die here
+    return check_device_error(w);
+}
 
 // Sharded worlds: a prior change applied on ANOTHER rank (to a robot that is a ghost here) still delivers a message to the
 // inter-robot factors local robots own on that variable (variable.rs:210-221): the counters are told, nothing else happens.

@@ -59,6 +59,8 @@ hipError_t launch_retopo_robots(const DevWorld &w, const RetopoBlock &b, const i
 hipError_t launch_var_tables(int R, int K, const int32_t *in_ptr, const int32_t *in_mid, int32_t *var_ptr, int32_t *var_mid,
                              hipStream_t stream);
 hipError_t launch_edge_gates(int n, const IrEdgeRec *recs, const uint8_t *antenna, const uint8_t *idle, uint8_t *gate, hipStream_t stream);
+hipError_t launch_set_safety(int n_edges, IrEdgeRec *recs, int n_slots, IrSlotRec *slots, int n_robots, const double *radius,
+                             double multiplier, hipStream_t stream);
 hipError_t launch_halo_push(const DevWorld &w, int n, const int32_t *robots, const unsigned long long *dst, int n_peers,
                             const unsigned long long *peer_flags, unsigned long long seq, unsigned int *done, hipStream_t stream);
 hipError_t launch_halo_wait_unpack(const DevWorld &w, int n, const int32_t *ghosts, const double *recv, int n_sources,
@@ -512,6 +514,7 @@ struct mgx_world {
     DevBuf<uint32_t> epoch0, epoch1;
     DevBuf<float> trk_last_pos, path_xy;
     DevBuf<uint8_t> ir_gate, antenna, idle, sdf;
+    DevBuf<double> radius_dev;  // [R_total] the robots' radii by device index (laid out by commit): what mgx_set_safety_multiplier rewrites d_safe from
     StageRing stage;  // packed per-tick arguments
     // resident schedule launches (SegPlan, mgx_dev.h): progress words, peer lists, the abort / error words
     DevBuf<unsigned long long> sweep_flag_buf, sweep_abort_buf;

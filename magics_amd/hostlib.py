@@ -127,6 +127,7 @@ SYMBOLS = {
     "mgx_ir_connect": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_uint64]),
     "mgx_ir_disconnect": (C.c_int, [_V, C.c_int32, C.c_int32]),
     "mgx_set_enabled": (C.c_int, [_V, C.c_uint32]),
+    "mgx_set_safety_multiplier": (C.c_int, [_V, C.c_double]),
     "mgx_set_antenna": (C.c_int, [_V, C.c_int32, C.c_int32]),
     "mgx_set_idle": (C.c_int, [_V, C.c_int32, C.c_int32]),
     "mgx_set_antennas": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p]),
@@ -180,6 +181,7 @@ SYMBOLS = {
     "mgx_ipc_close": (C.c_int, [C.c_void_p]),
     "mgx_reset_variables": (C.c_int, [_V, C.c_int32, c_double_p, C.c_uint32, C.c_double, C.c_double]),
     "mgx_reset_tracking_factors": (C.c_int, [_V, C.c_int32]),
+    "mgx_set_tracking_path": (C.c_int, [_V, C.c_int32, C.c_void_p, C.c_uint32]),
     "mgx_mission_set": (C.c_int, [_V, C.c_int32, C.c_void_p]),
     "mgx_mission_tick": (C.c_int, [_V, C.c_float, C.c_uint32, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p, C.c_double, C.c_double,
                                    C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]),

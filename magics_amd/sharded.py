@@ -572,6 +572,11 @@ class ShardedWorld:
         self.world.set_enabled(mask)
         self._settle_resident()
 
+    def set_safety_multiplier(self, multiplier):
+        """update_inter_robot_safety_distance_multiplier on every rank (collective: the same value between the same two
+        schedules).  No exchange: the ghosts' radii are on every rank already and nothing that travels changes."""
+        self.world.set_safety_multiplier(multiplier)
+
     def _settle_resident(self):
         """Whether a schedule may run as one resident launch has to come out the same on every rank (a rank that went resident
         next to one that did not would wait for records that never come), and "factors are still thawing" depends on the flags of
@@ -987,6 +992,10 @@ class LocalCluster:
         for sw in self.ranks:
             sw.world.set_enabled(mask)
         self._settle_resident()
+
+    def set_safety_multiplier(self, multiplier):
+        for sw in self.ranks:
+            sw.set_safety_multiplier(multiplier)
 
     def _settle_resident(self):
         """see ShardedWorld._settle_resident: resident launches are off on every rank while any rank is thawing"""

@@ -136,6 +136,11 @@ class World:
         """change_factor_enabled for every graph (factorgraph.rs:1529-1539): MGX_FACTOR_* bits."""
         self._chk(self._L.mgx_set_enabled(self._w, int(mask)))
 
+    def set_safety_multiplier(self, multiplier):
+        """update_inter_robot_safety_distance_multiplier for every graph and for factors created from now on
+        (factorgraph.rs:892-910, ui/settings.rs:586-590): applied on the device, in place."""
+        self._chk(self._L.mgx_set_safety_multiplier(self._w, float(multiplier)))
+
     def set_antenna(self, robot, active):
         self._chk(self._L.mgx_set_antenna(self._w, robot, int(bool(active))))
 
@@ -235,6 +240,12 @@ class World:
     def reset_tracking_factors(self, robot):
         """FactorGraph::reset_tracking_factors (factorgraph.rs:1566-1590)."""
         self._chk(self._L.mgx_reset_tracking_factors(self._w, robot))
+
+    def set_tracking_path(self, robot, path):
+        """modify_tracking_factors(|t| t.set_tracking_path(path)) (factorgraph.rs:1467, tracking.rs:134-136, robot.rs:674-682):
+        the robot's tracking factors follow `path` ([n >= 2][2]) and keep their records and timeouts."""
+        path = np.ascontiguousarray(path, dtype=np.float32).reshape(-1, 2)
+        self._chk(self._L.mgx_set_tracking_path(self._w, robot, path.ctypes.data, path.shape[0]))
 
     def change_priors(self, robots, var_ix, means):
         robots = np.ascontiguousarray(robots, dtype=np.int32)
@@ -685,6 +696,14 @@ class FactorGraph:
 
     def variable(self, variable_index):
         return self.world.get_belief(self.id, variable_index)
+
+    def set_tracking_path(self, path):
+        """modify_tracking_factors(|t| t.set_tracking_path(path)) (robot.rs:674-682)"""
+        self.world.set_tracking_path(self.id, path)
+
+    def update_inter_robot_safety_distance_multiplier(self, multiplier):
+        """world-wide, like the reference's only caller (ui/settings.rs:586-590: every graph and the config entry)"""
+        self.world.set_safety_multiplier(multiplier)
 
 
 _STEP_BYTES = {}

@@ -56,6 +56,11 @@ impl World {
     pub fn change_factor_enabled(&self, kind_mask: u32) -> Result<(), MgxError> {
         check(unsafe { sys::mgx_set_enabled(self.raw, kind_mask) })
     }
+    /// `FactorGraph::update_inter_robot_safety_distance_multiplier` for every graph and for factors created from now on
+    /// (factorgraph.rs:892-910, ui/settings.rs:586-590); `multiplier` finite and > 0
+    pub fn update_inter_robot_safety_distance_multiplier(&self, multiplier: f64) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_set_safety_multiplier(self.raw, multiplier) })
+    }
     /// `update_failed_comms` (robot.rs:1593-1601): the Bernoulli draws stay with the caller's PRNG
     pub fn set_antennas(&self, robots: &[i32], active: &[u8]) -> Result<(), MgxError> {
         assert_eq!(robots.len(), active.len());
@@ -223,6 +228,11 @@ impl FactorGraph {
     pub fn change_prior_of_variable(&mut self, variable_index: u32, new_mean: [f64; 4]) -> Result<Vec<()>, MgxError> {
         check(unsafe { sys::mgx_change_prior(self.world.raw, self.robot, variable_index, new_mean.as_ptr()) })?;
         Ok(Vec::new())
+    }
+    /// `modify_tracking_factors(|t| t.set_tracking_path(path))` (factorgraph.rs:1467, tracking.rs:134-136; robot.rs:674-682):
+    /// the graph's tracking factors follow `path` (two points or more) and keep their records and timeouts
+    pub fn set_tracking_path(&mut self, path: &[[f32; 2]]) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_set_tracking_path(self.world.raw, self.robot, path.as_ptr().cast(), path.len() as u32) })
     }
     /// `FactorGraph::reset_variables(&means, first_last_sigma, inbetween_sigma)` (factorgraph.rs:1541-1564); the
     /// reference's call is `(means, 1e30, Float::INFINITY)` (robot.rs:768)

@@ -177,6 +177,7 @@ extern "C" {
     pub fn mgx_ir_connect(w: *mut mgx_world, owner: i32, other: i32, first_robot_number: u64) -> c_int;
     pub fn mgx_ir_disconnect(w: *mut mgx_world, a: i32, b: i32) -> c_int;
     pub fn mgx_set_enabled(w: *mut mgx_world, kind_mask: u32) -> c_int;
+    pub fn mgx_set_safety_multiplier(w: *mut mgx_world, multiplier: f64) -> c_int;
     pub fn mgx_set_antenna(w: *mut mgx_world, robot: i32, active: i32) -> c_int;
     pub fn mgx_set_idle(w: *mut mgx_world, robot: i32, idle: i32) -> c_int;
     pub fn mgx_set_antennas(w: *mut mgx_world, n: u32, robots: *const i32, active: *const u8) -> c_int;
@@ -203,6 +204,7 @@ extern "C" {
     pub fn mgx_change_priors(w: *mut mgx_world, n: u32, robots: *const i32, var_ix: *const u32, means: *const f64) -> c_int;
     pub fn mgx_reset_variables(w: *mut mgx_world, robot: i32, means: *const f64, n_means: u32, first_last_sigma: f64, inbetween_sigma: f64) -> c_int;
     pub fn mgx_reset_tracking_factors(w: *mut mgx_world, robot: i32) -> c_int;
+    pub fn mgx_set_tracking_path(w: *mut mgx_world, robot: i32, path_xy: *const f32, n_path: u32) -> c_int;
     pub fn mgx_update_priors(w: *mut mgx_world, n: u32, robots: *const i32, waypoints_xy: *const f64, time_scale: *const f64, what: *const u8, max_speed: f64, delta_t: f64) -> c_int;
     pub fn mgx_tick(w: *mut mgx_world, n: u32, robots: *const i32, waypoints_xy: *const f64, time_scale: *const f64, what: *const u8, max_speed: f64, delta_t: f64, steps: *const u8, n_steps: u32) -> c_int;
     pub fn mgx_mission_set(w: *mut mgx_world, robot: i32, desc: *const mgx_mission_desc) -> c_int;
