@@ -1,0 +1,67 @@
+// mgx_resident.h — the arithmetic of the host's side of resident and lingering schedule launches (mgx_world_launch.inc drives
+// them, mgx_world_types.h holds their state): a schedule's segments, their bytes in a launch's plan, where a world stands in its
+// snapshot parity and segment count, the back-off after a declined launch, the prior updates that ride in a launch.  Free of HIP:
+// compiles with a plain C++17 compiler (tests/cpu_resident/resident_harness.cpp).
+#pragma once
+#include <algorithm>
+#include <cstddef>
+#include <cstdint>
+#include <vector>
+
+namespace mgx {
+
+#ifndef __HIPCC__  // stand-alone: mgx_dev.h, which needs HIP, is not there — its values restated.  (In the library's build the assertion
+                   // below reads mgx_dev.h's own constants: that is where a change there is caught; stand-alone it only checks these copies.)
+constexpr uint32_t PH_INT_FACTOR = 4u, PH_INT_VARIABLE = 8u;
+constexpr int MAX_SEGS = 32;
+#endif
+static_assert((PH_INT_FACTOR | PH_INT_VARIABLE) == 12u && MAX_SEGS == 32, "the phases and the plan's size as mgx_dev.h has them");
+
+struct Launch { uint32_t ext; int n_int; uint32_t hints; };  // one [external iteration] internal* segment of a schedule
+// the internal phases of a segment's launch: factor and variable sweeps together, or none
+inline uint32_t int_phases(const Launch &l) { return l.n_int ? (PH_INT_FACTOR | PH_INT_VARIABLE) : 0; }
+
+// The part of `plan` that starts at segment `from` as a launch's plan reads it (SegPlan and LingerPlan share the bytes): one byte
+// per segment in ext[MAX_SEGS] and n_int[MAX_SEGS], zero behind the part.  Returns the part's segments (at most MAX_SEGS).
+inline int fill_segments(const std::vector<Launch> &plan, size_t from, uint8_t *ext, uint8_t *n_int) {
+    const int n = (int)std::min<size_t>((size_t)MAX_SEGS, plan.size() - std::min(from, plan.size()));
+    for (int k = 0; k < MAX_SEGS; k++) {
+        ext[k] = k < n && plan[from + (size_t)k].ext ? 1 : 0;
+        n_int[k] = k < n ? (uint8_t)plan[from + (size_t)k].n_int : 0;
+    }
+    return n;
+}
+
+// Where a world stands between launches: the parity of its snapshot buffers (DevWorld::cur) and its segment count (every
+// progress word is below or at it).  A launch of n segments moves both by n; a post CONTINUES the last segment of the plan
+// before it, so it moves them by n - 1.  Taking a launch or a post back is going back to where the world stood before it.
+struct Standing {
+    int cur = 0;
+    unsigned long long flag_base = 0;
+    Standing after_launch(int n) const { return {(cur + n) & 1, flag_base + (unsigned long long)n}; }
+    Standing after_post(int n) const { return after_launch(n - 1); }
+};
+
+// After a declined launch the schedules skip the resident form for a while: `left` counts world-wide external iterations that
+// ran launch by launch, `len` doubles with every decline in a row (64 .. 32768) and starts over with a launch that went ahead.
+struct Backoff {
+    int left = 0, len = 0;
+    void declined(int segments) {  // (+ the declined schedule's own re-run)
+        len = std::min(std::max(2 * len, 64), 32768);
+        left = len + segments;
+    }
+    void external_iteration() { if (left > 0) left--; }
+    void went_ahead() { len = 0; }
+};
+
+// mgx_tick's / mgx_mission_tick_end's prior updates that ride in a schedule's first launch: [R_local][4] f64 records
+struct RidingUpdates {
+    const double *dev = nullptr;   // as the kernel reads them (DevWorld::upd is written from here)
+    const double *host = nullptr;  // the host's view of the same records; null: they live in device memory
+    int slot = -1;                 // the pinned ring slot they sit in (released behind the launch that reads them); -1: none
+    double max_speed = 0.0, delta_t = 0.0;
+    bool any() const { return dev || host; }
+    bool postable() const { return !dev || host; }  // records in device memory cannot ride in a post (the box is the host's)
+};
+
+}  // namespace mgx

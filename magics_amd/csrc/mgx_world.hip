@@ -8,10 +8,11 @@
 // disturb existing state (the reference mutates its graphs in place,
 // factorgraph.rs:190-226,304-353,380-436).
 //
-// ONE translation unit, eleven files: the parts below share file-local helpers (commit, confirm_resident, flush_counts, sweep,
+// ONE translation unit, twelve files: the parts below share file-local helpers (commit, confirm_resident, flush_counts, sweep,
 // run_resident, linger_close ...) that have no business in the library's symbol table, so they are included here in
 // dependency order instead of being linked:
-//   mgx_world_types.h — what the host side is made of: launcher prototypes of the kernel files, error text, device buffers, the pinned argument ring, the host mirror's records (Robot, IrConn), connection sets and index, the world itself, the entry hooks of the C ABI (MGX_ENTER)
+//   mgx_world_types.h — what the host side is made of: launcher prototypes of the kernel files, error text, device buffers, the pinned argument ring, the neighbour search's and the resident launches' state, the host mirror's records (Robot, IrConn), connection sets and index, the world itself, the entry hooks of the C ABI (MGX_ENTER)
+//   mgx_resident.h — resident launches, the host's arithmetic, free of HIP (included by mgx_world_types.h): a schedule's segments, their bytes in a launch's plan, parity and segment count, the back-off, riding prior updates
 //   mgx_world_mirror.inc — SoA helpers, blob <-> host mirror, pull (device -> host mirror)
 //   mgx_world_counters.inc — message counters (MessageCount): the launch log, lazy settling of the connections, flush_counts
 //   mgx_world_commit.inc — commit (host mirror -> device arrays), the connection index, the incoming tables, retopo (edge tables rebuilt on the device)

@@ -29,15 +29,13 @@ int mgx_world_create(const mgx_params *params, mgx_world **out) {
 int mgx_world_destroy(mgx_world *w) {
     if (!w) return MGX_OK;
     w->batch.steps.clear();
-    if (w->linger.open) (void)linger_close(w);  // (nobody is left to post: the launch would wait out its bound)
+    (void)linger_close(w);  // (nobody is left to post: the launch would wait out its bound)
     if (w->dev_valid) (void)hipStreamSynchronize(w->stream);
-    if (w->linger.box) (void)hipHostFree(w->linger.box);
     if (w->rccl.comm && g_rccl.ok) (void)g_rccl.comm_destroy(w->rccl.comm);
     if (w->direct.recv) (void)hipFree(w->direct.recv);
     if (w->direct.flags) (void)hipFree(w->direct.flags);
     if (w->xres.area) (void)hipFree(w->xres.area);
     if (w->search.stream) { (void)hipStreamSynchronize(w->search.stream); (void)hipStreamDestroy(w->search.stream); }
-    if (w->decision_host) (void)hipHostFree(w->decision_host);
     if (w->sweep_err_host) (void)hipHostFree(w->sweep_err_host);
     if (w->mission.ev_host) (void)hipHostFree(w->mission.ev_host);
     if (w->mission.tr_host) (void)hipHostFree(w->mission.tr_host);
@@ -57,7 +55,7 @@ int mgx_synchronize(mgx_world *w) {
     MGX_ENTER(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no usable HIP device");
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     HIP_TRY(hipStreamSynchronize(w->stream));
     return check_device_error(w);
 }
@@ -72,15 +70,13 @@ int mgx_flush(mgx_world *w) {
 int mgx_set_linger(mgx_world *w, int32_t microseconds) {
     MGX_ENTER(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    w->linger.ticks = -1;
-    if (microseconds >= 0) w->linger.ticks = (long long)std::min(microseconds, 1000000) * 100ll;
-    w->linger.useless = 0;
+    w->res.set_linger(microseconds);
     return MGX_OK;
 }
 int mgx_linger_stats(mgx_world *w, uint64_t *launches, uint64_t *posts, uint64_t *reruns, uint64_t *ended_by_device) {
     MGX_ENTER_SCHEDULE(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    const mgx_world::Linger &lg = w->linger;
+    const ResidentLaunches::Linger &lg = w->res.linger;
     if (launches) *launches = lg.launches;
     if (posts) *posts = lg.posts + (lg.un.active ? 1u : 0u);
     if (reruns) *reruns = lg.reruns;
@@ -440,7 +436,7 @@ int mgx_set_safety_multiplier(mgx_world *w, double multiplier) {
     if (!std::isfinite(multiplier) || !(multiplier > 0)) return fail(MGX_ERR_INVALID, "safety multiplier must be finite and > 0");
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     // (a resident launch the census declined is run again first: its schedule was issued under the old distance)
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     w->p.safety_multiplier = multiplier;
     if (w->dirty || !w->dev_valid || w->dev_in_ptr.empty()) return MGX_OK;
     const size_t n_slots = (size_t)w->dev_in_ptr.back(), n_edges = n_slots * (size_t)(w->K - 1);

@@ -149,7 +149,7 @@ static int contacts_read(mgx_world *w, ContactBook *b, uint64_t first, void *eve
     MGX_ENTER(w);
     if (!w || (!events && capacity)) return fail(MGX_ERR_INVALID, "null argument");
     if (!b->enabled) return fail(MGX_ERR_STATE, "%s", off);
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     hipStream_t s = w->stream;
     unsigned long long words[2] = {0ull, 0ull};
     HIP_TRY(hipMemcpyAsync(words, b->words.p, sizeof words, hipMemcpyDeviceToHost, s));

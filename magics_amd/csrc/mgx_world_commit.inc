@@ -184,7 +184,7 @@ static int retopo(mgx_world *w) {
     StageTimer tm("retopo");
     mgx_world::RetopoInc &ri = w->rinc;
     // (a world whose schedules can run as resident launches gets that kernel's peer table in the same block)
-    const bool want_peers = (w->d.R_total == w->d.R_local || w->xres.connected) && (w->p.enable_mask & 2u) && w->sweep_flag_buf.p;
+    const bool want_peers = (w->d.R_total == w->d.R_local || w->xres.connected) && (w->p.enable_mask & 2u) && w->res.sweep_flag_buf.p;
     conn_index_ensure(w);
     const ConnIndex &x = w->cidx;
     if (x.interleaved) return fail(MGX_ERR_STATE, "internal: node slots of two connections interleave");
@@ -208,7 +208,7 @@ static int retopo(mgx_world *w) {
     auto local_of = [&](int32_t id) -> long { return ((size_t)id < w->dev_of.size() && (size_t)dev_of[(size_t)id] < R) ? (long)dev_of[(size_t)id] : -1; };
     // (the peer table the device holds is only good for the robots it is not told about if it IS the table of the layout being
     // replaced: a world that could not run resident launches a moment ago has none)
-    if (want_peers && !w->peers_valid) ri.all = true;
+    if (want_peers && !w->res.peers_valid) ri.all = true;
     // which robots send their piece: the ones whose incoming list or peer row the index saw change
     ri.mark.assign(std::max<size_t>(R, 1), ri.all ? 1 : 0);
     if (!ri.all) {
@@ -310,12 +310,12 @@ static int retopo(mgx_world *w) {
     const bool gates_along = !w->flags_dirty;
     if (gates_along) HIP_TRY(w->ir_gate.reserve(NIs));
     const size_t peer_words = R + 1 + std::max<size_t>(n_peers, 1);
-    if (want_peers) HIP_TRY(w->peer_ptr_dev_b.reserve(peer_words));
+    if (want_peers) HIP_TRY(w->res.peer_ptr_dev_b.reserve(peer_words));
     RetopoBlock blk;
     blk.hdr = (const RetopoHeader *)dp;
     blk.data = (const uint4 *)((const char *)dp + b_hdr);
-    HIP_TRY(launch_retopo_robots(w->d, blk, w->in_ptr_dev.p, w->slot_recs.p, w->peer_ptr_dev.p, w->in_ptr_dev_b.p, w->slot_recs_b.p,
-                                 want_peers ? w->peer_ptr_dev_b.p : nullptr, w->ir_var_ptr.p, w->ir_var_mid.p, (int)NIs, w->ir_rec_b.p, w->ir_fv_eta_b.p,
+    HIP_TRY(launch_retopo_robots(w->d, blk, w->in_ptr_dev.p, w->slot_recs.p, w->res.peer_ptr_dev.p, w->in_ptr_dev_b.p, w->slot_recs_b.p,
+                                 want_peers ? w->res.peer_ptr_dev_b.p : nullptr, w->ir_var_ptr.p, w->ir_var_mid.p, (int)NIs, w->ir_rec_b.p, w->ir_fv_eta_b.p,
                                  w->ir_fv_lam_b.p, w->ir_bmu_b.p, gates_along ? w->ir_gate.p : nullptr, s));
     HIP_TRY(w->stage.release(ring_slot, s));
     tm.lap("launch");
@@ -325,24 +325,16 @@ static int retopo(mgx_world *w) {
     w->ir_bmu.swap(w->ir_bmu_b);
     w->in_ptr_dev.swap(w->in_ptr_dev_b);
     w->slot_recs.swap(w->slot_recs_b);
-    if (want_peers) w->peer_ptr_dev.swap(w->peer_ptr_dev_b);
     DevWorld &d = w->d;
     d.NI = (int)NIs;
     d.ir_rec = w->ir_rec.p; d.ir_fv_eta = w->ir_fv_eta.p; d.ir_fv_lam = w->ir_fv_lam.p; d.ir_bmu = w->ir_bmu.p;
-    // the resident kernel's LDS per workgroup (hence workgroups per CU) follows the largest number of edges on one robot:
-    // a capacity asked for a sparser topology says nothing about this one
-    if (ir_max_edges != d.ir_max_edges) w->resident_cap = w->resident_cap_sharded = -1;
+    if (ir_max_edges != d.ir_max_edges) w->res.lds_footprint_changed();
     d.ir_max_edges = ir_max_edges;
     w->dev_in_ptr.assign(ri.in_ptr.begin(), ri.in_ptr.end());
     ri.all = false;
     ri.clear_marks();
     w->conns_dirty = false;
-    w->peers_valid = want_peers;
-    if (want_peers) {
-        w->peer_idx_off = R + 1;
-        w->d.peer_ptr = w->peer_ptr_dev.p;
-        w->d.peer_idx = w->peer_ptr_dev.p + w->peer_idx_off;
-    }
+    w->res.peers_rebuilt(want_peers, R, d);
     int rc_flags = MGX_OK;  // the gate bytes follow the edges (the robots' own flags only when they changed too)
     if (w->flags_dirty) {
         rc_flags = upload_flags(w);
@@ -357,10 +349,10 @@ static int retopo(mgx_world *w) {
 
 static int commit(mgx_world *w) {
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     // (whoever comes through here enqueues work or reads state: a lingering launch ends first — unless the caller is on its way
     // to post a schedule into it)
-    if (w->linger.open && !w->linger.hold) { const int rcl = linger_close(w); if (rcl != MGX_OK) return rcl; }
+    if (!w->res.linger.hold) { const int rcl = linger_close(w); if (rcl != MGX_OK) return rcl; }
     if (!w->dirty) {
         if (w->conns_dirty) return retopo(w);
         if (w->flags_dirty) return upload_flags(w);
@@ -579,10 +571,7 @@ static int commit(mgx_world *w) {
     w->rinc.clear_marks();
     w->dev_valid = true;
     w->halo_dirty = true;
-    w->peers_valid = false;
-    w->sweep_flag_buf.n = 0;  // progress words of resident launches: re-created (zero) for the new device arrays
-    w->flag_base = 0;
-    w->resident_cap = w->resident_cap_sharded = -1;
+    w->res.arrays_rebuilt();
     w->xres.connected = false;  // ghost slots and progress words belonged to the old layout: the ranks wire them again
     // the direct exchange's pushes name device indices and ghost slots: they stay good for as long as the robots' device order does
     // (a relayout for new obstacles or reset variables keeps it; a robot that joins, migrates or is released does not)

@@ -33,10 +33,8 @@ static void settle_conn(mgx_world *w, IrConn &c) {
 // (the per-tick topology pass: what it deletes it settles itself).  Not while factors still lack inbox keys (their counting
 // replays the log per connection).
 static void flush_counts(mgx_world *w, bool lazy) {
-    if (w->pending.active) {  // the launch's entries join the log once it is known to have run
-        const int rcc = confirm_resident(w);
-        if (rcc != MGX_OK && w->sticky_rc == MGX_OK) w->sticky_rc = rcc;  // (a re-run that failed: reported by whatever runs or reads next)
-    }
+    const int rcc = confirm_resident(w);  // the pending launch's entries join the log once it is known to have run
+    if (rcc != MGX_OK && w->sticky_rc == MGX_OK) w->sticky_rc = rcc;  // (a re-run that failed: reported by whatever runs or reads next)
     const size_t n = w->robots.size();
     mgx_world::Cum &cu = w->cum;
     if (cu.nIv.size() < n) { cu.nIv.resize(n, 0); cu.nEv.resize(n, 0); cu.nEf.resize(n, 0); cu.on_ir.resize(n, 0); }

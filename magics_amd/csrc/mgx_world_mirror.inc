@@ -95,10 +95,9 @@ static void blob_unpack(Robot &rb, const double *b) {
 }
 
 // ---- pull: device -> host mirror ----------------------------------------------------------------
-static int confirm_resident(mgx_world *w, bool rerun = true, int32_t *outcome = nullptr);
 static int pull(mgx_world *w) {
     if (!w->dev_valid) return MGX_OK;
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     const int K = w->K;
     const size_t NT = (size_t)w->d.NT, NI = (size_t)w->d.NI, BS = (size_t)w->d.BS;
     std::vector<double> bl, sn, tlv, ife, ifl, ibm;

@@ -255,7 +255,7 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     w->stale_kinds |= ~w->p.enable_mask & 15u;
     tm.lap("counter log");
     const std::vector<Launch> plan = plan_launches(steps, n_steps);
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }  // (a declined launch is run again here: not this call's launches)
+    MGX_CONFIRM(w);  // (a declined launch is run again here: not this call's launches)
     w->last_sweep_launches = 0;
     w->last_sweep = SweepRan{};
     w->last_sweep_form = -1;
@@ -264,22 +264,11 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
         HIP_TRY(launch_update_priors(w->d, R, ms.robots_d.p, ms.waypoints_d.p, ms.ts_list_d.p, ms.what_d.p, max_speed, delta_t, s));
         rc = iterate_now(w, steps, n_steps);
     } else {
-        w->d.upd = ms.rec_d.p; w->d.upd_max_speed = max_speed; w->d.upd_delta_t = delta_t;
-        const int resident = run_resident(w, plan);
-        if (resident != 0) {
-            w->d.upd = nullptr;
-            rc = resident < 0 ? resident : MGX_OK;
-        } else {
-            bool first = true;
-            rc = MGX_OK;
-            for (const Launch &l : plan) {
-                if (!first) w->d.upd = nullptr;
-                rc = sweep(w, -1, l.ext, l.n_int ? (PH_INT_FACTOR | PH_INT_VARIABLE) : 0, l.n_int, l.hints);
-                first = false;
-                if (rc != MGX_OK) break;
-            }
-            w->d.upd = nullptr;
-        }
+        RidingUpdates upd;  // (in device memory: no host view, no ring slot)
+        upd.dev = ms.rec_d.p;
+        upd.max_speed = max_speed;
+        upd.delta_t = delta_t;
+        rc = run_schedule(w, plan, upd);
     }
     ms.tick_no += 1;
     tm.lap("prior updates + schedule");
@@ -346,8 +335,7 @@ int mgx_mission_run(mgx_world *w, mgx_mission_run_desc *d) {
         }
     }
     if (d->ticks_done && d->translations) {  // the last tick's Transforms: behind its launches
-        if (w->linger.open && (rc = linger_close(w)) != MGX_OK) return rc;
-        if (w->pending.active && (rc = confirm_resident(w)) != MGX_OK) return rc;
+        if ((rc = linger_close(w)) != MGX_OK || (rc = confirm_resident(w)) != MGX_OK) return rc;
         HIP_TRY(hipStreamSynchronize(w->stream));
         if (ms.tr_host) memcpy(d->translations + (size_t)(d->ticks_done - 1) * R * 3, ms.tr_host, sizeof(float) * 3 * R);
         if ((rc = check_device_error(w)) != MGX_OK) return rc;

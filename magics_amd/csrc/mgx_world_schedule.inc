@@ -62,23 +62,13 @@ int mgx_iterate(mgx_world *w, const uint8_t *steps, uint32_t n) {
 
 static int iterate_now(mgx_world *w, const uint8_t *steps, uint32_t n) {
     const std::vector<Launch> plan = plan_launches(steps, n);
-    if (w->pending.active) {  // (a declined launch is run again here: not this call's launches)
-        w->linger.hold = true;
-        const int rcc = confirm_resident(w);
-        w->linger.hold = false;
-        if (rcc != MGX_OK) return rcc;
-    }
+    const int rcc = confirm_held(w);  // (a declined launch is run again here: not this call's launches)
+    if (rcc != MGX_OK) return rcc;
     w->last_sweep_launches = 0;
     w->last_sweep = SweepRan{};
     w->last_sweep_form = -1;
-    w->linger.streak++;  // (every other entry point resets it: MGX_ENTER)
-    const int resident = run_resident(w, plan);
-    if (resident != 0) return resident < 0 ? resident : MGX_OK;
-    for (const Launch &l : plan) {
-        int rc = sweep(w, -1, l.ext, l.n_int ? (PH_INT_FACTOR | PH_INT_VARIABLE) : 0, l.n_int, l.hints);
-        if (rc != MGX_OK) return rc;
-    }
-    return MGX_OK;
+    w->res.schedule_issued();  // (every other entry point resets the streak: MGX_ENTER)
+    return run_schedule(w, plan, RidingUpdates{});
 }
 
 int mgx_internal_factor_iteration(mgx_world *w, int32_t robot) {
@@ -174,12 +164,8 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
     MGX_ENTER_SCHEDULE(w);
     if (!w || (!steps && n_steps) || (n && (!robots || !waypoints_xy || !time_scale || !what))) return fail(MGX_ERR_INVALID, "null argument");
     const std::vector<Launch> plan = plan_launches(steps, n_steps);
-    if (w->pending.active) {  // (a declined launch is run again here: not this call's launches)
-        w->linger.hold = true;
-        const int rcc = confirm_resident(w);
-        w->linger.hold = false;
-        if (rcc != MGX_OK) return rcc;
-    }
+    const int rcc = confirm_held(w);  // (a declined launch is run again here: not this call's launches)
+    if (rcc != MGX_OK) return rcc;
     w->last_sweep_launches = 0;
     w->last_sweep = SweepRan{};
     w->last_sweep_form = -1;
@@ -192,9 +178,7 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
         if (robots[i] < 0 || (size_t)robots[i] >= w->robots.size() || w->sets.ghost[(size_t)robots[i]] || w->sets.removed[(size_t)robots[i]] || (what[i] & ~3u))
             return fail(MGX_ERR_INVALID, "bad entry %u", i);
     StageTimer tmk("tick");
-    w->linger.hold = true;  // (a lingering launch stays: this tick is posted into it if it qualifies)
-    int rc = commit(w);
-    w->linger.hold = false;
+    const int rc = commit_held(w);  // (a lingering launch stays: this tick is posted into it if it qualifies)
     tmk.lap("commit (confirm + table rebuild)");
     if (rc != MGX_OK) return rc;
     const size_t RL = (size_t)w->d.R_local;
@@ -203,10 +187,10 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
     // a launch lingers and takes this tick: the records go straight into the coming number's slot of its box (the pinned ring's
     // slots are guarded by events, and an event behind a launch that lingers does not complete)
     int posting = 0;
-    if (w->linger.open && (posting = linger_prepare_post(w, plan)) < 0) return posting;
+    if (w->res.linger.open && (posting = linger_prepare_post(w, plan)) < 0) return posting;
     double *rec = nullptr;
     if (posting) {
-        rec = linger_upd_slot(w, w->launch_seq + 1ull);
+        rec = linger_upd_slot(w, w->res.launch_seq + 1ull);
     } else {
         HIP_TRY(w->stage.acquire(4 * RL * sizeof(double), &hp, &slot));
         rec = (double *)hp;
@@ -218,44 +202,23 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
         if (what[i] & 1u) log_change_prior(w, robots[i], w->K - 1);
         if (what[i] & 2u) log_change_prior(w, robots[i], 0);
     }
-    w->linger.streak++;  // (every other entry point resets it: MGX_ENTER)
+    w->res.schedule_issued();  // (every other entry point resets the streak: MGX_ENTER)
+    RidingUpdates upd;
+    upd.host = rec;
+    upd.max_speed = max_speed;
+    upd.delta_t = delta_t;
     if (posting) {
-        (void)linger_post(w, plan, true, max_speed, delta_t);
+        linger_post(w, plan, upd);
         tmk.lap("update records + counter log + post");
         return MGX_OK;
     }
     HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
     w->stale_kinds |= ~w->p.enable_mask & 15u;
     tmk.lap("update records + counter log");
-    {   // the whole tick as one resident launch when the world qualifies: the prior updates ride in it all the same
-        w->d.upd = (const double *)dp; w->d.upd_max_speed = max_speed; w->d.upd_delta_t = delta_t;
-        w->upd_ring_slot = slot;
-        w->upd_host = rec;
-        const int resident = run_resident(w, plan);
-        w->upd_host = nullptr;
-        w->upd_ring_slot = -1;
-        tmk.lap("resident launch enqueued");
-        if (resident != 0) {
-            w->d.upd = nullptr;
-            hipError_t e = w->stage.release(slot, w->stream);
-            if (resident < 0) return resident;
-            return e == hipSuccess ? MGX_OK : fail(MGX_ERR_HIP, "event record: %s", hipGetErrorString(e));
-        }
-        w->d.upd = nullptr;
-    }
-    bool first = true;
-    for (const Launch &l : plan) {
-        if (first) { w->d.upd = (const double *)dp; w->d.upd_max_speed = max_speed; w->d.upd_delta_t = delta_t; }
-        rc = sweep(w, -1, l.ext, l.n_int ? (PH_INT_FACTOR | PH_INT_VARIABLE) : 0, l.n_int, l.hints);
-        if (first) {
-            w->d.upd = nullptr;
-            first = false;
-            hipError_t e = w->stage.release(slot, w->stream);
-            if (rc == MGX_OK && e != hipSuccess) rc = fail(MGX_ERR_HIP, "event record: %s", hipGetErrorString(e));
-        }
-        if (rc != MGX_OK) return rc;
-    }
-    return MGX_OK;
+    // the whole tick as one resident launch when the world qualifies: the prior updates ride in it all the same
+    upd.dev = (const double *)dp;
+    upd.slot = slot;
+    return run_schedule(w, plan, upd, &tmk);
 }
 
 // FactorGraph::reset_variables (factorgraph.rs:1541-1564: VariableNode::reset, variable.rs:350-360, for every variable, then
@@ -328,7 +291,7 @@ int mgx_set_tracking_path(mgx_world *w, int32_t robot, const float *path_xy, uin
     if (w->robots[(size_t)robot].ghost || w->robots[(size_t)robot].removed) return fail(MGX_ERR_INVALID, "robot %d is not a live local robot", robot);
     if (n_path > 0xffffu) return fail(MGX_ERR_INVALID, "n_path %u: a factor's record is kept in 16 bits", n_path);
     // (a resident launch the census declined is run again first: its schedule was issued under the old path)
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     w->robots[(size_t)robot].path.assign(path_xy, path_xy + 2 * (size_t)n_path);
     if (w->dirty || !w->dev_valid) return MGX_OK;
     const size_t RL = (size_t)w->d.R_local;
@@ -370,8 +333,7 @@ int mgx_change_prior(mgx_world *w, int32_t robot, uint32_t var_ix, const double 
 int mgx_set_resident_launches(mgx_world *w, int32_t enabled) {
     MGX_ENTER(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    w->resident_off = enabled == 0;
-    w->resident_decline = enabled == 2;
+    w->res.set_mode(enabled);
     return MGX_OK;
 }
 int mgx_is_thawing(mgx_world *w, int32_t *thawing) {
@@ -383,7 +345,7 @@ int mgx_is_thawing(mgx_world *w, int32_t *thawing) {
 int mgx_last_launch_count(mgx_world *w, uint32_t *n_launches) {
     MGX_ENTER_SCHEDULE(w);
     if (!w || !n_launches) return fail(MGX_ERR_INVALID, "null argument");
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     *n_launches = w->last_sweep_launches;
     return MGX_OK;
 }
@@ -391,13 +353,13 @@ int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *fo
     MGX_ENTER_SCHEDULE(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     // (a resident launch the census declined has been run again launch by launch by the time it is decided: that is what ran)
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     if (variant) *variant = w->last_sweep.variant;
     if (ir_mode) *ir_mode = w->last_sweep.ir_mode;
     if (form) *form = w->last_sweep_form;
     if (resident_capacity) {
         const bool sharded = w->xres.connected;
-        int cap = sharded ? w->resident_cap_sharded : w->resident_cap;
+        int cap = sharded ? w->res.cap_sharded : w->res.cap;
         // (not asked by a launch yet: asked here, for the topology on the device — no commit, which would end a lingering launch)
         if (cap < 0) cap = device_ok() ? sweep_resident_capacity(w->d, sharded) : 0;
         *resident_capacity = cap;
@@ -453,7 +415,7 @@ int mgx_read_variable_means(mgx_world *w, uint32_t var_ix, double *means) {
 int mgx_message_counts(mgx_world *w, int32_t robot, uint64_t counts[4]) {
     MGX_ENTER(w);
     if (!w || !counts || robot < 0 || (size_t)robot >= w->robots.size()) return fail(MGX_ERR_INVALID, "bad argument");
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     if (w->robots[(size_t)robot].ghost) return fail(MGX_ERR_INVALID, "robot %d is a ghost here: its graph is counted on the rank that owns it", robot);
     flush_counts(w);
     const Robot &rb = w->robots[(size_t)robot];

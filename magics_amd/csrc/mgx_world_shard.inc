@@ -276,7 +276,7 @@ int mgx_robot_release(mgx_world *w, int32_t robot) {
 }
 
 static int halo_commit(mgx_world *w) {
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     // Changed connections alone (conns_dirty) are left to the next sweep: an exchange does not read the
     // edge tables, and the edges created by a topology pass must find the ghosts' records of the exchange
     // that follows the pass (their creation epoch is the owner's delivery count at that moment).
@@ -591,8 +591,7 @@ int mgx_halo_resident_setup(mgx_world *w, void **area_base, uint32_t *n_ghost_sl
     const bool has_factors = d.ir_max_edges > 0 && !w->conns.empty();
     bool ok = resident_enabled() && (w->p.enable_mask & 2u) && sweep_lds_bytes(w->K, d.ir_max_edges, true) <= sweep_resident_lds_max();
     if (ok && has_factors) {
-        if (w->resident_cap_sharded < 0) w->resident_cap_sharded = sweep_resident_capacity(d, true);
-        ok = d.R_local + 1 <= w->resident_cap_sharded;  // (+ the launch's decider workgroup)
+        ok = d.R_local + 1 <= w->res.capacity_for(d, true);  // (+ the launch's decider workgroup)
     }
     rc = ensure_resident_tables(w);  // settles this rank's segment count (progress words are created here)
     if (rc != MGX_OK) return rc;
@@ -603,7 +602,7 @@ int mgx_halo_resident_setup(mgx_world *w, void **area_base, uint32_t *n_ghost_sl
     xr.n_ghosts = NG;
     HIP_TRY(hipMemsetAsync(xr.area, 0, L.bytes, w->stream));
     {   // every ghost "has completed" what this rank's segment count says: nothing of an earlier launch is still being read
-        std::vector<unsigned long long> f((size_t)std::max(NG, 1), w->flag_base);
+        std::vector<unsigned long long> f((size_t)std::max(NG, 1), w->res.flag_base);
         HIP_TRY(hipMemcpyAsync((char *)xr.area + L.flag, f.data(), sizeof(unsigned long long) * f.size(), hipMemcpyHostToDevice, w->stream));
         HIP_TRY(hipStreamSynchronize(w->stream));
     }
@@ -611,7 +610,7 @@ int mgx_halo_resident_setup(mgx_world *w, void **area_base, uint32_t *n_ghost_sl
     *area_base = xr.area;
     *n_ghost_slots = (uint32_t)NG;
     *parity = (uint32_t)d.cur;
-    *segment_count = w->flag_base;
+    *segment_count = w->res.flag_base;
     // 2: everything but inter-robot factors is there — a world that follows its topology may get them later (every schedule is then
     // decided where the ranks agree: a rank that cannot run one as a resident launch says so there)
     *eligible = ok ? (has_factors ? 1 : 2) : 0;
@@ -637,7 +636,7 @@ int mgx_halo_resident_connect_peers(mgx_world *w, uint32_t n_peers, void *const 
         xr.peers[p].base = (unsigned long long)(uintptr_t)peer_area_base[p];
         xr.peers[p].n_slots = peer_ghost_slots[p];
         xr.peers[p].x = ((unsigned)d.cur ^ peer_parity[p]) & 1u;
-        xr.peers[p].flag_delta = peer_segment_count[p] - w->flag_base;  // modulo 2^64
+        xr.peers[p].flag_delta = peer_segment_count[p] - w->res.flag_base;  // modulo 2^64
     }
     const GhostAreaLayout Lm((size_t)xr.n_ghosts, (size_t)w->K);
     for (int p = 0; p < 2; p++) d.gxrec[p] = (const unsigned char *)xr.area + Lm.xrec[p];
@@ -662,7 +661,7 @@ int mgx_halo_resident_aim(mgx_world *w, uint32_t n_targets, const int32_t *robot
     if (n_targets && (!robots || !peer_index || !peer_slot)) return fail(MGX_ERR_INVALID, "null argument");
     mgx_world::ResidentHalo &xr = w->xres;
     if (!xr.area || !xr.connected) return fail(MGX_ERR_STATE, "mgx_halo_resident_connect_peers first");
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     if (!w->dev_valid || w->dirty) return fail(MGX_ERR_STATE, "the world's layout changed since mgx_halo_resident_setup");
     const DevWorld &d = w->d;
     const size_t R = (size_t)d.R_local, K = (size_t)w->K;
@@ -691,7 +690,7 @@ int mgx_halo_resident_aim(mgx_world *w, uint32_t n_targets, const int32_t *robot
     HIP_TRY(xr.xp_rec.upload(flat, w->stream));
     {
         const GhostAreaLayout Lm((size_t)xr.n_ghosts, K);
-        std::vector<unsigned long long> f((size_t)std::max(xr.n_ghosts, 1), w->flag_base);
+        std::vector<unsigned long long> f((size_t)std::max(xr.n_ghosts, 1), w->res.flag_base);
         HIP_TRY(hipMemcpyAsync((char *)xr.area + Lm.flag, f.data(), sizeof(unsigned long long) * f.size(), hipMemcpyHostToDevice, w->stream));
     }
     HIP_TRY(hipStreamSynchronize(w->stream));
@@ -703,7 +702,7 @@ int mgx_halo_resident_aim(mgx_world *w, uint32_t n_targets, const int32_t *robot
 int mgx_halo_resident_disconnect(mgx_world *w) {
     MGX_ENTER(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+    MGX_CONFIRM(w);
     HIP_TRY(hipStreamSynchronize(w->stream));
     w->xres.connected = false;
     w->xres.wired = false;
@@ -726,13 +725,7 @@ int mgx_resident_ready(mgx_world *w, const uint8_t *steps, uint32_t n, int32_t *
     if (rc != MGX_OK) return rc;
     *ready = resident_gate(w, plan_launches(steps, n)) ? 1 : 0;
     if (*ready && !(w->xres.connected && w->xres.agree)) {  // nobody to agree with: what this world's own launch needs
-        const DevWorld &d = w->d;
-        const bool sharded = w->xres.connected;
-        int &cap = sharded ? w->resident_cap_sharded : w->resident_cap;
-        bool can = d.ir_max_edges > 0 && !w->conns.empty() && !w->thaw_kinds && !w->ir_thaw_active && w->n_keyless == 0 && !w->resident_decline &&
-                   sweep_lds_bytes(w->K, d.ir_max_edges, true) <= sweep_resident_lds_max();
-        if (can && cap < 0) cap = sweep_resident_capacity(d, sharded);
-        *ready = can && d.R_local + 1 <= cap ? 1 : 0;
+        *ready = resident_fits(w, w->xres.connected) == FITS ? 1 : 0;
     }
     return MGX_OK;
 }
@@ -740,10 +733,10 @@ int mgx_resident_ready(mgx_world *w, const uint8_t *steps, uint32_t n, int32_t *
 int mgx_resident_stats(mgx_world *w, uint64_t *launches, uint64_t *declined, uint32_t *backoff) {
     MGX_ENTER_SCHEDULE(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
-    if (launches) *launches = w->resident_launches;
-    if (declined) *declined = w->resident_aborts;
-    if (backoff) *backoff = (uint32_t)w->resident_backoff;
+    MGX_CONFIRM(w);
+    if (launches) *launches = w->res.launches;
+    if (declined) *declined = w->res.aborts;
+    if (backoff) *backoff = (uint32_t)w->res.backoff.left;
     return MGX_OK;
 }
 

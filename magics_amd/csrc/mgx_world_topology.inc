@@ -85,7 +85,7 @@ static int search_front(mgx_world *w, const float **pos, float radius, uint32_t 
         // leave two or three free slots per XCD; enqueued at once "when both fit" the search still cost every third launch its
         // residency: tools/dynamic_tick_bench.py, 27 of 90 launches declined, 4.2 k ticks/s against 5.9 k behind the decision).
         // Behind a DECIDED launch the search finds the holes that launch leaves (mgx_topology.hip) and runs beside it.
-        if (w->pending.active) { const int rcc = confirm_resident(w); if (rcc != MGX_OK) return rcc; }
+        MGX_CONFIRM(w);
         if (!S.stream) HIP_TRY(hipStreamCreateWithFlags(&S.stream, hipStreamNonBlocking));
         ps.stream = S.stream;
     }

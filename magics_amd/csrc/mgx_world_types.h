@@ -1,4 +1,4 @@
-// mgx_world_types.h — what the host side is made of: launcher prototypes of the kernel files, error text, device buffers, the pinned argument ring, the neighbour search's state, the host mirror's records (Robot, IrConn), connection sets and index, the world itself, the entry hooks of the C ABI (MGX_ENTER).
+// mgx_world_types.h — what the host side is made of: launcher prototypes of the kernel files, error text, device buffers, the pinned argument ring, the neighbour search's state, the resident launches' state, the host mirror's records (Robot, IrConn), connection sets and index, the world itself, the entry hooks of the C ABI (MGX_ENTER).
 // Part of ONE translation unit (mgx_world.hip includes its parts in order); not a stand-alone header.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -21,6 +21,7 @@
 #include "mgx_dev.h"
 #include "mgx_grid.h"
 #include "mgx_search.h"  // the neighbour search: its dispatch, its pure helpers, the launchers of mgx_topology.hip
+#include "mgx_resident.h"  // resident launches, the host's arithmetic: segments, plan bytes, parity and segment count, back-off, riding updates
 
 namespace mgx {
 size_t sweep_lds_bytes(int K, int ir_edges);
@@ -439,6 +440,117 @@ struct NeighbourSearch {
     } mission;  // the coming tick's search, enqueued by mgx_mission_tick_end
 };
 
+// A block of host-mapped words the device writes and the host polls (a launch's verdict, a lingering launch's box): zeroed when
+// it is made, freed with its owner
+struct MappedBlock {
+    void *p = nullptr;
+    MappedBlock() = default;
+    MappedBlock(const MappedBlock &) = delete;
+    MappedBlock &operator=(const MappedBlock &) = delete;
+    ~MappedBlock() { release(); }
+    void release() { if (p) (void)hipHostFree(p); p = nullptr; }
+    hipError_t alloc(size_t bytes) {
+        release();
+        const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocMapped);
+        if (e == hipSuccess) memset(p, 0, bytes);
+        return e;
+    }
+};
+
+// A schedule (or the part of one that fits a launch) handed to the device that may have to be taken back: the resident launch
+// whose census verdict the host has not seen, and the post a lingering launch has not taken yet.  Everything needed to undo the
+// host's bookkeeping and run the same segments again launch by launch.
+struct Submitted {
+    bool active = false;
+    unsigned long long number = 0;  // the world's launch number it went out under
+    std::vector<Launch> plan;       // its segments
+    Standing before;                // where the world stood when it went out
+    bool partial = false;           // a launch that is not the first of its schedule (more than MAX_SEGS segments)
+    // the prior updates that ride in it.  A launch: where the kernel read them, and the ring slot a re-run guards again (the event
+    // behind a declined launch completed at once).  A post: host = its slot of records in the box, nothing else.
+    RidingUpdates upd;
+    void take_back(mgx_world *w);   // the world stands where it stood before; nothing of the schedule counts as launched
+};
+
+// The resident and lingering schedule launches of a world (SegPlan, LingerBox: mgx_dev.h): everything their host side owns
+// between calls.  mgx_world_launch.inc drives it (run_resident, confirm_resident, the linger_* functions); the entry points
+// of the C ABI come through MGX_ENTER, commit and confirm_resident, and the table builds of mgx_world_commit.inc tell it what
+// they changed through the methods below.  mgx_resident.h holds its arithmetic.
+struct ResidentLaunches {
+    // progress words, the abort word, the census' per-group counts and decision word (with its host-mapped copy), the exchange
+    // records of the local robots' variables in two parities
+    DevBuf<unsigned long long> sweep_flag_buf, sweep_abort_buf, census_buf, decision_buf;
+    DevBuf<unsigned char> xrec_buf;
+    MappedBlock decision_mem;
+    unsigned long long *decision_host() const { return (unsigned long long *)decision_mem.p; }
+    // the peer table: [R + 1 row pointers | entries] (current / being built by a topology change)
+    DevBuf<int32_t> peer_ptr_dev, peer_ptr_dev_b;
+    size_t peer_idx_off = 0;
+    std::vector<int32_t> peer_fill;
+    bool peers_valid = false;
+    unsigned long long flag_base = 0;   // the segment count: every progress word is below or at this value between launches
+    unsigned long long launch_seq = 0;  // the number of the last launch or post
+    enum Mode : int32_t { OFF = 0, ON = 1, DECLINE = 2 } mode = ON;  // mgx_set_resident_launches
+    Backoff backoff;
+    int cap = -1, cap_sharded = -1;  // workgroups of the resident kernel (of its sharded instantiation) the device holds at once; -1: not asked yet
+    int capacity_for(const DevWorld &d, bool sharded) {  // (asked of the runtime once per topology)
+        int &c = sharded ? cap_sharded : cap;
+        if (c < 0) c = sweep_resident_capacity(d, sharded);
+        return c;
+    }
+    uint64_t aborts = 0, launches = 0;
+    Submitted pending;      // the launch the host has enqueued but not yet seen decided (go / abort)
+    RidingUpdates riding;   // the prior updates of the schedule being submitted (run_schedule sets and clears them)
+    // LINGERING resident launches (mgx_dev.h): the host's side of the box.  `open`: a launch that lingers is in flight — every
+    // entry point but mgx_iterate / mgx_tick (and the pure queries) ends it first (MGX_ENTER, commit); those two POST their schedule
+    // into it when it qualifies (run_resident).  At most one post is outstanding without the launch's word for it (`un`): what
+    // is needed to take it back and run it as a launch of its own if the launch ended first.
+    struct Linger {
+        long long ticks = -1;  // wall-clock ticks (100 MHz) a robot's workgroup waits for the next post; -1: not asked yet, 0: off
+        MappedBlock box_mem;   // the box, then two blocks of prior-update records
+        LingerBox *box() const { return (LingerBox *)box_mem.p; }
+        size_t upd_stride = 0;  // f64 words per slot of prior-update records behind the box
+        DevBuf<unsigned long long> go;
+        DevBuf<unsigned char> dev;  // the launch's device-side slots (the postman's copies of the posts): [2][dev_stride]
+        size_t dev_stride = 0;
+        bool open = false, hold = false;
+        unsigned long long seq0 = 0;       // number of the open launch's own plan
+        SweepRan ran;                      // the open launch's instantiation (what a post runs in)
+        uint32_t taken_in_launch = 0;      // posts the open launch has taken
+        int useless = 0;                   // lingering launches in a row that ended without having taken a post
+        uint32_t streak = 0;               // schedules issued back to back, this one included (no other call on the world in between)
+        Submitted un;
+        uint64_t launches = 0, posts = 0, reruns = 0, ended_by_device = 0;
+    } linger;
+    // ---- what the rest of the host tells it ----
+    void arrays_rebuilt() {  // commit laid the device arrays out again: progress words are re-created (zero), the count starts over
+        peers_valid = false;
+        sweep_flag_buf.n = 0;
+        flag_base = 0;
+        cap = cap_sharded = -1;
+    }
+    // the resident kernel's LDS per workgroup (hence workgroups per CU) follows the largest number of edges on one robot: a
+    // capacity asked for a sparser topology says nothing about this one
+    void lds_footprint_changed() { cap = cap_sharded = -1; }
+    // retopo built the peer table of the new topology beside the edge tables (or could not: no resident launches on this world now)
+    void peers_rebuilt(bool built, size_t R, DevWorld &d) {
+        if (built) {
+            peer_ptr_dev.swap(peer_ptr_dev_b);
+            peer_idx_off = R + 1;
+            d.peer_ptr = peer_ptr_dev.p;
+            d.peer_idx = peer_ptr_dev.p + peer_idx_off;
+        }
+        peers_valid = built;
+    }
+    void set_mode(int32_t enabled) { mode = enabled == 0 ? OFF : enabled == 2 ? DECLINE : ON; }
+    void set_linger(int32_t microseconds) {  // negative: as the environment says (asked again at the next launch)
+        linger.ticks = microseconds >= 0 ? (long long)std::min(microseconds, 1000000) * 100ll : -1;
+        linger.useless = 0;
+    }
+    void schedule_issued() { linger.streak++; }  // mgx_iterate / mgx_tick
+    void other_call() { linger.streak = 0; }     // every other entry point (MGX_ENTER)
+};
+
 }  // namespace
 
 // Incoming inter-robot connections of every local robot in inbox key order (graph key, node index
@@ -457,7 +569,6 @@ struct Incoming {
     int ir_max_edges = 0;
     bool blocks_ok = true;
 };
-struct Launch { uint32_t ext; int n_int; uint32_t hints; };  // one [external iteration] internal* segment of a schedule
 
 // Who points at whom, kept IN STEP with the connection list (ir_connect, ir_disconnect_batch) instead of being derived from it in
 // two passes over every connection whenever a topology pass has changed something: per robot id the connections it is the TARGET
@@ -516,14 +627,7 @@ struct mgx_world {
     DevBuf<uint8_t> ir_gate, antenna, idle, sdf;
     DevBuf<double> radius_dev;  // [R_total] the robots' radii by device index (laid out by commit): what mgx_set_safety_multiplier rewrites d_safe from
     StageRing stage;  // packed per-tick arguments
-    // resident schedule launches (SegPlan, mgx_dev.h): progress words, peer lists, the abort / error words
-    DevBuf<unsigned long long> sweep_flag_buf, sweep_abort_buf;
-    DevBuf<unsigned char> xrec_buf;  // exchange records of the local robots' variables, two parities (mgx_dev.h)
-    DevBuf<int32_t> peer_ptr_dev, peer_ptr_dev_b;  // [R + 1 row pointers | entries] (current / being built by a topology change)
-    size_t peer_idx_off = 0;
-    std::vector<int32_t> peer_fill;
-    unsigned long long *sweep_err_host = nullptr;  // host-mapped; non-zero once a wait inside a resident launch gave up
-    unsigned long long flag_base = 0;              // every progress word is below or at this value between launches
+    unsigned long long *sweep_err_host = nullptr;  // host-mapped; non-zero once a wait inside a resident launch (or the direct halo's) gave up
     // mgx_batch_begin .. mgx_batch_end: the schedules mgx_iterate was handed since the last submission, one after the other (what
     // iterate(a); iterate(b) computes is what iterate(a ++ b) computes), the launches they were submitted as and how many of them
     struct Batch {
@@ -531,67 +635,9 @@ struct mgx_world {
         std::vector<uint8_t> steps;
         uint32_t schedules = 0, submissions = 0, launches = 0;
     } batch;
-    bool resident_off = false;                     // mgx_set_resident_launches(w, 0)
-    bool resident_decline = false;                 // mgx_set_resident_launches(w, 2)
-    // residency census of resident launches (SegPlan, mgx_dev.h): cumulative per-group counts the device counters reach, the
-    // launch number, and the launch the host has enqueued but not yet seen decided (go / abort)
-    DevBuf<unsigned long long> census_buf, decision_buf;
-    unsigned long long *decision_host = nullptr;   // host-mapped
-    unsigned long long launch_seq = 0;
-    struct PendingResident {
-        bool active = false;
-        unsigned long long seq = 0;
-        std::vector<std::pair<uint32_t, int>> segs;  // (external phases, internal iterations) of the launch's segments
-        std::vector<uint32_t> hints;
-        int cur_before = 0;
-        unsigned long long flag_base_before = 0;
-        bool partial = false;  // the launch is not the first of its schedule (more than MAX_SEGS segments)
-        const double *upd = nullptr;  // mgx_tick: the prior updates that ride in the launch
-        int upd_slot = -1;            // ... and the pinned ring slot they sit in (-1: device memory of the caller's, mgx_mission_tick):
-                                      // a re-run guards it again — the event behind the declined launch completed at once
-        double upd_max_speed = 0.0, upd_delta_t = 0.0;
-    } pending;
-    int upd_ring_slot = -1;  // mgx_tick -> run_resident: the ring slot d.upd points into
-    const double *upd_host = nullptr;  // ... and the host's view of the same records (null: they live in device memory)
-    // LINGERING resident launches (mgx_dev.h): the host's side of the box.  `open`: a launch that lingers is in flight — every
-    // entry point but mgx_iterate / mgx_tick (and the pure queries) ends it first (MGX_ENTER, commit); those two POST their schedule
-    // into it when it qualifies (run_resident).  At most one post is outstanding without the launch's word for it (`un`): what
-    // is needed to take it back and run it as a launch of its own if the launch ended first.
-    struct Linger {
-        long long ticks = -1;  // wall-clock ticks (100 MHz) a robot's workgroup waits for the next post; -1: not asked yet, 0: off
-        LingerBox *box = nullptr;
-        size_t upd_stride = 0;  // f64 words per slot of prior-update records behind the box
-        DevBuf<unsigned long long> go;
-        DevBuf<unsigned char> dev;  // the launch's device-side slots (the postman's copies of the posts): [2][dev_stride]
-        size_t dev_stride = 0;
-        bool open = false, hold = false;
-        unsigned long long seq0 = 0;       // number of the open launch's own plan
-        SweepRan ran;                      // the open launch's instantiation (what a post runs in)
-        uint32_t taken_in_launch = 0;      // posts the open launch has taken
-        int useless = 0;                   // lingering launches in a row that ended without having taken a post
-        uint32_t streak = 0;               // schedules issued back to back, this one included (no other call on the world in between)
-        struct Post {
-            bool active = false;
-            unsigned long long number = 0;
-            std::vector<Launch> plan;
-            bool has_upd = false;
-            double max_speed = 0.0, delta_t = 0.0;
-            int cur_before = 0;
-            unsigned long long flag_base_before = 0;
-        } un;
-        uint64_t launches = 0, posts = 0, reruns = 0, ended_by_device = 0;
-    } linger;
+    ResidentLaunches res;  // resident and lingering schedule launches: their words and tables, the launch not yet decided, the open launch and its post
     int sticky_rc = 0;       // a declined launch whose re-run failed inside a call that cannot report it (flush_counts): every
                              // later sweep, read-back and mgx_synchronize reports it (check_device_error)
-    // after a declined launch the schedules skip the resident form for a while: counted in world-wide external iterations that
-    // ran launch by launch (whoever drives them: the engine's own schedules or a host's mgx_sweep calls — on a sharded world
-    // every rank runs the same ones, so every rank comes back to the resident form with the same schedule)
-    int resident_backoff = 0;
-    int resident_backoff_len = 0;
-    uint64_t resident_aborts = 0, resident_launches = 0;
-    int resident_cap = -1;                         // workgroups of the resident kernel the device holds at once (-1: not asked yet)
-    int resident_cap_sharded = -1;                 // the same for the instantiation that takes ghost records in-launch
-    bool peers_valid = false;
     // what the per-tick table rebuild reads of EVERY connection, 16 bytes apiece beside the connections themselves (168 bytes and
     // four vectors each): kept in step wherever the list changes (ir_connect, ir_disconnect, ir_disconnect_batch)
     struct ConnHot {
@@ -787,6 +833,14 @@ static void conn_index_ensure(mgx_world *w);
 static int iterate_now(mgx_world *w, const uint8_t *steps, uint32_t n);
 static int submit_batch(mgx_world *w);
 static int linger_close(mgx_world *w);
+// the verdict of the resident launch not yet decided, if there is one (mgx_world_launch.inc): whoever enqueues work behind it or
+// reads what it wrote comes through here first
+static int confirm_resident(mgx_world *w, bool rerun = true, int32_t *outcome = nullptr);
+#define MGX_CONFIRM(w)                                                  \
+    do {                                                                \
+        const int rc_confirm_ = confirm_resident(w);                    \
+        if (rc_confirm_ != MGX_OK) return rc_confirm_;                  \
+    } while (0)
 // MGX_ENTER_SCHEDULE: mgx_tick (mgx_iterate has the batch's own logic) and the pure queries — recorded schedules are submitted,
 // a lingering launch stays open.  MGX_ENTER: everything else — it also ends a lingering launch (what the call does would sit
 // behind it in the stream, or read what it has not written back) and breaks the streak of back-to-back schedules.
@@ -801,8 +855,8 @@ static int linger_close(mgx_world *w);
     do {                                                                \
         MGX_ENTER_SCHEDULE(w);                                          \
         if (w) {                                                        \
-            (w)->linger.streak = 0;                                     \
-            if ((w)->linger.open) {                                     \
+            (w)->res.other_call();                                      \
+            if ((w)->res.linger.open) {                                 \
                 const int rc_enter_ = linger_close(w);                  \
                 if (rc_enter_ != MGX_OK) return rc_enter_;              \
             }                                                           \
