@@ -327,6 +327,32 @@ int mgx_reset_tracking_factors(mgx_world *w, int32_t robot);
  * (MGX_ERR_INVALID otherwise, nothing changes).  Only the packed path arrays are rebuilt
  * and uploaded: no state is pulled, nothing else is laid out again. */
 int mgx_set_tracking_path(mgx_world *w, int32_t robot, const float *path_xy, uint32_t n_path);
+/* The whole path-finding completion handler (robot.rs:643-799) for a batch of robots in ONE call — global paths arrive in bursts
+ * (a formation that spawns, a fleet that re-plans).  For every listed robot i, in the handler's order and with the same arguments:
+ *   mgx_set_tracking_path(robots[i], path_i)                                   robot.rs:674-682
+ *   mgx_reset_variables(robots[i], means[i], K, first_last_sigma, inbetween_sigma)   robot.rs:766-768
+ *   mgx_reset_tracking_factors(robots[i])        if MGX_GLOBAL_PATH_RESET_TRACKING   robot.rs:769
+ *   Route::update_waypoints(path_i)              if MGX_GLOBAL_PATH_ROUTE            robot.rs:778, :389-392
+ *   mgx_set_idle(robots[i], 0)                   if MGX_GLOBAL_PATH_ACTIVATE         robot.rs:786
+ * path_i = path_xy[path_ptr[i] .. path_ptr[i+1]) ([.][2] f32, 2 <= points <= 65535); means: [n][K][4].  With ROUTE the robot's
+ * device mission (mgx_mission_set) takes the route path_i[1:] widened to f64 — target_index = 1 skips the first point — and its
+ * next waypoint is that route's first; reach rules, Transform and time scale stay.
+ * Refused as a whole, nothing changed: null arrays, a path outside 2 .. 65535 points, a robot that is not a live local one or
+ * is listed twice (MGX_ERR_INVALID); ROUTE on a robot without a mission or whose mission is complete (MGX_ERR_STATE).
+ * Which worlds take which path:
+ *   - laid out (launched at least once, no robot / obstacle change pending), unsharded, and in none of the switching states
+ *     (no factor kind ever switched at run time, no factors that still lack inbox keys): applied IN PLACE on the device by one
+ *     small kernel pair — nothing is pulled, nothing is laid out again (mgx_layout_stats does not move);
+ *   - every other world (not laid out yet or about to be laid out again, sharded, a kind switched with mgx_set_enabled): the
+ *     per-robot calls above run internally — the same result, at the price of one re-layout by the next launch. */
+#define MGX_GLOBAL_PATH_RESET_TRACKING 1u  /* reset_tracking_factors          robot.rs:769                 */
+#define MGX_GLOBAL_PATH_ROUTE          2u  /* active_route.update_waypoints   robot.rs:778, :389-392       */
+#define MGX_GLOBAL_PATH_ACTIVATE       4u  /* mission.state = Active          robot.rs:786  (idle := 0)     */
+int mgx_apply_global_paths(mgx_world *w, uint32_t n, const int32_t *robots, const uint32_t *path_ptr, const float *path_xy,
+                           const double *means, double first_last_sigma, double inbetween_sigma, uint32_t flags);
+/* Which path ran (read-only, no side effect on launches in flight): n_layouts counts the full rebuilds of the device arrays
+ * from the host mirror, n_pulls the downloads of the device state into it, since the world was created.  Either may be null. */
+int mgx_layout_stats(mgx_world *w, uint64_t *n_layouts, uint64_t *n_pulls);
 
 /* The driver's per-tick prior updates, batched over robots in one launch:
  *   what[i] & 1: update_prior_of_horizon_state (robot.rs:2182-2283) — the last variable of robots[i]
@@ -360,7 +386,12 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
  *   update_failed_comms                      robot.rs:1593-1601  `antennas` (one byte per robot id, the caller's draws; NULL: none)
  *   update_prior_of_horizon_state / _current_state_v3 + the Transform increment   robot.rs:2182-2338
  *   iterate_gbp_v2                           robot.rs:1769-1861  over `steps`
- * stats (optional) = {connections created, pairs deleted, missions completed this tick}.  Unsharded worlds. */
+ * stats (optional) = {connections created, pairs deleted, missions completed this tick}.  Unsharded worlds.
+ * A robot whose mission is idle (mgx_set_idle: MissionState::Idle, waiting for a global path) waits: its next waypoint does not
+ * advance (Mission::advance_to_next_waypoint, robot.rs:995-1005), it gets no prior update and its Transform does not move
+ * (both systems skip it, robot.rs:2212, 2303); it still takes part in the neighbour search, the topology pass and the collision
+ * passes, and sits out the sweeps.  mgx_apply_global_paths with MGX_GLOBAL_PATH_ROUTE | MGX_GLOBAL_PATH_ACTIVATE hands it its
+ * route and wakes it up. */
 typedef struct mgx_mission_desc {
     uint32_t n_waypoints;         /* waypoints still to visit; the first one is the next target (>= 1)                 */
     uint32_t reserved;

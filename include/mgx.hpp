@@ -15,6 +15,7 @@
 
 #include <array>
 #include <cstdint>
+#include <limits>
 #include <memory>
 #include <optional>
 #include <stdexcept>
@@ -217,6 +218,33 @@ public:
         std::vector<uint8_t> what(robots.size(), 3);
         check(mgx_update_priors(w_, (uint32_t)robots.size(), robots.data(), next_waypoints[0].data(), time_scale.data(), what.data(),
                                 max_speed, delta_t));
+    }
+    /// The path-finding completion handler (robot.rs:643-799) for a batch of robots in one call (mgx_apply_global_paths):
+    /// set_tracking_path, reset_variables(means, first_last_sigma, inbetween_sigma), and per `flags` (MGX_GLOBAL_PATH_*)
+    /// reset_tracking_factors, the device mission's new route paths[i][1:] and mission.state = Active.  means[i]: K vectors.
+    /// In place on the device for a laid-out, unsharded world that never switched a factor kind; the per-robot calls otherwise.
+    void apply_global_paths(const std::vector<int32_t> &robots, const std::vector<std::vector<std::array<float, 2>>> &paths,
+                            const std::vector<std::vector<Vector4>> &means, double first_last_sigma = 1e30,
+                            double inbetween_sigma = std::numeric_limits<double>::infinity(),
+                            uint32_t flags = MGX_GLOBAL_PATH_RESET_TRACKING) {
+        if (paths.size() != robots.size() || means.size() != robots.size()) throw Error(MGX_ERR_INVALID, "one path and one set of means per robot");
+        std::vector<uint32_t> ptr(robots.size() + 1, 0);
+        std::vector<float> xy;
+        std::vector<double> m;
+        for (size_t i = 0; i < robots.size(); i++) {
+            for (const auto &p : paths[i]) { xy.push_back(p[0]); xy.push_back(p[1]); }
+            ptr[i + 1] = (uint32_t)(xy.size() / 2);
+            if (means[i].size() != (size_t)K_) throw Error(MGX_ERR_INVALID, "means: one vector per variable");
+            for (const Vector4 &v : means[i]) m.insert(m.end(), v.begin(), v.end());
+        }
+        check(mgx_apply_global_paths(w_, (uint32_t)robots.size(), robots.data(), ptr.data(), xy.data(), m.data(), first_last_sigma,
+                                     inbetween_sigma, flags));
+    }
+    /// (full rebuilds of the device arrays from the host mirror, downloads of the device state into it) — mgx_layout_stats
+    std::pair<uint64_t, uint64_t> layout_stats() {
+        uint64_t layouts = 0, pulls = 0;
+        check(mgx_layout_stats(w_, &layouts, &pulls));
+        return {layouts, pulls};
     }
     std::vector<Vector4> read_variable_means(uint32_t variable_index) {
         uint32_t n = 0;

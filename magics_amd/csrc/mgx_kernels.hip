@@ -143,6 +143,57 @@ __global__ void k_update_priors(DevWorld w, int n, const int32_t *robots, const 
     }
 }
 
+// ---- global paths (mgx_apply_global_paths) ------------------------------------------------------------
+// FactorGraph::reset_variables + reset_tracking_factors (factorgraph.rs:1541-1590) of the listed robots, applied to the arrays
+// pull() reads back — the host edit of mgx_reset_variables / mgx_reset_tracking_factors restated where the state lives.
+// k_global_paths_robots, one workgroup per listed robot: belief mean <- the given means, belief precision <- diag(sigma)
+// (+inf allowed), own factor -> variable messages empty, the snapshot's means and the delivery counts back to zero, the
+// tracking factors' timeout to Some(10), the messages of foreign inter-robot factors attached to its variables empty, and —
+// under device missions — the next waypoint back to the first of the new route.  Every array is component-major: consecutive
+// lanes write consecutive elements.  means: [n][4][K], component-major as the blob keeps them (the host transposes).
+constexpr int GLOBAL_PATHS_THREADS = 256;
+__global__ void __launch_bounds__(GLOBAL_PATHS_THREADS) k_global_paths_robots(DevWorld w, int n, const int32_t *__restrict__ robots,
+                                                                              const double *__restrict__ means, double first_last_sigma,
+                                                                              double inbetween_sigma, int reset_tracking,
+                                                                              int32_t *__restrict__ mission_target) {
+    if ((int)blockIdx.x >= n) return;
+    const int r = robots[blockIdx.x], tid = threadIdx.x, K = w.K, E1 = w.E + 1;
+    const BlobLayout L(K);
+    double *b = w.blob + (size_t)r * w.BS;
+    const double *m = means + (size_t)blockIdx.x * 4 * K;
+    for (int t = tid; t < 4 * K; t += GLOBAL_PATHS_THREADS) b[L.mu() + t] = m[t];
+    for (int t = tid; t < 16 * K; t += GLOBAL_PATHS_THREADS) {
+        const int c = t / K, i = t - c * K;
+        b[L.bel() + 4 * K + t] = (c % 5 == 0) ? ((i == 0 || i == K - 1) ? first_last_sigma : inbetween_sigma) : 0.0;
+    }
+    for (int t = tid; t < 20 * E1; t += GLOBAL_PATHS_THREADS) b[L.fv() + t] = 0.0;  // (column E is zero already)
+    const int v0 = r * K;
+    double *snap = w.snap[w.cur] + (size_t)v0 * SNAP_W;
+    for (int t = tid; t < 4 * K; t += GLOBAL_PATHS_THREADS) snap[(t >> 2) * SNAP_W + 20 + (t & 3)] = 0.0;
+    for (int t = tid; t < K; t += GLOBAL_PATHS_THREADS) w.snap_epoch[w.cur][v0 + t] = 0u;
+    if (reset_tracking)
+        for (int t = tid; t < K - 2; t += GLOBAL_PATHS_THREADS) {
+            int32_t *rec = w.trk_record + (size_t)r * (K - 2) + t;
+            *rec = (*rec & 0xffff) | (11 << 16);  // Some(10), gbp_math.h tracking_timeout_skips
+        }
+    const int e0 = w.ir_var_ptr[v0], e1 = w.ir_var_ptr[v0 + K];
+    for (int c = 0; c < 4; c++)
+        for (int e = e0 + tid; e < e1; e += GLOBAL_PATHS_THREADS) w.ir_fv_eta[(size_t)c * w.NI + e] = 0.0;
+    for (int c = 0; c < 16; c++)
+        for (int e = e0 + tid; e < e1; e += GLOBAL_PATHS_THREADS) w.ir_fv_lam[(size_t)c * w.NI + e] = 0.0;
+    if (mission_target && tid == 0) mission_target[r] = 0;  // (device index == robot id: missions run on unsharded worlds)
+}
+// k_global_paths_owned, one thread per inter-robot edge: the factors a listed robot OWNS (selected[src_robot]) have their other
+// inbox entry — the target variable's last response mean — emptied, and their creation epoch restarts with the delivery counts.
+__global__ void k_global_paths_owned(DevWorld w, int n_edges, IrEdgeRec *__restrict__ recs, const uint8_t *__restrict__ selected) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= n_edges) return;
+    if (!selected[recs[e].src_robot]) return;
+#pragma unroll
+    for (int c = 0; c < 4; c++) w.ir_bmu[(size_t)c * w.NI + e] = 0.0;
+    recs[e].created = 0u;
+}
+
 // ---- factor kinds switched off and on at run time (mgx_set_enabled) ------------------------------------
 // k_freeze: the inbox of every internal factor of the given kinds as it is NOW (a kind is being switched
 // off: from here on these factors receive nothing, factor/mod.rs:307-310), one thread per (robot, edge slot).
@@ -473,6 +524,7 @@ __global__ void k_gather_variable_means(DevWorld w, int var, double *__restrict_
 __global__ void k_mission_reached(DevWorld w, DevMission m, int n, long long tick, unsigned int *ev) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n || !m.has[r]) return;
+    if (w.idle[r]) return;  // Mission::advance_to_next_waypoint does nothing while MissionState::Idle (robot.rs:995-1005)
     const int n_wp = m.wp_ptr[r + 1] - m.wp_ptr[r];
     const int t = m.target[r];
     if (t >= n_wp) return;
@@ -508,7 +560,8 @@ __global__ void k_mission_prepare(DevWorld w, DevMission m, int n, const uint8_t
     if (r >= n) return;
     const int n_wp = m.has[r] ? m.wp_ptr[r + 1] - m.wp_ptr[r] : 0;
     const int t = m.has[r] ? m.target[r] : 0;
-    const bool go = moving[r] && m.has[r] && t < n_wp;  // alive and a next waypoint exists (robot.rs:2216-2228)
+    // alive, a next waypoint exists (robot.rs:2216-2228) and the mission is not idle (both systems skip it, robot.rs:2212, 2303)
+    const bool go = moving[r] && m.has[r] && t < n_wp && !w.idle[r];
     double wx = 0.0, wy = 0.0;
     const double ts = m.time_scale[r];
     if (go) {
@@ -750,6 +803,16 @@ hipError_t launch_change_prior(const DevWorld &w, int n, const int32_t *robots, 
                                hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_change_prior, dim3((n + 63) / 64), dim3(64), 0, stream, w, n, robots, vars, means);
+    return hipGetLastError();
+}
+hipError_t launch_global_paths(const DevWorld &w, int n, const int32_t *robots, const double *means, double first_last_sigma,
+                               double inbetween_sigma, bool reset_tracking, int32_t *mission_target, int n_edges, IrEdgeRec *recs,
+                               const uint8_t *selected, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_global_paths_robots, dim3((unsigned)n), dim3(GLOBAL_PATHS_THREADS), 0, stream, w, n, robots, means, first_last_sigma,
+                       inbetween_sigma, reset_tracking ? 1 : 0, mission_target);
+    if (n_edges > 0)
+        hipLaunchKernelGGL(k_global_paths_owned, dim3((unsigned)((n_edges + 255) / 256)), dim3(256), 0, stream, w, n_edges, recs, selected);
     return hipGetLastError();
 }
 hipError_t launch_update_priors(const DevWorld &w, int n, const int32_t *robots, const double *waypoints, const double *time_scale,

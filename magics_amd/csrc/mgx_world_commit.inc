@@ -570,6 +570,7 @@ static int commit(mgx_world *w) {
     w->rinc.all = true;  // (no slot records on the device yet, device indices may have moved: the first topology change sends everything)
     w->rinc.clear_marks();
     w->dev_valid = true;
+    w->n_layouts++;
     w->halo_dirty = true;
     w->res.arrays_rebuilt();
     w->xres.connected = false;  // ghost slots and progress words belonged to the old layout: the ranks wire them again

@@ -98,6 +98,7 @@ static void blob_unpack(Robot &rb, const double *b) {
 static int pull(mgx_world *w) {
     if (!w->dev_valid) return MGX_OK;
     MGX_CONFIRM(w);
+    w->n_pulls++;
     const int K = w->K;
     const size_t NT = (size_t)w->d.NT, NI = (size_t)w->d.NI, BS = (size_t)w->d.BS;
     std::vector<double> bl, sn, tlv, ife, ifl, ibm;

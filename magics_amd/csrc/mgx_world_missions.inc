@@ -248,7 +248,7 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     tm.lap("search of the coming tick enqueued");
     for (int r = 0; r < R; r++) {  // message counters: the prior changes of the robots that move (what the device decides too)
         const Robot &rb = w->robots[(size_t)r];
-        if (rb.removed || rb.ghost || !ms.has[(size_t)r] || ms.finished_tick[(size_t)r] >= 0) continue;
+        if (rb.removed || rb.ghost || rb.idle || !ms.has[(size_t)r] || ms.finished_tick[(size_t)r] >= 0) continue;
         log_change_prior(w, r, w->K - 1);
         log_change_prior(w, r, 0);
     }

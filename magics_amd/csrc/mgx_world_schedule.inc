@@ -313,6 +313,156 @@ int mgx_set_tracking_path(mgx_world *w, int32_t robot, const float *path_xy, uin
     return check_device_error(w);
 }
 
+// The whole path-finding completion handler (robot.rs:643-799) for a batch of robots: set_tracking_path, reset_variables,
+// reset_tracking_factors, mission.state = Active, and — under device missions — Route::update_waypoints.  On a world that is
+// laid out, unsharded and in none of the switching states the reset is applied IN PLACE (k_global_paths_robots /
+// k_global_paths_owned, which restate the host edit of mgx_reset_variables above on the arrays pull() reads back): nothing is
+// pulled, nothing is laid out again, the device stays the truth.  Any other world runs the per-robot calls above.
+static int apply_global_route(mgx_world *w, int32_t robot, const float *xy, uint32_t n_path, bool on_device);
+int mgx_apply_global_paths(mgx_world *w, uint32_t n, const int32_t *robots, const uint32_t *path_ptr, const float *path_xy, const double *means,
+                           double first_last_sigma, double inbetween_sigma, uint32_t flags) {
+    MGX_ENTER(w);
+    if (!w || !robots || !path_ptr || !path_xy || !means) return fail(MGX_ERR_INVALID, "null argument");
+    if (flags & ~(MGX_GLOBAL_PATH_RESET_TRACKING | MGX_GLOBAL_PATH_ROUTE | MGX_GLOBAL_PATH_ACTIVATE)) return fail(MGX_ERR_INVALID, "bad flags");
+    if (n == 0) return MGX_OK;
+    const mgx_world::Mission &msc = w->mission;
+    std::vector<uint8_t> listed(w->robots.size(), 0);
+    for (uint32_t i = 0; i < n; i++) {
+        const int32_t r = robots[i];
+        if (r < 0 || (size_t)r >= w->robots.size()) return fail(MGX_ERR_INVALID, "bad robot id at %u", i);
+        if (w->robots[(size_t)r].ghost || w->robots[(size_t)r].removed) return fail(MGX_ERR_INVALID, "robot %d is not a live local robot", r);
+        if (listed[(size_t)r]) return fail(MGX_ERR_INVALID, "robot %d is listed twice", r);
+        listed[(size_t)r] = 1;
+        if (path_ptr[i + 1] < path_ptr[i]) return fail(MGX_ERR_INVALID, "path_ptr decreases at %u", i);
+        const uint32_t np = path_ptr[i + 1] - path_ptr[i];
+        if (np < 2) return fail(MGX_ERR_INVALID, "path %u: n_path must be >= 2 (TwoOrMore), got %u", i, np);
+        if (np > 0xffffu) return fail(MGX_ERR_INVALID, "path %u: n_path %u: a factor's record is kept in 16 bits", i, np);
+        if (flags & MGX_GLOBAL_PATH_ROUTE) {
+            if (!msc.any || (size_t)r >= msc.has.size() || !msc.has[(size_t)r]) return fail(MGX_ERR_STATE, "robot %d has no mission (mgx_mission_set)", r);
+            if (msc.finished_tick[(size_t)r] >= 0) return fail(MGX_ERR_STATE, "robot %d has completed its mission", r);
+        }
+    }
+    const int K = w->K;
+    const bool sharded = std::find(w->sets.ghost.begin(), w->sets.ghost.end(), (uint8_t)1) != w->sets.ghost.end() || w->xres.connected;
+    const bool in_place = w->dev_valid && !w->dirty && !sharded && !w->frozen_live && !w->ir_frozen_live && w->thaw_kinds == 0 && w->n_keyless == 0;
+    if (!in_place) {  // the per-robot calls, in the handler's order (every one of them validated above)
+        for (uint32_t i = 0; i < n; i++) {
+            const int32_t r = robots[i];
+            const float *xy = path_xy + 2 * (size_t)path_ptr[i];
+            const uint32_t np = path_ptr[i + 1] - path_ptr[i];
+            int rc = mgx_set_tracking_path(w, r, xy, np);
+            if (rc == MGX_OK) rc = mgx_reset_variables(w, r, means + 4 * (size_t)K * i, (uint32_t)K, first_last_sigma, inbetween_sigma);
+            if (rc == MGX_OK && (flags & MGX_GLOBAL_PATH_RESET_TRACKING)) rc = mgx_reset_tracking_factors(w, r);
+            if (rc == MGX_OK && (flags & MGX_GLOBAL_PATH_ROUTE)) rc = apply_global_route(w, r, xy, np, false);
+            if (rc == MGX_OK && (flags & MGX_GLOBAL_PATH_ACTIVATE)) rc = mgx_set_idle(w, r, 0);
+            if (rc != MGX_OK) return rc;
+        }
+        return MGX_OK;
+    }
+    // pending topology and flag differences reach the device in place: no connection of a listed robot exists only on the host
+    int rc = commit(w);
+    if (rc != MGX_OK) return rc;
+    flush_counts(w);
+    const size_t RL = (size_t)w->d.R_local, RT = (size_t)w->d.R_total;
+    for (uint32_t i = 0; i < n; i++) {
+        const float *xy = path_xy + 2 * (size_t)path_ptr[i];
+        w->robots[(size_t)robots[i]].path.assign(xy, xy + 2 * (size_t)(path_ptr[i + 1] - path_ptr[i]));
+    }
+    {  // the packed path arrays, as mgx_set_tracking_path rebuilds them
+        std::vector<int32_t> pptr(RL + 1, 0);
+        std::vector<float> pxy;
+        for (size_t dr = 0; dr < RL; dr++) {
+            const Robot &rb = w->robots[(size_t)w->robot_of[dr]];
+            pptr[dr] = (int32_t)(pxy.size() / 2);
+            pxy.insert(pxy.end(), rb.path.begin(), rb.path.end());
+            pptr[dr + 1] = (int32_t)(pxy.size() / 2);
+        }
+        if (pptr.size() > w->path_ptr.cap || pxy.size() > w->path_xy.cap)
+            HIP_TRY(hipStreamSynchronize(w->stream));  // (an array that has to grow is freed first: nothing may still read it)
+        HIP_TRY(w->path_ptr.upload(pptr, w->stream));
+        HIP_TRY(w->path_xy.upload(pxy, w->stream));
+        w->d.path_ptr = w->path_ptr.p;
+        w->d.path_xy = w->path_xy.p;
+        HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vectors die here
+    }
+    mgx_world::Mission &ms = w->mission;
+    const bool route = (flags & MGX_GLOBAL_PATH_ROUTE) != 0;
+    const bool route_on_device = route && ms.uploaded && !ms.dirty && ms.has.size() == w->robots.size();
+    if (route)
+        for (uint32_t i = 0; i < n; i++)
+            if ((rc = apply_global_route(w, robots[i], path_xy + 2 * (size_t)path_ptr[i], path_ptr[i + 1] - path_ptr[i], route_on_device)) != MGX_OK) return rc;
+    if (route_on_device) {  // the packed waypoints, as mission_upload packs them; what the device advances is not laid out again
+        const size_t R = w->robots.size();
+        std::vector<int32_t> ptr(R + 1, 0);
+        std::vector<double> xy;
+        for (size_t r = 0; r < R; r++) {
+            xy.insert(xy.end(), ms.wp[r].begin(), ms.wp[r].end());
+            ptr[r + 1] = (int32_t)(xy.size() / 2);
+        }
+        if (xy.size() > ms.wp_xy_d.cap) HIP_TRY(hipStreamSynchronize(w->stream));
+        HIP_TRY(ms.wp_ptr_d.upload(ptr, w->stream));
+        HIP_TRY(ms.wp_xy_d.upload(xy, w->stream));
+        ms.d.wp_ptr = ms.wp_ptr_d.p;
+        ms.d.wp_xy = ms.wp_xy_d.p;
+        HIP_TRY(hipStreamSynchronize(w->stream));
+    }
+    // ONE pinned block, f64 words: means [n][4][K] (component-major, as the blob keeps them) | device robots (int32)[n] | selected (u8)[R_total]
+    const size_t w_m = 4 * (size_t)K * n, w_r = (n + 1) / 2, w_s = (RT + 7) / 8;
+    void *hp = nullptr, *dp = nullptr;
+    int slot = 0;
+    HIP_TRY(w->stage.acquire((w_m + w_r + w_s) * sizeof(double), &hp, &slot));
+    double *hm = (double *)hp;
+    int32_t *hr = (int32_t *)(hm + w_m);
+    uint8_t *hs = (uint8_t *)(hm + w_m + w_r);
+    memset(hs, 0, w_s * sizeof(double));
+    for (uint32_t i = 0; i < n; i++) {
+        const double *src = means + 4 * (size_t)K * i;
+        double *dst = hm + 4 * (size_t)K * i;
+        for (int v = 0; v < K; v++)
+            for (int c = 0; c < 4; c++) dst[c * K + v] = src[4 * v + c];
+        hr[i] = w->dev_of[(size_t)robots[i]];
+        hs[(size_t)hr[i]] = 1;
+    }
+    HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
+    const double *dm = (const double *)dp;
+    const int n_edges = w->dev_in_ptr.empty() ? 0 : w->dev_in_ptr.back() * (K - 1);
+    if ((size_t)n_edges > w->ir_rec.n) return fail(MGX_ERR_STATE, "internal: %d edges on the device, %zu records", n_edges, w->ir_rec.n);
+    HIP_TRY(launch_global_paths(w->d, (int)n, (const int32_t *)(dm + w_m), dm, first_last_sigma, inbetween_sigma,
+                                (flags & MGX_GLOBAL_PATH_RESET_TRACKING) != 0, route_on_device ? ms.target_d.p : nullptr, n_edges, w->ir_rec.p,
+                                (const uint8_t *)(dm + w_m + w_r), w->stream));
+    HIP_TRY(w->stage.release(slot, w->stream));
+    if (flags & MGX_GLOBAL_PATH_ACTIVATE) {  // mission.state = Active (robot.rs:786): the flags travel with the next commit
+        for (uint32_t i = 0; i < n; i++) {
+            Robot &rb = w->robots[(size_t)robots[i]];
+            if (rb.idle) { rb.idle = 0; w->flags_dirty = true; }
+        }
+    }
+    return check_device_error(w);
+}
+// Route::update_waypoints (robot.rs:389-392, called at :778): the route becomes path[1:] — target_index = 1 skips the first point,
+// the robot's own position — widened to f64, and the next waypoint is its first.  Reach rules, Transform and time scale stay.
+// on_device: the device's mission arrays stay as they are (the caller uploads the packed waypoints and k_global_paths_robots
+// rewinds the target); otherwise what the device has advanced is fetched first and the missions are laid out again.
+static int apply_global_route(mgx_world *w, int32_t robot, const float *xy, uint32_t n_path, bool on_device) {
+    mgx_world::Mission &ms = w->mission;
+    if (!on_device && ms.uploaded && !ms.dirty) {
+        const int rc = mission_download(w);
+        if (rc != MGX_OK) return rc;
+    }
+    std::vector<double> &wp = ms.wp[(size_t)robot];
+    wp.resize(2 * (size_t)(n_path - 1));
+    for (size_t q = 0; q < wp.size(); q++) wp[q] = (double)xy[2 + q];
+    ms.target[(size_t)robot] = 0;
+    if (!on_device) ms.dirty = true;
+    return MGX_OK;
+}
+int mgx_layout_stats(mgx_world *w, uint64_t *n_layouts, uint64_t *n_pulls) {
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (n_layouts) *n_layouts = w->n_layouts;
+    if (n_pulls) *n_pulls = w->n_pulls;
+    return MGX_OK;
+}
+
 // Sharded worlds: a prior change applied on ANOTHER rank (to a robot that is a ghost here) still delivers a message to the
 // inter-robot factors local robots own on that variable (variable.rs:210-221): the counters are told, nothing else happens.
 int mgx_note_change_priors(mgx_world *w, uint32_t n, const int32_t *robots, const uint32_t *var_ix) {

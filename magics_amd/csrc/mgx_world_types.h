@@ -39,6 +39,9 @@ hipError_t launch_change_prior(const DevWorld &w, int n, const int32_t *robots, 
                                hipStream_t stream);
 hipError_t launch_update_priors(const DevWorld &w, int n, const int32_t *robots, const double *waypoints, const double *time_scale,
                                 const uint8_t *what, double max_speed, double delta_t, hipStream_t stream);
+hipError_t launch_global_paths(const DevWorld &w, int n, const int32_t *robots, const double *means, double first_last_sigma,
+                               double inbetween_sigma, bool reset_tracking, int32_t *mission_target, int n_edges, IrEdgeRec *recs,
+                               const uint8_t *selected, hipStream_t stream);
 hipError_t launch_halo_pack(const DevWorld &w, int n, const int32_t *robots, double *buf, hipStream_t stream);
 hipError_t launch_halo_unpack(const DevWorld &w, int n, const int32_t *ghosts, const double *buf, hipStream_t stream);
 hipError_t launch_copy_bytes(uint8_t *dst, const uint8_t *src, size_t n, hipStream_t stream);
@@ -600,6 +603,7 @@ struct mgx_world {
     bool conns_dirty = false;  // only inter-robot connections changed: edge tables are rebuilt in place
     bool flags_dirty = true;
     bool dev_valid = false;  // device arrays hold live state
+    uint64_t n_layouts = 0, n_pulls = 0;  // full rebuilds of the device arrays in commit(), pull()s that downloaded (mgx_layout_stats)
     bool frozen_live = false;     // the frozen-inbox arrays exist (a kind has been switched at run time)
     uint32_t thaw_kinds = 0;      // kinds some robot may still be thawing: k_thaw runs before sweeps with a factor phase
     DevBuf<double> frozen_buf;

@@ -19,14 +19,75 @@ import numpy as np
 F32 = np.float32
 
 
+def global_path_plan(path_xy, target_speed, planning_horizon, K):
+    """What the path-finding completion handler derives from a global path (robot.rs:652-667, 690-763), in f32 as there:
+    -> (waypoints [n][4] f32, means [K][4] f64).
+
+        waypoints[i] = (p_i, target_speed * normalize(p_i - p_{i+1}))    the last point paired with itself; NaN -> 0
+        dir          = waypoints[1] - waypoints[0]                       a Vec4: the velocity difference is part of it
+        next         = waypoints[0] + min(target_speed * planning_horizon, 0.9 * |dir|) * dir / |dir|
+        means[i]     = (lerp(start.xy, next.xy, i / K), target_speed * (dir / |dir|).xy)   widened to f64
+
+    glam is not part of the reference tree; the operations are assumed to be its scalar forms: Vec2::normalize multiplies by the
+    reciprocal length, v * (1 / sqrt(x*x + y*y)); Vec4::length is sqrt(((x*x + y*y) + z*z) + w*w) and Vec4::normalize
+    multiplies by its reciprocal; lerp(a, b, s) is a + (b - a) * s.  Axis-aligned paths do not depend on these choices; the
+    engine and its checker consume the same output either way."""
+    p = np.ascontiguousarray(path_xy, dtype=F32).reshape(-1, 2)
+    n = p.shape[0]
+    if n < 2:
+        raise ValueError("a global path has at least two points (TwoOrMore)")
+    speed = F32(target_speed)
+    wps = np.zeros((n, 4), dtype=F32)
+    with np.errstate(all="ignore"):
+        for i in range(n):
+            d = p[i] - p[min(i + 1, n - 1)]
+            d = d * (F32(1.0) / np.sqrt(F32(d[0] * d[0] + d[1] * d[1])))
+            if np.isnan(d).any():
+                d = np.zeros(2, dtype=F32)
+            wps[i] = (p[i, 0], p[i, 1], speed * d[0], speed * d[1])
+        start, dirv = wps[0], wps[1] - wps[0]
+        length = np.sqrt(F32(F32(F32(dirv[0] * dirv[0] + dirv[1] * dirv[1]) + dirv[2] * dirv[2]) + dirv[3] * dirv[3]))
+        dir_n = dirv * (F32(1.0) / length)
+        reach, most = F32(speed * F32(planning_horizon)), F32(length * F32(0.9))
+        s = reach if reach < most else most
+        nxt = start + s * dir_n
+        means = np.zeros((K, 4), dtype=np.float64)
+        for i in range(K):
+            r = F32(i) / F32(K)
+            pos = start[:2] + (nxt[:2] - start[:2]) * r
+            means[i] = (pos[0], pos[1], speed * dir_n[0], speed * dir_n[1])
+    return wps, means
+
+
+def _global_path(driver, robot, path_xy, planning_horizon, **flags):
+    """the completion handler on the driver's world: one call where the world offers it, the reference's sequence otherwise"""
+    w = driver.w
+    wps, means = global_path_plan(path_xy, driver.max_speed, planning_horizon, driver.K)
+    path = np.ascontiguousarray(wps[:, :2])
+    if hasattr(w, "apply_global_paths"):
+        w.apply_global_paths([robot], [path], means[None], activate=True, **flags)
+    else:
+        w.set_tracking_path(robot, path)
+        w.reset_variables(robot, means)
+        w.reset_tracking_factors(robot)
+        w.set_idle(robot, False)
+    return path
+
+
 class Driver:
     def __init__(self, world, n_robots, K, waypoints, radii, t0, steps, comms_radius, target_speed, hz=10.0,
-                 height=0.5, despawn_when_finished=True, failure_draws=None):
+                 height=0.5, despawn_when_finished=True, failure_draws=None, idle=()):
         """waypoints[r]: list of (x, y) still to visit (the first one is the next waypoint);
         radii[r]: robot radius (reached-when-intersects distance, formation.yaml `robot-radius`);
         t0[r]: the robot's T0 component (f32); failure_draws: callable(tick, n) -> bool array of
-        antennas that stay ON this tick (None: no comms failures)."""
+        antennas that stay ON this tick (None: no comms failures); idle: robots that start in MissionState::Idle —
+        they wait where they are (no waypoint advance, no prior update, no Transform move: robot.rs:995-1005, 2212, 2303)
+        until `global_path` hands them a route."""
         self.w, self.n, self.K = world, n_robots, K
+        self.idle = np.zeros(n_robots, dtype=bool)
+        for r in idle:
+            world.set_idle(int(r), True)
+            self.idle[int(r)] = True
         self.way = [list(map(tuple, wp)) for wp in waypoints]
         self.radii = np.asarray(radii, dtype=np.float64)
         self.dt32 = F32(1.0) / F32(hz)                                   # Time<Fixed>::delta_seconds
@@ -45,7 +106,7 @@ class Driver:
     # reached_waypoint (robot.rs:2080-2176): intermediate waypoints are checked against the horizon
     # variable, the last one against the current variable (formation.yaml of the Circle Experiment)
     def _reached_waypoint(self):
-        todo = [r for r in range(self.n) if self.alive[r] and self.way[r]]
+        todo = [r for r in range(self.n) if self.alive[r] and self.way[r] and not self.idle[r]]
         if not todo:
             return
         horizon, current = self.w.read_variable_means(self.K - 1), self.w.read_variable_means(0)
@@ -69,7 +130,7 @@ class Driver:
         live = np.nonzero(self.alive)[0]
         if self.failure_draws is not None and len(live):
             w.set_antennas(live.astype(np.int32), self.failure_draws(self.tick_no, len(live)))
-        moving = np.array([r for r in live if self.way[r]], dtype=np.int32)   # a next waypoint exists (robot.rs:2216-2228)
+        moving = np.array([r for r in live if self.way[r] and not self.idle[r]], dtype=np.int32)   # a next waypoint exists (robot.rs:2216-2228), not idle
         if len(moving):
             m0, m1 = w.read_variable_means(0), w.read_variable_means(1)
             change = self.time_scale[moving, None] * (m1[moving] - m0[moving])   # change_in_state (robot.rs:2314)
@@ -88,6 +149,13 @@ class Driver:
             w.iterate(self.steps)
         self.tick_no += 1
         return created, deleted
+
+    def global_path(self, robot, path_xy, planning_horizon):
+        """A global path has been found for `robot` (robot.rs:643-799): tracking path, variables and tracking factors reset,
+        the route becomes path[1:], the mission is Active."""
+        path = _global_path(self, robot, path_xy, planning_horizon)
+        self.way[robot] = [(float(x), float(y)) for x, y in path[1:]]
+        self.idle[robot] = False
 
     def run(self, max_ticks):
         """Ticks until every robot has finished (or max_ticks).  Returns the summary the reference's
@@ -111,8 +179,10 @@ class DeviceDriver:
     read-back at all.  Engine worlds only; `Driver` above on the CPU oracle is its checker (tests/test_gpu_driver.py)."""
 
     def __init__(self, world, n_robots, K, waypoints, radii, t0, steps, comms_radius, target_speed, hz=10.0,
-                 height=0.5, despawn_when_finished=True, failure_draws=None):
+                 height=0.5, despawn_when_finished=True, failure_draws=None, idle=()):
         self.w, self.n, self.K = world, n_robots, K
+        for r in idle:  # MissionState::Idle: the device missions wait (k_mission_reached, k_mission_prepare)
+            world.set_idle(int(r), True)
         self.dt32 = F32(1.0) / F32(hz)
         self.steps, self.comms_radius = steps, float(comms_radius)
         self.max_speed, self.delta_t = float(F32(target_speed)), float(self.dt32)
@@ -148,6 +218,12 @@ class DeviceDriver:
         self.tick_no += 1
         self._finished_dirty = True
         return created, deleted
+
+    def global_path(self, robot, path_xy, planning_horizon):
+        """A global path has been found for `robot` (robot.rs:643-799): one call, applied on the device — the mission takes the
+        route path[1:] and becomes Active."""
+        path = _global_path(self, robot, path_xy, planning_horizon, route=True)
+        self.n_way[robot] = len(path) - 1
 
     def state(self):
         """(translation [n, 3] f32, remaining waypoints per robot, completion tick per robot) — synchronises"""

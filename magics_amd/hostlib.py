@@ -25,6 +25,7 @@ SCHEDULE_HALF_BEGINNING_HALF_END = 4
 STEP_INTERNAL = 1
 STEP_EXTERNAL = 2
 NEIGHBOURS_AUTO, NEIGHBOURS_PAIRS, NEIGHBOURS_GRID = 0, 1, 2
+GLOBAL_PATH_RESET_TRACKING, GLOBAL_PATH_ROUTE, GLOBAL_PATH_ACTIVATE = 1, 2, 4  # mgx_apply_global_paths
 RESIDENT_NONE, RESIDENT_RAN, RESIDENT_DECLINED = 0, 1, 2
 # mgx_last_search: the kernel a neighbour search launched last
 SEARCH_NONE, SEARCH_TWO_PASS_PAIRS, SEARCH_TWO_PASS_GRID, SEARCH_ROWS_PAIRS_4, SEARCH_ROWS_PAIRS_2, SEARCH_ROWS_GRID_16, SEARCH_ROWS_GRID_32 = -1, 0, 1, 2, 3, 4, 5
@@ -182,6 +183,8 @@ SYMBOLS = {
     "mgx_reset_variables": (C.c_int, [_V, C.c_int32, c_double_p, C.c_uint32, C.c_double, C.c_double]),
     "mgx_reset_tracking_factors": (C.c_int, [_V, C.c_int32]),
     "mgx_set_tracking_path": (C.c_int, [_V, C.c_int32, C.c_void_p, C.c_uint32]),
+    "mgx_apply_global_paths": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_uint32]),
+    "mgx_layout_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mgx_mission_set": (C.c_int, [_V, C.c_int32, C.c_void_p]),
     "mgx_mission_tick": (C.c_int, [_V, C.c_float, C.c_uint32, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p, C.c_double, C.c_double,
                                    C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]),

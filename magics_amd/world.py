@@ -247,6 +247,32 @@ class World:
         path = np.ascontiguousarray(path, dtype=np.float32).reshape(-1, 2)
         self._chk(self._L.mgx_set_tracking_path(self._w, robot, path.ctypes.data, path.shape[0]))
 
+    def apply_global_paths(self, robots, paths, means, first_last_sigma=1e30, inbetween_sigma=float("inf"), reset_tracking=True,
+                           route=False, activate=False):
+        """The path-finding completion handler (robot.rs:643-799) for a batch of robots in one call (mgx_apply_global_paths):
+        set_tracking_path, reset_variables, reset_tracking_factors and — on request — the device mission's new route (`route`:
+        paths[i][1:]) and mission.state = Active (`activate`: idle off).  paths: one [n_i >= 2][2] polyline per robot; means:
+        [len(robots)][K][4].  Applied in place on the device when the world is laid out, unsharded and has never switched a
+        factor kind at run time; otherwise the per-robot calls run internally."""
+        robots = np.ascontiguousarray(robots, dtype=np.int32).reshape(-1)
+        if len(paths) != robots.size:
+            raise ValueError(f"{robots.size} robots, {len(paths)} paths")
+        paths = [np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 2) for p in paths]
+        ptr = np.zeros(robots.size + 1, dtype=np.uint32)
+        ptr[1:] = np.cumsum([p.shape[0] for p in paths])
+        xy = np.ascontiguousarray(np.concatenate(paths, axis=0)) if paths else np.zeros((1, 2), dtype=np.float32)
+        m = _f64(means).reshape(robots.size, -1, 4) if robots.size else np.zeros((1, 1, 4))
+        flags = ((hostlib.GLOBAL_PATH_RESET_TRACKING if reset_tracking else 0) | (hostlib.GLOBAL_PATH_ROUTE if route else 0)
+                 | (hostlib.GLOBAL_PATH_ACTIVATE if activate else 0))
+        self._chk(self._L.mgx_apply_global_paths(self._w, robots.size, robots.ctypes.data, ptr.ctypes.data, xy.ctypes.data, m.ctypes.data,
+                                                 float(first_last_sigma), float(inbetween_sigma), flags))
+
+    def layout_stats(self):
+        """-> (full rebuilds of the device arrays from the host mirror, downloads of the device state into it) — mgx_layout_stats"""
+        nl, npl = C.c_uint64(), C.c_uint64()
+        self._chk(self._L.mgx_layout_stats(self._w, C.byref(nl), C.byref(npl)))
+        return int(nl.value), int(npl.value)
+
     def change_priors(self, robots, var_ix, means):
         robots = np.ascontiguousarray(robots, dtype=np.int32)
         var_ix = np.ascontiguousarray(var_ix, dtype=np.uint32)

@@ -61,6 +61,25 @@ impl World {
     pub fn update_inter_robot_safety_distance_multiplier(&self, multiplier: f64) -> Result<(), MgxError> {
         check(unsafe { sys::mgx_set_safety_multiplier(self.raw, multiplier) })
     }
+    /// The path-finding completion handler (robot.rs:643-799) for a batch of robots in one call: `set_tracking_path`,
+    /// `reset_variables(means, first_last_sigma, inbetween_sigma)` and, per `flags` (1: `reset_tracking_factors`, 2: the device
+    /// mission takes the route `path[1..]`, 4: `mission.state = Active`).  `path_ptr[i] .. path_ptr[i + 1]` are robot i's points
+    /// in `path_xy`; `means` holds K vectors per robot.  Applied in place on the device where the world allows it (include/mgx.h).
+    pub fn apply_global_paths(&self, robots: &[i32], path_ptr: &[u32], path_xy: &[[f32; 2]], means: &[[f64; 4]], first_last_sigma: f64,
+                              inbetween_sigma: f64, flags: u32) -> Result<(), MgxError> {
+        assert_eq!(path_ptr.len(), robots.len() + 1);
+        assert_eq!(*path_ptr.last().unwrap() as usize, path_xy.len());
+        check(unsafe {
+            sys::mgx_apply_global_paths(self.raw, robots.len() as u32, robots.as_ptr(), path_ptr.as_ptr(), path_xy.as_ptr().cast(),
+                                        means.as_ptr().cast(), first_last_sigma, inbetween_sigma, flags)
+        })
+    }
+    /// (full rebuilds of the device arrays from the host mirror, downloads of the device state into it) since the world began
+    pub fn layout_stats(&self) -> Result<(u64, u64), MgxError> {
+        let (mut layouts, mut pulls) = (0u64, 0u64);
+        check(unsafe { sys::mgx_layout_stats(self.raw, &mut layouts, &mut pulls) })?;
+        Ok((layouts, pulls))
+    }
     /// `update_failed_comms` (robot.rs:1593-1601): the Bernoulli draws stay with the caller's PRNG
     pub fn set_antennas(&self, robots: &[i32], active: &[u8]) -> Result<(), MgxError> {
         assert_eq!(robots.len(), active.len());
