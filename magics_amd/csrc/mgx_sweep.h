@@ -31,6 +31,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+#include <utility>
+
 #include "gbp_math.h"
 #include "mgx_dev.h"
 
@@ -214,22 +217,39 @@ __device__ __forceinline__ void st16_agent(__amdgpu_buffer_rsrc_t rs, unsigned b
 
 // The same at SYSTEM scope (aux = sc0 | sc1): fine-grained memory that another GPU stores into or reads from over xGMI (the
 // ghost areas of sharded resident launches).
-__device__ __forceinline__ v4u32 ld16_system_raw(__amdgpu_buffer_rsrc_t rs, unsigned byte_off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, 0, 17);
-}
 __device__ __forceinline__ void st16_system(__amdgpu_buffer_rsrc_t rs, unsigned byte_off, double a, double b) {
     v4u32 v;
     v.x = (unsigned)__double2loint(a); v.y = (unsigned)__double2hiint(a);
     v.z = (unsigned)__double2loint(b); v.w = (unsigned)__double2hiint(b);
     __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)byte_off, 0, 17);
 }
-// four dwords as they are (exchange records: three payload dwords and the sequence word, mgx_dev.h); `sbase` is a wave-uniform
-// byte offset that rides in the instruction's scalar operand (the parity of the records: ONE descriptor serves both)
-__device__ __forceinline__ v4u32 ld16_agent_raw(__amdgpu_buffer_rsrc_t rs, unsigned byte_off, unsigned sbase) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, (int)sbase, 16);
+// Four dwords as they are (exchange records: three payload dwords and the sequence word, mgx_dev.h), loaded INTO the registers that
+// hold `r` already (the polling gather: a chunk that is asked for again arrives where its last copy sits, for the lanes that ask,
+// and no register is copied to carry the others' across).  `sbase` is a wave-uniform byte offset that rides in the instruction's
+// scalar operand (the parity of the records: ONE descriptor serves both); IMM a constant one in the instruction's offset field;
+// SYS: system scope instead of agent scope.  The compiler does not see these loads: nothing of `r` may be read, copied or written
+// before ld16_landed has been passed every register they were aimed at.
+template <int IMM, bool SYS>
+__device__ __forceinline__ void ld16_into(v4u32 &r, __amdgpu_buffer_rsrc_t rs, unsigned byte_off, unsigned sbase) {
+    static_assert(IMM >= 0 && IMM < 4096, "the instruction's offset field has 12 bits");
+    if constexpr (SYS) asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4 sc0 sc1" : "+v"(r) : "v"(byte_off), "s"(rs), "s"(sbase), "n"(IMM) : "memory");
+    else asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:%4 sc1" : "+v"(r) : "v"(byte_off), "s"(rs), "s"(sbase), "n"(IMM) : "memory");
 }
-__device__ __forceinline__ v4u32 ld16_system_raw(__amdgpu_buffer_rsrc_t rs, unsigned byte_off, unsigned sbase) {
-    return __builtin_amdgcn_raw_buffer_load_b128(rs, (int)byte_off, (int)sbase, 17);
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a constant in the body
+template <int... I, typename F>
+__device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F &&f) { (f(std::integral_constant<int, I>{}), ...); }
+template <int N>
+__device__ __forceinline__ void ld16_unset(v4u32 (&r)[N]) {  // "holds some value": no instruction
+#pragma unroll
+    for (int ch = 0; ch < N; ch++) asm volatile("" : "=v"(r[ch]));  // (volatile: one register quad each, not one for all)
+}
+template <int N>
+__device__ __forceinline__ void ld16_landed(v4u32 (&r)[N]) {
+    static_assert(N == 15 || N == 16, "one operand per chunk of an exchange record");
+#define MGX_LANDED_15 "+v"(r[0]), "+v"(r[1]), "+v"(r[2]), "+v"(r[3]), "+v"(r[4]), "+v"(r[5]), "+v"(r[6]), "+v"(r[7]), "+v"(r[8]), "+v"(r[9]), "+v"(r[10]), "+v"(r[11]), "+v"(r[12]), "+v"(r[13]), "+v"(r[14])
+    if constexpr (N == 15) asm volatile("s_waitcnt vmcnt(0)" : MGX_LANDED_15::"memory");
+    else asm volatile("s_waitcnt vmcnt(0)" : MGX_LANDED_15, "+v"(r[N - 1])::"memory");
+#undef MGX_LANDED_15
 }
 // (stores: the wave-uniform part is ADDED to the per-lane offset, never passed in the scalar operand.  A buffer store of more than
 // 8 bytes reads its data registers some cycles after issue; the compiler keeps the next VALU write of those registers away from
@@ -871,33 +891,59 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     // delivery count to `deliveries`.  off_mine: byte offset of chunk 0 of the lane's record (top bit: in the ghost area); lanes
     // without an edge ask for nothing.  A wait that outlasts the bound raises the world's abort word like any other wait of the
     // launch (reported, never a hang).
-    auto gather_records = [&](auto fetch, bool mine, unsigned off_mine, uint32_t seq, double (&out)[SNAP_W], uint32_t &deliveries) __attribute__((always_inline)) {
+    auto gather_records = [&](int buf, bool mine, unsigned off_mine, uint32_t seq, double (&out)[SNAP_W], uint32_t &deliveries) __attribute__((always_inline)) {
+        // The chunks' registers are loaded IN PLACE (ld16_into), by the first request and by every later one, under the mask of the
+        // lanes that ask: nothing of R is copied to carry it round the spin loop, and nothing is written for lanes that are not
+        // `mine` — their words never count as missing, their record is not read.  (The empty statement only tells the compiler
+        // that the registers hold SOME value.)  One address register serves all chunks wherever the last chunk's offset fits the
+        // instruction's field (horizons up to 17); longer and run-time horizons add the chunk's offset to it.
         v4u32 R[XREC_CHUNKS];
+        constexpr auto CHUNKS = std::make_integer_sequence<int, XREC_CHUNKS>{};
+        ld16_unset(R);
+        constexpr bool IMM_OFF = KT > 0 && (XREC_CHUNKS - 1) * 16 * KT < 4096;
         const unsigned cstride = 16u * (unsigned)K;
-#pragma unroll
-        for (int ch = 0; ch < XREC_CHUNKS; ch++) R[ch] = v4u32{0u, 0u, 0u, 0u};
+        const unsigned off = off_mine & ~GHOST_BIT, sb_x = buf ? xrec_bytes : 0u, sb_gx = buf ? gx_bytes : 0u;
         // (ghost records crossed the fabric: their sequence word carries a mix of the payload it arrived with, mgx_dev.h — undone
         // ONCE, where a chunk is fetched, and only in waves that gather a ghost record at all: fifteen mixes per look of every lane
         // of every robot were 0.7 us of a sharded world's iteration)
         const bool remote = SHARD && (off_mine & GHOST_BIT) != 0u;
         const bool any_remote = SHARD && __ballot(remote) != 0ull;
-        if (mine) {
+        // ask for the chunks whose word is not `seq` (first: for all of them) and say which; the answer is there behind ld16_landed
+        auto request = [&](auto first) __attribute__((always_inline)) {
+            unsigned asked = 0u;  // (of use in sharded launches only)
+            static_for(CHUNKS, [&](auto ch) __attribute__((always_inline)) {
+                constexpr int imm = IMM_OFF ? ch * 16 * KT : 0;
+                const unsigned voff = IMM_OFF ? off : off + (unsigned)ch * cstride;
+                if (first || R[ch].w != seq) {
+                    asked |= 1u << ch;
+                    if (SHARD && remote) ld16_into<imm, true>(R[ch], rs_gx, voff, sb_gx);
+                    else ld16_into<imm, false>(R[ch], rs_x, voff, sb_x);
+                }
+            });
+            return asked;
+        };
+        // every lane of the wave passes here behind a request: the loads have landed, the chunks asked for may be read — and a ghost's
+        // word is unmixed (behind ALL the fetches: a mix between two of them would wait for the first before asking for the second)
+        auto landed = [&](unsigned asked) __attribute__((always_inline)) {
+            ld16_landed(R);
+            if constexpr (SHARD) {
+                if (any_remote) {
 #pragma unroll
-            for (int ch = 0; ch < XREC_CHUNKS; ch++) R[ch] = fetch(off_mine + (unsigned)ch * cstride);
-        }
-        if constexpr (SHARD) {  // (behind ALL the fetches: a mix between two of them would wait for the first before asking for the second)
-            if (any_remote) {
-#pragma unroll
-                for (int ch = 0; ch < XREC_CHUNKS; ch++) R[ch].w ^= remote ? xrec_mix(R[ch].x, R[ch].y, R[ch].z) : 0u;
+                    for (int ch = 0; ch < XREC_CHUNKS; ch++) R[ch].w ^= (remote && ((asked >> ch) & 1u)) ? xrec_mix(R[ch].x, R[ch].y, R[ch].z) : 0u;
+                }
             }
+        };
+        {
+            unsigned asked = 0u;
+            if (mine) asked = request(std::true_type{});
+            landed(asked);
         }
-        auto word_of = [&](const v4u32 &c) __attribute__((always_inline)) { return c.w; };
         long long t0 = 0;
         for (unsigned spins = 0;; spins++) {
             bool missing = false;
 #pragma unroll
-            for (int ch = 0; ch < XREC_CHUNKS; ch++) missing = missing || word_of(R[ch]) != seq;
-            missing = missing && mine;
+            for (int ch = 0; ch < XREC_CHUNKS; ch++) missing = missing || R[ch].w != seq;
+            missing = mine && missing;
             if (__ballot(missing) == 0ull) break;
             // (a waiting workgroup's re-requests load the memory pipeline of its CU, which the workgroups beside it — the ones it
             // may be waiting FOR — gather through: 2048 clocks between looks measured 2.5 % faster than 128, 8192 slower)
@@ -916,19 +962,9 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                 }
                 if (__ballot(stop) != 0ull) break;  // (the launch ends with wrong beliefs; the host reports it)
             }
-            if (missing) {
-                unsigned again = 0u;  // the chunks asked for again
-#pragma unroll
-                for (int ch = 0; ch < XREC_CHUNKS; ch++)
-                    if (word_of(R[ch]) != seq) { again |= 1u << ch; R[ch] = fetch(off_mine + (unsigned)ch * cstride); }
-                if constexpr (SHARD) {
-                    if (remote) {
-#pragma unroll
-                        for (int ch = 0; ch < XREC_CHUNKS; ch++)
-                            if ((again >> ch) & 1u) R[ch].w ^= xrec_mix(R[ch].x, R[ch].y, R[ch].z);
-                    }
-                }
-            }
+            unsigned asked = 0u;  // the chunks asked for again
+            if (missing) asked = request(std::false_type{});
+            landed(asked);
         }
         auto D = [&](int n) __attribute__((always_inline)) { return R[n / 3][n % 3]; };  // payload dword n
 #pragma unroll
@@ -969,12 +1005,6 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
         t_edges0 = __builtin_readcyclecounter();
 #endif
         if (radio && ir_on) {
-            auto fetch_xrec = [&](unsigned off) __attribute__((always_inline)) {
-                if constexpr (SHARD) {
-                    if (off & GHOST_BIT) return ld16_system_raw(rs_gx, off & ~GHOST_BIT, buf ? gx_bytes : 0u);
-                }
-                return ld16_agent_raw(rs_x, off, buf ? xrec_bytes : 0u);
-            };
             const uint32_t want_seq = xrec_seq(plan.flag_base + (unsigned long long)kg);
             for (int j0 = 0; j0 < ne; j0 += NT) {  // rounds of the whole workgroup: every lane takes part in the gather
                 const int q = j0 + tid;                                        // edge lane
@@ -1002,7 +1032,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                         const int sv = mine ? (ghost_src ? er_src_var - VL : er_src_var) : 0, si = sv % K;  // variable si of robot sv / K
                         const unsigned off_mine = ((unsigned)(sv - si) * (unsigned)XREC_BYTES + 16u * (unsigned)si) | (ghost_src ? GHOST_BIT : 0u);
                         if (j0 == 0) TLSTAMP(k - 1, 2);
-                        gather_records(fetch_xrec, mine, off_mine, want_seq, grec, grec_deliveries);
+                        gather_records(buf, mine, off_mine, want_seq, grec, grec_deliveries);
                         if (j0 == 0) TLSTAMP(k - 1, 3);
                         DELAY_AT(4, j0 == 0);
                         DELAY_AT(6, j0 == 0 && role == ROLE_UV);
