@@ -353,6 +353,24 @@ int mgx_apply_global_paths(mgx_world *w, uint32_t n, const int32_t *robots, cons
 /* Which path ran (read-only, no side effect on launches in flight): n_layouts counts the full rebuilds of the device arrays
  * from the host mirror, n_pulls the downloads of the device state into it, since the world was created.  Either may be null. */
 int mgx_layout_stats(mgx_world *w, uint64_t *n_layouts, uint64_t *n_pulls);
+/* Head-room for robots that join a running world (the reference's spawner, spawner.rs:415-646, builds a RobotBundle —
+ * robot.rs:1134-1356 — for as long as a formation repeats).  The world expects to hold up to `robots` robots, removed ones
+ * included: the next full layout sizes every per-robot device array, and strides the tables keyed by (robot, factor), for that
+ * many, and from then on the robots mgx_robot_add brings are APPENDED on the device by the next call that needs it — one staged
+ * block and one kernel for all robots added since, nothing pulled, nothing laid out again (mgx_layout_stats does not move, the
+ * resident launches' capacity and the neighbour search's buffers stay).  Callable at any time: before the first layout the
+ * wish is only recorded; on a laid-out world it costs ONE full layout and one pull, by the next launch.  A value at or below
+ * the current robot count, or below an earlier wish, keeps the head-room already there; 0 on a world that never reserved
+ * is a no-op.  A world that never calls this keeps the layout, the strides and the add path it always had.
+ * The append is taken when nothing but additions is pending, the world is unsharded and the new robots are no ghosts, no factor
+ * kind was ever switched at run time (mgx_set_enabled) and no factor lacks inbox keys, and the robots and their paths fit
+ * the head-room; anything else — ghosts and sharded worlds accept the call and never append — is laid out in full as before,
+ * with the same results.  Robots beyond the head-room: one full layout sized max(robots asked for, 2 x robots there). */
+int mgx_world_reserve(mgx_world *w, uint32_t robots);
+/* Which path the additions took (read-only, as mgx_layout_stats): `appends` counts the commits that appended in place,
+ * `robots_appended` the robots they brought onto the device, `fallbacks` the commits of a reserved, already laid-out world
+ * that had new robots and ran the full layout all the same.  Any may be null; a null world: -1, nothing written. */
+int mgx_append_stats(mgx_world *w, uint64_t *appends, uint64_t *robots_appended, uint64_t *fallbacks);
 
 /* The driver's per-tick prior updates, batched over robots in one launch:
  *   what[i] & 1: update_prior_of_horizon_state (robot.rs:2182-2283) — the last variable of robots[i]

@@ -246,6 +246,14 @@ public:
         check(mgx_layout_stats(w_, &layouts, &pulls));
         return {layouts, pulls};
     }
+    /// head-room for robots that join while the world runs: they are appended on the device instead of laid out again — mgx_world_reserve
+    void reserve(uint32_t robots) { check(mgx_world_reserve(w_, robots)); }
+    /// (commits that appended in place, robots they brought onto the device, commits that fell back to the full layout) — mgx_append_stats
+    std::array<uint64_t, 3> append_stats() {
+        uint64_t appends = 0, robots = 0, fallbacks = 0;
+        check(mgx_append_stats(w_, &appends, &robots, &fallbacks));
+        return {appends, robots, fallbacks};
+    }
     std::vector<Vector4> read_variable_means(uint32_t variable_index) {
         uint32_t n = 0;
         check(mgx_num_robots(w_, &n, nullptr));

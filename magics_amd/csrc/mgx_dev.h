@@ -72,6 +72,45 @@ struct RetopoBlock {
     const uint4 *data;        // per changed robot: n_in slot records (IrSlotRec, old_slot: position in the robot's OLD list, -1 = created now), then its peer row (int32, padded to 16 bytes)
 };
 
+// What the host sends for robots that join a laid-out world with head-room (mgx_world_reserve; k_append_robots): ONE pinned
+// block, read over the host link — one record of AppendLayout::words() f64 words per new robot, then the new robots' path points
+// (f32 pairs).  A record is what commit() packs for the robot, item-major as the host mirror keeps it: a 32-byte header, the
+// blob row, the K snapshot records, the K-1 dynamic potentials [f][16], then last tracking values, delivery counts, tracking
+// records and last tracking positions ([x .. | y ..]).  Every part starts on a 16-byte boundary (BS is even).
+struct AppendHeader {
+    int32_t path_at;    // first float of the robot's path behind the records
+    int32_t n_path;     // its points
+    int32_t path_base;  // first point of its span in the device's packed path array
+    int32_t iter_factor;
+    double radius;
+    uint8_t antenna, idle, pad[6];
+};
+struct AppendLayout {
+    int K, BS;
+    __host__ __device__ static constexpr int even(int n) { return (n + 1) & ~1; }
+    __host__ __device__ int blob() const { return (int)(sizeof(AppendHeader) / sizeof(double)); }
+    __host__ __device__ int snap() const { return blob() + BS; }
+    __host__ __device__ int dyn() const { return snap() + 24 * K; }
+    __host__ __device__ int trk_val() const { return dyn() + 16 * (K - 1); }
+    __host__ __device__ int epoch() const { return trk_val() + even(K - 2); }       // u32 [K]
+    __host__ __device__ int trk_rec() const { return epoch() + even((K + 1) / 2); }  // i32 [K-2]
+    __host__ __device__ int trk_pos() const { return trk_rec() + even((K - 1) / 2); }  // f32 [2][K-2]
+    __host__ __device__ int words() const { return trk_pos() + even(K - 2); }
+};
+// the arrays k_append_robots writes that DevWorld names read-only or not at all, and the room the host found in them
+struct AppendTargets {
+    const double *block;  // the staged block (device address of the pinned memory)
+    int n;                // robots in it; robot a becomes device robot R_local + a
+    int room;             // robots the per-robot arrays hold (a record beyond it is not written)
+    int path_room;        // points the packed path array holds
+    int in_end;           // slots of the layout on the device: a new robot's (empty) range starts and ends there
+    int32_t *path_ptr;
+    float *path_xy;
+    double *radius;
+    uint8_t *antenna, *idle;
+    int32_t *in_ptr, *in_mid, *var_ptr, *var_mid;
+};
+
 // EXCHANGE RECORDS of resident schedule launches — the hand-off between neighbouring robots' workgroups (and, on sharded worlds,
 // between GPUs).  What an inter-robot factor F_AB reads of its owner A is the message A's variable sends it: (eta, lam, mu) — of
 // which the factor's arithmetic touches eta, lam and the two position means (interrobot.rs:149-159: the Jacobian has no velocity

@@ -682,6 +682,72 @@ __global__ void k_var_tables(int R, int K, const int32_t *__restrict__ in_ptr, c
     var_ptr[t] = p;
     var_mid[t] = (i == 0) ? p : p + in_mid[r];
 }
+// Robots that join a laid-out world with head-room (mgx_world_reserve): one workgroup per new robot reads its record of the
+// staged block (AppendLayout, mgx_dev.h) over the host link and scatters it behind the robots the device holds — the blob row,
+// its records in BOTH snapshot buffers and delivery-count arrays (w.cur may be either), its columns of the strided tables at
+// the strides of the layout there (ND, NT: the head-room's, not the robot count's), its path span and the tail of path_ptr,
+// iteration count, radius, flag bytes, and the empty tails of the slot ranges and the per-variable tables (no incoming
+// connection yet: a topology pass behind this kernel on the same stream brings its edges).  Bounded copies: no wait, no atomic.
+constexpr int APPEND_THREADS = 256;
+__global__ void __launch_bounds__(APPEND_THREADS) k_append_robots(DevWorld w, AppendLayout L, AppendTargets t) {
+    const int a = blockIdx.x, tid = threadIdx.x, K = w.K, r = w.R_local + a;
+    if (a >= t.n || r >= t.room) return;
+    const double *rec = t.block + (size_t)a * (size_t)L.words();
+    const AppendHeader h = *reinterpret_cast<const AppendHeader *>(rec);
+    // 16-byte copies: the blob row and the snapshot records (both even numbers of words at even offsets on both sides)
+    {
+        const double2 *src = reinterpret_cast<const double2 *>(rec + L.blob());
+        double2 *dst = reinterpret_cast<double2 *>(w.blob + (size_t)r * (size_t)w.BS);
+        for (int q = tid; q < (w.BS >> 1); q += APPEND_THREADS) dst[q] = src[q];
+    }
+    {
+        const double2 *src = reinterpret_cast<const double2 *>(rec + L.snap());
+        double2 *d0 = reinterpret_cast<double2 *>(w.snap[0] + (size_t)r * (size_t)K * SNAP_W);
+        double2 *d1 = reinterpret_cast<double2 *>(w.snap[1] + (size_t)r * (size_t)K * SNAP_W);
+        for (int q = tid; q < (SNAP_W * K) >> 1; q += APPEND_THREADS) {
+            const double2 v = src[q];
+            d0[q] = v;
+            d1[q] = v;
+        }
+    }
+    const uint32_t *ep = reinterpret_cast<const uint32_t *>(rec + L.epoch());
+    for (int i = tid; i < K; i += APPEND_THREADS) {
+        const uint32_t e = ep[i];
+        w.snap_epoch[0][(size_t)r * K + i] = e;
+        w.snap_epoch[1][(size_t)r * K + i] = e;
+        // variable i of a robot nobody points at yet: an empty range at the end of the edge arrays
+        if (i > 0) t.var_ptr[(size_t)r * K + i] = (K - 1) * t.in_end;
+        t.var_mid[(size_t)r * K + i] = (K - 1) * t.in_end;
+    }
+    // [f][16] -> [16][ND]
+    for (int q = tid; q < 16 * (K - 1); q += APPEND_THREADS) {
+        const int f = q >> 4, c = q & 15;
+        w.dyn_m[(size_t)c * (size_t)w.ND + (size_t)r * (K - 1) + f] = rec[L.dyn() + q];
+    }
+    const int32_t *trc = reinterpret_cast<const int32_t *>(rec + L.trk_rec());
+    const float *tlp = reinterpret_cast<const float *>(rec + L.trk_pos());
+    for (int j = tid; j < K - 2; j += APPEND_THREADS) {
+        const size_t item = (size_t)r * (K - 2) + j;
+        w.trk_record[item] = trc[j];
+        w.trk_last_pos[item] = tlp[j];
+        w.trk_last_pos[(size_t)w.NT + item] = tlp[(K - 2) + j];
+        w.trk_last_val[item] = rec[L.trk_val() + j];
+    }
+    if (h.path_base >= 0 && h.path_base + h.n_path <= t.path_room) {
+        const float *src = reinterpret_cast<const float *>(t.block + (size_t)t.n * (size_t)L.words()) + h.path_at;
+        for (int q = tid; q < 2 * h.n_path; q += APPEND_THREADS) t.path_xy[2 * (size_t)h.path_base + q] = src[q];
+    }
+    if (tid == 0) {
+        t.path_ptr[r + 1] = h.path_base + h.n_path;  // (entry r is the predecessor's end)
+        w.iter_factor[r] = h.iter_factor;
+        t.radius[r] = h.radius;
+        t.antenna[r] = h.antenna;
+        t.idle[r] = h.idle;
+        t.in_ptr[r + 1] = t.in_end;
+        t.in_mid[r] = 0;
+        t.var_ptr[(size_t)(r + 1) * K] = (K - 1) * t.in_end;  // (variable 0 of the successor, or the table's closing entry)
+    }
+}
 // gate byte of every edge: its OWNER is on air (antenna on, not idle)
 __global__ void k_edge_gates(int n, const IrEdgeRec *__restrict__ recs, const uint8_t *__restrict__ antenna,
                              const uint8_t *__restrict__ idle, uint8_t *__restrict__ gate) {
@@ -866,6 +932,11 @@ hipError_t launch_retopo_robots(const DevWorld &w, const RetopoBlock &b, const i
     if (w.R_local <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_retopo_robots, dim3((unsigned)w.R_local), dim3(RETOPO_THREADS), 0, stream, w, b, in_old, slots_old, peers_old, in_dst, slots_new, peers_dst,
                        var_ptr, var_mid, stride_new, recs, fv_eta, fv_lam, bmu, gate);
+    return hipGetLastError();
+}
+hipError_t launch_append_robots(const DevWorld &w, const AppendLayout &l, const AppendTargets &t, hipStream_t stream) {
+    if (t.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_append_robots, dim3((unsigned)t.n), dim3(APPEND_THREADS), 0, stream, w, l, t);
     return hipGetLastError();
 }
 hipError_t launch_var_tables(int R, int K, const int32_t *in_ptr, const int32_t *in_mid, int32_t *var_ptr, int32_t *var_mid,

@@ -90,7 +90,7 @@ int mgx_world_set_sdf(mgx_world *w, const uint8_t *rgb, uint32_t width, uint32_t
     w->sdf_red.resize((size_t)width * height);
     for (size_t i = 0; i < w->sdf_red.size(); i++) w->sdf_red[i] = rgb[3 * i];  // pixel[0], obstacle.rs:178
     w->sdf_w = width; w->sdf_h = height; w->world_w = world_w; w->world_h = world_h;
-    w->dirty = true;
+    w->dirty = w->relayout = true;
     return MGX_OK;
 }
 
@@ -103,7 +103,7 @@ int mgx_world_set_environment(mgx_world *w, const mgx_env_desc *env) {
     w->sdf_w = W; w->sdf_h = H;
     w->world_w = (double)env->tile_size * (double)env->n_cols;  // robot.rs:1259-1264
     w->world_h = (double)env->tile_size * (double)env->n_rows;
-    w->dirty = true;
+    w->dirty = w->relayout = true;
     return MGX_OK;
 }
 
@@ -171,7 +171,7 @@ int mgx_robot_add(mgx_world *w, const mgx_robot_desc *d, int32_t *robot_id) {
     w->robots.push_back(std::move(rb));
     w->sets.ensure(w->robots.size());
     w->K = K;
-    w->dirty = true;
+    w->dirty = true;  // (robots were added — a reason of its own: a world with head-room takes them on the device, commit())
     if (robot_id) *robot_id = (int32_t)w->robots.size() - 1;
     return MGX_OK;
 }
@@ -438,7 +438,8 @@ int mgx_set_safety_multiplier(mgx_world *w, double multiplier) {
     // (a resident launch the census declined is run again first: its schedule was issued under the old distance)
     MGX_CONFIRM(w);
     w->p.safety_multiplier = multiplier;
-    if (w->dirty || !w->dev_valid || w->dev_in_ptr.empty()) return MGX_OK;
+    // (robots that only wait to be appended have no records on the device yet: theirs are formed from w->p later)
+    if (w->relayout || !w->dev_valid || w->dev_in_ptr.empty()) return MGX_OK;
     const size_t n_slots = (size_t)w->dev_in_ptr.back(), n_edges = n_slots * (size_t)(w->K - 1);
     if (n_edges == 0) return MGX_OK;
     if (n_edges > w->ir_rec.n || (size_t)w->d.R_total > w->radius_dev.n)

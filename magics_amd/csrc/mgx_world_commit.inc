@@ -14,8 +14,8 @@ static int upload_flags(mgx_world *w) {
         an[dr] = w->robots[(size_t)w->robot_of[dr]].antenna;
         id[dr] = w->robots[(size_t)w->robot_of[dr]].idle;
     }
-    HIP_TRY(w->antenna.reserve(R));
-    HIP_TRY(w->idle.reserve(R));
+    HIP_TRY(w->antenna.reserve(std::max(R, (size_t)w->R_cap)));  // (a reserved world's head-room: k_append_robots writes the bytes of the robots that join)
+    HIP_TRY(w->idle.reserve(std::max(R, (size_t)w->R_cap)));
     HIP_TRY(w->ir_gate.reserve(NE));
     void *dp = nullptr;
     HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
@@ -302,7 +302,7 @@ static int retopo(mgx_world *w) {
     }
     hipStream_t s = w->stream;
     HIP_TRY(w->slot_recs_b.reserve(n_slots + 1));  // (slot_recs holds the layout being replaced: left alone)
-    HIP_TRY(w->in_ptr_dev_b.reserve(R + 1));
+    HIP_TRY(w->in_ptr_dev_b.reserve(std::max(R, (size_t)w->R_cap) + 1));  // (with the head-room of a reserved world: the next "old" ranges, which an append extends)
     HIP_TRY(w->ir_rec_b.reserve(NIs));
     HIP_TRY(w->ir_fv_eta_b.reserve(4 * NIs));
     HIP_TRY(w->ir_fv_lam_b.reserve(16 * NIs));
@@ -347,12 +347,162 @@ static int retopo(mgx_world *w) {
 }
 
 
+// What commit() packs of ONE robot, for both of its paths: the full layout (the world's host arrays: strided tables, stride
+// dyn_cs between components) and the append (the robot's record of the staged block: item-major, dyn_is = 16).  Paths, radius,
+// iteration count and flags are scalars and spans the callers place themselves.
+struct RobotSink {
+    double *blob, *snap;  // [BS], [K][24]
+    uint32_t *epoch;      // [K]
+    double *dyn;          // component c of factor f at dyn[c * dyn_cs + f * dyn_is]
+    size_t dyn_cs, dyn_is;
+    int32_t *trk_rec;     // [K-2] ...
+    float *trk_x, *trk_y;
+    double *trk_val;
+};
+static void pack_robot(const Robot &rb, const RobotSink &o) {
+    const int K = rb.K;
+    blob_pack(rb, o.blob);
+    memcpy(o.snap, rb.snap.data(), 24 * (size_t)K * sizeof(double));
+    for (int i = 0; i < K; i++) o.epoch[i] = rb.epoch[i];
+    if (rb.ghost) return;
+    for (int f = 0; f < K - 1; f++)
+        for (int c = 0; c < 16; c++) o.dyn[(size_t)c * o.dyn_cs + (size_t)f * o.dyn_is] = rb.dyn_m[16 * f + c];
+    for (int j = 0; j < K - 2; j++) {
+        o.trk_rec[j] = rb.trk_record[j];
+        o.trk_x[j] = rb.trk_last_pos[2 * j];
+        o.trk_y[j] = rb.trk_last_pos[2 * j + 1];
+        o.trk_val[j] = rb.trk_last_val[j];
+    }
+}
+constexpr size_t APPEND_PATH_POINTS = 32;  // (path slack per free place of a reserved world, in points, when no robot has a longer path)
+
+// ---- robots that join a laid-out world with head-room: appended on the device ------------------------------------------------
+static size_t device_path_points(const mgx_world *w) {  // what the packed path array holds (Robot::path is the truth of paths)
+    size_t n = 0;
+    for (const int id : w->robot_of) n += w->robots[(size_t)id].path.size() / 2;
+    return n;
+}
+// the packed path array of a reserved world keeps its slack when the paths are packed again (mgx_set_tracking_path, mgx_apply_global_paths)
+static size_t path_room_for(const mgx_world *w, size_t floats, size_t longest) {
+    const size_t free_places = (size_t)std::max(w->R_cap - w->d.R_local, 0);
+    return floats + free_places * std::max<size_t>(longest, 2 * APPEND_PATH_POINTS);
+}
+// The conditions of mgx_apply_global_paths' in-place form, and room: in the per-robot arrays (R_cap, and — an array another pass
+// has re-allocated since — every allocation itself) and in the packed paths.  Anything else is laid out in full.
+static bool append_fits(const mgx_world *w) {
+#ifdef MGX_STAMPS
+    return false;  // (the diagnostic words are sized by the robot count)
+#endif
+    const DevWorld &d = w->d;
+    const size_t R0 = w->robot_of.size(), R1 = w->robots.size(), K = (size_t)w->K;
+    if (!w->reserve_want || R1 > (size_t)w->R_cap || (size_t)d.R_local != R0 || d.R_total != d.R_local) return false;
+    if (w->xres.connected || w->direct.connected || w->rccl.connected) return false;
+    if (w->frozen_live || w->ir_frozen_live || w->thaw_kinds != 0 || w->n_keyless != 0) return false;
+    size_t pts = device_path_points(w);
+    for (size_t id = R0; id < R1; id++) {
+        const Robot &rb = w->robots[id];
+        if (rb.ghost || rb.K != w->K) return false;
+        pts += rb.path.size() / 2;
+    }
+    const size_t K2 = K - 2;
+    return 2 * pts <= w->path_xy.cap && R1 + 1 <= w->path_ptr.cap && (size_t)d.BS * R1 <= w->blob.cap && 24 * K * R1 <= std::min(w->snap0.cap, w->snap1.cap) &&
+           K * R1 <= std::min(w->epoch0.cap, w->epoch1.cap) && (K - 1) * R1 <= (size_t)d.ND && 16 * (size_t)d.ND <= w->dyn_m.cap &&
+           std::max<size_t>(K2, 1) * R1 <= (size_t)d.NT && (size_t)d.NT <= std::min(w->trk_record.cap, w->trk_last_val.cap) && 2 * (size_t)d.NT <= w->trk_last_pos.cap &&
+           R1 <= w->iter_factor.cap && R1 <= w->radius_dev.cap && R1 <= std::min(w->antenna.cap, w->idle.cap) && R1 + 1 <= w->in_ptr_dev.cap &&
+           R1 <= w->in_mid_dev.cap && K * R1 + 1 <= w->ir_var_ptr.cap && K * R1 <= w->ir_var_mid.cap && w->dev_in_ptr.size() == R0 + 1;
+}
+// All robots added since the last commit, together: one staged block (one record each, as commit() packs them: pack_robot),
+// one dispatch (k_append_robots).  Unsharded, so the device order is the id order and the new robots' device indices follow
+// the old ones'.  Nothing is pulled: the host mirror of the robots already there stays as stale as it is between two pulls.
+static int append_robots(mgx_world *w) {
+    StageTimer tm("append");
+    DevWorld &d = w->d;
+    const int K = w->K, R0 = d.R_local, R1 = (int)w->robots.size(), n = R1 - R0;
+    const AppendLayout L{K, d.BS};
+    const size_t RW = (size_t)L.words();
+    size_t path_floats = 0;
+    for (int id = R0; id < R1; id++) path_floats += w->robots[(size_t)id].path.size();
+    void *hp = nullptr, *dp = nullptr;
+    int slot = 0;
+    HIP_TRY(w->stage.acquire(RW * sizeof(double) * (size_t)n + path_floats * sizeof(float), &hp, &slot));
+    HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
+    double *rec0 = (double *)hp;
+    float *paths = (float *)(rec0 + RW * (size_t)n);
+    size_t path_at = 0, path_base = device_path_points(w);
+    memset(hp, 0, RW * sizeof(double) * (size_t)n);
+    for (int a = 0; a < n; a++) {
+        const Robot &rb = w->robots[(size_t)(R0 + a)];
+        double *rec = rec0 + RW * (size_t)a;
+        AppendHeader *h = (AppendHeader *)rec;
+        h->path_at = (int32_t)path_at;
+        h->n_path = (int32_t)(rb.path.size() / 2);
+        h->path_base = (int32_t)path_base;
+        h->iter_factor = rb.iter_factor;
+        h->radius = rb.radius;
+        h->antenna = rb.antenna;
+        h->idle = rb.idle;
+        float *tp = (float *)(rec + L.trk_pos());
+        pack_robot(rb, RobotSink{rec + L.blob(), rec + L.snap(), (uint32_t *)(rec + L.epoch()), rec + L.dyn(), 1, 16, (int32_t *)(rec + L.trk_rec()),
+                                 tp, tp + (K - 2), rec + L.trk_val()});
+        std::copy(rb.path.begin(), rb.path.end(), paths + path_at);
+        path_at += rb.path.size();
+        path_base += rb.path.size() / 2;
+    }
+    tm.lap("block");
+    AppendTargets t{};
+    t.block = (const double *)dp;
+    t.n = n;
+    t.room = w->R_cap;
+    t.path_room = (int)(w->path_xy.cap / 2);
+    t.in_end = w->dev_in_ptr.back();
+    t.path_ptr = w->path_ptr.p; t.path_xy = w->path_xy.p; t.radius = w->radius_dev.p;
+    t.antenna = w->antenna.p; t.idle = w->idle.p;
+    t.in_ptr = w->in_ptr_dev.p; t.in_mid = w->in_mid_dev.p; t.var_ptr = w->ir_var_ptr.p; t.var_mid = w->ir_var_mid.p;
+    HIP_TRY(launch_append_robots(d, L, t, w->stream));
+    HIP_TRY(w->stage.release(slot, w->stream));
+    tm.lap("launch");
+    // the host's picture of the layout
+    w->dev_of.resize(w->robots.size(), -1);
+    for (int id = R0; id < R1; id++) {
+        w->dev_of[(size_t)id] = id;
+        w->robot_of.push_back(id);
+        w->dev_in_ptr.push_back(t.in_end);
+    }
+    d.R_local = d.R_total = R1;
+    d.V = R1 * K;
+    w->path_ptr.n = std::max(w->path_ptr.n, (size_t)R1 + 1);
+    w->path_xy.n = std::max(w->path_xy.n, 2 * path_base);
+    w->radius_dev.n = std::max(w->radius_dev.n, (size_t)R1);
+    w->iter_factor.n = std::max(w->iter_factor.n, (size_t)R1);
+    w->rinc.all = true;  // (every robot's peer row moves with the row pointers' count: the next topology pass sends everybody's piece — a device pass)
+    w->res.robots_appended();
+    w->halo_dirty = true;
+    w->direct.aimed = false;
+    w->search.sets_touched();
+    w->mission.alive_dirty = true;
+    w->dirty = false;
+    w->n_appends++;
+    w->n_robots_appended += (uint64_t)n;
+    tm.lap("bookkeeping");
+    return MGX_OK;
+}
+
 static int commit(mgx_world *w) {
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no usable HIP device (this library has no CPU path)");
     MGX_CONFIRM(w);
     // (whoever comes through here enqueues work or reads state: a lingering launch ends first — unless the caller is on its way
     // to post a schedule into it)
     if (!w->res.linger.hold) { const int rcl = linger_close(w); if (rcl != MGX_OK) return rcl; }
+    if (w->dirty && !w->relayout && w->dev_valid) {
+        // nothing but robots joined since the arrays were laid out: a world with head-room takes them on the device
+        if (w->robots.size() == w->robot_of.size()) {
+            w->dirty = false;
+        } else if (append_fits(w)) {
+            if (w->res.linger.open) { const int rcl = linger_close(w); if (rcl != MGX_OK) return rcl; }  // (every call that adds a robot has ended it already)
+            const int rca = append_robots(w);
+            if (rca != MGX_OK) return rca;
+        }
+    }
     if (!w->dirty) {
         if (w->conns_dirty) return retopo(w);
         if (w->flags_dirty) return upload_flags(w);
@@ -360,6 +510,8 @@ static int commit(mgx_world *w) {
     }
     if (w->robots.empty()) return fail(MGX_ERR_STATE, "world has no robots");
     StageTimer tmc("commit");
+    // (a reserved world that was laid out before and has new robots, on the full path all the same: what mgx_append_stats calls a fallback)
+    if (w->reserve_want && !w->robot_of.empty() && w->robots.size() > w->robot_of.size()) w->n_append_fallbacks++;
     int rc = pull(w);
     if (rc != MGX_OK) return rc;
     tmc.lap("pull (device -> host mirror)");
@@ -377,8 +529,14 @@ static int commit(mgx_world *w) {
     for (size_t r = 0; r < w->robots.size(); r++)
         if (w->robots[r].ghost) { w->dev_of[r] = (int)w->robot_of.size(); w->robot_of.push_back((int)r); }
     const int R_total = (int)w->robot_of.size();
-    const size_t V = (size_t)R_total * K, EI = (size_t)std::max(R_local, 1) * E, ND = (size_t)std::max(R_local, 1) * (K - 1),
-                 NT = (size_t)std::max(R_local, 1) * std::max(K - 2, 1);
+    // Head-room (mgx_world_reserve): the per-robot arrays are sized, and the strided tables strided, for R_cap robots — what the
+    // caller asked for, or twice the robots there are once they outgrew that (a logarithmic number of layouts).  Ghosts follow
+    // the locals in device order, so a world that holds any has none; a world that never asked has R_cap == R_local, and every
+    // array below is what it always was.
+    const int R_cap = (w->reserve_want && R_total == R_local) ? ((uint32_t)R_local > w->reserve_want ? 2 * R_local : (int)w->reserve_want) : R_local;
+    const int RT_cap = R_total + (R_cap - R_local);
+    const size_t V = (size_t)R_total * K, V_cap = (size_t)RT_cap * K, EI = (size_t)std::max(R_cap, 1) * E, ND = (size_t)std::max(R_cap, 1) * (K - 1),
+                 NT = (size_t)std::max(R_cap, 1) * std::max(K - 2, 1);
 
     // initialise fresh inter-robot edges from the (pulled) current state: created epoch of the
     // owner's variable (its inbox slot stays empty until the owner's next delivery) and the target
@@ -418,35 +576,33 @@ static int commit(mgx_world *w) {
     const int ir_max_edges = t.ir_max_edges;
 
     const size_t BS = (size_t)blob_words(K);
-    std::vector<double> blb(BS * (size_t)R_total, 0.0), sn(24 * V), dm(16 * ND, 0.0), tlv(NT, 0.0);
-    std::vector<int32_t> trc(NT, 0), pptr((size_t)R_local + 1, 0), itf((size_t)std::max(R_local, 1), 0);
-    std::vector<uint32_t> ep(V);
+    std::vector<double> blb(BS * (size_t)RT_cap, 0.0), sn(24 * V_cap), dm(16 * ND, 0.0), tlv(NT, 0.0);
+    std::vector<int32_t> trc(NT, 0), pptr((size_t)R_cap + 1, 0), itf((size_t)std::max(R_cap, 1), 0);
+    std::vector<uint32_t> ep(V_cap);
     std::vector<float> tlp(2 * NT, 0.f), pxy;
-    std::vector<double> rad((size_t)R_total, 0.0);
+    std::vector<double> rad((size_t)RT_cap, 0.0);
+    size_t longest_path = 0;
     for (int dr = 0; dr < R_total; dr++) {
         const Robot &rb = w->robots[(size_t)w->robot_of[(size_t)dr]];
         rad[(size_t)dr] = rb.radius;
-        blob_pack(rb, &blb[(size_t)dr * BS]);
-        for (int i = 0; i < K; i++) {
-            const size_t v = (size_t)dr * K + i;
-            memcpy(&sn[v * 24], &rb.snap[24 * i], 24 * sizeof(double));
-            ep[v] = rb.epoch[i];
-        }
+        const size_t d0 = (size_t)dr * (K - 1), t0 = (size_t)dr * (K - 2);
+        pack_robot(rb, RobotSink{&blb[(size_t)dr * BS], &sn[(size_t)dr * K * 24], &ep[(size_t)dr * K], dm.data() + d0, ND, 1, trc.data() + t0,
+                                 tlp.data() + t0, tlp.data() + NT + t0, tlv.data() + t0});
         if (rb.ghost) continue;
-        for (int f = 0; f < K - 1; f++) scatter(dm, ND, (size_t)dr * (K - 1) + f, &rb.dyn_m[16 * f], 16);
-        for (int j = 0; j < K - 2; j++) {
-            const size_t t = (size_t)dr * (K - 2) + j;
-            trc[t] = rb.trk_record[j];
-            tlp[t] = rb.trk_last_pos[2 * j];
-            tlp[NT + t] = rb.trk_last_pos[2 * j + 1];
-            tlv[t] = rb.trk_last_val[j];
-        }
         pptr[(size_t)dr] = (int32_t)(pxy.size() / 2);
         pxy.insert(pxy.end(), rb.path.begin(), rb.path.end());
         pptr[(size_t)dr + 1] = (int32_t)(pxy.size() / 2);
         itf[(size_t)dr] = rb.iter_factor;
+        longest_path = std::max(longest_path, rb.path.size());
     }
+    for (int dr = R_local; dr < R_cap; dr++) {  // the head-room's (empty) ranges end where the last robot's do
+        pptr[(size_t)dr + 1] = pptr[(size_t)R_local];
+        t.in_ptr.push_back(t.in_ptr[(size_t)R_local]);
+    }
+    t.mid.resize((size_t)std::max(R_cap, 1), 0);
     if (pxy.empty()) pxy.assign(2, 0.f);
+    // (path slack: a robot that joins brings a path; room for one as long as the longest so far, 32 points at the least, per free place)
+    const size_t path_room = pxy.size() + (size_t)(R_cap - R_local) * std::max<size_t>(longest_path, 2 * APPEND_PATH_POINTS);
     if (recs.empty()) recs.push_back(IrEdgeRec{0, 0, 0, 0, 0.0, 0.0});
     if (w->sdf_red.empty()) {  // no image: every lookup is "outside" => h = 0
         w->sdf_red.assign(1, 255);
@@ -465,13 +621,13 @@ static int commit(mgx_world *w) {
     HIP_TRY(w->trk_last_pos.upload(tlp, s));
     HIP_TRY(w->trk_last_val.upload(tlv, s));
     HIP_TRY(w->path_ptr.upload(pptr, s));
-    HIP_TRY(w->path_xy.upload(pxy, s));
+    HIP_TRY(w->path_xy.upload(pxy, s, path_room));
     HIP_TRY(w->iter_factor.upload(itf, s));
     HIP_TRY(w->radius_dev.upload(rad, s));
     HIP_TRY(w->in_ptr_dev.upload(t.in_ptr, s));
     HIP_TRY(w->in_mid_dev.upload(t.mid, s));
-    HIP_TRY(w->ir_var_ptr.reserve((size_t)R_local * K + 1));
-    HIP_TRY(w->ir_var_mid.reserve((size_t)std::max(R_local, 1) * K));
+    HIP_TRY(w->ir_var_ptr.reserve((size_t)R_cap * K + 1));
+    HIP_TRY(w->ir_var_mid.reserve((size_t)std::max(R_cap, 1) * K));
     HIP_TRY(launch_var_tables(R_local, K, w->in_ptr_dev.p, w->in_mid_dev.p, w->ir_var_ptr.p, w->ir_var_mid.p, s));
     HIP_TRY(w->ir_rec.upload(recs, s));
     HIP_TRY(w->ir_fv_eta.upload(ife, s));
@@ -565,7 +721,8 @@ static int commit(mgx_world *w) {
 #else
     d.dbg = nullptr;
 #endif
-    w->dirty = false;
+    w->dirty = w->relayout = false;
+    w->R_cap = R_cap;
     w->conns_dirty = false;
     w->rinc.all = true;  // (no slot records on the device yet, device indices may have moved: the first topology change sends everything)
     w->rinc.clear_marks();

@@ -260,7 +260,7 @@ int mgx_reset_variables(mgx_world *w, int32_t robot, const double *means, uint32
         if (c.owner == robot)  // own inter-robot factors: both inbox entries emptied
             for (IrEdge &ed : c.edges) { std::fill(ed.bmu, ed.bmu + 4, 0.0); ed.created = 0; ed.fresh = false; }
     }
-    w->dirty = true;
+    w->dirty = w->relayout = true;
     w->dev_valid = false;  // the host mirror is the truth now: the next launch lays it out again (and must not pull over it)
     return MGX_OK;
 }
@@ -274,7 +274,7 @@ int mgx_reset_tracking_factors(mgx_world *w, int32_t robot) {
     if (rc != MGX_OK) return rc;
     Robot &rb = w->robots[(size_t)robot];
     for (int32_t &rec : rb.trk_record) rec = (rec & 0xffff) | (11 << 16);  // Some(10), gbp_math.h tracking_timeout_skips
-    w->dirty = true;
+    w->dirty = w->relayout = true;
     w->dev_valid = false;
     return MGX_OK;
 }
@@ -293,20 +293,23 @@ int mgx_set_tracking_path(mgx_world *w, int32_t robot, const float *path_xy, uin
     // (a resident launch the census declined is run again first: its schedule was issued under the old path)
     MGX_CONFIRM(w);
     w->robots[(size_t)robot].path.assign(path_xy, path_xy + 2 * (size_t)n_path);
-    if (w->dirty || !w->dev_valid) return MGX_OK;
+    // (about to be laid out in full; robots that only wait to be appended bring their paths along, the ones on the device are packed here)
+    if (w->relayout || !w->dev_valid) return MGX_OK;
     const size_t RL = (size_t)w->d.R_local;
     std::vector<int32_t> pptr(RL + 1, 0);
     std::vector<float> pxy;
+    size_t longest = 0;
     for (size_t dr = 0; dr < RL; dr++) {  // (as commit packs them — every robot's again: one packed array, a rare call)
         const Robot &rb = w->robots[(size_t)w->robot_of[dr]];
         pptr[dr] = (int32_t)(pxy.size() / 2);
         pxy.insert(pxy.end(), rb.path.begin(), rb.path.end());
         pptr[dr + 1] = (int32_t)(pxy.size() / 2);
+        longest = std::max(longest, rb.path.size());
     }
     if (pptr.size() > w->path_ptr.cap || pxy.size() > w->path_xy.cap)
         HIP_TRY(hipStreamSynchronize(w->stream));  // (an array that has to grow is freed first: nothing may still read it)
-    HIP_TRY(w->path_ptr.upload(pptr, w->stream));
-    HIP_TRY(w->path_xy.upload(pxy, w->stream));
+    HIP_TRY(w->path_ptr.upload(pptr, w->stream, (size_t)w->R_cap + 1));
+    HIP_TRY(w->path_xy.upload(pxy, w->stream, pxy.size() > w->path_xy.cap ? path_room_for(w, pxy.size(), longest) : 0));
     w->d.path_ptr = w->path_ptr.p;
     w->d.path_xy = w->path_xy.p;
     HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vectors die here
@@ -371,16 +374,18 @@ int mgx_apply_global_paths(mgx_world *w, uint32_t n, const int32_t *robots, cons
     {  // the packed path arrays, as mgx_set_tracking_path rebuilds them
         std::vector<int32_t> pptr(RL + 1, 0);
         std::vector<float> pxy;
+        size_t longest = 0;
         for (size_t dr = 0; dr < RL; dr++) {
             const Robot &rb = w->robots[(size_t)w->robot_of[dr]];
             pptr[dr] = (int32_t)(pxy.size() / 2);
             pxy.insert(pxy.end(), rb.path.begin(), rb.path.end());
             pptr[dr + 1] = (int32_t)(pxy.size() / 2);
+            longest = std::max(longest, rb.path.size());
         }
         if (pptr.size() > w->path_ptr.cap || pxy.size() > w->path_xy.cap)
             HIP_TRY(hipStreamSynchronize(w->stream));  // (an array that has to grow is freed first: nothing may still read it)
-        HIP_TRY(w->path_ptr.upload(pptr, w->stream));
-        HIP_TRY(w->path_xy.upload(pxy, w->stream));
+        HIP_TRY(w->path_ptr.upload(pptr, w->stream, (size_t)w->R_cap + 1));
+        HIP_TRY(w->path_xy.upload(pxy, w->stream, pxy.size() > w->path_xy.cap ? path_room_for(w, pxy.size(), longest) : 0));
         w->d.path_ptr = w->path_ptr.p;
         w->d.path_xy = w->path_xy.p;
         HIP_TRY(hipStreamSynchronize(w->stream));  // the staging vectors die here
@@ -454,6 +459,25 @@ static int apply_global_route(mgx_world *w, int32_t robot, const float *xy, uint
     for (size_t q = 0; q < wp.size(); q++) wp[q] = (double)xy[2 + q];
     ms.target[(size_t)robot] = 0;
     if (!on_device) ms.dirty = true;
+    return MGX_OK;
+}
+// The world expects to hold up to `robots` robots: the next full layout sizes the per-robot arrays for that many, and commit()
+// brings the robots that join afterwards onto the device in place (append_robots).  Before the first layout only the wish is
+// recorded; a laid-out world is marked for ONE full layout with the head-room.
+int mgx_world_reserve(mgx_world *w, uint32_t robots) {
+    MGX_ENTER(w);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (robots > 0x3fffffffu) return fail(MGX_ERR_INVALID, "%u robots: more than a world can hold", robots);
+    if ((size_t)robots <= w->robots.size() || robots <= w->reserve_want) return MGX_OK;  // (the head-room already there stays)
+    w->reserve_want = robots;
+    if (w->dev_valid && (int)robots > w->R_cap) w->dirty = w->relayout = true;
+    return MGX_OK;
+}
+int mgx_append_stats(mgx_world *w, uint64_t *appends, uint64_t *robots_appended, uint64_t *fallbacks) {
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (appends) *appends = w->n_appends;
+    if (robots_appended) *robots_appended = w->n_robots_appended;
+    if (fallbacks) *fallbacks = w->n_append_fallbacks;
     return MGX_OK;
 }
 int mgx_layout_stats(mgx_world *w, uint64_t *n_layouts, uint64_t *n_pulls) {

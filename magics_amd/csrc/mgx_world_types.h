@@ -60,6 +60,7 @@ hipError_t launch_mission_prepare(const DevWorld &w, const DevMission &m, int n,
 hipError_t launch_retopo_robots(const DevWorld &w, const RetopoBlock &b, const int32_t *in_old, const IrSlotRec *slots_old, const int32_t *peers_old,
                                 int32_t *in_dst, IrSlotRec *slots_new, int32_t *peers_dst, int32_t *var_ptr, int32_t *var_mid, int stride_new,
                                 IrEdgeRec *recs, double *fv_eta, double *fv_lam, double *bmu, uint8_t *gate, hipStream_t stream);
+hipError_t launch_append_robots(const DevWorld &w, const AppendLayout &l, const AppendTargets &t, hipStream_t stream);
 hipError_t launch_var_tables(int R, int K, const int32_t *in_ptr, const int32_t *in_mid, int32_t *var_ptr, int32_t *var_mid,
                              hipStream_t stream);
 hipError_t launch_edge_gates(int n, const IrEdgeRec *recs, const uint8_t *antenna, const uint8_t *idle, uint8_t *gate, hipStream_t stream);
@@ -142,9 +143,10 @@ struct DevBuf {
         n = cap = 0;
     }
     // (re)allocates only when growing; the copy is enqueued on `s` from pageable memory, so the
-    // caller synchronises before `h` dies
-    hipError_t upload(const std::vector<T> &h, hipStream_t s) {
-        const size_t want = h.size() ? h.size() : 1;
+    // caller synchronises before `h` dies.  room: elements the allocation holds at least (head-room behind the upload: what a
+    // reserved world appends into, mgx_world_reserve)
+    hipError_t upload(const std::vector<T> &h, hipStream_t s, size_t room = 0) {
+        const size_t want = std::max<size_t>(std::max(h.size(), room), 1);
         if (want > cap) {
             release();
             hipError_t e = hipMalloc((void **)&p, sizeof(T) * want);
@@ -532,6 +534,15 @@ struct ResidentLaunches {
         flag_base = 0;
         cap = cap_sharded = -1;
     }
+    // commit appended robots behind the ones on the device (append_robots): progress words and exchange records are re-created
+    // for the new count (a launch's first segment reads snapshots, not records) and the peer table is built again — row pointers
+    // and entries share one array whose split moves with the count; the capacity asked of the runtime stays: it follows the
+    // LDS footprint, which a robot without connections does not change
+    void robots_appended() {
+        peers_valid = false;
+        sweep_flag_buf.n = 0;
+        flag_base = 0;
+    }
     // the resident kernel's LDS per workgroup (hence workgroups per CU) follows the largest number of edges on one robot: a
     // capacity asked for a sparser topology says nothing about this one
     void lds_footprint_changed() { cap = cap_sharded = -1; }
@@ -599,7 +610,13 @@ struct mgx_world {
     int K = 0;
 
     hipStream_t stream = nullptr;
-    bool dirty = true;       // robots / image changed since the device arrays were built: full rebuild
+    bool dirty = true;       // robots / image changed since the device arrays were built: commit() has robots to bring onto the device
+    bool relayout = true;    // ... and not only robots were added (image, shard calls, edits of the host mirror): full rebuild.  relayout implies dirty
+    // mgx_world_reserve: the robots the world expects to hold (0: never asked), the robots the per-robot device arrays of the
+    // layout there now have room for (== d.R_local on a world that never asked: today's arrays), and what mgx_append_stats counts
+    uint32_t reserve_want = 0;
+    int R_cap = 0;
+    uint64_t n_appends = 0, n_robots_appended = 0, n_append_fallbacks = 0;
     bool conns_dirty = false;  // only inter-robot connections changed: edge tables are rebuilt in place
     bool flags_dirty = true;
     bool dev_valid = false;  // device arrays hold live state

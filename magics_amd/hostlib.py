@@ -185,6 +185,8 @@ SYMBOLS = {
     "mgx_set_tracking_path": (C.c_int, [_V, C.c_int32, C.c_void_p, C.c_uint32]),
     "mgx_apply_global_paths": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double, C.c_uint32]),
     "mgx_layout_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mgx_world_reserve": (C.c_int, [_V, C.c_uint32]),
+    "mgx_append_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mgx_mission_set": (C.c_int, [_V, C.c_int32, C.c_void_p]),
     "mgx_mission_tick": (C.c_int, [_V, C.c_float, C.c_uint32, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p, C.c_double, C.c_double,
                                    C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]),

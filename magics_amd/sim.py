@@ -143,6 +143,8 @@ class Simulation:
         self.method = neighbours_method
         world.set_environment(self.env)                          # simulation_loader.rs:154-162
         self.spawners = [spawner.FormationSpawner(i, f) for i, f in enumerate(self.formations)]
+        if hasattr(world, "reserve"):  # (the engine: robots that spawn while the world runs are appended on the device)
+            world.reserve(self._robots_expected())
         self.robots = []           # per robot: dict (see _add_robot)
         self._translation = np.zeros((0, 3), dtype=F)
         self.tick_no, self.next_number, self.K = 0, 1, None
@@ -155,6 +157,26 @@ class Simulation:
         elif self._env_coll:
             self._colliders, self._collider_vertices = hostlib.env_colliders(self.env)
         self.entities = spawner.EntityAllocator()  # the robots' Entity bits = their graphs' order (id.rs:19-54)
+
+    RESERVE_LIMIT = 256  # robots reserved at most for formations that repeat forever (beyond it the engine doubles its head-room)
+
+    def _robots_expected(self):
+        """robots the formations will ever spawn (removed ones included) where that is finite; formations that repeat forever:
+        what they spawn within the scenario's max-time, RESERVE_LIMIT at the most"""
+        horizon_ns = float(self.cfg["simulation"]["max-time"]) * 1e9
+        total = 0
+        for f in self.formations:
+            rep = f["repeat"]
+            if rep is None:
+                spawns = 1
+            elif rep["times"] is not None:
+                spawns = 1 + rep["times"]
+            elif rep["every"] > 0 and np.isfinite(horizon_ns):
+                spawns = 1 + int(max(horizon_ns - f["delay"], 0) // rep["every"])
+            else:
+                return self.RESERVE_LIMIT
+            total += f["robots"] * spawns
+        return int(min(total, self.RESERVE_LIMIT))
 
     # -- spawn_formation (spawner.rs:415-649) + RobotBundle::new (robot.rs:1134-1356) -------------------
     def _add_robot(self, desc, formation_index):

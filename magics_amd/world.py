@@ -273,6 +273,18 @@ class World:
         self._chk(self._L.mgx_layout_stats(self._w, C.byref(nl), C.byref(npl)))
         return int(nl.value), int(npl.value)
 
+    def reserve(self, robots):
+        """The world expects to hold up to `robots` robots (removed ones included): robots added to the laid-out world are then
+        appended on the device — nothing pulled, nothing laid out again — for as long as they fit (mgx_world_reserve)."""
+        self._chk(self._L.mgx_world_reserve(self._w, int(robots)))
+
+    def append_stats(self):
+        """-> (commits that appended in place, robots they brought onto the device, commits of the reserved world that had new
+        robots and ran the full layout all the same) — mgx_append_stats"""
+        a, r, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self._L.mgx_append_stats(self._w, C.byref(a), C.byref(r), C.byref(f)))
+        return int(a.value), int(r.value), int(f.value)
+
     def change_priors(self, robots, var_ix, means):
         robots = np.ascontiguousarray(robots, dtype=np.int32)
         var_ix = np.ascontiguousarray(var_ix, dtype=np.uint32)

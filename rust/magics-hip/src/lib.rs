@@ -80,6 +80,16 @@ impl World {
         check(unsafe { sys::mgx_layout_stats(self.raw, &mut layouts, &mut pulls) })?;
         Ok((layouts, pulls))
     }
+    /// head-room for the robots the spawner adds while the world runs (spawner.rs:415-646): they are appended on the device
+    pub fn reserve(&self, robots: u32) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_world_reserve(self.raw, robots) })
+    }
+    /// (commits that appended in place, robots they brought onto the device, commits that fell back to the full layout)
+    pub fn append_stats(&self) -> Result<(u64, u64, u64), MgxError> {
+        let (mut appends, mut robots, mut fallbacks) = (0u64, 0u64, 0u64);
+        check(unsafe { sys::mgx_append_stats(self.raw, &mut appends, &mut robots, &mut fallbacks) })?;
+        Ok((appends, robots, fallbacks))
+    }
     /// `update_failed_comms` (robot.rs:1593-1601): the Bernoulli draws stay with the caller's PRNG
     pub fn set_antennas(&self, robots: &[i32], active: &[u8]) -> Result<(), MgxError> {
         assert_eq!(robots.len(), active.len());

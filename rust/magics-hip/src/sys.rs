@@ -207,6 +207,8 @@ extern "C" {
     pub fn mgx_set_tracking_path(w: *mut mgx_world, robot: i32, path_xy: *const f32, n_path: u32) -> c_int;
     pub fn mgx_apply_global_paths(w: *mut mgx_world, n: u32, robots: *const i32, path_ptr: *const u32, path_xy: *const f32, means: *const f64, first_last_sigma: f64, inbetween_sigma: f64, flags: u32) -> c_int;
     pub fn mgx_layout_stats(w: *mut mgx_world, n_layouts: *mut u64, n_pulls: *mut u64) -> c_int;
+    pub fn mgx_world_reserve(w: *mut mgx_world, robots: u32) -> c_int;
+    pub fn mgx_append_stats(w: *mut mgx_world, appends: *mut u64, robots_appended: *mut u64, fallbacks: *mut u64) -> c_int;
     pub fn mgx_update_priors(w: *mut mgx_world, n: u32, robots: *const i32, waypoints_xy: *const f64, time_scale: *const f64, what: *const u8, max_speed: f64, delta_t: f64) -> c_int;
     pub fn mgx_tick(w: *mut mgx_world, n: u32, robots: *const i32, waypoints_xy: *const f64, time_scale: *const f64, what: *const u8, max_speed: f64, delta_t: f64, steps: *const u8, n_steps: u32) -> c_int;
     pub fn mgx_mission_set(w: *mut mgx_world, robot: i32, desc: *const mgx_mission_desc) -> c_int;
