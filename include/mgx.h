@@ -922,6 +922,91 @@ int mgx_env_collisions_read(mgx_world *w, uint64_t first, mgx_env_collision_even
                             uint64_t *n_total, uint64_t *dropped, uint32_t *per_robot);
 int mgx_env_collisions_clear(mgx_world *w);
 
+/* ---- global planner: batched RRT* over the map's colliders -------------------------------------------------------
+ * What crates/gbp_global_planner does for one robot (rrtstar.rs:15-83; started from progress_missions, robot.rs:578-633),
+ * for many requests in one call: a formation spawns and every robot of it asks at once.  The paths it returns are what
+ * mgx_apply_global_paths takes.
+ *
+ * SPECIFICATION OF A PLAN.  This is the specification, not a claim about the `rrt` crate: the reference calls a git fork of it
+ *   (Cargo.toml:72-84) that is absent from its tree, as is `rand`, so there is nothing to be bit-identical to.
+ *   magics_amd/global_planner.py restates it on the host and is the checker of the device.
+ *   ARITHMETIC.  f64, every operation rounded on its own (the same in libmgx.so and libmgx_fma.so): d2(a, b) = dx*dx + dy*dy,
+ *     dist = sqrt(d2).  Planner (x, y) is the collider table's (x, z), the frame of the contact specification above: no flip.
+ *   feasible(p): no collider of the table touches a ball at ((float)p.x, (float)p.y) with radius collision_radius under the
+ *     specification of a contact above.  Points outside the grid are feasible unless a collider reaches them.  Neither the root
+ *     nor `end` is tested (the reference hands only tree nodes to its callback).
+ *   RANDOM STREAM.  One wyrand state per request (state += 0xA0761D6478BD642F; t = state * (state ^ 0xE7037ED1A0B428DB) in 128
+ *     bits; next_u64 = hi(t) ^ lo(t); next_u32 = its low half).  uniform(h): u = next_u64,
+ *     v = f64_from_bits((u >> 12) | 0x3FF0000000000000) - 1.0, result v*(2h) + (-h).  A sample is (uniform(h), uniform(h)), x
+ *     first, h = sample_half_extent.  gen_index(n) is rand 0.8.5's UniformInt::<u32>::sample_single(0, n): zone =
+ *     (n << clz(n)) - 1; draw next_u32 until lo32(draw * n) <= zone; the result is hi32(draw * n).
+ *   TREE GROWTH.  Node 0 is ((double)start.x, (double)start.y), cost 0, no parent.  Iteration i = 1 .. max_iterations:
+ *     1. q = sample.
+ *     2. n* = the node with the smallest d2(node, q); ties: the lowest index.
+ *     3. d = sqrt(d2*).  d == 0: the iteration ends.  d <= step: p = q.  Otherwise t = step / d, p = n* + t*(q - n*) per axis.
+ *     4. !feasible(p): the iteration ends.
+ *     5. N = the nodes with d2(node, p) <= radius*radius.
+ *     6. parent = the k in N u {n*} with the smallest cost[k] + dist(k, p); ties: the lowest index.  That value is cost_new.
+ *     7. The tree already holds max_nodes: the request ends with MGX_PLAN_TREE_FULL.  Otherwise append m = (p, parent, cost_new).
+ *     8. Rewire: for k in N, k != parent: c = cost_new + dist(k, p); c < cost[k]: parent[k] = m, cost[k] = c.  Descendants'
+ *        costs are NOT propagated.
+ *     9. dist(p, end) <= step: the goal is reached at m, growth stops (the first reach), and the path's cost is
+ *        cost_new + dist(p, end).
+ *     max_iterations without a reach: MGX_PLAN_MAX_ITERATIONS (PathfindingError::ReachedMaxIterations).
+ *   PATH.  The parent chain from m to node 0, reversed, then `end`.
+ *   SMOOTHING.  If enabled, while the path has >= 3 points, for s < smoothing_max_iterations: a = gen_index(len - 2);
+ *     b = a + 2 + gen_index(len - 2 - a); L = dist(P[a], P[b]); the chord is free iff feasible(P[a] + (P[b] - P[a]) * ((j*h)/L))
+ *     for every j = 1 .. floor(L/h), h = smoothing_step; a free chord deletes P[a+1 .. b-1].
+ *   Points go out as f32.  A request that fails has no points.
+ *
+ * mgx_planner_enable(w, env, params): builds the collider table of `env` and uploads it with the per-tile grid the
+ *   robot-environment pass uses (its own copy: either can be switched off without the other).  env == NULL switches off and drops
+ *   every allocation.  Default: off — no allocation, no change to anything else.  Calling it while on replaces map and
+ *   parameters.  MGX_ERR_INVALID: step_size, neighbourhood_radius (and smoothing_step when smoothing is enabled) not positive
+ *   and finite, collision_radius or sample_half_extent negative or not finite, max_nodes beyond 65536.  The positions of a
+ *   tree live in the workgroup's LDS: max_nodes beyond 8192 needs more of it than a gfx950 CU has and fails at the launch.
+ * mgx_plan_paths(w, n, requests, results, path_xy, point_capacity, n_points): plans the n requests, synchronously (like every
+ *   other call it first ends a lingering launch).  One workgroup per request; a launch runs at most iterations_per_launch
+ *   iterations of every request (growth and smoothing iterations alike) and the host launches again until every request has
+ *   ended: no kernel is unbounded, and the result does not depend on where the slices fall.  results[i] is filled for every
+ *   request; the points of request i are path_xy[first_point .. first_point + n_points), requests in order; *n_points = all
+ *   points.  point_capacity too small: results (first_point, n_points and the rest) and *n_points are filled, path_xy is not
+ *   touched, MGX_ERR_INVALID.  NULL requests / results / n_points, NULL path_xy with a capacity, or a non-finite coordinate:
+ *   MGX_ERR_INVALID and nothing is changed.  MGX_ERR_STATE while switched off and on a sharded world (one with ghosts).
+ * mgx_plan_tree(w, request, capacity, xy, parent, cost, n_nodes): the tree of a request of the LAST mgx_plan_paths (for tests and
+ *   tools): positions [.][2], parents (-1: the root) and stored costs of the first min(capacity, *n_nodes) nodes; any array
+ *   may be NULL. */
+#define MGX_PLAN_OK 0
+#define MGX_PLAN_MAX_ITERATIONS 1
+#define MGX_PLAN_TREE_FULL 2
+typedef struct mgx_plan_params {
+    float step_size, neighbourhood_radius, collision_radius; /* RRTSection (config)                          */
+    uint32_t max_iterations;
+    int32_t smoothing_enabled;
+    uint32_t smoothing_max_iterations;
+    float smoothing_step;
+    float sample_half_extent;       /* 0: 2000, the reference's constant (gbp_global_planner lib.rs:155-185) */
+    uint32_t max_nodes;             /* 0: 8192                                                               */
+    uint32_t iterations_per_launch; /* 0: 1024                                                               */
+} mgx_plan_params;
+typedef struct mgx_plan_request {
+    float start[2], end[2];
+    uint64_t wyrand_state;
+} mgx_plan_request;
+typedef struct mgx_plan_result {
+    int32_t status;                 /* MGX_PLAN_*                                                            */
+    uint32_t first_point, n_points; /* into path_xy; 0 points unless status is MGX_PLAN_OK                   */
+    uint32_t n_nodes, iterations;
+    uint32_t reserved;
+    double cost;                    /* of the path before smoothing                                          */
+    uint64_t wyrand_state;          /* the stream after the draws made                                       */
+} mgx_plan_result;
+int mgx_planner_enable(mgx_world *w, const mgx_env_desc *env, const mgx_plan_params *params);
+int mgx_plan_paths(mgx_world *w, uint32_t n, const mgx_plan_request *requests, mgx_plan_result *results, float *path_xy,
+                   uint32_t point_capacity, uint32_t *n_points);
+int mgx_plan_tree(mgx_world *w, uint32_t request, uint32_t capacity, double *xy, int32_t *parent, double *cost,
+                  uint32_t *n_nodes);
+
 /* ---- host helpers (no device needed) --------------------------------------------------- */
 /* gbp_schedule: fills steps[max(n_int,n_ext)] with MGX_STEP_* bits. Returns the count
  * or a negative status. (crates/gbp_schedule/src/schedules/ *.rs) */

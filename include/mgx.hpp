@@ -305,6 +305,26 @@ public:
         return out;
     }
     void env_collisions_clear() { check(mgx_env_collisions_clear(w_)); }
+    /// the global planner (batched RRT* over the colliders of `env`, specified in mgx.h); nullptr switches it off
+    void planner_enable(const mgx_env_desc *env, const mgx_plan_params &params) { check(mgx_planner_enable(w_, env, &params)); }
+    struct Plans {
+        std::vector<mgx_plan_result> results;     ///< one per request; its points are path_xy[first_point .. + n_points)
+        std::vector<std::array<float, 2>> path_xy;
+    };
+    Plans plan_paths(const std::vector<mgx_plan_request> &requests) {
+        Plans out;
+        out.results.resize(requests.size());
+        out.path_xy.resize(256 * requests.size() + 1);
+        uint32_t total = 0;
+        int rc = mgx_plan_paths(w_, (uint32_t)requests.size(), requests.data(), out.results.data(), out.path_xy[0].data(), (uint32_t)out.path_xy.size(), &total);
+        if (rc == MGX_ERR_INVALID && total > out.path_xy.size()) {  // (the counts came back: once more with room for them)
+            out.path_xy.resize(total);
+            rc = mgx_plan_paths(w_, (uint32_t)requests.size(), requests.data(), out.results.data(), out.path_xy[0].data(), total, &total);
+        }
+        check(rc);
+        out.path_xy.resize(total);
+        return out;
+    }
     void synchronize() { check(mgx_synchronize(w_)); }
     uint32_t K() const { return K_; }
 

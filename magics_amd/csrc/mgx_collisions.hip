@@ -49,6 +49,7 @@
 #include "../../include/mgx.h"
 #include "gbp_math.h"
 #include "mgx_dev.h"
+#include "mgx_env_contact.h"
 #include "mgx_grid.h"
 
 namespace mgx {
@@ -245,45 +246,7 @@ static_assert(offsetof(mgx_env_collision_event, robot) == offsetof(ContactEvent,
               "ContactEvent is the ABI's record");
 static_assert(ENV_COLL_SLOTS == 8, "the slots travel as two int4");
 
-__device__ __forceinline__ float sq_sum(float a, float b) { return __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)); }
-
-// the contact of include/mgx.h: every operation rounded to f32 on its own; a NaN anywhere: false
-__device__ bool env_touches(const EnvCollider &k, const float *__restrict__ verts, float x, float z, float r) {
-    switch (k.kind) {
-    case MGX_COLLIDER_BALL: {
-        const float rs = __fadd_rn(r, k.radius);
-        return sq_sum(__fsub_rn(x, k.tx), __fsub_rn(z, k.tz)) <= __fmul_rn(rs, rs);
-    }
-    case MGX_COLLIDER_CUBOID: {
-        const float dx = __fsub_rn(fabsf(__fsub_rn(x, k.tx)), k.hx), dz = __fsub_rn(fabsf(__fsub_rn(z, k.tz)), k.hz);
-        if (dx != dx || dz != dz) return false;  // (fmaxf below would drop a NaN)
-        return sq_sum(fmaxf(dx, 0.f), fmaxf(dz, 0.f)) <= __fmul_rn(r, r);
-    }
-    case MGX_COLLIDER_POLYGON: {
-        const uint32_t n = k.n_vertices;
-        if (n == 0) return false;
-        const float *v = verts + 2 * (size_t)k.first_vertex;
-        bool inside = n >= 3 && r == r;
-        float best = INFINITY;
-        float ax = v[2 * (n - 1)], az = v[2 * (n - 1) + 1];  // edge n-1 first: v_{n-1} -> v_0
-        for (uint32_t i = 0; i < n; i++) {
-            const float bx = v[2 * i], bz = v[2 * i + 1];
-            const float ex = __fsub_rn(bx, ax), ez = __fsub_rn(bz, az), qx = __fsub_rn(x, ax), qz = __fsub_rn(z, az);
-            inside = inside && (__fsub_rn(__fmul_rn(ex, qz), __fmul_rn(ez, qx)) >= 0.f);
-            const float len2 = sq_sum(ex, ez);
-            float t = len2 == 0.f ? 0.f : __fdiv_rn(__fadd_rn(__fmul_rn(qx, ex), __fmul_rn(qz, ez)), len2);
-            if (t != t) return false;
-            t = fminf(fmaxf(t, 0.f), 1.f);
-            const float d2 = sq_sum(__fsub_rn(qx, __fmul_rn(t, ex)), __fsub_rn(qz, __fmul_rn(t, ez)));
-            if (d2 != d2) return false;
-            best = fminf(best, d2);
-            ax = bx; az = bz;
-        }
-        return inside || best <= __fmul_rn(r, r);
-    }
-    default: return false;
-    }
-}
+// (the contact itself, env_touches, is shared with the global planner: mgx_env_contact.h)
 
 __global__ void __launch_bounds__(64) k_env_collisions(EnvCollDev c) {
     const int i = (int)(blockIdx.x * 64 + threadIdx.x);

@@ -344,6 +344,49 @@ struct EnvCollDev : ContactDev {  // words[1]: a robot touched more than the slo
 };
 static_assert(sizeof(CollDev) == 128 && sizeof(EnvCollDev) == 152, "kernel arguments by value: no larger than before the fold");
 
+// The map's side of EnvCollDev on its own: what a kernel needs to test a ball against the colliders (mgx_env_contact.h).  The
+// global planner's feasibility test reads it (mgx_planner.hip).
+struct EnvMapDev {
+    int n_colliders;
+    int n_cx, n_cz;            // a cell is one tile
+    int reserved;
+    const EnvCollider *colliders;
+    const float *verts;
+    const uint32_t *cell_ptr;  // [n_cx * n_cz + 1] CSR over cells (cz * n_cx + cx)
+    const int32_t *cell_idx;   // collider indices
+    double x0, z0, inv_cell;   // cell of a coordinate: floor((v - origin) * inv_cell), clamped into the grid
+    double pad;                // added to a ball's radius when its cells are chosen
+};
+
+// Global planner (mgx_planner.hip): one request's state between launches, and what a launch is handed.
+constexpr int32_t PLAN_PHASE_INIT = 0, PLAN_PHASE_GROW = 1, PLAN_PHASE_SMOOTH = 2, PLAN_PHASE_FINISH = 3, PLAN_PHASE_DONE = 4;
+struct PlanState {             // 64 bytes
+    unsigned long long rng;    // the wyrand state
+    double cost;               // of the path before smoothing
+    float start[2], end[2];
+    int32_t phase;             // PLAN_PHASE_*
+    int32_t status;            // MGX_PLAN_* once the phase is DONE
+    uint32_t n_nodes, iterations;
+    uint32_t path_len;         // points of the path (the tree's nodes on it, then `end`)
+    uint32_t smooth_done;      // smoothing iterations so far
+    int32_t goal;              // the node that reached the goal
+    uint32_t reserved;
+};
+static_assert(sizeof(PlanState) == 64, "one request's state is one 64-byte record");
+struct PlanDev {
+    EnvMapDev map;
+    PlanState *state;          // [n]
+    double *x, *y, *cost;      // [n][max_nodes] the trees, SoA
+    int32_t *parent;           // [n][max_nodes]
+    int32_t *path;             // [n][max_nodes + 1] node indices along the path, -1: `end`
+    float *out;                // [n][max_nodes + 1][2] the path's points as f32
+    double step, radius2, half_extent, smoothing_step;
+    float collision_radius;
+    uint32_t max_iterations, max_nodes, smoothing_max;
+    uint32_t budget;           // iterations (growth and smoothing together) one launch runs per request at the most
+    int32_t smoothing;
+};
+
 __host__ __device__ constexpr int frozen_words(int K) { return 40 * (K - 1) + 8 * (K - 2); }
 
 // phases of one launch

@@ -249,7 +249,7 @@ static int collisions_reset(mgx_world *w) {  // everybody Free, nothing logged, 
 static void env_collisions_drop(mgx_world *w) {
     mgx_world::EnvCollisions &c = w->envcoll;
     contacts_drop(c);
-    c.colliders.release(); c.verts.release(); c.cell_ptr.release(); c.cell_idx.release(); c.touching.release();
+    c.map.release(); c.touching.release();
     c.d = EnvCollDev{};
 }
 
@@ -291,9 +291,9 @@ static int env_collisions_reset(mgx_world *w) {  // everybody Free, nothing logg
     return contacts_reset(c, w->stream);
 }
 
-// switched on: the map's colliders, the grid over them and the log go up (a failure leaves the caller to drop what went up)
-static int env_collisions_open(mgx_world *w, const mgx_env_desc *env, uint64_t event_capacity) {
-    mgx_world::EnvCollisions &c = w->envcoll;
+// the map's colliders and the grid over them, built on the host (the map is static) and uploaded: what the robot-environment pass
+// and the global planner both read.  Synchronises the stream (the tables go up from pageable memory)
+static int env_map_upload(mgx_world *w, const mgx_env_desc *env, mgx_world::EnvMap &m) {
     uint32_t n = 0, nv = 0;
     int rc = mgx_env_colliders(env, nullptr, 0, &n, nullptr, 0, &nv);
     if (rc != MGX_OK) return rc;
@@ -301,9 +301,6 @@ static int env_collisions_open(mgx_world *w, const mgx_env_desc *env, uint64_t e
     std::vector<float> verts(2 * (size_t)nv);
     if (n && (rc = mgx_env_colliders(env, cols.data(), n, &n, verts.data(), nv, &nv)) != MGX_OK) return rc;
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no usable HIP device");
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "collision bookkeeping runs on unsharded worlds");
-    c.d = EnvCollDev{};
-    if ((rc = contacts_open(c, c.d, event_capacity)) != MGX_OK) return rc;
     if ((uint64_t)env->n_cols * env->n_rows > (1ull << 24)) return fail(MGX_ERR_INVALID, "more than 2^24 tiles");
     // the grid: a cell is one tile, the world is centred on the origin (map_generator.rs:563-579)
     const int ncx = (int)env->n_cols, ncz = (int)env->n_rows;
@@ -331,14 +328,29 @@ static int env_collisions_open(mgx_world *w, const mgx_env_desc *env, uint64_t e
                 for (int cx = dev[k].cx0; cx <= dev[k].cx1; cx++) idx[at[(size_t)cz * ncx + cx]++] = (int32_t)k;
     }
     hipStream_t s = w->stream;
-    HIP_TRY(c.colliders.upload(dev, s));
-    HIP_TRY(c.verts.upload(verts, s));
-    HIP_TRY(c.cell_ptr.upload(ptr, s));
-    HIP_TRY(c.cell_idx.upload(idx, s));
+    HIP_TRY(m.colliders.upload(dev, s));
+    HIP_TRY(m.verts.upload(verts, s));
+    HIP_TRY(m.cell_ptr.upload(ptr, s));
+    HIP_TRY(m.cell_idx.upload(idx, s));
     HIP_TRY(hipStreamSynchronize(s));  // (the tables go up from pageable memory)
-    c.d.colliders = c.colliders.p; c.d.n_colliders = (int)n; c.d.verts = c.verts.p;
-    c.d.cell_ptr = c.cell_ptr.p; c.d.cell_idx = c.cell_idx.p; c.d.n_cx = ncx; c.d.n_cz = ncz;
-    c.d.x0 = x0; c.d.z0 = z0; c.d.inv_cell = inv; c.d.pad = ENV_COLL_PAD * ts;
+    m.d.colliders = m.colliders.p; m.d.n_colliders = (int)n; m.d.verts = m.verts.p;
+    m.d.cell_ptr = m.cell_ptr.p; m.d.cell_idx = m.cell_idx.p; m.d.n_cx = ncx; m.d.n_cz = ncz;
+    m.d.x0 = x0; m.d.z0 = z0; m.d.inv_cell = inv; m.d.pad = ENV_COLL_PAD * ts;
+    return MGX_OK;
+}
+
+// switched on: the map's colliders, the grid over them and the log go up (a failure leaves the caller to drop what went up)
+static int env_collisions_open(mgx_world *w, const mgx_env_desc *env, uint64_t event_capacity) {
+    mgx_world::EnvCollisions &c = w->envcoll;
+    int rc = env_map_upload(w, env, c.map);
+    if (rc != MGX_OK) return rc;
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "collision bookkeeping runs on unsharded worlds");
+    c.d = EnvCollDev{};
+    if ((rc = contacts_open(c, c.d, event_capacity)) != MGX_OK) return rc;
+    const EnvMapDev &m = c.map.d;
+    c.d.colliders = m.colliders; c.d.n_colliders = m.n_colliders; c.d.verts = m.verts;
+    c.d.cell_ptr = m.cell_ptr; c.d.cell_idx = m.cell_idx; c.d.n_cx = m.n_cx; c.d.n_cz = m.n_cz;
+    c.d.x0 = m.x0; c.d.z0 = m.z0; c.d.inv_cell = m.inv_cell; c.d.pad = m.pad;
     return env_collisions_reset(w);
 }
 

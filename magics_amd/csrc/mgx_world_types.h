@@ -77,6 +77,8 @@ int env_red_plane(const mgx_env_desc *d, uint32_t resolution, float expansion, f
 hipError_t launch_collisions_pass(const CollDev &c, bool grid, double cell, uint32_t n_buckets, hipStream_t s);
 hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s);
 hipError_t launch_env_collisions_pass(const EnvCollDev &c, hipStream_t s);
+// mgx_planner.hip
+hipError_t launch_plan(const PlanDev &c, int n_requests, hipStream_t s);
 }  // namespace mgx
 
 using namespace mgx;
@@ -766,13 +768,32 @@ struct mgx_world {
         CollDev d{};
     } coll;
     // robot-environment (mgx_env_collisions_*): the map's side, uploaded once by _enable, and the colliders every robot touches
-    struct EnvCollisions : ContactBook {
+    // the map as the device reads it: the collider table, the polygons' vertices and the per-tile grid (env_map_upload,
+    // mgx_world_collisions.inc).  The robot-environment pass and the global planner each hold one
+    struct EnvMap {
         DevBuf<EnvCollider> colliders;
         DevBuf<float> verts;
         DevBuf<uint32_t> cell_ptr;
-        DevBuf<int32_t> cell_idx, touching;
+        DevBuf<int32_t> cell_idx;
+        EnvMapDev d{};
+        void release() { colliders.release(); verts.release(); cell_ptr.release(); cell_idx.release(); d = EnvMapDev{}; }
+    };
+    struct EnvCollisions : ContactBook {
+        EnvMap map;
+        DevBuf<int32_t> touching;
         EnvCollDev d{};
     } envcoll;
+    // the global planner (mgx_planner_enable / mgx_plan_paths, mgx_world_planner.inc): the map, and the trees of the last call
+    struct Planner {
+        bool enabled = false;
+        mgx_plan_params params{};  // defaults filled in
+        EnvMap map;
+        DevBuf<PlanState> state;
+        DevBuf<double> x, y, cost;
+        DevBuf<int32_t> parent, path;
+        DevBuf<float> out;
+        std::vector<PlanState> host_state;  // of the last mgx_plan_paths (mgx_plan_tree reads by it)
+    } planner;
     uint32_t last_sweep_launches = 0;  // sweep-kernel launches of the last mgx_iterate / mgx_tick call (mgx_last_launch_count)
     SweepRan last_sweep;               // the sweep instantiation it launched last (mgx_last_sweep) ...
     int32_t last_sweep_form = -1;      // ... and in which form (MGX_SWEEP_FORM_*; -1: none)

@@ -123,6 +123,9 @@ SYMBOLS = {
     "mgx_env_collisions_update": (C.c_int, [_V, C.c_void_p]),
     "mgx_env_collisions_read": (C.c_int, [_V, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     "mgx_env_collisions_clear": (C.c_int, [_V]),
+    "mgx_planner_enable": (C.c_int, [_V, C.POINTER(EnvDesc), C.c_void_p]),
+    "mgx_plan_paths": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "mgx_plan_tree": (C.c_int, [_V, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
     "mgx_robot_add": (C.c_int, [_V, C.POINTER(RobotDesc), C.POINTER(C.c_int32)]),
     "mgx_robot_remove": (C.c_int, [_V, C.c_int32]),
     "mgx_ir_connect": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_uint64]),
@@ -400,6 +403,29 @@ def env_collision_event_dtype():
     """numpy view of an array of mgx_env_collision_event"""
     import numpy as np
     return np.dtype([("pass", np.uint64), ("robot", np.int32), ("collider", np.int32), ("mins", np.float32, 2), ("maxs", np.float32, 2)])
+
+
+PLAN_OK, PLAN_MAX_ITERATIONS, PLAN_TREE_FULL = 0, 1, 2
+
+
+class PlanParams(C.Structure):
+    """mgx_plan_params (include/mgx.h)"""
+    _fields_ = [("step_size", C.c_float), ("neighbourhood_radius", C.c_float), ("collision_radius", C.c_float), ("max_iterations", C.c_uint32),
+                ("smoothing_enabled", C.c_int32), ("smoothing_max_iterations", C.c_uint32), ("smoothing_step", C.c_float),
+                ("sample_half_extent", C.c_float), ("max_nodes", C.c_uint32), ("iterations_per_launch", C.c_uint32)]
+
+
+def plan_request_dtype():
+    """numpy view of an array of mgx_plan_request"""
+    import numpy as np
+    return np.dtype([("start", np.float32, 2), ("end", np.float32, 2), ("wyrand_state", np.uint64)])
+
+
+def plan_result_dtype():
+    """numpy view of an array of mgx_plan_result"""
+    import numpy as np
+    return np.dtype([("status", np.int32), ("first_point", np.uint32), ("n_points", np.uint32), ("n_nodes", np.uint32), ("iterations", np.uint32),
+                     ("reserved", np.uint32), ("cost", np.float64), ("wyrand_state", np.uint64)])
 
 
 def env_colliders(env, fma=None):

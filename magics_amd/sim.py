@@ -13,8 +13,9 @@ by the frame's Update systems that matter to the path (the formation spawners):
 
 The reference runs its Update systems at the display's frame rate against virtual time, so the
 interleaving of spawns with fixed ticks is not reproducible there; here a frame is exactly one
-fixed tick long.  Rendering, picking, RRT* planning (`planning-strategy: rrt-star` is rejected) and goal areas are outside
-the path (SURVEY §8 out of scope).  Robot-environment collisions (planner/collisions.rs:368-438) are counted on request
+fixed tick long.  Rendering, picking and goal areas are outside the path (SURVEY §8 out of scope); RRT* planning
+(`planning-strategy: rrt-star`) is rejected unless a global planner is asked for (`global_planner=`: the engine's, or its host
+restatement, magics_amd/global_planner.py).  Robot-environment collisions (planner/collisions.rs:368-438) are counted on request
 (`environment_collisions=True`) against the map's colliders (hostlib.env_colliders) with the contact include/mgx.h
 specifies: parry2d's own shape queries are third party and absent, so contacts within rounding of tangency are not pinned.
 """
@@ -99,7 +100,7 @@ def _take_in(table, read, a, b, what):
 
 class Simulation:
     def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None,
-                 environment_collisions=False):
+                 environment_collisions=False, global_planner=None, planner_overrides=None):
         """scenario: `config.load_scenario(dir)` (or a dict of the same shape); world: a fresh
         World-like object created with `config.world_params(scenario["config"])`.
         device_missions (default: whenever the world offers them, i.e. the engine): routes, reached-when rules and
@@ -111,7 +112,15 @@ class Simulation:
         from its event log when somebody asks; otherwise _collide below runs on the host every tick (the checker).
         environment_collisions (default off: the export keeps 0 / []): True — robot-environment collisions are counted, on the
         device (mgx_env_collisions_*) whenever the missions live there, otherwise by _collide_environment on the host; "host" —
-        the host pass whatever the missions do (the checker of the device pass)."""
+        the host pass whatever the missions do (the checker of the device pass).
+        global_planner (default None: `planning-strategy: rrt-star` raises NotImplementedError): True — robots of that strategy spawn
+        Idle (RobotBundle::new, robot.rs:1195, 1294), their requests (taskpoints[0] -> taskpoints[1], a clone of the robot's forked
+        stream, config.rrt) are planned in the tick they spawn, all of a tick in ONE mgx_plan_paths, and the paths are applied by ONE
+        mgx_apply_global_paths at the start of the next tick — the earliest the reference's poll could see a result; "host" — the
+        same with the host restatement (the checker).  Both need an engine world with device missions.  A request that fails
+        leaves its robot Idle and is reported in the export; it is not retried (the reference retries with the same cloned
+        stream, which can only fail again).  planner_overrides: fields of global_planner.params that replace what config.rrt
+        gives (sample_half_extent, max_iterations ...)."""
         self.dev = hasattr(world, "mission_tick_begin") if device_missions is None else bool(device_missions)
         self._dev_coll = (self.dev and hasattr(world, "collisions_enable")) if device_collisions is None else bool(device_collisions)
         if self._dev_coll and not self.dev:
@@ -123,6 +132,12 @@ class Simulation:
         self._dev_env_coll = environment_collisions is True and self.dev and hasattr(world, "env_collisions_enable")
         self._env_coll_cursor = 0
         self._env_collisions = {}  # (robot, collider) -> {"colliding": bool, "times": int, "aabbs": [...]}
+        if global_planner not in (None, True, "host"):
+            raise ValueError('global_planner: None, True or "host"')
+        self._planner = global_planner
+        self._plan_requests = []   # (robot id, start, end, stream state) of the robots spawned in this tick
+        self._plans_ready = []     # (robot id, result) planned in the tick before: applied when the next one starts
+        self._plan_log = []        # per request: {"robot", "status", "n_nodes", "iterations", "n_points"}
         self._pending_track = None
         self._trk_log = []  # what _track noted since _tracks last ran
         self.name = scenario.get("name", "")
@@ -156,6 +171,12 @@ class Simulation:
             world.env_collisions_enable(self.env)
         elif self._env_coll:
             self._colliders, self._collider_vertices = hostlib.env_colliders(self.env)
+        if self._planner is not None:
+            from . import global_planner as _gp
+            self._plan_params = _gp.params_from_config(self.cfg, **(planner_overrides or {}))
+            _gp.check_params(self._plan_params)
+            if self._planner is True and self.dev and hasattr(world, "planner_enable"):
+                world.planner_enable(self.env, self._plan_params)
         self.entities = spawner.EntityAllocator()  # the robots' Entity bits = their graphs' order (id.rs:19-54)
 
     RESERVE_LIMIT = 256  # robots reserved at most for formations that repeat forever (beyond it the engine doubles its head-room)
@@ -180,11 +201,20 @@ class Simulation:
 
     # -- spawn_formation (spawner.rs:415-649) + RobotBundle::new (robot.rs:1134-1356) -------------------
     def _add_robot(self, desc, formation_index):
-        if desc["planning-strategy"] != "only-local":
-            raise NotImplementedError("planning-strategy rrt-star: the global planner is outside the hot path")
+        planned = desc["planning-strategy"] != "only-local"
+        if planned:
+            if self._planner is None:
+                raise NotImplementedError("planning-strategy rrt-star: the global planner is outside the hot path")
+            if not (self.dev and hasattr(self.w, "apply_global_paths") and (self._planner == "host" or hasattr(self.w, "planner_enable"))):
+                raise NotImplementedError("planning-strategy rrt-star: the global planner needs an engine world with device missions")
+            if len(desc["waypoints"]) > 2:
+                raise NotImplementedError("planning-strategy rrt-star: a mission of more than two taskpoints (its later legs are "
+                                          "planned when the earlier ones end) is not supported")
         rb = self.cfg["robot"]
         states = desc["waypoints"]
         mean0, prior, dt = robot_initial_state(states[0], states[1], desc["timesteps"], desc["radius"], rb["target-speed"], rb["planning-horizon"])
+        if planned:
+            mean0[:] = np.asarray(states[0], dtype=F).astype(np.float64)  # horizon state = start (robot.rs:1195)
         if self.K is None:
             self.K = len(desc["timesteps"])
         path = np.array([s[:2] for s in states], dtype=np.float32)  # the route's positions (robot.rs:1310-1315)
@@ -197,7 +227,7 @@ class Simulation:
                             "time_scale": float(self.dt32 / t0), "colour": desc["colour"], "rng": desc["rng"],
                             "strategy": desc["planning-strategy"], "reach": desc["waypoint-reached-when-intersects"],
                             "finish": desc["finished-when-intersects"], "positions": [], "velocities": [], "travelled": 0.0,
-                            "trk_elapsed": 0, "trk_prev": None, "entity": key})
+                            "trk_elapsed": 0, "trk_prev": None, "entity": key, "idle": planned})
         self._translation = np.vstack([self._translation, np.array([[states[0][0], -1.5, states[0][1]]], dtype=F)])  # spawner.rs:548
         if self.dev:
             me = self.robots[-1]
@@ -211,6 +241,10 @@ class Simulation:
             (rv, rd), (fv, fd) = rule(me["reach"]), rule(me["finish"])
             self.w.mission_set(rid, np.array([s_[:2] for s_ in states[1:]], dtype=np.float64), rv, fv, rd, fd,
                                self._translation[-1], me["time_scale"])
+            if planned:  # Mission::global (robot.rs:1294): Idle until a path has been found
+                self.w.set_idle(rid, True)
+                self._plan_requests.append((rid, tuple(float(v) for v in states[0][:2]), tuple(float(v) for v in states[1][:2]),
+                                            desc["rng"].state))
 
     @property
     def translation(self):
@@ -219,6 +253,42 @@ class Simulation:
             tr = self.w.mission_read()[0]
             self._translation[:len(tr)] = tr[:len(self._translation)]
         return self._translation
+
+    # -- progress_missions (robot.rs:578-633) + the path-finding completion handler (robot.rs:643-799) ----------------------
+    def _plan(self):
+        """the requests of the robots that spawned in this tick, in one call; what comes back waits for the next tick"""
+        reqs, self._plan_requests = self._plan_requests, []
+        if not reqs:
+            return
+        if self._planner == "host":
+            from . import global_planner as _gp
+            res = _gp.plan_paths(self.env, [q[1:] for q in reqs], self._plan_params)
+        else:
+            res = self.w.plan_paths([q[1:] for q in reqs])
+        self._plans_ready += [(q[0], r) for q, r in zip(reqs, res)]
+
+    def _apply_plans(self):
+        """the paths planned in the tick before: tracking path, variables, tracking factors, route and MissionState::Active of
+        every robot whose request succeeded, in one call"""
+        ready, self._plans_ready = self._plans_ready, []
+        if not ready:
+            return
+        from .driver import global_path_plan
+        rb = self.cfg["robot"]
+        ids, paths, means = [], [], []
+        for rid, r in ready:
+            self._plan_log.append({"robot": rid, "status": int(r["status"]), "n_nodes": int(r["n_nodes"]), "iterations": int(r["iterations"]),
+                                   "n_points": int(len(r["path"]))})
+            me = self.robots[rid]
+            if r["status"] != 0 or not me["alive"]:
+                continue
+            wps, m = global_path_plan(r["path"], rb["target-speed"], rb["planning-horizon"], self.K)
+            ids.append(rid)
+            paths.append(np.ascontiguousarray(wps[:, :2]))
+            means.append(m)
+            me["waypoints"], me["target"], me["idle"] = [w.copy() for w in wps], 1, False
+        if ids:
+            self.w.apply_global_paths(ids, paths, np.stack(means), reset_tracking=True, route=True, activate=True)
 
     def _spawn(self):
         for sp in self.spawners:
@@ -383,13 +453,15 @@ class Simulation:
             if self.failure_rate > 0.0:
                 ant = np.ones(len(self.robots), dtype=np.uint8)
                 ant[[r["id"] for r in live]] = active
-        moving = [r for r in live if not r["completed"]]
+        moving = [r for r in live if not r["completed"] and not r["idle"]]
         w.mission_tick_end(self.steps, float(self.max_speed), float(self.dt32), antennas=ant)
         self._pending_track = (moving, (self.tick_no + 1) * self.dt_ns * 1e-9, live)
 
     def tick(self):
         w = self.w
+        self._apply_plans()
         self._spawn()
+        self._plan()
         if self.robots and self.dev:
             self._tick_device()
         elif self.robots:
@@ -445,12 +517,14 @@ class Simulation:
         """One frame's Update (the spawners) and then every FixedUpdate up to the next frame in which a spawner acts, in one
         engine call: identical to tick() that many times — the per-tick bookkeeping (events, completions, trackers,
         collisions) is replayed from what the call returns per tick."""
+        self._apply_plans()
         self._spawn()
+        self._plan()
         if not self.robots:
             self.tick_no += 1
             return
         self._flush_trackers(synchronise=True)
-        m = 1 + (self._quiet_ticks(cap - 1) if cap > 1 else 0)
+        m = 1 + (self._quiet_ticks(cap - 1) if cap > 1 and not self._plans_ready else 0)  # (planned paths are applied one tick on)
         for _ in range(m - 1):  # the real spawners live through the same frames (nothing happens in them)
             for sp in self.spawners:
                 sp.tick(self.dt_ns)
@@ -469,7 +543,7 @@ class Simulation:
                     r["alive"] = False
                     self.entities.free(r["entity"])
             live = [r for r in self.robots if r["alive"]]
-            moving = [r for r in live if not r["completed"]]
+            moving = [r for r in live if not r["completed"] and not r["idle"]]
             tr = out["translations"][j]
             self._track(moving, tr, (self.tick_no + 1) * self.dt_ns * 1e-9)
             if not self._dev_coll:
@@ -516,7 +590,12 @@ class Simulation:
                 "mission": {"waypoints": [wps[0], wps[-1]], "started_at": r["started_at"], "finished_at": fin,
                             "routes": [{"waypoints": wps, "started_at": r["started_at"], "finished_at": fin}]},
                 "planning_strategy": r["strategy"], "color": r["colour"]}
-        return {"scenario": self.name, "makespan": self.elapsed(), "delta_t": float(self.dt32),
+        extra = {}
+        if self._planner is not None:  # what became of every path-finding request; a failed one left its robot Idle
+            from .global_planner import STATUS_NAMES as _PLAN_STATUS
+            extra["global_planner"] = {"requests": self._plan_log,
+                                       "failed": [{"robot": q["robot"], "status": _PLAN_STATUS[q["status"]]} for q in self._plan_log if q["status"] != 0]}
+        return {**extra, "scenario": self.name, "makespan": self.elapsed(), "delta_t": float(self.dt32),
                 "gbp": {"iterations": {"internal": sch["internal"], "external": sch["external"]}}, "robots": robots,
                 "prng_seed": self.cfg["simulation"]["prng-seed"], "config": self.cfg, "obstacles": {},
                 "collisions": {"robots": [{"robot_a": a, "robot_b": b, "aabbs": h["aabbs"]} for (a, b), h in sorted(collisions.items())],

@@ -494,6 +494,57 @@ class World:
     def env_collisions_clear(self):
         self._chk(self._L.mgx_env_collisions_clear(self._w))
 
+    # -- the global planner (include/mgx.h): batched RRT* over the map's colliders
+    def planner_enable(self, env, params=None):
+        """env: an environment dict — its colliders go to the device; params: a dict as global_planner.params makes it (the fields
+        of mgx_plan_params).  env None: off, every allocation is dropped."""
+        if env is None:
+            self._chk(self._L.mgx_planner_enable(self._w, None, None))
+            return
+        from .environment import _Desc
+        d = _Desc(env)
+        p = hostlib.PlanParams(float(params["step_size"]), float(params["neighbourhood_radius"]), float(params["collision_radius"]),
+                               int(params["max_iterations"]), 1 if params.get("smoothing_enabled") else 0,
+                               int(params.get("smoothing_max_iterations", 0)), float(params.get("smoothing_step", 0.0)),
+                               float(params.get("sample_half_extent", 0.0)), int(params.get("max_nodes", 0)),
+                               int(params.get("iterations_per_launch", 0)))
+        self._chk(self._L.mgx_planner_enable(self._w, C.byref(d.desc), C.byref(p)))
+
+    def plan_paths_raw(self, requests, point_capacity):
+        """mgx_plan_paths as it is: requests a structured array (hostlib.plan_request_dtype) -> (status code, results, points
+        [point_capacity, 2] f32, all points); nothing is raised"""
+        req = np.ascontiguousarray(requests, dtype=hostlib.plan_request_dtype())
+        res = np.zeros(len(req), hostlib.plan_result_dtype())
+        xy = np.full((max(int(point_capacity), 1), 2), np.nan, np.float32)
+        total = C.c_uint32(0)
+        rc = self._L.mgx_plan_paths(self._w, len(req), req.ctypes.data, res.ctypes.data, xy.ctypes.data, int(point_capacity), C.byref(total))
+        return rc, res, xy[:int(point_capacity)], int(total.value)
+
+    def plan_paths(self, requests):
+        """requests: [(start (x, y), end (x, y), wyrand_state)] -> one dict per request (status, n_nodes, iterations, cost,
+        wyrand_state, path [n, 2] f32 — empty unless the status is hostlib.PLAN_OK), as global_planner.plan_paths gives them.
+        One call, synchronous (mgx_plan_paths)."""
+        req = np.zeros(len(requests), hostlib.plan_request_dtype())
+        for i, (s, e, state) in enumerate(requests):
+            req["start"][i], req["end"][i], req["wyrand_state"][i] = s, e, int(state)
+        room = 256 * max(len(req), 1)
+        rc, res, xy, total = self.plan_paths_raw(req, room)
+        if rc < 0 and total > room:  # (the counts came back: once more with room for them)
+            rc, res, xy, total = self.plan_paths_raw(req, total)
+        self._chk(rc)
+        return [{"status": int(r["status"]), "n_nodes": int(r["n_nodes"]), "iterations": int(r["iterations"]), "cost": float(r["cost"]),
+                 "wyrand_state": int(r["wyrand_state"]), "path": xy[int(r["first_point"]):int(r["first_point"]) + int(r["n_points"])].copy()}
+                for r in res]
+
+    def plan_tree(self, request):
+        """(positions [n, 2] f64, parents [n], stored costs [n]) of a request of the last plan_paths (mgx_plan_tree)"""
+        n = C.c_uint32()
+        self._chk(self._L.mgx_plan_tree(self._w, int(request), 0, None, None, None, C.byref(n)))
+        xy, par, cost = np.zeros((n.value, 2)), np.zeros(n.value, np.int32), np.zeros(n.value)
+        if n.value:
+            self._chk(self._L.mgx_plan_tree(self._w, int(request), n.value, xy.ctypes.data, par.ctypes.data, cost.ctypes.data, C.byref(n)))
+        return xy, par, cost
+
     def set_resident_launches(self, enabled):
         """per-world switch: False keeps every schedule on the launch-per-segment path (mgx_set_resident_launches)"""
         self._chk(self._L.mgx_set_resident_launches(self._w, 2 if enabled == "decline" else 1 if enabled else 0))

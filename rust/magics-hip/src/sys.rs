@@ -159,6 +159,45 @@ pub struct mgx_env_collision_event {
     pub maxs: [f32; 2],
 }
 
+/// the global planner's parameters (include/mgx.h, mgx_planner_enable)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_plan_params {
+    pub step_size: f32,
+    pub neighbourhood_radius: f32,
+    pub collision_radius: f32,
+    pub max_iterations: u32,
+    pub smoothing_enabled: i32,
+    pub smoothing_max_iterations: u32,
+    pub smoothing_step: f32,
+    pub sample_half_extent: f32,
+    pub max_nodes: u32,
+    pub iterations_per_launch: u32,
+}
+
+/// one request of mgx_plan_paths
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_plan_request {
+    pub start: [f32; 2],
+    pub end: [f32; 2],
+    pub wyrand_state: u64,
+}
+
+/// what mgx_plan_paths says about one request
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_plan_result {
+    pub status: i32,
+    pub first_point: u32,
+    pub n_points: u32,
+    pub n_nodes: u32,
+    pub iterations: u32,
+    pub reserved: u32,
+    pub cost: f64,
+    pub wyrand_state: u64,
+}
+
 #[repr(C)]
 pub struct mgx_mvn { _private: [u8; 0] }
 #[repr(C)]
@@ -292,6 +331,9 @@ extern "C" {
     pub fn mgx_env_collisions_update(w: *mut mgx_world, positions_xyz: *const f32) -> c_int;
     pub fn mgx_env_collisions_read(w: *mut mgx_world, first: u64, events: *mut mgx_env_collision_event, capacity: u64, n_total: *mut u64, dropped: *mut u64, per_robot: *mut u32) -> c_int;
     pub fn mgx_env_collisions_clear(w: *mut mgx_world) -> c_int;
+    pub fn mgx_planner_enable(w: *mut mgx_world, env: *const mgx_env_desc, params: *const mgx_plan_params) -> c_int;
+    pub fn mgx_plan_paths(w: *mut mgx_world, n: u32, requests: *const mgx_plan_request, results: *mut mgx_plan_result, path_xy: *mut f32, point_capacity: u32, n_points: *mut u32) -> c_int;
+    pub fn mgx_plan_tree(w: *mut mgx_world, request: u32, capacity: u32, xy: *mut f64, parent: *mut i32, cost: *mut f64, n_nodes: *mut u32) -> c_int;
     pub fn mgx_schedule(kind: i32, n_internal: u8, n_external: u8, steps: *mut u8, capacity: u32) -> c_int;
     pub fn mgx_variable_timesteps(lookahead_horizon: u32, lookahead_multiple: u32, timesteps: *mut u32, capacity: u32) -> c_int;
 }

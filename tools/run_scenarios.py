@@ -1,7 +1,11 @@
 """Runs the reference's scenarios (parsed form: tests/golden/scenarios.json, or directories given on the command
 line) headless on the engine and prints what the reference's export would say about them: makespan, robots
 finished, distance travelled (with --environment-collisions also the robot-environment contacts, counted on the device).
-usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [scenario-dir | name ...]"""
+--global-planner [device|host] lets `planning-strategy: rrt-star` robots run: their paths come from the engine's planner (or its
+host restatement); --planner-half-extent H and --planner-max-iterations N replace the reference's +-2000 sampler and
+config.rrt.max-iterations.  Without it those scenarios are left out (named explicitly, they raise).
+usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [--global-planner [device|host]]
+           [--planner-half-extent H] [--planner-max-iterations N] [scenario-dir | name ...]"""
 import json
 import os
 import sys
@@ -19,14 +23,26 @@ if "--max-time" in args:
 env_collisions = "--environment-collisions" in args
 if env_collisions:
     args.remove("--environment-collisions")
+global_planner, overrides = None, {}
+if "--global-planner" in args:
+    i = args.index("--global-planner")
+    mode = args[i + 1] if i + 1 < len(args) and args[i + 1] in ("device", "host") else None
+    global_planner = "host" if mode == "host" else True
+    del args[i:i + (2 if mode else 1)]
+for flag, key, kind in (("--planner-half-extent", "sample_half_extent", float), ("--planner-max-iterations", "max_iterations", int)):
+    if flag in args:
+        i = args.index(flag)
+        overrides[key] = kind(args[i + 1])
+        del args[i:i + 2]
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 names = args or [n for n, sc in sorted(known.items())
-                 if all(f["planning-strategy"] == "only-local" for f in sc["formation"]["formations"]) and sum(f["robots"] for f in sc["formation"]["formations"])]
+                 if (global_planner or all(f["planning-strategy"] == "only-local" for f in sc["formation"]["formations"])) and sum(f["robots"] for f in sc["formation"]["formations"])]
 for name in names:
     sc = config.load_scenario(name) if os.path.isdir(name) else known[name]
     t0 = time.perf_counter()
-    s = sim.Simulation(sc, World(config.world_params(sc["config"])), environment_collisions=env_collisions)
+    s = sim.Simulation(sc, World(config.world_params(sc["config"])), environment_collisions=env_collisions,
+                       global_planner=global_planner, planner_overrides=overrides)
     s.run(max_time=max_time)
     wall = time.perf_counter() - t0
     done = [r for r in s.robots if r["completed"]]
@@ -36,4 +52,5 @@ for name in names:
                       "mean_distance": round(sum(trav) / max(1, len(trav)), 1),
                       "last_finish_s": round(max((r["finished_at"] for r in done), default=0.0), 1),
                       "topology_events": len(s.events),
+                      **({"plans": len(s._plan_log), "plans_failed": sum(q["status"] != 0 for q in s._plan_log)} if global_planner else {}),
                       **({"environment_collisions": sum(h["times"] for h in s.environment_collisions.values())} if env_collisions else {})}), flush=True)
