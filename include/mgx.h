@@ -975,7 +975,41 @@ int mgx_env_collisions_clear(mgx_world *w);
  *   MGX_ERR_INVALID and nothing is changed.  MGX_ERR_STATE while switched off and on a sharded world (one with ghosts).
  * mgx_plan_tree(w, request, capacity, xy, parent, cost, n_nodes): the tree of a request of the LAST mgx_plan_paths (for tests and
  *   tools): positions [.][2], parents (-1: the root) and stored costs of the first min(capacity, *n_nodes) nodes; any array
- *   may be NULL. */
+ *   may be NULL.
+ *
+ * PLANS THAT RIDE THE STREAM.  mgx_plan_paths holds its caller until every request has ended — tens of driver ticks.  The
+ *   reference starts a path-finding task and polls it once a frame while every other robot keeps ticking (robot.rs:578-799); these
+ *   calls are that: requests wait in a pool that outlives a call, a slice of iterations is ENQUEUED on the world's stream, and the
+ *   host hears which requests have ended from a completion log the launches append to in host-mapped memory.  A request's arrays
+ *   never move while it is pending (the pool grows by blocks of slots), and the plan is mgx_plan_paths' bit for bit: the same
+ *   slice of the same kernel code, and where the slices fall does not show.  Unsharded worlds, planner on.
+ * mgx_plan_submit(w, n, requests, tickets): queues the n requests and returns at once — nothing is launched, nothing waited for.
+ *   tickets[i] names request i: counted from 1 per world, never used twice (not after mgx_planner_enable(NULL) either).  Requests
+ *   already pending are not disturbed.  MGX_ERR_STATE: planner off, sharded world.  MGX_ERR_INVALID: NULL arguments, a non-finite
+ *   coordinate, more than 4096 requests pending — nothing is queued.
+ * mgx_plan_advance(w, iterations): enqueues ONE launch that gives every pending request that has not ended at most `iterations`
+ *   iterations (growth and smoothing iterations alike), one workgroup each, and does not wait.  Nothing pending: nothing is
+ *   launched.  iterations == 0: MGX_ERR_INVALID.  A request's SLICE NUMBER is the count of advances since it was submitted.
+ *   HOW MANY SLICES A REQUEST TAKES, with g its `iterations`, s its `smoothing_iterations` and B the budget of every advance:
+ *     MGX_PLAN_OK, MGX_PLAN_TREE_FULL: ceil((g + s) / B), and never less than 1 — the launch that makes the last iteration also
+ *       writes the points out: the finish takes no budget.
+ *     MGX_PLAN_MAX_ITERATIONS: max_iterations / B + 1 in integer division — the limit is seen at the top of an iteration that
+ *       still has budget, so a launch that ends exactly on the limit leaves the verdict to the next.
+ * mgx_planner_set_tick_budget(w, iterations): 0 (the default) is off.  Otherwise every mgx_mission_tick_end, and so every tick of
+ *   mgx_mission_run, ends by enqueuing one such slice behind its own launches when requests are pending — on the SAME stream: a
+ *   planner workgroup that ran beside the tick would hold a CU's LDS and make the residency census decline the tick's resident
+ *   launch.  A setting of the world: it survives mgx_planner_enable.
+ * mgx_plan_collect(w, flags, capacity, done, path_xy, point_capacity, n_done, n_points): hands out requests that have ended, in the
+ *   order of (slice number, ticket), each once.  done[i].result is what mgx_plan_paths returns for the request, first_point into
+ *   this call's path_xy.  flags 0: what the device has reported so far — it looks at the event behind the last slice
+ *   (hipEventQuery) and at the log, and never waits.  MGX_PLAN_WAIT: it first waits for the slices enqueued so far; it advances
+ *   nothing itself.  A request that does not fit into what is left of `done` or `path_xy` stays, with those behind it, for the
+ *   next call: MGX_OK, *n_done and *n_points say what came.  MGX_ERR_STATE: planner off.
+ * mgx_plan_cancel(w, ticket): the request will never be handed out (its robot was despawned while it waited); its slot is used
+ *   again once the slices in flight have completed.  MGX_ERR_INVALID: a ticket that is unknown, collected or cancelled.
+ * mgx_plan_pending(w, n): requests submitted and neither collected nor cancelled.
+ * mgx_planner_enable while requests are pending: env == NULL drops them with everything else; a new map is MGX_ERR_STATE and
+ *   changes nothing.  mgx_plan_paths and mgx_plan_tree work beside pending requests (they wait for the slices enqueued). */
 #define MGX_PLAN_OK 0
 #define MGX_PLAN_MAX_ITERATIONS 1
 #define MGX_PLAN_TREE_FULL 2
@@ -997,7 +1031,7 @@ typedef struct mgx_plan_result {
     int32_t status;                 /* MGX_PLAN_*                                                            */
     uint32_t first_point, n_points; /* into path_xy; 0 points unless status is MGX_PLAN_OK                   */
     uint32_t n_nodes, iterations;
-    uint32_t reserved;
+    uint32_t smoothing_iterations;  /* smoothing iterations made (a word that was reserved and 0)            */
     double cost;                    /* of the path before smoothing                                          */
     uint64_t wyrand_state;          /* the stream after the draws made                                       */
 } mgx_plan_result;
@@ -1006,6 +1040,20 @@ int mgx_plan_paths(mgx_world *w, uint32_t n, const mgx_plan_request *requests, m
                    uint32_t point_capacity, uint32_t *n_points);
 int mgx_plan_tree(mgx_world *w, uint32_t request, uint32_t capacity, double *xy, int32_t *parent, double *cost,
                   uint32_t *n_nodes);
+#define MGX_PLAN_WAIT 1u
+typedef struct mgx_plan_done {
+    uint64_t ticket;
+    uint32_t slices;                /* the slice number it ended in                                          */
+    uint32_t reserved;
+    mgx_plan_result result;
+} mgx_plan_done;
+int mgx_plan_submit(mgx_world *w, uint32_t n, const mgx_plan_request *requests, uint64_t *tickets);
+int mgx_plan_advance(mgx_world *w, uint32_t iterations);
+int mgx_planner_set_tick_budget(mgx_world *w, uint32_t iterations);
+int mgx_plan_collect(mgx_world *w, uint32_t flags, uint32_t capacity, mgx_plan_done *done, float *path_xy,
+                     uint32_t point_capacity, uint32_t *n_done, uint32_t *n_points);
+int mgx_plan_cancel(mgx_world *w, uint64_t ticket);
+int mgx_plan_pending(mgx_world *w, uint32_t *n);
 
 /* ---- host helpers (no device needed) --------------------------------------------------- */
 /* gbp_schedule: fills steps[max(n_int,n_ext)] with MGX_STEP_* bits. Returns the count

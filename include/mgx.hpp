@@ -325,6 +325,35 @@ public:
         out.path_xy.resize(total);
         return out;
     }
+    /// plans that ride the stream (mgx.h): submit returns tickets at once, advance enqueues one slice for every pending request,
+    /// collect hands out what has ended — in the order of (slice number, ticket), each once; wait = false never blocks
+    std::vector<uint64_t> plan_submit(const std::vector<mgx_plan_request> &requests) {
+        std::vector<uint64_t> tickets(requests.size());
+        check(mgx_plan_submit(w_, (uint32_t)requests.size(), requests.data(), tickets.data()));
+        return tickets;
+    }
+    void plan_advance(uint32_t iterations) { check(mgx_plan_advance(w_, iterations)); }
+    void planner_set_tick_budget(uint32_t iterations) { check(mgx_planner_set_tick_budget(w_, iterations)); }
+    struct PlansDone {
+        std::vector<mgx_plan_done> done;          ///< result.first_point .. + n_points index path_xy
+        std::vector<std::array<float, 2>> path_xy;
+    };
+    PlansDone plan_collect(bool wait = false, uint32_t capacity = 64, uint32_t point_capacity = 4096) {
+        PlansDone out;
+        out.done.resize(capacity);
+        out.path_xy.resize((size_t)point_capacity + 1);
+        uint32_t n_done = 0, n_points = 0;
+        check(mgx_plan_collect(w_, wait ? MGX_PLAN_WAIT : 0u, capacity, out.done.data(), out.path_xy[0].data(), point_capacity, &n_done, &n_points));
+        out.done.resize(n_done);
+        out.path_xy.resize(n_points);
+        return out;
+    }
+    void plan_cancel(uint64_t ticket) { check(mgx_plan_cancel(w_, ticket)); }
+    uint32_t plan_pending() {
+        uint32_t n = 0;
+        check(mgx_plan_pending(w_, &n));
+        return n;
+    }
     void synchronize() { check(mgx_synchronize(w_)); }
     uint32_t K() const { return K_; }
 

@@ -386,6 +386,35 @@ struct PlanDev {
     uint32_t budget;           // iterations (growth and smoothing together) one launch runs per request at the most
     int32_t smoothing;
 };
+// The pool of requests that ride the world's stream (k_plan_pool; the host's side: mgx_plan_pool.h, mgx_world_planner.inc).
+// Slots are allocated a block at a time and never move: a launch finds a slot's arrays through its block's base pointers.
+struct PlanBlockDev {          // slot 0 of the block; slot i follows at i * (the array's length per request)
+    double *x, *y, *cost;
+    int32_t *parent, *path;
+    float *out;                // host-mapped: the host reads an ended request's points in place
+    PlanState *state;          // host-mapped: written by the host at submit, read by it once the log names the request
+};
+struct PlanActive {            // one entry of a launch's compact list: a slot whose request has not ended
+    unsigned long long ticket;
+    uint32_t slot;
+    uint32_t first_seq;        // advances enqueued before the request was submitted (low word)
+};
+struct alignas(16) PlanLogEntry {  // the completion log: one entry per request, by the launch it ended in
+    unsigned long long ticket; // 0: not written yet (the host zeroes what it has taken)
+    uint32_t slices;           // the request's slice number of that launch
+    uint32_t slot;
+};
+static_assert(sizeof(PlanActive) == 16 && sizeof(PlanLogEntry) == 16, "one 16-byte load, one 16-byte store");
+struct PlanPoolDev {
+    const PlanBlockDev *blocks;  // host-mapped table, [MAX_BLOCKS]
+    const PlanActive *active;    // host-mapped, this launch's list
+    PlanLogEntry *log;           // host-mapped ring of log_cap entries
+    unsigned int *log_count;     // host-mapped: entries claimed so far
+    uint32_t log_cap;
+    uint32_t slots_per_block;
+    uint32_t seq;                // the number of this advance (low word): slice number = seq - first_seq
+    uint32_t reserved;
+};
 
 __host__ __device__ constexpr int frozen_words(int K) { return 40 * (K - 1) + 8 * (K - 2); }
 

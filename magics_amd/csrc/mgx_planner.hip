@@ -15,7 +15,8 @@
 // chord spreads its POINTS over the lanes (each lane walks its points' cells alone) and combines the same way.
 // A launch runs at most `budget` iterations per request (growth and smoothing iterations count alike) and leaves everything in
 // global memory — tree, counters, stream state, phase — so the host launches again until every request is done, and where the
-// slices fall does not show in the result.
+// slices fall does not show in the result.  Two launches share the slice (plan_slice): k_plan over the requests of one synchronous
+// call, k_plan_pool over the active slots of the pool whose requests ride the world's stream (mgx_plan_submit / _advance / _collect).
 // All planner arithmetic is f64 with every operation rounded on its own: contraction is switched off for this file whatever
 // the command line says, so libmgx.so and libmgx_fma.so hold the same code here.
 #include <hip/hip_runtime.h>
@@ -99,18 +100,27 @@ __device__ __forceinline__ double dist2(double ax, double ay, double bx, double 
     return dx * dx + dy * dy;
 }
 
-__global__ void __launch_bounds__(PLAN_BLOCK) k_plan(PlanDev c) {
+// One request's arrays, wherever they live: request `req` of a call's contiguous arrays (k_plan), or a slot of the pool (k_plan_pool).
+struct PlanSlot {
+    PlanState *state;
+    double *x, *y, *cost;  // [max_nodes]
+    int32_t *parent;       // [max_nodes]
+    int32_t *path;         // [max_nodes + 1]
+    float *out;            // [max_nodes + 1][2]
+};
+
+// One slice of one request by one workgroup.  True (in every lane) when the request ENDED in this slice.
+__device__ __forceinline__ bool plan_slice(const PlanDev &c, const PlanSlot &slot) {
     extern __shared__ double plan_lds[];  // X [max_nodes], Y [max_nodes]
     __shared__ PlanScratch sc;
     __shared__ uint32_t s_len;
     const int tid = (int)threadIdx.x;
-    const size_t req = blockIdx.x;
-    PlanState st = c.state[req];  // (the same in every lane, and kept so)
-    if (st.phase == PLAN_PHASE_DONE) return;
+    PlanState st = *slot.state;  // (the same in every lane, and kept so)
+    if (st.phase == PLAN_PHASE_DONE) return false;
     const uint32_t cap = c.max_nodes;
     double *const X = plan_lds, *const Y = plan_lds + cap;
-    double *const gx = c.x + req * cap, *const gy = c.y + req * cap, *const gcost = c.cost + req * cap;
-    int32_t *const gparent = c.parent + req * cap, *const gpath = c.path + req * ((size_t)cap + 1);
+    double *const gx = slot.x, *const gy = slot.y, *const gcost = slot.cost;
+    int32_t *const gparent = slot.parent, *const gpath = slot.path;
     const double ex = (double)st.end[0], ey = (double)st.end[1];
     if (st.phase == PLAN_PHASE_INIT) {
         if (tid == 0) {
@@ -239,7 +249,7 @@ __global__ void __launch_bounds__(PLAN_BLOCK) k_plan(PlanDev c) {
     }
 
     if (st.phase == PLAN_PHASE_FINISH) {
-        float *const out = c.out + 2 * req * ((size_t)cap + 1);
+        float *const out = slot.out;
         for (uint32_t i = (uint32_t)tid; i < st.path_len && i <= cap; i += PLAN_BLOCK) {
             const int k = gpath[i];
             out[2 * i] = (float)(k < 0 ? ex : X[k]);
@@ -248,19 +258,77 @@ __global__ void __launch_bounds__(PLAN_BLOCK) k_plan(PlanDev c) {
         st.status = MGX_PLAN_OK;
         st.phase = PLAN_PHASE_DONE;
     }
-    if (tid == 0) c.state[req] = st;
+    if (tid == 0) *slot.state = st;
+    return st.phase == PLAN_PHASE_DONE;
+}
+
+// mgx_plan_paths: workgroup = request of the call, the arrays of all requests contiguous
+__global__ void __launch_bounds__(PLAN_BLOCK) k_plan(PlanDev c) {
+    const size_t req = blockIdx.x, cap = c.max_nodes;
+    PlanSlot slot;
+    slot.state = c.state + req;
+    slot.x = c.x + req * cap; slot.y = c.y + req * cap; slot.cost = c.cost + req * cap;
+    slot.parent = c.parent + req * cap;
+    slot.path = c.path + req * (cap + 1);
+    slot.out = c.out + 2 * req * (cap + 1);
+    (void)plan_slice(c, slot);
+}
+
+// mgx_plan_advance: workgroup = entry of the compact list of active slots; a slot's arrays are found through its block's base
+// pointers (blocks never move while the pool lives).  State and points of a slot are in host-mapped memory, and so is the
+// completion log: a request that ends here makes its state and points visible to the host, then claims the next log entry (the one
+// atomic) and fills it with one 16-byte store.  The host takes an entry once its ticket is not 0 (tickets count from 1) and zeroes
+// it again, so a counter that is ahead of an entry's store only delays that entry to the next look.
+__global__ void __launch_bounds__(PLAN_BLOCK) k_plan_pool(PlanDev c, PlanPoolDev pool) {
+    const PlanActive a = pool.active[blockIdx.x];
+    const PlanBlockDev b = pool.blocks[a.slot / pool.slots_per_block];
+    const size_t i = a.slot % pool.slots_per_block, cap = c.max_nodes;
+    PlanSlot slot;
+    slot.state = b.state + i;
+    slot.x = b.x + i * cap; slot.y = b.y + i * cap; slot.cost = b.cost + i * cap;
+    slot.parent = b.parent + i * cap;
+    slot.path = b.path + i * (cap + 1);
+    slot.out = b.out + 2 * i * (cap + 1);
+    if (!plan_slice(c, slot)) return;
+    __threadfence_system();  // every lane: its points; lane 0: the state
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the fence's own wait is not relied on)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        __threadfence_system();
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned int at = atomicAdd_system(pool.log_count, 1u);
+        PlanLogEntry e;
+        e.ticket = a.ticket;
+        e.slices = pool.seq - a.first_seq;
+        e.slot = a.slot;
+        pool.log[at % pool.log_cap] = e;
+    }
+}
+
+static hipError_t plan_lds_grant(const void *kernel, size_t lds, size_t &granted) {
+    if (lds <= granted) return hipSuccess;  // dynamic LDS beyond 64 KiB has to be asked for once per size
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e == hipSuccess) granted = lds;
+    return e;
 }
 
 hipError_t launch_plan(const PlanDev &c, int n_requests, hipStream_t s) {
     if (n_requests <= 0) return hipSuccess;
-    static size_t granted = 0;  // dynamic LDS beyond 64 KiB has to be asked for once per size
+    static size_t granted = 0;
     const size_t lds = sizeof(double) * 2 * (size_t)c.max_nodes;
-    if (lds > granted) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_plan), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        granted = lds;
-    }
+    const hipError_t e = plan_lds_grant(reinterpret_cast<const void *>(k_plan), lds, granted);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_plan, dim3((unsigned)n_requests), dim3(PLAN_BLOCK), lds, s, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s) {
+    if (n_active <= 0) return hipSuccess;
+    static size_t granted = 0;
+    const size_t lds = sizeof(double) * 2 * (size_t)c.max_nodes;
+    const hipError_t e = plan_lds_grant(reinterpret_cast<const void *>(k_plan_pool), lds, granted);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_plan_pool, dim3((unsigned)n_active), dim3(PLAN_BLOCK), lds, s, c, pool);
     return hipGetLastError();
 }
 

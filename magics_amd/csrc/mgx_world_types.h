@@ -21,6 +21,7 @@
 #include "mgx_dev.h"
 #include "mgx_grid.h"
 #include "mgx_search.h"  // the neighbour search: its dispatch, its pure helpers, the launchers of mgx_topology.hip
+#include "mgx_plan_pool.h"  // the global planner's pool of pending requests: slots, tickets, the order they are handed out in
 #include "mgx_resident.h"  // resident launches, the host's arithmetic: segments, plan bytes, parity and segment count, back-off, riding updates
 
 namespace mgx {
@@ -79,6 +80,7 @@ hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s);
 hipError_t launch_env_collisions_pass(const EnvCollDev &c, hipStream_t s);
 // mgx_planner.hip
 hipError_t launch_plan(const PlanDev &c, int n_requests, hipStream_t s);
+hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s);
 }  // namespace mgx
 
 using namespace mgx;
@@ -793,6 +795,42 @@ struct mgx_world {
         DevBuf<int32_t> parent, path;
         DevBuf<float> out;
         std::vector<PlanState> host_state;  // of the last mgx_plan_paths (mgx_plan_tree reads by it)
+        // the requests that ride the stream (mgx_plan_submit / _advance / _collect): bookkeeping in `book` (mgx_plan_pool.h), the
+        // slots' arrays a block at a time — trees and node paths in device memory, states and points host-mapped — so that nothing
+        // a pending request uses ever moves; the table of blocks, the completion log and the launches' active lists are host-mapped
+        struct Pool {
+            static constexpr uint32_t LOG_CAP = 2 * PlanPoolBook::MAX_SLOTS;  // (more than can be unread: one entry per slot's tenant)
+            PlanPoolBook book;
+            struct Block { void *dev = nullptr; PlanState *state = nullptr; float *out = nullptr; };  // state, out: one host allocation
+            std::vector<Block> blocks;
+            PlanBlockDev *table = nullptr;   // [MAX_BLOCKS]
+            PlanLogEntry *log = nullptr;     // [LOG_CAP], then the counter
+            unsigned int *log_count = nullptr;
+            uint64_t log_taken = 0;
+            struct List { PlanActive *p = nullptr; size_t cap = 0; uint64_t last_seq = 0; };  // last_seq: the last advance that reads it
+            std::vector<List> lists;
+            int cur = -1;                    // the list the running slots were last written to
+            uint32_t cur_n = 0;
+            hipEvent_t ev = nullptr;         // behind the last slice
+            uint64_t ev_seq = 0;
+            uint32_t tick_budget = 0;        // mgx_planner_set_tick_budget (a setting of the world: release keeps it)
+            Pool() = default;
+            Pool(const Pool &) = delete;
+            Pool &operator=(const Pool &) = delete;
+            ~Pool() { release(); }
+            void release() {  // (the caller has synchronised the stream)
+                for (Block &b : blocks) { if (b.dev) (void)hipFree(b.dev); if (b.state) (void)hipHostFree(b.state); }
+                blocks.clear();
+                for (List &l : lists) if (l.p) (void)hipHostFree(l.p);
+                lists.clear();
+                if (table) (void)hipHostFree(table);
+                if (log) (void)hipHostFree(log);
+                if (ev) (void)hipEventDestroy(ev);
+                table = nullptr; log = nullptr; log_count = nullptr; ev = nullptr;
+                log_taken = 0; cur = -1; cur_n = 0; ev_seq = 0;
+                book.drop();
+            }
+        } pool;
     } planner;
     uint32_t last_sweep_launches = 0;  // sweep-kernel launches of the last mgx_iterate / mgx_tick call (mgx_last_launch_count)
     SweepRan last_sweep;               // the sweep instantiation it launched last (mgx_last_sweep) ...

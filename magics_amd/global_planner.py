@@ -148,7 +148,7 @@ class Planner:
             if math.sqrt(gx * gx + gy * gy) <= step:
                 goal, status = m, PLAN_OK
                 break
-        out = {"status": status, "n_nodes": n, "iterations": it if status != PLAN_MAX_ITERATIONS else p["max_iterations"], "cost": 0.0,
+        out = {"status": status, "n_nodes": n, "smoothing_iterations": 0, "iterations": it if status != PLAN_MAX_ITERATIONS else p["max_iterations"], "cost": 0.0,
                "path": np.zeros((0, 2), F), "rewires": rewires, "tree": (np.stack([X[:n], Y[:n]], axis=1), P[:n].copy(), C[:n].copy())}
         if status == PLAN_OK:
             gx, gy = float(X[goal]) - ex, float(Y[goal]) - ey
@@ -162,7 +162,7 @@ class Planner:
             pts = [(float(X[k]), float(Y[k])) for k in reversed(chain)] + [(ex, ey)]
             out["unsmoothed"] = np.array(pts, dtype=np.float64)
             if p["smoothing_enabled"]:
-                pts = self._smooth(pts, rng)
+                pts, out["smoothing_iterations"] = self._smooth(pts, rng)
             out["path64"] = np.array(pts, dtype=np.float64)
             out["path"] = out["path64"].astype(F)
         out["wyrand_state"], out["draws"] = rng.state, rng.draws
@@ -184,7 +184,7 @@ class Planner:
             if self.feasible(self.chord_points(pts[a], pts[b])).all():
                 del pts[a + 1:b]
             s += 1
-        return pts
+        return pts, s
 
 
 def plan_paths(env, requests, p, fma=None):
@@ -192,3 +192,18 @@ def plan_paths(env, requests, p, fma=None):
     wyrand_state, path [n, 2] f32 — empty unless status is PLAN_OK —, tree, rewires, draws)"""
     pl = Planner(env, p, fma)
     return [pl.plan(s, e, st) for s, e, st in requests]
+
+
+def slices_needed(result, p, budget):
+    """The slice number a request ends in when every advance gives it `budget` iterations (include/mgx.h, mgx_plan_advance):
+    PLAN_OK and PLAN_TREE_FULL: ceil((iterations + smoothing_iterations) / budget), never less than 1 — the finish takes no budget;
+    PLAN_MAX_ITERATIONS: max_iterations // budget + 1 — the limit is seen at the top of an iteration that still has budget."""
+    budget = int(budget)
+    if budget <= 0:
+        raise ValueError("the budget of a slice is positive")
+    if result["status"] == PLAN_MAX_ITERATIONS:
+        return int(p["max_iterations"]) // budget + 1
+    if result["status"] not in (PLAN_OK, PLAN_TREE_FULL):
+        raise ValueError("unknown status %r" % (result["status"],))
+    done = int(result["iterations"]) + int(result["smoothing_iterations"])
+    return max(1, -(-done // budget))

@@ -126,6 +126,12 @@ SYMBOLS = {
     "mgx_planner_enable": (C.c_int, [_V, C.POINTER(EnvDesc), C.c_void_p]),
     "mgx_plan_paths": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_plan_tree": (C.c_int, [_V, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "mgx_plan_submit": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mgx_plan_advance": (C.c_int, [_V, C.c_uint32]),
+    "mgx_planner_set_tick_budget": (C.c_int, [_V, C.c_uint32]),
+    "mgx_plan_collect": (C.c_int, [_V, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "mgx_plan_cancel": (C.c_int, [_V, C.c_uint64]),
+    "mgx_plan_pending": (C.c_int, [_V, C.POINTER(C.c_uint32)]),
     "mgx_robot_add": (C.c_int, [_V, C.POINTER(RobotDesc), C.POINTER(C.c_int32)]),
     "mgx_robot_remove": (C.c_int, [_V, C.c_int32]),
     "mgx_ir_connect": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_uint64]),
@@ -425,7 +431,16 @@ def plan_result_dtype():
     """numpy view of an array of mgx_plan_result"""
     import numpy as np
     return np.dtype([("status", np.int32), ("first_point", np.uint32), ("n_points", np.uint32), ("n_nodes", np.uint32), ("iterations", np.uint32),
-                     ("reserved", np.uint32), ("cost", np.float64), ("wyrand_state", np.uint64)])
+                     ("smoothing_iterations", np.uint32), ("cost", np.float64), ("wyrand_state", np.uint64)])
+
+
+PLAN_WAIT = 1  # MGX_PLAN_WAIT
+
+
+def plan_done_dtype():
+    """numpy view of an array of mgx_plan_done"""
+    import numpy as np
+    return np.dtype([("ticket", np.uint64), ("slices", np.uint32), ("reserved", np.uint32), ("result", plan_result_dtype())])
 
 
 def env_colliders(env, fma=None):

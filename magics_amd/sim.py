@@ -100,7 +100,7 @@ def _take_in(table, read, a, b, what):
 
 class Simulation:
     def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None,
-                 environment_collisions=False, global_planner=None, planner_overrides=None):
+                 environment_collisions=False, global_planner=None, planner_overrides=None, plan_budget=64):
         """scenario: `config.load_scenario(dir)` (or a dict of the same shape); world: a fresh
         World-like object created with `config.world_params(scenario["config"])`.
         device_missions (default: whenever the world offers them, i.e. the engine): routes, reached-when rules and
@@ -120,7 +120,16 @@ class Simulation:
         same with the host restatement (the checker).  Both need an engine world with device missions.  A request that fails
         leaves its robot Idle and is reported in the export; it is not retried (the reference retries with the same cloned
         stream, which can only fail again).  planner_overrides: fields of global_planner.params that replace what config.rrt
-        gives (sample_half_extent, max_iterations ...)."""
+        gives (sample_half_extent, max_iterations ...).
+        global_planner "sliced": the engine's planner, but a plan rides the ticks instead of holding one up (mgx_plan_submit /
+        _collect, mgx_planner_set_tick_budget): the requests are submitted in the tick their robots spawn, every tick ends with one
+        slice of at most plan_budget iterations per pending request (default 64: about 160 us of device time at the 2.5 us an
+        iteration was measured at outside a tick), and the start of a tick collects — waiting for the slices enqueued, so that
+        the tick a path arrives in depends on the request and the budget and not on timing — and applies what has ended: a
+        request that takes s slices activates its robot at the start of tick s after the one it spawned in (True: tick 1).
+        A robot despawned while it waits has its request cancelled; a request that FAILS is submitted again with the stream
+        state its result carries (the reference's "try again"), and every attempt is in the export.  While requests are pending
+        run() goes tick by tick."""
         self.dev = hasattr(world, "mission_tick_begin") if device_missions is None else bool(device_missions)
         self._dev_coll = (self.dev and hasattr(world, "collisions_enable")) if device_collisions is None else bool(device_collisions)
         if self._dev_coll and not self.dev:
@@ -132,9 +141,14 @@ class Simulation:
         self._dev_env_coll = environment_collisions is True and self.dev and hasattr(world, "env_collisions_enable")
         self._env_coll_cursor = 0
         self._env_collisions = {}  # (robot, collider) -> {"colliding": bool, "times": int, "aabbs": [...]}
-        if global_planner not in (None, True, "host"):
-            raise ValueError('global_planner: None, True or "host"')
+        if global_planner not in (None, True, "host", "sliced"):
+            raise ValueError('global_planner: None, True, "host" or "sliced"')
+        if isinstance(plan_budget, bool) or int(plan_budget) != plan_budget or plan_budget <= 0:
+            raise ValueError("plan_budget: a positive count of iterations")
         self._planner = global_planner
+        self._sliced = global_planner == "sliced"
+        self._plan_budget = int(plan_budget)
+        self._plan_tickets = {}    # sliced: ticket -> (robot id, start, end) of the requests that ride the ticks
         self._plan_requests = []   # (robot id, start, end, stream state) of the robots spawned in this tick
         self._plans_ready = []     # (robot id, result) planned in the tick before: applied when the next one starts
         self._plan_log = []        # per request: {"robot", "status", "n_nodes", "iterations", "n_points"}
@@ -175,8 +189,12 @@ class Simulation:
             from . import global_planner as _gp
             self._plan_params = _gp.params_from_config(self.cfg, **(planner_overrides or {}))
             _gp.check_params(self._plan_params)
-            if self._planner is True and self.dev and hasattr(world, "planner_enable"):
+            if (self._planner is True or self._sliced) and self.dev and hasattr(world, "planner_enable"):
                 world.planner_enable(self.env, self._plan_params)
+            if self._sliced:
+                if not (self.dev and hasattr(world, "plan_submit")):
+                    raise NotImplementedError('global_planner "sliced" needs an engine world with device missions')
+                world.planner_set_tick_budget(self._plan_budget)
         self.entities = spawner.EntityAllocator()  # the robots' Entity bits = their graphs' order (id.rs:19-54)
 
     RESERVE_LIMIT = 256  # robots reserved at most for formations that repeat forever (beyond it the engine doubles its head-room)
@@ -260,6 +278,10 @@ class Simulation:
         reqs, self._plan_requests = self._plan_requests, []
         if not reqs:
             return
+        if self._sliced:
+            for q, t in zip(reqs, self.w.plan_submit([q[1:] for q in reqs])):
+                self._plan_tickets[t] = q[:3]
+            return
         if self._planner == "host":
             from . import global_planner as _gp
             res = _gp.plan_paths(self.env, [q[1:] for q in reqs], self._plan_params)
@@ -270,6 +292,8 @@ class Simulation:
     def _apply_plans(self):
         """the paths planned in the tick before: tracking path, variables, tracking factors, route and MissionState::Active of
         every robot whose request succeeded, in one call"""
+        if self._plan_tickets:
+            self._collect_plans()
         ready, self._plans_ready = self._plans_ready, []
         if not ready:
             return
@@ -289,6 +313,24 @@ class Simulation:
             me["waypoints"], me["target"], me["idle"] = [w.copy() for w in wps], 1, False
         if ids:
             self.w.apply_global_paths(ids, paths, np.stack(means), reset_tracking=True, route=True, activate=True)
+
+    def _collect_plans(self):
+        """sliced: the requests that have ended by the slices enqueued so far -> _plans_ready; a robot that is gone has its
+        request cancelled, a request that failed goes in again with the stream where the attempt left it"""
+        for t in [t for t, q in self._plan_tickets.items() if not self.robots[q[0]]["alive"]]:
+            self.w.plan_cancel(t)
+            del self._plan_tickets[t]
+        again = []
+        while self._plan_tickets:
+            done = self.w.plan_collect(wait=True, capacity=len(self._plan_tickets))
+            if not done:
+                break
+            for r in done:
+                rid, start, end = self._plan_tickets.pop(r["ticket"])
+                self._plans_ready.append((rid, r))
+                if r["status"] != 0:
+                    again.append((rid, start, end, r["wyrand_state"]))
+        self._plan_requests += again  # (submitted by this tick's _plan, with the robots that spawn in it)
 
     def _spawn(self):
         for sp in self.spawners:
@@ -524,7 +566,8 @@ class Simulation:
             self.tick_no += 1
             return
         self._flush_trackers(synchronise=True)
-        m = 1 + (self._quiet_ticks(cap - 1) if cap > 1 and not self._plans_ready else 0)  # (planned paths are applied one tick on)
+        # (planned paths are applied one tick on; a pending plan is looked for at the start of every tick)
+        m = 1 + (self._quiet_ticks(cap - 1) if cap > 1 and not self._plans_ready and not self._plan_tickets else 0)
         for _ in range(m - 1):  # the real spawners live through the same frames (nothing happens in them)
             for sp in self.spawners:
                 sp.tick(self.dt_ns)

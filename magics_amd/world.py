@@ -532,9 +532,58 @@ class World:
         if rc < 0 and total > room:  # (the counts came back: once more with room for them)
             rc, res, xy, total = self.plan_paths_raw(req, total)
         self._chk(rc)
-        return [{"status": int(r["status"]), "n_nodes": int(r["n_nodes"]), "iterations": int(r["iterations"]), "cost": float(r["cost"]),
+        return [{"status": int(r["status"]), "n_nodes": int(r["n_nodes"]), "iterations": int(r["iterations"]),
+                 "smoothing_iterations": int(r["smoothing_iterations"]), "cost": float(r["cost"]),
                  "wyrand_state": int(r["wyrand_state"]), "path": xy[int(r["first_point"]):int(r["first_point"]) + int(r["n_points"])].copy()}
                 for r in res]
+
+    # plans that ride the stream (include/mgx.h): submit returns at once, advance enqueues one slice, collect hands out what ended
+    def plan_submit(self, requests):
+        """requests: [(start (x, y), end (x, y), wyrand_state)] -> their tickets (mgx_plan_submit: nothing is launched or waited for)"""
+        req = np.zeros(len(requests), hostlib.plan_request_dtype())
+        for i, (s, e, state) in enumerate(requests):
+            req["start"][i], req["end"][i], req["wyrand_state"][i] = s, e, int(state)
+        tickets = np.zeros(len(req), np.uint64)
+        self._chk(self._L.mgx_plan_submit(self._w, len(req), req.ctypes.data, tickets.ctypes.data))
+        return [int(t) for t in tickets]
+
+    def plan_advance(self, iterations):
+        """one slice of at most `iterations` iterations for every pending request, enqueued on the world's stream (mgx_plan_advance)"""
+        self._chk(self._L.mgx_plan_advance(self._w, int(iterations)))
+
+    def planner_set_tick_budget(self, iterations):
+        """0: off; otherwise every mission tick ends by enqueuing one such slice when requests are pending"""
+        self._chk(self._L.mgx_planner_set_tick_budget(self._w, int(iterations)))
+
+    def plan_collect(self, wait=False, capacity=64, point_capacity=None):
+        """The requests that have ended, in the order of (slice number, ticket), each once: one dict per request as plan_paths gives
+        them, with `ticket`, `slices` and `smoothing_iterations` beside.  wait: first wait for the slices enqueued so far
+        (MGX_PLAN_WAIT); otherwise the call never blocks.  What does not fit into capacity / point_capacity stays for the next call."""
+        capacity = int(capacity)
+        room = 256 * max(capacity, 1) if point_capacity is None else int(point_capacity)
+        done = np.zeros(max(capacity, 1), hostlib.plan_done_dtype())
+        xy = np.full((max(room, 1), 2), np.nan, np.float32)
+        nd, npts = C.c_uint32(0), C.c_uint32(0)
+        self._chk(self._L.mgx_plan_collect(self._w, hostlib.PLAN_WAIT if wait else 0, capacity, done.ctypes.data, xy.ctypes.data, room,
+                                           C.byref(nd), C.byref(npts)))
+        out = []
+        for d in done[:nd.value]:
+            r = d["result"]
+            out.append({"ticket": int(d["ticket"]), "slices": int(d["slices"]), "status": int(r["status"]), "n_nodes": int(r["n_nodes"]),
+                        "iterations": int(r["iterations"]), "smoothing_iterations": int(r["smoothing_iterations"]), "cost": float(r["cost"]),
+                        "wyrand_state": int(r["wyrand_state"]),
+                        "path": xy[int(r["first_point"]):int(r["first_point"]) + int(r["n_points"])].copy()})
+        return out
+
+    def plan_cancel(self, ticket):
+        """the request is never handed out (mgx_plan_cancel); an unknown, collected or cancelled ticket raises"""
+        self._chk(self._L.mgx_plan_cancel(self._w, int(ticket)))
+
+    def plan_pending(self):
+        """requests submitted and neither collected nor cancelled"""
+        n = C.c_uint32(0)
+        self._chk(self._L.mgx_plan_pending(self._w, C.byref(n)))
+        return int(n.value)
 
     def plan_tree(self, request):
         """(positions [n, 2] f64, parents [n], stored costs [n]) of a request of the last plan_paths (mgx_plan_tree)"""

@@ -178,6 +178,46 @@ impl World {
         assert!(robots.len() == vars.len() && vars.len() == means.len());
         check(unsafe { sys::mgx_change_priors(self.raw, robots.len() as u32, robots.as_ptr(), vars.as_ptr(), means.as_ptr().cast()) })
     }
+    /// Plans that ride the stream (include/mgx.h): what `progress_missions` does with its path-finding task (robot.rs:578-799).
+    /// Queues the requests and returns their tickets at once; nothing is launched.
+    pub fn plan_submit(&self, requests: &[sys::mgx_plan_request]) -> Result<Vec<u64>, MgxError> {
+        let mut tickets = vec![0u64; requests.len()];
+        check(unsafe { sys::mgx_plan_submit(self.raw, requests.len() as u32, requests.as_ptr(), tickets.as_mut_ptr()) })?;
+        Ok(tickets)
+    }
+    /// One slice of at most `iterations` iterations for every pending request, enqueued on the world's stream; does not wait.
+    pub fn plan_advance(&self, iterations: u32) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_plan_advance(self.raw, iterations) })
+    }
+    /// 0: off; otherwise every mission tick ends by enqueuing one such slice when requests are pending.
+    pub fn planner_set_tick_budget(&self, iterations: u32) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_planner_set_tick_budget(self.raw, iterations) })
+    }
+    /// The requests that have ended, in the order of (slice number, ticket), each once, with their points: at most `capacity`
+    /// requests and `point_capacity` points, the rest stays.  `wait`: first wait for the slices enqueued so far (the per-frame
+    /// poll passes false and never blocks).
+    pub fn plan_collect(&self, wait: bool, capacity: u32, point_capacity: u32) -> Result<(Vec<sys::mgx_plan_done>, Vec<[f32; 2]>), MgxError> {
+        let mut done: Vec<sys::mgx_plan_done> = Vec::with_capacity(capacity as usize);
+        let mut xy = vec![[0f32; 2]; point_capacity as usize];
+        let (mut n_done, mut n_points) = (0u32, 0u32);
+        check(unsafe {
+            sys::mgx_plan_collect(self.raw, if wait { sys::MGX_PLAN_WAIT } else { 0 }, capacity, done.as_mut_ptr(), xy.as_mut_ptr().cast(),
+                                  point_capacity, &mut n_done, &mut n_points)
+        })?;
+        unsafe { done.set_len(n_done as usize) };
+        xy.truncate(n_points as usize);
+        Ok((done, xy))
+    }
+    /// The robot was despawned while it waited: the request is never handed out.
+    pub fn plan_cancel(&self, ticket: u64) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_plan_cancel(self.raw, ticket) })
+    }
+    /// Requests submitted and neither collected nor cancelled.
+    pub fn plan_pending(&self) -> Result<u32, MgxError> {
+        let mut n = 0u32;
+        check(unsafe { sys::mgx_plan_pending(self.raw, &mut n) })?;
+        Ok(n)
+    }
 }
 
 /// Owner rank of every robot for a node of `n_ranks` GPUs (`mgx_shard_partition`: equal-count strips in (y, x) order).

@@ -193,9 +193,22 @@ pub struct mgx_plan_result {
     pub n_points: u32,
     pub n_nodes: u32,
     pub iterations: u32,
-    pub reserved: u32,
+    pub smoothing_iterations: u32,
     pub cost: f64,
     pub wyrand_state: u64,
+}
+
+/// mgx_plan_collect: first wait for the slices enqueued so far
+pub const MGX_PLAN_WAIT: u32 = 1;
+
+/// one ended request of mgx_plan_collect
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_plan_done {
+    pub ticket: u64,
+    pub slices: u32,
+    pub reserved: u32,
+    pub result: mgx_plan_result,
 }
 
 #[repr(C)]
@@ -334,6 +347,12 @@ extern "C" {
     pub fn mgx_planner_enable(w: *mut mgx_world, env: *const mgx_env_desc, params: *const mgx_plan_params) -> c_int;
     pub fn mgx_plan_paths(w: *mut mgx_world, n: u32, requests: *const mgx_plan_request, results: *mut mgx_plan_result, path_xy: *mut f32, point_capacity: u32, n_points: *mut u32) -> c_int;
     pub fn mgx_plan_tree(w: *mut mgx_world, request: u32, capacity: u32, xy: *mut f64, parent: *mut i32, cost: *mut f64, n_nodes: *mut u32) -> c_int;
+    pub fn mgx_plan_submit(w: *mut mgx_world, n: u32, requests: *const mgx_plan_request, tickets: *mut u64) -> c_int;
+    pub fn mgx_plan_advance(w: *mut mgx_world, iterations: u32) -> c_int;
+    pub fn mgx_planner_set_tick_budget(w: *mut mgx_world, iterations: u32) -> c_int;
+    pub fn mgx_plan_collect(w: *mut mgx_world, flags: u32, capacity: u32, done: *mut mgx_plan_done, path_xy: *mut f32, point_capacity: u32, n_done: *mut u32, n_points: *mut u32) -> c_int;
+    pub fn mgx_plan_cancel(w: *mut mgx_world, ticket: u64) -> c_int;
+    pub fn mgx_plan_pending(w: *mut mgx_world, n: *mut u32) -> c_int;
     pub fn mgx_schedule(kind: i32, n_internal: u8, n_external: u8, steps: *mut u8, capacity: u32) -> c_int;
     pub fn mgx_variable_timesteps(lookahead_horizon: u32, lookahead_multiple: u32, timesteps: *mut u32, capacity: u32) -> c_int;
 }

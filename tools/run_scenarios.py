@@ -1,11 +1,12 @@
 """Runs the reference's scenarios (parsed form: tests/golden/scenarios.json, or directories given on the command
 line) headless on the engine and prints what the reference's export would say about them: makespan, robots
 finished, distance travelled (with --environment-collisions also the robot-environment contacts, counted on the device).
---global-planner [device|host] lets `planning-strategy: rrt-star` robots run: their paths come from the engine's planner (or its
-host restatement); --planner-half-extent H and --planner-max-iterations N replace the reference's +-2000 sampler and
+--global-planner [device|host|sliced] lets `planning-strategy: rrt-star` robots run: their paths come from the engine's planner (or its
+host restatement; sliced: the engine's planner with the plans riding the ticks, --plan-budget N iterations per tick and request,
+default 64); --planner-half-extent H and --planner-max-iterations N replace the reference's +-2000 sampler and
 config.rrt.max-iterations.  Without it those scenarios are left out (named explicitly, they raise).
-usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [--global-planner [device|host]]
-           [--planner-half-extent H] [--planner-max-iterations N] [scenario-dir | name ...]"""
+usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [--global-planner [device|host|sliced]]
+           [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N] [scenario-dir | name ...]"""
 import json
 import os
 import sys
@@ -26,9 +27,14 @@ if env_collisions:
 global_planner, overrides = None, {}
 if "--global-planner" in args:
     i = args.index("--global-planner")
-    mode = args[i + 1] if i + 1 < len(args) and args[i + 1] in ("device", "host") else None
-    global_planner = "host" if mode == "host" else True
+    mode = args[i + 1] if i + 1 < len(args) and args[i + 1] in ("device", "host", "sliced") else None
+    global_planner = mode if mode in ("host", "sliced") else True
     del args[i:i + (2 if mode else 1)]
+plan_budget = 64
+if "--plan-budget" in args:
+    i = args.index("--plan-budget")
+    plan_budget = int(args[i + 1])
+    del args[i:i + 2]
 for flag, key, kind in (("--planner-half-extent", "sample_half_extent", float), ("--planner-max-iterations", "max_iterations", int)):
     if flag in args:
         i = args.index(flag)
@@ -42,7 +48,7 @@ for name in names:
     sc = config.load_scenario(name) if os.path.isdir(name) else known[name]
     t0 = time.perf_counter()
     s = sim.Simulation(sc, World(config.world_params(sc["config"])), environment_collisions=env_collisions,
-                       global_planner=global_planner, planner_overrides=overrides)
+                       global_planner=global_planner, planner_overrides=overrides, plan_budget=plan_budget)
     s.run(max_time=max_time)
     wall = time.perf_counter() - t0
     done = [r for r in s.robots if r["completed"]]
