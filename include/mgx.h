@@ -968,7 +968,11 @@ int mgx_env_collisions_clear(mgx_world *w);
  * mgx_plan_paths(w, n, requests, results, path_xy, point_capacity, n_points): plans the n requests, synchronously (like every
  *   other call it first ends a lingering launch).  One workgroup per request; a launch runs at most iterations_per_launch
  *   iterations of every request (growth and smoothing iterations alike) and the host launches again until every request has
- *   ended: no kernel is unbounded, and the result does not depend on where the slices fall.  results[i] is filled for every
+ *   ended: no kernel is unbounded, and the result does not depend on where the slices fall.  The call is the pool of PLANS THAT
+ *   RIDE THE STREAM (below) driven to the end — submit, advance and wait until nothing runs, read the results in place — on a
+ *   pool of its own, one block of as many slots as the largest call so far: no ticket and no slice number of a pending request
+ *   moves, and nothing is copied back between the launches.  A call whose pool cannot be allocated fails with MGX_ERR_HIP and
+ *   leaves no pool behind: the same requests in smaller calls go through.  results[i] is filled for every
  *   request; the points of request i are path_xy[first_point .. first_point + n_points), requests in order; *n_points = all
  *   points.  point_capacity too small: results (first_point, n_points and the rest) and *n_points are filled, path_xy is not
  *   touched, MGX_ERR_INVALID.  NULL requests / results / n_points, NULL path_xy with a capacity, or a non-finite coordinate:
@@ -982,7 +986,7 @@ int mgx_env_collisions_clear(mgx_world *w);
  *   calls are that: requests wait in a pool that outlives a call, a slice of iterations is ENQUEUED on the world's stream, and the
  *   host hears which requests have ended from a completion log the launches append to in host-mapped memory.  A request's arrays
  *   never move while it is pending (the pool grows by blocks of slots), and the plan is mgx_plan_paths' bit for bit: the same
- *   slice of the same kernel code, and where the slices fall does not show.  Unsharded worlds, planner on.
+ *   kernel through the same host code, and where the slices fall does not show.  Unsharded worlds, planner on.
  * mgx_plan_submit(w, n, requests, tickets): queues the n requests and returns at once — nothing is launched, nothing waited for.
  *   tickets[i] names request i: counted from 1 per world, never used twice (not after mgx_planner_enable(NULL) either).  Requests
  *   already pending are not disturbed.  MGX_ERR_STATE: planner off, sharded world.  MGX_ERR_INVALID: NULL arguments, a non-finite
@@ -1009,7 +1013,8 @@ int mgx_env_collisions_clear(mgx_world *w);
  *   again once the slices in flight have completed.  MGX_ERR_INVALID: a ticket that is unknown, collected or cancelled.
  * mgx_plan_pending(w, n): requests submitted and neither collected nor cancelled.
  * mgx_planner_enable while requests are pending: env == NULL drops them with everything else; a new map is MGX_ERR_STATE and
- *   changes nothing.  mgx_plan_paths and mgx_plan_tree work beside pending requests (they wait for the slices enqueued). */
+ *   changes nothing.  mgx_plan_paths and mgx_plan_tree work beside pending requests (they wait for the slices enqueued, and
+ *   advance none of them). */
 #define MGX_PLAN_OK 0
 #define MGX_PLAN_MAX_ITERATIONS 1
 #define MGX_PLAN_TREE_FULL 2

@@ -375,23 +375,19 @@ struct PlanState {             // 64 bytes
 static_assert(sizeof(PlanState) == 64, "one request's state is one 64-byte record");
 struct PlanDev {
     EnvMapDev map;
-    PlanState *state;          // [n]
-    double *x, *y, *cost;      // [n][max_nodes] the trees, SoA
-    int32_t *parent;           // [n][max_nodes]
-    int32_t *path;             // [n][max_nodes + 1] node indices along the path, -1: `end`
-    float *out;                // [n][max_nodes + 1][2] the path's points as f32
     double step, radius2, half_extent, smoothing_step;
     float collision_radius;
     uint32_t max_iterations, max_nodes, smoothing_max;
     uint32_t budget;           // iterations (growth and smoothing together) one launch runs per request at the most
     int32_t smoothing;
 };
-// The pool of requests that ride the world's stream (k_plan_pool; the host's side: mgx_plan_pool.h, mgx_world_planner.inc).
-// Slots are allocated a block at a time and never move: a launch finds a slot's arrays through its block's base pointers.
+// A pool of requests (k_plan_pool; the host's side: mgx_plan_pool.h, mgx_world_planner.inc): the one that rides the world's
+// stream, or the one of a mgx_plan_paths call.  Slots are allocated a block at a time and never move: a launch finds a slot's
+// arrays through its block's base pointers.
 struct PlanBlockDev {          // slot 0 of the block; slot i follows at i * (the array's length per request)
-    double *x, *y, *cost;
-    int32_t *parent, *path;
-    float *out;                // host-mapped: the host reads an ended request's points in place
+    double *x, *y, *cost;      // [max_nodes] the tree, SoA
+    int32_t *parent, *path;    // [max_nodes]; [max_nodes + 1] node indices along the path, -1: `end`
+    float *out;                // [max_nodes + 1][2] the path's points as f32; host-mapped: the host reads them in place
     PlanState *state;          // host-mapped: written by the host at submit, read by it once the log names the request
 };
 struct PlanActive {            // one entry of a launch's compact list: a slot whose request has not ended
@@ -406,10 +402,10 @@ struct alignas(16) PlanLogEntry {  // the completion log: one entry per request,
 };
 static_assert(sizeof(PlanActive) == 16 && sizeof(PlanLogEntry) == 16, "one 16-byte load, one 16-byte store");
 struct PlanPoolDev {
-    const PlanBlockDev *blocks;  // host-mapped table, [MAX_BLOCKS]
+    const PlanBlockDev *blocks;  // host-mapped table, one entry per block
     const PlanActive *active;    // host-mapped, this launch's list
     PlanLogEntry *log;           // host-mapped ring of log_cap entries
-    unsigned int *log_count;     // host-mapped: entries claimed so far
+    unsigned int *log_count;     // device memory: entries claimed so far
     uint32_t log_cap;
     uint32_t slots_per_block;
     uint32_t seq;                // the number of this advance (low word): slice number = seq - first_seq

@@ -2,6 +2,7 @@
 // include/mgx.h): slots in blocks, the free list, ticket -> slot, the requests that have ended and the order they are handed out
 // in.  Host arithmetic only: no HIP, no allocation of a slot's arrays (mgx_world_planner.inc does that, one block of slots at a
 // time, and tells add_block) — so that it builds and runs on its own (tests/c_abi/plan_pool_fuzz.cpp).
+// A world has two books, which differ in shape (slots_per_block x max_blocks): the riding requests', and mgx_plan_paths' own.
 //
 // A slot's life: FREE -> RUNNING (submit) -> ENDED (the device's completion log named its ticket) -> COOLING (collected) -> FREE.
 // A cancelled request goes to COOLING from RUNNING or ENDED.  COOLING lasts until every slice enqueued when the slot was given
@@ -17,7 +18,6 @@
 namespace mgx {
 
 struct PlanPoolBook {
-    static constexpr uint32_t SLOTS_PER_BLOCK = 16, MAX_BLOCKS = 256, MAX_SLOTS = SLOTS_PER_BLOCK * MAX_BLOCKS;
     enum : uint8_t { FREE = 0, RUNNING = 1, ENDED = 2, COOLING = 3 };
     struct Slot {
         uint64_t ticket = 0;
@@ -26,6 +26,7 @@ struct PlanPoolBook {
         uint32_t slices = 0;      // ENDED: the slice it ended in
         uint8_t st = FREE;
     };
+    uint32_t slots_per_block, max_blocks;  // the pool's shape (drop keeps it, reset sets another)
     std::vector<Slot> slots;
     std::vector<uint32_t> free_list;
     std::vector<uint32_t> cooling;
@@ -37,13 +38,15 @@ struct PlanPoolBook {
     uint32_t n_running = 0;
     bool list_dirty = true;    // the set of RUNNING slots changed since the active list was last written
 
+    PlanPoolBook(uint32_t slots_per_block_, uint32_t max_blocks_) : slots_per_block(slots_per_block_), max_blocks(max_blocks_) {}
+    uint32_t max_slots() const { return slots_per_block * max_blocks; }
     uint32_t pending() const { return (uint32_t)by_ticket.size(); }
-    uint32_t blocks() const { return (uint32_t)(slots.size() / SLOTS_PER_BLOCK); }
+    uint32_t blocks() const { return (uint32_t)(slots.size() / slots_per_block); }
 
     void add_block() {
         const uint32_t first = (uint32_t)slots.size();
-        slots.resize(first + SLOTS_PER_BLOCK);
-        for (uint32_t i = SLOTS_PER_BLOCK; i-- > 0;) free_list.push_back(first + i);  // (lowest index is taken first)
+        slots.resize(first + slots_per_block);
+        for (uint32_t i = slots_per_block; i-- > 0;) free_list.push_back(first + i);  // (lowest index is taken first)
     }
     // a slot nothing in flight can touch, or -1: add a block first
     int take_slot() {
@@ -120,10 +123,11 @@ struct PlanPoolBook {
         for (uint32_t s = 0; s < (uint32_t)slots.size(); s++)
             if (slots[s].st == RUNNING) f(s, slots[s]);
     }
-    // everything goes but the ticket counter (the caller frees the blocks)
-    void drop() {
+    // everything goes but the shape and the ticket counter (the caller frees the blocks); reset: and the shape is another
+    void drop() { reset(slots_per_block, max_blocks); }
+    void reset(uint32_t slots_per_block_, uint32_t max_blocks_) {
         const uint64_t t = next_ticket;
-        *this = PlanPoolBook{};
+        *this = PlanPoolBook(slots_per_block_, max_blocks_);
         next_ticket = t;
     }
 };

@@ -15,8 +15,9 @@
 // chord spreads its POINTS over the lanes (each lane walks its points' cells alone) and combines the same way.
 // A launch runs at most `budget` iterations per request (growth and smoothing iterations count alike) and leaves everything in
 // global memory — tree, counters, stream state, phase — so the host launches again until every request is done, and where the
-// slices fall does not show in the result.  Two launches share the slice (plan_slice): k_plan over the requests of one synchronous
-// call, k_plan_pool over the active slots of the pool whose requests ride the world's stream (mgx_plan_submit / _advance / _collect).
+// slices fall does not show in the result.  One kernel runs the slice (plan_slice): k_plan_pool, over the active slots of a pool
+// of requests — the pool whose requests ride the world's stream (mgx_plan_submit / _advance / _collect), or the pool that
+// mgx_plan_paths fills, drives to the end and empties within one call.
 // All planner arithmetic is f64 with every operation rounded on its own: contraction is switched off for this file whatever
 // the command line says, so libmgx.so and libmgx_fma.so hold the same code here.
 #include <hip/hip_runtime.h>
@@ -100,7 +101,7 @@ __device__ __forceinline__ double dist2(double ax, double ay, double bx, double 
     return dx * dx + dy * dy;
 }
 
-// One request's arrays, wherever they live: request `req` of a call's contiguous arrays (k_plan), or a slot of the pool (k_plan_pool).
+// One request's arrays: a slot of a pool (k_plan_pool).
 struct PlanSlot {
     PlanState *state;
     double *x, *y, *cost;  // [max_nodes]
@@ -262,23 +263,12 @@ __device__ __forceinline__ bool plan_slice(const PlanDev &c, const PlanSlot &slo
     return st.phase == PLAN_PHASE_DONE;
 }
 
-// mgx_plan_paths: workgroup = request of the call, the arrays of all requests contiguous
-__global__ void __launch_bounds__(PLAN_BLOCK) k_plan(PlanDev c) {
-    const size_t req = blockIdx.x, cap = c.max_nodes;
-    PlanSlot slot;
-    slot.state = c.state + req;
-    slot.x = c.x + req * cap; slot.y = c.y + req * cap; slot.cost = c.cost + req * cap;
-    slot.parent = c.parent + req * cap;
-    slot.path = c.path + req * (cap + 1);
-    slot.out = c.out + 2 * req * (cap + 1);
-    (void)plan_slice(c, slot);
-}
-
-// mgx_plan_advance: workgroup = entry of the compact list of active slots; a slot's arrays are found through its block's base
-// pointers (blocks never move while the pool lives).  State and points of a slot are in host-mapped memory, and so is the
-// completion log: a request that ends here makes its state and points visible to the host, then claims the next log entry (the one
-// atomic) and fills it with one 16-byte store.  The host takes an entry once its ticket is not 0 (tickets count from 1) and zeroes
-// it again, so a counter that is ahead of an entry's store only delays that entry to the next look.
+// One slice of a pool (mgx_plan_advance, a mission tick's budget, mgx_plan_paths): workgroup = entry of the compact list of
+// active slots; a slot's arrays are found through its block's base pointers (blocks never move while the pool lives).  State and
+// points of a slot are in host-mapped memory, and so is the completion log: a request that ends here makes its state and points
+// visible to the host, then claims the next log entry (the one atomic, on a counter in device memory: the host never reads it)
+// and fills it with one 16-byte store.  The host takes an entry once its ticket is not 0 (tickets count from 1) and zeroes it
+// again, so a counter that is ahead of an entry's store only delays that entry to the next look.
 __global__ void __launch_bounds__(PLAN_BLOCK) k_plan_pool(PlanDev c, PlanPoolDev pool) {
     const PlanActive a = pool.active[blockIdx.x];
     const PlanBlockDev b = pool.blocks[a.slot / pool.slots_per_block];
@@ -305,29 +295,15 @@ __global__ void __launch_bounds__(PLAN_BLOCK) k_plan_pool(PlanDev c, PlanPoolDev
     }
 }
 
-static hipError_t plan_lds_grant(const void *kernel, size_t lds, size_t &granted) {
-    if (lds <= granted) return hipSuccess;  // dynamic LDS beyond 64 KiB has to be asked for once per size
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess) granted = lds;
-    return e;
-}
-
-hipError_t launch_plan(const PlanDev &c, int n_requests, hipStream_t s) {
-    if (n_requests <= 0) return hipSuccess;
-    static size_t granted = 0;
-    const size_t lds = sizeof(double) * 2 * (size_t)c.max_nodes;
-    const hipError_t e = plan_lds_grant(reinterpret_cast<const void *>(k_plan), lds, granted);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_plan, dim3((unsigned)n_requests), dim3(PLAN_BLOCK), lds, s, c);
-    return hipGetLastError();
-}
-
 hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s) {
     if (n_active <= 0) return hipSuccess;
     static size_t granted = 0;
     const size_t lds = sizeof(double) * 2 * (size_t)c.max_nodes;
-    const hipError_t e = plan_lds_grant(reinterpret_cast<const void *>(k_plan_pool), lds, granted);
-    if (e != hipSuccess) return e;
+    if (lds > granted) {  // dynamic LDS beyond 64 KiB has to be asked for once per size
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_plan_pool), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+        granted = lds;
+    }
     hipLaunchKernelGGL(k_plan_pool, dim3((unsigned)n_active), dim3(PLAN_BLOCK), lds, s, c, pool);
     return hipGetLastError();
 }

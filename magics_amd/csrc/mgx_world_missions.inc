@@ -274,7 +274,7 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     tm.lap("prior updates + schedule");
     // plans that ride the ticks (mgx_planner_set_tick_budget): one slice for every pending request, behind this tick's launches on
     // the same stream — a planner workgroup beside them would take a CU's LDS from the resident launch's census
-    if (rc == MGX_OK && w->planner.enabled && w->planner.pool.tick_budget) rc = plan_pool_advance(w, w->planner.pool.tick_budget);
+    if (rc == MGX_OK && w->planner.enabled && w->planner.tick_budget) rc = plan_pool_advance(w->planner.pool, w->planner, w->stream, w->planner.tick_budget);
     return rc;
 }
 

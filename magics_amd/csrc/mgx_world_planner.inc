@@ -2,23 +2,29 @@
 // _collect, _cancel, _pending and mgx_planner_set_tick_budget for plans that ride the stream).
 // Part of ONE translation unit: included by mgx_world.hip (which says in which order, and why one unit).
 // What a plan is: include/mgx.h; how a launch computes it: mgx_planner.hip.  The host's side here: the map goes up once
-// (env_map_upload, shared with the robot-environment pass), a call sizes the trees for its requests, uploads one 64-byte state
-// per request and launches slices of iterations_per_launch iterations until every state says DONE — one small read-back per slice.
-// Requests that ride the stream live in a pool instead (mgx_world::Planner::Pool; its bookkeeping: mgx_plan_pool.h): submit writes
-// a state into a slot's host-mapped record, advance enqueues one launch over the slots still running and records an event behind
-// it, and collect reads the completion log the launches append to — no call of the three waits unless it is asked to.
+// (env_map_upload, shared with the robot-environment pass), and every request lives in a slot of a pool (mgx_world::Planner::Pool;
+// its bookkeeping: mgx_plan_pool.h).  ONE lifecycle: plan_pool_submit writes a state into a slot's host-mapped record,
+// plan_pool_advance enqueues one launch over the slots still running with an event behind it, plan_pool_poll learns what has ended
+// from the completion log the launches append to, plan_pool_result reads it in place.  mgx_plan_submit / _advance / _collect are
+// those steps for requests that ride the stream; mgx_plan_paths is the same steps with a wait behind every slice, on a pool of
+// its own (Planner::call: no ticket or slice number of a pending request moves).
 
 static constexpr uint32_t PLAN_DEFAULT_NODES = 8192, PLAN_DEFAULT_SLICE = 1024, PLAN_MAX_NODES = 1u << 16;
 static constexpr float PLAN_DEFAULT_HALF_EXTENT = 2000.f;
 static const char *const PLAN_OFF = "the global planner is off (mgx_planner_enable)";
 
+// the pool of mgx_plan_paths goes with the last call's trees (the stream is synchronised); the next call builds one of its size
+static void plan_call_drop(mgx_world::Planner &p) {
+    p.call_slots.clear();
+    p.call.release();
+    p.call.book.reset(1, 1);
+}
 static void planner_drop(mgx_world *w) {
     mgx_world::Planner &p = w->planner;
     p.enabled = false;
     p.map.release();
-    p.state.release(); p.x.release(); p.y.release(); p.cost.release(); p.parent.release(); p.path.release(); p.out.release();
-    p.host_state.clear();
     p.pool.release();
+    plan_call_drop(p);
 }
 
 // what a launch is handed apart from its arrays and its budget
@@ -77,33 +83,41 @@ static hipError_t plan_dev_view(T *host, T **dev) {
     return e;
 }
 
-// what the device has reported since the last look: the event behind the last slice (never waited for here), then the log
-static void plan_pool_poll(mgx_world::Planner &p) {
-    mgx_world::Planner::Pool &pl = p.pool;
-    if (pl.ev && pl.ev_seq > pl.book.completed && hipEventQuery(pl.ev) == hipSuccess) pl.book.complete(pl.ev_seq);
-    if (!pl.log) return;
+using PlanPool = mgx_world::Planner::Pool;
+
+// what the device has reported since the last look: the event behind the last slice (waited for only if `wait`), then the log
+static int plan_pool_poll(PlanPool &pl, bool wait = false) {
+    if (pl.ev && pl.ev_seq > pl.book.completed) {
+        if (wait) HIP_TRY(hipEventSynchronize(pl.ev));
+        if (wait || hipEventQuery(pl.ev) == hipSuccess) pl.book.complete(pl.ev_seq);
+    }
+    if (!pl.log) return MGX_OK;
     for (;;) {
-        PlanLogEntry &e = pl.log[pl.log_taken % mgx_world::Planner::Pool::LOG_CAP];
+        PlanLogEntry &e = pl.log[pl.log_taken % pl.log_cap];
         const unsigned long long ticket = __atomic_load_n(&e.ticket, __ATOMIC_ACQUIRE);
         if (!ticket) break;
         pl.book.finished(ticket, e.slices);
         __atomic_store_n(&e.ticket, 0ull, __ATOMIC_RELAXED);
         pl.log_taken += 1;
     }
+    return MGX_OK;
 }
 
-static int plan_pool_add_block(mgx_world *w) {
-    mgx_world::Planner &p = w->planner;
-    mgx_world::Planner::Pool &pl = p.pool;
-    const size_t S = PlanPoolBook::SLOTS_PER_BLOCK, cap = p.params.max_nodes, b = pl.blocks.size();
-    if (b >= PlanPoolBook::MAX_BLOCKS) return fail(MGX_ERR_INVALID, "more than %u requests pending", PlanPoolBook::MAX_SLOTS);
+static int plan_pool_add_block(PlanPool &pl, const mgx_plan_params &q, hipStream_t stream) {
+    const size_t S = pl.book.slots_per_block, cap = q.max_nodes, b = pl.blocks.size();
+    if (b >= pl.book.max_blocks) return fail(MGX_ERR_INVALID, "more than %u requests pending", pl.book.max_slots());
     if (!pl.table) {
-        HIP_TRY(plan_host_mapped(&pl.table, (size_t)PlanPoolBook::MAX_BLOCKS));
-        HIP_TRY(plan_host_mapped(&pl.log, (size_t)mgx_world::Planner::Pool::LOG_CAP + 1));  // (the counter is the word behind the ring)
-        pl.log_count = reinterpret_cast<unsigned int *>(pl.log + mgx_world::Planner::Pool::LOG_CAP);
+        // more entries than can be unread, and a power of two: the device's 32-bit counter and the host's 64-bit one agree for ever
+        for (pl.log_cap = 1; pl.log_cap < 2 * pl.book.max_slots();) pl.log_cap *= 2;
+        HIP_TRY(plan_host_mapped(&pl.table, (size_t)pl.book.max_blocks));
+        HIP_TRY(plan_host_mapped(&pl.log, (size_t)pl.log_cap));
+        // the counter of claimed entries is the device's alone: in device memory, or workgroups that end together queue up for one
+        // word across the bus (1 us each, profiles/global_planner.md); zeroed on the launches' stream: a submit waits for nothing
+        HIP_TRY(hipMalloc((void **)&pl.log_count, sizeof(unsigned int)));
+        HIP_TRY(hipMemsetAsync(pl.log_count, 0, sizeof(unsigned int), stream));
         HIP_TRY(hipEventCreateWithFlags(&pl.ev, hipEventDisableTiming));
     }
-    mgx_world::Planner::Pool::Block blk;
+    PlanPool::Block blk;
     const size_t f64s = 3 * S * cap, i32s = S * cap + S * (cap + 1);
     HIP_TRY(hipMalloc(&blk.dev, sizeof(double) * f64s + sizeof(int32_t) * i32s));
     char *host = nullptr;
@@ -122,9 +136,43 @@ static int plan_pool_add_block(mgx_world *w) {
     return MGX_OK;
 }
 
+// n requests into n slots that nothing in flight can touch (blocks are added as needed; on failure what was taken goes back): each
+// slot gets its request's initial state and a ticket (book.slots[slot].ticket)
+static int plan_pool_submit(PlanPool &pl, const mgx_plan_params &q, hipStream_t stream, uint32_t n, const mgx_plan_request *requests,
+                            std::vector<uint32_t> &slots) {
+    (void)plan_pool_poll(pl);  // (before a slot changes its tenant: what the log says of the one before is taken)
+    slots.clear();
+    slots.reserve(n);
+    while (slots.size() < n) {
+        const int s = pl.book.take_slot();
+        if (s >= 0) { slots.push_back((uint32_t)s); continue; }
+        const int rc = plan_pool_add_block(pl, q, stream);
+        if (rc != MGX_OK) {
+            for (size_t i = slots.size(); i-- > 0;) pl.book.give_back(slots[i]);
+            slots.clear();
+            return rc;
+        }
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        pl.blocks[slots[i] / pl.book.slots_per_block].state[slots[i] % pl.book.slots_per_block] = plan_initial_state(requests[i]);
+        (void)pl.book.submit(slots[i]);
+    }
+    return MGX_OK;
+}
+
+// the result of the request that ended in `slot`, and its points: both are read in place
+static int plan_pool_result(const PlanPool &pl, uint32_t slot, size_t cap, uint32_t first_point, mgx_plan_result &r) {
+    plan_result_of(pl.blocks[slot / pl.book.slots_per_block].state[slot % pl.book.slots_per_block], first_point, r);
+    return r.n_points <= cap + 1 ? MGX_OK : fail(MGX_ERR_STATE, "slot %u: a path of %u points", slot, r.n_points);
+}
+static void plan_pool_points(const PlanPool &pl, uint32_t slot, size_t cap, const mgx_plan_result &r, float *path_xy) {
+    const float *from = pl.blocks[slot / pl.book.slots_per_block].out + 2 * (size_t)(slot % pl.book.slots_per_block) * (cap + 1);
+    if (r.n_points) memcpy(path_xy + 2 * (size_t)r.first_point, from, sizeof(float) * 2 * r.n_points);
+}
+
 // the list of the slots still running, in a buffer no launch in flight reads
-static int plan_pool_write_list(mgx_world::Planner::Pool &pl) {
-    using List = mgx_world::Planner::Pool::List;
+static int plan_pool_write_list(PlanPool &pl) {
+    using List = PlanPool::List;
     const size_t n = pl.book.n_running;
     int k = -1;
     for (size_t i = 0; i < pl.lists.size() && k < 0; i++)
@@ -149,11 +197,9 @@ static int plan_pool_write_list(mgx_world::Planner::Pool &pl) {
     return MGX_OK;
 }
 
-// one slice for every request still running, enqueued behind whatever the stream holds; nothing running: nothing is launched
-static int plan_pool_advance(mgx_world *w, uint32_t iterations) {
-    mgx_world::Planner &p = w->planner;
-    mgx_world::Planner::Pool &pl = p.pool;
-    plan_pool_poll(p);
+// one slice for every request of the pool still running, enqueued behind whatever the stream holds; nothing running: nothing is launched
+static int plan_pool_advance(PlanPool &pl, const mgx_world::Planner &p, hipStream_t stream, uint32_t iterations) {
+    (void)plan_pool_poll(pl);
     if (pl.book.n_running == 0) return MGX_OK;
     if (pl.book.list_dirty || pl.cur < 0) {
         const int rc = plan_pool_write_list(pl);
@@ -165,14 +211,15 @@ static int plan_pool_advance(mgx_world *w, uint32_t iterations) {
     HIP_TRY(plan_dev_view(pl.table, const_cast<PlanBlockDev **>(&pd.blocks)));
     HIP_TRY(plan_dev_view(pl.lists[(size_t)pl.cur].p, const_cast<PlanActive **>(&pd.active)));
     HIP_TRY(plan_dev_view(pl.log, &pd.log));
-    HIP_TRY(plan_dev_view(pl.log_count, &pd.log_count));
-    pd.log_cap = mgx_world::Planner::Pool::LOG_CAP;
-    pd.slots_per_block = PlanPoolBook::SLOTS_PER_BLOCK;
-    const uint64_t seq = pl.book.advance();
+    pd.log_count = pl.log_count;
+    pd.log_cap = pl.log_cap;
+    pd.slots_per_block = pl.book.slots_per_block;
+    const uint64_t seq = pl.book.seq + 1;
     pd.seq = (uint32_t)seq;
+    HIP_TRY(launch_plan_pool(d, pd, (int)pl.cur_n, stream));
+    (void)pl.book.advance();  // (a launch that was refused is no advance: nothing of it is in flight)
     pl.lists[(size_t)pl.cur].last_seq = seq;
-    HIP_TRY(launch_plan_pool(d, pd, (int)pl.cur_n, w->stream));
-    HIP_TRY(hipEventRecord(pl.ev, w->stream));
+    HIP_TRY(hipEventRecord(pl.ev, stream));
     pl.ev_seq = seq;
     return MGX_OK;
 }
@@ -221,50 +268,45 @@ int mgx_plan_paths(mgx_world *w, uint32_t n, const mgx_plan_request *requests, m
     for (uint32_t i = 0; i < n; i++)
         if (!plan_request_finite(requests[i])) return fail(MGX_ERR_INVALID, "request %u: a coordinate is not finite", i);
     if (n > (1u << 20)) return fail(MGX_ERR_INVALID, "more than 2^20 requests");
-    if (n == 0) { *n_points = 0; p.host_state.clear(); return MGX_OK; }
+    if (n == 0) { *n_points = 0; p.call_slots.clear(); return MGX_OK; }
     MGX_CONFIRM(w);
     const mgx_plan_params &q = p.params;
-    const size_t cap = q.max_nodes, N = n;
-    hipStream_t s = w->stream;
-    HIP_TRY(p.state.reserve(N));
-    HIP_TRY(p.x.reserve(N * cap));
-    HIP_TRY(p.y.reserve(N * cap));
-    HIP_TRY(p.cost.reserve(N * cap));
-    HIP_TRY(p.parent.reserve(N * cap));
-    HIP_TRY(p.path.reserve(N * (cap + 1)));
-    HIP_TRY(p.out.reserve(2 * N * (cap + 1)));
-    std::vector<PlanState> &st = p.host_state;
-    st.resize(N);
-    for (size_t i = 0; i < N; i++) st[i] = plan_initial_state(requests[i]);
-    HIP_TRY(hipMemcpyAsync(p.state.p, st.data(), sizeof(PlanState) * N, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (pageable memory)
-    PlanDev d = plan_dev_params(p);
-    d.state = p.state.p; d.x = p.x.p; d.y = p.y.p; d.cost = p.cost.p; d.parent = p.parent.p; d.path = p.path.p; d.out = p.out.p;
-    d.budget = q.iterations_per_launch;
+    PlanPool &pl = p.call;
+    // nothing of this pool is in flight between two calls: one that needs more slots builds it again, with a quarter to spare
+    if (n > pl.book.slots_per_block) {
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        plan_call_drop(p);
+        pl.book.reset(n + n / 4, 1);
+    }
+    int rc = plan_pool_submit(pl, q, w->stream, n, requests, p.call_slots);
     // every launch takes `budget` off what a request has left (growth, then smoothing), and one more finishes it
     const uint64_t most = ((uint64_t)q.max_iterations + q.smoothing_max_iterations) / q.iterations_per_launch + 3;
-    bool done = false;
-    for (uint64_t l = 0; l < most && !done; l++) {
-        HIP_TRY(launch_plan(d, (int)n, s));
-        HIP_TRY(hipMemcpyAsync(st.data(), p.state.p, sizeof(PlanState) * N, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        done = true;
-        for (size_t i = 0; i < N; i++) done = done && st[i].phase == PLAN_PHASE_DONE;
+    for (uint64_t l = 0; l < most && rc == MGX_OK && pl.book.n_running; l++) {
+        rc = plan_pool_advance(pl, p, w->stream, q.iterations_per_launch);
+        if (rc == MGX_OK) rc = plan_pool_poll(pl, true);
     }
-    if (!done) return fail(MGX_ERR_STATE, "the planner's launches ran out before every request had ended");
+    if (rc != MGX_OK) {  // an allocation, a launch or a wait failed: the pool goes, and a smaller call can build its own
+        (void)hipStreamSynchronize(w->stream);
+        plan_call_drop(p);
+        (void)hipGetLastError();  // (the failure has been reported: the next launch's check does not find it again)
+        return rc;
+    }
+    if (pl.book.n_running) rc = fail(MGX_ERR_STATE, "the planner's launches ran out before every request had ended");
+    // the slots are given up; what is in them stays until the next call takes them (mgx_plan_tree)
+    for (const uint32_t s : p.call_slots) (void)pl.book.cancel(pl.book.slots[s].ticket);
+    pl.book.complete(pl.book.completed);
+    if (rc != MGX_OK) return rc;
+    const size_t cap = q.max_nodes;
     uint64_t total = 0;
-    for (size_t i = 0; i < N; i++) {
-        plan_result_of(st[i], (uint32_t)total, results[i]);
+    for (uint32_t i = 0; i < n; i++) {
+        rc = plan_pool_result(pl, p.call_slots[i], cap, (uint32_t)total, results[i]);
+        if (rc != MGX_OK) return rc;
         total += results[i].n_points;
     }
     if (total > 0xffffffffull) return fail(MGX_ERR_INVALID, "more than 2^32 points");
     *n_points = (uint32_t)total;
     if (total > point_capacity) return fail(MGX_ERR_INVALID, "room for %u points, the paths have %llu", point_capacity, (unsigned long long)total);
-    for (size_t i = 0; i < N; i++)
-        if (results[i].n_points)
-            HIP_TRY(hipMemcpyAsync(path_xy + 2 * (size_t)results[i].first_point, p.out.p + 2 * i * (cap + 1), sizeof(float) * 2 * results[i].n_points,
-                                   hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < n; i++) plan_pool_points(pl, p.call_slots[i], cap, results[i], path_xy);
     return check_device_error(w);
 }
 
@@ -273,20 +315,22 @@ int mgx_plan_tree(mgx_world *w, uint32_t request, uint32_t capacity, double *xy,
     if (!w || !n_nodes) return fail(MGX_ERR_INVALID, "null argument");
     mgx_world::Planner &p = w->planner;
     if (!p.enabled) return fail(MGX_ERR_STATE, "%s", PLAN_OFF);
-    if (request >= p.host_state.size()) return fail(MGX_ERR_INVALID, "request %u: the last mgx_plan_paths had %zu", request, p.host_state.size());
-    const size_t cap = p.params.max_nodes, nn = p.host_state[request].n_nodes, m = std::min<size_t>(std::min<size_t>(nn, capacity), cap);
+    if (request >= p.call_slots.size()) return fail(MGX_ERR_INVALID, "request %u: the last mgx_plan_paths had %zu", request, p.call_slots.size());
+    const size_t slot = p.call_slots[request];  // (the call's pool is one block: the slot is the index into its arrays)
+    const PlanBlockDev &b = p.call.table[0];
+    const size_t cap = p.params.max_nodes, nn = p.call.blocks[0].state[slot].n_nodes, m = std::min<size_t>(std::min<size_t>(nn, capacity), cap);
     *n_nodes = (uint32_t)nn;
     if (m == 0) return MGX_OK;
     hipStream_t s = w->stream;
     if (xy) {
-        std::vector<double> a(m), b(m);
-        HIP_TRY(hipMemcpyAsync(a.data(), p.x.p + request * cap, sizeof(double) * m, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(b.data(), p.y.p + request * cap, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+        std::vector<double> x(m), y(m);
+        HIP_TRY(hipMemcpyAsync(x.data(), b.x + slot * cap, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(y.data(), b.y + slot * cap, sizeof(double) * m, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        for (size_t k = 0; k < m; k++) { xy[2 * k] = a[k]; xy[2 * k + 1] = b[k]; }
+        for (size_t k = 0; k < m; k++) { xy[2 * k] = x[k]; xy[2 * k + 1] = y[k]; }
     }
-    if (parent) HIP_TRY(hipMemcpyAsync(parent, p.parent.p + request * cap, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
-    if (cost) HIP_TRY(hipMemcpyAsync(cost, p.cost.p + request * cap, sizeof(double) * m, hipMemcpyDeviceToHost, s));
+    if (parent) HIP_TRY(hipMemcpyAsync(parent, b.parent + slot * cap, sizeof(int32_t) * m, hipMemcpyDeviceToHost, s));
+    if (cost) HIP_TRY(hipMemcpyAsync(cost, b.cost + slot * cap, sizeof(double) * m, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return MGX_OK;
 }
@@ -299,28 +343,12 @@ int mgx_plan_submit(mgx_world *w, uint32_t n, const mgx_plan_request *requests, 
     if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the global planner runs on unsharded worlds");
     for (uint32_t i = 0; i < n; i++)
         if (!plan_request_finite(requests[i])) return fail(MGX_ERR_INVALID, "request %u: a coordinate is not finite", i);
-    mgx_world::Planner::Pool &pl = p.pool;
-    plan_pool_poll(p);  // (before a slot changes its tenant: what the log says of the one before is taken)
-    if ((uint64_t)pl.book.pending() + n > PlanPoolBook::MAX_SLOTS) return fail(MGX_ERR_INVALID, "more than %u requests pending", PlanPoolBook::MAX_SLOTS);
+    PlanPool &pl = p.pool;
+    if ((uint64_t)pl.book.pending() + n > pl.book.max_slots()) return fail(MGX_ERR_INVALID, "more than %u requests pending", pl.book.max_slots());
     std::vector<uint32_t> slots;
-    slots.reserve(n);
-    while (slots.size() < n) {
-        int s = pl.book.take_slot();
-        if (s < 0) {
-            const int rc = plan_pool_add_block(w);
-            if (rc != MGX_OK) {
-                for (size_t i = slots.size(); i-- > 0;) pl.book.give_back(slots[i]);
-                return rc;
-            }
-            continue;
-        }
-        slots.push_back((uint32_t)s);
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        const uint32_t s = slots[i];
-        pl.blocks[s / PlanPoolBook::SLOTS_PER_BLOCK].state[s % PlanPoolBook::SLOTS_PER_BLOCK] = plan_initial_state(requests[i]);
-        tickets[i] = pl.book.submit(s);
-    }
+    const int rc = plan_pool_submit(pl, p.params, w->stream, n, requests, slots);
+    if (rc != MGX_OK) return rc;
+    for (uint32_t i = 0; i < n; i++) tickets[i] = pl.book.slots[slots[i]].ticket;
     return MGX_OK;
 }
 
@@ -329,13 +357,13 @@ int mgx_plan_advance(mgx_world *w, uint32_t iterations) {
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     if (iterations == 0) return fail(MGX_ERR_INVALID, "a slice of 0 iterations");
     if (!w->planner.enabled) return fail(MGX_ERR_STATE, "%s", PLAN_OFF);
-    return plan_pool_advance(w, iterations);
+    return plan_pool_advance(w->planner.pool, w->planner, w->stream, iterations);
 }
 
 int mgx_planner_set_tick_budget(mgx_world *w, uint32_t iterations) {
     MGX_ENTER(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    w->planner.pool.tick_budget = iterations;
+    w->planner.tick_budget = iterations;
     return MGX_OK;
 }
 
@@ -346,25 +374,20 @@ int mgx_plan_collect(mgx_world *w, uint32_t flags, uint32_t capacity, mgx_plan_d
     if (flags & ~(uint32_t)MGX_PLAN_WAIT) return fail(MGX_ERR_INVALID, "unknown flags");
     mgx_world::Planner &p = w->planner;
     if (!p.enabled) return fail(MGX_ERR_STATE, "%s", PLAN_OFF);
-    mgx_world::Planner::Pool &pl = p.pool;
-    if ((flags & MGX_PLAN_WAIT) && pl.ev && pl.ev_seq > pl.book.completed) {
-        HIP_TRY(hipEventSynchronize(pl.ev));
-        pl.book.complete(pl.ev_seq);
-    }
-    plan_pool_poll(p);
+    PlanPool &pl = p.pool;
+    const int rc_poll = plan_pool_poll(pl, (flags & MGX_PLAN_WAIT) != 0);
+    if (rc_poll != MGX_OK) return rc_poll;
     const size_t cap = p.params.max_nodes;
     uint32_t nd = 0, np = 0, slices = 0, slot = 0;
     uint64_t ticket = 0;
     while (nd < capacity && pl.book.next_done(&ticket, &slices, &slot)) {
-        const mgx_world::Planner::Pool::Block &b = pl.blocks[slot / PlanPoolBook::SLOTS_PER_BLOCK];
-        const size_t i = slot % PlanPoolBook::SLOTS_PER_BLOCK;
         mgx_plan_done d{};
-        plan_result_of(b.state[i], np, d.result);
-        if (d.result.n_points > cap + 1) return fail(MGX_ERR_STATE, "ticket %llu: a path of %u points", (unsigned long long)ticket, d.result.n_points);
+        const int rc = plan_pool_result(pl, slot, cap, np, d.result);
+        if (rc != MGX_OK) return rc;
         if (d.result.n_points > point_capacity - np) break;  // (it stays for the next call)
         d.ticket = ticket;
         d.slices = slices;
-        if (d.result.n_points) memcpy(path_xy + 2 * (size_t)np, b.out + 2 * i * (cap + 1), sizeof(float) * 2 * d.result.n_points);
+        plan_pool_points(pl, slot, cap, d.result, path_xy);
         np += d.result.n_points;
         done[nd++] = d;
         pl.book.pop_done();
@@ -377,7 +400,7 @@ int mgx_plan_collect(mgx_world *w, uint32_t flags, uint32_t capacity, mgx_plan_d
 int mgx_plan_cancel(mgx_world *w, uint64_t ticket) {
     MGX_ENTER(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");
-    plan_pool_poll(w->planner);
+    (void)plan_pool_poll(w->planner.pool);
     if (!w->planner.pool.book.cancel(ticket)) return fail(MGX_ERR_INVALID, "ticket %llu is not pending", (unsigned long long)ticket);
     return MGX_OK;
 }

@@ -79,7 +79,6 @@ hipError_t launch_collisions_pass(const CollDev &c, bool grid, double cell, uint
 hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s);
 hipError_t launch_env_collisions_pass(const EnvCollDev &c, hipStream_t s);
 // mgx_planner.hip
-hipError_t launch_plan(const PlanDev &c, int n_requests, hipStream_t s);
 hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s);
 }  // namespace mgx
 
@@ -785,27 +784,26 @@ struct mgx_world {
         DevBuf<int32_t> touching;
         EnvCollDev d{};
     } envcoll;
-    // the global planner (mgx_planner_enable / mgx_plan_paths, mgx_world_planner.inc): the map, and the trees of the last call
+    // the global planner (mgx_planner_enable, mgx_world_planner.inc): the map and two pools of requests.  `pool`: the requests that
+    // ride the stream (mgx_plan_submit / _advance / _collect), 256 blocks of 16 slots.  `call`: the requests of one mgx_plan_paths,
+    // which gives its slots up before it returns — one block, sized by the largest call so far; the arrays of given-up slots are
+    // the trees of the last call (mgx_plan_tree) until the next call takes them
     struct Planner {
         bool enabled = false;
         mgx_plan_params params{};  // defaults filled in
         EnvMap map;
-        DevBuf<PlanState> state;
-        DevBuf<double> x, y, cost;
-        DevBuf<int32_t> parent, path;
-        DevBuf<float> out;
-        std::vector<PlanState> host_state;  // of the last mgx_plan_paths (mgx_plan_tree reads by it)
-        // the requests that ride the stream (mgx_plan_submit / _advance / _collect): bookkeeping in `book` (mgx_plan_pool.h), the
-        // slots' arrays a block at a time — trees and node paths in device memory, states and points host-mapped — so that nothing
-        // a pending request uses ever moves; the table of blocks, the completion log and the launches' active lists are host-mapped
+        uint32_t tick_budget = 0;  // mgx_planner_set_tick_budget (a setting of the world: mgx_planner_enable keeps it)
+        // a pool: bookkeeping in `book` (mgx_plan_pool.h), the slots' arrays a block at a time — trees and node paths in device
+        // memory, states and points host-mapped — so that nothing a pending request uses ever moves; the table of blocks, the
+        // completion log and the launches' active lists are host-mapped
         struct Pool {
-            static constexpr uint32_t LOG_CAP = 2 * PlanPoolBook::MAX_SLOTS;  // (more than can be unread: one entry per slot's tenant)
             PlanPoolBook book;
             struct Block { void *dev = nullptr; PlanState *state = nullptr; float *out = nullptr; };  // state, out: one host allocation
             std::vector<Block> blocks;
-            PlanBlockDev *table = nullptr;   // [MAX_BLOCKS]
-            PlanLogEntry *log = nullptr;     // [LOG_CAP], then the counter
-            unsigned int *log_count = nullptr;
+            PlanBlockDev *table = nullptr;   // [book.max_blocks]
+            uint32_t log_cap = 0;            // a power of two, at least 2 * book.max_slots() (more than can be unread)
+            PlanLogEntry *log = nullptr;     // [log_cap]
+            unsigned int *log_count = nullptr;  // device memory: entries claimed so far (the host never reads it)
             uint64_t log_taken = 0;
             struct List { PlanActive *p = nullptr; size_t cap = 0; uint64_t last_seq = 0; };  // last_seq: the last advance that reads it
             std::vector<List> lists;
@@ -813,8 +811,7 @@ struct mgx_world {
             uint32_t cur_n = 0;
             hipEvent_t ev = nullptr;         // behind the last slice
             uint64_t ev_seq = 0;
-            uint32_t tick_budget = 0;        // mgx_planner_set_tick_budget (a setting of the world: release keeps it)
-            Pool() = default;
+            Pool(uint32_t slots_per_block, uint32_t max_blocks) : book(slots_per_block, max_blocks) {}
             Pool(const Pool &) = delete;
             Pool &operator=(const Pool &) = delete;
             ~Pool() { release(); }
@@ -825,12 +822,15 @@ struct mgx_world {
                 lists.clear();
                 if (table) (void)hipHostFree(table);
                 if (log) (void)hipHostFree(log);
+                if (log_count) (void)hipFree(log_count);
                 if (ev) (void)hipEventDestroy(ev);
                 table = nullptr; log = nullptr; log_count = nullptr; ev = nullptr;
-                log_taken = 0; cur = -1; cur_n = 0; ev_seq = 0;
+                log_cap = 0; log_taken = 0; cur = -1; cur_n = 0; ev_seq = 0;
                 book.drop();
             }
-        } pool;
+        };
+        Pool pool{16, 256}, call{1, 1};
+        std::vector<uint32_t> call_slots;  // slot of request i of the last mgx_plan_paths (mgx_plan_tree reads by it)
     } planner;
     uint32_t last_sweep_launches = 0;  // sweep-kernel launches of the last mgx_iterate / mgx_tick call (mgx_last_launch_count)
     SweepRan last_sweep;               // the sweep instantiation it launched last (mgx_last_sweep) ...

@@ -1,8 +1,10 @@
 // The bookkeeping of the global planner's request pool (magics_amd/csrc/mgx_plan_pool.h) on its own, without HIP: 10 000 random
 // submit / advance / complete / collect / cancel steps against a plain model of what the C ABI promises.  A "device" is played
 // by this program: a launch is the list of slots running when it was enqueued, it completes later, and a request ends in the
-// slice the model drew for it.  Built with -fsanitize=address,undefined by tests/test_planner_slices.py; exit status 0 and the
-// line "plan pool ok" mean every check held.
+// slice the model drew for it.  The same walk runs over two shapes of pool: 256 blocks of 16 slots (the pool whose requests ride
+// the stream) and one block of 5 slots (the kind mgx_plan_paths builds for a call; here it is full most of the time, and a submit
+// finds every slot pending or cooling).  Built with -fsanitize=address,undefined by tests/test_planner_slices.py; exit status 0
+// and a line "plan pool ok" per shape mean every check held.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
@@ -35,10 +37,10 @@ struct Model {
     uint32_t slot;
 };
 
-int main(int argc, char **argv) {
-    const int steps = argc > 1 ? std::atoi(argv[1]) : 10000;
-    std::mt19937_64 rng(argc > 2 ? (uint64_t)std::atoll(argv[2]) : 12345u);
-    PlanPoolBook book;
+static int walk(const int steps, const uint64_t seed, const uint32_t slots_per_block, const uint32_t max_blocks) {
+    std::mt19937_64 rng(seed);
+    PlanPoolBook book(slots_per_block, max_blocks);
+    const uint32_t most = std::min(200u, book.max_slots());
     std::map<uint64_t, Model> live;      // submitted, neither collected nor cancelled
     std::set<uint64_t> gone;             // collected or cancelled
     std::deque<Launch> flight;           // enqueued, not completed
@@ -50,11 +52,15 @@ int main(int argc, char **argv) {
         const unsigned op = (unsigned)(rng() % 100);
         if (op < 30) {  // submit 1..5
             const unsigned n = 1 + (unsigned)(rng() % 5);
-            for (unsigned i = 0; i < n && book.pending() < 200; i++) {
+            for (unsigned i = 0; i < n && book.pending() < most; i++) {
                 int s = book.take_slot();
+                if (s < 0 && book.blocks() == book.max_blocks) {  // every slot is pending or cooling: the submit is refused
+                    CHECK(book.cooling.size() + live.size() == book.slots.size() && !book.cooling.empty());
+                    break;
+                }
                 if (s < 0) {
-                    CHECK(book.blocks() < PlanPoolBook::MAX_BLOCKS);
                     book.add_block();
+                    CHECK(book.slots.size() == (size_t)book.blocks() * slots_per_block);
                     s = book.take_slot();
                 }
                 CHECK(s >= 0 && (size_t)s < book.slots.size());
@@ -139,11 +145,22 @@ int main(int argc, char **argv) {
         CHECK(book.ended.size() == live.size() - running);
         CHECK(book.free_list.size() + book.cooling.size() + live.size() == book.slots.size());
     }
-    // drop keeps the ticket counter
+    CHECK(book.slots.size() <= book.max_slots());
+    // drop keeps the ticket counter and the shape; reset sets another shape
     book.drop();
     CHECK(book.pending() == 0 && book.slots.empty() && book.next_ticket == last_ticket + 1);
+    CHECK(book.slots_per_block == slots_per_block && book.max_blocks == max_blocks);
+    book.reset(slots_per_block + 1, 1);
+    CHECK(book.max_slots() == slots_per_block + 1 && book.slots.empty() && book.next_ticket == last_ticket + 1);
     CHECK(collected > 100 && cancelled > 100 && reused > 100);
-    std::printf("plan pool ok: %d steps, %llu tickets, %llu collected, %llu cancelled, %llu slots taken again\n", steps,
-                (unsigned long long)last_ticket, (unsigned long long)collected, (unsigned long long)cancelled, (unsigned long long)reused);
+    std::printf("plan pool ok, %u x %u slots: %d steps, %llu tickets, %llu collected, %llu cancelled, %llu slots taken again\n", max_blocks,
+                slots_per_block, steps, (unsigned long long)last_ticket, (unsigned long long)collected, (unsigned long long)cancelled, (unsigned long long)reused);
     return 0;
+}
+
+int main(int argc, char **argv) {
+    const int steps = argc > 1 ? std::atoi(argv[1]) : 10000;
+    const uint64_t seed = argc > 2 ? (uint64_t)std::atoll(argv[2]) : 12345u;
+    const int rc = walk(steps, seed, 16, 256);
+    return rc ? rc : walk(steps, seed, 5, 1);
 }

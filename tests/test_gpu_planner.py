@@ -206,3 +206,76 @@ def test_beside_the_environment_pass_and_the_layout(solo, expected):
             w.env_collisions_enable(None)      # either goes without the other
             _same(w.plan_paths(reqs[:1])[0], None, ref[0])
     assert logs[0] == logs[1]
+
+
+# ---- the call is the pool driven to the end: one block of as many slots as the largest call so far (Planner::call) ---------------
+def test_calls_grow_and_shrink(solo, expected):
+    """1, then 4, then 2 requests on one world: the pool of the call is built again for the larger call and keeps its size for the
+    smaller one; a request's tree is found through the slot it got, and only the last call's requests have one"""
+    p, reqs, ref = expected["dense"]
+    w = _world()
+    w.planner_enable(solo[0], p)
+    for n in (1, 4, 2):
+        res = w.plan_paths(reqs[:n])
+        assert len(res) == n
+        for i in range(n):
+            _same(res[i], w.plan_tree(i), ref[i])
+    with pytest.raises(hostlib.MgxError, match="request 2: the last mgx_plan_paths had 2"):
+        w.plan_tree(2)
+    assert w.plan_paths([]) == []
+    with pytest.raises(hostlib.MgxError, match="request 0: the last mgx_plan_paths had 0"):
+        w.plan_tree(0)
+
+
+def test_more_requests_than_a_block_of_the_riding_pool(solo, expected):
+    """20 requests, more than the 16 slots of a block of the pool that rides the stream: the call's pool is one block of 20"""
+    p = dict(expected["dense"][0], max_iterations=300)
+    reqs = [(DENSE[i % len(DENSE)][0], DENSE[i % len(DENSE)][1], 100 + i) for i in range(20)]
+    ref = gp.plan_paths(solo[0], reqs, p)
+    res, trees = _plan(_world(), solo[0], p, reqs)
+    assert len(res) == len(ref) == 20
+    for d, t, r in zip(res, trees, ref):
+        assert d["status"] == r["status"] == gp.PLAN_MAX_ITERATIONS
+        _same(d, t, r)
+
+
+def test_a_call_does_not_disturb_pending_requests(solo, expected):
+    """the call has a pool of its own: what rides the stream keeps its tickets and its slice numbers, and is not advanced"""
+    p, reqs, ref = expected["dense"]
+    w = _world()
+    w.planner_enable(solo[0], p)
+    assert w.plan_submit(reqs[:2]) == [1, 2]
+    for _ in range(2):
+        w.plan_advance(7)
+    res = w.plan_paths(reqs[2:])  # (iterations_per_launch is the default, 1024)
+    assert p["iterations_per_launch"] in (0, 1024) and w.plan_pending() == 2
+    for i, d in enumerate(res):
+        _same(d, w.plan_tree(i), ref[2 + i])
+    want = {1 + i: gp.slices_needed(ref[i], p, 7) for i in range(2)}
+    assert min(want.values()) > 2
+    got = []
+    for _ in range(max(want.values()) - 2):
+        w.plan_advance(7)
+        got += w.plan_collect(wait=True)
+    assert w.plan_pending() == 0 and {d["ticket"]: d["slices"] for d in got} == want
+    for d in got:
+        _same(d, None, ref[d["ticket"] - 1])
+    assert w.plan_submit(reqs[:1]) == [3]
+
+
+def test_a_call_too_large_to_allocate_leaves_smaller_calls_working(solo, expected):
+    """2^20 requests with trees of 8192 nodes ask for 300 GB in one allocation: the call is refused with the runtime's error, the
+    pool it tried to build is gone, and the same world plans a small call afterwards (as the caller's retry in batches would)"""
+    p, reqs, ref = expected["dense"]
+    w = _world()
+    w.planner_enable(solo[0], dict(p, max_nodes=8192))
+    _same(w.plan_paths(reqs[:1])[0], w.plan_tree(0), ref[0])
+    req = np.zeros(1 << 20, hostlib.plan_request_dtype())
+    req["wyrand_state"] = 1
+    rc, _, _, _ = w.plan_paths_raw(req, 1)
+    assert rc < 0 and b"hipMalloc" in w._L.mgx_last_error()
+    with pytest.raises(hostlib.MgxError, match="the last mgx_plan_paths had 0"):
+        w.plan_tree(0)
+    res = w.plan_paths(reqs[:2])
+    for i in range(2):
+        _same(res[i], w.plan_tree(i), ref[i])

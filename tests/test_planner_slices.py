@@ -115,11 +115,12 @@ def test_calls_without_a_world_fail_before_the_device():
 
 def test_pool_bookkeeping_under_sanitizers(tmp_path):
     """slots in blocks, the free list, ticket -> slot, the order of collect, cancel, cooling until the slices in flight have
-    completed: 10 000 random steps, two seeds, as a program of its own (host code only)"""
+    completed: 10 000 random steps, two seeds, over two shapes of pool (16 x 256, and one block of 5 slots as a call's pool is
+    one block), as a program of its own (host code only)"""
     exe = str(tmp_path / "plan_pool_fuzz")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                     "-static-libasan", "-static-libubsan",  # (a program of its own: nothing of the runtimes is looked up when it starts)
                     os.path.join(ROOT, "tests", "c_abi", "plan_pool_fuzz.cpp"), "-o", exe], check=True)
     for seed in ("12345", "99"):
         r = subprocess.run([exe, "10000", seed], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-        assert r.returncode == 0 and b"plan pool ok" in r.stdout, r.stdout.decode()
+        assert r.returncode == 0 and r.stdout.count(b"plan pool ok") == 2, r.stdout.decode()  # (one line per shape)
