@@ -922,6 +922,56 @@ int mgx_env_collisions_read(mgx_world *w, uint64_t first, mgx_env_collision_even
                             uint64_t *n_total, uint64_t *dropped, uint32_t *per_robot);
 int mgx_env_collisions_clear(mgx_world *w);
 
+/* ---- trackers on the device: position and velocity samples, distance travelled ---------------------------------
+ * track_positions / track_velocities (crates/magics/src/planner/tracking.rs:117-136, 210-240; both on 100 ms timers,
+ * planner/spawner.rs:627-628) and the distance travelled the export carries (export.rs:249-262), restated on the host by
+ * magics_amd/sim.py (_track / _tracks) and magics_amd/driver.py (Driver.tick), which are the checkers.
+ * STATE per robot id (ids are stable and never reused): elapsed_ns (0), a has-previous flag with the previous sample's position
+ *   (f32[3]) and tick, travelled (f64, 0).  Robots added after _enable start from zero state, the others keep theirs — through an
+ *   in-place append, a relayout, or a join between mgx_mission_tick_begin and _end: the arrays are no part of the blob layout.
+ * CLOCK: one u64 per world, the simulated tick index k of the coming tick; the time of tick k is
+ *   t(k) = (double)((k + 1) * tick_ns) * 1e-9 — the integer product is exact, there is ONE f64 multiplication.
+ * A PASS takes a tick k, positions [n][3] as f32 and a "moved this tick" byte per robot.  For every robot that moved:
+ *   elapsed_ns += tick_ns; if elapsed_ns < period_ns nothing else happens, otherwise elapsed_ns %= period_ns and ONE sample is
+ *   taken (at most one per tick): {tick = k, robot, position = p, span_ticks = k - previous tick (0: the robot's first sample)}
+ *   and, when span_ticks != 0, velocity[c] = (p[c] - prev[c]) / (float)(t(k) - t(k - span_ticks)), c = 0..2: the difference of
+ *   the times in f64, rounded to f32 once; the subtraction and the division each rounded to f32 on their own, the division
+ *   correctly rounded, nothing contracted — libmgx.so and libmgx_fma.so agree bit for bit.  Then prev = (p, k), also when the
+ *   log is full, so that later velocities stay right.  Robots that did not move keep their timers: idle, completed and removed
+ *   robots take no sample.
+ * DISTANCE is accumulated in the mission chain only, every tick, for every robot that moves, whatever its timer says:
+ *   c0 = ts * (mu_x[1] - mu_x[0]), c1 likewise for y — the values k_mission_prepare casts into the Transform (robot.rs:2314) —
+ *   travelled += sqrt(c0*c0 + c1*c1), every operation rounded to f64 on its own, no FMA in either library.
+ * LOG: append-only in device memory, sample_capacity records allocated by _enable (0: 262144), never growing.  A sample that
+ *   finds the log full is counted in `dropped`, not stored; which samples of the overflowing tick are kept is unspecified.
+ * mgx_tracks_enable(w, 1, period_ns, tick_ns, next_tick, sample_capacity): on (default: off — no kernel, no allocation);
+ *   period_ns and tick_ns > 0.  While on, every mgx_mission_tick_end (so every mgx_mission_tick and every tick of
+ *   mgx_mission_run) enqueues ONE pass on the world's stream over the Transforms after that tick's move, with "moved" = the
+ *   robots the tick moves, behind the Transform increment and in front of the prior updates; the clock then advances by one.
+ *   No synchronisation, nothing read back.  Enabling again while on keeps everything and sets the clock (other timers or
+ *   another capacity: MGX_ERR_STATE).  enabled = 0 drops the state.
+ * mgx_tracks_set_clock: the tick index of the coming tick.
+ * mgx_tracks_update: the same sampling pass over positions the caller keeps, at a tick the caller names (positions_xyz NULL: the
+ *   device's mission Transforms; moved NULL: every live robot; a removed robot never moves).  Adds no distance, does not move
+ *   the clock; enqueued, not waited for.
+ * mgx_tracks_take: the one call that synchronises.  *n_in_log and *dropped are always filled, travelled [n_robots] if given.  If
+ *   capacity >= *n_in_log the whole log is copied out in (tick, robot) order and emptied (*n_taken = *n_in_log; per-robot
+ *   state, distances and `dropped` stay); otherwise nothing is taken and *n_taken = 0 — capacity 0 asks for the size.
+ * mgx_tracks_clear: the log empty, `dropped` and the distances zero, every robot's timer and previous sample forgotten.
+ * Unsharded worlds (MGX_ERR_STATE on a world with ghosts); MGX_ERR_STATE from every other call while switched off. */
+typedef struct mgx_track_sample {   /* 40 bytes */
+    uint64_t tick;
+    int32_t  robot;
+    uint32_t span_ticks;            /* 0: first sample of this robot, velocity not set (zeros) */
+    float    position[3], velocity[3];
+} mgx_track_sample;
+int mgx_tracks_enable(mgx_world *w, int32_t enabled, uint64_t period_ns, uint64_t tick_ns, uint64_t next_tick, uint64_t sample_capacity);
+int mgx_tracks_set_clock(mgx_world *w, uint64_t next_tick);
+int mgx_tracks_update(mgx_world *w, const float *positions_xyz, const uint8_t *moved, uint64_t tick);
+int mgx_tracks_take(mgx_world *w, mgx_track_sample *samples, uint64_t capacity, uint64_t *n_taken, uint64_t *n_in_log,
+                    uint64_t *dropped, double *travelled /* [n_robots] or NULL */);
+int mgx_tracks_clear(mgx_world *w);
+
 /* ---- global planner: batched RRT* over the map's colliders -------------------------------------------------------
  * What crates/gbp_global_planner does for one robot (rrtstar.rs:15-83; started from progress_missions, robot.rs:578-633),
  * for many requests in one call: a formation spawns and every robot of it asks at once.  The paths it returns are what

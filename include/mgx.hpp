@@ -305,6 +305,34 @@ public:
         return out;
     }
     void env_collisions_clear() { check(mgx_env_collisions_clear(w_)); }
+    /// the trackers on the device (planner/tracking.rs:117-136, 210-240, specified in mgx.h): while enabled every mission tick ends
+    /// with one pass — a sample of every moving robot every `period_ns` and its distance travelled; `update` is the sampling pass
+    /// over Transforms the caller keeps; `take` is the one call that waits for the device and empties the log
+    void tracks_enable(bool enabled, uint64_t period_ns, uint64_t tick_ns, uint64_t next_tick = 0, uint64_t sample_capacity = 0) {
+        check(mgx_tracks_enable(w_, enabled ? 1 : 0, period_ns, tick_ns, next_tick, sample_capacity));
+    }
+    void tracks_set_clock(uint64_t next_tick) { check(mgx_tracks_set_clock(w_, next_tick)); }
+    void tracks_update(uint64_t tick, const std::vector<std::array<float, 3>> &translations, const std::vector<uint8_t> &moved) {
+        check(mgx_tracks_update(w_, translations.empty() ? nullptr : translations[0].data(), moved.empty() ? nullptr : moved.data(), tick));
+    }
+    struct Tracks {
+        std::vector<mgx_track_sample> samples;  ///< the whole log, in (tick, robot) order
+        uint64_t dropped = 0;
+        std::vector<double> travelled;          ///< per robot
+    };
+    Tracks tracks_take() {
+        Tracks out;
+        uint32_t n = 0;
+        uint64_t taken = 0, in_log = 0;
+        check(mgx_num_robots(w_, &n, nullptr));
+        out.travelled.assign(n, 0.0);
+        check(mgx_tracks_take(w_, nullptr, 0, &taken, &in_log, &out.dropped, nullptr));
+        out.samples.resize((size_t)in_log);
+        check(mgx_tracks_take(w_, out.samples.data(), out.samples.size(), &taken, &in_log, &out.dropped, out.travelled.data()));
+        out.samples.resize((size_t)taken);
+        return out;
+    }
+    void tracks_clear() { check(mgx_tracks_clear(w_)); }
     /// the global planner (batched RRT* over the colliders of `env`, specified in mgx.h); nullptr switches it off
     void planner_enable(const mgx_env_desc *env, const mgx_plan_params &params) { check(mgx_planner_enable(w_, env, &params)); }
     struct Plans {

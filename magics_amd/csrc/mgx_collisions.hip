@@ -12,7 +12,7 @@
 //     counts once for robot a and once for robot b.
 //   * a pair that parts, or loses a robot, is Free again.
 // Robot-environment collisions are the second half of this file (k_env_collisions: its own state, log and calls).  The
-// position / velocity tracker samples stay on the host.
+// position / velocity tracker samples are a pass of their own beside these two (mgx_tracks.hip).
 //
 // STATE (all keyed by robot ID, so nothing moves when the world lays its arrays out again; CollDev, mgx_dev.h):
 //   bits   one bit per ordered pair (a * stride + b): the pair overlapped after the last pass

@@ -344,6 +344,35 @@ struct EnvCollDev : ContactDev {  // words[1]: a robot touched more than the slo
 };
 static_assert(sizeof(CollDev) == 128 && sizeof(EnvCollDev) == 152, "kernel arguments by value: no larger than before the fold");
 
+// Trackers on the device (mgx_tracks.hip, which says what a pass does): per-robot state and the sample log, keyed by robot id.
+struct TrackState {            // 40 bytes; all zero: a robot nobody has sampled yet
+    unsigned long long elapsed_ns;  // the 100 ms timer's remainder
+    unsigned long long prev_tick;   // tick of the last sample
+    float prev[3];             // ... and its position
+    uint32_t has_prev;
+    double travelled;          // sum of the Transform increments' lengths (mission chain only)
+};
+struct TrackSample {           // == mgx_track_sample (include/mgx.h; mgx_tracks.hip asserts it)
+    unsigned long long tick;
+    int32_t robot;
+    uint32_t span_ticks;
+    float position[3], velocity[3];
+};
+struct TrackDev {
+    TrackState *state;         // [n]
+    TrackSample *log;          // [cap]
+    unsigned long long cap;
+    unsigned long long *cursor;  // samples claimed since the log was last emptied (keeps counting beyond cap)
+    unsigned long long period_ns, tick_ns, tick;
+    const float *pos;          // [n][3]
+    const uint8_t *moved;      // [n] non-zero: the robot moved this tick
+    // the mission chain's pass only (blob == null: no distance): the increment k_mission_prepare formed, from the same means
+    const double *blob;
+    const double *time_scale;  // [n]
+    int BS, K;
+    int n;
+};
+
 // The map's side of EnvCollDev on its own: what a kernel needs to test a ball against the colliders (mgx_env_contact.h).  The
 // global planner's feasibility test reads it (mgx_planner.hip).
 struct EnvMapDev {

@@ -231,6 +231,13 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     if (w->coll.enabled && (rc = collisions_pass(w, ms.translation_d.p, ms.moving_d.p, s)) != MGX_OK) return rc;
     // update_robot_environment_collisions (collisions.rs:368-438), beside it on the same stream (mgx_env_collisions_read)
     if (w->envcoll.enabled && (rc = env_collisions_pass(w, ms.translation_d.p, ms.moving_d.p, s)) != MGX_OK) return rc;
+    // track_positions / track_velocities (tracking.rs:117-136, 210-240) and the distance travelled, for the robots k_mission_prepare
+    // has just moved (its `what` flags): in front of the prior updates, which change the means the increment is formed from
+    // again — no synchronisation, nothing read back (mgx_tracks_take).  The world's clock then names the coming tick
+    if (w->tracks.enabled) {
+        if ((rc = tracks_pass(w, ms.translation_d.p, ms.what_d.p, w->tracks.clock, true, s)) != MGX_OK) return rc;
+        w->tracks.clock += 1;
+    }
     // the Transforms after this tick's move travel to the host behind the launch: complete at the next synchronisation
     // (the next tick's own one), read without one by mgx_mission_translations
     if (ms.tr_cap < (size_t)R) {

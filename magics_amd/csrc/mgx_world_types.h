@@ -78,6 +78,8 @@ int env_red_plane(const mgx_env_desc *d, uint32_t resolution, float expansion, f
 hipError_t launch_collisions_pass(const CollDev &c, bool grid, double cell, uint32_t n_buckets, hipStream_t s);
 hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s);
 hipError_t launch_env_collisions_pass(const EnvCollDev &c, hipStream_t s);
+// mgx_tracks.hip
+hipError_t launch_tracks_pass(const TrackDev &t, hipStream_t s);
 // mgx_planner.hip
 hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s);
 }  // namespace mgx
@@ -784,6 +786,21 @@ struct mgx_world {
         DevBuf<int32_t> touching;
         EnvCollDev d{};
     } envcoll;
+    // trackers on the device (mgx_tracks_*, mgx_world_tracks.inc, mgx_tracks.hip): per-robot state keyed by robot id — no part of the
+    // blob layout, so a relayout moves nothing here and robots that join only make the array grow, zeroed — the sample log and
+    // the world's clock
+    struct Tracks {
+        bool enabled = false;
+        size_t n_sized = 0;      // robots the state array has been sized for
+        DevBuf<TrackState> state;
+        DevBuf<TrackSample> log;
+        DevBuf<unsigned long long> cursor;
+        DevBuf<float> pos;       // positions the caller handed in (mgx_tracks_update)
+        DevBuf<uint8_t> moved;   // ... and who moved then
+        uint64_t log_cap = 0, period_ns = 0, tick_ns = 0;
+        uint64_t clock = 0;      // the simulated tick index of the coming tick
+        uint64_t dropped = 0;    // samples that found the log full, up to the last time it was emptied
+    } tracks;
     // the global planner (mgx_planner_enable, mgx_world_planner.inc): the map and two pools of requests.  `pool`: the requests that
     // ride the stream (mgx_plan_submit / _advance / _collect), 256 blocks of 16 slots.  `call`: the requests of one mgx_plan_paths,
     // which gives its slots up before it returns — one block, sized by the largest call so far; the arrays of given-up slots are

@@ -16,6 +16,8 @@ Missions are plain waypoint lists (the reference's `Mission` with one route, pla
 """
 import numpy as np
 
+from . import hostlib
+
 F32 = np.float32
 
 
@@ -176,11 +178,16 @@ class DeviceDriver:
     reached-when rules and Transforms are handed over once, and a tick is ONE call — reached_waypoint, the topology
     pass on the device's Transforms, the comms draws, both prior updates with the Transform increment and the GBP
     schedule — with one synchronisation inside (the neighbour rows of the connection bookkeeping) and no belief
-    read-back at all.  Engine worlds only; `Driver` above on the CPU oracle is its checker (tests/test_gpu_driver.py)."""
+    read-back at all.  Engine worlds only; `Driver` above on the CPU oracle is its checker (tests/test_gpu_driver.py).
+    tracks=True: the trackers run on the device too (mgx_tracks_*): summary() carries `distance_travelled` as Driver's does, and
+    the position / velocity samples taken every 100 ms of simulated time collect in `track_samples`."""
 
     def __init__(self, world, n_robots, K, waypoints, radii, t0, steps, comms_radius, target_speed, hz=10.0,
-                 height=0.5, despawn_when_finished=True, failure_draws=None, idle=()):
+                 height=0.5, despawn_when_finished=True, failure_draws=None, idle=(), tracks=False):
         self.w, self.n, self.K = world, n_robots, K
+        self.tracks, self.track_samples, self.travelled = bool(tracks), [], np.zeros(n_robots)
+        if self.tracks:
+            world.tracks_enable(True, period_ns=100_000_000, tick_ns=int(round(1e9 / hz)), next_tick=0)
         for r in idle:  # MissionState::Idle: the device missions wait (k_mission_reached, k_mission_prepare)
             world.set_idle(int(r), True)
         self.dt32 = F32(1.0) / F32(hz)
@@ -244,12 +251,27 @@ class DeviceDriver:
         """Ticks until every robot has finished (or max_ticks), looking at the missions every `check_every` ticks."""
         while self.tick_no < max_ticks:
             self.tick()
-            if self.tick_no % check_every == 0 and not (self.finished_at < 0).any():
-                break
+            if self.tick_no % check_every == 0:
+                self._take_tracks()  # (the look at the missions below waits for the device anyway)
+                if not (self.finished_at < 0).any():
+                    break
         return self.summary()
+
+    def _take_tracks(self):
+        """the device's sample log -> track_samples, the distances so far -> travelled (synchronises)"""
+        if not self.tracks:
+            return
+        samples, _, dropped, dist = self.w.tracks_take()
+        if dropped:
+            raise hostlib.MgxError(f"the device's tracker log was full: {dropped} samples were not stored")
+        if len(samples):
+            self.track_samples.append(samples)
+        self.travelled = dist
 
     def summary(self):
         tr, left, fin = self.state()
         done = fin >= 0
+        self._take_tracks()
         return {"ticks": self.tick_no, "finished": int(done.sum()), "makespan_s": float(fin.max() * self.delta_t) if done.all() else None,
-                "finished_at_tick": fin.tolist(), "messages": [self.w.message_counts(r) for r in range(self.n)]}
+                "finished_at_tick": fin.tolist(), **({"distance_travelled": self.travelled.tolist()} if self.tracks else {}),
+                "messages": [self.w.message_counts(r) for r in range(self.n)]}

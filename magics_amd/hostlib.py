@@ -209,6 +209,11 @@ SYMBOLS = {
     "mgx_collisions_update": (C.c_int, [_V, C.c_void_p]),
     "mgx_collisions_read": (C.c_int, [_V, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     "mgx_collisions_clear": (C.c_int, [_V]),
+    "mgx_tracks_enable": (C.c_int, [_V, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
+    "mgx_tracks_set_clock": (C.c_int, [_V, C.c_uint64]),
+    "mgx_tracks_update": (C.c_int, [_V, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "mgx_tracks_take": (C.c_int, [_V, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
+    "mgx_tracks_clear": (C.c_int, [_V]),
     "mgx_num_robots": (C.c_int, [_V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mgx_last_launch_count": (C.c_int, [_V, C.POINTER(C.c_uint32)]),
     "mgx_last_sweep": (C.c_int, [_V, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -409,6 +414,17 @@ def env_collision_event_dtype():
     """numpy view of an array of mgx_env_collision_event"""
     import numpy as np
     return np.dtype([("pass", np.uint64), ("robot", np.int32), ("collider", np.int32), ("mins", np.float32, 2), ("maxs", np.float32, 2)])
+
+
+class TrackSample(C.Structure):
+    """mgx_track_sample (include/mgx.h)"""
+    _fields_ = [("tick", C.c_uint64), ("robot", C.c_int32), ("span_ticks", C.c_uint32), ("position", C.c_float * 3), ("velocity", C.c_float * 3)]
+
+
+def track_sample_dtype():
+    """numpy view of an array of mgx_track_sample"""
+    import numpy as np
+    return np.dtype([("tick", np.uint64), ("robot", np.int32), ("span_ticks", np.uint32), ("position", np.float32, 3), ("velocity", np.float32, 3)])
 
 
 PLAN_OK, PLAN_MAX_ITERATIONS, PLAN_TREE_FULL = 0, 1, 2

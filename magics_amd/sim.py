@@ -100,7 +100,7 @@ def _take_in(table, read, a, b, what):
 
 class Simulation:
     def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None,
-                 environment_collisions=False, global_planner=None, planner_overrides=None, plan_budget=64):
+                 environment_collisions=False, global_planner=None, planner_overrides=None, plan_budget=64, device_trackers=None):
         """scenario: `config.load_scenario(dir)` (or a dict of the same shape); world: a fresh
         World-like object created with `config.world_params(scenario["config"])`.
         device_missions (default: whenever the world offers them, i.e. the engine): routes, reached-when rules and
@@ -113,6 +113,10 @@ class Simulation:
         environment_collisions (default off: the export keeps 0 / []): True — robot-environment collisions are counted, on the
         device (mgx_env_collisions_*) whenever the missions live there, otherwise by _collide_environment on the host; "host" —
         the host pass whatever the missions do (the checker of the device pass).
+        device_trackers (default: whenever the missions live on the device and the world offers tracks_enable): the position /
+        velocity samples and the distance travelled are made on the device at the end of every tick (mgx_tracks_*) and taken
+        into the robots' `positions` / `velocities` / `travelled` when somebody asks; no tick then brings Transforms to the
+        host unless a host collision pass needs them.  False: _track / _tracks below on the host (the checker).
         global_planner (default None: `planning-strategy: rrt-star` raises NotImplementedError): True — robots of that strategy spawn
         Idle (RobotBundle::new, robot.rs:1195, 1294), their requests (taskpoints[0] -> taskpoints[1], a clone of the robot's forked
         stream, config.rrt) are planned in the tick they spawn, all of a tick in ONE mgx_plan_paths, and the paths are applied by ONE
@@ -135,6 +139,11 @@ class Simulation:
         if self._dev_coll and not self.dev:
             raise ValueError("device_collisions needs device_missions (the pass reads the device's Transforms)")
         self._coll_cursor = 0      # events of the device's log already taken into `collisions`
+        self._dev_trk = (self.dev and hasattr(world, "tracks_enable")) if device_trackers is None else bool(device_trackers)
+        if self._dev_trk and not self.dev:
+            raise ValueError("device_trackers needs device_missions (the pass reads the device's Transforms)")
+        self._trk_clock_set = False  # the device's clock has been set to tick_no (when the first robots tick)
+        self._trk_bound = 0          # samples the device's log holds at the most since it was last taken
         if environment_collisions not in (False, True, "host"):
             raise ValueError('environment_collisions: False, True or "host"')
         self._env_coll = bool(environment_collisions)
@@ -185,6 +194,8 @@ class Simulation:
             world.env_collisions_enable(self.env)
         elif self._env_coll:
             self._colliders, self._collider_vertices = hostlib.env_colliders(self.env)
+        if self._dev_trk:
+            world.tracks_enable(True, period_ns=self.TRACK_PERIOD_NS, tick_ns=self.dt_ns, next_tick=0, sample_capacity=self.TRACK_LOG_SAMPLES)
         if self._planner is not None:
             from . import global_planner as _gp
             self._plan_params = _gp.params_from_config(self.cfg, **(planner_overrides or {}))
@@ -197,6 +208,8 @@ class Simulation:
                 world.planner_set_tick_budget(self._plan_budget)
         self.entities = spawner.EntityAllocator()  # the robots' Entity bits = their graphs' order (id.rs:19-54)
 
+    TRACK_PERIOD_NS = 100_000_000  # the trackers' timers (spawner.rs:627-628)
+    TRACK_LOG_SAMPLES = 1 << 18    # room of the device's sample log: drained before it can fill
     RESERVE_LIMIT = 256  # robots reserved at most for formations that repeat forever (beyond it the engine doubles its head-room)
 
     def _robots_expected(self):
@@ -385,7 +398,11 @@ class Simulation:
             self._trk_log.append((ids, np.asarray(translation)[ids].copy(), now))
 
     def _tracks(self):
-        """bring every robot's positions / velocities up to the last tick noted by _track"""
+        """bring every robot's positions / velocities up to the last tick noted by _track (device trackers: up to the last tick
+        enqueued — the samples of the device's log, whose velocities are the device's own; `travelled` comes along)"""
+        if self._dev_trk:
+            self._tracks_device()
+            return
         log, self._trk_log = self._trk_log, []
         for ids, rows, now in log:
             for k, rid in enumerate(ids):
@@ -402,6 +419,39 @@ class Simulation:
                     r["velocities"].append({"velocity": [float(v[0]), float(v[1]), float(v[2])], "timestamp": now,
                                             "measured_over": {"secs": int(dt), "nanos": int(round((dt - int(dt)) * 1e9))}})
                 r["trk_prev"] = (pos, now)
+
+    def _tracks_device(self):
+        if not self._trk_clock_set:  # (no robot has ticked yet: nothing sampled, nothing travelled)
+            return
+        samples, _, dropped, dist = self.w.tracks_take()
+        self._trk_bound = 0
+        if dropped:
+            raise hostlib.MgxError(f"the device's tracker log was full: {dropped} samples were not stored")
+        for r, d in zip(self.robots, dist):
+            r["travelled"] = float(d)
+        for tick, rid, span, pos, vel in zip(samples["tick"].tolist(), samples["robot"].tolist(), samples["span_ticks"].tolist(),
+                                             samples["position"].tolist(), samples["velocity"].tolist()):
+            r = self.robots[rid]
+            r["positions"].append([pos[0], pos[2]])
+            if span:
+                now = (tick + 1) * self.dt_ns * 1e-9
+                dt = now - (tick - span + 1) * self.dt_ns * 1e-9
+                r["velocities"].append({"velocity": [vel[0], vel[1], vel[2]], "timestamp": now,
+                                        "measured_over": {"secs": int(dt), "nanos": int(round((dt - int(dt)) * 1e9))}})
+
+    def _tracks_room(self, ticks, robots):
+        """before `ticks` more ticks of `robots` live robots are enqueued: take the device's log in if they could fill it.  A
+        robot gives at most one sample per tick and, its timer's remainder being below the period, at most
+        ticks * dt_ns / period + 1 samples in `ticks` ticks."""
+        if not self._dev_trk:
+            return
+        if not self._trk_clock_set:
+            self.w.tracks_set_clock(self.tick_no)
+            self._trk_clock_set = True
+        most = robots * min(ticks, ticks * self.dt_ns // self.TRACK_PERIOD_NS + 1)
+        if self._trk_bound + most > self.TRACK_LOG_SAMPLES:
+            self._tracks_device()
+        self._trk_bound += most
 
     # update_robot_robot_collisions (planner/collisions.rs:72-140, FixedUpdate): every pair of live robots, bounding
     # spheres of their Ball(radius) at the Transform's (x, z) — parry2d 0.13 BoundingSphere::intersects, restated from its
@@ -464,18 +514,27 @@ class Simulation:
         launches (complete after the next synchronisation — the next tick's own, or an explicit one here)"""
         if self._pending_track is None:
             return
+        if not self._host_needs_transforms():  # (trackers and collision passes all on the device: nobody waits, nothing comes back)
+            self._pending_track = None
+            return
         if synchronise:
             self.w.synchronize()
         moving, now, alive = self._pending_track
         self._pending_track = None
         tr = self.w.mission_translations()
-        self._track(moving, tr, now)
+        if not self._dev_trk:
+            self._track(moving, tr, now)
         if not self._dev_coll:
             self._collide(alive, tr)
         self._collide_environment(alive, tr)
 
+    def _host_needs_transforms(self):
+        """a host tracker or a host collision pass still reads every tick's Transforms"""
+        return not self._dev_trk or not self._dev_coll or (self._env_coll and not self._dev_env_coll)
+
     def _tick_device(self):
         w = self.w
+        self._tracks_room(1, sum(1 for r in self.robots if r["alive"]))
         self.next_number, created, deleted, fin = w.mission_tick_begin(self.comms_radius, self.next_number, despawn_finished=self.despawn,
                                                                        method=self.method)
         self._flush_trackers()
@@ -571,9 +630,12 @@ class Simulation:
         for _ in range(m - 1):  # the real spawners live through the same frames (nothing happens in them)
             for sp in self.spawners:
                 sp.tick(self.dt_ns)
+        self._tracks_room(m, sum(1 for r in self.robots if r["alive"]))
+        host_tr = self._host_needs_transforms()
         out = self.w.mission_run(m, self.comms_radius, self.next_number, self.steps, float(self.max_speed), float(self.dt32),
                                  despawn_finished=self.despawn, method=self.method, failure_rate=self.failure_rate,
-                                 wyrand_state=self.rng.state, stop_when_all_finished=all(sp.exhausted() for sp in self.spawners))
+                                 wyrand_state=self.rng.state, stop_when_all_finished=all(sp.exhausted() for sp in self.spawners),
+                                 want_translations=host_tr)
         self.next_number, self.rng.state = out["next_number"], out["wyrand_state"]
         for j in range(out["ticks"]):
             if out["created"][j] or out["deleted"][j]:
@@ -585,13 +647,14 @@ class Simulation:
                 if self.despawn:
                     r["alive"] = False
                     self.entities.free(r["entity"])
-            live = [r for r in self.robots if r["alive"]]
-            moving = [r for r in live if not r["completed"] and not r["idle"]]
-            tr = out["translations"][j]
-            self._track(moving, tr, (self.tick_no + 1) * self.dt_ns * 1e-9)
-            if not self._dev_coll:
-                self._collide(live, tr)
-            self._collide_environment(live, tr)
+            if host_tr:
+                live = [r for r in self.robots if r["alive"]]
+                tr = out["translations"][j]
+                if not self._dev_trk:
+                    self._track([r for r in live if not r["completed"] and not r["idle"]], tr, (self.tick_no + 1) * self.dt_ns * 1e-9)
+                if not self._dev_coll:
+                    self._collide(live, tr)
+                self._collide_environment(live, tr)
             self.tick_no += 1
 
     def run(self, max_ticks=None, max_time=None, chunk=256):
@@ -607,6 +670,8 @@ class Simulation:
                 self.tick()
         if self.dev:
             self._flush_trackers(synchronise=True)
+        if self._dev_trk:
+            self._tracks()  # (`travelled` is up to date when run() returns)
         return self
 
     # -- export (export.rs:249-262, 283-620) ------------------------------------------------------------------

@@ -494,6 +494,48 @@ class World:
     def env_collisions_clear(self):
         self._chk(self._L.mgx_env_collisions_clear(self._w))
 
+    # -- trackers on the device (include/mgx.h, mgx_tracks_*): position / velocity samples and distance travelled
+    def tracks_enable(self, enabled=True, period_ns=100_000_000, tick_ns=0, next_tick=0, sample_capacity=0):
+        """while on, every mission tick ends with one tracker pass on the device (no synchronisation): a sample of every moving
+        robot's Transform every period_ns of simulated time, and the length of its Transform increment added to its distance"""
+        self._chk(self._L.mgx_tracks_enable(self._w, 1 if enabled else 0, int(period_ns), int(tick_ns), int(next_tick), int(sample_capacity)))
+
+    def tracks_set_clock(self, next_tick):
+        """the simulated tick index of the coming mission tick"""
+        self._chk(self._L.mgx_tracks_set_clock(self._w, int(next_tick)))
+
+    def tracks_update(self, tick, positions=None, moved=None):
+        """one sampling pass at `tick` over the caller's Transforms [n, 3] f32 (None: the device's mission Transforms) for the robots
+        with a non-zero `moved` byte (None: every live robot); adds no distance; enqueued, not waited for"""
+        n = self.num_robots()[0]
+        pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        mv = None if moved is None else np.ascontiguousarray(moved, dtype=np.uint8).reshape(-1)
+        if (pos is not None and len(pos) != n) or (mv is not None and len(mv) != n):
+            raise ValueError("one position and one moved byte per robot of the world")
+        self._chk(self._L.mgx_tracks_update(self._w, None if pos is None else pos.ctypes.data, None if mv is None else mv.ctypes.data, int(tick)))
+
+    def tracks_take(self, capacity=None, travelled=True):
+        """(samples in (tick, robot) order — a structured array with fields tick, robot, span_ticks, position [3], velocity [3] —,
+        samples that were in the log, samples dropped because it was full, distance travelled per robot or None).  Synchronises.
+        The log is emptied when it is handed out.  capacity (default: whatever the log holds): with less room than the log needs
+        nothing is taken and the samples come back empty."""
+        n = self.num_robots()[0]
+        dist = np.zeros(n, np.float64) if travelled else None
+        took, in_log, drop = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        dp = None if dist is None else dist.ctypes.data
+        buf = np.zeros(int(capacity) if capacity is not None else self._tracks_room, hostlib.track_sample_dtype())
+        self._chk(self._L.mgx_tracks_take(self._w, buf.ctypes.data if len(buf) else None, len(buf), C.byref(took), C.byref(in_log), C.byref(drop), dp))
+        if capacity is None and in_log.value > len(buf):  # (nothing was taken: once more with the room the log needs)
+            self._tracks_room = int(in_log.value) + int(in_log.value) // 4
+            buf = np.zeros(int(in_log.value), hostlib.track_sample_dtype())
+            self._chk(self._L.mgx_tracks_take(self._w, buf.ctypes.data, len(buf), C.byref(took), C.byref(in_log), C.byref(drop), dp))
+        return buf[:took.value], int(in_log.value), int(drop.value), dist
+
+    _tracks_room = 1024
+
+    def tracks_clear(self):
+        self._chk(self._L.mgx_tracks_clear(self._w))
+
     # -- the global planner (include/mgx.h): batched RRT* over the map's colliders
     def planner_enable(self, env, params=None):
         """env: an environment dict — its colliders go to the device; params: a dict as global_planner.params makes it (the fields

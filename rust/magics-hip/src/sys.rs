@@ -159,6 +159,17 @@ pub struct mgx_env_collision_event {
     pub maxs: [f32; 2],
 }
 
+/// one tracker sample (include/mgx.h, mgx_tracks_*): position and, from the robot's second sample on, velocity
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_track_sample {
+    pub tick: u64,
+    pub robot: i32,
+    pub span_ticks: u32,
+    pub position: [f32; 3],
+    pub velocity: [f32; 3],
+}
+
 /// the global planner's parameters (include/mgx.h, mgx_planner_enable)
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -344,6 +355,11 @@ extern "C" {
     pub fn mgx_env_collisions_update(w: *mut mgx_world, positions_xyz: *const f32) -> c_int;
     pub fn mgx_env_collisions_read(w: *mut mgx_world, first: u64, events: *mut mgx_env_collision_event, capacity: u64, n_total: *mut u64, dropped: *mut u64, per_robot: *mut u32) -> c_int;
     pub fn mgx_env_collisions_clear(w: *mut mgx_world) -> c_int;
+    pub fn mgx_tracks_enable(w: *mut mgx_world, enabled: i32, period_ns: u64, tick_ns: u64, next_tick: u64, sample_capacity: u64) -> c_int;
+    pub fn mgx_tracks_set_clock(w: *mut mgx_world, next_tick: u64) -> c_int;
+    pub fn mgx_tracks_update(w: *mut mgx_world, positions_xyz: *const f32, moved: *const u8, tick: u64) -> c_int;
+    pub fn mgx_tracks_take(w: *mut mgx_world, samples: *mut mgx_track_sample, capacity: u64, n_taken: *mut u64, n_in_log: *mut u64, dropped: *mut u64, travelled: *mut f64) -> c_int;
+    pub fn mgx_tracks_clear(w: *mut mgx_world) -> c_int;
     pub fn mgx_planner_enable(w: *mut mgx_world, env: *const mgx_env_desc, params: *const mgx_plan_params) -> c_int;
     pub fn mgx_plan_paths(w: *mut mgx_world, n: u32, requests: *const mgx_plan_request, results: *mut mgx_plan_result, path_xy: *mut f32, point_capacity: u32, n_points: *mut u32) -> c_int;
     pub fn mgx_plan_tree(w: *mut mgx_world, request: u32, capacity: u32, xy: *mut f64, parent: *mut i32, cost: *mut f64, n_nodes: *mut u32) -> c_int;

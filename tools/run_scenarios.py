@@ -5,7 +5,9 @@ finished, distance travelled (with --environment-collisions also the robot-envir
 host restatement; sliced: the engine's planner with the plans riding the ticks, --plan-budget N iterations per tick and request,
 default 64); --planner-half-extent H and --planner-max-iterations N replace the reference's +-2000 sampler and
 config.rrt.max-iterations.  Without it those scenarios are left out (named explicitly, they raise).
-usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [--global-planner [device|host|sliced]]
+--host-trackers keeps the position / velocity samples on the host (every tick's Transforms come back, and no distance is
+accumulated: mean_distance stays 0): for A/B runs against the device's trackers, which are the default.
+usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [--host-trackers] [--global-planner [device|host|sliced]]
            [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N] [scenario-dir | name ...]"""
 import json
 import os
@@ -24,6 +26,9 @@ if "--max-time" in args:
 env_collisions = "--environment-collisions" in args
 if env_collisions:
     args.remove("--environment-collisions")
+host_trackers = "--host-trackers" in args
+if host_trackers:
+    args.remove("--host-trackers")
 global_planner, overrides = None, {}
 if "--global-planner" in args:
     i = args.index("--global-planner")
@@ -48,7 +53,8 @@ for name in names:
     sc = config.load_scenario(name) if os.path.isdir(name) else known[name]
     t0 = time.perf_counter()
     s = sim.Simulation(sc, World(config.world_params(sc["config"])), environment_collisions=env_collisions,
-                       global_planner=global_planner, planner_overrides=overrides, plan_budget=plan_budget)
+                       global_planner=global_planner, planner_overrides=overrides, plan_budget=plan_budget,
+                       device_trackers=False if host_trackers else None)
     s.run(max_time=max_time)
     wall = time.perf_counter() - t0
     done = [r for r in s.robots if r["completed"]]
