@@ -184,7 +184,11 @@ int mgx_connections(mgx_world *w, int32_t robot, int32_t *others, uint32_t capac
 /* ---- the hot path ------------------------------------------------------------------ */
 /* iterate_gbp_v2 (robot.rs:1769-1861): runs `n` schedule steps, step i doing the
  * internal phase if steps[i] & MGX_STEP_INTERNAL and the external phase if
- * steps[i] & MGX_STEP_EXTERNAL.  Asynchronous on the world's stream. */
+ * steps[i] & MGX_STEP_EXTERNAL.  Asynchronous on the world's stream.
+ * While a resident launch lingers and has not yet taken the schedule posted before (LINGERING, POST MERGING below), the call
+ * RECORDS its schedule instead of waiting: it reaches the device with the caller's next call on this world, whichever that is,
+ * merged with its neighbours into one plan.  Results are the same bit for bit; a caller that issues schedules back to back and
+ * then goes silent ends with mgx_flush, mgx_synchronize or a read (any of them submits what is recorded). */
 int mgx_iterate(mgx_world *w, const uint8_t *steps, uint32_t n);
 /* Batches: several schedules, one submission.  A resident schedule launch pays for itself once — the robots' graphs go
  * HBM -> LDS when it starts and back when it ends, a sixth of a ten-iteration launch at 1000 x 16 — so a caller that issues
@@ -259,11 +263,37 @@ int mgx_last_search(mgx_world *w, int32_t *kernel, int32_t *row_cap, int32_t *n_
  * A posted schedule the launch did not take any more (it ended first) is run as a launch of its own — nothing lost, nothing
  * twice.  Launches linger only where the calling pattern promises schedules to come (two lingering launches in a row that ended
  * without a post switch it off until schedules are issued back to back again).
- * mgx_linger_stats: launches that lingered, schedules posted into them, posts taken back and re-run, launches that ended by
- * themselves (waited out their bound) while the host was about to post. */
+ * mgx_linger_stats: launches that lingered, schedules posted into them, posted schedules taken back and re-run (both count
+ * SCHEDULES, however many rode in one plan), launches that ended by themselves (waited out their bound) while the host was
+ * about to post.
+ * mgx_flush: everything issued so far is ENQUEUED — schedules mgx_iterate has recorded (below) are submitted, the launch is told
+ * to end — without waiting for the stream.  A caller that shares the world's stream with work of its own flushes first.
+ * mgx_set_linger: schedules already recorded are submitted under the old bound first.
+ *
+ * POST MERGING.  A lingering launch takes post P only when every workgroup has picked up plan P - 2, so a host that issues
+ * mgx_iterate back to back soon — from the fourth schedule behind a launch on — waits for the device with the next schedules
+ * already in hand.  Instead of waiting, mgx_iterate then records its schedule, and the recorded ones go out TOGETHER as one
+ * plan (up to 32 segments: three ticks of the 10 / 10 schedule) — with the first mgx_iterate that finds the post before taken,
+ * when one more would not fit, and in front of ANY other call on this world (mgx_tick, every query and read, mgx_flush,
+ * mgx_synchronize), which therefore finds the world as if every schedule had run when it was issued.  iterate(a); iterate(b) computes what iterate(a ++ b) computes, bit for bit (batches,
+ * above); what is saved is the plan boundary between them: every belief image through HBM and back, three barriers, a poll.
+ * The one visible difference: a recorded schedule is on the device only after the caller's NEXT call on the world.  A caller
+ * that issues five or more schedules back to back and then goes silent — no flush, synchronize or read — leaves the last ones
+ * unsubmitted: the launch (which holds at least two plans of work at that moment) waits out its bound and ends, and the recorded
+ * schedules run as a launch with the next call.  Same results, later.  The reference's pattern — one tick, then a read — never
+ * has a post outstanding at its next call and is unaffected; mgx_tick is never recorded (its prior updates belong to its first
+ * sweep), nor are schedules on sharded worlds (their launches do not linger).
+ * mgx_set_post_merge: 0 = off (every schedule its own post, waited for); 1 = automatic (default; MGX_POST_MERGE in the
+ * environment, < 0 here: ask it again): record while the post before is untaken, and only schedules that would have been posted
+ * on their own; 2 = record whenever a launch lingers and the plan fits, whatever the device has taken, a schedule that opens
+ * with an external iteration included behind others — deterministic, for tests and diagnostics.
+ * mgx_post_merge_stats: plans posted (mgx_tick's among them, one schedule each; an explicit batch's plan counts as one schedule),
+ * schedules in them, schedules in the largest.  Any pointer may be NULL. */
 int mgx_flush(mgx_world *w);
 int mgx_set_linger(mgx_world *w, int32_t microseconds /* < 0: default (environment) */);
 int mgx_linger_stats(mgx_world *w, uint64_t *launches, uint64_t *posts, uint64_t *reruns, uint64_t *ended_by_device);
+int mgx_set_post_merge(mgx_world *w, int32_t mode /* 0 off, 1 automatic, 2 always; < 0: default (environment) */);
+int mgx_post_merge_stats(mgx_world *w, uint64_t *plans_posted, uint64_t *schedules_in_them, uint64_t *largest);
 /* Per-world switch for the above (default: on): 0 keeps every schedule of THIS world on the launch-per-segment path — what
  * MGX_PERSISTENT=0 does for the whole process.  For measuring one against the other; results are identical either way.
  * On a sharded world with resident launches agreed on (mgx_halo_resident_connect_peers) every rank has to switch alike.

@@ -184,6 +184,8 @@ public:
     /// everything issued so far is enqueued: a lingering launch is told to end (no wait); how long launches linger (us, 0: never)
     void flush() { check(mgx_flush(w_)); }
     void set_linger(int32_t microseconds) { check(mgx_set_linger(w_, microseconds)); }
+    /// back-to-back schedules merged into one post: 0 off, 1 while the launch is behind (default), 2 whenever they fit
+    void set_post_merge(int32_t mode) { check(mgx_set_post_merge(w_, mode)); }
     /// FactorGraph::change_factor_enabled (factorgraph.rs:1529-1539) for every graph: MGX_FACTOR_* bits
     void change_factor_enabled(uint32_t kind_mask) { check(mgx_set_enabled(w_, kind_mask)); }
     /// FactorGraph::update_inter_robot_safety_distance_multiplier (factorgraph.rs:892-910) for every graph and for factors

@@ -54,6 +54,51 @@ struct Backoff {
     void went_ahead() { len = 0; }
 };
 
+// A plan that can be POSTED into a launch that lingers: it fits the box's plan, and it opens with an internal iteration (a post
+// CONTINUES the last segment of the plan before it).
+inline bool linger_plan_fits(const std::vector<Launch> &plan) {
+    if (plan.empty() || plan.size() > (size_t)MAX_SEGS || plan[0].ext) return false;
+    for (const Launch &l : plan)
+        if (l.n_int > 255) return false;
+    return true;
+}
+
+// Merging back-to-back schedules into one post (mgx_iterate, mgx_set_post_merge).  While the launch that lingers is behind — the
+// post before this call's has not been taken yet — the host would only spin; it records the schedule instead, and what is
+// recorded rides with a later call's schedule as ONE plan: iterate(a); iterate(b) computes what iterate(a ++ b) computes, and
+// the plan boundary between them (a trip of every belief image through HBM, three barriers, a poll) is never paid.
+//   launch_open    a launch lingers, its census is confirmed and it has not ended (read once, never waited for)
+//   outstanding    the place of the outstanding post among its launch's posts (1: the first behind the launch's own plan);
+//                  0: no post is outstanding
+//   taken          the launch has taken that post (read once, never waited for)
+//   qualifies      the world can take a post at all (nothing dirty, nothing thawing, resident launches on, no back-off)
+//   held           schedules are recorded already (their plan alone could be posted: that is why they were)
+//   fresh          the plan of this call's schedule alone
+//   merged         the plan of the recorded schedules ++ this call's (== fresh where nothing is recorded)
+// SUBMIT: recorded ++ this call's schedule go out now, as one plan.  DEFER: this call's schedule is recorded behind the others.
+// SUBMIT_RECORDED: what is recorded goes out alone (waiting as a post waits), then the call is decided again with nothing
+// recorded.  A schedule is only ever recorded where it could be posted with what it is recorded behind, so a schedule of more
+// than MAX_SEGS segments never is, and one that opens with an external iteration cannot be the first.  Mode AUTO records only
+// schedules that would have been posted on their own as well (so what is posted and what is launched does not depend on how far
+// behind the device happens to be: only how the posts are grouped does); mode ALWAYS lets a schedule that opens with an external
+// iteration follow in a merge, and records whatever was taken — deterministic, for tests and diagnostics.
+// Untaken BECAUSE THE LAUNCH IS BEHIND is what AUTO asks: the first two posts of a launch go into slots that are free whatever
+// the workgroups are doing — the postman takes them within a poll — so finding one of them untaken says nothing about the
+// device, and a schedule recorded behind it would only sit on the host (and, if the caller then went silent, miss the launch);
+// from the third on, a post waits for every workgroup to have picked up the plan two before it.  So a launch and three posts
+// go out singly, as ever.  A schedule without a single sweep is never recorded (it ends the launch, as ever).
+enum PostMergeMode : int32_t { POST_MERGE_OFF = 0, POST_MERGE_AUTO = 1, POST_MERGE_ALWAYS = 2 };
+enum class PostMerge { SUBMIT, DEFER, SUBMIT_RECORDED };
+inline PostMerge post_merge_decide(int32_t mode, bool launch_open, unsigned outstanding, bool taken, bool qualifies, bool held,
+                                   const std::vector<Launch> &fresh, const std::vector<Launch> &merged) {
+    if (fresh.empty()) return held ? PostMerge::SUBMIT_RECORDED : PostMerge::SUBMIT;
+    const bool post_untaken = outstanding > 2u && !taken;
+    const bool joins = linger_plan_fits(merged) && (mode == POST_MERGE_ALWAYS || linger_plan_fits(fresh));
+    if (held && !joins) return PostMerge::SUBMIT_RECORDED;
+    const bool record = mode != POST_MERGE_OFF && launch_open && qualifies && joins && (mode == POST_MERGE_ALWAYS || post_untaken);
+    return record ? PostMerge::DEFER : PostMerge::SUBMIT;
+}
+
 // mgx_tick's / mgx_mission_tick_end's prior updates that ride in a schedule's first launch: [R_local][4] f64 records
 struct RidingUpdates {
     const double *dev = nullptr;   // as the kernel reads them (DevWorld::upd is written from here)

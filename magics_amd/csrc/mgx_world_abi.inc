@@ -78,9 +78,26 @@ int mgx_linger_stats(mgx_world *w, uint64_t *launches, uint64_t *posts, uint64_t
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     const ResidentLaunches::Linger &lg = w->res.linger;
     if (launches) *launches = lg.launches;
-    if (posts) *posts = lg.posts + (lg.un.active ? 1u : 0u);
+    if (posts) *posts = lg.posts + (lg.un.active ? lg.un.schedules : 0u);
     if (reruns) *reruns = lg.reruns;
     if (ended_by_device) *ended_by_device = lg.ended_by_device;
+    return MGX_OK;
+}
+
+int mgx_set_post_merge(mgx_world *w, int32_t mode) {
+    MGX_ENTER_SCHEDULE(w);  // (what was recorded under the old mode goes out first; a launch that lingers stays)
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (mode > POST_MERGE_ALWAYS) return fail(MGX_ERR_INVALID, "bad post-merge mode %d", mode);
+    w->res.linger.merge_mode = mode < 0 ? -1 : mode;
+    return MGX_OK;
+}
+int mgx_post_merge_stats(mgx_world *w, uint64_t *plans_posted, uint64_t *schedules_in_them, uint64_t *largest) {
+    MGX_ENTER_SCHEDULE(w);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    const ResidentLaunches::Linger &lg = w->res.linger;
+    if (plans_posted) *plans_posted = lg.plans_posted;
+    if (schedules_in_them) *schedules_in_them = lg.schedules_in_plans;
+    if (largest) *largest = lg.largest_plan;
     return MGX_OK;
 }
 

@@ -203,6 +203,10 @@ struct ResidentKnobs {
     // plain launch, +15..19 us of host time per launch: MI355X_MICROARCH.md); a grid it turns down takes the launch-per-segment
     // path from now on instead of waiting for workgroups that never become resident
     static bool cooperative() { static const bool v = [] { const char *e = getenv("MGX_COOPERATIVE"); return e && e[0] == '1'; }(); return v; }
+    static int32_t post_merge() {  // 0: every schedule its own post; 1 (default): merged while the launch is behind; 2: whenever they fit
+        const char *e = getenv("MGX_POST_MERGE");
+        return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : POST_MERGE_AUTO;
+    }
     static long long linger_ticks() {  // microseconds a workgroup waits for the next schedule before it ends the launch
         const char *off = getenv("MGX_LINGER"), *us = getenv("MGX_LINGER_US");
         const long long v = off && off[0] == '0' ? 0 : us ? atoll(us) : 300;
@@ -327,6 +331,11 @@ static long long linger_ticks(mgx_world *w) {  // (per world: asked at its first
     if (lg.ticks < 0) lg.ticks = ResidentKnobs::linger_ticks();
     return lg.ticks;
 }
+static int32_t post_merge_mode(mgx_world *w) {  // (per world: asked at its first use, and again after mgx_set_post_merge(w, -1))
+    ResidentLaunches::Linger &lg = w->res.linger;
+    if (lg.merge_mode < 0) lg.merge_mode = ResidentKnobs::post_merge();
+    return lg.merge_mode;
+}
 static double *linger_upd_slot(mgx_world *w, unsigned long long number) {
     ResidentLaunches::Linger &lg = w->res.linger;
     return reinterpret_cast<double *>(reinterpret_cast<char *>(lg.box()) + sizeof(LingerBox)) + (size_t)(number & 1ull) * lg.upd_stride;
@@ -367,7 +376,7 @@ static void linger_confirm(mgx_world *w) {
     ResidentLaunches::Linger &lg = w->res.linger;
     log_plan(w, lg.un.plan);
     lg.un.active = false;
-    lg.posts++;
+    lg.posts += lg.un.schedules;
     lg.taken_in_launch++;
 }
 // Submits `plan` with `upd` riding in it: posted or as resident launches where the world qualifies, launch by launch where not.
@@ -396,7 +405,7 @@ static int linger_settle(mgx_world *w, bool nested = false) {  // nested: on the
     } else if (lg.un.active) {
         Submitted un = std::move(lg.un);
         lg.un = Submitted{};
-        lg.reruns++;
+        lg.reruns += un.schedules;
         un.take_back(w);
         RidingUpdates upd;
         if (un.upd.any()) {  // (a copy in the pinned ring: the box's slot belongs to the posts of the launch that follows)
@@ -426,6 +435,16 @@ static int linger_close(mgx_world *w) {
     const int rc = confirm_held(w);  // (the launch's census: an aborted launch does not linger)
     if (rc != MGX_OK || !lg.open) return rc;
     StageTimer clock("linger");
+    if (lg.un.active) {
+        // The post before is in the launch's hands first.  The postman reads `posted`, then `close_req` (mgx_sweep.h): a close asked
+        // for within the same call as the post — what is recorded goes out, then a schedule that cannot be posted ends the
+        // launch — could be seen with the post still unseen, and the launch would end in front of it (taken back and run as a
+        // launch: right, but a launch for nothing).  The launch ends behind the post either way: nothing is waited for twice.
+        const unsigned long long n = lg.un.number;
+        const int r0 = linger_wait(w, [&] { return __atomic_load_n(&lg.box()->taken, __ATOMIC_ACQUIRE) >= n; }, "the last post to be taken");
+        if (r0 < 0) return r0;
+        if (r0 == 1) return linger_settle(w);  // (the launch ended meanwhile: its workgroups had waited out their bound)
+    }
     __atomic_store_n(&lg.box()->close_req, lg.seq0, __ATOMIC_RELEASE);
     const int r = linger_wait(w, [] { return false; }, "the launch to end");
     if (r < 0) return r;
@@ -434,16 +453,20 @@ static int linger_close(mgx_world *w) {
 }
 // On the way to post `plan` into the open launch: 1 = the slot of the next number may be written and posted; 0 = no launch
 // lingers any more (it had ended, or the plan does not qualify and it was ended): the caller launches.
-static bool linger_plan_fits(const std::vector<Launch> &plan) {
-    if (plan.empty() || plan.size() > (size_t)MAX_SEGS || plan[0].ext) return false;  // a post CONTINUES the last segment of the plan before
-    for (const Launch &l : plan)
-        if (l.n_int > 255) return false;
-    return true;
+// (the plan's own conditions: linger_plan_fits, mgx_resident.h)  What the WORLD has to be like for a post: nothing that a commit
+// would have to bring to the device first, nothing thawing, resident launches on and not backing off.
+static bool linger_world_qualifies(const mgx_world *w) {
+    const ResidentLaunches &rl = w->res;
+    return !w->dirty && !w->conns_dirty && !w->flags_dirty && !w->thaw_kinds && !w->ir_thaw_active && w->n_keyless == 0 &&
+           rl.mode == ResidentLaunches::ON && (w->p.enable_mask & 2u) && rl.backoff.left == 0;
 }
 static int linger_prepare_post(mgx_world *w, const std::vector<Launch> &plan) {
     ResidentLaunches &rl = w->res;
     ResidentLaunches::Linger &lg = rl.linger;
     if (!lg.open) return 0;
+    // a wait inside the launch gave up: nothing more is posted into it (the host-mapped word: no runtime call; linger_post
+    // follows a successful return of this function and nothing else, so the check here is the check of both)
+    if (const int rce = check_device_error(w)) return rce;
     {   // the launch's own census first (one launch of run-ahead, as ever)
         const uint32_t count_before = w->last_sweep_launches;  // (a declined launch is run again here: not the coming schedule's launches)
         const int rc = confirm_held(w);
@@ -451,8 +474,7 @@ static int linger_prepare_post(mgx_world *w, const std::vector<Launch> &plan) {
         if (rc != MGX_OK) return rc;
         if (!lg.open) return 0;
     }
-    const bool fits = linger_plan_fits(plan) && !w->dirty && !w->conns_dirty && !w->flags_dirty && !w->thaw_kinds && !w->ir_thaw_active &&
-                      w->n_keyless == 0 && rl.mode == ResidentLaunches::ON && (w->p.enable_mask & 2u) && rl.backoff.left == 0;
+    const bool fits = linger_plan_fits(plan) && linger_world_qualifies(w);
     if (!fits) {
         const int rc = linger_close(w);
         return rc != MGX_OK ? rc : 0;
@@ -493,6 +515,10 @@ static void linger_post(mgx_world *w, const std::vector<Launch> &plan, const Rid
     un.number = P;
     un.plan = plan;
     un.before = standing(w);
+    un.schedules = std::max(lg.coming, 1u);
+    lg.plans_posted++;
+    lg.schedules_in_plans += un.schedules;
+    lg.largest_plan = std::max<uint64_t>(lg.largest_plan, un.schedules);
     un.upd = RidingUpdates{};
     if (upd.any()) {
         double *slot = linger_upd_slot(w, P);

@@ -13,14 +13,80 @@ extern "C" {
 static int submit_batch(mgx_world *w) {
     std::vector<uint8_t> st;
     st.swap(w->batch.steps);  // (first: whatever runs below may pass MGX_ENTER again)
+    const uint32_t merged = w->batch.implicit;  // (schedules mgx_iterate recorded by itself: they count as schedules where posted)
+    w->batch.implicit = 0;
     if (st.empty()) return MGX_OK;
+    ResidentLaunches::Linger &lg = w->res.linger;
+    if (merged > 1) lg.streak += merged - 1;  // (iterate_now counts the submission as one schedule issued)
+    lg.coming = std::max(merged, 1u);
     const int rc = iterate_now(w, st.data(), (uint32_t)st.size());
+    lg.coming = 1;
     w->batch.submissions++;
     w->batch.launches += w->last_sweep_launches;
     return rc;
 }
 
+// ---- post merging: mgx_iterate records by itself while the launch that lingers is behind ----------------------------------
+// Schedules issued back to back into a launch that lingers are posted one plan each, and the host stays at most two plans ahead:
+// post P is taken only when every workgroup has picked up plan P - 2, and until then the host spins in linger_prepare_post.  In
+// that time it already holds the next schedules — which could ride in ONE plan and spare the launch the boundaries between them
+// (what the explicit batch above buys, without the caller asking).  So mgx_iterate outside a batch looks — once, without
+// waiting — whether the post before is still untaken, and if so records its schedule in the batch's buffer instead of spinning
+// (post_merge_decide, mgx_resident.h, has the rule).  MGX_ENTER_SCHEDULE / MGX_ENTER submit the buffer in front of every other
+// entry point, so mgx_tick, every query, read, mgx_flush and mgx_synchronize find the world as ever; the one difference is that
+// a recorded schedule reaches the device only with the caller's next call on the world (include/mgx.h, mgx_iterate).
+// A launch lingers, its census is confirmed (waited for, as iterate_now would: it falls within microseconds of the launch's
+// start) and it has not ended — the box's `closed` word, read once.
+static int iterate_plan(mgx_world *w, const std::vector<Launch> &plan);
+static bool linger_open_now(mgx_world *w, int *rc) {
+    ResidentLaunches::Linger &lg = w->res.linger;
+    *rc = MGX_OK;
+    if (!lg.open) return false;
+    const uint32_t count_before = w->last_sweep_launches;  // (a declined launch is run again here: not the coming schedule's launches)
+    *rc = confirm_held(w);
+    w->last_sweep_launches = count_before;
+    if (*rc != MGX_OK || !lg.open) return false;
+    const unsigned long long c = __atomic_load_n(&lg.box()->closed, __ATOMIC_ACQUIRE);
+    return !((c & 1ull) && (c >> 1) >= lg.seq0);
+}
+static int iterate_merging(mgx_world *w, const uint8_t *steps, uint32_t n) {
+    mgx_world::Batch &b = w->batch;
+    ResidentLaunches::Linger &lg = w->res.linger;
+    const int32_t mode = post_merge_mode(w);
+    if (mode == POST_MERGE_OFF && b.steps.empty()) return iterate_now(w, steps, n);
+    // (the checks of the explicit batch: a call that would fail when it runs fails when it is issued)
+    if (w->robots.empty()) return fail(MGX_ERR_STATE, "world has no robots");
+    int rc = check_device_error(w);
+    if (rc != MGX_OK) return rc;
+    const std::vector<Launch> fresh = plan_launches(steps, n);
+    for (int round = 0; round < 2; round++) {  // (the second: behind SUBMIT_RECORDED, with nothing recorded)
+        const bool held = !b.steps.empty();
+        std::vector<Launch> merged_plan;
+        if (held) {
+            std::vector<uint8_t> both(b.steps);
+            both.insert(both.end(), steps, steps + n);
+            merged_plan = plan_launches(both.data(), (uint32_t)both.size());
+        }
+        const std::vector<Launch> &merged = held ? merged_plan : fresh;
+        const bool open = linger_open_now(w, &rc);
+        if (rc != MGX_OK) return rc;
+        const unsigned outstanding = open && lg.un.active ? (unsigned)std::min<unsigned long long>(lg.un.number - lg.seq0, 1000ull) : 0u;
+        const bool taken = outstanding && __atomic_load_n(&lg.box()->taken, __ATOMIC_ACQUIRE) >= lg.un.number;
+        const PostMerge what = post_merge_decide(mode, open, outstanding, taken, linger_world_qualifies(w), held, fresh, merged);
+        if (what == PostMerge::SUBMIT_RECORDED) {
+            if ((rc = submit_batch(w)) != MGX_OK) return rc;
+            continue;
+        }
+        if (what == PostMerge::SUBMIT && !held) return iterate_plan(w, fresh);  // (a post — or launches — of its own, as ever)
+        b.steps.insert(b.steps.end(), steps, steps + n);
+        b.implicit++;
+        return what == PostMerge::DEFER ? MGX_OK : submit_batch(w);
+    }
+    return fail(MGX_ERR_STATE, "internal: a schedule was neither recorded nor submitted");
+}
+
 int mgx_batch_begin(mgx_world *w) {
+    MGX_ENTER_SCHEDULE(w);  // (schedules mgx_iterate recorded by itself go out first: the batch's counters start clean)
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     if (w->batch.open) return fail(MGX_ERR_STATE, "a batch is open already");
     w->batch.open = true;
@@ -42,7 +108,11 @@ int mgx_iterate(mgx_world *w, const uint8_t *steps, uint32_t n) {
     // (the same checks inside and outside a batch: a call that would fail when it runs fails when it is issued)
     for (uint32_t i = 0; i < n; i++)
         if (steps[i] & ~(MGX_STEP_INTERNAL | MGX_STEP_EXTERNAL)) return fail(MGX_ERR_INVALID, "bad step %u", i);
-    if (!w->batch.open) return iterate_now(w, steps, n);
+    if (!w->batch.open) {
+        // (no launch lingers and nothing is recorded — every world that does not post, sharded ones among them: as ever)
+        if (!w->res.linger.open && w->batch.steps.empty()) return iterate_now(w, steps, n);
+        return iterate_merging(w, steps, n);
+    }
     if (w->robots.empty()) return fail(MGX_ERR_STATE, "world has no robots");
     int rc0 = check_device_error(w);
     if (rc0 != MGX_OK) return rc0;
@@ -60,8 +130,8 @@ int mgx_iterate(mgx_world *w, const uint8_t *steps, uint32_t n) {
     return MGX_OK;
 }
 
-static int iterate_now(mgx_world *w, const uint8_t *steps, uint32_t n) {
-    const std::vector<Launch> plan = plan_launches(steps, n);
+static int iterate_now(mgx_world *w, const uint8_t *steps, uint32_t n) { return iterate_plan(w, plan_launches(steps, n)); }
+static int iterate_plan(mgx_world *w, const std::vector<Launch> &plan) {
     const int rcc = confirm_held(w);  // (a declined launch is run again here: not this call's launches)
     if (rcc != MGX_OK) return rcc;
     w->last_sweep_launches = 0;

@@ -476,6 +476,7 @@ struct Submitted {
     std::vector<Launch> plan;       // its segments
     Standing before;                // where the world stood when it went out
     bool partial = false;           // a launch that is not the first of its schedule (more than MAX_SEGS segments)
+    uint32_t schedules = 1;         // a post: the schedules merged into its plan (mgx_set_post_merge)
     // the prior updates that ride in it.  A launch: where the kernel read them, and the ring slot a re-run guards again (the event
     // behind a declined launch completed at once).  A post: host = its slot of records in the box, nothing else.
     RidingUpdates upd;
@@ -530,7 +531,12 @@ struct ResidentLaunches {
         int useless = 0;                   // lingering launches in a row that ended without having taken a post
         uint32_t streak = 0;               // schedules issued back to back, this one included (no other call on the world in between)
         Submitted un;
-        uint64_t launches = 0, posts = 0, reruns = 0, ended_by_device = 0;
+        uint64_t launches = 0, posts = 0, reruns = 0, ended_by_device = 0;  // (posts, reruns: SCHEDULES, however they were grouped)
+        // merging back-to-back schedules into one post (post_merge_decide, mgx_resident.h): the switch, the schedules in the plan
+        // being submitted (linger_post takes the number; 1 outside submit_batch), and what was posted as how many plans
+        int32_t merge_mode = -1;  // PostMergeMode; -1: not asked yet (MGX_POST_MERGE)
+        uint32_t coming = 1;
+        uint64_t plans_posted = 0, schedules_in_plans = 0, largest_plan = 0;
     } linger;
     // ---- what the rest of the host tells it ----
     void arrays_rebuilt() {  // commit laid the device arrays out again: progress words are re-created (zero), the count starts over
@@ -660,6 +666,7 @@ struct mgx_world {
         bool open = false;
         std::vector<uint8_t> steps;
         uint32_t schedules = 0, submissions = 0, launches = 0;
+        uint32_t implicit = 0;  // schedules in `steps` that mgx_iterate recorded by itself, outside a batch (post merging)
     } batch;
     ResidentLaunches res;  // resident and lingering schedule launches: their words and tables, the launch not yet decided, the open launch and its post
     int sticky_rc = 0;       // a declined launch whose re-run failed inside a call that cannot report it (flush_counts): every

@@ -84,6 +84,17 @@ class World:
         self._chk(self._L.mgx_linger_stats(self._w, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    def set_post_merge(self, mode):
+        """back-to-back schedules merged into one post: 0 off, 1 while the launch is behind (default), 2 whenever they fit
+        (None: the default) — mgx_set_post_merge"""
+        self._chk(self._L.mgx_set_post_merge(self._w, -1 if mode is None else int(mode)))
+
+    def post_merge_stats(self):
+        """(plans posted into lingering launches, schedules in them, schedules in the largest) — mgx_post_merge_stats"""
+        v = [C.c_uint64() for _ in range(3)]
+        self._chk(self._L.mgx_post_merge_stats(self._w, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
+
     # -- topology --------------------------------------------------------------------------
     def set_sdf(self, rgb, world_w, world_h):
         rgb = np.ascontiguousarray(rgb, dtype=np.uint8)

@@ -155,6 +155,10 @@ impl World {
     pub fn set_linger(&self, microseconds: i32) -> Result<(), MgxError> {
         check(unsafe { sys::mgx_set_linger(self.raw, microseconds) })
     }
+    /// Back-to-back schedules merged into one post: 0 off, 1 while the launch is behind (the default), 2 whenever they fit.
+    pub fn set_post_merge(&self, mode: i32) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_set_post_merge(self.raw, mode) })
+    }
     /// (resident launches so far, those declined before they wrote anything, what is left of the back-off)
     pub fn resident_stats(&self) -> Result<(u64, u64, u32), MgxError> {
         let (mut launches, mut declined, mut backoff) = (0u64, 0u64, 0u32);

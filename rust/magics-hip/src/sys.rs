@@ -256,6 +256,8 @@ extern "C" {
     pub fn mgx_flush(w: *mut mgx_world) -> c_int;
     pub fn mgx_set_linger(w: *mut mgx_world, microseconds: i32) -> c_int;
     pub fn mgx_linger_stats(w: *mut mgx_world, launches: *mut u64, posts: *mut u64, reruns: *mut u64, ended_by_device: *mut u64) -> c_int;
+    pub fn mgx_set_post_merge(w: *mut mgx_world, mode: i32) -> c_int;
+    pub fn mgx_post_merge_stats(w: *mut mgx_world, plans_posted: *mut u64, schedules_in_them: *mut u64, largest: *mut u64) -> c_int;
     pub fn mgx_set_resident_launches(w: *mut mgx_world, enabled: i32) -> c_int;
     pub fn mgx_is_thawing(w: *mut mgx_world, thawing: *mut i32) -> c_int;
     pub fn mgx_sweep(w: *mut mgx_world, robot: i32, external_phases: u32, internal_phases: u32, n_internal: u32, hints: u32) -> c_int;
