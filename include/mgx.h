@@ -1002,6 +1002,77 @@ int mgx_tracks_take(mgx_world *w, mgx_track_sample *samples, uint64_t capacity, 
                     uint64_t *dropped, double *travelled /* [n_robots] or NULL */);
 int mgx_tracks_clear(mgx_world *w);
 
+/* ---- run metrics on the device: dimensionless jerk and path deviation per robot ----------------------------------
+ * What the reference's analysis scripts compute from an export — smoothness (scripts/ldj.py:17-55, Log Dimensionless Jerk) and
+ * perpendicular path deviation (scripts/perpendicular-path-deviation.py:40-60, 99-115) — carried as O(1) state per robot and
+ * updated by the tracker pass at the moment a sample is taken, so that a run needs no sample log.  Restated on the host by
+ * magics_amd/track_metrics.py, the checker.  The lane arithmetic: magics_amd/csrc/mgx_track_metrics.h.
+ * ARITHMETIC: f64, every operation rounded on its own, nothing contracted, division and square root correctly rounded:
+ *   libmgx.so and libmgx_fma.so agree bit for bit.  sq2(a, b) = (a*a) + (b*b).  There is no logarithm on the device: it
+ *   reports the dimensionless jerk DJ, and LDJ = -log(DJ) is the caller's.
+ * VELOCITY SERIES of a robot: u_i = (double)velocity[0], w_i = (double)velocity[2] of its samples with span_ticks != 0, in the
+ *   order they are made, i = 0 .. n-1 (the reference's columns [0, 2], ldj.py:92).
+ * JERK, free of times.  g(x)_0 = x_1 - x_0, g(x)_{n-1} = x_{n-1} - x_{n-2}, g(x)_i = (x_{i+1} - x_{i-1}) / 2 otherwise
+ *   (np.gradient with unit spacing); a = g(x), j = g(a), where a difference of two a's is formed it is (later - earlier);
+ *   q_i = sq2(g(g(u))_i, g(g(w))_i); W = the composite Simpson sum of q with unit spacing under scipy.integrate.simpson's rule
+ *   (scipy >= 1.11): n odd: (q_0 + 4 O + 2 E + q_{n-1}) / 3 with O the sum over odd i and E over even interior i; n even: the
+ *   same over q_0 .. q_{n-2}, plus (5/12) q_{n-1} + (2/3) q_{n-2} - (1/12) q_{n-3}.  vmax2 = max_i sq2(u_i, w_i).
+ *   DJ = (n-1)^3 W / vmax2.  This is ldj.py's figure: it differentiates with dt = the mean spacing of the time stamps and
+ *   integrates over linspace(t_0, t_{n-1}, n), whose spacing is the same dt; with T = (n-1) dt,
+ *   T^3 / vmax^2 * (dt * W / dt^4) = (n-1)^3 W / vmax2.  Valid for n >= 3 and vmax2 > 0; otherwise DJ = NaN and the flag is
+ *   clear (the reference asserts or divides by zero there).
+ * STREAMING, and the ORDER OF THE SUMS.  State: n, the last five velocities, q0, s_odd, s_even, hold, vmax2 (all zero at first).
+ *   When velocity m = n arrives: it enters the window; vmax2 = max(vmax2, sq2(u, w)); n = m + 1; then
+ *     m == 3: q0 = q_0 and s_odd = q_1 (both final from here on: a_0 one-sided, a_1 and a_2 central);
+ *     m >= 4: q = q_{m-2}, from a_{m-1} = (x_m - x_{m-2}) / 2 and a_{m-3} = (x_{m-2} - x_{m-4}) / 2, j = (a_{m-1} - a_{m-3}) / 2;
+ *             if m >= 5 the value held so far, q_{m-3}, is added to s_odd (m-3 odd) or s_even (m-3 even); then hold = q.
+ *   So s_odd = ((q_1 + q_3) + q_5) + ..., s_even = ((0 + q_2) + q_4) + ... up to index n-4, and hold = q_{n-3}: arrival order.
+ *   FINALISATION works on a copy of the state whenever somebody reads; the accumulation goes on undisturbed.  With
+ *   a_{n-1} = x_{n-1} - x_{n-2}:
+ *     n == 3: a_0 = x_1 - x_0, a_1 = (x_2 - x_0) / 2; q_0 = sq2(a_1 - a_0), q_1 = sq2((a_2 - a_0) / 2), q_2 = sq2(a_2 - a_1);
+ *             W = ((q_0 + 4 q_1) + q_2) / 3.
+ *     n >= 4: a_{n-2} = (x_{n-1} - x_{n-3}) / 2, a_{n-3} = (x_{n-2} - x_{n-4}) / 2, qa = q_{n-2} = sq2((a_{n-1} - a_{n-3}) / 2),
+ *             qb = q_{n-1} = sq2(a_{n-1} - a_{n-2});
+ *       n odd:  O = s_odd + qa, E = s_even + hold, W = (((q0 + 4 O) + 2 E) + qb) / 3;
+ *       n even: O = s_odd + hold and qc = hold (n == 4: O = qc = s_odd), W = (((q0 + 4 O) + 2 s_even) + qa) / 3
+ *               + (((5/12) qb + (2/3) qa) - (1/12) qc), the three constants being the f64 quotients.
+ *     T = (double)(n - 1), DJ = (((T T) T) W) / vmax2.
+ * PATH DEVIATION.  For every sample taken, first samples included: p = ((double)position[0], (double)position[2]).  Over the
+ *   segments (a, b) of the robot's route polyline, in order, with d = b - a and l2 = sq2(d_x, d_y) > 0:
+ *   dist = |d_x (p_y - a_y) - d_y (p_x - a_x)| / sqrt(l2) (each product rounded, then the difference); the sample's deviation is
+ *   the smallest (the first on ties); deviation_sum += deviation, deviation_max = max(deviation_max, deviation),
+ *   n_positions += 1.  This is the reference's distance to the INFINITE lines through consecutive waypoints.  The difference:
+ *   its slope-intercept form yields inf / NaN for a vertical segment or one of zero length; here a vertical segment is a line
+ *   like any other and a segment of zero length is left out.  Elsewhere the two agree up to rounding.  A sample taken while
+ *   the robot has no route, or none with a segment of non-zero length, is counted in n_unrouted and not in n_positions.  The
+ *   reference's "RMSE" is sqrt(deviation_sum / n_positions) (sic, :114-115).
+ * mgx_track_metrics_enable(w, 1, max_route_points): on (default: off — no allocation, no extra work in the pass).  Needs the
+ *   trackers on (MGX_ERR_STATE otherwise, and on a world with ghosts); max_route_points in 2 .. 65536, 0: 16.  Enabling again
+ *   while on keeps everything (another max_route_points: MGX_ERR_STATE).  The state follows the tracker state's rules: robots
+ *   added later start from zero and without a route, and the state survives an in-place append, a relayout and a join between
+ *   mgx_mission_tick_begin and _end.  mgx_tracks_clear zeroes it (routes stay), mgx_tracks_enable(.. 0 ..) drops it, and so
+ *   does enabled = 0 here.
+ * mgx_track_metrics_set_route(w, robot, xy, n_points): the polyline [n_points][2] (x, z of the world) the deviation is measured
+ *   against, uploaded in stream order: it holds for the samples of passes enqueued after the call.  n_points = 0 clears it;
+ *   more than max_route_points: MGX_ERR_INVALID.  It can be replaced at any time.
+ * mgx_tracks_set_logging(w, on): default on (and on again after mgx_tracks_enable(.. 0 ..)).  Off: a sample still moves the
+ *   timer, the previous sample, the distance and the metrics, but is not appended: the cursor does not move and `dropped`
+ *   does not count.
+ * mgx_track_metrics_read(w, out, capacity): the one call that synchronises; finalises every robot on a copy into
+ *   out[0 .. n_robots) (capacity < n_robots: MGX_ERR_INVALID).  flags: MGX_TRACK_JERK_VALID, MGX_TRACK_DEVIATION_VALID
+ *   (n_positions > 0). */
+#define MGX_TRACK_JERK_VALID      1u
+#define MGX_TRACK_DEVIATION_VALID 2u
+typedef struct mgx_track_metrics {  /* 48 bytes */
+    uint32_t n_positions, n_velocities, n_unrouted, flags;
+    double   dimensionless_jerk;    /* NaN unless MGX_TRACK_JERK_VALID */
+    double   vmax2, deviation_sum, deviation_max;
+} mgx_track_metrics;
+int mgx_track_metrics_enable(mgx_world *w, int32_t enabled, uint32_t max_route_points);
+int mgx_track_metrics_set_route(mgx_world *w, int32_t robot, const double *xy, uint32_t n_points);
+int mgx_tracks_set_logging(mgx_world *w, int32_t on);
+int mgx_track_metrics_read(mgx_world *w, mgx_track_metrics *out, uint64_t capacity);
+
 /* ---- global planner: batched RRT* over the map's colliders -------------------------------------------------------
  * What crates/gbp_global_planner does for one robot (rrtstar.rs:15-83; started from progress_missions, robot.rs:578-633),
  * for many requests in one call: a formation spawns and every robot of it asks at once.  The paths it returns are what

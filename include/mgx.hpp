@@ -335,6 +335,20 @@ public:
         return out;
     }
     void tracks_clear() { check(mgx_tracks_clear(w_)); }
+    void tracks_set_logging(bool on) { check(mgx_tracks_set_logging(w_, on ? 1 : 0)); }
+    /// run metrics (mgx_track_metrics_*, specified in mgx.h): dimensionless jerk and path deviation per robot, carried by the
+    /// tracker pass; `read` is the one call that waits, LDJ = -log(dimensionless_jerk)
+    void track_metrics_enable(bool enabled, uint32_t max_route_points = 0) { check(mgx_track_metrics_enable(w_, enabled ? 1 : 0, max_route_points)); }
+    void track_metrics_set_route(int32_t robot, const std::vector<std::array<double, 2>> &xy) {
+        check(mgx_track_metrics_set_route(w_, robot, xy.empty() ? nullptr : xy[0].data(), (uint32_t)xy.size()));
+    }
+    std::vector<mgx_track_metrics> track_metrics_read() {
+        uint32_t n = 0;
+        check(mgx_num_robots(w_, &n, nullptr));
+        std::vector<mgx_track_metrics> out(n);
+        check(mgx_track_metrics_read(w_, out.data(), out.size()));
+        return out;
+    }
     /// the global planner (batched RRT* over the colliders of `env`, specified in mgx.h); nullptr switches it off
     void planner_enable(const mgx_env_desc *env, const mgx_plan_params &params) { check(mgx_planner_enable(w_, env, &params)); }
     struct Plans {

@@ -13,6 +13,8 @@
 #pragma once
 #include <cstdint>
 
+#include "mgx_track_metrics.h"  // TrackMetricsState (its functions keep their own contraction setting)
+
 namespace mgx {
 
 constexpr int SNAP_W = 24;  // eta(4) lam(16) mu(4)
@@ -358,8 +360,11 @@ struct TrackSample {           // == mgx_track_sample (include/mgx.h; mgx_tracks
     uint32_t span_ticks;
     float position[3], velocity[3];
 };
+struct TrackRoute {            // a robot's route in the flat table: `count` points from point `offset` on
+    uint32_t offset, count;
+};
 struct TrackDev {
-    TrackState *state;         // [n]
+    TrackState *state;        // [n]
     TrackSample *log;          // [cap]
     unsigned long long cap;
     unsigned long long *cursor;  // samples claimed since the log was last emptied (keeps counting beyond cap)
@@ -371,6 +376,12 @@ struct TrackDev {
     const double *time_scale;  // [n]
     int BS, K;
     int n;
+    // the run metrics (mgx_track_metrics.h; metrics == null: off — the pass does what it did without them)
+    int no_log;                // non-zero: a sample is not appended (mgx_tracks_set_logging)
+    TrackMetricsState *metrics;  // [n]
+    const double *route_xy;    // one flat table of route points (x, y)
+    const TrackRoute *routes;  // [n] where a robot's points are in it
+    uint32_t max_route_points; // bound of the segment loop
 };
 
 // The map's side of EnvCollDev on its own: what a kernel needs to test a ball against the colliders (mgx_env_contact.h).  The

@@ -16,6 +16,9 @@
 // division and the f64 square root are the correctly rounded ones: libmgx.so and libmgx_fma.so agree bit for bit.
 //   log     append-only 40-byte records under an atomic cursor that keeps counting when the log is full (what did not fit is
 //           cursor - capacity: nothing is lost silently); one atomic per sample, i.e. per robot every 100 ms of simulated time.
+//   metrics (mgx_track_metrics.h; off unless mgx_track_metrics_enable): a robot that takes a sample also feeds the sample's velocity
+//           to its jerk state and the sample's position, against its route, to its deviation state — 152 bytes of state and the
+//           route's points, loaded and stored inside the sampling branch only.  k_track_metrics_read finalises copies.
 // A lane touches its own robot's state only; no LDS, one wave per 64 robots.
 #include <hip/hip_runtime.h>
 
@@ -35,6 +38,17 @@ static_assert(offsetof(mgx_track_sample, tick) == offsetof(TrackSample, tick) &&
                   offsetof(mgx_track_sample, position) == offsetof(TrackSample, position) &&
                   offsetof(mgx_track_sample, velocity) == offsetof(TrackSample, velocity),
               "TrackSample is the ABI's record");
+static_assert(sizeof(mgx_track_metrics) == 48 && sizeof(TrackMetricsOut) == 48, "48-byte records");
+static_assert(offsetof(mgx_track_metrics, n_positions) == offsetof(TrackMetricsOut, n_positions) &&
+                  offsetof(mgx_track_metrics, n_velocities) == offsetof(TrackMetricsOut, n_velocities) &&
+                  offsetof(mgx_track_metrics, n_unrouted) == offsetof(TrackMetricsOut, n_unrouted) &&
+                  offsetof(mgx_track_metrics, flags) == offsetof(TrackMetricsOut, flags) &&
+                  offsetof(mgx_track_metrics, dimensionless_jerk) == offsetof(TrackMetricsOut, dimensionless_jerk) &&
+                  offsetof(mgx_track_metrics, vmax2) == offsetof(TrackMetricsOut, vmax2) &&
+                  offsetof(mgx_track_metrics, deviation_sum) == offsetof(TrackMetricsOut, deviation_sum) &&
+                  offsetof(mgx_track_metrics, deviation_max) == offsetof(TrackMetricsOut, deviation_max),
+              "TrackMetricsOut is the ABI's record");
+static_assert(MGX_TRACK_JERK_VALID == TRACK_METRICS_JERK_VALID && MGX_TRACK_DEVIATION_VALID == TRACK_METRICS_DEVIATION_VALID, "the record's flags");
 
 // t(k): the simulated time at the end of tick k — an exact integer product, one f64 multiplication
 __device__ __forceinline__ double track_time(unsigned long long k, unsigned long long tick_ns) {
@@ -72,15 +86,38 @@ __global__ void __launch_bounds__(64) k_tracks_pass(TrackDev t) {
         }
         st.prev_tick = t.tick;
         st.has_prev = 1u;
-        const unsigned long long e = atomicAdd(t.cursor, 1ull);
-        if (e < t.cap) t.log[e] = s;
+        if (!t.no_log) {
+            const unsigned long long e = atomicAdd(t.cursor, 1ull);
+            if (e < t.cap) t.log[e] = s;
+        }
+        if (t.metrics) {  // the run metrics: state and route are touched by the robots that take a sample only
+            TrackMetricsState m = t.metrics[r];
+            if (s.span_ticks) track_metrics_velocity(m, (double)s.velocity[0], (double)s.velocity[2]);
+            const TrackRoute rt = t.routes[r];
+            const uint32_t np = rt.count < t.max_route_points ? rt.count : t.max_route_points;
+            track_metrics_position(m, (double)s.position[0], (double)s.position[2], t.route_xy + 2 * (size_t)rt.offset, np);
+            t.metrics[r] = m;
+        }
     }
     t.state[r] = st;
+}
+
+// every robot's metrics as if its series ended now, from a copy of the state: nothing is written back
+__global__ void __launch_bounds__(64) k_track_metrics_read(int n, const TrackMetricsState *state, TrackMetricsOut *out) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n) return;
+    out[r] = track_metrics_finalise(state[r]);
 }
 
 hipError_t launch_tracks_pass(const TrackDev &t, hipStream_t s) {
     if (t.n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_tracks_pass, dim3((unsigned)((t.n + 63) / 64)), dim3(64), 0, s, t);
+    return hipGetLastError();
+}
+
+hipError_t launch_track_metrics_read(int n, const TrackMetricsState *state, TrackMetricsOut *out, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_track_metrics_read, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, n, state, out);
     return hipGetLastError();
 }
 

@@ -9,8 +9,20 @@
 static constexpr uint64_t TRACKS_DEFAULT_SAMPLES = 1ull << 18;  // 10 MB of 40-byte records
 static const char *const TRACKS_OFF = "the trackers are off (mgx_tracks_enable)";
 
+static const char *const METRICS_OFF = "the run metrics are off (mgx_track_metrics_enable)";
+static constexpr uint32_t METRICS_DEFAULT_ROUTE_POINTS = 16, METRICS_MAX_ROUTE_POINTS = 1u << 16;
+
+static void metrics_drop(mgx_world *w) {
+    mgx_world::Tracks &t = w->tracks;
+    t.metrics = false;
+    t.mstate.release(); t.route_xy.release(); t.routes.release(); t.mout.release();
+    t.m_sized = t.m_room = 0; t.max_route_points = 0;
+}
+
 static void tracks_drop(mgx_world *w) {  // switched off: the state goes with it
     mgx_world::Tracks &t = w->tracks;
+    metrics_drop(w);
+    t.logging = true;
     t.enabled = false;
     t.state.release(); t.log.release(); t.cursor.release(); t.pos.release(); t.moved.release();
     t.n_sized = 0; t.log_cap = 0; t.period_ns = 0; t.tick_ns = 0; t.clock = 0; t.dropped = 0;
@@ -32,6 +44,29 @@ static int tracks_size(mgx_world *w) {
     return MGX_OK;
 }
 
+// the metrics' arrays for the robots the world has NOW, under the rule of tracks_size: the robots so far keep state and route, the
+// others start from zero and without a route.  All three arrays have room for the same number of robots
+static int metrics_size(mgx_world *w) {
+    mgx_world::Tracks &t = w->tracks;
+    const size_t R = w->robots.size(), P = t.max_route_points;
+    if (R <= t.m_sized) return MGX_OK;
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the trackers run on unsharded worlds");
+    if (t.m_room < R) {
+        hipStream_t s = w->stream;
+        const size_t room = R + R / 4 + 64;
+        DevBuf<TrackMetricsState> old_state;
+        DevBuf<double> old_xy;
+        DevBuf<TrackRoute> old_routes;
+        HIP_TRY(grow_keep(t.mstate, room, t.m_sized, 0, old_state, s));
+        HIP_TRY(grow_keep(t.route_xy, room * P * 2, t.m_sized * P * 2, 0, old_xy, s));
+        HIP_TRY(grow_keep(t.routes, room, t.m_sized, 0, old_routes, s));
+        HIP_TRY(hipStreamSynchronize(s));  // (passes enqueued earlier may still have used what was grown out of)
+        t.m_room = room;
+    }
+    t.m_sized = R;
+    return MGX_OK;
+}
+
 // one pass at `tick` over device-resident positions [R][3] and moved bytes [R], enqueued on `s`.  distance: the mission chain's
 // pass — the increment is formed from the blob's means and the missions' time scales as k_mission_prepare has just done
 static int tracks_pass(mgx_world *w, const float *pos_d, const uint8_t *moved_d, uint64_t tick, bool distance, hipStream_t s) {
@@ -44,6 +79,12 @@ static int tracks_pass(mgx_world *w, const float *pos_d, const uint8_t *moved_d,
     d.pos = pos_d; d.moved = moved_d;
     if (distance) { d.blob = w->d.blob; d.time_scale = w->mission.time_scale_d.p; d.BS = w->d.BS; d.K = w->d.K; }
     d.n = (int)w->robots.size();
+    d.no_log = t.logging ? 0 : 1;
+    if (t.metrics) {
+        const int mrc = metrics_size(w);
+        if (mrc != MGX_OK) return mrc;
+        d.metrics = t.mstate.p; d.route_xy = t.route_xy.p; d.routes = t.routes.p; d.max_route_points = t.max_route_points;
+    }
     HIP_TRY(launch_tracks_pass(d, s));
     return MGX_OK;
 }
@@ -52,6 +93,7 @@ static int tracks_reset(mgx_world *w) {  // nothing logged, nothing travelled, e
     mgx_world::Tracks &t = w->tracks;
     hipStream_t s = w->stream;
     if (t.state.p) HIP_TRY(hipMemsetAsync(t.state.p, 0, sizeof(TrackState) * t.state.cap, s));
+    if (t.mstate.p) HIP_TRY(hipMemsetAsync(t.mstate.p, 0, sizeof(TrackMetricsState) * t.mstate.cap, s));  // (the routes stay)
     HIP_TRY(hipMemsetAsync(t.cursor.p, 0, sizeof(unsigned long long), s));
     t.dropped = 0;
     return MGX_OK;
@@ -168,6 +210,90 @@ int mgx_tracks_clear(mgx_world *w) {
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     if (!w->tracks.enabled) return fail(MGX_ERR_STATE, "%s", TRACKS_OFF);
     return tracks_reset(w);
+}
+
+int mgx_tracks_set_logging(mgx_world *w, int32_t on) {
+    MGX_ENTER(w);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (!w->tracks.enabled) return fail(MGX_ERR_STATE, "%s", TRACKS_OFF);
+    w->tracks.logging = on != 0;  // (a kernel argument of the passes enqueued from now on)
+    return MGX_OK;
+}
+
+int mgx_track_metrics_enable(mgx_world *w, int32_t enabled, uint32_t max_route_points) {
+    MGX_ENTER(w);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    mgx_world::Tracks &t = w->tracks;
+    if (!t.enabled) return fail(MGX_ERR_STATE, "%s", TRACKS_OFF);
+    if (!enabled) {
+        if (t.metrics) HIP_TRY(hipStreamSynchronize(w->stream));
+        metrics_drop(w);
+        return MGX_OK;
+    }
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the trackers run on unsharded worlds");
+    const uint32_t P = max_route_points ? max_route_points : METRICS_DEFAULT_ROUTE_POINTS;
+    if (P < 2 || P > METRICS_MAX_ROUTE_POINTS) return fail(MGX_ERR_INVALID, "max_route_points must be in 2 .. %u, got %u", METRICS_MAX_ROUTE_POINTS, P);
+    if (t.metrics) {
+        if (max_route_points && P != t.max_route_points)
+            return fail(MGX_ERR_STATE, "the run metrics are on with room for %u route points per robot", t.max_route_points);
+        return MGX_OK;
+    }
+    t.max_route_points = P;
+    t.m_sized = t.m_room = 0;
+    t.metrics = true;
+    const int rc = metrics_size(w);
+    if (rc != MGX_OK) metrics_drop(w);
+    return rc;
+}
+
+int mgx_track_metrics_set_route(mgx_world *w, int32_t robot, const double *xy, uint32_t n_points) {
+    MGX_ENTER(w);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    mgx_world::Tracks &t = w->tracks;
+    if (!t.enabled) return fail(MGX_ERR_STATE, "%s", TRACKS_OFF);
+    if (!t.metrics) return fail(MGX_ERR_STATE, "%s", METRICS_OFF);
+    if (robot < 0 || (size_t)robot >= w->robots.size() || (!xy && n_points)) return fail(MGX_ERR_INVALID, "bad argument");
+    if (n_points > t.max_route_points) return fail(MGX_ERR_INVALID, "a route of %u points, room for %u (mgx_track_metrics_enable)", n_points, t.max_route_points);
+    const int rc = metrics_size(w);
+    if (rc != MGX_OK) return rc;
+    // the points and where they are: up from a pinned slot, behind the passes enqueued so far
+    hipStream_t s = w->stream;
+    const size_t P = t.max_route_points, xy_bytes = sizeof(double) * 2 * n_points;
+    void *hp = nullptr;
+    int slot = 0;
+    HIP_TRY(w->stage.acquire(xy_bytes + sizeof(TrackRoute), &hp, &slot));
+    char *h = static_cast<char *>(hp);
+    const TrackRoute rt{(uint32_t)((size_t)robot * P), n_points};
+    if (xy_bytes) memcpy(h, xy, xy_bytes);
+    memcpy(h + xy_bytes, &rt, sizeof rt);
+    if (xy_bytes) HIP_TRY(hipMemcpyAsync(t.route_xy.p + 2 * (size_t)robot * P, h, xy_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(t.routes.p + robot, h + xy_bytes, sizeof rt, hipMemcpyHostToDevice, s));
+    HIP_TRY(w->stage.release(slot, s));
+    return MGX_OK;
+}
+
+int mgx_track_metrics_read(mgx_world *w, mgx_track_metrics *out, uint64_t capacity) {
+    MGX_ENTER(w);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    mgx_world::Tracks &t = w->tracks;
+    if (!t.enabled) return fail(MGX_ERR_STATE, "%s", TRACKS_OFF);
+    if (!t.metrics) return fail(MGX_ERR_STATE, "%s", METRICS_OFF);
+    const size_t R = w->robots.size(), n = std::min(R, t.m_sized);
+    if (capacity < R || (!out && R)) return fail(MGX_ERR_INVALID, "room for %llu records, %llu robots", (unsigned long long)capacity, (unsigned long long)R);
+    MGX_CONFIRM(w);
+    hipStream_t s = w->stream;
+    TrackMetricsOut *o = reinterpret_cast<TrackMetricsOut *>(out);  // (the ABI's record is TrackMetricsOut's layout: mgx_tracks.hip asserts it)
+    if (n) {
+        HIP_TRY(t.mout.reserve(n));
+        HIP_TRY(launch_track_metrics_read((int)n, t.mstate.p, t.mout.p, s));
+        HIP_TRY(hipMemcpyAsync(o, t.mout.p, sizeof(TrackMetricsOut) * n, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    for (size_t r = n; r < R; r++) {  // (robots that joined since the last pass: nothing sampled yet)
+        o[r] = TrackMetricsOut{};
+        o[r].dimensionless_jerk = __builtin_nan("");
+    }
+    return check_device_error(w);
 }
 
 }  // extern "C" (continued in the next part)

@@ -80,6 +80,7 @@ hipError_t launch_collisions_rebits(const CollDev &c, hipStream_t s);
 hipError_t launch_env_collisions_pass(const EnvCollDev &c, hipStream_t s);
 // mgx_tracks.hip
 hipError_t launch_tracks_pass(const TrackDev &t, hipStream_t s);
+hipError_t launch_track_metrics_read(int n, const TrackMetricsState *state, TrackMetricsOut *out, hipStream_t s);
 // mgx_planner.hip
 hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s);
 }  // namespace mgx
@@ -807,6 +808,16 @@ struct mgx_world {
         uint64_t log_cap = 0, period_ns = 0, tick_ns = 0;
         uint64_t clock = 0;      // the simulated tick index of the coming tick
         uint64_t dropped = 0;    // samples that found the log full, up to the last time it was emptied
+        bool logging = true;     // mgx_tracks_set_logging
+        // the run metrics (mgx_track_metrics_*): state per robot id beside `state`, under the same rules; every robot's route has
+        // max_route_points places of the flat table, at robot * max_route_points
+        bool metrics = false;
+        uint32_t max_route_points = 0;
+        size_t m_sized = 0, m_room = 0;  // robots the three arrays have been sized for / have room for
+        DevBuf<TrackMetricsState> mstate;
+        DevBuf<double> route_xy;
+        DevBuf<TrackRoute> routes;
+        DevBuf<TrackMetricsOut> mout;    // what mgx_track_metrics_read finalises into
     } tracks;
     // the global planner (mgx_planner_enable, mgx_world_planner.inc): the map and two pools of requests.  `pool`: the requests that
     // ride the stream (mgx_plan_submit / _advance / _collect), 256 blocks of 16 slots.  `call`: the requests of one mgx_plan_paths,

@@ -214,6 +214,10 @@ SYMBOLS = {
     "mgx_tracks_update": (C.c_int, [_V, C.c_void_p, C.c_void_p, C.c_uint64]),
     "mgx_tracks_take": (C.c_int, [_V, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     "mgx_tracks_clear": (C.c_int, [_V]),
+    "mgx_track_metrics_enable": (C.c_int, [_V, C.c_int32, C.c_uint32]),
+    "mgx_track_metrics_set_route": (C.c_int, [_V, C.c_int32, C.c_void_p, C.c_uint32]),
+    "mgx_tracks_set_logging": (C.c_int, [_V, C.c_int32]),
+    "mgx_track_metrics_read": (C.c_int, [_V, C.c_void_p, C.c_uint64]),
     "mgx_num_robots": (C.c_int, [_V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mgx_last_launch_count": (C.c_int, [_V, C.POINTER(C.c_uint32)]),
     "mgx_last_sweep": (C.c_int, [_V, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -427,6 +431,22 @@ def track_sample_dtype():
     """numpy view of an array of mgx_track_sample"""
     import numpy as np
     return np.dtype([("tick", np.uint64), ("robot", np.int32), ("span_ticks", np.uint32), ("position", np.float32, 3), ("velocity", np.float32, 3)])
+
+
+class TrackMetrics(C.Structure):
+    """mgx_track_metrics (include/mgx.h)"""
+    _fields_ = [("n_positions", C.c_uint32), ("n_velocities", C.c_uint32), ("n_unrouted", C.c_uint32), ("flags", C.c_uint32),
+                ("dimensionless_jerk", C.c_double), ("vmax2", C.c_double), ("deviation_sum", C.c_double), ("deviation_max", C.c_double)]
+
+
+TRACK_JERK_VALID, TRACK_DEVIATION_VALID = 1, 2
+
+
+def track_metrics_dtype():
+    """numpy view of an array of mgx_track_metrics"""
+    import numpy as np
+    return np.dtype([("n_positions", np.uint32), ("n_velocities", np.uint32), ("n_unrouted", np.uint32), ("flags", np.uint32),
+                     ("dimensionless_jerk", np.float64), ("vmax2", np.float64), ("deviation_sum", np.float64), ("deviation_max", np.float64)])
 
 
 PLAN_OK, PLAN_MAX_ITERATIONS, PLAN_TREE_FULL = 0, 1, 2

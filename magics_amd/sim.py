@@ -26,6 +26,7 @@ import numpy as np
 from . import config as _config
 from . import environment as _environment
 from . import hostlib, spawner
+from . import track_metrics as _metrics
 from .prng import WyRand
 from .scenarios import robot_initial_state
 
@@ -100,7 +101,8 @@ def _take_in(table, read, a, b, what):
 
 class Simulation:
     def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None,
-                 environment_collisions=False, global_planner=None, planner_overrides=None, plan_budget=64, device_trackers=None):
+                 environment_collisions=False, global_planner=None, planner_overrides=None, plan_budget=64, device_trackers=None,
+                 device_metrics=False, sample_log=True):
         """scenario: `config.load_scenario(dir)` (or a dict of the same shape); world: a fresh
         World-like object created with `config.world_params(scenario["config"])`.
         device_missions (default: whenever the world offers them, i.e. the engine): routes, reached-when rules and
@@ -117,6 +119,13 @@ class Simulation:
         velocity samples and the distance travelled are made on the device at the end of every tick (mgx_tracks_*) and taken
         into the robots' `positions` / `velocities` / `travelled` when somebody asks; no tick then brings Transforms to the
         host unless a host collision pass needs them.  False: _track / _tracks below on the host (the checker).
+        device_metrics (default off; needs device trackers): the run metrics — dimensionless jerk and path deviation per robot —
+        are carried on the device by the tracker pass (mgx_track_metrics_*), every robot's route being exactly what export() gives
+        as its mission's routes[0]["waypoints"]: set at spawn, and again when a global path replaces it.  metrics() then reads
+        the device's records; otherwise it computes the same figures on the host from the robots' lists (the checker).
+        sample_log (default on; False needs device_metrics): False switches the device's sample log off
+        (mgx_tracks_set_logging) — the robots' `positions` / `velocities` lists, in export() too, then STAY EMPTY: the run's
+        figures are in metrics() and nothing per sample ever leaves the device.
         global_planner (default None: `planning-strategy: rrt-star` raises NotImplementedError): True — robots of that strategy spawn
         Idle (RobotBundle::new, robot.rs:1195, 1294), their requests (taskpoints[0] -> taskpoints[1], a clone of the robot's forked
         stream, config.rrt) are planned in the tick they spawn, all of a tick in ONE mgx_plan_paths, and the paths are applied by ONE
@@ -142,6 +151,11 @@ class Simulation:
         self._dev_trk = (self.dev and hasattr(world, "tracks_enable")) if device_trackers is None else bool(device_trackers)
         if self._dev_trk and not self.dev:
             raise ValueError("device_trackers needs device_missions (the pass reads the device's Transforms)")
+        self._dev_metrics, self._sample_log = bool(device_metrics), bool(sample_log)
+        if self._dev_metrics and not self._dev_trk:
+            raise ValueError("device_metrics needs device_trackers (the tracker pass carries them)")
+        if not self._sample_log and not self._dev_metrics:
+            raise ValueError("sample_log=False needs device_metrics (nothing else would be left of the samples)")
         self._trk_clock_set = False  # the device's clock has been set to tick_no (when the first robots tick)
         self._trk_bound = 0          # samples the device's log holds at the most since it was last taken
         if environment_collisions not in (False, True, "host"):
@@ -196,6 +210,10 @@ class Simulation:
             self._colliders, self._collider_vertices = hostlib.env_colliders(self.env)
         if self._dev_trk:
             world.tracks_enable(True, period_ns=self.TRACK_PERIOD_NS, tick_ns=self.dt_ns, next_tick=0, sample_capacity=self.TRACK_LOG_SAMPLES)
+        if self._dev_metrics:
+            world.track_metrics_enable(True, max_route_points=self.METRIC_ROUTE_POINTS)
+            if not self._sample_log:
+                world.tracks_set_logging(False)
         if self._planner is not None:
             from . import global_planner as _gp
             self._plan_params = _gp.params_from_config(self.cfg, **(planner_overrides or {}))
@@ -210,6 +228,7 @@ class Simulation:
 
     TRACK_PERIOD_NS = 100_000_000  # the trackers' timers (spawner.rs:627-628)
     TRACK_LOG_SAMPLES = 1 << 18    # room of the device's sample log: drained before it can fill
+    METRIC_ROUTE_POINTS = 256      # room per robot for the route its deviation is measured against
     RESERVE_LIMIT = 256  # robots reserved at most for formations that repeat forever (beyond it the engine doubles its head-room)
 
     def _robots_expected(self):
@@ -272,10 +291,17 @@ class Simulation:
             (rv, rd), (fv, fd) = rule(me["reach"]), rule(me["finish"])
             self.w.mission_set(rid, np.array([s_[:2] for s_ in states[1:]], dtype=np.float64), rv, fv, rd, fd,
                                self._translation[-1], me["time_scale"])
+            if self._dev_metrics:
+                self.w.track_metrics_set_route(rid, self._route(me))
             if planned:  # Mission::global (robot.rs:1294): Idle until a path has been found
                 self.w.set_idle(rid, True)
                 self._plan_requests.append((rid, tuple(float(v) for v in states[0][:2]), tuple(float(v) for v in states[1][:2]),
                                             desc["rng"].state))
+
+    @staticmethod
+    def _route(r):
+        """a robot's route as export() gives it: mission.routes[0].waypoints"""
+        return [[float(s[0]), float(s[1])] for s in r["waypoints"]]
 
     @property
     def translation(self):
@@ -326,6 +352,9 @@ class Simulation:
             me["waypoints"], me["target"], me["idle"] = [w.copy() for w in wps], 1, False
         if ids:
             self.w.apply_global_paths(ids, paths, np.stack(means), reset_tracking=True, route=True, activate=True)
+            if self._dev_metrics:  # (the robots were Idle so far: no sample was measured against the route this one replaces)
+                for rid in ids:
+                    self.w.track_metrics_set_route(rid, self._route(self.robots[rid]))
 
     def _collect_plans(self):
         """sliced: the requests that have ended by the slices enqueued so far -> _plans_ready; a robot that is gone has its
@@ -448,6 +477,8 @@ class Simulation:
         if not self._trk_clock_set:
             self.w.tracks_set_clock(self.tick_no)
             self._trk_clock_set = True
+        if not self._sample_log:  # (nothing is appended: nothing to drain)
+            return
         most = robots * min(ticks, ticks * self.dt_ns // self.TRACK_PERIOD_NS + 1)
         if self._trk_bound + most > self.TRACK_LOG_SAMPLES:
             self._tracks_device()
@@ -714,6 +745,35 @@ class Simulation:
                 # (setup_goal_areas_for_junction_scenario, goal_area.rs:105-119) is commented out of the plugin (:8-11):
                 # the exported map is empty in the reference itself
                 "goal_areas": {}}
+
+    # -- the run metrics (the reference's scripts/ldj.py and scripts/perpendicular-path-deviation.py over an export) -----------
+    def metrics(self):
+        """{"robots": {id: {ldj, path_deviation, mean_deviation, max_deviation, distance_travelled, duration, dimensionless_jerk,
+        deviation_sum, n_positions, n_velocities, n_unrouted}}, "summary": {figure: track_metrics.summary}, "makespan",
+        "collisions": {"robots", "environment"}}.  With device_metrics the records are the device's (one read that waits);
+        otherwise the streaming restatement (track_metrics.Stream) over the robots' positions / velocities lists and the routes
+        export() gives — the same figures bit for bit, and the checker of the device."""
+        if self.dev:
+            self._flush_trackers(synchronise=True)
+        self._tracks()
+        if self._dev_metrics:
+            recs = self.w.track_metrics_read() if self._trk_clock_set else []
+            recs = [{k: rec[k].item() for k in rec.dtype.names} for rec in recs]
+            recs += [_metrics.Stream().read() for _ in range(len(self.robots) - len(recs))]
+        else:
+            recs = [_metrics.stream([(v["velocity"][0], v["velocity"][2]) for v in r["velocities"]], r["positions"], self._route(r))
+                    for r in self.robots]
+        robots = {}
+        for r, rec in zip(self.robots, recs):
+            fin = r["finished_at"] if r["finished_at"] is not None else self.elapsed()
+            robots[str(r["id"])] = {**_metrics.robot_metrics(rec), "distance_travelled": float(r["travelled"]), "duration": fin - r["started_at"],
+                                    "dimensionless_jerk": rec["dimensionless_jerk"], "deviation_sum": rec["deviation_sum"],
+                                    "n_positions": rec["n_positions"], "n_velocities": rec["n_velocities"], "n_unrouted": rec["n_unrouted"]}
+        figures = ("ldj", "path_deviation", "mean_deviation", "max_deviation", "distance_travelled", "duration")
+        env_coll = self.environment_collisions if self._env_coll else {}
+        return {"robots": robots, "summary": {f: _metrics.summary([m[f] for m in robots.values()]) for f in figures},
+                "makespan": self.elapsed(),
+                "collisions": {"robots": sum(h["times"] for h in self.collisions.values()), "environment": sum(h["times"] for h in env_coll.values())}}
 
     def export_json(self, path):
         with open(path, "w", encoding="utf-8") as f:

@@ -547,6 +547,28 @@ class World:
     def tracks_clear(self):
         self._chk(self._L.mgx_tracks_clear(self._w))
 
+    def tracks_set_logging(self, on=True):
+        """off: a sample still moves the timer, the previous sample, the distance and the run metrics, but is not appended to the log"""
+        self._chk(self._L.mgx_tracks_set_logging(self._w, 1 if on else 0))
+
+    # -- run metrics on the device (include/mgx.h, mgx_track_metrics_*): dimensionless jerk and path deviation per robot
+    def track_metrics_enable(self, enabled=True, max_route_points=0):
+        """while on (the trackers must be), every sample a tracker pass takes also feeds the robot's jerk and deviation state"""
+        self._chk(self._L.mgx_track_metrics_enable(self._w, 1 if enabled else 0, int(max_route_points)))
+
+    def track_metrics_set_route(self, robot, xy):
+        """the polyline [n, 2] f64 the robot's deviation is measured against from the next pass on (None or empty: no route)"""
+        pts = np.zeros((0, 2), np.float64) if xy is None else np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        self._chk(self._L.mgx_track_metrics_set_route(self._w, int(robot), pts.ctypes.data if len(pts) else None, len(pts)))
+
+    def track_metrics_read(self):
+        """one record per robot (hostlib.track_metrics_dtype: n_positions, n_velocities, n_unrouted, flags, dimensionless_jerk,
+        vmax2, deviation_sum, deviation_max), finalised on a copy of the device's state.  Synchronises."""
+        n = self.num_robots()[0]
+        out = np.zeros(n, hostlib.track_metrics_dtype())
+        self._chk(self._L.mgx_track_metrics_read(self._w, out.ctypes.data if n else None, n))
+        return out
+
     # -- the global planner (include/mgx.h): batched RRT* over the map's colliders
     def planner_enable(self, env, params=None):
         """env: an environment dict — its colliders go to the device; params: a dict as global_planner.params makes it (the fields

@@ -170,6 +170,20 @@ pub struct mgx_track_sample {
     pub velocity: [f32; 3],
 }
 
+/// one robot's run metrics (include/mgx.h, mgx_track_metrics_read): LDJ = -ln(dimensionless_jerk)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_track_metrics {
+    pub n_positions: u32,
+    pub n_velocities: u32,
+    pub n_unrouted: u32,
+    pub flags: u32,
+    pub dimensionless_jerk: f64,
+    pub vmax2: f64,
+    pub deviation_sum: f64,
+    pub deviation_max: f64,
+}
+
 /// the global planner's parameters (include/mgx.h, mgx_planner_enable)
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -362,6 +376,10 @@ extern "C" {
     pub fn mgx_tracks_update(w: *mut mgx_world, positions_xyz: *const f32, moved: *const u8, tick: u64) -> c_int;
     pub fn mgx_tracks_take(w: *mut mgx_world, samples: *mut mgx_track_sample, capacity: u64, n_taken: *mut u64, n_in_log: *mut u64, dropped: *mut u64, travelled: *mut f64) -> c_int;
     pub fn mgx_tracks_clear(w: *mut mgx_world) -> c_int;
+    pub fn mgx_track_metrics_enable(w: *mut mgx_world, enabled: i32, max_route_points: u32) -> c_int;
+    pub fn mgx_track_metrics_set_route(w: *mut mgx_world, robot: i32, xy: *const f64, n_points: u32) -> c_int;
+    pub fn mgx_tracks_set_logging(w: *mut mgx_world, on: i32) -> c_int;
+    pub fn mgx_track_metrics_read(w: *mut mgx_world, out: *mut mgx_track_metrics, capacity: u64) -> c_int;
     pub fn mgx_planner_enable(w: *mut mgx_world, env: *const mgx_env_desc, params: *const mgx_plan_params) -> c_int;
     pub fn mgx_plan_paths(w: *mut mgx_world, n: u32, requests: *const mgx_plan_request, results: *mut mgx_plan_result, path_xy: *mut f32, point_capacity: u32, n_points: *mut u32) -> c_int;
     pub fn mgx_plan_tree(w: *mut mgx_world, request: u32, capacity: u32, xy: *mut f64, parent: *mut i32, cost: *mut f64, n_nodes: *mut u32) -> c_int;

@@ -7,7 +7,10 @@ default 64); --planner-half-extent H and --planner-max-iterations N replace the 
 config.rrt.max-iterations.  Without it those scenarios are left out (named explicitly, they raise).
 --host-trackers keeps the position / velocity samples on the host (every tick's Transforms come back, and no distance is
 accumulated: mean_distance stays 0): for A/B runs against the device's trackers, which are the default.
-usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [--host-trackers] [--global-planner [device|host|sliced]]
+--metrics prints the run metrics after each scenario's line — per robot the LDJ, the path deviation figures, distance and mission
+duration, then the per-run summaries (Simulation.metrics(); carried on the device unless --host-trackers); with --no-sample-log no
+sample is logged on the device and the robots' positions / velocities lists stay empty.
+usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
            [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N] [scenario-dir | name ...]"""
 import json
 import os
@@ -29,6 +32,14 @@ if env_collisions:
 host_trackers = "--host-trackers" in args
 if host_trackers:
     args.remove("--host-trackers")
+metrics = "--metrics" in args
+if metrics:
+    args.remove("--metrics")
+no_sample_log = "--no-sample-log" in args
+if no_sample_log:
+    args.remove("--no-sample-log")
+if no_sample_log and (not metrics or host_trackers):
+    sys.exit("--no-sample-log needs --metrics on the device's trackers")
 global_planner, overrides = None, {}
 if "--global-planner" in args:
     i = args.index("--global-planner")
@@ -54,7 +65,7 @@ for name in names:
     t0 = time.perf_counter()
     s = sim.Simulation(sc, World(config.world_params(sc["config"])), environment_collisions=env_collisions,
                        global_planner=global_planner, planner_overrides=overrides, plan_budget=plan_budget,
-                       device_trackers=False if host_trackers else None)
+                       device_trackers=False if host_trackers else None, device_metrics=metrics and not host_trackers, sample_log=not no_sample_log)
     s.run(max_time=max_time)
     wall = time.perf_counter() - t0
     done = [r for r in s.robots if r["completed"]]
@@ -66,3 +77,12 @@ for name in names:
                       "topology_events": len(s.events),
                       **({"plans": len(s._plan_log), "plans_failed": sum(q["status"] != 0 for q in s._plan_log)} if global_planner else {}),
                       **({"environment_collisions": sum(h["times"] for h in s.environment_collisions.values())} if env_collisions else {})}), flush=True)
+    if metrics:
+        m = s.metrics()
+        cols = ("ldj", "path_deviation", "mean_deviation", "max_deviation", "distance_travelled", "duration")
+        print("  " + "robot".rjust(8) + "".join(c.rjust(20) for c in cols))
+        for rid, row in m["robots"].items():
+            print("  " + rid.rjust(8) + "".join(f"{row[c]:20.6f}" for c in cols))
+        for stat in ("robots", "mean", "median", "largest", "smallest", "variance", "stdev"):
+            print("  " + stat.rjust(8) + "".join((f"{m['summary'][c][stat]:20d}" if stat == "robots" else f"{m['summary'][c][stat]:20.6f}") for c in cols))
+        print("  " + json.dumps({"makespan": m["makespan"], "collisions": m["collisions"]}), flush=True)

@@ -7,6 +7,11 @@ comparison in alternating blocks after a warm-up:
     python tools/tracks_bench.py --part scenarios   # Junction Twoway and Circle Experiment as tools/run_scenarios.py runs them,
                                                     # device trackers against --host-trackers (Simulation(device_trackers=False))
 
+    python tools/tracks_bench.py --part tick --metrics [--no-log]
+                                                    # the same with the run metrics carried by the pass of the "on" side (every
+                                                    # robot measured against the line from its start to its goal), and with the
+                                                    # sample log switched off (profiles/track_metrics.md)
+
 One JSON line per part: medians, the spread (min / max) of the blocks, and the ratio of the medians."""
 import argparse
 import json
@@ -30,7 +35,11 @@ ap.add_argument("--blocks", type=int, default=7, help="per side")
 ap.add_argument("--warmup", type=int, default=60)
 ap.add_argument("--max-time", type=float, default=60.0, help="simulated seconds per scenario run")
 ap.add_argument("--reps", type=int, default=7, help="scenario runs per side")
+ap.add_argument("--metrics", action="store_true", help="tick part: the run metrics on in the blocks that have the trackers on")
+ap.add_argument("--no-log", action="store_true", help="tick part: the sample log off in the blocks that have the trackers on (needs --metrics)")
 a = ap.parse_args()
+if a.no_log and not a.metrics:
+    ap.error("--no-log needs --metrics (nothing else would be left of the samples)")
 
 
 def spread(v):
@@ -52,6 +61,12 @@ def part_tick():
                          t0=[rb["t0"] for rb in sc["robots"]], steps=sc["steps"], comms_radius=8.0, target_speed=sc["target_speed"])
         if tracks:  # (hz = 10: a sample per robot and tick — room for all of them, nothing is taken inside the timed ticks)
             w.tracks_enable(True, period_ns=100_000_000, tick_ns=100_000_000, next_tick=0, sample_capacity=n * (a.ticks + a.warmup))
+            if a.metrics:
+                w.track_metrics_enable(True, max_route_points=2)
+                for r, rb in enumerate(sc["robots"]):
+                    w.track_metrics_set_route(r, [[float(rb["pos"][0]), float(rb["pos"][1])], [float(rb["goal"][0]), float(rb["goal"][1])]])
+                if a.no_log:
+                    w.tracks_set_logging(False)
         for _ in range(a.warmup):
             d.tick()
         w.synchronize()
@@ -65,6 +80,10 @@ def part_tick():
             got, _, dropped, dist = w.tracks_take()
             assert not dropped and (dist > 0).all()
             taken = len(got)
+            assert taken == (0 if a.no_log else n * (a.ticks + a.warmup))
+            if a.metrics:
+                rec = w.track_metrics_read()
+                assert (rec["n_positions"] == a.ticks + a.warmup).all() and (rec["flags"] == 3).all() and (rec["dimensionless_jerk"] >= 0).all()
         assert (d.finished_at < 0).all()  # (nobody has arrived: all robots move in every tick)
         return a.ticks / wall, wall, taken, list(w.last_sweep())
     block(True)  # (code objects, allocator, clocks)
@@ -76,7 +95,7 @@ def part_tick():
             walls.append(wall)
     on, off = spread(rates["on"]), spread(rates["off"])
     print(json.dumps({"part": "tick", "robots": n, "K": a.K, "ticks_per_block": a.ticks, "block_seconds_min": round(min(walls), 2),
-                      "unit": "mission ticks/s", "trackers_off": off, "trackers_on": on, "on_over_off": round(on["median"] / off["median"], 4),
+                      "unit": "mission ticks/s", "metrics": a.metrics, "sample_log": not a.no_log, "trackers_off": off, "trackers_on": on, "on_over_off": round(on["median"] / off["median"], 4),
                       "off_spread_rel": round((off["max"] - off["min"]) / off["median"], 4),
                       "on_spread_rel": round((on["max"] - on["min"]) / on["median"], 4), "samples_per_block": taken,
                       "last_sweep": sweep}), flush=True)
