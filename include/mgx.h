@@ -952,6 +952,63 @@ int mgx_env_collisions_read(mgx_world *w, uint64_t first, mgx_env_collision_even
                             uint64_t *n_total, uint64_t *dropped, uint32_t *per_robot);
 int mgx_env_collisions_clear(mgx_world *w);
 
+/* ---- goal areas on the device: the first arrival of every robot in every area ----------------------------------
+ * goal_area::detect_collisions (crates/magics/src/goal_area.rs:67-103, FixedUpdate): every robot carries a
+ * goal_area::components::Collider(Ball::new(radius)) (planner/spawner.rs:638); per goal area the reference records the first
+ * time each robot's ball intersects the area's box, and export.rs:235-247, 261, 556-571 writes it as
+ * goal_areas: {area: {aabb, history: {robot: seconds}}}, which scripts/analyse-junction-scenario.py:52-109 reads (the
+ * throughput of a junction).  The one system that spawns areas (setup_goal_areas_for_junction_scenario, goal_area.rs:105-119)
+ * is commented out of the reference's plugin, so its exports carry an empty map; here the caller hands the areas in.
+ * Restated on the host by magics_amd/sim.py (goal_area_contacts, _goal_areas_host), which is the checker.
+ * AREA: mgx_goal_area {mins, maxs} in world (x, z), the plane the collision passes use.  The corners are sorted per axis when
+ *   the areas are set (mins = min of the two, maxs = max): the reference's first junction area is written with its second
+ *   coordinates swapped, Aabb::new((-8, -48), (8, -52)).  Centre c = (mins + maxs) * 0.5f and half extents
+ *   h = (maxs - mins) * 0.5f, in f32, every operation rounded on its own.  At most MGX_GOAL_AREAS_MAX areas.
+ * CONTACT: the cuboid line of the SPECIFICATION OF A CONTACT above with t = c, h as here and r = (float)desc.radius:
+ *   e = max(|p - c| - h, 0) per axis, e_x*e_x + e_z*e_z <= r*r, in f32, nothing contracted (the same in libmgx.so and
+ *   libmgx_fma.so; the device runs the very predicate of the robot-environment pass); a NaN anywhere means no contact.  As
+ *   there, this is the specification, not a claim about parry2d.
+ * WHO: the robots alive as the robot-robot pass defines alive (not removed, not ghosts) — idle robots and robots whose mission
+ *   is complete included: they are still in the reference's query.
+ * STATE per (area, robot id): the tick of the first pass in which the two touched, or "never".  Once set it never changes
+ *   (history.contains_key -> continue); the arrivals of robots despawned later stay.  The table is no part of the blob layout:
+ *   it survives an in-place append, a relayout, and a robot that joins between mgx_mission_tick_begin and _end, as the
+ *   trackers' arrays do; robots added later start at "never".  On a world with head-room (mgx_world_reserve) the table is
+ *   strided for the reserved robots, so an append does not move it.
+ * CLOCK: one u64 per world, the index k of the coming tick — a clock of its own (the trackers may be off).  The device stores
+ *   tick indices only (k + 1 in 32 bits: a tick beyond 2^32 - 2 is MGX_ERR_INVALID).  Seconds are made on the host:
+ *   elapsed = (k + 1) * tick_ns as a duration of whole seconds and nanoseconds, value = (float)secs + (float)nanos / 1e9f —
+ *   Duration::as_secs_f32, which Time<Fixed>::elapsed_seconds() returns inside the k-th FixedUpdate.  bevy_time is third party
+ *   and absent from the reference's tree: this reading is the specification.
+ * mgx_goal_areas_enable(w, areas, n_areas, next_tick): on (default: off — no kernel, no allocation, no change to anything
+ *   else).  n_areas == 0 switches off and drops the state.  Calling it while on is MGX_ERR_STATE (switch off first).
+ *   MGX_ERR_INVALID: a non-finite corner, more than MGX_GOAL_AREAS_MAX areas, areas == NULL with n_areas > 0.
+ * mgx_goal_areas_set_clock: the tick index of the coming tick.
+ * While on, every mgx_mission_tick_end (so every mgx_mission_tick and every tick of mgx_mission_run) enqueues ONE pass on the
+ *   Transforms after that tick's move and the robots alive after that tick's despawns, beside the collision passes; the clock
+ *   then advances by one.  No synchronisation, nothing read back; no launch while no robot is alive.
+ * mgx_goal_areas_update: the same pass over positions the caller keeps ([n_robots][3], x and z are read; NULL: the device's
+ *   mission Transforms as they are), at a tick the caller names.  Does not move the clock; enqueued, not waited for.
+ * mgx_goal_areas_read: the one call that synchronises.  Every arrival in (tick, robot, area) order; *n_total and per_area
+ *   [n_areas] (may be NULL) are always filled.  capacity 0 asks for the size; a non-zero capacity below *n_total is
+ *   MGX_ERR_INVALID.
+ * mgx_goal_areas_clear: everybody "never"; the areas and the clock stay.
+ * Unsharded worlds (MGX_ERR_STATE on a world with ghosts); MGX_ERR_STATE from every call but _enable while switched off. */
+#define MGX_GOAL_AREAS_MAX 64u
+typedef struct mgx_goal_area {      /* 16 bytes */
+    float mins[2], maxs[2];         /* (x, z); either order per axis */
+} mgx_goal_area;
+typedef struct mgx_goal_arrival {   /* 16 bytes */
+    uint64_t tick;
+    int32_t area, robot;
+} mgx_goal_arrival;
+int mgx_goal_areas_enable(mgx_world *w, const mgx_goal_area *areas, uint32_t n_areas, uint64_t next_tick);
+int mgx_goal_areas_set_clock(mgx_world *w, uint64_t next_tick);
+int mgx_goal_areas_update(mgx_world *w, const float *positions_xyz, uint64_t tick);
+int mgx_goal_areas_read(mgx_world *w, mgx_goal_arrival *arrivals, uint64_t capacity, uint64_t *n_total,
+                        uint32_t *per_area /* [n_areas] or NULL */);
+int mgx_goal_areas_clear(mgx_world *w);
+
 /* ---- trackers on the device: position and velocity samples, distance travelled ---------------------------------
  * track_positions / track_velocities (crates/magics/src/planner/tracking.rs:117-136, 210-240; both on 100 ms timers,
  * planner/spawner.rs:627-628) and the distance travelled the export carries (export.rs:249-262), restated on the host by

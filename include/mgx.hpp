@@ -307,6 +307,31 @@ public:
         return out;
     }
     void env_collisions_clear() { check(mgx_env_collisions_clear(w_)); }
+    /// goal areas on the device (goal_area.rs:67-103, specified in mgx.h): while enabled every mission tick ends with one pass that
+    /// records the first arrival of every robot in every area; `update` is the same pass over Transforms the caller keeps at a
+    /// tick the caller names; `read` is the one call that waits for the device.  No areas: off
+    void goal_areas_enable(const std::vector<mgx_goal_area> &areas, uint64_t next_tick = 0) {
+        check(mgx_goal_areas_enable(w_, areas.empty() ? nullptr : areas.data(), (uint32_t)areas.size(), next_tick));
+        goal_areas_ = (uint32_t)areas.size();
+    }
+    void goal_areas_set_clock(uint64_t next_tick) { check(mgx_goal_areas_set_clock(w_, next_tick)); }
+    void goal_areas_update(uint64_t tick, const std::vector<std::array<float, 3>> &translations) {
+        check(mgx_goal_areas_update(w_, translations.empty() ? nullptr : translations[0].data(), tick));  // (empty: the device's Transforms)
+    }
+    struct GoalArrivals {
+        std::vector<mgx_goal_arrival> arrivals;  ///< every arrival, in (tick, robot, area) order
+        std::vector<uint32_t> per_area;
+    };
+    GoalArrivals goal_areas_read() {
+        GoalArrivals out;
+        uint64_t total = 0;
+        out.per_area.assign(goal_areas_, 0u);
+        check(mgx_goal_areas_read(w_, nullptr, 0, &total, out.per_area.data()));
+        out.arrivals.resize((size_t)total);
+        if (total) check(mgx_goal_areas_read(w_, out.arrivals.data(), out.arrivals.size(), &total, out.per_area.data()));
+        return out;
+    }
+    void goal_areas_clear() { check(mgx_goal_areas_clear(w_)); }
     /// the trackers on the device (planner/tracking.rs:117-136, 210-240, specified in mgx.h): while enabled every mission tick ends
     /// with one pass — a sample of every moving robot every `period_ns` and its distance travelled; `update` is the sampling pass
     /// over Transforms the caller keeps; `take` is the one call that waits for the device and empties the log
@@ -404,6 +429,7 @@ public:
 private:
     mgx_world *w_ = nullptr;
     uint32_t K_ = 0;
+    uint32_t goal_areas_ = 0;  // areas handed to goal_areas_enable (the size of per_area)
 };
 
 inline void FactorGraph::internal_factor_iteration() { check(mgx_internal_factor_iteration(world_->raw(), robot_)); }

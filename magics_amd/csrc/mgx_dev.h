@@ -384,6 +384,24 @@ struct TrackDev {
     uint32_t max_route_points; // bound of the segment loop
 };
 
+// Goal areas on the device (mgx_goal_areas.hip, which says what a pass does): the areas as the pass reads them and the table of
+// first arrivals, keyed by (area, robot id).
+constexpr int GOAL_AREAS_MAX = 64;  // == MGX_GOAL_AREAS_MAX (mgx_goal_areas.hip asserts it): one lane of a wave stages one area
+struct GoalAreaRec {           // centre and half extents in world (x, z), f32
+    float cx, cz, hx, hz;
+};
+struct GoalAreasDev {
+    const float *pos;          // [n][3] Transform::translation (x, height, z)
+    const uint8_t *alive;      // [n] not removed, not a ghost
+    const float *radius;       // [n] (float)desc.radius
+    const GoalAreaRec *areas;  // [n_areas]
+    uint32_t *first;           // [n_areas][stride] tick + 1 of the first pass in which (area, robot) touched, 0: never
+    uint32_t stride;           // robots a row has room for (>= n: the head-room of a reserved world)
+    uint32_t stamp;            // this pass's tick + 1
+    int n;                     // robots of the world (ids 0 .. n-1)
+    int n_areas;
+};
+
 // The map's side of EnvCollDev on its own: what a kernel needs to test a ball against the colliders (mgx_env_contact.h).  The
 // global planner's feasibility test reads it (mgx_planner.hip).
 struct EnvMapDev {

@@ -16,6 +16,14 @@ namespace mgx {
 
 __device__ __forceinline__ float sq_sum(float a, float b) { return __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b)); }
 
+// the cuboid line of that contact: centre (tx, tz), half extents (hx, hz), no rotation.  env_touches' cuboid arm, and the whole
+// contact of a goal area (mgx_goal_areas.hip)
+__device__ __forceinline__ bool cuboid_touches(float tx, float tz, float hx, float hz, float x, float z, float r) {
+    const float dx = __fsub_rn(fabsf(__fsub_rn(x, tx)), hx), dz = __fsub_rn(fabsf(__fsub_rn(z, tz)), hz);
+    if (dx != dx || dz != dz) return false;  // (fmaxf below would drop a NaN)
+    return sq_sum(fmaxf(dx, 0.f), fmaxf(dz, 0.f)) <= __fmul_rn(r, r);
+}
+
 // the contact of include/mgx.h: every operation rounded to f32 on its own; a NaN anywhere: false
 __device__ inline bool env_touches(const EnvCollider &k, const float *__restrict__ verts, float x, float z, float r) {
     switch (k.kind) {
@@ -23,11 +31,7 @@ __device__ inline bool env_touches(const EnvCollider &k, const float *__restrict
         const float rs = __fadd_rn(r, k.radius);
         return sq_sum(__fsub_rn(x, k.tx), __fsub_rn(z, k.tz)) <= __fmul_rn(rs, rs);
     }
-    case MGX_COLLIDER_CUBOID: {
-        const float dx = __fsub_rn(fabsf(__fsub_rn(x, k.tx)), k.hx), dz = __fsub_rn(fabsf(__fsub_rn(z, k.tz)), k.hz);
-        if (dx != dx || dz != dz) return false;  // (fmaxf below would drop a NaN)
-        return sq_sum(fmaxf(dx, 0.f), fmaxf(dz, 0.f)) <= __fmul_rn(r, r);
-    }
+    case MGX_COLLIDER_CUBOID: return cuboid_touches(k.tx, k.tz, k.hx, k.hz, x, z, r);
     case MGX_COLLIDER_POLYGON: {
         const uint32_t n = k.n_vertices;
         if (n == 0) return false;

@@ -8,7 +8,7 @@
 // disturb existing state (the reference mutates its graphs in place,
 // factorgraph.rs:190-226,304-353,380-436).
 //
-// ONE translation unit, fourteen files: the parts below share file-local helpers (commit, confirm_resident, flush_counts, sweep,
+// ONE translation unit, fifteen files: the parts below share file-local helpers (commit, confirm_resident, flush_counts, sweep,
 // run_resident, linger_close ...) that have no business in the library's symbol table, so they are included here in
 // dependency order instead of being linked:
 //   mgx_world_types.h — what the host side is made of: launcher prototypes of the kernel files, error text, device buffers, the pinned argument ring, the neighbour search's and the resident launches' state, the host mirror's records (Robot, IrConn), connection sets and index, the world itself, the entry hooks of the C ABI (MGX_ENTER)
@@ -21,6 +21,7 @@
 //   mgx_world_topology.inc — C ABI: dynamic inter-robot topology — neighbour search, delete / create_interrobot_factors
 //   mgx_world_collisions.inc — C ABI: robot-robot and robot-environment collision bookkeeping on the device, one contact book under both (the passes mgx_mission_tick_end enqueues)
 //   mgx_world_tracks.inc — C ABI: the trackers on the device — position / velocity samples and distance travelled (the pass mgx_mission_tick_end enqueues beside the collision passes)
+//   mgx_world_goal_areas.inc — C ABI: goal areas on the device — the first arrival of every robot in every area (the pass mgx_mission_tick_end enqueues beside the collision passes)
 //   mgx_world_planner.inc — C ABI: the global planner — the map it plans over, batched RRT* requests in bounded launches, the trees read back
 //   mgx_world_missions.inc — C ABI: missions on the device, many ticks per call, fine-grained sweeps, schedules -> launches
 //   mgx_world_schedule.inc — C ABI: batches, mgx_iterate, prior changes, mgx_tick, resets, diagnostics, read-back
@@ -34,6 +35,7 @@
 #include "mgx_world_topology.inc"
 #include "mgx_world_collisions.inc"
 #include "mgx_world_tracks.inc"
+#include "mgx_world_goal_areas.inc"
 #include "mgx_world_planner.inc"
 #include "mgx_world_missions.inc"
 #include "mgx_world_schedule.inc"

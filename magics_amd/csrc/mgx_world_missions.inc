@@ -231,6 +231,12 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     if (w->coll.enabled && (rc = collisions_pass(w, ms.translation_d.p, ms.moving_d.p, s)) != MGX_OK) return rc;
     // update_robot_environment_collisions (collisions.rs:368-438), beside it on the same stream (mgx_env_collisions_read)
     if (w->envcoll.enabled && (rc = env_collisions_pass(w, ms.translation_d.p, ms.moving_d.p, s)) != MGX_OK) return rc;
+    // goal_area::detect_collisions (goal_area.rs:67-103), beside them on the same Transforms and alive bytes (mgx_goal_areas_read);
+    // the goal areas' own clock then names the coming tick
+    if (w->goals.enabled) {
+        if ((rc = goal_areas_pass(w, ms.translation_d.p, ms.moving_d.p, w->goals.clock, s)) != MGX_OK) return rc;
+        w->goals.clock += 1;
+    }
     // track_positions / track_velocities (tracking.rs:117-136, 210-240) and the distance travelled, for the robots k_mission_prepare
     // has just moved (its `what` flags): in front of the prior updates, which change the means the increment is formed from
     // again — no synchronisation, nothing read back (mgx_tracks_take).  The world's clock then names the coming tick

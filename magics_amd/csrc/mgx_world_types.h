@@ -81,6 +81,8 @@ hipError_t launch_env_collisions_pass(const EnvCollDev &c, hipStream_t s);
 // mgx_tracks.hip
 hipError_t launch_tracks_pass(const TrackDev &t, hipStream_t s);
 hipError_t launch_track_metrics_read(int n, const TrackMetricsState *state, TrackMetricsOut *out, hipStream_t s);
+// mgx_goal_areas.hip
+hipError_t launch_goal_areas_pass(const GoalAreasDev &g, hipStream_t s);
 // mgx_planner.hip
 hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s);
 }  // namespace mgx
@@ -819,6 +821,20 @@ struct mgx_world {
         DevBuf<TrackRoute> routes;
         DevBuf<TrackMetricsOut> mout;    // what mgx_track_metrics_read finalises into
     } tracks;
+    // goal areas on the device (mgx_goal_areas_*, mgx_world_goal_areas.inc, mgx_goal_areas.hip): the table of first arrivals keyed
+    // by (area, robot id) — no part of the blob layout, so a relayout moves nothing here; its rows have room for `stride` robots
+    // (the head-room of a reserved world: an append does not move it) — and a clock of its own
+    struct GoalAreas {
+        bool enabled = false;
+        uint32_t n_areas = 0;
+        uint32_t stride = 0;     // robots a row of `first` has room for
+        size_t n_sized = 0;      // robots the table was last sized and the radii uploaded for
+        uint64_t clock = 0;      // the simulated tick index of the coming tick
+        DevBuf<GoalAreaRec> recs;
+        DevBuf<uint32_t> first;  // [n_areas][stride] tick + 1, 0: never
+        DevBuf<float> radius, pos;  // pos: positions the caller handed in (mgx_goal_areas_update)
+        DevBuf<uint8_t> alive;      // ... and who was alive then
+    } goals;
     // the global planner (mgx_planner_enable, mgx_world_planner.inc): the map and two pools of requests.  `pool`: the requests that
     // ride the stream (mgx_plan_submit / _advance / _collect), 256 blocks of 16 slots.  `call`: the requests of one mgx_plan_paths,
     // which gives its slots up before it returns — one block, sized by the largest call so far; the arrays of given-up slots are

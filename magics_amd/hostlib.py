@@ -209,6 +209,11 @@ SYMBOLS = {
     "mgx_collisions_update": (C.c_int, [_V, C.c_void_p]),
     "mgx_collisions_read": (C.c_int, [_V, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_void_p]),
     "mgx_collisions_clear": (C.c_int, [_V]),
+    "mgx_goal_areas_enable": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.c_uint64]),
+    "mgx_goal_areas_set_clock": (C.c_int, [_V, C.c_uint64]),
+    "mgx_goal_areas_update": (C.c_int, [_V, C.c_void_p, C.c_uint64]),
+    "mgx_goal_areas_read": (C.c_int, [_V, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p]),
+    "mgx_goal_areas_clear": (C.c_int, [_V]),
     "mgx_tracks_enable": (C.c_int, [_V, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64]),
     "mgx_tracks_set_clock": (C.c_int, [_V, C.c_uint64]),
     "mgx_tracks_update": (C.c_int, [_V, C.c_void_p, C.c_void_p, C.c_uint64]),
@@ -420,6 +425,39 @@ def env_collision_event_dtype():
     """numpy view of an array of mgx_env_collision_event"""
     import numpy as np
     return np.dtype([("pass", np.uint64), ("robot", np.int32), ("collider", np.int32), ("mins", np.float32, 2), ("maxs", np.float32, 2)])
+
+
+GOAL_AREAS_MAX = 64  # MGX_GOAL_AREAS_MAX
+
+
+class GoalArea(C.Structure):
+    """mgx_goal_area (include/mgx.h)"""
+    _fields_ = [("mins", C.c_float * 2), ("maxs", C.c_float * 2)]
+
+
+class GoalArrival(C.Structure):
+    """mgx_goal_arrival (include/mgx.h)"""
+    _fields_ = [("tick", C.c_uint64), ("area", C.c_int32), ("robot", C.c_int32)]
+
+
+def goal_area_dtype():
+    """numpy view of an array of mgx_goal_area"""
+    import numpy as np
+    return np.dtype([("mins", np.float32, 2), ("maxs", np.float32, 2)])
+
+
+def goal_arrival_dtype():
+    """numpy view of an array of mgx_goal_arrival"""
+    import numpy as np
+    return np.dtype([("tick", np.uint64), ("area", np.int32), ("robot", np.int32)])
+
+
+def goal_seconds(tick, tick_ns):
+    """the time the reference writes for an arrival in the pass of tick k (include/mgx.h, CLOCK): Duration::as_secs_f32 of
+    (k + 1) * tick_ns — (float)secs + (float)nanos / 1e9f, each operation rounded to f32 — as a Python float"""
+    import numpy as np
+    secs, nanos = divmod((int(tick) + 1) * int(tick_ns), 1_000_000_000)
+    return float(np.float32(secs) + np.float32(nanos) / np.float32(1e9))
 
 
 class TrackSample(C.Structure):

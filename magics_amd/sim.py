@@ -13,7 +13,8 @@ by the frame's Update systems that matter to the path (the formation spawners):
 
 The reference runs its Update systems at the display's frame rate against virtual time, so the
 interleaving of spawns with fixed ticks is not reproducible there; here a frame is exactly one
-fixed tick long.  Rendering, picking and goal areas are outside the path (SURVEY §8 out of scope); RRT* planning
+fixed tick long.  Rendering and picking are outside the path (SURVEY §8 out of scope); goal areas (goal_area.rs:67-103) are
+recorded on request (`goal_areas=`: the reference spawns none, the caller hands them in); RRT* planning
 (`planning-strategy: rrt-star`) is rejected unless a global planner is asked for (`global_planner=`: the engine's, or its host
 restatement, magics_amd/global_planner.py).  Robot-environment collisions (planner/collisions.rs:368-438) are counted on request
 (`environment_collisions=True`) against the map's colliders (hostlib.env_colliders) with the contact include/mgx.h
@@ -69,6 +70,43 @@ def environment_contacts(colliders, vertices, pos, rad):
     return out
 
 
+# setup_goal_areas_for_junction_scenario (goal_area.rs:105-119; commented out of the reference's plugin): the two exits of the
+# junction.  The first box is written with its second coordinates swapped, as there
+JUNCTION_GOAL_AREAS = (((-8.0, -48.0), (8.0, -52.0)), ((48.0, -8.0), (52.0, 8.0)))
+
+
+def goal_area_boxes(areas):
+    """boxes ((x0, z0), (x1, z1)) -> (mins [m, 2], maxs [m, 2]) in f32 with the corners sorted per axis (include/mgx.h, AREA)"""
+    a = np.asarray(areas, dtype=F).reshape(-1, 2, 2)
+    return np.minimum(a[:, 0], a[:, 1]), np.maximum(a[:, 0], a[:, 1])
+
+
+def goal_area_contacts(areas, pos, rad):
+    """The contact of a goal area (include/mgx.h, "goal areas": the cuboid line of the specification of a contact with the box's
+    centre and half extents) in numpy f32, every operation rounded on its own: [n, m] bool, robot i (pos [n, 2] = Transform
+    (x, z), rad [n]) touches box j of `areas` (((x0, z0), (x1, z1)), corners in either order).  A NaN anywhere: no contact.  The
+    checker of the device pass (mgx_goal_areas.hip)."""
+    pos, rad = np.ascontiguousarray(pos, dtype=F).reshape(-1, 2), np.ascontiguousarray(rad, dtype=F).reshape(-1)
+    lo, hi = goal_area_boxes(areas)
+    with np.errstate(all="ignore"):
+        c, h = (lo + hi) * F(0.5), (hi - lo) * F(0.5)
+        dx = np.abs(pos[:, 0:1] - c[None, :, 0]) - h[None, :, 0]
+        dz = np.abs(pos[:, 1:2] - c[None, :, 1]) - h[None, :, 1]
+        ex, ez = np.maximum(dx, F(0)), np.maximum(dz, F(0))          # (np.maximum keeps a NaN: the comparison below is then false)
+        return ex * ex + ez * ez <= (rad * rad)[:, None]
+
+
+def goal_flow(export, window=50.0):
+    """The throughput scripts/analyse-junction-scenario.py:52-109 reads out of an export: the robots that started before
+    `window` seconds and are in some goal area's history, per second of the window — written as there, 1 / (window / n), and
+    0.0 where that divides by zero (n == 0)."""
+    reached = set()
+    for area in export["goal_areas"].values():
+        reached.update(area["history"].keys())
+    n = sum(1 for rid, r in export["robots"].items() if not r["mission"]["started_at"] >= window and rid in reached)
+    return 1 / (window / n) if n else 0.0
+
+
 def _box(lo, hi):
     return {"mins": [float(lo[0]), float(lo[1])], "maxs": [float(hi[0]), float(hi[1])]}
 
@@ -102,7 +140,7 @@ def _take_in(table, read, a, b, what):
 class Simulation:
     def __init__(self, scenario, world, neighbours_method=hostlib.NEIGHBOURS_AUTO, device_missions=None, device_collisions=None,
                  environment_collisions=False, global_planner=None, planner_overrides=None, plan_budget=64, device_trackers=None,
-                 device_metrics=False, sample_log=True):
+                 device_metrics=False, sample_log=True, goal_areas=None, device_goal_areas=None):
         """scenario: `config.load_scenario(dir)` (or a dict of the same shape); world: a fresh
         World-like object created with `config.world_params(scenario["config"])`.
         device_missions (default: whenever the world offers them, i.e. the engine): routes, reached-when rules and
@@ -126,6 +164,12 @@ class Simulation:
         sample_log (default on; False needs device_metrics): False switches the device's sample log off
         (mgx_tracks_set_logging) — the robots' `positions` / `velocities` lists, in export() too, then STAY EMPTY: the run's
         figures are in metrics() and nothing per sample ever leaves the device.
+        goal_areas (default None: the export's goal_areas stays {}, as in the reference, whose plugin spawns none): a list of boxes
+        ((x0, z0), (x1, z1)) in world (x, z), or "junction" (JUNCTION_GOAL_AREAS) — the first tick in which every robot's ball
+        touches every box is recorded (goal_area::detect_collisions, goal_area.rs:67-103) and written into export() and metrics().
+        device_goal_areas (default: whenever the missions live on the device and the world offers goal_areas_enable): the pass
+        runs on the device at the end of every tick (mgx_goal_areas_*) and is read when somebody asks; False: _goal_areas_host
+        below on the host every tick (the checker).
         global_planner (default None: `planning-strategy: rrt-star` raises NotImplementedError): True — robots of that strategy spawn
         Idle (RobotBundle::new, robot.rs:1195, 1294), their requests (taskpoints[0] -> taskpoints[1], a clone of the robot's forked
         stream, config.rrt) are planned in the tick they spawn, all of a tick in ONE mgx_plan_paths, and the paths are applied by ONE
@@ -156,6 +200,19 @@ class Simulation:
             raise ValueError("device_metrics needs device_trackers (the tracker pass carries them)")
         if not self._sample_log and not self._dev_metrics:
             raise ValueError("sample_log=False needs device_metrics (nothing else would be left of the samples)")
+        if isinstance(goal_areas, str):
+            if goal_areas != "junction":
+                raise ValueError('goal_areas: a list of boxes ((x0, z0), (x1, z1)) or "junction"')
+            goal_areas = JUNCTION_GOAL_AREAS
+        self._goal_areas = None if goal_areas is None else [tuple(tuple(float(v) for v in c) for c in box) for box in goal_areas]
+        if self._goal_areas is not None and not 0 < len(self._goal_areas) <= hostlib.GOAL_AREAS_MAX:
+            raise ValueError(f"goal_areas: between 1 and {hostlib.GOAL_AREAS_MAX} boxes")
+        self._dev_goals = self._goal_areas is not None and ((self.dev and hasattr(world, "goal_areas_enable")) if device_goal_areas is None
+                                                            else bool(device_goal_areas))
+        if self._dev_goals and not self.dev:
+            raise ValueError("device_goal_areas needs device_missions (the pass reads the device's Transforms)")
+        self._goal_clock_set = False  # the device's goal-area clock has been set to tick_no (when the first robots tick)
+        self._goal_first = [{} for _ in self._goal_areas or []]  # host pass: per area, robot id -> tick of the first contact
         self._trk_clock_set = False  # the device's clock has been set to tick_no (when the first robots tick)
         self._trk_bound = 0          # samples the device's log holds at the most since it was last taken
         if environment_collisions not in (False, True, "host"):
@@ -208,6 +265,8 @@ class Simulation:
             world.env_collisions_enable(self.env)
         elif self._env_coll:
             self._colliders, self._collider_vertices = hostlib.env_colliders(self.env)
+        if self._dev_goals:
+            world.goal_areas_enable(self._goal_areas, next_tick=0)
         if self._dev_trk:
             world.tracks_enable(True, period_ns=self.TRACK_PERIOD_NS, tick_ns=self.dt_ns, next_tick=0, sample_capacity=self.TRACK_LOG_SAMPLES)
         if self._dev_metrics:
@@ -540,6 +599,48 @@ class Simulation:
         _edges(self._env_collisions, seen, lambda key, i: (np.maximum(pos[i] - rad[i], self._colliders[key[1]]["mins"]),
                                                            np.minimum(pos[i] + rad[i], self._colliders[key[1]]["maxs"])))
 
+    # goal_area::detect_collisions (goal_area.rs:67-103, FixedUpdate): every live robot's Ball against every goal area's box, the
+    # contact of include/mgx.h; the first tick in which the two touch is kept, later ones are not looked at
+    def _goal_areas_host(self, alive, translation, tick):
+        if self._goal_areas is None or self._dev_goals or not alive:
+            return
+        ids = np.array([r["id"] for r in alive])
+        rad = np.array([r["radius"] for r in alive], dtype=F)
+        pos = np.ascontiguousarray(np.asarray(translation)[ids][:, [0, 2]], dtype=F)
+        for i, a in zip(*np.nonzero(goal_area_contacts(self._goal_areas, pos, rad))):
+            self._goal_first[int(a)].setdefault(int(ids[i]), int(tick))
+
+    def _goal_clock(self):
+        """before the first mission tick: the device's goal-area clock names the tick that is coming"""
+        if self._dev_goals and not self._goal_clock_set:
+            self.w.goal_areas_set_clock(self.tick_no)
+            self._goal_clock_set = True
+
+    @property
+    def goal_arrivals(self):
+        """per goal area: robot id -> tick index of the first pass in which the two touched, in (tick, robot) order; [] while
+        no areas are configured.  With the pass on the device this is the one read that waits for it."""
+        if self._goal_areas is None:
+            return []
+        if self._dev_goals:
+            first = [{} for _ in self._goal_areas]
+            for e in self.w.goal_areas_read()[0]:
+                first[int(e["area"])][int(e["robot"])] = int(e["tick"])
+        else:
+            if self.dev:
+                self._flush_trackers(synchronise=True)
+            first = self._goal_first
+        return [dict(sorted(h.items(), key=lambda kv: (kv[1], kv[0]))) for h in first]
+
+    def _goal_areas_export(self):
+        """export.rs:235-247, 556-571: {area: {"aabb": {"mins", "maxs"}, "history": {robot: seconds}}} — the robots' keys are those
+        of export()["robots"]; seconds: hostlib.goal_seconds (Time<Fixed>::elapsed_seconds() inside that FixedUpdate)"""
+        if self._goal_areas is None:
+            return {}
+        lo, hi = goal_area_boxes(self._goal_areas)
+        return {str(a): {"aabb": _box(lo[a], hi[a]), "history": {str(rid): hostlib.goal_seconds(k, self.dt_ns) for rid, k in h.items()}}
+                for a, h in enumerate(self.goal_arrivals)}
+
     def _flush_trackers(self, synchronise=False):
         """device missions: the samples of the last tick, taken from the Transforms that tick sent to the host behind its
         launches (complete after the next synchronisation — the next tick's own, or an explicit one here)"""
@@ -550,7 +651,7 @@ class Simulation:
             return
         if synchronise:
             self.w.synchronize()
-        moving, now, alive = self._pending_track
+        moving, now, alive, tick = self._pending_track
         self._pending_track = None
         tr = self.w.mission_translations()
         if not self._dev_trk:
@@ -558,14 +659,17 @@ class Simulation:
         if not self._dev_coll:
             self._collide(alive, tr)
         self._collide_environment(alive, tr)
+        self._goal_areas_host(alive, tr, tick)
 
     def _host_needs_transforms(self):
         """a host tracker or a host collision pass still reads every tick's Transforms"""
-        return not self._dev_trk or not self._dev_coll or (self._env_coll and not self._dev_env_coll)
+        return (not self._dev_trk or not self._dev_coll or (self._env_coll and not self._dev_env_coll)
+                or (self._goal_areas is not None and not self._dev_goals))
 
     def _tick_device(self):
         w = self.w
         self._tracks_room(1, sum(1 for r in self.robots if r["alive"]))
+        self._goal_clock()
         self.next_number, created, deleted, fin = w.mission_tick_begin(self.comms_radius, self.next_number, despawn_finished=self.despawn,
                                                                        method=self.method)
         self._flush_trackers()
@@ -587,7 +691,7 @@ class Simulation:
                 ant[[r["id"] for r in live]] = active
         moving = [r for r in live if not r["completed"] and not r["idle"]]
         w.mission_tick_end(self.steps, float(self.max_speed), float(self.dt32), antennas=ant)
-        self._pending_track = (moving, (self.tick_no + 1) * self.dt_ns * 1e-9, live)
+        self._pending_track = (moving, (self.tick_no + 1) * self.dt_ns * 1e-9, live, self.tick_no)
 
     def tick(self):
         w = self.w
@@ -624,6 +728,7 @@ class Simulation:
             self._track(moving, self._translation, (self.tick_no + 1) * self.dt_ns * 1e-9)
             self._collide(live, self._translation)
             self._collide_environment(live, self._translation)
+            self._goal_areas_host(live, self._translation, self.tick_no)
         self.tick_no += 1
 
     def finished(self):
@@ -662,6 +767,7 @@ class Simulation:
             for sp in self.spawners:
                 sp.tick(self.dt_ns)
         self._tracks_room(m, sum(1 for r in self.robots if r["alive"]))
+        self._goal_clock()
         host_tr = self._host_needs_transforms()
         out = self.w.mission_run(m, self.comms_radius, self.next_number, self.steps, float(self.max_speed), float(self.dt32),
                                  despawn_finished=self.despawn, method=self.method, failure_rate=self.failure_rate,
@@ -686,6 +792,7 @@ class Simulation:
                 if not self._dev_coll:
                     self._collide(live, tr)
                 self._collide_environment(live, tr)
+                self._goal_areas_host(live, tr, self.tick_no)
             self.tick_no += 1
 
     def run(self, max_ticks=None, max_time=None, chunk=256):
@@ -743,8 +850,8 @@ class Simulation:
                                                for (a, k), h in sorted(env_coll.items()) if h["aabbs"]]},
                 # goal_areas: the reference registers GoalAreaPlugin but its only system that SPAWNS goal areas
                 # (setup_goal_areas_for_junction_scenario, goal_area.rs:105-119) is commented out of the plugin (:8-11):
-                # the exported map is empty in the reference itself
-                "goal_areas": {}}
+                # the exported map is empty in the reference itself — and here unless the caller hands areas in (goal_areas=)
+                "goal_areas": self._goal_areas_export()}
 
     # -- the run metrics (the reference's scripts/ldj.py and scripts/perpendicular-path-deviation.py over an export) -----------
     def metrics(self):
@@ -773,7 +880,28 @@ class Simulation:
         env_coll = self.environment_collisions if self._env_coll else {}
         return {"robots": robots, "summary": {f: _metrics.summary([m[f] for m in robots.values()]) for f in figures},
                 "makespan": self.elapsed(),
-                "collisions": {"robots": sum(h["times"] for h in self.collisions.values()), "environment": sum(h["times"] for h in env_coll.values())}}
+                "collisions": {"robots": sum(h["times"] for h in self.collisions.values()), "environment": sum(h["times"] for h in env_coll.values())},
+                **self._goal_metrics()}
+
+    def _goal_metrics(self, window=50.0):
+        """{"goal_areas": {"arrivals": per area, "reached": robots in any history, "time_to_goal": {robot: first arrival minus
+        started_at}, "flow": goal_flow over `window` seconds, "window"}} — the key exists only when areas are configured"""
+        if self._goal_areas is None:
+            return {}
+        arrivals = self.goal_arrivals
+        first = {}
+        for h in arrivals:
+            for rid, k in h.items():
+                first[rid] = min(first.get(rid, k), k)
+        started = {r["id"]: r["started_at"] for r in self.robots}
+        n = sum(1 for rid in first if not started[rid] >= window)
+        return {"goal_areas": {"arrivals": [len(h) for h in arrivals], "reached": len(first),
+                               "time_to_goal": {str(rid): hostlib.goal_seconds(k, self.dt_ns) - started[rid] for rid, k in sorted(first.items())},
+                               "flow": 1 / (window / n) if n else 0.0, "window": window}}
+
+    def goal_flow(self, window=50.0):
+        """metrics()["goal_areas"]["flow"] for another window (scripts/analyse-junction-scenario.py:81-109)"""
+        return self._goal_metrics(window)["goal_areas"]["flow"]
 
     def export_json(self, path):
         with open(path, "w", encoding="utf-8") as f:

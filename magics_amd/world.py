@@ -505,6 +505,46 @@ class World:
     def env_collisions_clear(self):
         self._chk(self._L.mgx_env_collisions_clear(self._w))
 
+    # -- goal areas on the device (include/mgx.h, mgx_goal_areas_*): the first arrival of every robot in every area
+    def goal_areas_enable(self, areas, next_tick=0):
+        """areas: boxes ((x0, z0), (x1, z1)) in world (x, z), corners in either order, at most hostlib.GOAL_AREAS_MAX — while on,
+        every mission tick ends with one pass of goal_area::detect_collisions on the device (no synchronisation); None or
+        empty: off, the state is dropped"""
+        boxes = np.zeros(0 if areas is None else len(areas), hostlib.goal_area_dtype())
+        for i in range(len(boxes)):
+            boxes[i]["mins"], boxes[i]["maxs"] = areas[i][0], areas[i][1]
+        self._chk(self._L.mgx_goal_areas_enable(self._w, boxes.ctypes.data if len(boxes) else None, len(boxes), int(next_tick)))
+        self._goal_areas_n = len(boxes)
+
+    _goal_areas_n = 0
+
+    def goal_areas_set_clock(self, next_tick):
+        """the simulated tick index of the coming mission tick"""
+        self._chk(self._L.mgx_goal_areas_set_clock(self._w, int(next_tick)))
+
+    def goal_areas_update(self, tick, positions=None):
+        """one pass at `tick` over the caller's Transforms [n, 3] f32 (None: the device's mission Transforms); does not move the
+        clock; enqueued, not waited for"""
+        pos = None if positions is None else np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        if pos is not None and len(pos) != self.num_robots()[0]:
+            raise ValueError("one position per robot of the world")
+        self._chk(self._L.mgx_goal_areas_update(self._w, None if pos is None else pos.ctypes.data, int(tick)))
+
+    def goal_areas_read(self):
+        """(arrivals in (tick, robot, area) order — a structured array with fields tick, area, robot —, arrivals per area).
+        Synchronises."""
+        tot = C.c_uint64()
+        per = np.zeros(self._goal_areas_n, np.uint32)
+        self._chk(self._L.mgx_goal_areas_read(self._w, None, 0, C.byref(tot), per.ctypes.data if len(per) else None))
+        out = np.zeros(tot.value, hostlib.goal_arrival_dtype())
+        if tot.value:
+            self._chk(self._L.mgx_goal_areas_read(self._w, out.ctypes.data, len(out), C.byref(tot), per.ctypes.data))
+        return out[:tot.value], per
+
+    def goal_areas_clear(self):
+        """every (area, robot) back to "never"; the areas and the clock stay"""
+        self._chk(self._L.mgx_goal_areas_clear(self._w))
+
     # -- trackers on the device (include/mgx.h, mgx_tracks_*): position / velocity samples and distance travelled
     def tracks_enable(self, enabled=True, period_ns=100_000_000, tick_ns=0, next_tick=0, sample_capacity=0):
         """while on, every mission tick ends with one tracker pass on the device (no synchronisation): a sample of every moving

@@ -182,6 +182,38 @@ impl World {
         assert!(robots.len() == vars.len() && vars.len() == means.len());
         check(unsafe { sys::mgx_change_priors(self.raw, robots.len() as u32, robots.as_ptr(), vars.as_ptr(), means.as_ptr().cast()) })
     }
+    /// Goal areas on the device (include/mgx.h): what `goal_area::detect_collisions` does (goal_area.rs:67-103).  While on, every
+    /// mission tick ends with one pass that records the first arrival of every robot in every area; no areas: off.
+    pub fn goal_areas_enable(&self, areas: &[sys::mgx_goal_area], next_tick: u64) -> Result<(), MgxError> {
+        let p = if areas.is_empty() { std::ptr::null() } else { areas.as_ptr() };
+        check(unsafe { sys::mgx_goal_areas_enable(self.raw, p, areas.len() as u32, next_tick) })
+    }
+    /// The tick index of the coming mission tick.
+    pub fn goal_areas_set_clock(&self, next_tick: u64) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_goal_areas_set_clock(self.raw, next_tick) })
+    }
+    /// The same pass over Transforms the caller keeps (`None`: the device's mission Transforms), at a tick the caller names.
+    pub fn goal_areas_update(&self, translations: Option<&[[f32; 3]]>, tick: u64) -> Result<(), MgxError> {
+        let p = translations.map_or(std::ptr::null(), |t| t.as_ptr().cast());
+        check(unsafe { sys::mgx_goal_areas_update(self.raw, p, tick) })
+    }
+    /// Every arrival in (tick, robot, area) order and the arrivals per area (`n_areas`: what was handed to `goal_areas_enable`).
+    /// The one call that waits for the device.
+    pub fn goal_areas_read(&self, n_areas: usize) -> Result<(Vec<sys::mgx_goal_arrival>, Vec<u32>), MgxError> {
+        let mut per_area = vec![0u32; n_areas];
+        let mut total = 0u64;
+        check(unsafe { sys::mgx_goal_areas_read(self.raw, std::ptr::null_mut(), 0, &mut total, per_area.as_mut_ptr()) })?;
+        let mut out: Vec<sys::mgx_goal_arrival> = Vec::with_capacity(total as usize);
+        if total > 0 {
+            check(unsafe { sys::mgx_goal_areas_read(self.raw, out.as_mut_ptr(), total, &mut total, per_area.as_mut_ptr()) })?;
+            unsafe { out.set_len(total as usize) };
+        }
+        Ok((out, per_area))
+    }
+    /// Every (area, robot) back to "never"; the areas and the clock stay.
+    pub fn goal_areas_clear(&self) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_goal_areas_clear(self.raw) })
+    }
     /// Plans that ride the stream (include/mgx.h): what `progress_missions` does with its path-finding task (robot.rs:578-799).
     /// Queues the requests and returns their tickets at once; nothing is launched.
     pub fn plan_submit(&self, requests: &[sys::mgx_plan_request]) -> Result<Vec<u64>, MgxError> {

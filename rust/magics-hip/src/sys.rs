@@ -159,6 +159,23 @@ pub struct mgx_env_collision_event {
     pub maxs: [f32; 2],
 }
 
+/// one goal area (include/mgx.h, mgx_goal_areas_enable): a box in world (x, z), corners in either order per axis
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_goal_area {
+    pub mins: [f32; 2],
+    pub maxs: [f32; 2],
+}
+
+/// the first arrival of a robot in a goal area (include/mgx.h, mgx_goal_areas_read)
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct mgx_goal_arrival {
+    pub tick: u64,
+    pub area: i32,
+    pub robot: i32,
+}
+
 /// one tracker sample (include/mgx.h, mgx_tracks_*): position and, from the robot's second sample on, velocity
 #[repr(C)]
 #[derive(Clone, Copy)]
@@ -371,6 +388,11 @@ extern "C" {
     pub fn mgx_env_collisions_update(w: *mut mgx_world, positions_xyz: *const f32) -> c_int;
     pub fn mgx_env_collisions_read(w: *mut mgx_world, first: u64, events: *mut mgx_env_collision_event, capacity: u64, n_total: *mut u64, dropped: *mut u64, per_robot: *mut u32) -> c_int;
     pub fn mgx_env_collisions_clear(w: *mut mgx_world) -> c_int;
+    pub fn mgx_goal_areas_enable(w: *mut mgx_world, areas: *const mgx_goal_area, n_areas: u32, next_tick: u64) -> c_int;
+    pub fn mgx_goal_areas_set_clock(w: *mut mgx_world, next_tick: u64) -> c_int;
+    pub fn mgx_goal_areas_update(w: *mut mgx_world, positions_xyz: *const f32, tick: u64) -> c_int;
+    pub fn mgx_goal_areas_read(w: *mut mgx_world, arrivals: *mut mgx_goal_arrival, capacity: u64, n_total: *mut u64, per_area: *mut u32) -> c_int;
+    pub fn mgx_goal_areas_clear(w: *mut mgx_world) -> c_int;
     pub fn mgx_tracks_enable(w: *mut mgx_world, enabled: i32, period_ns: u64, tick_ns: u64, next_tick: u64, sample_capacity: u64) -> c_int;
     pub fn mgx_tracks_set_clock(w: *mut mgx_world, next_tick: u64) -> c_int;
     pub fn mgx_tracks_update(w: *mut mgx_world, positions_xyz: *const f32, moved: *const u8, tick: u64) -> c_int;

@@ -5,6 +5,7 @@
     python tools/collisions_bench.py --mode host     # Transforms read per tick + sim.Simulation._collide per tick (the host pass)
     python tools/collisions_bench.py --mode env      # the robot-environment pass on the device (mgx_env_collisions_*), Junction tile
     python tools/collisions_bench.py --mode both     # both device passes
+    python tools/collisions_bench.py --mode goal --areas 2   # the goal-area pass on the device (mgx_goal_areas_*; profiles/goal_areas.md)
 
 A grid world with inter-robot factors on, driven through mgx_mission_tick_begin / _end like sim.Simulation does; `--reps`
 timings of `--ticks` ticks each, one JSON line with the median ticks/s."""
@@ -24,13 +25,14 @@ from magics_amd import scenarios as S  # noqa: E402
 from magics_amd.driver import DeviceDriver  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=["off", "device", "host", "env", "both"], required=True)
+ap.add_argument("--mode", choices=["off", "device", "host", "env", "both", "goal"], required=True)
 ap.add_argument("--robots", type=int, default=1000)
 ap.add_argument("--K", type=int, default=16)
 ap.add_argument("--ticks", type=int, default=200)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--warmup", type=int, default=30)
 ap.add_argument("--method", type=int, default=hostlib.NEIGHBOURS_AUTO)
+ap.add_argument("--areas", type=int, default=2, help="--mode goal: the junction's two exits, then boxes along the grid up to this many")
 a = ap.parse_args()
 
 sc = S.grid_scenario(a.robots, a.K, interrobot=True, comm_radius=8.0)
@@ -44,6 +46,9 @@ if a.mode in ("device", "both"):
     w.collisions_enable(True, method=a.method)
 if a.mode in ("env", "both"):  # the Junction scenarios' map: one crossroads tile, four corner cuboids
     w.env_collisions_enable(environment.new(["┼"], 0.16, 2.0, 100.0))
+if a.mode == "goal":  # the junction's two exits first; the others lie where the grid's robots drive
+    boxes = list(sim.JUNCTION_GOAL_AREAS) + [((4.0 * i - 60.0, -30.0), (4.0 * i - 58.0, 30.0)) for i in range(62)]
+    w.goal_areas_enable(boxes[:a.areas], next_tick=0)
 host = sim.Simulation.__new__(sim.Simulation)
 host.collisions = {}
 robots = [{"id": r, "radius": np.float32(sc["robots"][r]["radius"])} for r in range(n)]
@@ -71,6 +76,8 @@ for rep in range(a.reps + 1):
         events, total, dropped, per = w.collisions_read()
     if a.mode in ("env", "both"):
         env_total = w.env_collisions_read()[1]
+    if a.mode == "goal":
+        goal_total = len(w.goal_areas_read()[0])
     if a.mode in ("off", "host"):
         w.synchronize()
     if rep:
@@ -79,4 +86,5 @@ total = int(w.collisions_read()[1]) if a.mode in ("device", "both") else sum(h["
 print(json.dumps({"mode": a.mode, "robots": n, "K": a.K, "ticks": a.ticks, "ticks_per_s_median": round(statistics.median(rates), 1),
                   "ticks_per_s": [round(r, 1) for r in rates], "alive": int(alive.sum()), "collision_events": total,
                   **({"env_collision_events": int(env_total)} if a.mode in ("env", "both") else {}),
+                  **({"goal_areas": a.areas, "goal_arrivals": goal_total} if a.mode == "goal" else {}),
                   "last_sweep": list(w.last_sweep())}))

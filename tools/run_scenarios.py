@@ -10,7 +10,11 @@ accumulated: mean_distance stays 0): for A/B runs against the device's trackers,
 --metrics prints the run metrics after each scenario's line — per robot the LDJ, the path deviation figures, distance and mission
 duration, then the per-run summaries (Simulation.metrics(); carried on the device unless --host-trackers); with --no-sample-log no
 sample is logged on the device and the robots' positions / velocities lists stay empty.
-usage: python tools/run_scenarios.py [--max-time S] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
+--goal-areas junction|FILE.json records the first arrival of every robot in every goal area (on the device; goal_area.rs:67-103):
+"junction" is the two exits of the reference's junction scenario, FILE.json holds a list of boxes [[x0, z0], [x1, z1]]; each
+scenario's line then carries the arrivals per area and the throughput the reference's analyse-junction-scenario.py reads out of an
+export (robots that started within 50 s and arrived, per second).  --export DIR writes each scenario's export to DIR/<name>.json.
+usage: python tools/run_scenarios.py [--max-time S] [--goal-areas junction|FILE.json] [--export DIR] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
            [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N] [scenario-dir | name ...]"""
 import json
 import os
@@ -40,6 +44,19 @@ if no_sample_log:
     args.remove("--no-sample-log")
 if no_sample_log and (not metrics or host_trackers):
     sys.exit("--no-sample-log needs --metrics on the device's trackers")
+goal_areas = None
+if "--goal-areas" in args:
+    i = args.index("--goal-areas")
+    goal_areas = args[i + 1]
+    if goal_areas != "junction":
+        with open(goal_areas, encoding="utf-8") as f:
+            goal_areas = json.load(f)
+    del args[i:i + 2]
+export_dir = None
+if "--export" in args:
+    i = args.index("--export")
+    export_dir = args[i + 1]
+    del args[i:i + 2]
 global_planner, overrides = None, {}
 if "--global-planner" in args:
     i = args.index("--global-planner")
@@ -65,7 +82,8 @@ for name in names:
     t0 = time.perf_counter()
     s = sim.Simulation(sc, World(config.world_params(sc["config"])), environment_collisions=env_collisions,
                        global_planner=global_planner, planner_overrides=overrides, plan_budget=plan_budget,
-                       device_trackers=False if host_trackers else None, device_metrics=metrics and not host_trackers, sample_log=not no_sample_log)
+                       device_trackers=False if host_trackers else None, device_metrics=metrics and not host_trackers, sample_log=not no_sample_log,
+                       goal_areas=goal_areas)
     s.run(max_time=max_time)
     wall = time.perf_counter() - t0
     done = [r for r in s.robots if r["completed"]]
@@ -76,7 +94,12 @@ for name in names:
                       "last_finish_s": round(max((r["finished_at"] for r in done), default=0.0), 1),
                       "topology_events": len(s.events),
                       **({"plans": len(s._plan_log), "plans_failed": sum(q["status"] != 0 for q in s._plan_log)} if global_planner else {}),
-                      **({"environment_collisions": sum(h["times"] for h in s.environment_collisions.values())} if env_collisions else {})}), flush=True)
+                      **({"environment_collisions": sum(h["times"] for h in s.environment_collisions.values())} if env_collisions else {}),
+                      **({"goal_arrivals": s.metrics()["goal_areas"]["arrivals"], "goal_flow": s.metrics()["goal_areas"]["flow"]} if goal_areas else {})}),
+          flush=True)
+    if export_dir:
+        os.makedirs(export_dir, exist_ok=True)
+        s.export_json(os.path.join(export_dir, os.path.basename(os.path.normpath(sc.get("name", name))) + ".json"))
     if metrics:
         m = s.metrics()
         cols = ("ldj", "path_deviation", "mean_deviation", "max_deviation", "distance_travelled", "duration")
