@@ -8,7 +8,7 @@
 // disturb existing state (the reference mutates its graphs in place,
 // factorgraph.rs:190-226,304-353,380-436).
 //
-// ONE translation unit, fifteen files: the parts below share file-local helpers (commit, confirm_resident, flush_counts, sweep,
+// ONE translation unit, sixteen files: the parts below share file-local helpers (commit, confirm_resident, flush_counts, sweep,
 // run_resident, linger_close ...) that have no business in the library's symbol table, so they are included here in
 // dependency order instead of being linked:
 //   mgx_world_types.h — what the host side is made of: launcher prototypes of the kernel files, error text, device buffers, the pinned argument ring, the neighbour search's and the resident launches' state, the host mirror's records (Robot, IrConn), connection sets and index, the world itself, the entry hooks of the C ABI (MGX_ENTER)
@@ -19,6 +19,7 @@
 //   mgx_world_launch.inc — launches: confirm_resident, sweep, resident schedule launches, lingering launches (the host's side)
 //   mgx_world_abi.inc — C ABI: lifecycle, environment, robots, connections, factor kinds, flags
 //   mgx_world_topology.inc — C ABI: dynamic inter-robot topology — neighbour search, delete / create_interrobot_factors
+//   mgx_world_observers.inc — what the observers (the three parts below) share: the robots' radii, staged positions and flags, "sharded", the growth of arrays that follow the robots, the checks of an _update call, the observers' end of a tick
 //   mgx_world_collisions.inc — C ABI: robot-robot and robot-environment collision bookkeeping on the device, one contact book under both (the passes mgx_mission_tick_end enqueues)
 //   mgx_world_tracks.inc — C ABI: the trackers on the device — position / velocity samples and distance travelled (the pass mgx_mission_tick_end enqueues beside the collision passes)
 //   mgx_world_goal_areas.inc — C ABI: goal areas on the device — the first arrival of every robot in every area (the pass mgx_mission_tick_end enqueues beside the collision passes)
@@ -33,6 +34,7 @@
 #include "mgx_world_launch.inc"
 #include "mgx_world_abi.inc"
 #include "mgx_world_topology.inc"
+#include "mgx_world_observers.inc"
 #include "mgx_world_collisions.inc"
 #include "mgx_world_tracks.inc"
 #include "mgx_world_goal_areas.inc"

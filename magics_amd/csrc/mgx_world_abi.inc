@@ -183,6 +183,7 @@ int mgx_robot_add(mgx_world *w, const mgx_robot_desc *d, int32_t *robot_id) {
     if (d->n_path && d->path_xy) rb.path.assign(d->path_xy, d->path_xy + 2 * (size_t)d->n_path);
     w->sets.keys.push_back(rb.order_key);
     w->sets.ghost.push_back(rb.ghost ? 1 : 0);
+    w->obs.n_ghosts += rb.ghost ? 1 : 0;
     w->sets.radius.push_back(rb.radius);
     w->sets.removed.push_back(0);
     w->robots.push_back(std::move(rb));

@@ -1,11 +1,11 @@
 // mgx_world_collisions.inc — C ABI: robot-robot and robot-environment collision bookkeeping on the device (the passes
 // mgx_mission_tick_end enqueues).
 // Part of ONE translation unit: included by mgx_world.hip (which says in which order, and why one unit).
-// What a pass computes and how its state is kept: mgx_collisions.hip.  The host's side here: the arrays follow the world's robots
-// (ids never change, so commit / mgx_robot_remove move nothing: robots that join make the per-robot arrays and the stride of the
-// pair bits grow, and the bits are set again from the pair list), a pass is enqueued on the world's stream without a
-// synchronisation or a read-back, and mgx_collisions_read / mgx_env_collisions_read are the calls that wait.
-// What the two bookkeepings share (ContactBook, mgx_world_types.h) is written once, as contacts_*; the entry points hand in what differs.
+// What a pass computes and how its state is kept: mgx_collisions.hip.  The host's side here: the books' own per-robot arrays follow
+// the world's robots under the rule of mgx_world_observers.inc (a longer stride of the pair bits: the bits are set again from the
+// pair list), a pass is enqueued on the world's stream without a synchronisation or a read-back, and mgx_collisions_read /
+// mgx_env_collisions_read are the calls that wait.  What the two bookkeepings share (ContactBook, mgx_world_types.h) is written
+// once, as contacts_*; the entry points hand in what differs.
 
 static constexpr uint64_t COLL_DEFAULT_EVENTS = 1ull << 18;  // 8 MB of 32-byte records
 static constexpr uint32_t COLL_LIST_CAP = 1u << 16;          // pairs overlapping at the same time
@@ -13,14 +13,9 @@ static constexpr uint32_t COLL_MAX_STRIDE = 46336u;          // stride^2 bits st
 static constexpr double ENV_COLL_PAD = 1e-4;                 // of a tile, added to a robot's reach when its cells are chosen
 static const char *const COLL_OFF = "collision bookkeeping is off (mgx_collisions_enable)";
 static const char *const ENV_COLL_OFF = "environment collision bookkeeping is off (mgx_env_collisions_enable)";
+static const char *const COLL_UNSHARDED = "collision bookkeeping runs on unsharded worlds";
 using ContactBook = mgx_world::ContactBook;
 using ContactPass = int (*)(mgx_world *w, const float *pos_d, const uint8_t *alive_d, hipStream_t s);
-
-static bool collisions_sharded(const mgx_world *w) {
-    for (const Robot &q : w->robots)
-        if (q.ghost) return true;
-    return false;
-}
 
 // ---- what both bookkeepings do ------------------------------------------------------------------------------------------------
 // switched on: room for the log (event_capacity 0: the default) and its two words; `d` is the pass's argument, fresh
@@ -37,7 +32,7 @@ static int contacts_open(ContactBook &b, ContactDev &d, uint64_t event_capacity)
 
 static void contacts_drop(ContactBook &b) {  // switched off: the state goes with it
     b.enabled = false;
-    b.log.release(); b.words.release(); b.per_robot.release(); b.radius.release(); b.pos.release(); b.alive.release();
+    b.log.release(); b.words.release(); b.per_robot.release();
     b.n_sized = 0; b.pass = 0; b.log_cap = 0;
     b.host_log.clear();
 }
@@ -50,67 +45,24 @@ static int contacts_reset(ContactBook &b, hipStream_t s) {  // nothing logged, n
     return MGX_OK;
 }
 
-// room for `want`, the first `keep` as they were, every byte behind them `byte`.  Enqueued: the array grown out of goes to `old`,
-// which the caller frees once the stream has been synchronised (passes enqueued earlier may still read it)
-template <class T>
-static hipError_t grow_keep(DevBuf<T> &buf, size_t want, size_t keep, int byte, DevBuf<T> &old, hipStream_t s) {
-    hipError_t e = old.reserve(want);
-    if (e == hipSuccess) e = hipMemsetAsync(old.p, byte, sizeof(T) * old.cap, s);
-    if (e == hipSuccess && keep) e = hipMemcpyAsync(old.p, buf.p, sizeof(T) * keep, hipMemcpyDeviceToDevice, s);
-    if (e == hipSuccess) buf.swap(old);
-    return e;
-}
-
-// the robots' side of a sizing, for the robots the world has NOW: the radii go up, the counts so far move to the front of a
-// longer array.  Enqueued: `out` lives until the caller has synchronised the stream
-struct ContactsOutgrown {
-    std::vector<float> radii;  // (they go up from pageable memory)
-    DevBuf<uint32_t> counts;
-};
-static int contacts_size(mgx_world *w, ContactBook &b, ContactDev &d, ContactsOutgrown &out, hipStream_t s) {
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "collision bookkeeping runs on unsharded worlds");
-    const size_t R = w->robots.size();
-    out.radii.resize(R);
-    for (size_t r = 0; r < R; r++) out.radii[r] = (float)w->robots[r].radius;
-    HIP_TRY(b.radius.upload(out.radii, s));
-    if (b.per_robot.cap < R) HIP_TRY(grow_keep(b.per_robot, R, b.n_sized, 0, out.counts, s));
-    d.radius = b.radius.p;
+// the robots' side of a sizing, for the robots the world has NOW: the shared radii complete, the counts so far in a longer array
+static int contacts_size(mgx_world *w, ContactBook &b, ContactDev &d, Outgrown &out) {
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "%s", COLL_UNSHARDED);
+    const int rc = observers_radii(w, out);
+    if (rc != MGX_OK) return rc;
+    if (w->robots.size() > b.per_robot.cap) HIP_TRY(out.grow(b.per_robot, observers_room(w, w->robots.size()), b.n_sized, 0));
+    d.radius = w->obs.radius.p;
     d.per_robot = b.per_robot.p;
     return MGX_OK;
 }
 
-// who is alive, and the caller's positions (NULL: none): up from a pinned slot, behind whatever the stream is busy with
-static int collisions_stage(mgx_world *w, const float *positions_xyz, DevBuf<float> &pos, DevBuf<uint8_t> &alive, hipStream_t s) {
-    const size_t R = w->robots.size(), pos_bytes = positions_xyz ? sizeof(float) * 3 * R : 0;
-    void *hp = nullptr;
-    int slot = 0;
-    HIP_TRY(alive.reserve(R));
-    if (positions_xyz) HIP_TRY(pos.reserve(3 * R));
-    HIP_TRY(w->stage.acquire(pos_bytes + R, &hp, &slot));
-    char *h = static_cast<char *>(hp);
-    if (positions_xyz) memcpy(h, positions_xyz, pos_bytes);
-    for (size_t r = 0; r < R; r++) h[pos_bytes + r] = (!w->robots[r].removed && !w->robots[r].ghost) ? 1 : 0;
-    if (positions_xyz) HIP_TRY(hipMemcpyAsync(pos.p, h, pos_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(alive.p, h + pos_bytes, R, hipMemcpyHostToDevice, s));
-    HIP_TRY(w->stage.release(slot, s));
-    return MGX_OK;
-}
-
-// mgx_*collisions_update: one pass over the caller's positions, or over the device's mission Transforms
+// mgx_*collisions_update: one pass over the caller's positions, or over the device's mission Transforms (no robots: it counts too)
 static int contacts_update(mgx_world *w, ContactBook *b, const float *positions_xyz, const char *off, ContactPass pass) {
-    MGX_ENTER(w);
-    if (!w) return fail(MGX_ERR_INVALID, "null world");
-    if (!b->enabled) return fail(MGX_ERR_STATE, "%s", off);
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "collision bookkeeping runs on unsharded worlds");
-    const size_t R = w->robots.size();
-    if (R == 0) { b->pass += 1; return MGX_OK; }
-    const mgx_world::Mission &ms = w->mission;
-    if (!positions_xyz && (!ms.uploaded || ms.dirty || ms.has.size() != R))
-        return fail(MGX_ERR_STATE, "the device holds no Transforms of these robots (mgx_mission_tick)");
-    hipStream_t s = w->stream;
-    const int rc = collisions_stage(w, positions_xyz, b->pos, b->alive, s);
+    ObserverInputs in;
+    const int rc = observers_update_begin(w, b && b->enabled, off, COLL_UNSHARDED, nullptr, positions_xyz, nullptr, in);
     if (rc != MGX_OK) return rc;
-    return pass(w, positions_xyz ? b->pos.p : ms.translation_d.p, b->alive.p, s);
+    if (!in.flags) { b->pass += 1; return MGX_OK; }
+    return pass(w, in.pos, in.flags, w->stream);
 }
 
 // what a read call hands out.  The log only grows and every pass enqueued so far is complete: what was fetched before keeps its
@@ -171,17 +123,16 @@ static int contacts_clear(mgx_world *w, ContactBook *b, const char *off, int (*r
 }
 
 // ---- robot-robot: pair bits, pair lists, the hash grid's links ----------------------------------------------------------------
-// the per-robot arrays for the robots the world has NOW (radii, contact counts, grid links, pair bits)
+// the per-robot arrays for the robots the world has NOW (contact counts, grid links, pair bits)
 static int collisions_size(mgx_world *w) {
     mgx_world::Collisions &c = w->coll;
     const size_t R = w->robots.size();
-    if (R == c.n_sized) return MGX_OK;
+    if (R <= c.n_sized) return MGX_OK;
     hipStream_t s = w->stream;
-    ContactsOutgrown out;
-    DevBuf<uint32_t> old_bits;  // (of the old stride: passes enqueued earlier may still read them)
-    const int rc = contacts_size(w, c, c.d, out, s);
+    Outgrown out{s};
+    const int rc = contacts_size(w, c, c.d, out);
     if (rc != MGX_OK) return rc;
-    HIP_TRY(c.next.reserve(R));
+    if (R > c.next.cap) HIP_TRY(out.grow(c.next, observers_room(w, R), 0, 0));
     uint32_t M = 64;
     while (M < 2u * (uint32_t)R) M <<= 1;
     if (c.head.cap < M) {
@@ -190,16 +141,16 @@ static int collisions_size(mgx_world *w) {
     }
     c.n_buckets = M;
     if (R > c.stride) {  // a new stride: every bit clear, then the bits of the listed pairs again
-        const uint64_t stride = ((uint64_t)R + R / 4 + 64 + 31) & ~31ull;
+        const uint64_t stride = robots_room(R);
         if (stride > COLL_MAX_STRIDE) return fail(MGX_ERR_NOMEM, "collision bookkeeping: %zu robots are more than the pair bits hold", R);
-        HIP_TRY(grow_keep(c.bits, (size_t)(stride * stride / 32), 0, 0, old_bits, s));
+        HIP_TRY(out.grow(c.bits, (size_t)(stride * stride / 32), 0, 0));
         c.stride = (uint32_t)stride;
         c.d.bits = c.bits.p;
         c.d.stride = c.stride;
         c.d.pass = c.pass;
         HIP_TRY(launch_collisions_rebits(c.d, s));
     }
-    HIP_TRY(hipStreamSynchronize(s));  // (the radii went up from pageable memory; what was grown out of is free to go)
+    HIP_TRY(out.retire());
     c.d.head = c.head.p;
     c.d.next = c.next.p;
     c.n_sized = R;
@@ -217,7 +168,7 @@ static int collisions_pass(mgx_world *w, const float *pos_d, const uint8_t *aliv
     bool radii_ok = true;
     for (size_t r = 0; r < R; r++) {
         const Robot &rb = w->robots[r];
-        if (rb.removed || rb.ghost) continue;
+        if (!observed(rb)) continue;
         const float rr = (float)rb.radius;
         n_alive++;
         if (!std::isfinite(rr)) radii_ok = false;
@@ -253,19 +204,17 @@ static void env_collisions_drop(mgx_world *w) {
     c.d = EnvCollDev{};
 }
 
-// the per-robot arrays for the robots the world has NOW: radii; counts and touched colliders of the robots so far keep their place
+// the per-robot arrays for the robots the world has NOW: counts and touched colliders of the robots so far keep their place
 static int env_collisions_size(mgx_world *w) {
     mgx_world::EnvCollisions &c = w->envcoll;
     const size_t R = w->robots.size();
-    if (R == c.n_sized) return MGX_OK;
-    hipStream_t s = w->stream;
-    ContactsOutgrown out;
-    DevBuf<int32_t> old_slots;
-    const int rc = contacts_size(w, c, c.d, out, s);
+    if (R <= c.n_sized) return MGX_OK;
+    Outgrown out{w->stream};
+    const int rc = contacts_size(w, c, c.d, out);
     if (rc != MGX_OK) return rc;
     if (c.touching.cap < c.per_robot.cap * ENV_COLL_SLOTS)  // slots for every robot the counts have room for; -1: a new robot touches nothing
-        HIP_TRY(grow_keep(c.touching, c.per_robot.cap * ENV_COLL_SLOTS, c.n_sized * ENV_COLL_SLOTS, 0xff, old_slots, s));
-    HIP_TRY(hipStreamSynchronize(s));  // (the radii went up from pageable memory; what was grown out of is free to go)
+        HIP_TRY(out.grow(c.touching, c.per_robot.cap * ENV_COLL_SLOTS, c.n_sized * ENV_COLL_SLOTS, 0xff));
+    HIP_TRY(out.retire());
     c.d.touching = c.touching.p;
     c.n_sized = R;
     return MGX_OK;
@@ -344,7 +293,7 @@ static int env_collisions_open(mgx_world *w, const mgx_env_desc *env, uint64_t e
     mgx_world::EnvCollisions &c = w->envcoll;
     int rc = env_map_upload(w, env, c.map);
     if (rc != MGX_OK) return rc;
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "collision bookkeeping runs on unsharded worlds");
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "%s", COLL_UNSHARDED);
     c.d = EnvCollDev{};
     if ((rc = contacts_open(c, c.d, event_capacity)) != MGX_OK) return rc;
     const EnvMapDev &m = c.map.d;
@@ -370,7 +319,7 @@ int mgx_collisions_enable(mgx_world *w, int32_t enabled, uint32_t method, uint64
         return MGX_OK;
     }
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no usable HIP device");
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "collision bookkeeping runs on unsharded worlds");
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "%s", COLL_UNSHARDED);
     if (c.enabled) {  // the capacities were chosen when it was switched on
         if (event_capacity && event_capacity != c.log_cap) return fail(MGX_ERR_STATE, "collision bookkeeping is on with room for %llu events", (unsigned long long)c.log_cap);
         c.method = method;

@@ -2,50 +2,38 @@
 // mgx_mission_tick_end enqueues beside the collision passes).
 // Part of ONE translation unit: included by mgx_world.hip (which says in which order, and why one unit).
 // What a pass computes: mgx_goal_areas.hip; the specification: include/mgx.h.  The host's side here: the table follows the
-// world's robots (ids never change, so commit / mgx_robot_remove and a relayout move nothing: its rows are strided for the
-// world's head-room, and only robots beyond that make it grow, the arrivals so far copied row by row), a pass is enqueued on
-// the world's stream without a synchronisation or a read-back, and mgx_goal_areas_read is the call that waits.
+// world's robots under the rule of mgx_world_observers.inc (its rows are strided for the head-room of that rule, and only robots
+// beyond it make it grow, the arrivals so far copied row by row), a pass is enqueued on the world's stream without a
+// synchronisation or a read-back, and mgx_goal_areas_read is the call that waits.
 
 static const char *const GOALS_OFF = "the goal areas are off (mgx_goal_areas_enable)";
+static const char *const GOALS_UNSHARDED = "the goal areas run on unsharded worlds";
 static constexpr uint64_t GOALS_MAX_TICK = 0xfffffffeull;  // tick + 1 travels in 32 bits, 0 is "never"
 static constexpr size_t GOALS_MAX_STRIDE = (size_t)1 << 24;
 
 static void goal_areas_drop(mgx_world *w) {  // switched off: the state goes with it
     mgx_world::GoalAreas &g = w->goals;
     g.enabled = false;
-    g.recs.release(); g.first.release(); g.radius.release(); g.pos.release(); g.alive.release();
+    g.recs.release(); g.first.release();
     g.n_areas = 0; g.stride = 0; g.n_sized = 0; g.clock = 0;
 }
 
-// the table and the radii for the robots the world has NOW: the robots so far keep their arrivals, the others start at "never".
-// While the robots fit the rows nothing moves; the radii go up from a pinned slot, behind the passes enqueued so far
+// the table for the robots the world has NOW, the shared radii complete: the robots so far keep their arrivals, the others start
+// at "never".  While the robots fit the rows nothing moves
 static int goal_areas_size(mgx_world *w) {
     mgx_world::GoalAreas &g = w->goals;
-    const size_t R = w->robots.size();
-    if (R == g.n_sized) return MGX_OK;
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the goal areas run on unsharded worlds");
-    hipStream_t s = w->stream;
-    if (R > g.stride) {  // longer rows: every cell "never", then the arrivals so far
-        size_t stride = std::max({R + R / 4 + 64, (size_t)w->reserve_want, (size_t)std::max(w->R_cap, 0)});
-        stride = (stride + 63) & ~(size_t)63;
-        if (stride > GOALS_MAX_STRIDE) return fail(MGX_ERR_NOMEM, "goal areas: %zu robots are more than the table holds", R);
-        DevBuf<uint32_t> old;
-        HIP_TRY(old.reserve((size_t)g.n_areas * stride));
-        HIP_TRY(hipMemsetAsync(old.p, 0, sizeof(uint32_t) * old.cap, s));
-        for (uint32_t a = 0; a < g.n_areas && g.n_sized; a++)
-            HIP_TRY(hipMemcpyAsync(old.p + (size_t)a * stride, g.first.p + (size_t)a * g.stride, sizeof(uint32_t) * g.n_sized, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipStreamSynchronize(s));  // (passes enqueued earlier may still use what is grown out of, the radii included)
-        g.first.swap(old);
+    const size_t R = w->robots.size(), stride = observers_room(w, R);
+    if (R <= g.n_sized) return MGX_OK;
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "%s", GOALS_UNSHARDED);
+    if (R > g.stride && stride > GOALS_MAX_STRIDE) return fail(MGX_ERR_NOMEM, "goal areas: %zu robots are more than the table holds", R);
+    Outgrown out{w->stream};
+    const int rc = observers_radii(w, out);
+    if (rc != MGX_OK) return rc;
+    if (R > g.stride) {  // longer rows: every cell "never", then the arrivals so far, row by row
+        HIP_TRY(out.grow(g.first, stride, g.n_sized, 0, g.n_areas, g.stride));
         g.stride = (uint32_t)stride;
-        HIP_TRY(g.radius.reserve(stride));
     }
-    void *hp = nullptr;
-    int slot = 0;
-    HIP_TRY(w->stage.acquire(sizeof(float) * R, &hp, &slot));
-    float *h = static_cast<float *>(hp);
-    for (size_t r = 0; r < R; r++) h[r] = (float)w->robots[r].radius;
-    HIP_TRY(hipMemcpyAsync(g.radius.p, h, sizeof(float) * R, hipMemcpyHostToDevice, s));
-    HIP_TRY(w->stage.release(slot, s));
+    HIP_TRY(out.retire());
     g.n_sized = R;
     return MGX_OK;
 }
@@ -58,10 +46,10 @@ static int goal_areas_pass(mgx_world *w, const float *pos_d, const uint8_t *aliv
     if (rc != MGX_OK) return rc;
     const size_t R = w->robots.size();
     bool any_alive = false;
-    for (size_t r = 0; r < R && !any_alive; r++) any_alive = !w->robots[r].removed && !w->robots[r].ghost;
-    if (!any_alive || R > g.stride) return MGX_OK;
-    GoalAreasDev d{};
-    d.pos = pos_d; d.alive = alive_d; d.radius = g.radius.p; d.areas = g.recs.p; d.first = g.first.p;
+    for (size_t r = 0; r < R && !any_alive; r++) any_alive = observed(w->robots[r]);
+    if (!any_alive) return MGX_OK;
+    GoalAreasDev d{};  // (goal_areas_size has succeeded: the rows and the radii hold R robots)
+    d.pos = pos_d; d.alive = alive_d; d.radius = w->obs.radius.p; d.areas = g.recs.p; d.first = g.first.p;
     d.stride = g.stride; d.stamp = (uint32_t)(tick + 1);
     d.n = (int)R; d.n_areas = (int)g.n_areas;
     HIP_TRY(launch_goal_areas_pass(d, s));
@@ -98,7 +86,7 @@ int mgx_goal_areas_enable(mgx_world *w, const mgx_goal_area *areas, uint32_t n_a
     }
     if (g.enabled) return fail(MGX_ERR_STATE, "the goal areas are on (switch them off before handing in other areas)");
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no usable HIP device");
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the goal areas run on unsharded worlds");
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "%s", GOALS_UNSHARDED);
     hipStream_t s = w->stream;
     goal_areas_drop(w);
     g.n_areas = n_areas;
@@ -122,21 +110,11 @@ int mgx_goal_areas_set_clock(mgx_world *w, uint64_t next_tick) {
 }
 
 int mgx_goal_areas_update(mgx_world *w, const float *positions_xyz, uint64_t tick) {
-    MGX_ENTER(w);
-    if (!w) return fail(MGX_ERR_INVALID, "null world");
-    mgx_world::GoalAreas &g = w->goals;
-    if (!g.enabled) return fail(MGX_ERR_STATE, "%s", GOALS_OFF);
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the goal areas run on unsharded worlds");
-    if (tick > GOALS_MAX_TICK) return fail(MGX_ERR_INVALID, "tick beyond 2^32 - 2");
-    const size_t R = w->robots.size();
-    if (R == 0) return MGX_OK;
-    const mgx_world::Mission &ms = w->mission;
-    if (!positions_xyz && (!ms.uploaded || ms.dirty || ms.has.size() != R))
-        return fail(MGX_ERR_STATE, "the device holds no Transforms of these robots (mgx_mission_tick)");
-    hipStream_t s = w->stream;
-    const int rc = collisions_stage(w, positions_xyz, g.pos, g.alive, s);
-    if (rc != MGX_OK) return rc;
-    return goal_areas_pass(w, positions_xyz ? g.pos.p : ms.translation_d.p, g.alive.p, tick, s);
+    ObserverInputs in;
+    const int rc = observers_update_begin(w, w && w->goals.enabled, GOALS_OFF, GOALS_UNSHARDED, tick > GOALS_MAX_TICK ? "tick beyond 2^32 - 2" : nullptr,
+                                          positions_xyz, nullptr, in);
+    if (rc != MGX_OK || !in.flags) return rc;
+    return goal_areas_pass(w, in.pos, in.flags, tick, w->stream);
 }
 
 int mgx_goal_areas_read(mgx_world *w, mgx_goal_arrival *arrivals, uint64_t capacity, uint64_t *n_total, uint32_t *per_area) {

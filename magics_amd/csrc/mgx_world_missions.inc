@@ -73,8 +73,7 @@ int mgx_mission_set(mgx_world *w, int32_t robot, const mgx_mission_desc *desc) {
     if (rb.ghost || rb.removed) return fail(MGX_ERR_INVALID, "robot %d is not a live local robot", robot);
     if (desc->n_waypoints == 0 || !desc->waypoints_xy) return fail(MGX_ERR_INVALID, "a mission needs at least one waypoint");
     if ((int)desc->reach_var >= rb.K || (int)desc->finish_var >= rb.K) return fail(MGX_ERR_INVALID, "rule names a variable beyond the horizon");
-    for (const Robot &q : w->robots)
-        if (q.ghost) return fail(MGX_ERR_STATE, "missions run on unsharded worlds");
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "missions run on unsharded worlds");
     mgx_world::Mission &ms = w->mission;
     if (ms.uploaded && !ms.dirty) {  // the device has advanced the missions it holds: fetch before the arrays are laid out again
         int rc = mission_download(w);
@@ -186,6 +185,31 @@ int mgx_mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, ui
     return MGX_OK;
 }
 
+// The observers' part of a tick's second half (mgx_world_observers.inc): over the Transforms after this tick's move (pos_d), the
+// robots alive after its despawns (alive_d) and the ones k_mission_prepare has just moved (what_d), enqueued on `s`
+static int observers_tick_end(mgx_world *w, const float *pos_d, const uint8_t *alive_d, const uint8_t *what_d, hipStream_t s) {
+    int rc = MGX_OK;
+    // update_robot_robot_collisions (collisions.rs:72-140) on the Transforms after this tick's move and the robots alive after its
+    // despawns: enqueued here, in front of the schedule's launches — no synchronisation, nothing read back (mgx_collisions_read)
+    if (w->coll.enabled && (rc = collisions_pass(w, pos_d, alive_d, s)) != MGX_OK) return rc;
+    // update_robot_environment_collisions (collisions.rs:368-438), beside it on the same stream (mgx_env_collisions_read)
+    if (w->envcoll.enabled && (rc = env_collisions_pass(w, pos_d, alive_d, s)) != MGX_OK) return rc;
+    // goal_area::detect_collisions (goal_area.rs:67-103), beside them on the same Transforms and alive bytes (mgx_goal_areas_read);
+    // the goal areas' own clock then names the coming tick
+    if (w->goals.enabled) {
+        if ((rc = goal_areas_pass(w, pos_d, alive_d, w->goals.clock, s)) != MGX_OK) return rc;
+        w->goals.clock += 1;
+    }
+    // track_positions / track_velocities (tracking.rs:117-136, 210-240) and the distance travelled, for the robots k_mission_prepare
+    // has just moved (its `what` flags): in front of the prior updates, which change the means the increment is formed from
+    // again — no synchronisation, nothing read back (mgx_tracks_take).  The world's clock then names the coming tick
+    if (w->tracks.enabled) {
+        if ((rc = tracks_pass(w, pos_d, what_d, w->tracks.clock, true, s)) != MGX_OK) return rc;
+        w->tracks.clock += 1;
+    }
+    return MGX_OK;
+}
+
 int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed, double delta_t, const uint8_t *steps, uint32_t n_steps) {
     MGX_ENTER(w);
     if (!w || (!steps && n_steps)) return fail(MGX_ERR_INVALID, "null argument");
@@ -220,30 +244,14 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
         int slot = 0;
         HIP_TRY(w->stage.acquire((size_t)R, &hp, &slot));
         uint8_t *mv = (uint8_t *)hp;
-        for (int r = 0; r < R; r++) mv[r] = (!w->robots[(size_t)r].removed && !w->robots[(size_t)r].ghost) ? 1 : 0;
+        for (int r = 0; r < R; r++) mv[r] = observed(w->robots[(size_t)r]) ? 1 : 0;
         HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
         HIP_TRY(launch_copy_bytes(ms.moving_d.p, (const uint8_t *)dp, (size_t)R, s));
         HIP_TRY(w->stage.release(slot, s));
     }
     HIP_TRY(launch_mission_prepare(w->d, ms.d, R, ms.moving_d.p, ms.rec_d.p, ms.robots_d.p, ms.waypoints_d.p, ms.ts_list_d.p, ms.what_d.p, s));
-    // update_robot_robot_collisions (collisions.rs:72-140) on the Transforms after this tick's move and the robots alive after its
-    // despawns: enqueued here, in front of the schedule's launches — no synchronisation, nothing read back (mgx_collisions_read)
-    if (w->coll.enabled && (rc = collisions_pass(w, ms.translation_d.p, ms.moving_d.p, s)) != MGX_OK) return rc;
-    // update_robot_environment_collisions (collisions.rs:368-438), beside it on the same stream (mgx_env_collisions_read)
-    if (w->envcoll.enabled && (rc = env_collisions_pass(w, ms.translation_d.p, ms.moving_d.p, s)) != MGX_OK) return rc;
-    // goal_area::detect_collisions (goal_area.rs:67-103), beside them on the same Transforms and alive bytes (mgx_goal_areas_read);
-    // the goal areas' own clock then names the coming tick
-    if (w->goals.enabled) {
-        if ((rc = goal_areas_pass(w, ms.translation_d.p, ms.moving_d.p, w->goals.clock, s)) != MGX_OK) return rc;
-        w->goals.clock += 1;
-    }
-    // track_positions / track_velocities (tracking.rs:117-136, 210-240) and the distance travelled, for the robots k_mission_prepare
-    // has just moved (its `what` flags): in front of the prior updates, which change the means the increment is formed from
-    // again — no synchronisation, nothing read back (mgx_tracks_take).  The world's clock then names the coming tick
-    if (w->tracks.enabled) {
-        if ((rc = tracks_pass(w, ms.translation_d.p, ms.what_d.p, w->tracks.clock, true, s)) != MGX_OK) return rc;
-        w->tracks.clock += 1;
-    }
+    // the collision passes, the goal areas and the trackers: the last of them in front of the prior updates
+    if ((rc = observers_tick_end(w, ms.translation_d.p, ms.moving_d.p, ms.what_d.p, s)) != MGX_OK) return rc;
     // the Transforms after this tick's move travel to the host behind the launch: complete at the next synchronisation
     // (the next tick's own one), read without one by mgx_mission_translations
     if (ms.tr_cap < (size_t)R) {

@@ -239,6 +239,7 @@ int mgx_robot_import(mgx_world *w, int32_t robot, const void *buf, uint64_t byte
         w->conn_hot[mine[m]].has_fresh = any_fresh ? 1 : 0;
     }
     w->sets.ghost[(size_t)robot] = 0;
+    w->obs.n_ghosts -= 1;
     w->dirty = w->relayout = true;
     w->dev_valid = false;  // the host mirror is the truth now (mgx_reset_variables does the same)
     w->conns_dirty = true;
@@ -268,6 +269,7 @@ int mgx_robot_release(mgx_world *w, int32_t robot) {
     rb.ghost = true;
     rb.path.clear();
     w->sets.ghost[(size_t)robot] = 1;
+    w->obs.n_ghosts += 1;
     w->dirty = w->relayout = true;
     w->dev_valid = false;
     w->conns_dirty = true;

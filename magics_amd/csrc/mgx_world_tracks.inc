@@ -2,12 +2,12 @@
 // robot has travelled (the pass mgx_mission_tick_end enqueues beside the two collision passes).
 // Part of ONE translation unit: included by mgx_world.hip (which says in which order, and why one unit).
 // What a pass computes: mgx_tracks.hip; the specification: include/mgx.h.  The host's side here: the per-robot state follows the
-// world's robots (ids never change, so commit / mgx_robot_remove and a relayout move nothing: robots that join make the array
-// grow, zeroed), a pass is enqueued on the world's stream without a synchronisation or a read-back, and mgx_tracks_take is the
-// call that waits.
+// world's robots under the rule of mgx_world_observers.inc (robots that join make the arrays grow, zeroed), a pass is enqueued on
+// the world's stream without a synchronisation or a read-back, and mgx_tracks_take is the call that waits.
 
 static constexpr uint64_t TRACKS_DEFAULT_SAMPLES = 1ull << 18;  // 10 MB of 40-byte records
 static const char *const TRACKS_OFF = "the trackers are off (mgx_tracks_enable)";
+static const char *const TRACKS_UNSHARDED = "the trackers run on unsharded worlds";
 
 static const char *const METRICS_OFF = "the run metrics are off (mgx_track_metrics_enable)";
 static constexpr uint32_t METRICS_DEFAULT_ROUTE_POINTS = 16, METRICS_MAX_ROUTE_POINTS = 1u << 16;
@@ -16,7 +16,7 @@ static void metrics_drop(mgx_world *w) {
     mgx_world::Tracks &t = w->tracks;
     t.metrics = false;
     t.mstate.release(); t.route_xy.release(); t.routes.release(); t.mout.release();
-    t.m_sized = t.m_room = 0; t.max_route_points = 0;
+    t.max_route_points = 0;
 }
 
 static void tracks_drop(mgx_world *w) {  // switched off: the state goes with it
@@ -24,46 +24,27 @@ static void tracks_drop(mgx_world *w) {  // switched off: the state goes with it
     metrics_drop(w);
     t.logging = true;
     t.enabled = false;
-    t.state.release(); t.log.release(); t.cursor.release(); t.pos.release(); t.moved.release();
+    t.state.release(); t.log.release(); t.cursor.release();
     t.n_sized = 0; t.log_cap = 0; t.period_ns = 0; t.tick_ns = 0; t.clock = 0; t.dropped = 0;
 }
 
-// the state array for the robots the world has NOW: the robots so far keep theirs, the others start from zero
+// the state array and, while the run metrics are on, their three arrays (`routes` grows last: where it has room, all three have) for
+// the robots the world has NOW: the robots so far keep state and route, the others start from zero and without a route
 static int tracks_size(mgx_world *w) {
     mgx_world::Tracks &t = w->tracks;
-    const size_t R = w->robots.size();
-    if (R <= t.n_sized) return MGX_OK;
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the trackers run on unsharded worlds");
-    if (t.state.cap < R) {  // (every element behind the robots so far is zero already: nothing to do while they fit)
-        hipStream_t s = w->stream;
-        DevBuf<TrackState> old;
-        HIP_TRY(grow_keep(t.state, R, t.n_sized, 0, old, s));
-        HIP_TRY(hipStreamSynchronize(s));  // (passes enqueued earlier may still have used what was grown out of)
+    const size_t R = w->robots.size(), P = t.max_route_points, room = observers_room(w, R);
+    const bool metrics = t.metrics && R > t.routes.cap;
+    if (R <= t.n_sized && !metrics) return MGX_OK;
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "%s", TRACKS_UNSHARDED);
+    Outgrown out{w->stream};
+    if (R > t.state.cap) HIP_TRY(out.grow(t.state, room, t.n_sized, 0));
+    if (metrics) {
+        HIP_TRY(out.grow(t.mstate, room, t.n_sized, 0));
+        HIP_TRY(out.grow(t.route_xy, room * P * 2, t.n_sized * P * 2, 0));
+        HIP_TRY(out.grow(t.routes, room, t.n_sized, 0));
     }
+    HIP_TRY(out.retire());
     t.n_sized = R;
-    return MGX_OK;
-}
-
-// the metrics' arrays for the robots the world has NOW, under the rule of tracks_size: the robots so far keep state and route, the
-// others start from zero and without a route.  All three arrays have room for the same number of robots
-static int metrics_size(mgx_world *w) {
-    mgx_world::Tracks &t = w->tracks;
-    const size_t R = w->robots.size(), P = t.max_route_points;
-    if (R <= t.m_sized) return MGX_OK;
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the trackers run on unsharded worlds");
-    if (t.m_room < R) {
-        hipStream_t s = w->stream;
-        const size_t room = R + R / 4 + 64;
-        DevBuf<TrackMetricsState> old_state;
-        DevBuf<double> old_xy;
-        DevBuf<TrackRoute> old_routes;
-        HIP_TRY(grow_keep(t.mstate, room, t.m_sized, 0, old_state, s));
-        HIP_TRY(grow_keep(t.route_xy, room * P * 2, t.m_sized * P * 2, 0, old_xy, s));
-        HIP_TRY(grow_keep(t.routes, room, t.m_sized, 0, old_routes, s));
-        HIP_TRY(hipStreamSynchronize(s));  // (passes enqueued earlier may still have used what was grown out of)
-        t.m_room = room;
-    }
-    t.m_sized = R;
     return MGX_OK;
 }
 
@@ -80,11 +61,7 @@ static int tracks_pass(mgx_world *w, const float *pos_d, const uint8_t *moved_d,
     if (distance) { d.blob = w->d.blob; d.time_scale = w->mission.time_scale_d.p; d.BS = w->d.BS; d.K = w->d.K; }
     d.n = (int)w->robots.size();
     d.no_log = t.logging ? 0 : 1;
-    if (t.metrics) {
-        const int mrc = metrics_size(w);
-        if (mrc != MGX_OK) return mrc;
-        d.metrics = t.mstate.p; d.route_xy = t.route_xy.p; d.routes = t.routes.p; d.max_route_points = t.max_route_points;
-    }
+    if (t.metrics) { d.metrics = t.mstate.p; d.route_xy = t.route_xy.p; d.routes = t.routes.p; d.max_route_points = t.max_route_points; }
     HIP_TRY(launch_tracks_pass(d, s));
     return MGX_OK;
 }
@@ -115,7 +92,7 @@ int mgx_tracks_enable(mgx_world *w, int32_t enabled, uint64_t period_ns, uint64_
     const uint64_t cap = sample_capacity ? sample_capacity : TRACKS_DEFAULT_SAMPLES;
     if (cap > (1ull << 31)) return fail(MGX_ERR_INVALID, "sample capacity beyond 2^31");
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no usable HIP device");
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the trackers run on unsharded worlds");
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "%s", TRACKS_UNSHARDED);
     if (t.enabled) {  // the timers and the capacity were chosen when they were switched on
         if (period_ns != t.period_ns || tick_ns != t.tick_ns || (sample_capacity && cap != t.log_cap))
             return fail(MGX_ERR_STATE, "the trackers are on with period %llu ns, tick %llu ns and room for %llu samples", (unsigned long long)t.period_ns,
@@ -141,31 +118,10 @@ int mgx_tracks_set_clock(mgx_world *w, uint64_t next_tick) {
 }
 
 int mgx_tracks_update(mgx_world *w, const float *positions_xyz, const uint8_t *moved, uint64_t tick) {
-    MGX_ENTER(w);
-    if (!w) return fail(MGX_ERR_INVALID, "null world");
-    mgx_world::Tracks &t = w->tracks;
-    if (!t.enabled) return fail(MGX_ERR_STATE, "%s", TRACKS_OFF);
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the trackers run on unsharded worlds");
-    const size_t R = w->robots.size();
-    if (R == 0) return MGX_OK;
-    const mgx_world::Mission &ms = w->mission;
-    if (!positions_xyz && (!ms.uploaded || ms.dirty || ms.has.size() != R))
-        return fail(MGX_ERR_STATE, "the device holds no Transforms of these robots (mgx_mission_tick)");
-    // the caller's positions and who moved (a robot that is gone never does): up from a pinned slot, behind whatever the stream is busy with
-    hipStream_t s = w->stream;
-    const size_t pos_bytes = positions_xyz ? sizeof(float) * 3 * R : 0;
-    void *hp = nullptr;
-    int slot = 0;
-    HIP_TRY(t.moved.reserve(R));
-    if (positions_xyz) HIP_TRY(t.pos.reserve(3 * R));
-    HIP_TRY(w->stage.acquire(pos_bytes + R, &hp, &slot));
-    char *h = static_cast<char *>(hp);
-    if (positions_xyz) memcpy(h, positions_xyz, pos_bytes);
-    for (size_t r = 0; r < R; r++) h[pos_bytes + r] = (!w->robots[r].removed && !w->robots[r].ghost && (!moved || moved[r])) ? 1 : 0;
-    if (positions_xyz) HIP_TRY(hipMemcpyAsync(t.pos.p, h, pos_bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(t.moved.p, h + pos_bytes, R, hipMemcpyHostToDevice, s));
-    HIP_TRY(w->stage.release(slot, s));
-    return tracks_pass(w, positions_xyz ? t.pos.p : ms.translation_d.p, t.moved.p, tick, false, s);
+    ObserverInputs in;  // the caller's positions and who moved (a robot that is gone never does)
+    const int rc = observers_update_begin(w, w && w->tracks.enabled, TRACKS_OFF, TRACKS_UNSHARDED, nullptr, positions_xyz, moved, in);
+    if (rc != MGX_OK || !in.flags) return rc;
+    return tracks_pass(w, in.pos, in.flags, tick, false, w->stream);
 }
 
 int mgx_tracks_take(mgx_world *w, mgx_track_sample *samples, uint64_t capacity, uint64_t *n_taken, uint64_t *n_in_log, uint64_t *dropped,
@@ -230,7 +186,7 @@ int mgx_track_metrics_enable(mgx_world *w, int32_t enabled, uint32_t max_route_p
         metrics_drop(w);
         return MGX_OK;
     }
-    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the trackers run on unsharded worlds");
+    if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "%s", TRACKS_UNSHARDED);
     const uint32_t P = max_route_points ? max_route_points : METRICS_DEFAULT_ROUTE_POINTS;
     if (P < 2 || P > METRICS_MAX_ROUTE_POINTS) return fail(MGX_ERR_INVALID, "max_route_points must be in 2 .. %u, got %u", METRICS_MAX_ROUTE_POINTS, P);
     if (t.metrics) {
@@ -239,9 +195,8 @@ int mgx_track_metrics_enable(mgx_world *w, int32_t enabled, uint32_t max_route_p
         return MGX_OK;
     }
     t.max_route_points = P;
-    t.m_sized = t.m_room = 0;
     t.metrics = true;
-    const int rc = metrics_size(w);
+    const int rc = tracks_size(w);
     if (rc != MGX_OK) metrics_drop(w);
     return rc;
 }
@@ -254,7 +209,7 @@ int mgx_track_metrics_set_route(mgx_world *w, int32_t robot, const double *xy, u
     if (!t.metrics) return fail(MGX_ERR_STATE, "%s", METRICS_OFF);
     if (robot < 0 || (size_t)robot >= w->robots.size() || (!xy && n_points)) return fail(MGX_ERR_INVALID, "bad argument");
     if (n_points > t.max_route_points) return fail(MGX_ERR_INVALID, "a route of %u points, room for %u (mgx_track_metrics_enable)", n_points, t.max_route_points);
-    const int rc = metrics_size(w);
+    const int rc = tracks_size(w);
     if (rc != MGX_OK) return rc;
     // the points and where they are: up from a pinned slot, behind the passes enqueued so far
     hipStream_t s = w->stream;
@@ -278,7 +233,7 @@ int mgx_track_metrics_read(mgx_world *w, mgx_track_metrics *out, uint64_t capaci
     mgx_world::Tracks &t = w->tracks;
     if (!t.enabled) return fail(MGX_ERR_STATE, "%s", TRACKS_OFF);
     if (!t.metrics) return fail(MGX_ERR_STATE, "%s", METRICS_OFF);
-    const size_t R = w->robots.size(), n = std::min(R, t.m_sized);
+    const size_t R = w->robots.size(), n = std::min(R, t.n_sized);
     if (capacity < R || (!out && R)) return fail(MGX_ERR_INVALID, "room for %llu records, %llu robots", (unsigned long long)capacity, (unsigned long long)R);
     MGX_CONFIRM(w);
     hipStream_t s = w->stream;

@@ -755,17 +755,29 @@ struct mgx_world {
         size_t tr_cap = 0, tr_n = 0;
         DevMission d{};
     } mission;
-    // collision bookkeeping on the device (mgx_world_collisions.inc, mgx_collisions.hip).  What its two kinds share: the log, the
-    // contact counts and the robots' inputs — keyed by robot id, so a relayout of the world's arrays moves nothing here and
-    // robots that join only make the per-robot arrays grow
+    // What the observers — the passes mgx_mission_tick_end enqueues beside the GBP schedule: the contact books, the trackers, the
+    // goal areas — read of the robots, kept ONCE (mgx_world_observers.inc) and keyed by robot id, so a relayout moves nothing.
+    // robots.size() never shrinks: every array that follows the robots, here and in the observers, is sized again when R > n_sized,
+    // with room for observers_room(R) robots when it is outgrown.  Lifetime: switching an observer off releases its own state only;
+    // these inputs live until mgx_world_destroy.  The radii never change after mgx_robot_add, so the first n_sized are complete
+    // whoever sized them: an observer switched on later uploads nothing.  `radius` moves only when robots have joined, and every
+    // observer sizes itself again then: the pointers kept in the passes' argument structs stay good.  `pos` and `flags` are written
+    // by every _update call, on the world's stream: the copy of one call is ordered behind the pass of the call before, so each
+    // pass reads its own; where they have to grow, DevBuf::reserve frees them with hipFree, which waits for the device.
+    struct RobotInputs {
+        DevBuf<float> radius;    // [robot id] (float)Robot::radius
+        size_t n_sized = 0;      // robots whose radii are up
+        DevBuf<float> pos;       // positions the caller of the last _update handed in
+        DevBuf<uint8_t> flags;   // ... and who was looked at then: not removed, not a ghost, and moved where the caller said who did
+        uint32_t n_ghosts = 0;   // ghosts among the robots (mgx_robot_add, _import, _release): collisions_sharded
+    } obs;
+    // collision bookkeeping on the device (mgx_world_collisions.inc, mgx_collisions.hip): what its two kinds share
     struct ContactBook {
         bool enabled = false;
-        size_t n_sized = 0;      // robots the per-robot arrays were last sized and the radii uploaded for
+        size_t n_sized = 0;      // robots the per-robot arrays were last sized for
         DevBuf<ContactEvent> log;
         DevBuf<unsigned long long> words;
-        DevBuf<uint32_t> per_robot;
-        DevBuf<float> radius, pos;  // pos: positions the caller handed in (mgx_collisions_update / mgx_env_collisions_update)
-        DevBuf<uint8_t> alive;      // ... and who was alive then
+        DevBuf<uint32_t> per_robot;  // contacts, by robot id
         uint64_t log_cap = 0, pass = 0;
         std::vector<ContactEvent> host_log;  // the events fetched so far, in (pass, a, b) order
     };
@@ -796,17 +808,14 @@ struct mgx_world {
         DevBuf<int32_t> touching;
         EnvCollDev d{};
     } envcoll;
-    // trackers on the device (mgx_tracks_*, mgx_world_tracks.inc, mgx_tracks.hip): per-robot state keyed by robot id — no part of the
-    // blob layout, so a relayout moves nothing here and robots that join only make the array grow, zeroed — the sample log and
-    // the world's clock
+    // trackers on the device (mgx_tracks_*, mgx_world_tracks.inc, mgx_tracks.hip): per-robot state keyed by robot id (robots that
+    // join only make the array grow, zeroed), the sample log and the world's clock
     struct Tracks {
         bool enabled = false;
-        size_t n_sized = 0;      // robots the state array has been sized for
+        size_t n_sized = 0;      // robots the state array (and the metrics' arrays, while they are on) has been sized for
         DevBuf<TrackState> state;
         DevBuf<TrackSample> log;
         DevBuf<unsigned long long> cursor;
-        DevBuf<float> pos;       // positions the caller handed in (mgx_tracks_update)
-        DevBuf<uint8_t> moved;   // ... and who moved then
         uint64_t log_cap = 0, period_ns = 0, tick_ns = 0;
         uint64_t clock = 0;      // the simulated tick index of the coming tick
         uint64_t dropped = 0;    // samples that found the log full, up to the last time it was emptied
@@ -815,25 +824,21 @@ struct mgx_world {
         // max_route_points places of the flat table, at robot * max_route_points
         bool metrics = false;
         uint32_t max_route_points = 0;
-        size_t m_sized = 0, m_room = 0;  // robots the three arrays have been sized for / have room for
         DevBuf<TrackMetricsState> mstate;
         DevBuf<double> route_xy;
         DevBuf<TrackRoute> routes;
         DevBuf<TrackMetricsOut> mout;    // what mgx_track_metrics_read finalises into
     } tracks;
     // goal areas on the device (mgx_goal_areas_*, mgx_world_goal_areas.inc, mgx_goal_areas.hip): the table of first arrivals keyed
-    // by (area, robot id) — no part of the blob layout, so a relayout moves nothing here; its rows have room for `stride` robots
-    // (the head-room of a reserved world: an append does not move it) — and a clock of its own
+    // by (area, robot id), its rows with room for `stride` robots (observers_room: an append does not move it), and a clock of its own
     struct GoalAreas {
         bool enabled = false;
         uint32_t n_areas = 0;
         uint32_t stride = 0;     // robots a row of `first` has room for
-        size_t n_sized = 0;      // robots the table was last sized and the radii uploaded for
+        size_t n_sized = 0;      // robots the table was last sized for
         uint64_t clock = 0;      // the simulated tick index of the coming tick
         DevBuf<GoalAreaRec> recs;
         DevBuf<uint32_t> first;  // [n_areas][stride] tick + 1, 0: never
-        DevBuf<float> radius, pos;  // pos: positions the caller handed in (mgx_goal_areas_update)
-        DevBuf<uint8_t> alive;      // ... and who was alive then
     } goals;
     // the global planner (mgx_planner_enable, mgx_world_planner.inc): the map and two pools of requests.  `pool`: the requests that
     // ride the stream (mgx_plan_submit / _advance / _collect), 256 blocks of 16 slots.  `call`: the requests of one mgx_plan_paths,

@@ -359,14 +359,14 @@ def test_a_radius_larger_than_a_tile_finds_contacts_in_every_cell():
 
 
 def test_robots_join_across_the_first_sizing_while_a_contact_is_held():
-    """The first sizing (for the two robots of the first pass) leaves room for R + R/4 + 64 per-robot
-    counts and as many sets of slots.  One robot more than that joins while robot 0 rests on a collider: counts and `touching`
+    """The first sizing (for the two robots of the first pass) leaves room for R + R/4 + 64 per-robot counts, rounded up to a
+    multiple of 64, and as many sets of slots.  One robot more than that joins while robot 0 rests on a collider: counts and `touching`
     slots move to the front of longer arrays — no second event for the held contact, one for the new robot, the earlier
     count kept."""
     env = _cross_grid()
     chk = Checker(env)
     first = 2
-    n = first + first // 4 + 64 + 1                    # DevBuf::reserve: the room the first sizing leaves for the counts; one more
+    n = ((first + first // 4 + 64 + 63) & ~63) + 1     # observers_room: the room the first sizing leaves for the counts; one more
     radii = np.full(n, 0.5, F)
     cuboids = np.nonzero(chk.cols["kind"] == CUBOID)[0]
     held, met = int(cuboids[0]), int(cuboids[-1])
