@@ -84,11 +84,41 @@ typedef struct mgx_robot_desc {
     const float *path_xy;     /* [n_path][2] f32 waypoints for the tracking factors or NULL  */
     double radius;            /* robot radius; d_safe = safety_multiplier * radius           */
     uint64_t order_key;       /* total order of graphs = Bevy Entity order (id.rs:19-117);
-                                 must be unique per world (across ranks when sharded)       */
+                                 must be unique per world (across ranks when sharded, and across
+                                 groups); it is only ever COMPARED between robots of one group  */
     uint32_t ghost;           /* 1 = halo copy of a robot owned by another rank: only its
                                  variable->factor snapshots exist, filled by mgx_halo_unpack */
-    uint32_t reserved;
+    uint32_t group;           /* the independent run this robot belongs to (ROBOT GROUPS below),
+                                 < MGX_GROUPS_MAX; 0 = the one run of an ungrouped world (the word
+                                 was reserved and 0)                                           */
 } mgx_robot_desc;
+
+/* ---- ROBOT GROUPS: many independent runs in one world ---------------------------------------------------------------
+ * A robot's graph couples to other robots only through inter-robot factors, so robots that are never connected are independent
+ * runs already: M runs (the seeds and parameters of an experiment, a few dozen robots each) can share one world, one launch per
+ * schedule and one synchronisation per tick, and every run stays bit-identical to the same run in a world of its own.  A world is
+ * GROUPED once any robot has been added with a non-zero `group`; a world whose robots are all in group 0 takes exactly the code
+ * paths it took before groups existed (the same search kernels, the same collision kernels, the same events).  In a grouped world:
+ *   * robots of different groups are never in comms range of one another — in mgx_neighbours, mgx_update_topology, both halves of
+ *     the mission tick, the search mgx_mission_tick_end enqueues for the coming tick, and the compacted queries over the alive
+ *     robots.  Within a group the predicate is unchanged (a NaN distance is in range; radius 0, negative, NaN as before).  The
+ *     search is ONE one-pass kernel whatever the method, MGX_SEARCH_ROWS_GROUPS: a workgroup serves sixteen robots of one group and
+ *     stages and tests that group's positions only, so a search costs the sum of the squared group sizes, not the square of the
+ *     world's size.  A group of more than 4096 robots in one query is refused (MGX_ERR_INVALID);
+ *   * robots of different groups never collide (mgx_collisions_update, and the pass at every tick's end).  Within a group the
+ *     predicate, the Free / Colliding state machine, the event order, the per-robot counts and the overflow rules are unchanged;
+ *   * the RobotNumberGenerator, whose numbers enter the arithmetic of the inter-robot factors, is per group with
+ *     mgx_update_topology_groups / mgx_mission_tick_begin_groups: a connection is numbered from the generator of its creating
+ *     robot's group.  Within a group the creation order (robot id ascending, row order) and the deletion quirk (the largest
+ *     out-of-range key per robot) are the existing ones.  The single-generator calls keep working on a grouped world: one shared
+ *     generator, grouped search.  mgx_mission_run has ONE generator and ONE stream of comms draws: per-group many-tick runs are
+ *     not part of it.
+ * Everything else is per robot and does not look at the group: sweeps, prior updates, missions, trackers, run metrics, environment
+ * collisions, goal areas, the planner, the message counters.
+ * Ghosts have no group: mgx_robot_add of a ghost with a non-zero group is MGX_ERR_INVALID; a ghost added to a grouped world, a
+ * grouped robot added to a world with ghosts, and mgx_robot_release on a grouped world are MGX_ERR_STATE.  group >= MGX_GROUPS_MAX
+ * is MGX_ERR_INVALID. */
+#define MGX_GROUPS_MAX 4096u
 
 /* ---- lifecycle ------------------------------------------------------------------- */
 int mgx_world_create(const mgx_params *params, mgx_world **out);
@@ -177,6 +207,12 @@ int mgx_neighbours(mgx_world *w, const float *positions_xyz, float radius, uint3
  * rebuilt, only when something changed. */
 int mgx_update_topology(mgx_world *w, const float *positions_xyz, float radius, uint32_t method,
                         uint64_t *robot_number_next, uint32_t *stats);
+/* The same pass with one RobotNumberGenerator per group (ROBOT GROUPS above): number_next [n_groups], in / out, none of them 0;
+ * stats (optional) [n_groups][2] = {connections created by robots of the group, pairs deleted}.  Every robot's group must be
+ * below n_groups, n_groups in 1 .. MGX_GROUPS_MAX (MGX_ERR_INVALID otherwise, nothing changes).  Works on an ungrouped world too
+ * (n_groups >= 1, everything in group 0). */
+int mgx_update_topology_groups(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint32_t n_groups,
+                               uint64_t *number_next, uint32_t *stats);
 /* RobotConnections::robots_connected_with of one robot (robot.rs:515-531), ascending.
  * others may be NULL to query the count. */
 int mgx_connections(mgx_world *w, int32_t robot, int32_t *others, uint32_t capacity, uint32_t *n);
@@ -243,6 +279,7 @@ int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *fo
 #define MGX_SEARCH_ROWS_PAIRS_2 3    /* one pass, all pairs, two lanes per robot, workgroups of 128 */
 #define MGX_SEARCH_ROWS_GRID_16 4    /* one pass, hash grid in LDS, rows of up to 16 */
 #define MGX_SEARCH_ROWS_GRID_32 5    /* one pass, hash grid in LDS, rows of up to 32 */
+#define MGX_SEARCH_ROWS_GROUPS 6     /* one pass, all pairs WITHIN each group (a grouped world, whatever the method) */
 int mgx_last_search(mgx_world *w, int32_t *kernel, int32_t *row_cap, int32_t *n_launches, int32_t *n_changed, uint8_t *changed,
                     uint32_t capacity);
 
@@ -464,6 +501,11 @@ int mgx_mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, ui
                            int32_t despawn_finished, uint32_t *stats);
 int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed, double delta_t,
                          const uint8_t *steps, uint32_t n_steps);
+/* mgx_mission_tick_begin with one RobotNumberGenerator per group (ROBOT GROUPS; arguments as mgx_update_topology_groups): stats
+ * (optional) [n_groups][3] = {connections created, pairs deleted, missions completed this tick} per group.  Paired with
+ * mgx_mission_tick_end; mgx_mission_finished lists the robots of all groups, ascending ids. */
+int mgx_mission_tick_begin_groups(mgx_world *w, float comms_radius, uint32_t method, uint32_t n_groups, uint64_t *number_next,
+                                  int32_t despawn_finished, uint32_t *stats);
 int mgx_mission_finished(mgx_world *w, int32_t *robots, uint32_t capacity, uint32_t *n);
 /* MANY ticks in one call: what a headless run does between two spawns (the reference's FixedUpdate chain tick after tick,
  * robot.rs:85-108, with update_failed_comms' draws in between) without the caller's interpreter in the loop —
@@ -475,7 +517,8 @@ int mgx_mission_finished(mgx_world *w, int32_t *robots, uint32_t capacity, uint3
  * number of missions completed and, one after the other in `finished`, the robots concerned (ascending within a tick), the
  * Transform::translation of EVERY robot after the tick's move ([n_ticks][n_robots][3], may be NULL) and the draws
  * ([n_ticks][n_robots], 1 = on air, may be NULL).  stop_when_all_finished: returns behind the tick that completed the last
- * mission.  No robot may join during the call.  Identical to the same ticks issued one by one (tests/test_gpu_sim.py). */
+ * mission.  No robot may join during the call.  Identical to the same ticks issued one by one (tests/test_gpu_sim.py).
+ * ONE generator and ONE draw stream, also on a grouped world (ROBOT GROUPS): per-group many-tick runs are not part of this call. */
 typedef struct mgx_mission_run_desc {
     uint32_t n_ticks;
     float comms_radius;

@@ -143,9 +143,10 @@ public:
     }
     // RobotBundle::new (robot.rs:1134-1356): K variables, their initial means, prior diagonal, delta_t
     FactorGraph add_robot(const std::vector<Vector4> &mean0, const std::vector<double> &prior_diag, const std::vector<double> &delta_t,
-                          double radius, uint64_t order_key, const std::vector<std::array<float, 2>> &path = {}) {
+                          double radius, uint64_t order_key, const std::vector<std::array<float, 2>> &path = {}, uint32_t group = 0) {
         if (prior_diag.size() != mean0.size() || delta_t.size() + 1 != mean0.size()) throw Error(MGX_ERR_INVALID, "inconsistent sizes");
         mgx_robot_desc d{};
+        d.group = group;  // the independent run the robot belongs to (mgx.h, ROBOT GROUPS)
         d.K = (uint32_t)mean0.size();
         d.n_path = (uint32_t)path.size();
         d.mean0 = mean0[0].data();
@@ -196,6 +197,20 @@ public:
         uint32_t stats[2] = {0, 0};
         check(mgx_update_topology(w_, translations[0].data(), comms_radius, MGX_NEIGHBOURS_AUTO, &numbers.next_value, stats));
         return {stats[0], stats[1]};
+    }
+    // the same pass on a grouped world (mgx.h, ROBOT GROUPS): one generator per group; {created, deleted} per group
+    std::vector<std::pair<uint32_t, uint32_t>> update_topology_groups(const std::vector<std::array<float, 3>> &translations, float comms_radius,
+                                                                      std::vector<RobotNumberGenerator> &numbers) {
+        std::vector<uint64_t> next(numbers.size());
+        for (size_t g = 0; g < numbers.size(); g++) next[g] = numbers[g].next_value;
+        std::vector<uint32_t> stats(2 * numbers.size() + 2, 0u);
+        check(mgx_update_topology_groups(w_, translations[0].data(), comms_radius, MGX_NEIGHBOURS_AUTO, (uint32_t)numbers.size(), next.data(), stats.data()));
+        std::vector<std::pair<uint32_t, uint32_t>> out(numbers.size());
+        for (size_t g = 0; g < numbers.size(); g++) {
+            numbers[g].next_value = next[g];
+            out[g] = {stats[2 * g], stats[2 * g + 1]};
+        }
+        return out;
     }
     // iterate_gbp_v2 (robot.rs:1769-1861)
     void iterate_gbp_v2(const std::vector<GbpScheduleAtIteration> &sched) {

@@ -40,6 +40,11 @@
 //               TRUE cell is the one being looked at (two of the nine cells may share a bucket: no pair is seen twice).
 //               Robots that are not alive or have a non-finite coordinate are in no cell: they overlap nobody under the
 //               predicate above.  (A non-finite or non-positive r_max takes the all-pairs form: the host decides.)
+// GROUPS (include/mgx.h, ROBOT GROUPS): in a grouped world only robots of one group collide.  The all-pairs form stages the
+// candidates' groups beside x, z and r and asks for equality in front of the predicate; the hash grid mixes the group into the
+// bucket hash, so that equal cells of different groups do not share a list, and compares the group before the predicate as well
+// (two groups' cells may still share a bucket).  Group 0 mixes to nothing: an ungrouped world (CollDev::group null) hashes as
+// before.  The listed pairs are pairs of one group by construction, so the retest does not look.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -88,6 +93,12 @@ __device__ __forceinline__ void robot_ball(const CollDev &c, int i, float &x, fl
     r = c.radius[i];
 }
 
+__device__ __forceinline__ uint32_t robot_group(const CollDev &c, int i) { return c.group ? c.group[i] : 0u; }
+// the bucket of a cell of one group's robots
+__device__ __forceinline__ uint32_t group_bucket_of(int cx, int cz, uint32_t group, uint32_t mask) {
+    return (bucket_of(cx, cz, mask) + group * 0x9E3779B1u) & mask;
+}
+
 __device__ __forceinline__ void list_append(const CollDev &c, int a, int b) {
     const uint32_t at = atomicAdd(&c.cnt[(c.pass + 1) % 3], 1u);
     if (at < c.list_cap) c.list[(c.pass + 1) & 1][at] = make_int2(a, b);
@@ -131,6 +142,7 @@ constexpr int COLL_BLOCK = 64, COLL_CHUNK = 256, COLL_RETEST_BLOCKS = 8;
 // workgroups [0, n_search): robots [64 bi, 64 bi + 64) against candidates [256 bj, 256 bj + 256); the last COLL_RETEST_BLOCKS: retest
 __global__ void __launch_bounds__(COLL_BLOCK) k_collisions_pairs(CollDev c, int n_i, int n_search) {
     __shared__ float X[COLL_CHUNK], Z[COLL_CHUNK], Rr[COLL_CHUNK];
+    __shared__ uint32_t G[COLL_CHUNK];
     const int blk = (int)blockIdx.x;
     if (blk >= n_search) {
         if (blk == n_search && threadIdx.x == 0) c.cnt[(c.pass + 2) % 3] = 0u;
@@ -142,8 +154,12 @@ __global__ void __launch_bounds__(COLL_BLOCK) k_collisions_pairs(CollDev c, int 
     if (j0 + COLL_CHUNK <= i0 + 1) return;  // every candidate of the chunk has an id <= every robot's of the workgroup
     for (int q = (int)threadIdx.x; q < COLL_CHUNK; q += COLL_BLOCK) {
         float x = NAN, z = NAN, r = 0.f;
-        if (j0 + q < c.n) robot_ball(c, j0 + q, x, z, r);
-        X[q] = x; Z[q] = z; Rr[q] = r;
+        uint32_t g = 0u;
+        if (j0 + q < c.n) {
+            robot_ball(c, j0 + q, x, z, r);
+            g = robot_group(c, j0 + q);
+        }
+        X[q] = x; Z[q] = z; Rr[q] = r; G[q] = g;
     }
     __syncthreads();
     const int i = i0 + (int)threadIdx.x;
@@ -151,8 +167,9 @@ __global__ void __launch_bounds__(COLL_BLOCK) k_collisions_pairs(CollDev c, int 
     float ax, az, ar;
     robot_ball(c, i, ax, az, ar);
     if (ax != ax || az != az) return;
+    const uint32_t ag = robot_group(c, i);
     for (int q = max(0, i + 1 - j0); q < COLL_CHUNK; q++)
-        if (balls_overlap(ax, az, ar, X[q], Z[q], Rr[q])) pair_overlaps(c, i, ax, az, ar, j0 + q, X[q], Z[q], Rr[q]);
+        if (G[q] == ag && balls_overlap(ax, az, ar, X[q], Z[q], Rr[q])) pair_overlaps(c, i, ax, az, ar, j0 + q, X[q], Z[q], Rr[q]);
 }
 
 // every alive robot with finite coordinates goes to the front of its bucket's list; a head of another pass is an empty bucket
@@ -163,7 +180,7 @@ __global__ void __launch_bounds__(256) k_collisions_link(CollDev c, double inv_c
     robot_ball(c, i, x, z, r);
     if (!isfinite(x) || !isfinite(z)) return;
     const unsigned long long stamp = (unsigned long long)(uint32_t)(c.pass + 1u) << 32;
-    const unsigned long long old = atomicExch(&c.head[bucket_of(cell_of(x, inv_cell), cell_of(z, inv_cell), mask)], stamp | (uint32_t)i);
+    const unsigned long long old = atomicExch(&c.head[group_bucket_of(cell_of(x, inv_cell), cell_of(z, inv_cell), robot_group(c, i), mask)], stamp | (uint32_t)i);
     c.next[i] = (old >> 32) == (stamp >> 32) ? (int32_t)(uint32_t)old : -1;
 }
 
@@ -181,13 +198,14 @@ __global__ void __launch_bounds__(COLL_BLOCK) k_collisions_grid(CollDev c, doubl
     if (!isfinite(ax) || !isfinite(az)) return;
     const int cx = cell_of(ax, inv_cell), cz = cell_of(az, inv_cell);
     const uint32_t stamp = (uint32_t)(c.pass + 1u);
+    const uint32_t ag = robot_group(c, i);
     for (int ox = -1; ox <= 1; ox++)
         for (int oz = -1; oz <= 1; oz++) {
             const int qx = cx + ox, qz = cz + oz;
-            const unsigned long long h = c.head[bucket_of(qx, qz, mask)];
+            const unsigned long long h = c.head[group_bucket_of(qx, qz, ag, mask)];
             int j = (uint32_t)(h >> 32) == stamp ? (int)(uint32_t)h : -1;
             for (int guard = 0; j >= 0 && j < c.n && guard < c.n; guard++) {
-                if (j > i) {
+                if (j > i && robot_group(c, j) == ag) {
                     float bx, bz, br;
                     robot_ball(c, j, bx, bz, br);
                     if (cell_of(bx, inv_cell) == qx && cell_of(bz, inv_cell) == qz && balls_overlap(ax, az, ar, bx, bz, br))

@@ -319,6 +319,7 @@ struct CollDev : ContactDev {  // robot-robot; words[1]: the pair list overflowe
     uint32_t list_cap;
     unsigned long long *head;  // hash grid: per bucket (pass stamp << 32) | first robot
     int32_t *next;             // [n] next robot of the same bucket, -1: none
+    const uint32_t *group;     // [n] the robots' groups (include/mgx.h, ROBOT GROUPS: only robots of one group collide); null: an ungrouped world
 };
 
 // Robot-environment collision bookkeeping (mgx_collisions.hip, second half): the map's colliders as the pass reads them, and
@@ -344,7 +345,7 @@ struct EnvCollDev : ContactDev {  // words[1]: a robot touched more than the slo
     double pad;                // added to a robot's radius when its cells are chosen (covers the roundings of the f32 predicate)
     int32_t *touching;         // [n][ENV_COLL_SLOTS] colliders touched after the last pass, -1: free slot
 };
-static_assert(sizeof(CollDev) == 128 && sizeof(EnvCollDev) == 152, "kernel arguments by value: no larger than before the fold");
+static_assert(sizeof(CollDev) == 136 && sizeof(EnvCollDev) == 152, "kernel arguments by value: what the fold left, and the robot-robot pass's group pointer");
 
 // Trackers on the device (mgx_tracks.hip, which says what a pass does): per-robot state and the sample log, keyed by robot id.
 struct TrackState {            // 40 bytes; all zero: a robot nobody has sampled yet

@@ -3,6 +3,7 @@
 // launchers' prototypes.  Everything above the prototypes is free of HIP and compiles with a plain C++17 compiler
 // (tests/cpu_search/search_harness.cpp).
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -19,6 +20,7 @@ constexpr int GRID_M = 1024;              // buckets of the hash grid in LDS (k_
 constexpr int GRID_ROWS_MAX_CAP = 32;     // largest row capacity of k_grid_rows (the rows are sorted in registers)
 constexpr int TWO_PASS_GRID_MIN_N = 512;  // AUTO, two passes: the hash grid in device memory from here on, all pairs below
 constexpr int PAIRS_2_MIN_N = 513, PAIRS_2_MAX_N = 1024;  // k_pairs_rows<2, 128>: the worlds that fill the device with their resident launch
+constexpr int GROUP_ROBOTS = 16;           // k_group_rows: robots of ONE group a workgroup serves (four lanes each), 256 candidates per pass
 constexpr int NEIGHBOURS_PREV_STRIDE = 33;       // words per robot of the kept rows: count, then up to 32 entries
 constexpr int32_t NEIGHBOURS_CHANGED = 1 << 30;  // in a robot's count: its row is not the one of the search before
 // the all-pairs rows kernel holds ALL positions in LDS (structure of arrays, padded to four robots)
@@ -28,9 +30,11 @@ static_assert(NEIGHBOURS_PREV_STRIDE == 1 + GRID_ROWS_MAX_CAP && GRID_M <= ROWS_
 
 inline bool usable_radius(float radius) { return std::isfinite(radius) && radius > 0.f; }  // (else every pair has to see the predicate)
 
-// the kernel (MGX_SEARCH_*) that answers a query of n robots — the one launched LAST where a search takes several launches
-inline int32_t search_kernel_for(int n, uint32_t method, float radius, int32_t cap) {
+// the kernel (MGX_SEARCH_*) that answers a query of n robots — the one launched LAST where a search takes several launches.
+// grouped: the world has robots of a non-zero group (include/mgx.h, ROBOT GROUPS) — one kernel, whatever the method and the size
+inline int32_t search_kernel_for(int n, uint32_t method, float radius, int32_t cap, bool grouped = false) {
     if (n <= 0) return MGX_SEARCH_NONE;  // (an empty query launches nothing)
+    if (grouped) return MGX_SEARCH_ROWS_GROUPS;
     if (method == MGX_NEIGHBOURS_AUTO && n <= ROWS_MAX_N) {  // small worlds: ONE small kernel, no scans
         if (n <= GRID_M && cap <= GRID_ROWS_MAX_CAP && usable_radius(radius)) return cap <= 16 ? MGX_SEARCH_ROWS_GRID_16 : MGX_SEARCH_ROWS_GRID_32;
         return n >= PAIRS_2_MIN_N && n <= PAIRS_2_MAX_N ? MGX_SEARCH_ROWS_PAIRS_2 : MGX_SEARCH_ROWS_PAIRS_4;
@@ -39,8 +43,9 @@ inline int32_t search_kernel_for(int n, uint32_t method, float radius, int32_t c
     return grid && usable_radius(radius) ? MGX_SEARCH_TWO_PASS_GRID : MGX_SEARCH_TWO_PASS_PAIRS;
 }
 inline bool search_in_rows(int32_t kernel) { return kernel >= MGX_SEARCH_ROWS_PAIRS_4; }   // one pass, rows of a fixed capacity
-inline bool search_keeps_rows(int32_t kernel) { return kernel >= MGX_SEARCH_ROWS_GRID_16; }  // ... and it can compare them with the kept ones
-static_assert(MGX_SEARCH_ROWS_PAIRS_4 == 2 && MGX_SEARCH_ROWS_PAIRS_2 == 3 && MGX_SEARCH_ROWS_GRID_16 == 4 && MGX_SEARCH_ROWS_GRID_32 == 5, "order of the codes");
+inline bool search_keeps_rows(int32_t kernel) { return kernel == MGX_SEARCH_ROWS_GRID_16 || kernel == MGX_SEARCH_ROWS_GRID_32; }  // ... and it can compare them with the kept ones
+static_assert(MGX_SEARCH_ROWS_PAIRS_4 == 2 && MGX_SEARCH_ROWS_PAIRS_2 == 3 && MGX_SEARCH_ROWS_GRID_16 == 4 && MGX_SEARCH_ROWS_GRID_32 == 5 &&
+                  MGX_SEARCH_ROWS_GROUPS == 6, "order of the codes");
 
 // ---- the host's side of a one-pass search ---------------------------------------------------------------------------------------
 // the mapped pinned block the kernel reads and writes in place: [3 n floats: positions up] [n ints: counts down] [n x cap ints: rows down]
@@ -74,6 +79,43 @@ inline void compact_to_world(const std::vector<int> &alive, int n_all, std::vect
     }
 }
 
+// ---- a grouped world's search: the query listed by group ---------------------------------------------------------------------
+// What k_group_rows reads beside the positions, built by the host when robots join or leave the query:
+//   members  the query's robots (indices INTO THE QUERY), group after group, ascending within a group — so rows come out ascending
+//   seg      [n_segments + 1] where each non-empty group's members start (a group nobody of the query is in has no segment)
+//   wg       [n_workgroups][2] (segment, first member of the slice within the segment): GROUP_ROBOTS robots of one group each
+//   largest  the largest segment: sizes the kernel's LDS
+struct GroupTables {
+    std::vector<int32_t> members, seg, wg;
+    int largest = 0;
+    int n_segments() const { return seg.empty() ? 0 : (int)seg.size() - 1; }
+    int n_workgroups() const { return (int)(wg.size() / 2); }
+    // the three tables behind one another, as the device holds them: [members n] [seg n_segments + 1] [wg 2 n_workgroups]
+    size_t off_seg() const { return members.size(); }
+    size_t off_wg() const { return members.size() + seg.size(); }
+    size_t words() const { return members.size() + seg.size() + wg.size(); }
+};
+// group_of_query [n]: the group of every robot of the query, in query order.  false: a group has more than ROWS_MAX_N robots (no
+// workgroup holds its positions) — t.largest says how many
+inline bool group_tables(const uint32_t *group_of_query, int n, GroupTables &t) {
+    t.members.resize((size_t)std::max(n, 0));
+    for (int q = 0; q < n; q++) t.members[(size_t)q] = q;
+    std::stable_sort(t.members.begin(), t.members.end(), [&](int32_t a, int32_t b) { return group_of_query[a] < group_of_query[b]; });
+    t.seg.assign(1, 0);
+    t.wg.clear();
+    t.largest = 0;
+    for (int q = 0; q < n;) {
+        int e = q + 1;
+        while (e < n && group_of_query[t.members[(size_t)e]] == group_of_query[t.members[(size_t)q]]) e++;
+        const int32_t segment = (int32_t)t.seg.size() - 1;
+        for (int first = 0; first < e - q; first += GROUP_ROBOTS) { t.wg.push_back(segment); t.wg.push_back(first); }
+        t.seg.push_back(e);
+        t.largest = std::max(t.largest, e - q);
+        q = e;
+    }
+    return t.largest <= ROWS_MAX_N;
+}
+
 // ---- the launchers (mgx_topology.hip) ---------------------------------------------------------------------------------------------
 // the two-pass search's scratch, all on the device: cnt[n], bucket_cnt[M], bucket_ptr[M + 1], cursor[M], members[n], special[n],
 // n_special[1], ptr[n + 1]
@@ -84,6 +126,9 @@ hipError_t neighbours_fill(const float *pos, int n, float radius, bool grid, uin
                            hipStream_t s);
 hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s,
                            int32_t *prev = nullptr, int prev_valid = 0, bool *flagged = nullptr, int32_t *ran = nullptr);
+// a grouped world's search: tables = GroupTables on the device (members, seg, wg behind one another), largest <= ROWS_MAX_N
+hipError_t neighbours_rows_groups(const float *pos, int n, const int32_t *members, const int32_t *seg, const int32_t *wg, int n_workgroups,
+                                  int largest, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, int32_t *ran = nullptr);
 #endif
 
 }  // namespace mgx

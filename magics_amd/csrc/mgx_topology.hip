@@ -170,6 +170,66 @@ __global__ void __launch_bounds__(ROWS_BLOCK) k_pairs_rows(const float *__restri
     }
     if (live && l == 0) cnt[i] = m;
 }
+// ---- all pairs WITHIN each group, ONE pass, rows of a fixed capacity (a grouped world: include/mgx.h, ROBOT GROUPS) -----------
+// Many independent runs share the world: robots of different groups are never in range of one another, so nobody has to look at
+// them.  The host lists the query's robots by group (GroupTables, mgx_search.h: members ascending within a group, a segment table,
+// and one (segment, first member) record per workgroup).  A workgroup is k_pairs_rows<4, 64> for a slice of ONE group: one wave,
+// GROUP_ROBOTS robots x 4 lanes; it stages only ITS group's positions into LDS, through the member list (structure of arrays), tests
+// only those — 256 candidates per pass, the same quad exchange of hit masks — and writes rows of QUERY indices (members[..]),
+// ascending because the members are.  The cost of a search is the sum of the squared group sizes.  A row that outgrows `cap` keeps
+// counting; the host repeats the search with more room.
+__global__ void __launch_bounds__(64) k_group_rows(const float *__restrict__ pos, const int32_t *__restrict__ members,
+                                                   const int32_t *__restrict__ seg, const int32_t *__restrict__ wg, float s_max, int32_t cap,
+                                                   int32_t *__restrict__ cnt, int32_t *__restrict__ rows) {
+    constexpr int L = 4;
+    extern __shared__ float lds_pos[];
+    const int segment = wg[2 * blockIdx.x], first = wg[2 * blockIdx.x + 1];
+    const int m0 = seg[segment], ng = seg[segment + 1] - m0;  // this group's members: members[m0 .. m0 + ng)
+    const int32_t *mem = members + m0;
+    const int npad = (ng + 3) & ~3;
+    float *X = lds_pos, *Y = lds_pos + npad, *Z = lds_pos + 2 * npad;
+    for (int j = (int)threadIdx.x; j < ng; j += 64) {
+        const float *p = pos + 3 * (size_t)mem[j];
+        X[j] = p[0]; Y[j] = p[1]; Z[j] = p[2];
+    }
+    __syncthreads();
+    const int i = first + (int)threadIdx.x / L, l = (int)threadIdx.x % L;  // robot i OF THE GROUP
+    const bool live = i < ng;
+    const int ii = live ? i : 0;
+    const float ax = X[ii], ay = Y[ii], az = Z[ii];
+    const int qi = mem[ii];  // ... and its index in the query: where its count and its row go
+    int m = 0;
+    int32_t *row = rows + (size_t)qi * (size_t)cap;
+    const int group0 = ((int)threadIdx.x & 63) - l;
+    for (int j0 = 0; j0 < ng; j0 += 64 * L) {
+        unsigned long long hits = 0ull;
+#pragma unroll 4
+        for (int k = 0; k < 64; k++) {
+            const int j = j0 + L * k + l;
+            if (j < ng && j != i && in_comms_range_sq(ax, ay, az, X[j], Y[j], Z[j], s_max)) hits |= 1ull << k;
+        }
+        if (!live) hits = 0ull;
+        unsigned long long mk[L];
+#pragma unroll
+        for (int o = 0; o < L; o++) {
+            const unsigned lo = (unsigned)__shfl((int)(unsigned)hits, group0 + o, 64), hi = (unsigned)__shfl((int)(unsigned)(hits >> 32), group0 + o, 64);
+            mk[o] = ((unsigned long long)hi << 32) | lo;
+        }
+        unsigned long long mine = hits;
+        while (mine) {
+            const int k = __ffsll((long long)mine) - 1;
+            mine &= mine - 1ull;
+            const unsigned long long below = (1ull << k) - 1ull;
+            int at = m;
+#pragma unroll
+            for (int o = 0; o < L; o++) at += __popcll(mk[o] & below) + (o < l ? (int)((mk[o] >> k) & 1ull) : 0);
+            if (at < cap) row[at] = mem[j0 + L * k + l];
+        }
+#pragma unroll
+        for (int o = 0; o < L; o++) m += __popcll(mk[o]);
+    }
+    if (live && l == 0) cnt[qi] = m;
+}
 // ---- hash grid, ONE pass, rows of a fixed capacity (worlds of up to 1024 robots, a usable radius) ----------------------------
 // The all-pairs kernel above tests a million pairs for a thousand robots; beside a resident launch, sharing its SIMDs, that is
 // 70 us.  Here every workgroup (128 threads, two lanes per robot: sixteen workgroups for 1000 robots — they fit the holes such a
@@ -399,6 +459,17 @@ hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, i
     default:  // beyond ROWS_MAX_N: no one-pass kernel holds the positions in its LDS
         return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+// One launch of a grouped world's search (k_group_rows): one workgroup per GROUP_ROBOTS robots of a group, LDS for the largest group
+hipError_t neighbours_rows_groups(const float *pos, int n, const int32_t *members, const int32_t *seg, const int32_t *wg, int n_workgroups,
+                                  int largest, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, int32_t *ran) {
+    if (n <= 0 || n_workgroups <= 0) return hipSuccess;
+    if (largest <= 0 || largest > ROWS_MAX_N) return hipErrorInvalidValue;  // (no workgroup holds the positions of such a group)
+    hipLaunchKernelGGL(k_group_rows, dim3((unsigned)n_workgroups), dim3(64), pairs_rows_lds(largest), s, pos, members, seg, wg,
+                       squared_threshold(radius), cap, cnt, rows);
+    if (ran) *ran = MGX_SEARCH_ROWS_GROUPS;
     return hipGetLastError();
 }
 

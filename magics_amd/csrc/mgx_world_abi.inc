@@ -126,10 +126,15 @@ int mgx_world_set_environment(mgx_world *w, const mgx_env_desc *env) {
 
 int mgx_robot_add(mgx_world *w, const mgx_robot_desc *d, int32_t *robot_id) {
     MGX_ENTER(w);
+    // (what the descriptor alone says comes first: it needs no world)
+    if (d && d->group >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "group %u is not below MGX_GROUPS_MAX (%u)", d->group, MGX_GROUPS_MAX);
+    if (d && d->group && d->ghost) return fail(MGX_ERR_INVALID, "a ghost has no group");
     if (!w || !d || !d->mean0 || !d->prior_diag || !d->dt) return fail(MGX_ERR_INVALID, "null argument");
     if (d->K < 3) return fail(MGX_ERR_INVALID, "K must be >= 3");
     if (w->K && (int)d->K != w->K) return fail(MGX_ERR_INVALID, "all robots of a world share K (%d), got %u", w->K, d->K);
     if (!(d->radius > 0)) return fail(MGX_ERR_INVALID, "radius must be positive");
+    if (d->group && w->obs.n_ghosts) return fail(MGX_ERR_STATE, "robot groups are for unsharded worlds: this one has ghosts");
+    if (d->ghost && w->sets.n_grouped) return fail(MGX_ERR_STATE, "a grouped world takes no ghosts");
     for (const Robot &o : w->robots)
         if (o.order_key == d->order_key) return fail(MGX_ERR_INVALID, "duplicate order_key");
     const int K = (int)d->K, E = 4 * K - 6;
@@ -186,6 +191,8 @@ int mgx_robot_add(mgx_world *w, const mgx_robot_desc *d, int32_t *robot_id) {
     w->obs.n_ghosts += rb.ghost ? 1 : 0;
     w->sets.radius.push_back(rb.radius);
     w->sets.removed.push_back(0);
+    w->sets.group.push_back(d->group);
+    w->sets.n_grouped += d->group ? 1 : 0;
     w->robots.push_back(std::move(rb));
     w->sets.ensure(w->robots.size());
     w->K = K;

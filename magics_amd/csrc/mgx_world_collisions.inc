@@ -162,6 +162,13 @@ static int collisions_pass(mgx_world *w, const float *pos_d, const uint8_t *aliv
     mgx_world::Collisions &c = w->coll;
     int rc = collisions_size(w);
     if (rc != MGX_OK) return rc;
+    c.d.group = nullptr;
+    if (w->sets.n_grouped) {  // a grouped world: the pass compares the robots' groups
+        Outgrown out{s};
+        if ((rc = observers_groups(w, out)) != MGX_OK) return rc;
+        HIP_TRY(out.retire());
+        c.d.group = w->obs.group.p;
+    }
     const size_t R = w->robots.size();
     size_t n_alive = 0;
     float r_max = 0.f;

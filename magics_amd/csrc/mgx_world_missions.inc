@@ -103,16 +103,31 @@ int mgx_mission_tick(mgx_world *w, float comms_radius, uint32_t method, uint64_t
     return rc != MGX_OK ? rc : mgx_mission_tick_end(w, antennas, max_speed, delta_t, steps, n_steps);
 }
 
+static int mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, uint64_t *robot_number_next, int32_t despawn_finished,
+                              uint32_t *stats, uint32_t n_groups);
 int mgx_mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, uint64_t *robot_number_next, int32_t despawn_finished,
                            uint32_t *stats) {
     MGX_ENTER(w);
     if (!w || !robot_number_next) return fail(MGX_ERR_INVALID, "null argument");
     if (*robot_number_next == 0) return fail(MGX_ERR_INVALID, "robot_number is NonZeroUsize");
     if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
+    return mission_tick_begin(w, comms_radius, method, robot_number_next, despawn_finished, stats, 0);
+}
+int mgx_mission_tick_begin_groups(mgx_world *w, float comms_radius, uint32_t method, uint32_t n_groups, uint64_t *number_next,
+                                  int32_t despawn_finished, uint32_t *stats) {
+    MGX_ENTER(w);
+    if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
+    const int rc = groups_arguments(w, n_groups, number_next);
+    return rc != MGX_OK ? rc : mission_tick_begin(w, comms_radius, method, number_next, despawn_finished, stats, n_groups);
+}
+// n_groups: 0 — one generator, stats {created, deleted, completed}; otherwise one generator and one stats triple per group
+static int mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, uint64_t *robot_number_next, int32_t despawn_finished,
+                              uint32_t *stats, uint32_t n_groups) {
+    int rc = MGX_OK;
     mgx_world::Mission &ms = w->mission;
     if (!ms.any) return fail(MGX_ERR_STATE, "no robot has a mission (mgx_mission_set)");
     if (w->K < 3) return fail(MGX_ERR_INVALID, "needs K >= 3");
-    int rc = commit(w);
+    rc = commit(w);
     if (rc != MGX_OK) return rc;
     if (w->d.R_total != w->d.R_local) return fail(MGX_ERR_STATE, "missions run on unsharded worlds");
     if (ms.dirty || ms.has.size() != w->robots.size()) {
@@ -177,10 +192,19 @@ int mgx_mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, ui
             idx.swap(nidx);
         }
     }
-    uint32_t st[2] = {0, 0};
-    rc = topology_bookkeeping(w, ptr, idx, robot_number_next, st, tm);
-    if (rc != MGX_OK) return rc;
-    if (stats) { stats[0] = st[0]; stats[1] = st[1]; stats[2] = n_fin; }
+    if (n_groups) {
+        rc = topology_bookkeeping(w, ptr, idx, robot_number_next, stats, tm, nullptr, n_groups, 3);
+        if (rc != MGX_OK) return rc;
+        if (stats) {
+            for (uint32_t g = 0; g < n_groups; g++) stats[3 * (size_t)g + 2] = 0;
+            for (int32_t r : ms.last_finished) stats[3 * (size_t)w->sets.group[(size_t)r] + 2] += 1;
+        }
+    } else {
+        uint32_t st[2] = {0, 0};
+        rc = topology_bookkeeping(w, ptr, idx, robot_number_next, st, tm);
+        if (rc != MGX_OK) return rc;
+        if (stats) { stats[0] = st[0]; stats[1] = st[1]; stats[2] = n_fin; }
+    }
     ms.in_tick = true;
     return MGX_OK;
 }

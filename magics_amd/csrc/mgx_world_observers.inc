@@ -60,6 +60,23 @@ static int observers_radii(mgx_world *w, Outgrown &out) {
     return MGX_OK;
 }
 
+// the groups of a GROUPED world's robots (include/mgx.h, ROBOT GROUPS), for the robot-robot pass: the ones that joined since they
+// were last brought up, behind the ones that are up — as the radii above.  An ungrouped world never comes here
+static int observers_groups(mgx_world *w, Outgrown &out) {
+    mgx_world::RobotInputs &o = w->obs;
+    const size_t R = w->robots.size(), n0 = o.group_sized;
+    if (R <= n0) return MGX_OK;
+    if (R > o.group.cap) HIP_TRY(out.grow(o.group, observers_room(w, R), n0, 0));
+    void *hp = nullptr;
+    int slot = 0;
+    HIP_TRY(w->stage.acquire(sizeof(uint32_t) * (R - n0), &hp, &slot));
+    for (size_t r = n0; r < R; r++) static_cast<uint32_t *>(hp)[r - n0] = w->sets.group[r];
+    HIP_TRY(hipMemcpyAsync(o.group.p + n0, hp, sizeof(uint32_t) * (R - n0), hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(w->stage.release(slot, w->stream));
+    o.group_sized = R;
+    return MGX_OK;
+}
+
 // who is looked at — and has moved, where the caller says who did (moved, may be NULL) — and the caller's positions (NULL: none):
 // up from a pinned slot, behind whatever the stream is busy with (a buffer that has to grow: RobotInputs says what frees it)
 static int observers_stage(mgx_world *w, const float *positions_xyz, const uint8_t *moved, hipStream_t s) {

@@ -253,6 +253,7 @@ int mgx_robot_release(mgx_world *w, int32_t robot) {
     MGX_ENTER(w);
     if (!w || robot < 0 || (size_t)robot >= w->robots.size()) return fail(MGX_ERR_INVALID, "bad robot id");
     if (w->robots[(size_t)robot].ghost) return fail(MGX_ERR_STATE, "robot %d is a ghost here already", robot);
+    if (w->sets.n_grouped) return fail(MGX_ERR_STATE, "a grouped world takes no ghosts");
     if ((size_t)robot < w->mission.has.size() && w->mission.has[(size_t)robot])
         return fail(MGX_ERR_STATE, "robot %d has a mission on this device (mgx_mission_set): missions do not migrate — routes, next waypoints "
                                    "and Transforms are state of unsharded worlds (include/mgx.h)", robot);

@@ -111,9 +111,17 @@ static int rows_launch(mgx_world *w, PendingSearch &ps, int cap, const float *ho
     HIP_TRY(hipHostGetDevicePointer(&dpin, S.pin.p, 0));
     char *dp = static_cast<char *>(dpin);
     ps.rows.cap = cap;
-    HIP_TRY(neighbours_rows(ps.from_missions ? S.pos.p : reinterpret_cast<const float *>(dp), ps.n, ps.radius, cap,
-                            reinterpret_cast<int32_t *>(dp + at.off_cnt), reinterpret_cast<int32_t *>(dp + at.off_rows), ps.stream, prev,
-                            prev_valid, &ps.rows.has_chg, &S.last_kernel));
+    if (ps.grouped) {  // a grouped world: its one kernel, over the query listed by group (groups_prepare)
+        const GroupTables &g = S.groups;
+        ps.rows.has_chg = false;
+        HIP_TRY(neighbours_rows_groups(ps.from_missions ? S.pos.p : reinterpret_cast<const float *>(dp), ps.n, S.groups_d.p, S.groups_d.p + g.off_seg(),
+                                       S.groups_d.p + g.off_wg(), g.n_workgroups(), g.largest, ps.radius, cap, reinterpret_cast<int32_t *>(dp + at.off_cnt),
+                                       reinterpret_cast<int32_t *>(dp + at.off_rows), ps.stream, &S.last_kernel));
+    } else {
+        HIP_TRY(neighbours_rows(ps.from_missions ? S.pos.p : reinterpret_cast<const float *>(dp), ps.n, ps.radius, cap,
+                                reinterpret_cast<int32_t *>(dp + at.off_cnt), reinterpret_cast<int32_t *>(dp + at.off_rows), ps.stream, prev,
+                                prev_valid, &ps.rows.has_chg, &S.last_kernel));
+    }
     S.last_cap = cap;
     S.last_launches++;
     return MGX_OK;
@@ -231,11 +239,36 @@ static int csr_collect(mgx_world *w, PendingSearch &ps, std::vector<int32_t> &pt
     return MGX_OK;
 }
 
+// A grouped world's query listed by group (GroupTables, mgx_search.h), on the device: built again only when robots have joined or
+// left the query — then uploaded and waited for (the kernels of an earlier search on this stream have read the old tables by then)
+static int groups_prepare(mgx_world *w, PendingSearch &ps) {
+    NeighbourSearch &S = w->search;
+    if (S.groups_valid && S.groups_alive == ps.alive) return MGX_OK;
+    S.groups_valid = false;
+    std::vector<uint32_t> of_query((size_t)ps.n);
+    for (int q = 0; q < ps.n; q++) of_query[(size_t)q] = w->sets.group[(size_t)ps.alive[(size_t)q]];
+    if (!group_tables(of_query.data(), ps.n, S.groups))
+        return fail(MGX_ERR_INVALID, "a group of %d robots: the grouped search holds one group's positions in a workgroup's LDS, %d at the most", S.groups.largest,
+                    ROWS_MAX_N);
+    const GroupTables &g = S.groups;
+    S.groups_host.clear();
+    S.groups_host.insert(S.groups_host.end(), g.members.begin(), g.members.end());
+    S.groups_host.insert(S.groups_host.end(), g.seg.begin(), g.seg.end());
+    S.groups_host.insert(S.groups_host.end(), g.wg.begin(), g.wg.end());
+    HIP_TRY(hipStreamSynchronize(ps.stream));  // (nothing reads the old tables any more)
+    HIP_TRY(S.groups_d.upload(S.groups_host, ps.stream));
+    HIP_TRY(hipStreamSynchronize(ps.stream));
+    S.groups_alive = ps.alive;
+    S.groups_valid = true;
+    return MGX_OK;
+}
 // track: the search of a topology pass over the caller's positions (see rows_enqueue)
 static int neighbours_enqueue(mgx_world *w, const float *pos, float radius, uint32_t method, PendingSearch &ps, bool track = false) {
     int rc = search_front(w, &pos, radius, method, ps);
     if (rc != MGX_OK) return rc;
-    const int32_t kernel = search_kernel_for(ps.n, method, radius, w->search.row_cap);
+    ps.grouped = w->sets.n_grouped != 0 && ps.n > 0;
+    const int32_t kernel = search_kernel_for(ps.n, method, radius, w->search.row_cap, ps.grouped);
+    if (ps.grouped && (rc = groups_prepare(w, ps)) != MGX_OK) return rc;
     ps.in_rows = search_in_rows(kernel);
     // (the kept rows: where robots left the query, or the positions are a mission's, nothing is kept)
     rc = ps.in_rows ? rows_enqueue(w, pos, ps, track && !ps.compact && !ps.from_missions && search_keeps_rows(kernel))
@@ -292,14 +325,42 @@ int mgx_connections(mgx_world *w, int32_t robot, int32_t *others, uint32_t capac
     return MGX_OK;
 }
 
+// n_groups: 0 — ONE generator (*robot_number_next), stats {created, deleted}; otherwise one generator per group
+// (robot_number_next[n_groups]) and stats [n_groups][stats_stride], {created, deleted, ..} per group (include/mgx.h, ROBOT GROUPS)
 static int topology_bookkeeping(mgx_world *w, std::vector<int32_t> &ptr, std::vector<int32_t> &idx, uint64_t *robot_number_next,
-                                uint32_t *stats, StageTimer &tm, const uint8_t *chg = nullptr);
+                                uint32_t *stats, StageTimer &tm, const uint8_t *chg = nullptr, uint32_t n_groups = 0, uint32_t stats_stride = 2);
+// what the per-group calls check before anything happens (no device needed; what the arguments alone say needs no world either)
+static int groups_arguments(mgx_world *w, uint32_t n_groups, const uint64_t *number_next) {
+    if (!number_next) return fail(MGX_ERR_INVALID, "null argument (number_next)");
+    if (n_groups == 0 || n_groups > MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "n_groups %u is not in 1 .. MGX_GROUPS_MAX (%u)", n_groups, MGX_GROUPS_MAX);
+    for (uint32_t g = 0; g < n_groups; g++)
+        if (number_next[g] == 0) return fail(MGX_ERR_INVALID, "robot_number is NonZeroUsize (group %u)", g);
+    if (!w) return fail(MGX_ERR_INVALID, "null argument");
+    for (size_t r = 0; r < w->sets.group.size(); r++)
+        if (w->sets.group[r] >= n_groups) return fail(MGX_ERR_INVALID, "robot %zu is in group %u: not below n_groups %u", r, w->sets.group[r], n_groups);
+    return MGX_OK;
+}
+static int update_topology(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint64_t *robot_number_next, uint32_t *stats,
+                           uint32_t n_groups);
 int mgx_update_topology(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint64_t *robot_number_next,
                         uint32_t *stats) {
     MGX_ENTER(w);
     if (!w || !positions_xyz || !robot_number_next) return fail(MGX_ERR_INVALID, "null argument");
     if (*robot_number_next == 0) return fail(MGX_ERR_INVALID, "robot_number is NonZeroUsize");
     if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
+    return update_topology(w, positions_xyz, radius, method, robot_number_next, stats, 0);
+}
+int mgx_update_topology_groups(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint32_t n_groups, uint64_t *number_next,
+                               uint32_t *stats) {
+    MGX_ENTER(w);
+    if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
+    const int rc = groups_arguments(w, n_groups, number_next);
+    if (rc != MGX_OK) return rc;
+    if (!positions_xyz) return fail(MGX_ERR_INVALID, "null argument");
+    return update_topology(w, positions_xyz, radius, method, number_next, stats, n_groups);
+}
+static int update_topology(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint64_t *robot_number_next, uint32_t *stats,
+                           uint32_t n_groups) {
     std::vector<int32_t> ptr, idx;
     StageTimer tm("update_topology");
     // update_robot_neighbours (robot.rs:1362-1384).  A small world's search runs BESIDE the GBP schedule of the tick before, on a
@@ -319,13 +380,13 @@ int mgx_update_topology(mgx_world *w, const float *positions_xyz, float radius, 
     rc = neighbours_collect(w, ps, ptr, idx, &chg);
     if (rc != MGX_OK) return rc;
     tm.lap("neighbour search");
-    return topology_bookkeeping(w, ptr, idx, robot_number_next, stats, tm, chg);
+    return topology_bookkeeping(w, ptr, idx, robot_number_next, stats, tm, chg, n_groups);
 }
 // delete_interrobot_factors + create_interrobot_factors on the search's result (rows per robot id, ascending)
 // chg (may be null): per robot, whether its row differs from the one of the pass before — which is its connection set (see
 // NeighbourSearch::prev): a robot whose byte is 0 has nothing out of range and nobody new, and its row was not even copied
 static int topology_bookkeeping(mgx_world *w, std::vector<int32_t> &ptr, std::vector<int32_t> &idx, uint64_t *robot_number_next,
-                                uint32_t *stats, StageTimer &tm, const uint8_t *chg) {
+                                uint32_t *stats, StageTimer &tm, const uint8_t *chg, uint32_t n_groups, uint32_t stats_stride) {
     int rc = MGX_OK;
     w->search.prev_valid = false;  // (until this pass has gone through)
     const int n = (int)w->robots.size();
@@ -335,6 +396,8 @@ static int topology_bookkeeping(mgx_world *w, std::vector<int32_t> &ptr, std::ve
         for (int r = 0; r < n; r++) w->search.last_changed += chg[r] ? 1 : 0;
     }
     uint32_t created = 0, deleted = 0;
+    if (n_groups && stats)
+        for (uint32_t g = 0; g < n_groups; g++) stats[(size_t)g * stats_stride] = stats[(size_t)g * stats_stride + 1] = 0;
     // a robot's row of the search and its connection set are both ascending in order key (BTreeSet<Entity>): merges
     ConnSets &cs = w->sets;
     auto key = [&](int x) { return cs.keys[(size_t)x]; };
@@ -397,18 +460,23 @@ static int topology_bookkeeping(mgx_world *w, std::vector<int32_t> &ptr, std::ve
             if (victim[(size_t)r] >= 0) pairs.emplace_back(r, victim[(size_t)r]);
         ir_disconnect_batch(w, pairs);
         deleted = (uint32_t)pairs.size();
+        if (n_groups && stats)
+            for (const auto &pr : pairs) stats[(size_t)cs.group[(size_t)pr.first] * stats_stride + 1] += 1;
         tm.lap("delete");
     }
     for (const auto &f : fresh) {
         const int r = f.first, o = f.second;
-        rc = ir_connect(w, r, o, *robot_number_next);
+        // (one generator, or the one of the creating robot's group)
+        uint64_t *number = n_groups ? robot_number_next + cs.group[(size_t)r] : robot_number_next;
+        rc = ir_connect(w, r, o, *number);
         if (rc != MGX_OK) return rc;
-        *robot_number_next += (uint64_t)(w->K - 1);
+        *number += (uint64_t)(w->K - 1);
         cs.insert_sorted((size_t)r, o);  // :1546
         created++;
+        if (n_groups && stats) stats[(size_t)cs.group[(size_t)r] * stats_stride] += 1;
     }
     tm.lap("create");
-    if (stats) { stats[0] = created; stats[1] = deleted; }
+    if (stats && !n_groups) { stats[0] = created; stats[1] = deleted; }
     w->search.prev_valid = chg != nullptr;  // (every robot's set is its row now — and where the search kept the rows, they are on the device)
     return MGX_OK;
 }

@@ -313,6 +313,8 @@ struct ConnSets {
     std::vector<uint8_t> ghost;   // the robots' ghost flags and radii, compact like the keys (fixed when a robot is added): the
     std::vector<double> radius;   // per-tick passes over all connections read them instead of the robots themselves
     std::vector<uint8_t> removed; // ... and Robot::removed (mgx_robot_remove)
+    std::vector<uint32_t> group;  // mgx_robot_desc::group of every robot (include/mgx.h, ROBOT GROUPS), fixed when it is added
+    size_t n_grouped = 0;         // robots of a non-zero group: the world is GROUPED when there are any
     // ids ascending == order keys ascending?  (the rule: robots get their keys in the order they are added.)  Looked at once per
     // robot count: the per-tick merges then compare ids instead of looking two keys up per comparison.
     size_t mono_n = 0;
@@ -435,6 +437,13 @@ struct NeighbourSearch {
     PinBuf pin;
     std::vector<float> packed;  // the callers' positions without the removed robots' (scratch)
     std::vector<uint8_t> chg;   // the rows-changed flags taken out of the counts (scratch; what mgx_last_search copies)
+    // a grouped world's search (k_group_rows): the query listed by group, on the host and on the device (members, seg, wg behind one
+    // another) — built again only when the robots of the query are not the ones it was built for
+    GroupTables groups;
+    std::vector<int> groups_alive;
+    bool groups_valid = false;
+    DevBuf<int32_t> groups_d;
+    std::vector<int32_t> groups_host;  // (scratch of the upload)
     // the last search (mgx_last_search): the kernel it launched last, written by the branch that launched it, with which row
     // capacity, in how many launches — and how many robots' changed-row flags reached the pass behind it (-1: none did)
     int32_t last_kernel = MGX_SEARCH_NONE, last_cap = 0, last_launches = 0, last_changed = -1;
@@ -447,6 +456,7 @@ struct NeighbourSearch {
         bool compact = false, from_missions = false;
         float radius = 0.f;
         uint32_t method = 0;
+        bool grouped = false;  // a grouped world's search: k_group_rows over NeighbourSearch::groups
         bool in_rows = false;  // the one-pass kernel with rows of a fixed capacity (`rows`), else count / scan / fill (`csr`)
         struct { int cap = 0; bool has_chg = false; } rows;  // has_chg: the counts carry "this robot's row changed" (see prev)
         struct Csr { size_t guess, off_ptr, off_idx; uint32_t M; bool grid; } csr{};  // the guessed buffer, where the pinned block holds what
@@ -770,6 +780,8 @@ struct mgx_world {
         DevBuf<float> pos;       // positions the caller of the last _update handed in
         DevBuf<uint8_t> flags;   // ... and who was looked at then: not removed, not a ghost, and moved where the caller said who did
         uint32_t n_ghosts = 0;   // ghosts among the robots (mgx_robot_add, _import, _release): collisions_sharded
+        DevBuf<uint32_t> group;  // [robot id] the robots' groups — of a grouped world only (observers_groups), what the robot-robot pass compares
+        size_t group_sized = 0;  // robots whose groups are up
     } obs;
     // collision bookkeeping on the device (mgx_world_collisions.inc, mgx_collisions.hip): what its two kinds share
     struct ContactBook {

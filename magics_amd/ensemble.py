@@ -1,0 +1,266 @@
+"""Many independent scenario runs in ONE world: robot groups (include/mgx.h, ROBOT GROUPS) under the scenario front-end.
+
+The reference's experiments loop over seeds and one or two parameters and start the binary once per combination; each of those
+runs has a few dozen robots and fills a few dozen of the device's workgroup slots.  An `Ensemble` runs M such scenarios — its
+MEMBERS — as the groups 0 .. M-1 of one world: one launch per schedule and one synchronisation per tick for all of them, and every
+member stays bit-identical to the same scenario run by a `Simulation` on a world of its own (tests/test_gpu_ensemble.py).
+
+Nothing of `Simulation` is restated here.  Every member IS a `Simulation`, on a view of the shared world (`_MemberWorld`) that
+speaks the member's own robot numbering and puts its robots into its group; the ensemble makes the two world-wide calls of a tick
+once (mission_tick_begin_groups, mission_tick_end) and runs the parts of `Simulation._tick_device` around them per member; the
+device's collision log and tracker sample log are drained once and their records routed to the members by robot id."""
+import copy
+
+import numpy as np
+
+from . import config as _config
+from . import hostlib
+from .sim import Simulation
+
+UNSUPPORTED = ("environment_collisions", "goal_areas", "device_metrics", "global_planner")
+
+
+def _shared_settings(sc):
+    """everything the world holds once, as (key, value) in the order it is compared"""
+    cfg = sc["config"]
+    out = [("params." + k, v) for k, v in _config.world_params(cfg).items()]
+    out += [("gbp.iteration-schedule", cfg["gbp"]["iteration-schedule"]), ("gbp.lookahead-multiple", cfg["gbp"]["lookahead-multiple"]),
+            ("robot.communication.radius", cfg["robot"]["communication"]["radius"]), ("robot.target-speed", cfg["robot"]["target-speed"]),
+            ("robot.planning-horizon", cfg["robot"]["planning-horizon"]), ("simulation.hz", cfg["simulation"]["hz"]),
+            ("simulation.despawn-robot-when-final-waypoint-reached", cfg["simulation"]["despawn-robot-when-final-waypoint-reached"]),
+            ("environment", sc["environment"])]
+    return out
+
+
+class _MemberWorld:
+    """What one member's Simulation sees of the shared world: its own robots under its own ids (0, 1, .. in the order it adds them),
+    in its group.  What the world holds once (environment, observers) is set up by the first member; the two halves of the
+    mission tick belong to the ensemble."""
+
+    def __init__(self, ensemble, group):
+        self._e, self._group = ensemble, group
+        self.ids = []            # member id -> world id
+        self.coll_events = []    # this member's collision events so far, member ids, in (pass, a, b) order
+        self.samples = []        # this member's tracker samples not taken yet
+        self.reserved = 0
+
+    # -- set up once for the world -------------------------------------------------------------------------------------------
+    def set_environment(self, env):
+        if self._group == 0:
+            self._e.world.set_environment(env)
+
+    def reserve(self, n):
+        self.reserved = int(n)   # (the ensemble reserves the sum once every member has said what it expects)
+
+    def collisions_enable(self, enabled=True, method=hostlib.NEIGHBOURS_AUTO, event_capacity=0):
+        if self._group == 0:
+            self._e.world.collisions_enable(enabled, method=method, event_capacity=event_capacity)
+
+    def tracks_enable(self, *args, **kwargs):
+        if self._group == 0:
+            self._e.world.tracks_enable(*args, **kwargs)
+            self._e._log_room = int(kwargs.get("sample_capacity", 0))
+
+    def tracks_set_clock(self, next_tick):
+        pass                     # (the members tick in step: the ensemble keeps the world's one clock)
+
+    # -- robots -----------------------------------------------------------------------------------------------------------------
+    def add_robot(self, mean0, prior_diag, dt, radius, path=None, order_key=None, ghost=False):
+        # the order key unique across the members, the order within a member as it was
+        key = int(order_key) * len(self._e.members_worlds) + self._group
+        if key >= 2 ** 64:
+            raise ValueError("order key too large for an ensemble of this size")
+        wid = self._e.world.add_robot(mean0, prior_diag, dt, radius, path=path, order_key=key, ghost=ghost, group=self._group)
+        self._e._owner[wid] = (self._group, len(self.ids))
+        self.ids.append(wid)
+        return len(self.ids) - 1
+
+    def mission_set(self, robot, *args, **kwargs):
+        self._e.world.mission_set(self.ids[robot], *args, **kwargs)
+
+    def message_counts(self, robot):
+        return self._e.world.message_counts(self.ids[robot])
+
+    def mission_read(self):
+        tr, tg, fin = self._e.world.mission_read()
+        return tr[self.ids], tg[self.ids], fin[self.ids]
+
+    def synchronize(self):
+        self._e.world.synchronize()
+
+    # -- the device's logs, routed -----------------------------------------------------------------------------------------------
+    def collisions_read(self, first=0):
+        dropped = self._e._drain_collisions()
+        ev = self.coll_events[int(first):]
+        out = np.zeros(len(ev), hostlib.collision_event_dtype())
+        for k, e in enumerate(ev):
+            out[k] = e
+        return out, len(self.coll_events), dropped, None
+
+    def tracks_take(self, capacity=None, travelled=True):
+        dropped, dist = self._e._drain_tracks()
+        mine, self.samples = self.samples, []
+        out = np.zeros(len(mine), hostlib.track_sample_dtype())
+        for k, s in enumerate(mine):
+            out[k] = s
+        return out, len(mine), dropped, (dist[self.ids] if len(self.ids) else np.zeros(0))
+
+    # -- the ensemble's -----------------------------------------------------------------------------------------------------------
+    def mission_tick_begin(self, *args, **kwargs):
+        raise RuntimeError("a member of an Ensemble does not tick on its own: Ensemble.tick()")
+
+    mission_tick_end = mission_tick_begin
+
+
+class Member:
+    """One run of an Ensemble: `sim` is its Simulation; export() and metrics() give what the same scenario gives alone — frozen
+    when the member was retired (its mission over, or its time up)"""
+
+    def __init__(self, sim, view):
+        self.sim, self._view = sim, view
+        self.retired = False
+        self._export = self._metrics = None
+
+    def export(self):
+        return copy.deepcopy(self._export) if self.retired else self.sim.export()
+
+    def metrics(self):
+        return copy.deepcopy(self._metrics) if self.retired else self.sim.metrics()
+
+    def elapsed(self):
+        return self.sim.elapsed()
+
+    @property
+    def tick_no(self):
+        return self.sim.tick_no
+
+
+class Ensemble:
+    def __init__(self, scenarios, world, **simulation_options):
+        """scenarios: one scenario dict per member (config.load_scenario, tests/golden/scenarios.json); member m's robots are in
+        group m of `world`, a fresh World made with config.world_params of any of them.  The members may differ in
+        simulation.prng-seed, robot.communication.failure-rate (and max-time) and in their formations; everything the world holds
+        once must be equal (ValueError names the first key that differs).  simulation_options go to every member's Simulation.
+        This version runs device missions with device robot-robot collisions and device trackers — the default export;
+        environment_collisions, goal_areas, device_metrics, global_planner (and so rrt-star formations) raise NotImplementedError."""
+        scenarios = list(scenarios)
+        if not scenarios:
+            raise ValueError("an Ensemble needs at least one scenario")
+        if len(scenarios) > hostlib.GROUPS_MAX:
+            raise ValueError(f"an Ensemble has at most {hostlib.GROUPS_MAX} members")
+        for opt in UNSUPPORTED:
+            if simulation_options.get(opt):
+                raise NotImplementedError(f"Ensemble: {opt} is not supported in this version (device missions, device robot-robot collisions and "
+                                          "device trackers are)")
+        for opt in ("device_missions", "device_collisions", "device_trackers"):
+            if simulation_options.get(opt) is False:
+                raise NotImplementedError(f"Ensemble: {opt}=False is not supported in this version (the members share the device's passes)")
+        for m, sc in enumerate(scenarios):
+            if any(f["planning-strategy"] != "only-local" for f in sc["formation"]["formations"]):
+                raise NotImplementedError(f"Ensemble: member {m} has an rrt-star formation; the global planner is not supported in this version")
+        first = _shared_settings(scenarios[0])
+        for m, sc in enumerate(scenarios[1:], 1):
+            for (key, a), (_, b) in zip(first, _shared_settings(sc)):
+                if a != b:
+                    raise ValueError(f"Ensemble: member {m} differs from member 0 in {key} ({b!r} against {a!r}): the world holds it once")
+        if not hasattr(world, "mission_tick_begin_groups"):
+            raise NotImplementedError("Ensemble needs an engine world (robot groups)")
+        self.world = world
+        self._owner = {}          # world id -> (member, member id)
+        self._coll_cursor = 0     # events of the world's collision log already routed
+        self._coll_dropped = 0
+        self._log_room = 0        # room of the device's sample log (what the first member enabled the trackers with)
+        self._log_bound = 0       # samples the log holds at the most since it was last drained
+        self._dist = np.zeros(0)
+        self._clock = None        # the tick the device's tracker clock names
+        self.tick_no = 0
+        self.members_worlds = [_MemberWorld(self, m) for m in range(len(scenarios))]
+        self.members = [Member(Simulation(sc, view, **simulation_options), view) for sc, view in zip(scenarios, self.members_worlds)]
+        s0 = self.members[0].sim
+        if not (s0.dev and s0._dev_coll and s0._dev_trk):
+            raise NotImplementedError("Ensemble needs device missions, device collisions and device trackers")
+        world.reserve(sum(v.reserved for v in self.members_worlds))
+
+    # -- the device's logs: drained once, routed by robot id ------------------------------------------------------------------------
+    def _drain_collisions(self):
+        ev, total, dropped = self.world.collisions_read(self._coll_cursor)[:3]
+        self._coll_cursor = total
+        for e in ev:
+            (m, a), (m2, b) = self._owner[int(e["robot_a"])], self._owner[int(e["robot_b"])]
+            assert m == m2, "robots of two members collided"
+            self.members_worlds[m].coll_events.append((e["pass"], a, b, e["mins"], e["maxs"]))
+        return dropped
+
+    def _drain_tracks(self):
+        if self._clock is None:   # (no robot has ticked yet)
+            return 0, np.zeros(len(self._owner))
+        samples, _, dropped, dist = self.world.tracks_take()
+        self._log_bound = 0
+        for s in samples:
+            m, r = self._owner[int(s["robot"])]
+            self.members_worlds[m].samples.append((s["tick"], r, s["span_ticks"], s["position"], s["velocity"]))
+        return dropped, dist
+
+    # -- a tick: the existing tick with the world-wide calls made once ---------------------------------------------------------------
+    def tick(self):
+        active = [m for m in self.members if not m.retired]
+        for m in active:          # every member applies its spawns, in member order
+            m.sim._apply_plans()
+            m.sim._spawn()
+            m.sim._plan()
+        ticking = [m for m in active if m.sim.robots]
+        if ticking:
+            w, s0 = self.world, ticking[0].sim
+            alive = sum(1 for m in ticking for r in m.sim.robots if r["alive"])
+            if self._log_room and self._log_bound + alive > self._log_room:   # (a robot gives at most one sample per tick)
+                dropped, _ = self._drain_tracks()
+                if dropped:
+                    raise hostlib.MgxError(f"the device's tracker log was full: {dropped} samples were not stored")
+            self._log_bound += alive
+            if self._clock != self.tick_no:
+                w.tracks_set_clock(self.tick_no)
+            for m in ticking:
+                m.sim._tick_device_before()
+            numbers = np.array([m.sim.next_number for m in self.members], dtype=np.uint64)
+            numbers, stats, fin = w.mission_tick_begin_groups(s0.comms_radius, numbers, despawn_finished=s0.despawn, method=s0.method)
+            finished = [[] for _ in self.members]
+            for wid in fin:
+                g, r = self._owner[int(wid)]
+                finished[g].append(r)
+            antennas = None
+            for m in ticking:     # every member makes its own draws from its own stream, in its own robot order
+                g = m._view._group
+                ant = m.sim._tick_device_between(int(numbers[g]), int(stats[g, 0]), int(stats[g, 1]), finished[g])
+                if ant is not None:
+                    if antennas is None:
+                        antennas = np.ones(len(self._owner), dtype=np.uint8)
+                    antennas[m._view.ids] = ant
+            w.mission_tick_end(s0.steps, float(s0.max_speed), float(s0.dt32), antennas=antennas)
+            self._clock = self.tick_no + 1
+        for m in active:
+            m.sim.tick_no += 1
+        self.tick_no += 1
+
+    def _retire(self, m):
+        """the member's run is over: trackers flushed, export and metrics frozen, its remaining robots out of the world"""
+        m.sim._flush_trackers(synchronise=True)
+        m.sim._tracks()
+        m._export, m._metrics = m.sim.export(), m.sim.metrics()
+        m.retired = True
+        for r in m.sim.robots:
+            if r["alive"]:
+                self.world.remove_robot(m._view.ids[r["id"]])
+
+    def run(self, max_ticks=None, max_time=None):
+        """until every member is retired: its mission finished (Simulation.finished), its max-time (the scenario's own, or
+        max_time) reached, or max_ticks ticks made — the bounds of Simulation.run, per member"""
+        def over(m):
+            limit = m.sim.cfg["simulation"]["max-time"] if max_time is None else max_time
+            return m.sim.finished() or not m.sim.elapsed() < limit or (max_ticks is not None and m.sim.tick_no >= max_ticks)
+        while True:
+            for m in self.members:
+                if not m.retired and over(m):
+                    self._retire(m)
+            if all(m.retired for m in self.members):
+                return self
+            self.tick()

@@ -29,6 +29,8 @@ GLOBAL_PATH_RESET_TRACKING, GLOBAL_PATH_ROUTE, GLOBAL_PATH_ACTIVATE = 1, 2, 4  #
 RESIDENT_NONE, RESIDENT_RAN, RESIDENT_DECLINED = 0, 1, 2
 # mgx_last_search: the kernel a neighbour search launched last
 SEARCH_NONE, SEARCH_TWO_PASS_PAIRS, SEARCH_TWO_PASS_GRID, SEARCH_ROWS_PAIRS_4, SEARCH_ROWS_PAIRS_2, SEARCH_ROWS_GRID_16, SEARCH_ROWS_GRID_32 = -1, 0, 1, 2, 3, 4, 5
+SEARCH_ROWS_GROUPS = 6  # a grouped world's search (include/mgx.h, ROBOT GROUPS)
+GROUPS_MAX = 4096       # MGX_GROUPS_MAX
 HALO_PUSH, HALO_WAIT = 1, 2
 HINT_NEXT_STARTS_EXTERNAL = 1
 
@@ -64,7 +66,7 @@ class RobotDesc(C.Structure):
         ("radius", C.c_double),
         ("order_key", C.c_uint64),
         ("ghost", C.c_uint32),
-        ("reserved", C.c_uint32),
+        ("group", C.c_uint32),
     ]
 
 
@@ -144,6 +146,7 @@ SYMBOLS = {
     "mgx_neighbours": (C.c_int, [_V, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                  C.POINTER(C.c_uint64)]),
     "mgx_update_topology": (C.c_int, [_V, C.c_void_p, C.c_float, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    "mgx_update_topology_groups": (C.c_int, [_V, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mgx_connections": (C.c_int, [_V, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_iterate": (C.c_int, [_V, C.c_char_p, C.c_uint32]),
     "mgx_batch_begin": (C.c_int, [_V]),
@@ -200,6 +203,7 @@ SYMBOLS = {
     "mgx_mission_tick": (C.c_int, [_V, C.c_float, C.c_uint32, C.POINTER(C.c_uint64), C.c_int32, C.c_void_p, C.c_double, C.c_double,
                                    C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_mission_tick_begin": (C.c_int, [_V, C.c_float, C.c_uint32, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint32)]),
+    "mgx_mission_tick_begin_groups": (C.c_int, [_V, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]),
     "mgx_mission_run": (C.c_int, [_V, C.c_void_p]),
     "mgx_mission_tick_end": (C.c_int, [_V, C.c_void_p, C.c_double, C.c_double, C.c_char_p, C.c_uint32]),
     "mgx_mission_finished": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

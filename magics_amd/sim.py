@@ -666,12 +666,16 @@ class Simulation:
         return (not self._dev_trk or not self._dev_coll or (self._env_coll and not self._dev_env_coll)
                 or (self._goal_areas is not None and not self._dev_goals))
 
-    def _tick_device(self):
-        w = self.w
+    # A device tick in three parts around the two world-wide calls (mission_tick_begin, mission_tick_end): _tick_device makes them
+    # for this run alone; an Ensemble (ensemble.py) makes each of them ONCE for all its members and runs the parts per member
+    def _tick_device_before(self):
         self._tracks_room(1, sum(1 for r in self.robots if r["alive"]))
         self._goal_clock()
-        self.next_number, created, deleted, fin = w.mission_tick_begin(self.comms_radius, self.next_number, despawn_finished=self.despawn,
-                                                                       method=self.method)
+
+    def _tick_device_between(self, next_number, created, deleted, fin):
+        """what mission_tick_begin gave -> the run's bookkeeping and this tick's comms draws; the antenna bytes for mission_tick_end
+        (one per robot of this run; None: nothing fails)"""
+        self.next_number = next_number
         self._flush_trackers()
         if created or deleted:
             self.events.append((self.tick_no, created, deleted))
@@ -690,8 +694,14 @@ class Simulation:
                 ant = np.ones(len(self.robots), dtype=np.uint8)
                 ant[[r["id"] for r in live]] = active
         moving = [r for r in live if not r["completed"] and not r["idle"]]
+        self._pending_track = (moving, (self.tick_no + 1) * self.dt_ns * 1e-9, live, self.tick_no)  # (read once mission_tick_end has run)
+        return ant
+
+    def _tick_device(self):
+        w = self.w
+        self._tick_device_before()
+        ant = self._tick_device_between(*w.mission_tick_begin(self.comms_radius, self.next_number, despawn_finished=self.despawn, method=self.method))
         w.mission_tick_end(self.steps, float(self.max_speed), float(self.dt32), antennas=ant)
-        self._pending_track = (moving, (self.tick_no + 1) * self.dt_ns * 1e-9, live, self.tick_no)
 
     def tick(self):
         w = self.w

@@ -110,7 +110,8 @@ class World:
         d = _Desc(env)
         self._chk(self._L.mgx_world_set_environment(self._w, C.byref(d.desc)))
 
-    def add_robot(self, mean0, prior_diag, dt, radius, path=None, order_key=None, ghost=False):
+    def add_robot(self, mean0, prior_diag, dt, radius, path=None, order_key=None, ghost=False, group=0):
+        """group: the independent run the robot belongs to (include/mgx.h, ROBOT GROUPS); 0: an ungrouped world's one run."""
         mean0 = _f64(mean0)
         K = mean0.shape[0]
         prior_diag = _f64(prior_diag, (K,))
@@ -128,6 +129,9 @@ class World:
         self._next_key = max(self._next_key, int(order_key) + 1)
         d.order_key = int(order_key)
         d.ghost = 1 if ghost else 0
+        if not 0 <= int(group) < 2 ** 32:
+            raise ValueError("group must be a non-negative 32-bit number")
+        d.group = int(group)
         rid = C.c_int32(-1)
         self._chk(self._L.mgx_robot_add(self._w, C.byref(d), C.byref(rid)))
         self._n_ids = max(self._n_ids, rid.value + 1)
@@ -191,6 +195,17 @@ class World:
         stats = (C.c_uint32 * 2)()
         self._chk(self._L.mgx_update_topology(self._w, pos.ctypes.data, float(radius), method, C.byref(nxt), stats))
         return nxt.value, stats[0], stats[1]
+
+    def update_topology_groups(self, positions, radius, next_numbers, method=hostlib.NEIGHBOURS_AUTO):
+        """update_topology with one RobotNumberGenerator per group (mgx_update_topology_groups): next_numbers [n_groups].
+        Returns (next robot numbers [n_groups] u64, stats [n_groups, 2] u32: connections created, pairs deleted)."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        nxt = None if next_numbers is None else np.array(next_numbers, dtype=np.uint64).reshape(-1)
+        n_groups = 0 if nxt is None else len(nxt)
+        stats = np.zeros((max(n_groups, 1), 2), dtype=np.uint32)
+        self._chk(self._L.mgx_update_topology_groups(self._w, pos.ctypes.data, float(radius), int(method), n_groups,
+                                                     None if nxt is None else nxt.ctypes.data, stats.ctypes.data))
+        return nxt, stats[:n_groups]
 
     def connections(self, robot):
         n = C.c_uint32()
@@ -391,6 +406,22 @@ class World:
             k = C.c_uint32()
             self._chk(self._L.mgx_mission_finished(self._w, fin.ctypes.data, st[2], C.byref(k)))
         return nn.value, st[0], st[1], fin
+
+    def mission_tick_begin_groups(self, comms_radius, next_numbers, despawn_finished=True, method=hostlib.NEIGHBOURS_AUTO):
+        """mission_tick_begin with one RobotNumberGenerator per group (mgx_mission_tick_begin_groups): next_numbers [n_groups].
+        Returns (next robot numbers [n_groups] u64, stats [n_groups, 3] u32: connections created, pairs deleted, missions
+        completed, ids of the robots of all groups whose mission completed in this tick, ascending)."""
+        nxt = None if next_numbers is None else np.array(next_numbers, dtype=np.uint64).reshape(-1)
+        n_groups = 0 if nxt is None else len(nxt)
+        stats = np.zeros((max(n_groups, 1), 3), dtype=np.uint32)
+        self._chk(self._L.mgx_mission_tick_begin_groups(self._w, float(comms_radius), int(method), n_groups,
+                                                        None if nxt is None else nxt.ctypes.data, 1 if despawn_finished else 0, stats.ctypes.data))
+        n_fin = int(stats[:n_groups, 2].sum())
+        fin = np.zeros(n_fin, dtype=np.int32)
+        if n_fin:
+            k = C.c_uint32()
+            self._chk(self._L.mgx_mission_finished(self._w, fin.ctypes.data, n_fin, C.byref(k)))
+        return nxt, stats[:n_groups], fin
 
     def mission_tick_end(self, steps, max_speed, delta_t, antennas=None):
         ant = None if antennas is None else np.ascontiguousarray(antennas, dtype=np.uint8)

@@ -111,7 +111,7 @@ impl World {
             radius,
             order_key,
             ghost: 0,
-            reserved: 0,
+            group: 0,
         };
         let mut id = -1;
         check(unsafe { sys::mgx_robot_add(self.raw, &desc, &mut id) })?;

@@ -1,0 +1,112 @@
+"""Many scenario runs as ONE Ensemble against the same runs one after another (profiles/ensemble.md).
+
+Two workloads, both from tests/golden/scenarios.json: the reference's communications-failure experiment as its script runs it — 5
+seeds x 8 failure rates, 21 robots per run: 40 members — and the Environment Obstacles Experiment with 32 seeds.  For each:
+  ensemble   the members as robot groups of one world (magics_amd/ensemble.py): wall time, member ticks per second, the kernel the
+             neighbour search ran, the resident schedule launches (ran / declined);
+  solo       the same members one after another, each a Simulation on a world of its own: run(chunk=1) and run(chunk=256).
+Every figure is a host clock around a whole run that ends in a device synchronisation, world creation and set-up included (that is
+what a sweep of runs pays); one untimed warm-up run in front, --reps timed repetitions (default 5): median, min, max.
+The solo part needs nothing of the ensemble: `--solo` runs it alone, also from the root of an older checkout
+(python <this file> --solo), which is how the figures of the parent commit are taken.
+
+usage: python tools/ensemble_bench.py [--solo | --ensemble] [--reps N] [--max-time S] [--out FILE.json]"""
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, ".")
+from magics_amd import World, config, sim  # noqa: E402
+
+args = sys.argv[1:]
+
+
+def option(flag, kind, default):
+    if flag in args:
+        i = args.index(flag)
+        v = kind(args[i + 1])
+        del args[i:i + 2]
+        return v
+    return default
+
+
+reps, max_time, out_file = option("--reps", int, 5), option("--max-time", float, 30.0), option("--out", str, None)
+only_solo, only_ensemble = "--solo" in args, "--ensemble" in args
+with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
+    known = json.load(f)
+
+
+def members(name, seeds, rates):
+    out = []
+    for rate in rates:
+        for seed in seeds:
+            sc = copy.deepcopy(known[name])
+            sc["config"]["simulation"]["prng-seed"] = seed
+            if rate is not None:
+                sc["config"]["robot"]["communication"]["failure-rate"] = rate
+            out.append(sc)
+    return out
+
+
+WORKLOADS = {
+    "comms-failure 5 seeds x 8 rates": lambda: members("Communications Failure Experiment", [0, 31, 227, 252, 805], [0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7]),
+    "environment-obstacles 32 seeds": lambda: members("Environment Obstacles Experiment", list(range(100, 132)), [None]),
+}
+
+
+def spread(xs):
+    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4), "n": len(xs)}
+
+
+def run_solo(scs, chunk):
+    ticks = 0
+    t0 = time.perf_counter()
+    for sc in scs:
+        s = sim.Simulation(copy.deepcopy(sc), World(config.world_params(sc["config"])))
+        s.run(max_time=max_time, chunk=chunk)
+        s.w.synchronize()
+        ticks += s.tick_no
+    return time.perf_counter() - t0, ticks, {}
+
+
+def run_ensemble(scs):
+    from magics_amd import ensemble
+    t0 = time.perf_counter()
+    e = ensemble.Ensemble([copy.deepcopy(sc) for sc in scs], World(config.world_params(scs[0]["config"])))
+    e.run(max_time=max_time)
+    e.world.synchronize()
+    wall = time.perf_counter() - t0
+    ran, declined, _ = e.world.resident_stats()
+    lingered, posted = e.world.linger_stats()[:2]
+    # (mgx_last_search names the kernel of the last search that launched one: the last tick with robots alive)
+    return wall, sum(m.tick_no for m in e.members), {"world_ticks": e.tick_no, "robots": e.world.num_robots()[0], "search_kernel": e.world.last_search()[0],
+                                                      "resident_launches": ran, "resident_declined": declined, "lingered_launches": lingered,
+                                                      "schedules_posted": posted}
+
+
+result = {"max_time": max_time, "reps": reps, "workloads": {}}
+for name, make in WORKLOADS.items():
+    scs = make()
+    row = {"members": len(scs)}
+    forms = []
+    if not only_solo:
+        forms.append(("ensemble", lambda: run_ensemble(scs)))
+    if not only_ensemble:
+        forms += [("solo_chunk1", lambda: run_solo(scs, 1)), ("solo_chunk256", lambda: run_solo(scs, 256))]
+    for form, run in forms:
+        run()   # warm-up: code objects, the environment's rasteriser, the allocator
+        walls, rates, extra, ticks = [], [], {}, 0
+        for _ in range(reps):
+            wall, ticks, extra = run()
+            walls.append(wall)
+            rates.append(ticks / wall)
+        row[form] = {"wall_s": spread(walls), "member_ticks_per_s": spread(rates), "member_ticks": ticks, **extra}
+        print(json.dumps({name: {form: row[form]}}), flush=True)
+    result["workloads"][name] = row
+if out_file:
+    os.makedirs(os.path.dirname(out_file) or ".", exist_ok=True)
+    with open(out_file, "w", encoding="utf-8") as f:
+        json.dump(result, f, indent=1)
