@@ -105,6 +105,16 @@ typedef struct mgx_robot_desc {
  *     search is ONE one-pass kernel whatever the method, MGX_SEARCH_ROWS_GROUPS: a workgroup serves sixteen robots of one group and
  *     stages and tests that group's positions only, so a search costs the sum of the squared group sizes, not the square of the
  *     world's size.  A group of more than 4096 robots in one query is refused (MGX_ERR_INVALID);
+ *   * the comms radius is per group with mgx_neighbours_groups, mgx_update_topology_groups_radii and
+ *     mgx_mission_tick_begin_groups_radii: radii [n_groups], by group id; a pair is tested against the radius of ITS group, each
+ *     radius meaning what the scalar means (NaN: everybody of the group in range; zero, negative: as before).  The kernel and the
+ *     number of launches are the same: a workgroup reads its group's threshold from a table the host keeps beside the query's
+ *     group lists and uploads again only when a radius changes or robots join or leave the query — not per search.  The search
+ *     mgx_mission_tick_end enqueues for the coming tick uses the radii of the last _begin; the next _begin takes those rows only if
+ *     every radius is still the one they were searched with, and searches again otherwise.  radii NULL, a robot whose group is
+ *     not below n_groups, n_groups outside 1 .. MGX_GROUPS_MAX: MGX_ERR_INVALID, nothing changes.  On an ungrouped world
+ *     (n_groups 1) the call is the scalar call with radii[0], on the kernels that one runs.  The calls with ONE radius
+ *     (mgx_update_topology_groups, mgx_mission_tick_begin_groups) are these with all radii equal;
  *   * robots of different groups never collide (mgx_collisions_update, and the pass at every tick's end).  Within a group the
  *     predicate, the Free / Colliding state machine, the event order, the per-robot counts and the overflow rules are unchanged;
  *   * the RobotNumberGenerator, whose numbers enter the arithmetic of the inter-robot factors, is per group with
@@ -213,6 +223,12 @@ int mgx_update_topology(mgx_world *w, const float *positions_xyz, float radius, 
  * (n_groups >= 1, everything in group 0). */
 int mgx_update_topology_groups(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint32_t n_groups,
                                uint64_t *number_next, uint32_t *stats);
+/* ... and one comms radius per group (ROBOT GROUPS above): radii [n_groups], by group id. */
+int mgx_update_topology_groups_radii(mgx_world *w, const float *positions_xyz, const float *radii, uint32_t method,
+                                     uint32_t n_groups, uint64_t *number_next, uint32_t *stats);
+/* mgx_neighbours with one radius per group: radii [n_groups], by group id (ROBOT GROUPS above). */
+int mgx_neighbours_groups(mgx_world *w, const float *positions_xyz, const float *radii, uint32_t n_groups, uint32_t method,
+                          int32_t *row_ptr, int32_t *neighbours_out, uint64_t capacity, uint64_t *needed);
 /* RobotConnections::robots_connected_with of one robot (robot.rs:515-531), ascending.
  * others may be NULL to query the count. */
 int mgx_connections(mgx_world *w, int32_t robot, int32_t *others, uint32_t capacity, uint32_t *n);
@@ -506,6 +522,10 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
  * mgx_mission_tick_end; mgx_mission_finished lists the robots of all groups, ascending ids. */
 int mgx_mission_tick_begin_groups(mgx_world *w, float comms_radius, uint32_t method, uint32_t n_groups, uint64_t *number_next,
                                   int32_t despawn_finished, uint32_t *stats);
+/* ... and one comms radius per group: comms_radii [n_groups], by group id.  A radius that is not the one of the tick before
+ * discards the rows that tick's _end searched ahead: this tick searches again, with the new radii. */
+int mgx_mission_tick_begin_groups_radii(mgx_world *w, const float *comms_radii, uint32_t method, uint32_t n_groups,
+                                        uint64_t *number_next, int32_t despawn_finished, uint32_t *stats);
 int mgx_mission_finished(mgx_world *w, int32_t *robots, uint32_t capacity, uint32_t *n);
 /* MANY ticks in one call: what a headless run does between two spawns (the reference's FixedUpdate chain tick after tick,
  * robot.rs:85-108, with update_failed_comms' draws in between) without the caller's interpreter in the loop —

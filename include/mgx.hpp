@@ -212,6 +212,22 @@ public:
         }
         return out;
     }
+    // ... with one comms radius per group (comms_radii.size() == numbers.size())
+    std::vector<std::pair<uint32_t, uint32_t>> update_topology_groups(const std::vector<std::array<float, 3>> &translations,
+                                                                      const std::vector<float> &comms_radii, std::vector<RobotNumberGenerator> &numbers) {
+        if (comms_radii.size() != numbers.size()) throw std::invalid_argument("one comms radius per group");
+        std::vector<uint64_t> next(numbers.size());
+        for (size_t g = 0; g < numbers.size(); g++) next[g] = numbers[g].next_value;
+        std::vector<uint32_t> stats(2 * numbers.size() + 2, 0u);
+        check(mgx_update_topology_groups_radii(w_, translations[0].data(), comms_radii.data(), MGX_NEIGHBOURS_AUTO, (uint32_t)numbers.size(), next.data(),
+                                               stats.data()));
+        std::vector<std::pair<uint32_t, uint32_t>> out(numbers.size());
+        for (size_t g = 0; g < numbers.size(); g++) {
+            numbers[g].next_value = next[g];
+            out[g] = {stats[2 * g], stats[2 * g + 1]};
+        }
+        return out;
+    }
     // iterate_gbp_v2 (robot.rs:1769-1861)
     void iterate_gbp_v2(const std::vector<GbpScheduleAtIteration> &sched) {
         std::vector<uint8_t> steps(sched.size());

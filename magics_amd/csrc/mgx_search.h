@@ -8,6 +8,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 #include <vector>
 
 #include "../../include/mgx.h"
@@ -29,6 +30,24 @@ static_assert(pairs_rows_lds(ROWS_MAX_N) <= 48 * 1024, "the one-pass search's la
 static_assert(NEIGHBOURS_PREV_STRIDE == 1 + GRID_ROWS_MAX_CAP && GRID_M <= ROWS_MAX_N && PAIRS_2_MAX_N <= ROWS_MAX_N, "dispatch constants");
 
 inline bool usable_radius(float radius) { return std::isfinite(radius) && radius > 0.f; }  // (else every pair has to see the predicate)
+
+// what the one-pass kernels compare squared distances with (in_comms_range_sq, mgx_topology.hip): the largest f32 s with
+// RN_f32(sqrt(s)) <= radius; NaN radius -> NaN (everybody in range), radius < 0 -> negative (nobody but NaN distances)
+inline float squared_threshold(float radius) {
+    if (radius != radius) return radius;
+    if (radius < 0.f) return -1.f;
+    if (std::isinf(radius)) return radius;
+    auto root = [](float s) { return (float)std::sqrt((double)s); };
+    float s = (float)((double)radius * (double)radius);
+    if (std::isinf(s)) s = std::numeric_limits<float>::max();
+    while (root(s) > radius) s = std::nextafter(s, -1.f);
+    for (;;) {
+        const float up = std::nextafter(s, std::numeric_limits<float>::infinity());
+        if (std::isinf(up) || root(up) > radius) break;
+        s = up;
+    }
+    return s;
+}
 
 // the kernel (MGX_SEARCH_*) that answers a query of n robots — the one launched LAST where a search takes several launches.
 // grouped: the world has robots of a non-zero group (include/mgx.h, ROBOT GROUPS) — one kernel, whatever the method and the size
@@ -85,15 +104,24 @@ inline void compact_to_world(const std::vector<int> &alive, int n_all, std::vect
 //   seg      [n_segments + 1] where each non-empty group's members start (a group nobody of the query is in has no segment)
 //   wg       [n_workgroups][2] (segment, first member of the slice within the segment): GROUP_ROBOTS robots of one group each
 //   largest  the largest segment: sizes the kernel's LDS
+//   thr      [n_segments] the squared threshold (squared_threshold) of each SEGMENT's group: the comms radius is per group, and a
+//            workgroup reads the one of its segment — listed by segment like seg, so a group without a segment shifts nobody's
+//            (group_thresholds, below: filled when a radius changes or the segments do; seg_group and seg_radius stay on the host)
 struct GroupTables {
     std::vector<int32_t> members, seg, wg;
     int largest = 0;
+    std::vector<uint32_t> seg_group;  // [n_segments] the group every segment lists
+    std::vector<float> seg_radius;    // [n_segments] the radius thr was made from
+    std::vector<float> thr;
     int n_segments() const { return seg.empty() ? 0 : (int)seg.size() - 1; }
     int n_workgroups() const { return (int)(wg.size() / 2); }
     // the three tables behind one another, as the device holds them: [members n] [seg n_segments + 1] [wg 2 n_workgroups]
     size_t off_seg() const { return members.size(); }
     size_t off_wg() const { return members.size() + seg.size(); }
     size_t words() const { return members.size() + seg.size() + wg.size(); }
+    // ... and the thresholds behind them (their bits, one word each): [thr n_segments]
+    size_t off_thr() const { return words(); }
+    size_t words_with_thr() const { return words() + thr.size(); }
 };
 // group_of_query [n]: the group of every robot of the query, in query order.  false: a group has more than ROWS_MAX_N robots (no
 // workgroup holds its positions) — t.largest says how many
@@ -104,16 +132,32 @@ inline bool group_tables(const uint32_t *group_of_query, int n, GroupTables &t) 
     t.seg.assign(1, 0);
     t.wg.clear();
     t.largest = 0;
+    t.seg_group.clear();
+    t.seg_radius.clear();  // (the segments are new ones: group_thresholds fills thr again)
+    t.thr.clear();
     for (int q = 0; q < n;) {
         int e = q + 1;
         while (e < n && group_of_query[t.members[(size_t)e]] == group_of_query[t.members[(size_t)q]]) e++;
         const int32_t segment = (int32_t)t.seg.size() - 1;
         for (int first = 0; first < e - q; first += GROUP_ROBOTS) { t.wg.push_back(segment); t.wg.push_back(first); }
         t.seg.push_back(e);
+        t.seg_group.push_back(group_of_query[t.members[(size_t)q]]);
         t.largest = std::max(t.largest, e - q);
         q = e;
     }
     return t.largest <= ROWS_MAX_N;
+}
+// The thresholds of the tables' segments: radii [n_radii] by GROUP id (a group beyond them, or radii null: `radius`).  false: they
+// are the ones the tables hold already (the same radii bit for bit, a NaN included) — nothing to upload
+inline bool group_thresholds(GroupTables &t, const float *radii, size_t n_radii, float radius) {
+    const size_t ns = t.seg_group.size();
+    std::vector<float> now(ns);
+    for (size_t s = 0; s < ns; s++) now[s] = radii && t.seg_group[s] < n_radii ? radii[t.seg_group[s]] : radius;
+    if (t.thr.size() == ns && t.seg_radius.size() == ns && (ns == 0 || memcmp(now.data(), t.seg_radius.data(), sizeof(float) * ns) == 0)) return false;
+    t.thr.resize(ns);
+    for (size_t s = 0; s < ns; s++) t.thr[s] = squared_threshold(now[s]);
+    t.seg_radius.swap(now);
+    return true;
 }
 
 // ---- the launchers (mgx_topology.hip) ---------------------------------------------------------------------------------------------
@@ -126,9 +170,9 @@ hipError_t neighbours_fill(const float *pos, int n, float radius, bool grid, uin
                            hipStream_t s);
 hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s,
                            int32_t *prev = nullptr, int prev_valid = 0, bool *flagged = nullptr, int32_t *ran = nullptr);
-// a grouped world's search: tables = GroupTables on the device (members, seg, wg behind one another), largest <= ROWS_MAX_N
+// a grouped world's search: tables = GroupTables on the device (members, seg, wg, thr behind one another), largest <= ROWS_MAX_N
 hipError_t neighbours_rows_groups(const float *pos, int n, const int32_t *members, const int32_t *seg, const int32_t *wg, int n_workgroups,
-                                  int largest, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, int32_t *ran = nullptr);
+                                  int largest, const float *thr, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, int32_t *ran = nullptr);
 #endif
 
 }  // namespace mgx

@@ -178,12 +178,17 @@ __global__ void __launch_bounds__(ROWS_BLOCK) k_pairs_rows(const float *__restri
 // only those — 256 candidates per pass, the same quad exchange of hit masks — and writes rows of QUERY indices (members[..]),
 // ascending because the members are.  The cost of a search is the sum of the squared group sizes.  A row that outgrows `cap` keeps
 // counting; the host repeats the search with more room.
+// The comms radius is per GROUP: thr [n_segments] holds every segment's squared threshold (GroupTables::thr), and a workgroup — a
+// slice of one segment — tests against its own.  The segment is the same for the whole workgroup, so the threshold is one scalar
+// load beside the two of seg: no lane pays for it and nothing diverges.
 __global__ void __launch_bounds__(64) k_group_rows(const float *__restrict__ pos, const int32_t *__restrict__ members,
-                                                   const int32_t *__restrict__ seg, const int32_t *__restrict__ wg, float s_max, int32_t cap,
-                                                   int32_t *__restrict__ cnt, int32_t *__restrict__ rows) {
+                                                   const int32_t *__restrict__ seg, const int32_t *__restrict__ wg,
+                                                   const float *__restrict__ thr, int32_t cap, int32_t *__restrict__ cnt,
+                                                   int32_t *__restrict__ rows) {
     constexpr int L = 4;
     extern __shared__ float lds_pos[];
     const int segment = wg[2 * blockIdx.x], first = wg[2 * blockIdx.x + 1];
+    const float s_max = thr[segment];
     const int m0 = seg[segment], ng = seg[segment + 1] - m0;  // this group's members: members[m0 .. m0 + ng)
     const int32_t *mem = members + m0;
     const int npad = (ng + 3) & ~3;
@@ -401,23 +406,6 @@ __global__ void __launch_bounds__(GRID_BLOCK) k_grid_rows(const float *__restric
     }
 }
 
-// the largest f32 s with RN_f32(sqrt(s)) <= radius (see in_comms_range_sq); NaN radius -> NaN (everybody in range), radius < 0 ->
-// negative (nobody but NaN distances)
-static float squared_threshold(float radius) {
-    if (radius != radius) return radius;
-    if (radius < 0.f) return -1.f;
-    if (std::isinf(radius)) return radius;
-    auto root = [](float s) { return (float)std::sqrt((double)s); };
-    float s = (float)((double)radius * (double)radius);
-    if (std::isinf(s)) s = std::numeric_limits<float>::max();
-    while (root(s) > radius) s = std::nextafter(s, -1.f);
-    for (;;) {
-        const float up = std::nextafter(s, std::numeric_limits<float>::infinity());
-        if (std::isinf(up) || root(up) > radius) break;
-        s = up;
-    }
-    return s;
-}
 // LDS of one workgroup of the grid search (k_grid_rows) for n robots and rows of up to `cap` entries; its workgroups: one per 64 robots
 static size_t neighbours_rows_lds(int n, int32_t cap) {
     const size_t npad = (size_t)((n + 3) & ~3);
@@ -464,11 +452,11 @@ hipError_t neighbours_rows(const float *pos, int n, float radius, int32_t cap, i
 
 // One launch of a grouped world's search (k_group_rows): one workgroup per GROUP_ROBOTS robots of a group, LDS for the largest group
 hipError_t neighbours_rows_groups(const float *pos, int n, const int32_t *members, const int32_t *seg, const int32_t *wg, int n_workgroups,
-                                  int largest, float radius, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, int32_t *ran) {
+                                  int largest, const float *thr, int32_t cap, int32_t *cnt, int32_t *rows, hipStream_t s, int32_t *ran) {
     if (n <= 0 || n_workgroups <= 0) return hipSuccess;
-    if (largest <= 0 || largest > ROWS_MAX_N) return hipErrorInvalidValue;  // (no workgroup holds the positions of such a group)
-    hipLaunchKernelGGL(k_group_rows, dim3((unsigned)n_workgroups), dim3(64), pairs_rows_lds(largest), s, pos, members, seg, wg,
-                       squared_threshold(radius), cap, cnt, rows);
+    if (largest <= 0 || largest > ROWS_MAX_N || !thr) return hipErrorInvalidValue;  // (no workgroup holds the positions of such a group)
+    hipLaunchKernelGGL(k_group_rows, dim3((unsigned)n_workgroups), dim3(64), pairs_rows_lds(largest), s, pos, members, seg, wg, thr, cap, cnt,
+                       rows);
     if (ran) *ran = MGX_SEARCH_ROWS_GROUPS;
     return hipGetLastError();
 }

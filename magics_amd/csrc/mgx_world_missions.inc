@@ -104,7 +104,7 @@ int mgx_mission_tick(mgx_world *w, float comms_radius, uint32_t method, uint64_t
 }
 
 static int mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, uint64_t *robot_number_next, int32_t despawn_finished,
-                              uint32_t *stats, uint32_t n_groups);
+                              uint32_t *stats, uint32_t n_groups, const float *radii = nullptr);
 int mgx_mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, uint64_t *robot_number_next, int32_t despawn_finished,
                            uint32_t *stats) {
     MGX_ENTER(w);
@@ -118,15 +118,29 @@ int mgx_mission_tick_begin_groups(mgx_world *w, float comms_radius, uint32_t met
     MGX_ENTER(w);
     if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
     const int rc = groups_arguments(w, n_groups, number_next);
-    return rc != MGX_OK ? rc : mission_tick_begin(w, comms_radius, method, number_next, despawn_finished, stats, n_groups);
+    if (rc != MGX_OK) return rc;
+    const std::vector<float> radii((size_t)n_groups, comms_radius);  // (the radii call with all radii equal)
+    return mission_tick_begin(w, comms_radius, method, number_next, despawn_finished, stats, n_groups, radii.data());
 }
-// n_groups: 0 — one generator, stats {created, deleted, completed}; otherwise one generator and one stats triple per group
+int mgx_mission_tick_begin_groups_radii(mgx_world *w, const float *comms_radii, uint32_t method, uint32_t n_groups, uint64_t *number_next,
+                                        int32_t despawn_finished, uint32_t *stats) {
+    MGX_ENTER(w);
+    if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
+    if (!comms_radii) return fail(MGX_ERR_INVALID, "null argument (radii)");
+    const int rc = groups_arguments(w, n_groups, number_next);
+    if (rc != MGX_OK) return rc;
+    return mission_tick_begin(w, comms_radii[0], method, number_next, despawn_finished, stats, n_groups, comms_radii);
+}
+// n_groups: 0 — one generator, stats {created, deleted, completed}; otherwise one generator and one stats triple per group.
+// radii (may be null): [n_groups], one comms radius per group (an ungrouped world: radii[0], which comms_radius is)
 static int mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method, uint64_t *robot_number_next, int32_t despawn_finished,
-                              uint32_t *stats, uint32_t n_groups) {
+                              uint32_t *stats, uint32_t n_groups, const float *radii) {
     int rc = MGX_OK;
     mgx_world::Mission &ms = w->mission;
     if (!ms.any) return fail(MGX_ERR_STATE, "no robot has a mission (mgx_mission_set)");
     if (w->K < 3) return fail(MGX_ERR_INVALID, "needs K >= 3");
+    if (w->sets.n_grouped == 0) radii = nullptr;  // (the scalar search)
+    const std::vector<float> now = radii ? std::vector<float>(radii, radii + n_groups) : std::vector<float>();
     rc = commit(w);
     if (rc != MGX_OK) return rc;
     if (w->d.R_total != w->d.R_local) return fail(MGX_ERR_STATE, "missions run on unsharded worlds");
@@ -146,9 +160,10 @@ static int mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method,
     HIP_TRY(launch_mission_reached(w->d, ms.d, R, ms.tick_no, (unsigned int *)evd, s));
     std::vector<int32_t> ptr, idx;
     // the search itself was enqueued by the last tick's end, in front of its GBP schedule, if nothing has changed since: the same
-    // radius and method, the same robots alive (this tick's despawns are taken out of the rows below either way)
+    // radius — every group's, where they have one each — and method, the same robots alive (this tick's despawns are taken out of
+    // the rows below either way)
     NeighbourSearch::PendingSearch &pf = w->search.mission;
-    bool prefetched = pf.valid && pf.radius == comms_radius && pf.method == method && pf.n_all == R;
+    bool prefetched = pf.valid && pf.radius == comms_radius && pf.radii == now && pf.method == method && pf.n_all == R;
     if (prefetched) {
         size_t a = 0;
         for (int r = 0; r < R && prefetched; r++)
@@ -158,9 +173,10 @@ static int mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method,
             }
         if (a != pf.alive.size()) prefetched = false;
     }
-    rc = prefetched ? neighbours_collect(w, pf, ptr, idx) : neighbours(w, nullptr, comms_radius, method, ptr, idx);
+    rc = prefetched ? neighbours_collect(w, pf, ptr, idx) : neighbours(w, nullptr, comms_radius, method, ptr, idx, radii, radii ? n_groups : 0);
     if (rc != MGX_OK) return rc;
     ms.search_radius = comms_radius;
+    ms.search_radii = now;
     ms.search_method = method;
     ms.search_known = true;
     tm.lap(prefetched ? "reached + rows of the search enqueued last tick" : "reached + search");
@@ -289,7 +305,9 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     // update_robot_neighbours of the COMING tick (robot.rs:1362-1384): the Transforms it looks at are final now, so the search goes
     // in front of this tick's GBP schedule and its rows reach the host while that runs
     tm.lap("prepare");
-    if (ms.search_known && (rc = neighbours_enqueue(w, nullptr, ms.search_radius, ms.search_method, w->search.mission)) != MGX_OK) return rc;
+    if (ms.search_known && (rc = neighbours_enqueue(w, nullptr, ms.search_radius, ms.search_method, w->search.mission, false,
+                                                    ms.search_radii.empty() ? nullptr : ms.search_radii.data(), (uint32_t)ms.search_radii.size())) != MGX_OK)
+        return rc;
     tm.lap("search of the coming tick enqueued");
     for (int r = 0; r < R; r++) {  // message counters: the prior changes of the robots that move (what the device decides too)
         const Robot &rb = w->robots[(size_t)r];

@@ -49,7 +49,8 @@ static int mission_positions(mgx_world *w, PendingSearch &ps) {
 }
 // what both strategies start with: who is in the query, on which stream, ordered against the search before; the positions of
 // a mission's search.  *pos: the caller's positions, compacted where robots have left the query
-static int search_front(mgx_world *w, const float **pos, float radius, uint32_t method, PendingSearch &ps) {
+static int search_front(mgx_world *w, const float **pos, float radius, uint32_t method, PendingSearch &ps, const float *radii = nullptr,
+                        uint32_t n_radii = 0) {
     if (!device_ok()) return fail(MGX_ERR_NO_DEVICE, "no HIP device");
     NeighbourSearch &S = w->search;
     S.mission.valid = false;  // the buffers below are shared: whatever was waiting in them is gone
@@ -57,6 +58,8 @@ static int search_front(mgx_world *w, const float **pos, float radius, uint32_t 
     ps.n_all = (int)w->robots.size();
     ps.from_missions = *pos == nullptr;
     ps.radius = radius;
+    if (radii) ps.radii.assign(radii, radii + n_radii);  // (may be the ones ps holds already: mgx_mission_tick_end's)
+    else ps.radii.clear();
     ps.method = method;
     std::vector<int> &alive = ps.alive;  // removed robots are in no query: search the others, map back
     alive.clear();
@@ -115,7 +118,8 @@ static int rows_launch(mgx_world *w, PendingSearch &ps, int cap, const float *ho
         const GroupTables &g = S.groups;
         ps.rows.has_chg = false;
         HIP_TRY(neighbours_rows_groups(ps.from_missions ? S.pos.p : reinterpret_cast<const float *>(dp), ps.n, S.groups_d.p, S.groups_d.p + g.off_seg(),
-                                       S.groups_d.p + g.off_wg(), g.n_workgroups(), g.largest, ps.radius, cap, reinterpret_cast<int32_t *>(dp + at.off_cnt),
+                                       S.groups_d.p + g.off_wg(), g.n_workgroups(), g.largest, reinterpret_cast<const float *>(S.groups_d.p + g.off_thr()),
+                                       cap, reinterpret_cast<int32_t *>(dp + at.off_cnt),
                                        reinterpret_cast<int32_t *>(dp + at.off_rows), ps.stream, &S.last_kernel));
     } else {
         HIP_TRY(neighbours_rows(ps.from_missions ? S.pos.p : reinterpret_cast<const float *>(dp), ps.n, ps.radius, cap,
@@ -240,21 +244,31 @@ static int csr_collect(mgx_world *w, PendingSearch &ps, std::vector<int32_t> &pt
 }
 
 // A grouped world's query listed by group (GroupTables, mgx_search.h), on the device: built again only when robots have joined or
-// left the query — then uploaded and waited for (the kernels of an earlier search on this stream have read the old tables by then)
+// left the query, the segments' thresholds also when a group's radius is not the one of the search before — then uploaded and
+// waited for (the kernels of an earlier search on this stream have read the old tables by then).  Not per search: a search with
+// the robots and the radii of the one before uploads nothing
 static int groups_prepare(mgx_world *w, PendingSearch &ps) {
     NeighbourSearch &S = w->search;
-    if (S.groups_valid && S.groups_alive == ps.alive) return MGX_OK;
+    const float *radii = ps.radii.empty() ? nullptr : ps.radii.data();
+    if (S.groups_valid && S.groups_alive == ps.alive) {
+        if (!group_thresholds(S.groups, radii, ps.radii.size(), ps.radius)) return MGX_OK;
+    } else {
+        S.groups_valid = false;
+        std::vector<uint32_t> of_query((size_t)ps.n);
+        for (int q = 0; q < ps.n; q++) of_query[(size_t)q] = w->sets.group[(size_t)ps.alive[(size_t)q]];
+        if (!group_tables(of_query.data(), ps.n, S.groups))
+            return fail(MGX_ERR_INVALID, "a group of %d robots: the grouped search holds one group's positions in a workgroup's LDS, %d at the most",
+                        S.groups.largest, ROWS_MAX_N);
+        group_thresholds(S.groups, radii, ps.radii.size(), ps.radius);
+    }
     S.groups_valid = false;
-    std::vector<uint32_t> of_query((size_t)ps.n);
-    for (int q = 0; q < ps.n; q++) of_query[(size_t)q] = w->sets.group[(size_t)ps.alive[(size_t)q]];
-    if (!group_tables(of_query.data(), ps.n, S.groups))
-        return fail(MGX_ERR_INVALID, "a group of %d robots: the grouped search holds one group's positions in a workgroup's LDS, %d at the most", S.groups.largest,
-                    ROWS_MAX_N);
     const GroupTables &g = S.groups;
     S.groups_host.clear();
     S.groups_host.insert(S.groups_host.end(), g.members.begin(), g.members.end());
     S.groups_host.insert(S.groups_host.end(), g.seg.begin(), g.seg.end());
     S.groups_host.insert(S.groups_host.end(), g.wg.begin(), g.wg.end());
+    S.groups_host.resize(g.words_with_thr());  // (the thresholds' bits)
+    if (!g.thr.empty()) memcpy(S.groups_host.data() + g.off_thr(), g.thr.data(), sizeof(float) * g.thr.size());
     HIP_TRY(hipStreamSynchronize(ps.stream));  // (nothing reads the old tables any more)
     HIP_TRY(S.groups_d.upload(S.groups_host, ps.stream));
     HIP_TRY(hipStreamSynchronize(ps.stream));
@@ -263,8 +277,12 @@ static int groups_prepare(mgx_world *w, PendingSearch &ps) {
     return MGX_OK;
 }
 // track: the search of a topology pass over the caller's positions (see rows_enqueue)
-static int neighbours_enqueue(mgx_world *w, const float *pos, float radius, uint32_t method, PendingSearch &ps, bool track = false) {
-    int rc = search_front(w, &pos, radius, method, ps);
+// radii (may be null) [n_radii]: one radius per group, for a grouped world's search; an ungrouped world's search is the scalar one
+// with radii[0] — `radius` is that one then
+static int neighbours_enqueue(mgx_world *w, const float *pos, float radius, uint32_t method, PendingSearch &ps, bool track = false,
+                              const float *radii = nullptr, uint32_t n_radii = 0) {
+    if (w->sets.n_grouped == 0) radii = nullptr;
+    int rc = search_front(w, &pos, radius, method, ps, radii, radii ? n_radii : 0);
     if (rc != MGX_OK) return rc;
     ps.grouped = w->sets.n_grouped != 0 && ps.n > 0;
     const int32_t kernel = search_kernel_for(ps.n, method, radius, w->search.row_cap, ps.grouped);
@@ -291,19 +309,35 @@ static int neighbours_collect(mgx_world *w, PendingSearch &ps, std::vector<int32
     return MGX_OK;
 }
 static int neighbours(mgx_world *w, const float *pos, float radius, uint32_t method, std::vector<int32_t> &ptr,
-                      std::vector<int32_t> &idx) {
+                      std::vector<int32_t> &idx, const float *radii = nullptr, uint32_t n_radii = 0) {
     PendingSearch ps;
-    const int rc = neighbours_enqueue(w, pos, radius, method, ps);
+    const int rc = neighbours_enqueue(w, pos, radius, method, ps, false, radii, n_radii);
     return rc != MGX_OK ? rc : neighbours_collect(w, ps, ptr, idx);
 }
 
+static int groups_radii_arguments(mgx_world *w, const float *radii, uint32_t n_groups);
+static int neighbours_to_caller(mgx_world *w, const float *positions_xyz, float radius, const float *radii, uint32_t n_groups, uint32_t method,
+                          int32_t *row_ptr, int32_t *neighbours_out, uint64_t capacity, uint64_t *needed);
 int mgx_neighbours(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, int32_t *row_ptr, int32_t *neighbours_out,
                    uint64_t capacity, uint64_t *needed) {
     MGX_ENTER(w);
     if (!w || !positions_xyz || !row_ptr) return fail(MGX_ERR_INVALID, "null argument");
     if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
+    return neighbours_to_caller(w, positions_xyz, radius, nullptr, 0, method, row_ptr, neighbours_out, capacity, needed);
+}
+int mgx_neighbours_groups(mgx_world *w, const float *positions_xyz, const float *radii, uint32_t n_groups, uint32_t method, int32_t *row_ptr,
+                          int32_t *neighbours_out, uint64_t capacity, uint64_t *needed) {
+    MGX_ENTER(w);
+    if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
+    const int rc = groups_radii_arguments(w, radii, n_groups);
+    if (rc != MGX_OK) return rc;
+    if (!positions_xyz || !row_ptr) return fail(MGX_ERR_INVALID, "null argument");
+    return neighbours_to_caller(w, positions_xyz, radii[0], radii, n_groups, method, row_ptr, neighbours_out, capacity, needed);
+}
+static int neighbours_to_caller(mgx_world *w, const float *positions_xyz, float radius, const float *radii, uint32_t n_groups, uint32_t method,
+                          int32_t *row_ptr, int32_t *neighbours_out, uint64_t capacity, uint64_t *needed) {
     std::vector<int32_t> ptr, idx;
-    int rc = neighbours(w, positions_xyz, radius, method, ptr, idx);
+    int rc = neighbours(w, positions_xyz, radius, method, ptr, idx, radii, n_groups);
     if (rc != MGX_OK) return rc;
     memcpy(row_ptr, ptr.data(), sizeof(int32_t) * ptr.size());
     if (needed) *needed = idx.size();
@@ -340,8 +374,17 @@ static int groups_arguments(mgx_world *w, uint32_t n_groups, const uint64_t *num
         if (w->sets.group[r] >= n_groups) return fail(MGX_ERR_INVALID, "robot %zu is in group %u: not below n_groups %u", r, w->sets.group[r], n_groups);
     return MGX_OK;
 }
+// ... and the calls with one radius per group: radii [n_groups] (any value: NaN, zero and negative radii mean what they mean as scalars)
+static int groups_radii_arguments(mgx_world *w, const float *radii, uint32_t n_groups) {
+    if (!radii) return fail(MGX_ERR_INVALID, "null argument (radii)");
+    if (n_groups == 0 || n_groups > MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "n_groups %u is not in 1 .. MGX_GROUPS_MAX (%u)", n_groups, MGX_GROUPS_MAX);
+    if (!w) return fail(MGX_ERR_INVALID, "null argument");
+    for (size_t r = 0; r < w->sets.group.size(); r++)
+        if (w->sets.group[r] >= n_groups) return fail(MGX_ERR_INVALID, "robot %zu is in group %u: not below n_groups %u", r, w->sets.group[r], n_groups);
+    return MGX_OK;
+}
 static int update_topology(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint64_t *robot_number_next, uint32_t *stats,
-                           uint32_t n_groups);
+                           uint32_t n_groups, const float *radii = nullptr);
 int mgx_update_topology(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint64_t *robot_number_next,
                         uint32_t *stats) {
     MGX_ENTER(w);
@@ -357,10 +400,22 @@ int mgx_update_topology_groups(mgx_world *w, const float *positions_xyz, float r
     const int rc = groups_arguments(w, n_groups, number_next);
     if (rc != MGX_OK) return rc;
     if (!positions_xyz) return fail(MGX_ERR_INVALID, "null argument");
-    return update_topology(w, positions_xyz, radius, method, number_next, stats, n_groups);
+    const std::vector<float> radii((size_t)n_groups, radius);  // (the radii call with all radii equal)
+    return update_topology(w, positions_xyz, radius, method, number_next, stats, n_groups, radii.data());
 }
+int mgx_update_topology_groups_radii(mgx_world *w, const float *positions_xyz, const float *radii, uint32_t method, uint32_t n_groups,
+                                     uint64_t *number_next, uint32_t *stats) {
+    MGX_ENTER(w);
+    if (method > MGX_NEIGHBOURS_GRID) return fail(MGX_ERR_INVALID, "bad method");
+    if (!radii) return fail(MGX_ERR_INVALID, "null argument (radii)");
+    const int rc = groups_arguments(w, n_groups, number_next);  // (n_groups, the generators, every robot's group)
+    if (rc != MGX_OK) return rc;
+    if (!positions_xyz) return fail(MGX_ERR_INVALID, "null argument");
+    return update_topology(w, positions_xyz, radii[0], method, number_next, stats, n_groups, radii);
+}
+// radii (may be null): [n_groups], one radius per group (an ungrouped world: radii[0], which `radius` is)
 static int update_topology(mgx_world *w, const float *positions_xyz, float radius, uint32_t method, uint64_t *robot_number_next, uint32_t *stats,
-                           uint32_t n_groups) {
+                           uint32_t n_groups, const float *radii) {
     std::vector<int32_t> ptr, idx;
     StageTimer tm("update_topology");
     // update_robot_neighbours (robot.rs:1362-1384).  A small world's search runs BESIDE the GBP schedule of the tick before, on a
@@ -371,7 +426,7 @@ static int update_topology(mgx_world *w, const float *positions_xyz, float radiu
     // under it (the pass is about to change who sends to whom).  (Who owns which connection — what the deletions walk —
     // comes from the connection index, kept in step with the list: round 4 listed the connections by owner here, every tick.)
     PendingSearch ps;
-    int rc = neighbours_enqueue(w, positions_xyz, radius, method, ps, true);  // (waits for the launch to be decided first if it has to)
+    int rc = neighbours_enqueue(w, positions_xyz, radius, method, ps, true, radii, radii ? n_groups : 0);  // (waits for the launch to be decided first if it has to)
     if (rc != MGX_OK) return rc;
     tm.lap("search enqueued");
     flush_counts(w, true);  // (lazy: the robots' counters and cumulative counts; connections are settled when deleted or read)

@@ -455,6 +455,7 @@ struct NeighbourSearch {
         std::vector<int> alive;        // the world ids of the robots in the query
         bool compact = false, from_missions = false;
         float radius = 0.f;
+        std::vector<float> radii;  // a grouped search's radius per GROUP id (empty: `radius` for every group)
         uint32_t method = 0;
         bool grouped = false;  // a grouped world's search: k_group_rows over NeighbourSearch::groups
         bool in_rows = false;  // the one-pass kernel with rows of a fixed capacity (`rows`), else count / scan / fill (`csr`)
@@ -760,6 +761,7 @@ struct mgx_world {
         std::vector<int32_t> last_finished;  // robots whose mission completed in the last begin, ascending
         float search_radius = 0.f;           // what the last tick's topology pass searched with: the coming tick's search is enqueued
         uint32_t search_method = 0;          //   with the same (mgx_mission_tick_end), used if the next begin asks for the same
+        std::vector<float> search_radii;     // ... per group where the last begin had one radius per group (else empty)
         bool search_known = false;
         float *tr_host = nullptr;            // pinned: Transforms after the last tick's move (valid after the next synchronisation)
         size_t tr_cap = 0, tr_n = 0;

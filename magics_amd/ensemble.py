@@ -8,7 +8,12 @@ member stays bit-identical to the same scenario run by a `Simulation` on a world
 Nothing of `Simulation` is restated here.  Every member IS a `Simulation`, on a view of the shared world (`_MemberWorld`) that
 speaks the member's own robot numbering and puts its robots into its group; the ensemble makes the two world-wide calls of a tick
 once (mission_tick_begin_groups, mission_tick_end) and runs the parts of `Simulation._tick_device` around them per member; the
-device's collision log and tracker sample log are drained once and their records routed to the members by robot id."""
+device's collision logs and tracker sample log are drained once and their records routed to the members by robot id.
+
+Per member (per group of the world): the seed, the comms failure rate, the formations, max-time — and the comms radius, which the
+grouped search holds per group (mission_tick_begin_groups with one radius per member).  The per-robot observers — environment
+collisions, goal areas, the run metrics — do not look at the group: the first member switches them on for the world, and every
+member reads its own robots' part."""
 import copy
 
 import numpy as np
@@ -17,7 +22,11 @@ from . import config as _config
 from . import hostlib
 from .sim import Simulation
 
-UNSUPPORTED = ("environment_collisions", "goal_areas", "device_metrics", "global_planner")
+UNSUPPORTED = ("global_planner",)
+# the observers an Ensemble runs on the device, and what the world has to offer for each
+OBSERVERS = (("environment_collisions", "env_collisions_enable"), ("goal_areas", "goal_areas_enable"), ("device_metrics", "track_metrics_enable"))
+ENV_EVENTS_PER_MEMBER = 262144   # the room a run of its own has for environment-collision events (mgx_env_collisions_enable's default)
+ENV_EVENTS_MOST = 1 << 24        # ... and where an ensemble's log stops growing with its members (24 bytes a record)
 
 
 def _shared_settings(sc):
@@ -25,7 +34,7 @@ def _shared_settings(sc):
     cfg = sc["config"]
     out = [("params." + k, v) for k, v in _config.world_params(cfg).items()]
     out += [("gbp.iteration-schedule", cfg["gbp"]["iteration-schedule"]), ("gbp.lookahead-multiple", cfg["gbp"]["lookahead-multiple"]),
-            ("robot.communication.radius", cfg["robot"]["communication"]["radius"]), ("robot.target-speed", cfg["robot"]["target-speed"]),
+            ("robot.target-speed", cfg["robot"]["target-speed"]),
             ("robot.planning-horizon", cfg["robot"]["planning-horizon"]), ("simulation.hz", cfg["simulation"]["hz"]),
             ("simulation.despawn-robot-when-final-waypoint-reached", cfg["simulation"]["despawn-robot-when-final-waypoint-reached"]),
             ("environment", sc["environment"])]
@@ -41,6 +50,7 @@ class _MemberWorld:
         self._e, self._group = ensemble, group
         self.ids = []            # member id -> world id
         self.coll_events = []    # this member's collision events so far, member ids, in (pass, a, b) order
+        self.env_events = []     # ... and its environment-collision events, in (pass, robot, collider) order
         self.samples = []        # this member's tracker samples not taken yet
         self.reserved = 0
 
@@ -64,6 +74,31 @@ class _MemberWorld:
     def tracks_set_clock(self, next_tick):
         pass                     # (the members tick in step: the ensemble keeps the world's one clock)
 
+    def tracks_set_logging(self, on=True):
+        if self._group == 0:
+            self._e.world.tracks_set_logging(on)
+            self._e._logging = bool(on)
+
+    def env_collisions_enable(self, env, event_capacity=0):
+        """the world's log holds the events of ALL members: the room a run of its own has (ENV_EVENTS_PER_MEMBER, the engine's
+        default) per member, so that no member loses an event its own run would have kept — up to ENV_EVENTS_MOST records; a log that
+        was full raises when it is read, here as there"""
+        if self._group == 0:
+            room = int(event_capacity) or ENV_EVENTS_PER_MEMBER
+            self._e.world.env_collisions_enable(env, event_capacity=min(room * len(self._e.members_worlds), max(room, ENV_EVENTS_MOST)))
+
+    def goal_areas_enable(self, areas, next_tick=0):
+        if self._group == 0:
+            self._e.world.goal_areas_enable(areas, next_tick=next_tick)
+            self._e._goals = True
+
+    def goal_areas_set_clock(self, next_tick):
+        pass                     # (the ensemble's, like the trackers' clock)
+
+    def track_metrics_enable(self, *args, **kwargs):
+        if self._group == 0:
+            self._e.world.track_metrics_enable(*args, **kwargs)
+
     # -- robots -----------------------------------------------------------------------------------------------------------------
     def add_robot(self, mean0, prior_diag, dt, radius, path=None, order_key=None, ghost=False):
         # the order key unique across the members, the order within a member as it was
@@ -77,6 +112,9 @@ class _MemberWorld:
 
     def mission_set(self, robot, *args, **kwargs):
         self._e.world.mission_set(self.ids[robot], *args, **kwargs)
+
+    def track_metrics_set_route(self, robot, xy):
+        self._e.world.track_metrics_set_route(self.ids[robot], xy)
 
     def message_counts(self, robot):
         return self._e.world.message_counts(self.ids[robot])
@@ -96,6 +134,28 @@ class _MemberWorld:
         for k, e in enumerate(ev):
             out[k] = e
         return out, len(self.coll_events), dropped, None
+
+    def env_collisions_read(self, first=0):
+        self._e._drain_env_collisions()
+        ev = self.env_events[int(first):]
+        out = np.zeros(len(ev), hostlib.env_collision_event_dtype())
+        for k, e in enumerate(ev):
+            out[k] = e
+        return out, len(self.env_events), 0, None
+
+    def goal_areas_read(self):
+        """the world's first arrivals of this member's robots, in member ids (the order of the world's: tick, robot, area)"""
+        ev, _ = self._e.world.goal_areas_read()
+        mine = [(int(e["tick"]), int(e["area"]), self._e._owner[int(e["robot"])]) for e in ev]
+        mine = [(t, a, r) for t, a, (g, r) in mine if g == self._group]
+        out = np.zeros(len(mine), hostlib.goal_arrival_dtype())
+        for k, (t, a, r) in enumerate(mine):
+            out[k]["tick"], out[k]["area"], out[k]["robot"] = t, a, r
+        return out, None
+
+    def track_metrics_read(self):
+        """this member's records, in member-id order"""
+        return self._e.world.track_metrics_read()[self.ids]
 
     def tracks_take(self, capacity=None, travelled=True):
         dropped, dist = self._e._drain_tracks()
@@ -139,10 +199,14 @@ class Ensemble:
     def __init__(self, scenarios, world, **simulation_options):
         """scenarios: one scenario dict per member (config.load_scenario, tests/golden/scenarios.json); member m's robots are in
         group m of `world`, a fresh World made with config.world_params of any of them.  The members may differ in
-        simulation.prng-seed, robot.communication.failure-rate (and max-time) and in their formations; everything the world holds
-        once must be equal (ValueError names the first key that differs).  simulation_options go to every member's Simulation.
-        This version runs device missions with device robot-robot collisions and device trackers — the default export;
-        environment_collisions, goal_areas, device_metrics, global_planner (and so rrt-star formations) raise NotImplementedError."""
+        simulation.prng-seed, robot.communication.failure-rate, robot.communication.radius (and max-time) and in their formations;
+        everything the world holds once must be equal (ValueError names the first key that differs; a world that takes no radius
+        per group holds the radius once, too).  simulation_options go to every member's Simulation, so the members share them —
+        goal_areas among them.  An Ensemble runs device missions with device robot-robot collisions and device trackers, and on
+        request the device's other observers: environment_collisions=True, goal_areas, device_metrics (with sample_log=False if
+        asked).  Still refused, with NotImplementedError: global_planner (and so rrt-star formations) — a per-group many-tick run
+        and per-group planning are not part of the engine — and every option that needs each tick's Transforms on the host:
+        environment_collisions="host", device_goal_areas=False, device_missions / device_collisions / device_trackers = False."""
         scenarios = list(scenarios)
         if not scenarios:
             raise ValueError("an Ensemble needs at least one scenario")
@@ -150,17 +214,28 @@ class Ensemble:
             raise ValueError(f"an Ensemble has at most {hostlib.GROUPS_MAX} members")
         for opt in UNSUPPORTED:
             if simulation_options.get(opt):
-                raise NotImplementedError(f"Ensemble: {opt} is not supported in this version (device missions, device robot-robot collisions and "
-                                          "device trackers are)")
-        for opt in ("device_missions", "device_collisions", "device_trackers"):
+                raise NotImplementedError(f"Ensemble: {opt} is not supported (the engine plans and runs many ticks for ONE group: mgx_mission_run, "
+                                          "mgx_plan_paths)")
+        for opt in ("device_missions", "device_collisions", "device_trackers", "device_goal_areas"):
             if simulation_options.get(opt) is False:
-                raise NotImplementedError(f"Ensemble: {opt}=False is not supported in this version (the members share the device's passes)")
+                raise NotImplementedError(f"Ensemble: {opt}=False is not supported (the members share the device's passes; a host pass needs every "
+                                          "tick's Transforms of every member on the host)")
+        if simulation_options.get("environment_collisions") == "host":
+            raise NotImplementedError('Ensemble: environment_collisions="host" is not supported (the host pass needs every tick\'s Transforms on the '
+                                      "host); True runs the device's pass")
+        for opt, needs in OBSERVERS:
+            if simulation_options.get(opt) and not hasattr(world, needs):
+                raise NotImplementedError(f"Ensemble: {opt} needs an engine world that offers {needs} (the pass runs on the device)")
         for m, sc in enumerate(scenarios):
             if any(f["planning-strategy"] != "only-local" for f in sc["formation"]["formations"]):
                 raise NotImplementedError(f"Ensemble: member {m} has an rrt-star formation; the global planner is not supported in this version")
-        first = _shared_settings(scenarios[0])
+        per_group_radius = hasattr(world, "neighbours_groups")   # (the engine's grouped search: one comms radius per group)
+
+        def shared(sc):
+            return _shared_settings(sc) + ([] if per_group_radius else [("robot.communication.radius", sc["config"]["robot"]["communication"]["radius"])])
+        first = shared(scenarios[0])
         for m, sc in enumerate(scenarios[1:], 1):
-            for (key, a), (_, b) in zip(first, _shared_settings(sc)):
+            for (key, a), (_, b) in zip(first, shared(sc)):
                 if a != b:
                     raise ValueError(f"Ensemble: member {m} differs from member 0 in {key} ({b!r} against {a!r}): the world holds it once")
         if not hasattr(world, "mission_tick_begin_groups"):
@@ -169,6 +244,10 @@ class Ensemble:
         self._owner = {}          # world id -> (member, member id)
         self._coll_cursor = 0     # events of the world's collision log already routed
         self._coll_dropped = 0
+        self._env_cursor = 0      # ... and of its environment-collision log
+        self._logging = True      # the device appends the trackers' samples to its log (sample_log)
+        self._goals = False       # goal areas are on: their clock is the ensemble's
+        self._per_group_radius = per_group_radius
         self._log_room = 0        # room of the device's sample log (what the first member enabled the trackers with)
         self._log_bound = 0       # samples the log holds at the most since it was last drained
         self._dist = np.zeros(0)
@@ -191,6 +270,15 @@ class Ensemble:
             self.members_worlds[m].coll_events.append((e["pass"], a, b, e["mins"], e["maxs"]))
         return dropped
 
+    def _drain_env_collisions(self):
+        ev, total, dropped = self.world.env_collisions_read(self._env_cursor)[:3]
+        if dropped:
+            raise hostlib.MgxError(f"the device's environment collision log was full: {dropped} events were not stored")
+        self._env_cursor = total
+        for e in ev:
+            m, r = self._owner[int(e["robot"])]
+            self.members_worlds[m].env_events.append((e["pass"], r, e["collider"], e["mins"], e["maxs"]))
+
     def _drain_tracks(self):
         if self._clock is None:   # (no robot has ticked yet)
             return 0, np.zeros(len(self._owner))
@@ -212,17 +300,21 @@ class Ensemble:
         if ticking:
             w, s0 = self.world, ticking[0].sim
             alive = sum(1 for m in ticking for r in m.sim.robots if r["alive"])
-            if self._log_room and self._log_bound + alive > self._log_room:   # (a robot gives at most one sample per tick)
+            if self._logging and self._log_room and self._log_bound + alive > self._log_room:   # (a robot gives at most one sample per tick)
                 dropped, _ = self._drain_tracks()
                 if dropped:
                     raise hostlib.MgxError(f"the device's tracker log was full: {dropped} samples were not stored")
             self._log_bound += alive
-            if self._clock != self.tick_no:
+            if self._clock != self.tick_no:   # (before the first tick that has robots, and behind ticks that had none)
                 w.tracks_set_clock(self.tick_no)
+                if self._goals:
+                    w.goal_areas_set_clock(self.tick_no)
             for m in ticking:
                 m.sim._tick_device_before()
             numbers = np.array([m.sim.next_number for m in self.members], dtype=np.uint64)
-            numbers, stats, fin = w.mission_tick_begin_groups(s0.comms_radius, numbers, despawn_finished=s0.despawn, method=s0.method)
+            # one comms radius per member (a retired member's is its own still: it changes nothing, so nothing is uploaded again)
+            radius = np.array([m.sim.comms_radius for m in self.members], dtype=np.float32) if self._per_group_radius else s0.comms_radius
+            numbers, stats, fin = w.mission_tick_begin_groups(radius, numbers, despawn_finished=s0.despawn, method=s0.method)
             finished = [[] for _ in self.members]
             for wid in fin:
                 g, r = self._owner[int(wid)]

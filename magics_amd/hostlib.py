@@ -147,6 +147,9 @@ SYMBOLS = {
                                  C.POINTER(C.c_uint64)]),
     "mgx_update_topology": (C.c_int, [_V, C.c_void_p, C.c_float, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     "mgx_update_topology_groups": (C.c_int, [_V, C.c_void_p, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mgx_update_topology_groups_radii": (C.c_int, [_V, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "mgx_neighbours_groups": (C.c_int, [_V, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                        C.POINTER(C.c_uint64)]),
     "mgx_connections": (C.c_int, [_V, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_iterate": (C.c_int, [_V, C.c_char_p, C.c_uint32]),
     "mgx_batch_begin": (C.c_int, [_V]),
@@ -204,6 +207,7 @@ SYMBOLS = {
                                    C.c_char_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_mission_tick_begin": (C.c_int, [_V, C.c_float, C.c_uint32, C.POINTER(C.c_uint64), C.c_int32, C.POINTER(C.c_uint32)]),
     "mgx_mission_tick_begin_groups": (C.c_int, [_V, C.c_float, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "mgx_mission_tick_begin_groups_radii": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]),
     "mgx_mission_run": (C.c_int, [_V, C.c_void_p]),
     "mgx_mission_tick_end": (C.c_int, [_V, C.c_void_p, C.c_double, C.c_double, C.c_char_p, C.c_uint32]),
     "mgx_mission_finished": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),

@@ -25,6 +25,17 @@ def _f64(a, shape=None):
     return a
 
 
+def group_radii(radius, n_groups):
+    """the comms radius of a per-group call as the engine takes it: None for ONE radius (a scalar: the scalar call), else one f32 per
+    group, by group id — ValueError unless there are exactly n_groups of them"""
+    if np.ndim(radius) == 0:
+        return None
+    radii = np.ascontiguousarray(radius, dtype=np.float32)
+    if radii.ndim != 1 or len(radii) != n_groups:
+        raise ValueError(f"one comms radius per group: got shape {radii.shape} for {n_groups} groups")
+    return radii
+
+
 def make_params(p):
     return Params(
         float(p["sigma_dynamics"]), float(p["sigma_interrobot"]), float(p["sigma_obstacle"]),
@@ -187,6 +198,20 @@ class World:
                                          need.value, C.byref(need)))
         return ptr, idx[:need.value]
 
+    def neighbours_groups(self, positions, radii, method=hostlib.NEIGHBOURS_AUTO, capacity=None):
+        """neighbours with one comms radius per group (mgx_neighbours_groups): radii [n_groups], by group id."""
+        pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+        rad = np.ascontiguousarray(radii, dtype=np.float32).reshape(-1)
+        ptr = np.zeros(pos.shape[0] + 1, dtype=np.int32)
+        need = C.c_uint64()
+        if capacity is None:
+            self._chk(self._L.mgx_neighbours_groups(self._w, pos.ctypes.data, rad.ctypes.data, len(rad), method, ptr.ctypes.data, None, 0, C.byref(need)))
+            capacity = need.value
+        idx = np.zeros(max(int(capacity), 1), dtype=np.int32)
+        self._chk(self._L.mgx_neighbours_groups(self._w, pos.ctypes.data, rad.ctypes.data, len(rad), method, ptr.ctypes.data, idx.ctypes.data,
+                                                int(capacity), C.byref(need)))
+        return ptr, idx[:need.value]
+
     def update_topology(self, positions, radius, next_number, method=hostlib.NEIGHBOURS_AUTO):
         """update_robot_neighbours + delete_/create_interrobot_factors; returns (next robot number,
         connections created, pairs deleted)."""
@@ -198,13 +223,19 @@ class World:
 
     def update_topology_groups(self, positions, radius, next_numbers, method=hostlib.NEIGHBOURS_AUTO):
         """update_topology with one RobotNumberGenerator per group (mgx_update_topology_groups): next_numbers [n_groups].
+        radius: one for all groups, or one per group [n_groups] (mgx_update_topology_groups_radii).
         Returns (next robot numbers [n_groups] u64, stats [n_groups, 2] u32: connections created, pairs deleted)."""
         pos = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
         nxt = None if next_numbers is None else np.array(next_numbers, dtype=np.uint64).reshape(-1)
         n_groups = 0 if nxt is None else len(nxt)
         stats = np.zeros((max(n_groups, 1), 2), dtype=np.uint32)
-        self._chk(self._L.mgx_update_topology_groups(self._w, pos.ctypes.data, float(radius), int(method), n_groups,
-                                                     None if nxt is None else nxt.ctypes.data, stats.ctypes.data))
+        radii = group_radii(radius, n_groups)
+        if radii is None:
+            self._chk(self._L.mgx_update_topology_groups(self._w, pos.ctypes.data, float(radius), int(method), n_groups,
+                                                         None if nxt is None else nxt.ctypes.data, stats.ctypes.data))
+        else:
+            self._chk(self._L.mgx_update_topology_groups_radii(self._w, pos.ctypes.data, radii.ctypes.data, int(method), n_groups,
+                                                               None if nxt is None else nxt.ctypes.data, stats.ctypes.data))
         return nxt, stats[:n_groups]
 
     def connections(self, robot):
@@ -409,13 +440,20 @@ class World:
 
     def mission_tick_begin_groups(self, comms_radius, next_numbers, despawn_finished=True, method=hostlib.NEIGHBOURS_AUTO):
         """mission_tick_begin with one RobotNumberGenerator per group (mgx_mission_tick_begin_groups): next_numbers [n_groups].
+        comms_radius: one for all groups, or one per group [n_groups] (mgx_mission_tick_begin_groups_radii).
         Returns (next robot numbers [n_groups] u64, stats [n_groups, 3] u32: connections created, pairs deleted, missions
         completed, ids of the robots of all groups whose mission completed in this tick, ascending)."""
         nxt = None if next_numbers is None else np.array(next_numbers, dtype=np.uint64).reshape(-1)
         n_groups = 0 if nxt is None else len(nxt)
         stats = np.zeros((max(n_groups, 1), 3), dtype=np.uint32)
-        self._chk(self._L.mgx_mission_tick_begin_groups(self._w, float(comms_radius), int(method), n_groups,
-                                                        None if nxt is None else nxt.ctypes.data, 1 if despawn_finished else 0, stats.ctypes.data))
+        radii = group_radii(comms_radius, n_groups)
+        if radii is None:
+            self._chk(self._L.mgx_mission_tick_begin_groups(self._w, float(comms_radius), int(method), n_groups,
+                                                            None if nxt is None else nxt.ctypes.data, 1 if despawn_finished else 0, stats.ctypes.data))
+        else:
+            self._chk(self._L.mgx_mission_tick_begin_groups_radii(self._w, radii.ctypes.data, int(method), n_groups,
+                                                                  None if nxt is None else nxt.ctypes.data, 1 if despawn_finished else 0,
+                                                                  stats.ctypes.data))
         n_fin = int(stats[:n_groups, 2].sum())
         fin = np.zeros(n_fin, dtype=np.int32)
         if n_fin:

@@ -278,6 +278,8 @@ extern "C" {
     pub fn mgx_neighbours(w: *mut mgx_world, positions_xyz: *const f32, radius: f32, method: u32, row_ptr: *mut i32, neighbours_out: *mut i32, capacity: u64, needed: *mut u64) -> c_int;
     pub fn mgx_update_topology(w: *mut mgx_world, positions_xyz: *const f32, radius: f32, method: u32, robot_number_next: *mut u64, stats: *mut u32) -> c_int;
     pub fn mgx_update_topology_groups(w: *mut mgx_world, positions_xyz: *const f32, radius: f32, method: u32, n_groups: u32, number_next: *mut u64, stats: *mut u32) -> c_int;
+    pub fn mgx_update_topology_groups_radii(w: *mut mgx_world, positions_xyz: *const f32, radii: *const f32, method: u32, n_groups: u32, number_next: *mut u64, stats: *mut u32) -> c_int;
+    pub fn mgx_neighbours_groups(w: *mut mgx_world, positions_xyz: *const f32, radii: *const f32, n_groups: u32, method: u32, row_ptr: *mut i32, neighbours_out: *mut i32, capacity: u64, needed: *mut u64) -> c_int;
     pub fn mgx_connections(w: *mut mgx_world, robot: i32, others: *mut i32, capacity: u32, n: *mut u32) -> c_int;
     pub fn mgx_iterate(w: *mut mgx_world, steps: *const u8, n: u32) -> c_int;
     pub fn mgx_batch_begin(w: *mut mgx_world) -> c_int;
@@ -313,6 +315,7 @@ extern "C" {
     pub fn mgx_mission_tick_begin(w: *mut mgx_world, comms_radius: f32, method: u32, robot_number_next: *mut u64, despawn_finished: i32, stats: *mut u32) -> c_int;
     pub fn mgx_mission_tick_end(w: *mut mgx_world, antennas: *const u8, max_speed: f64, delta_t: f64, steps: *const u8, n_steps: u32) -> c_int;
     pub fn mgx_mission_tick_begin_groups(w: *mut mgx_world, comms_radius: f32, method: u32, n_groups: u32, number_next: *mut u64, despawn_finished: i32, stats: *mut u32) -> c_int;
+    pub fn mgx_mission_tick_begin_groups_radii(w: *mut mgx_world, comms_radii: *const f32, method: u32, n_groups: u32, number_next: *mut u64, despawn_finished: i32, stats: *mut u32) -> c_int;
     pub fn mgx_mission_finished(w: *mut mgx_world, robots: *mut i32, capacity: u32, n: *mut u32) -> c_int;
     pub fn mgx_mission_run(w: *mut mgx_world, desc: *mut mgx_mission_run_desc) -> c_int;
     pub fn mgx_mission_translations(w: *mut mgx_world, translations: *mut f32, capacity_robots: u32, n_robots: *mut u32) -> c_int;

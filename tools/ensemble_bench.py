@@ -1,7 +1,9 @@
 """Many scenario runs as ONE Ensemble against the same runs one after another (profiles/ensemble.md).
 
-Two workloads, both from tests/golden/scenarios.json: the reference's communications-failure experiment as its script runs it — 5
-seeds x 8 failure rates, 21 robots per run: 40 members — and the Environment Obstacles Experiment with 32 seeds.  For each:
+Three workloads, all from tests/golden/scenarios.json: the reference's communications-failure experiment as its script runs it — 5
+seeds x 8 failure rates, 21 robots per run: 40 members —, the Environment Obstacles Experiment with 32 seeds, and the Varying Network
+Connectivity Experiment as its script runs it — 5 seeds x comms radii 20 / 40 / 60 / 80, 30 robots per run: 20 members that differ in
+their comms radius.  For each:
   ensemble   the members as robot groups of one world (magics_amd/ensemble.py): wall time, member ticks per second, the kernel the
              neighbour search ran, the resident schedule launches (ran / declined);
   solo       the same members one after another, each a Simulation on a world of its own: run(chunk=1) and run(chunk=256).
@@ -10,7 +12,10 @@ what a sweep of runs pays); one untimed warm-up run in front, --reps timed repet
 The solo part needs nothing of the ensemble: `--solo` runs it alone, also from the root of an older checkout
 (python <this file> --solo), which is how the figures of the parent commit are taken.
 
-usage: python tools/ensemble_bench.py [--solo | --ensemble] [--reps N] [--max-time S] [--out FILE.json]"""
+--only WORD keeps the workloads whose name contains WORD.  --observers runs the ensemble with environment_collisions=True,
+device_metrics=True, sample_log=False (the figures the Environment Obstacles analysis reads), for a run against the same without.
+
+usage: python tools/ensemble_bench.py [--solo | --ensemble] [--only WORD] [--observers] [--reps N] [--max-time S] [--out FILE.json]"""
 import copy
 import json
 import os
@@ -34,38 +39,45 @@ def option(flag, kind, default):
 
 
 reps, max_time, out_file = option("--reps", int, 5), option("--max-time", float, 30.0), option("--out", str, None)
+only, observers = option("--only", str, ""), "--observers" in args
 only_solo, only_ensemble = "--solo" in args, "--ensemble" in args
+OBSERVERS = {"environment_collisions": True, "device_metrics": True, "sample_log": False} if observers else {}
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 
 
-def members(name, seeds, rates):
+def members(name, seeds, rates, radii=(None,)):
     out = []
-    for rate in rates:
-        for seed in seeds:
-            sc = copy.deepcopy(known[name])
-            sc["config"]["simulation"]["prng-seed"] = seed
-            if rate is not None:
-                sc["config"]["robot"]["communication"]["failure-rate"] = rate
-            out.append(sc)
+    for radius in radii:
+        for rate in rates:
+            for seed in seeds:
+                sc = copy.deepcopy(known[name])
+                sc["config"]["simulation"]["prng-seed"] = seed
+                if rate is not None:
+                    sc["config"]["robot"]["communication"]["failure-rate"] = rate
+                if radius is not None:
+                    sc["config"]["robot"]["communication"]["radius"] = radius
+                out.append(sc)
     return out
 
 
 WORKLOADS = {
     "comms-failure 5 seeds x 8 rates": lambda: members("Communications Failure Experiment", [0, 31, 227, 252, 805], [0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7]),
     "environment-obstacles 32 seeds": lambda: members("Environment Obstacles Experiment", list(range(100, 132)), [None]),
+    "network-connectivity 5 seeds x 4 radii": lambda: members("Varying Network Connectivity Experiment", [0, 31, 227, 252, 805], [None],
+                                                              [20.0, 40.0, 60.0, 80.0]),
 }
 
 
 def spread(xs):
-    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4), "n": len(xs)}
+    return {"median": round(statistics.median(xs), 4), "min": round(min(xs), 4), "max": round(max(xs), 4), "n": len(xs), "runs": [round(x, 4) for x in xs]}
 
 
 def run_solo(scs, chunk):
     ticks = 0
     t0 = time.perf_counter()
     for sc in scs:
-        s = sim.Simulation(copy.deepcopy(sc), World(config.world_params(sc["config"])))
+        s = sim.Simulation(copy.deepcopy(sc), World(config.world_params(sc["config"])), **OBSERVERS)
         s.run(max_time=max_time, chunk=chunk)
         s.w.synchronize()
         ticks += s.tick_no
@@ -75,7 +87,7 @@ def run_solo(scs, chunk):
 def run_ensemble(scs):
     from magics_amd import ensemble
     t0 = time.perf_counter()
-    e = ensemble.Ensemble([copy.deepcopy(sc) for sc in scs], World(config.world_params(scs[0]["config"])))
+    e = ensemble.Ensemble([copy.deepcopy(sc) for sc in scs], World(config.world_params(scs[0]["config"])), **OBSERVERS)
     e.run(max_time=max_time)
     e.world.synchronize()
     wall = time.perf_counter() - t0
@@ -87,8 +99,10 @@ def run_ensemble(scs):
                                                       "schedules_posted": posted}
 
 
-result = {"max_time": max_time, "reps": reps, "workloads": {}}
+result = {"max_time": max_time, "reps": reps, "observers": observers, "workloads": {}}
 for name, make in WORKLOADS.items():
+    if only not in name:
+        continue
     scs = make()
     row = {"members": len(scs)}
     forms = []

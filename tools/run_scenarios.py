@@ -14,13 +14,15 @@ sample is logged on the device and the robots' positions / velocities lists stay
 "junction" is the two exits of the reference's junction scenario, FILE.json holds a list of boxes [[x0, z0], [x1, z1]]; each
 scenario's line then carries the arrivals per area and the throughput the reference's analyse-junction-scenario.py reads out of an
 export (robots that started within 50 s and arrived, per second).  --export DIR writes each scenario's export to DIR/<name>.json.
---ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] runs the cross product of ONE scenario — every seed with every failure
-rate (default: the scenario's own) — as one Ensemble (magics_amd/ensemble.py): the members are robot groups of one world, one
-launch per schedule and one synchronisation per tick for all of them, each member identical to the same run alone.  One line per
-member; with --export DIR one export per member, DIR/<name>.seed<A>.rate<X>.json.
+--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] runs the cross product of ONE scenario —
+every seed with every failure rate and every comms radius (default: the scenario's own) — as one Ensemble (magics_amd/ensemble.py):
+the members are robot groups of one world, one launch per schedule and one synchronisation per tick for all of them, each member
+identical to the same run alone.  One line per member — with --environment-collisions, --goal-areas and --metrics (with or
+without --no-sample-log) it carries the member's contacts, arrivals and the means of its run metrics; with --export DIR one
+export per member, DIR/<name>.seed<A>.rate<X>.radius<R>.json.  The global planner and host trackers do not run in an Ensemble.
 usage: python tools/run_scenarios.py [--max-time S] [--goal-areas junction|FILE.json] [--export DIR] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
-           [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N] [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..]]
-           [scenario-dir | name ...]"""
+           [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N]
+           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..]] [scenario-dir | name ...]"""
 import copy
 import json
 import os
@@ -79,7 +81,7 @@ for flag, key, kind in (("--planner-half-extent", "sample_half_extent", float), 
         i = args.index(flag)
         overrides[key] = kind(args[i + 1])
         del args[i:i + 2]
-ensemble_seeds, ensemble_rates = None, None
+ensemble_seeds, ensemble_rates, ensemble_radii = None, None, None
 if "--ensemble-seeds" in args:
     i = args.index("--ensemble-seeds")
     ensemble_seeds = [int(x) for x in args[i + 1].split(",")]
@@ -88,41 +90,54 @@ if "--ensemble-failure-rates" in args:
     i = args.index("--ensemble-failure-rates")
     ensemble_rates = [float(x) for x in args[i + 1].split(",")]
     del args[i:i + 2]
-if ensemble_rates and not ensemble_seeds:
-    sys.exit("--ensemble-failure-rates needs --ensemble-seeds")
+if "--ensemble-comms-radii" in args:
+    i = args.index("--ensemble-comms-radii")
+    ensemble_radii = [float(x) for x in args[i + 1].split(",")]
+    del args[i:i + 2]
+if (ensemble_rates or ensemble_radii) and not ensemble_seeds:
+    sys.exit("--ensemble-failure-rates and --ensemble-comms-radii need --ensemble-seeds")
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 if ensemble_seeds:
     from magics_amd import ensemble  # noqa: E402
     if len(args) != 1:
         sys.exit("--ensemble-seeds runs ONE scenario: name it")
-    if env_collisions or goal_areas or metrics or global_planner or host_trackers:
-        sys.exit("--ensemble-seeds: environment collisions, goal areas, device metrics, the global planner and host trackers are not "
-                 "supported by this version of the Ensemble")
+    if global_planner or host_trackers:
+        sys.exit("--ensemble-seeds: the global planner and host trackers do not run in an Ensemble (magics_amd/ensemble.py says why)")
     base = config.load_scenario(args[0]) if os.path.isdir(args[0]) else known[args[0]]
     members = []
-    for rate in ensemble_rates or [base["config"]["robot"]["communication"]["failure-rate"]]:
-        for seed in ensemble_seeds:
-            sc = copy.deepcopy(base)
-            sc["config"]["simulation"]["prng-seed"] = seed
-            sc["config"]["robot"]["communication"]["failure-rate"] = rate
-            members.append((seed, rate, sc))
+    for radius in ensemble_radii or [base["config"]["robot"]["communication"]["radius"]]:
+        for rate in ensemble_rates or [base["config"]["robot"]["communication"]["failure-rate"]]:
+            for seed in ensemble_seeds:
+                sc = copy.deepcopy(base)
+                sc["config"]["simulation"]["prng-seed"] = seed
+                sc["config"]["robot"]["communication"]["failure-rate"] = rate
+                sc["config"]["robot"]["communication"]["radius"] = radius
+                members.append((seed, rate, radius, sc))
     t0 = time.perf_counter()
-    e = ensemble.Ensemble([sc for _, _, sc in members], World(config.world_params(base["config"])))
+    e = ensemble.Ensemble([sc for *_, sc in members], World(config.world_params(base["config"])), environment_collisions=env_collisions,
+                          device_metrics=metrics, sample_log=not no_sample_log, goal_areas=goal_areas)
     e.run(max_time=max_time)
     wall = time.perf_counter() - t0
     stem = os.path.basename(os.path.normpath(base.get("name", args[0])))
-    for (seed, rate, sc), m in zip(members, e.members):
+    for (seed, rate, radius, sc), m in zip(members, e.members):
         s = m.sim
         done = [r for r in s.robots if r["completed"]]
         trav = [r["travelled"] for r in s.robots]
-        print(json.dumps({"scenario": sc.get("name", args[0]), "seed": seed, "failure_rate": rate, "simulated_s": round(s.elapsed(), 1),
+        figures = m.metrics() if metrics or env_collisions or goal_areas else None
+        print(json.dumps({"scenario": sc.get("name", args[0]), "seed": seed, "failure_rate": rate, "comms_radius": radius,
+                          "simulated_s": round(s.elapsed(), 1),
                           "robots": len(s.robots), "finished": len(done), "all_finished": s.finished(), "K": s.K,
                           "mean_distance": round(sum(trav) / max(1, len(trav)), 1),
-                          "last_finish_s": round(max((r["finished_at"] for r in done), default=0.0), 1), "topology_events": len(s.events)}), flush=True)
+                          "last_finish_s": round(max((r["finished_at"] for r in done), default=0.0), 1), "topology_events": len(s.events),
+                          **({"environment_collisions": figures["collisions"]["environment"]} if env_collisions else {}),
+                          **({"goal_arrivals": figures["goal_areas"]["arrivals"], "goal_flow": figures["goal_areas"]["flow"]} if goal_areas else {}),
+                          **({"makespan": figures["makespan"], "collisions": figures["collisions"],
+                              **{f"mean_{c}": figures["summary"][c]["mean"] for c in ("ldj", "path_deviation", "distance_travelled", "duration")}}
+                             if metrics else {})}), flush=True)
         if export_dir:
             os.makedirs(export_dir, exist_ok=True)
-            with open(os.path.join(export_dir, f"{stem}.seed{seed}.rate{rate:g}.json"), "w", encoding="utf-8") as f:
+            with open(os.path.join(export_dir, f"{stem}.seed{seed}.rate{rate:g}.radius{radius:g}.json"), "w", encoding="utf-8") as f:
                 json.dump(m.export(), f)
     print(json.dumps({"ensemble": len(members), "ticks": e.tick_no, "member_ticks": sum(m.tick_no for m in e.members), "wall_s": round(wall, 2),
                       "member_ticks_per_s": round(sum(m.tick_no for m in e.members) / wall, 1)}), flush=True)
