@@ -251,10 +251,15 @@ __global__ void k_thaw(DevWorld w, int robot0, int n_robots, uint32_t ext_mask) 
     const BlobLayout L(K);
     double *blob = w.blob + (size_t)r * w.BS;
     const double *fz = w.frozen + (size_t)r * frozen_words(K);
-    const bool present = w.frozen_flag[(size_t)r * E + e] != 0;
+    const uint8_t flag = w.frozen_flag[(size_t)r * E + e];
+    const bool present = flag != 0;
     double oe[4], ol[16];
     bool ok = true;
-    if (bit == 1u) {
+    if (flag == 2) {
+        // no inbox key at all (the factor was created switched off and nothing has been delivered to it since): an update
+        // sends one message per key — none; what the variable holds from it stays the empty message
+        ok = false;
+    } else if (bit == 1u) {
         const int f = e % (K - 1), slot = e / (K - 1);
         const int a2 = 2 * slot, b2 = 2 * (1 - slot), it = r * (K - 1) + f;
         double maa[4], mab[4], mba[4], mbb[4], me[4], ml[16];

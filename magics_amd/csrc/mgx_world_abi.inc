@@ -145,6 +145,12 @@ int mgx_robot_add(mgx_world *w, const mgx_robot_desc *d, int32_t *robot_id) {
     {   // add_internal_edge (factorgraph.rs:304-330): the variable receives an (empty) message, the factor one if enabled
         const uint32_t en = w->p.enable_mask;
         rb.cnt[2] = (uint64_t)(2 * (K - 1) + 2 * (K - 2)) + ((en & 1u) ? 2 * (K - 1) : 0) + ((en & 4u) ? K - 2 : 0) + ((en & 8u) ? K - 2 : 0);
+        // a robot that joins a world that has iterated: its switched-off factors stay without inbox keys, and switching the kind
+        // on has something to thaw even if no sweep runs in between
+        if (w->n_layouts > 0) {
+            rb.nokey = (uint8_t)(~en & 13u);
+            w->stale_kinds |= ~en & 13u;
+        }
     }
     rb.prior_eta.assign(4 * K, 0.0); rb.prior_lam.assign(16 * K, 0.0);
     rb.bel_eta.assign(4 * K, 0.0); rb.bel_lam.assign(16 * K, 0.0); rb.bel_mu.assign(4 * K, 0.0); rb.bel_cov.assign(16 * K, 0.0);
@@ -367,6 +373,8 @@ static int ensure_frozen(mgx_world *w) {
     const size_t RL = (size_t)std::max(w->d.R_local, 1);
     std::vector<double> z((size_t)frozen_words(w->K) * RL, 0.0);
     std::vector<uint8_t> zf((size_t)(4 * w->K - 6) * RL, 0), zb(RL, 0);
+    for (int dr = 0; dr < w->d.R_local; dr++)  // (robots that joined while a kind was off since the world began)
+        nokey_flags(w->robots[(size_t)w->robot_of[(size_t)dr]].nokey, w->K, &zf[(size_t)(4 * w->K - 6) * (size_t)dr]);
     HIP_TRY(w->frozen_buf.upload(z, w->stream));
     HIP_TRY(w->frozen_flag_buf.upload(zf, w->stream));
     HIP_TRY(w->thaw_buf.upload(zb, w->stream));

@@ -646,6 +646,7 @@ static int commit(mgx_world *w) {
             const Robot &rb = w->robots[(size_t)w->robot_of[(size_t)dr]];
             if (rb.frozen.size() == FZ) std::copy(rb.frozen.begin(), rb.frozen.end(), fzd.begin() + (long)((size_t)dr * FZ));
             if (rb.frozen_flag.size() == (size_t)E) std::copy(rb.frozen_flag.begin(), rb.frozen_flag.end(), fzf.begin() + (long)((size_t)dr * (size_t)E));
+            else nokey_flags(rb.nokey, K, &fzf[(size_t)dr * (size_t)E]);  // (joined while kinds were off: those factors have no inbox keys)
             thw[(size_t)dr] = rb.thaw;
         }
         HIP_TRY(w->frozen_buf.upload(fzd, s));

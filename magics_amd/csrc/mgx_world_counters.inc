@@ -55,6 +55,7 @@ static void flush_counts(mgx_world *w, bool lazy) {
     // dozen vectors wide.
     std::vector<uint64_t> nIv(n, 0), nEf(n, 0), nEv(n, 0), nIfv(n, 0), trkv(n, 0);
     std::vector<uint8_t> flags(n, 0);  // bit 0: on air (antenna and not idle), bit 1: idle
+    std::vector<int64_t> itf0(n, 0);   // the robots' factor iteration counts in front of this log
     // Past a robot's tracking gate (ten factor sweeps) every entry of the log only ADDS, and a world-wide entry adds the same to
     // every robot with the same flags: the log is summed once per class of robots — on air / silent / idle — as suffix sums, and
     // a robot walks the log itself only as far as its gate is still closed.  (A driver that iterates without reading fills the log
@@ -111,6 +112,7 @@ static void flush_counts(mgx_world *w, bool lazy) {
         flags[r] = (uint8_t)((radio ? 1 : 0) | (idle ? 2 : 0));
         Sum a;
         a.itf = rb.cnt_itf;
+        itf0[r] = rb.cnt_itf;
         if (world_wide_only) {
             size_t j = 0;
             while (j < n_log && a.itf < 10 && !idle) apply(w->clog[j++], radio, idle, a);  // (its gate: entry by entry; an idle robot's never moves)
@@ -193,6 +195,30 @@ static void flush_counts(mgx_world *w, bool lazy) {
             rb.cnt[0] += (nIv[r] + nEv[r]) * s_int;
             rb.cnt[1] += (nIv[r] + nEv[r]) * s_ext;
             rb.cnt[2] += nIv[r] * (dynf + obsf + trkf);
+            // factors without inbox keys (created switched off, Robot::nokey) send nothing: the internal factor sweeps in front
+            // of the robot's first internal variable sweep under the kind — the log in order — were counted above and are taken back
+            const uint32_t nk = (uint32_t)rb.nokey & en & 13u;
+            if (nk && !(flags[r] & 2u)) {
+                const bool radio = (flags[r] & 1u) != 0;
+                int64_t itf = itf0[r];
+                uint64_t missed = 0, missed_open = 0;  // sweeps without keys; those of them behind the tracking gate
+                bool filled = false;
+                for (const mgx_world::CountEntry &e : w->clog) {
+                    if (filled) break;
+                    if (e.robot >= 0 && (size_t)e.robot != r) continue;
+                    for (uint64_t rep = 0; rep < e.times && !filled; rep++) {
+                        if ((e.ext & 1u) && radio) itf++;
+                        for (int q = 0; q < e.n_int && !filled; q++) {
+                            if (e.in & 1u) { missed++; if (itf >= 10) missed_open++; itf++; }
+                            if (e.in & 2u) filled = true;
+                        }
+                    }
+                }
+                const uint64_t back = missed * (((nk & 1u) ? 2ull * (K - 1) : 0) + ((nk & 4u) ? (uint64_t)(K - 2) : 0)) + missed_open * ((nk & 8u) ? (uint64_t)(K - 2) : 0);
+                rb.cnt[0] -= back;
+                rb.cnt[2] -= back;
+                if (filled) rb.nokey &= (uint8_t)~en;
+            }
         }
     }
     if (keyless) {  // (their share of this log was added by hand above: the bases move with the cumulative counts)

@@ -315,6 +315,18 @@ int mgx_reset_variables(mgx_world *w, int32_t robot, const double *means, uint32
     flush_counts(w);
     Robot &rb = w->robots[(size_t)robot];
     const int K = rb.K, E = 4 * K - 6;
+    // connections made since the last commit whose TARGET is this robot took its variables' means when they were made
+    // (robot.rs:1549-1585): they are settled now, as the commit would settle them, before the means are replaced
+    for (IrConn &c : w->conns) {
+        if (c.other != robot) continue;
+        for (size_t j = 0; j < c.edges.size(); j++) {
+            IrEdge &ed = c.edges[j];
+            if (!ed.fresh) continue;
+            ed.created = w->robots[(size_t)c.owner].epoch[j + 1];
+            for (int q = 0; q < 4; q++) ed.bmu[q] = (w->p.enable_mask & 2u) ? rb.bel_mu[4 * (j + 1) + q] : 0.0;
+            ed.fresh = false;
+        }
+    }
     for (int i = 0; i < K; i++) {
         const double sigma = (i == 0 || i == K - 1) ? first_last_sigma : inbetween_sigma;
         for (int c = 0; c < 4; c++) rb.bel_mu[4 * i + c] = means[4 * i + c];
@@ -324,6 +336,10 @@ int mgx_reset_variables(mgx_world *w, int32_t robot, const double *means, uint32
     }
     std::fill(rb.fv_eta.begin(), rb.fv_eta.begin() + 4 * E, 0.0);
     std::fill(rb.fv_lam.begin(), rb.fv_lam.begin() + 16 * E, 0.0);
+    // ... the inboxes of switched-off and thawing factors too (empty_inbox asks no factor whether it is enabled): the entries they
+    // froze with become empty; a factor without inbox keys stays without
+    std::fill(rb.frozen.begin(), rb.frozen.end(), 0.0);
+    for (uint8_t &fl : rb.frozen_flag) fl = fl == 2 ? 2 : 0;
     for (IrConn &c : w->conns) {
         if (c.other == robot)  // foreign factors attached to these variables: their message to us is emptied
             for (IrEdge &ed : c.edges) { std::fill(ed.fv_eta, ed.fv_eta + 4, 0.0); std::fill(ed.fv_lam, ed.fv_lam + 16, 0.0); }

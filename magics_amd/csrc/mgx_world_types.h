@@ -265,9 +265,21 @@ struct Robot {
     std::vector<double> frozen;
     std::vector<uint8_t> frozen_flag;
     uint8_t thaw = 0;
-    std::vector<double> ir_frozen_snap;                    // [K][24] what the variables had sent when inter-robot factors went off
+    // internal kinds that were switched off when the robot joined and whose factors have not been delivered to since: a factor
+    // created switched off takes no message, not even the empty one that gives its inbox its keys (factorgraph.rs:304-330,
+    // factor/mod.rs:307-310) — until its variables deliver it sends nothing (frozen_flag 2 on the device, NO_KEY)
+    uint8_t nokey = 0;
+    std::vector<double> ir_frozen_snap;                   // [K][24] what the variables had sent when inter-robot factors went off
     std::vector<uint32_t> ir_frozen_epoch, ir_thaw_epoch;  // [K]
 };
+// frozen_flag [E] of a robot that has no frozen inbox yet: empty entries, and NO key at all for the kinds in `nokey`
+static inline void nokey_flags(uint8_t nokey, int K, uint8_t *fl) {
+    const int n_dyn = 2 * (K - 1), E = 4 * K - 6;
+    for (int e = 0; e < E; e++) {
+        const uint8_t bit = e < n_dyn ? 1u : (e < n_dyn + (K - 2) ? 4u : 8u);
+        fl[e] = (nokey & bit) ? 2 : 0;
+    }
+}
 
 struct IrEdge {  // one InterRobotFactor, kept at its target variable
     double fv_eta[4] = {0, 0, 0, 0}, fv_lam[16] = {0}, bmu[4] = {0, 0, 0, 0};

@@ -334,3 +334,49 @@ def test_route_on_a_completed_mission_is_refused():
     for tick in range(3):
         assert de.tick() == dr.tick()
     _compare_missions(de, dr, eng, ref, "after the refused route")
+
+
+# ---- 7. the handler where the engine keeps no laid-out, unfrozen world (found by tests/test_gpu_script_fuzz.py) -----------------
+def _handler_both(eng, ref, robots, paths, means):
+    eng.apply_global_paths(robots, paths, means)
+    _handler_on_the_oracle(ref, robots, paths, means)
+
+
+def test_handler_before_the_first_iteration():
+    sc = S.grid_scenario(6, 10, interrobot=True, tracking=True, seed=24, pitch=2.5, comm_radius=4.5)
+    eng, ref = make_pair(sc)
+    K = sc["K"]
+    rng = np.random.default_rng(5)
+    robots = [2, 3]
+    means = np.array([sc["robots"][r]["mean0"] + rng.normal(0, 0.3, size=(K, 4)) for r in robots])
+    paths = [np.ascontiguousarray(m[[0, K // 2, K - 1], :2], dtype=F32) for m in means]
+    _handler_both(eng, ref, robots, paths, means)
+    assert_identical(eng, ref, what="right after the handler")
+    for k, steps in enumerate(([1], [2], [3])):
+        for w in (eng, ref):
+            w.iterate(steps)
+        assert_identical(eng, ref, what=f"handler before the first iteration, schedule {k}")
+    assert np.isfinite(ref.read_beliefs()[2]).all()
+
+
+def test_handler_while_dynamics_factors_are_off():
+    sc = S.grid_scenario(6, 10, interrobot=False, tracking=True, seed=3, pitch=2.5, comm_radius=4.5)
+    eng, ref = make_pair(sc)
+    K, mask = sc["K"], sc["params"]["enable_mask"]
+    rng = np.random.default_rng(5)
+    robots = [1, 4]
+    means = np.array([sc["robots"][r]["mean0"] + rng.normal(0, 0.3, size=(K, 4)) for r in robots])
+    paths = [np.ascontiguousarray(m[[0, K // 2, K - 1], :2], dtype=F32) for m in means]
+    for w in (eng, ref):
+        w.iterate([3, 3])
+        w.set_enabled(mask & ~S.EN_DYN)
+        w.iterate([3])
+    _handler_both(eng, ref, robots, paths, means)
+    for k in range(3):
+        for w in (eng, ref):
+            w.iterate([3])
+        assert_identical(eng, ref, what=f"dynamics off, iteration {k} after the handler")
+    for w in (eng, ref):
+        w.set_enabled(mask)
+        w.iterate([1])
+    assert_identical(eng, ref, what="dynamics on again")

@@ -329,3 +329,46 @@ def test_junction_twoway_spawns_in_place():
     assert json.dumps(a.export(), sort_keys=True) == json.dumps(b.export(), sort_keys=True)
     assert a.w.layout_stats()[1] == pulls_at[spawn_ticks[1]], (pulls_at[spawn_ticks[1]], a.w.layout_stats(), spawn_ticks)
     assert a.w.append_stats()[0] >= 2 and a.w.append_stats()[2] == 0, a.w.append_stats()
+
+
+# ---- 10. robots that join while a factor kind is switched off (found by tests/test_gpu_script_fuzz.py) ---------------------------
+def _joins_while_off(kind):
+    """five robots iterate, `kind` goes off, a sixth joins (its factors of that kind are created switched off: they take no
+    message, not even the one that fills their inbox with keys — factorgraph.rs:304-330, factor/mod.rs:307-310), the kind
+    comes back: beliefs and message counts after every step"""
+    full = S.grid_scenario(6, 10, interrobot=True, seed=3, pitch=2.5, comm_radius=4.5)
+    sc = _first(full, 5)
+    eng, ref = World(sc["params"]), oracle.OracleWorld(sc["params"])
+    assert S.populate(eng, sc) == S.populate(ref, sc)
+    mask = sc["params"]["enable_mask"]
+    for w in (eng, ref):
+        w.iterate([3, 3])
+        w.set_enabled(mask & ~kind)
+        w.iterate([3])
+    assert_identical(eng, ref, what="kind off")
+    _add((eng, ref), full["robots"][5])
+    for w in (eng, ref):
+        w.iterate([3])
+    assert_identical(eng, ref, what="joined while the kind is off")
+    assert _counts(eng, 6) == _counts(ref, 6)
+    for w in (eng, ref):
+        w.set_enabled(mask)
+        w.iterate([1])
+    assert_identical(eng, ref, what="kind on again, one internal iteration")
+    assert _counts(eng, 6) == _counts(ref, 6)
+    for w in (eng, ref):
+        w.iterate([3, 3])
+    assert_identical(eng, ref, what="two more")
+    assert _counts(eng, 6) == _counts(ref, 6)
+
+
+def test_a_robot_joins_while_dynamics_factors_are_off():
+    _joins_while_off(S.EN_DYN)
+
+
+def test_a_robot_joins_while_obstacle_factors_are_off():
+    _joins_while_off(S.EN_OBS)
+
+
+def test_a_robot_joins_while_interrobot_factors_are_off():
+    _joins_while_off(S.EN_IR)
