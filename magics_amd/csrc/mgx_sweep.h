@@ -2090,6 +2090,58 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                 v.w = seq;
                 return v;
             };
+            // Constant K: the ceil(XREC_CHUNKS K / 64) passes are written out, pass p = items 64 p + lane with p a constant in the
+            // body.  publication_reads issues EVERY pass's LDS reads — the two snapshot rows, and the delivery counts in the pass
+            // (or the two) that holds chunk XREC_EPOCH_DWORD / 3, known here — so that one wait serves them all; publication_chunk
+            // packs pass p from those registers.  Lanes of the last pass beyond the last item read the last item (inside the
+            // block) and store nothing.  The index arithmetic is unsigned: t / K of a constant K is a multiplication and a shift.
+            // XAHEAD (horizons of 16 variables and more): the masked last pass's reads are in flight with the others'.  All passes
+            // in flight are four or five more live registers than the full passes alone; the kernels of the shorter horizons pay
+            // for them with a spilled VGPR (K = 11, 13; profiles/publication_rounds.md), so there the last pass's reads stay under
+            // its store's mask: two round trips.  The remote publication of a boundary robot (below) keeps the loop for the same
+            // reason.
+            constexpr bool XAHEAD = 4 * KT >= 64;
+            // XWRITTEN: which instantiations take the written-out form.  `<20,2,true>` keeps the loop: every written-out form that
+            // was compiled ended at 134 - 140 spilled SGPRs there, the loop at the parent's 130 (profiles/publication_rounds.md).
+            constexpr bool XWRITTEN = KT > 0 && !(KT == 20 && !SHARD);
+            constexpr int XN = KT > 0 ? XREC_CHUNKS * KT : 64, XPASSES = (XN + 63) / 64, XEP_CH = XREC_EPOCH_DWORD / 3;
+            static_assert(3 * XEP_CH + 2 == XREC_EPOCH_DWORD && (XEP_CH & 1) == 0, "the delivery count is the third dword of an even chunk");
+            constexpr auto XPASS_SEQ = std::make_integer_sequence<int, XPASSES>{};
+            auto xpass_item = [&](auto p) __attribute__((always_inline)) {
+                constexpr int t0 = 64 * decltype(p)::value;
+                const unsigned t = (unsigned)lane + (unsigned)t0;
+                return t0 + 64 > XN ? (t < (unsigned)XN ? t : (unsigned)(XN - 1)) : t;
+            };
+            auto xpass_has_epoch = [](auto p) constexpr { return KT > 0 && 64 * decltype(p)::value < (XEP_CH + 1) * KT && 64 * decltype(p)::value + 64 > XEP_CH * KT; };
+            auto publication_reads = [&](double (&A)[XPASSES], double (&B)[XPASSES], uint32_t (&ep)[XPASSES]) __attribute__((always_inline)) {
+                static_for(XPASS_SEQ, [&](auto p) __attribute__((always_inline)) {
+                    constexpr unsigned KU = (unsigned)(KT > 0 ? KT : 1);
+                    const unsigned t = xpass_item(p), ch = t / KU, i = t - ch * KU, da = (3u * ch) >> 1;
+                    A[p] = s_snap[da * KU + i];
+                    B[p] = s_snap[(da + 1u) * KU + i];
+                    ep[p] = 0u;
+                    if constexpr (xpass_has_epoch(p)) ep[p] = s_epoch[i];  // (every lane of the pass: i < K whatever its chunk)
+                });
+                // XAHEAD: the last pass's operands are "used" here.  Otherwise its reads sink under the mask of its store, a round trip
+                // of their own behind the other passes' — this way the one wait for everything in flight stands here.
+                if constexpr (XAHEAD) asm volatile("" : "+v"(A[XPASSES - 1]), "+v"(B[XPASSES - 1]), "+v"(ep[XPASSES - 1]));
+            };
+            auto publication_chunk = [&](auto p, const double (&A)[XPASSES], const double (&B)[XPASSES], const uint32_t (&ep)[XPASSES], uint32_t seq) __attribute__((always_inline)) {
+                constexpr unsigned KU = (unsigned)(KT > 0 ? KT : 1);
+                const unsigned t = xpass_item(p), ch = t / KU;
+                const bool odd = (ch & 1u) != 0u;
+                v4u32 v;
+                v.x = odd ? (unsigned)__double2hiint(A[p]) : (unsigned)__double2loint(A[p]);
+                v.y = odd ? (unsigned)__double2loint(B[p]) : (unsigned)__double2hiint(A[p]);
+                v.z = odd ? (unsigned)__double2hiint(B[p]) : (unsigned)__double2loint(B[p]);
+                if constexpr (xpass_has_epoch(p)) v.z = ch == (unsigned)XEP_CH ? ep[p] : v.z;
+                v.w = seq;
+#ifdef MGX_XREC_CHECKSUM
+                if (ch == (unsigned)(XREC_CHUNKS - 1)) v = chunk_of((int)t, seq);
+#endif
+                return v;
+            };
+            auto xpass_stores = [&](auto p) __attribute__((always_inline)) { return 64 * decltype(p)::value + 64 <= XN || lane + 64 * decltype(p)::value < XN; };
             const unsigned xbase = (unsigned)v0 * (unsigned)XREC_BYTES;
             if (role == ROLE_UV) {
                 QSTAMP(10, qt);
@@ -2098,7 +2150,17 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                 TLSTAMP(k, 0);
                 {
                     const uint32_t seq = xrec_seq(next_count);
-                    for (int t = lane; t < XREC_CHUNKS * K; t += 64) st16_agent_raw(rs_x, xbase + 16u * (unsigned)t, ob ? xrec_bytes : 0u, chunk_of(t, seq));
+                    if constexpr (XWRITTEN) {
+                        double A[XPASSES], B[XPASSES];
+                        uint32_t ep[XPASSES];
+                        publication_reads(A, B, ep);
+                        const unsigned at = xbase + 16u * (unsigned)lane + (ob ? xrec_bytes : 0u);
+                        static_for(XPASS_SEQ, [&](auto p) __attribute__((always_inline)) {
+                            if (xpass_stores(p)) st16_agent_raw(rs_x, at + 1024u * (unsigned)decltype(p)::value, 0u, publication_chunk(p, A, B, ep, seq));
+                        });
+                    } else {
+                        for (int t = lane; t < XREC_CHUNKS * K; t += 64) st16_agent_raw(rs_x, xbase + 16u * (unsigned)t, ob ? xrec_bytes : 0u, chunk_of(t, seq));
+                    }
                 }
                 QSTAMP(11, qt);
                 DELAY_AT(2, true);
