@@ -122,8 +122,32 @@ typedef struct mgx_robot_desc {
  *     robot's group.  Within a group the creation order (robot id ascending, row order) and the deletion quirk (the largest
  *     out-of-range key per robot) are the existing ones.  The single-generator calls keep working on a grouped world: one shared
  *     generator, grouped search.  mgx_mission_run has ONE generator and ONE stream of comms draws: per-group many-tick runs are
- *     not part of it.
- * Everything else is per robot and does not look at the group: sweeps, prior updates, missions, trackers, run metrics, environment
+ *     not part of it;
+ *   * the GBP iteration schedule is per group with mgx_iterate_groups and mgx_mission_tick_end_groups: group g runs
+ *     steps[step_first[g] .. step_first[g + 1]), step_first [n_groups + 1] ascending from 0.  Every robot of group g runs
+ *     mgx_iterate with group g's steps, bit for bit what the same robots compute in a world of their own: beliefs, means,
+ *     covariances, factor -> variable messages, inter-robot messages, iteration_count.factor, the tracking factors' records and
+ *     mgx_message_counts.  A group whose range is empty sits the call out.
+ *     EQUAL schedules — all groups that hold live robots have byte-equal steps, an ungrouped world (n_groups 1) among them — are
+ *     the plain call with those steps, through the same door: resident launch, lingering, post merging, batches, mgx_last_sweep
+ *     and mgx_resident_stats as after mgx_iterate / mgx_mission_tick_end.
+ *     MIXED schedules run launch by launch in the segments form: each group's steps are flattened to its own [external] internal*
+ *     segments and launch k carries segment k of every group — a robot's workgroup reads its group's segment from a table in place
+ *     of the kernel's scalars, and a workgroup whose group has no segment k (fewer segments, an empty range) sits the launch out:
+ *     it stages nothing and only carries its snapshot records over where the launch writes snapshots (mgx_group_schedule_stats
+ *     counts them).  mgx_last_launch_count is the largest segment count over the groups, mgx_last_sweep reports
+ *     MGX_SWEEP_FORM_SEGMENTS.  Like every other call, a mixed call first ends a lingering launch and submits recorded schedules,
+ *     an open batch's included.  The prior updates of a mixed mgx_mission_tick_end_groups go as the kernel of their own — what
+ *     mgx_update_priors followed by mgx_iterate does: the same result (mgx_tick below).  The observer passes at the tick's end
+ *     are unchanged, and the call pairs with any of the _begin forms.
+ *     MGX_ERR_INVALID, nothing changes: steps NULL with steps to read, step_first NULL, n_groups outside 1 .. MGX_GROUPS_MAX, a
+ *     step byte with a bit that is no MGX_STEP_* (its index is named), step_first not ascending from 0, a live robot whose group
+ *     is not below n_groups.  The arguments are checked before the world is touched; a NULL world is reported last.
+ *     MGX_ERR_STATE, nothing changes: a mixed schedule on a sharded world (ghosts have no group, and every robot there is in group
+ *     0: a call whose groups do not ALL have byte-equal steps is refused, whichever of them hold robots), and on a world that has
+ *     ever switched a factor kind with mgx_set_enabled (the thaw kernels in front of a sweep are world-wide).
+ *     The open end: a mixed call is never recorded, posted or run resident.
+ * Everything else is per robot and does not look at the group: prior updates, missions, trackers, run metrics, environment
  * collisions, goal areas, the planner, the message counters.
  * Ghosts have no group: mgx_robot_add of a ghost with a non-zero group is MGX_ERR_INVALID; a ghost added to a grouped world, a
  * grouped robot added to a world with ghosts, and mgx_robot_release on a grouped world are MGX_ERR_STATE.  group >= MGX_GROUPS_MAX
@@ -242,6 +266,13 @@ int mgx_connections(mgx_world *w, int32_t robot, int32_t *others, uint32_t capac
  * merged with its neighbours into one plan.  Results are the same bit for bit; a caller that issues schedules back to back and
  * then goes silent ends with mgx_flush, mgx_synchronize or a read (any of them submits what is recorded). */
 int mgx_iterate(mgx_world *w, const uint8_t *steps, uint32_t n);
+/* mgx_iterate with one schedule per robot group (ROBOT GROUPS above):
+ * group g runs steps[step_first[g] .. step_first[g + 1]); step_first [n_groups + 1], ascending, step_first[0] == 0 */
+int mgx_iterate_groups(mgx_world *w, uint32_t n_groups, const uint8_t *steps, const uint32_t *step_first);
+/* What the per-group schedule calls of this world have done so far: calls that ran MIXED, the sweep-kernel launches of those
+ * calls, and the workgroups that sat such a launch out (counted on the host, from the plan).  Equal schedules count nowhere here:
+ * they are the plain calls.  Host bookkeeping only: no synchronisation; any pointer may be NULL. */
+int mgx_group_schedule_stats(mgx_world *w, uint64_t *mixed_calls, uint64_t *mixed_launches, uint64_t *sat_out);
 /* Batches: several schedules, one submission.  A resident schedule launch pays for itself once — the robots' graphs go
  * HBM -> LDS when it starts and back when it ends, a sixth of a ten-iteration launch at 1000 x 16 — so a caller that issues
  * schedule after schedule with nothing in between (the reference's `iterate_gbp_v2` loop run ahead of the renderer, a planner
@@ -526,6 +557,10 @@ int mgx_mission_tick_begin_groups(mgx_world *w, float comms_radius, uint32_t met
  * discards the rows that tick's _end searched ahead: this tick searches again, with the new radii. */
 int mgx_mission_tick_begin_groups_radii(mgx_world *w, const float *comms_radii, uint32_t method, uint32_t n_groups,
                                         uint64_t *number_next, int32_t despawn_finished, uint32_t *stats);
+/* mgx_mission_tick_end with one schedule per robot group in place of the one `steps` (ROBOT GROUPS above; arguments as
+ * mgx_iterate_groups).  Pairs with any of the _begin forms. */
+int mgx_mission_tick_end_groups(mgx_world *w, const uint8_t *antennas, double max_speed, double delta_t,
+                                uint32_t n_groups, const uint8_t *steps, const uint32_t *step_first);
 int mgx_mission_finished(mgx_world *w, int32_t *robots, uint32_t capacity, uint32_t *n);
 /* MANY ticks in one call: what a headless run does between two spawns (the reference's FixedUpdate chain tick after tick,
  * robot.rs:85-108, with update_failed_comms' draws in between) without the caller's interpreter in the loop —

@@ -234,6 +234,22 @@ public:
         for (size_t i = 0; i < sched.size(); i++) steps[i] = (uint8_t)((sched[i].internal ? MGX_STEP_INTERNAL : 0) | (sched[i].external ? MGX_STEP_EXTERNAL : 0));
         check(mgx_iterate(w_, steps.data(), (uint32_t)steps.size()));
     }
+    /// iterate_gbp_v2 with one schedule per robot group (mgx_iterate_groups): group g runs per_group[g], an empty one sits the call out
+    void iterate_gbp_v2_groups(const std::vector<std::vector<GbpScheduleAtIteration>> &per_group) {
+        std::vector<uint8_t> steps;
+        std::vector<uint32_t> first(1, 0u);
+        for (const auto &sched : per_group) {
+            for (const GbpScheduleAtIteration &s : sched) steps.push_back((uint8_t)((s.internal ? MGX_STEP_INTERNAL : 0) | (s.external ? MGX_STEP_EXTERNAL : 0)));
+            first.push_back((uint32_t)steps.size());
+        }
+        check(mgx_iterate_groups(w_, (uint32_t)per_group.size(), steps.data(), first.data()));
+    }
+    /// calls that ran MIXED (groups with different schedules), the sweep-kernel launches of those calls, workgroups that sat one out
+    std::array<uint64_t, 3> group_schedule_stats() {
+        std::array<uint64_t, 3> s{};
+        check(mgx_group_schedule_stats(w_, &s[0], &s[1], &s[2]));
+        return s;
+    }
     /// several iterate_gbp_v2 calls, one submission (mgx_batch_begin / mgx_batch_end): `{ auto b = world.batch(); for (...) world.iterate_gbp_v2(s); }`
     struct Batch {
         mgx_world *w;

@@ -157,6 +157,10 @@ struct XPushRec {
     unsigned long long flag_delta;
 };
 
+// One group's segment of a MIXED launch (mgx_iterate_groups, include/mgx.h; mgx_resident.h builds them): what the kernel's
+// scalars ext_mask, int_mask, n_int and hints are to a launch whose robots all run the same segment.
+struct GroupSeg { uint32_t ext_mask, int_mask; int32_t n_int; uint32_t hints; };
+
 struct DevWorld {
     int R_local, R_total, K, E;
     int V, EI, ND, NT, NI;
@@ -262,6 +266,11 @@ struct DevWorld {
     int32_t n_ranks;
     // diagnostic builds only (-DMGX_STAMPS, tools/stamps.py): per-workgroup phase cycle sums
     unsigned long long *dbg;
+    // One schedule per robot group (mgx_iterate_groups): the robots' groups by device index and the launch's segment record per
+    // group — read by the launch-per-segment instantiations only, in place of the kernel's scalars.  Both null except in the
+    // launches of a mixed call.
+    const uint32_t *group_of;   // [R_local]
+    const GroupSeg *group_seg;  // [groups]: every group a local robot is in has a record
 };
 
 // An inter-robot factor created WHILE its kind was switched off dropped the two messages that would have filled its inbox

@@ -570,6 +570,30 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
 
     double *blob = w.blob + (size_t)r * w.BS;
     const int v0 = r * K;
+    // One schedule per robot group (mgx_iterate_groups): in a mixed launch the segment is the one of the robot's GROUP — its record
+    // replaces the kernel's scalars before anything derives from them (wave-uniform: scalar loads, as k_group_rows reads its
+    // threshold).  The launch's snap_out stays world-wide: a robot that runs no internal variable sweep in a launch that writes
+    // snapshots for others carries its records of buffer `cur` over unchanged — the full path's write-back does (the external
+    // sweeps leave s_snap and s_epoch alone), and a workgroup with nothing to run at all copies them and leaves without staging
+    // its graph: what the full path leaves for an idle robot (no prior updates ride in a mixed launch).
+    if constexpr (!PERSIST) {
+        if (w.group_seg) {
+            const GroupSeg *gs = w.group_seg + __builtin_amdgcn_readfirstlane((int)w.group_of[r]);
+            ext_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs->ext_mask);
+            int_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs->int_mask);
+            n_int = __builtin_amdgcn_readfirstlane(gs->n_int);
+            hints = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs->hints);
+            if (ext_mask == 0u && !(int_mask != 0u && n_int > 0) && !w.upd) {
+                if (snap_out >= 0 && snap_out != w.cur) {
+                    const double *src = w.snap[w.cur] + (size_t)v0 * SNAP_W;
+                    double *dst = w.snap[snap_out] + (size_t)v0 * SNAP_W;
+                    for (int t = threadIdx.x; t < SNAP_W * K; t += NT) dst[t] = src[t];
+                    for (int t = threadIdx.x; t < K; t += NT) w.snap_epoch[snap_out][v0 + t] = w.snap_epoch[w.cur][v0 + t];
+                }
+                return;
+            }
+        }
+    }
     const int ie0 = HAS_IR ? w.ir_var_ptr[v0] : 0, ne = HAS_IR ? w.ir_var_ptr[v0 + K] - ie0 : 0;
     const bool ir_on = HAS_IR && (w.enable & 2u) != 0;
     const int n_dyn = 2 * (K - 1);

@@ -86,8 +86,13 @@ static void flush_counts(mgx_world *w, bool lazy) {
         }
     };
     const size_t n_log = w->clog.size();
+    // an entry's scope (CountEntry::robot): a robot's id; -1: every robot; -2 - g: the robots of group g (a launch of a mixed
+    // mgx_iterate_groups call, whose phases are per group)
+    auto out_of_scope = [w](const mgx_world::CountEntry &e, size_t r) {
+        return e.robot >= 0 ? (size_t)e.robot != r : (e.robot <= -2 && w->sets.group[r] != (uint32_t)(-2 - e.robot));
+    };
     bool world_wide_only = true;
-    for (const mgx_world::CountEntry &e : w->clog) world_wide_only = world_wide_only && e.robot < 0;
+    for (const mgx_world::CountEntry &e : w->clog) world_wide_only = world_wide_only && e.robot == -1;
     std::vector<Sum> suffix[3];  // [class: 0 on air, 1 silent, 2 idle][j]: entries j .. end applied with the gate open
     if (world_wide_only)
         for (int c = 0; c < 3; c++) {
@@ -120,7 +125,7 @@ static void flush_counts(mgx_world *w, bool lazy) {
             a.nEf += t.nEf; a.nEv += t.nEv; a.nIv += t.nIv; a.nIf += t.nIf; a.trk += t.trk; a.itf += t.itf;
         } else {
             for (const mgx_world::CountEntry &e : w->clog) {
-                if (e.robot >= 0 && (size_t)e.robot != r) continue;
+                if (out_of_scope(e, r)) continue;
                 apply(e, radio, idle, a);
             }
         }
@@ -161,7 +166,7 @@ static void flush_counts(mgx_world *w, bool lazy) {
                 const bool a_idle = (flags[o] & 2u) != 0;
                 to_own = to_foreign = 0;
                 for (const mgx_world::CountEntry &e : w->clog) {
-                    if (e.robot >= 0 && e.robot != c.owner) continue;  // per-robot launches run internal sweeps only
+                    if (out_of_scope(e, (size_t)c.owner)) continue;  // per-robot launches run internal sweeps only
                     for (uint64_t rep = 0; rep < e.times; rep++) {
                         if (e.robot < 0 && (e.ext & 1u) && radio_a)
                             for (size_t f = 0; f < c.keys.size(); f++) { to_own += c.uses[f] * (c.keys[f] & 1u); to_foreign += c.uses[f] * ((c.keys[f] >> 1) & 1u); }
@@ -205,7 +210,7 @@ static void flush_counts(mgx_world *w, bool lazy) {
                 bool filled = false;
                 for (const mgx_world::CountEntry &e : w->clog) {
                     if (filled) break;
-                    if (e.robot >= 0 && (size_t)e.robot != r) continue;
+                    if (out_of_scope(e, r)) continue;
                     for (uint64_t rep = 0; rep < e.times && !filled; rep++) {
                         if ((e.ext & 1u) && radio) itf++;
                         for (int q = 0; q < e.n_int && !filled; q++) {

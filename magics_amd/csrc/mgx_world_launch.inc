@@ -681,3 +681,109 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
     }
     return 1;
 }
+
+// ---- one schedule per robot group (include/mgx.h, ROBOT GROUPS: mgx_iterate_groups, mgx_mission_tick_end_groups) ------------------
+// What the per-group schedule calls check before anything happens: the arrays alone first (no device needed, no world either), the
+// world last, then its live robots' groups.
+static int group_schedule_arguments(mgx_world *w, uint32_t n_groups, const uint8_t *steps, const uint32_t *step_first) {
+    if (!step_first) return fail(MGX_ERR_INVALID, "null argument (step_first)");
+    if (n_groups == 0 || n_groups > MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "n_groups %u is not in 1 .. MGX_GROUPS_MAX (%u)", n_groups, MGX_GROUPS_MAX);
+    const long long bad = group_steps_check(n_groups, steps, step_first);
+    if (bad == -1) return fail(MGX_ERR_INVALID, "step_first does not ascend from 0");
+    if (bad == -2) return fail(MGX_ERR_INVALID, "null argument (steps)");
+    if (bad > 0) return fail(MGX_ERR_INVALID, "bad step %lld", bad - 1);
+    if (!w) return fail(MGX_ERR_INVALID, "null argument");
+    for (size_t r = 0; r < w->robots.size(); r++)
+        if (!w->robots[r].removed && !w->robots[r].ghost && w->sets.group[r] >= n_groups)
+            return fail(MGX_ERR_INVALID, "robot %zu is in group %u: not below n_groups %u", r, w->sets.group[r], n_groups);
+    return MGX_OK;
+}
+// Equal schedules — every group that holds live robots has byte-equal steps — ARE the plain call with those steps (*eq_steps,
+// *eq_n): true.  Otherwise the call is MIXED, and a world that cannot run one is refused here, before anything changes (*rc).
+static bool group_schedule_is_plain(mgx_world *w, uint32_t n_groups, const uint8_t *steps, const uint32_t *step_first, const uint8_t **eq_steps,
+                                    uint32_t *eq_n, int *rc) {
+    std::vector<uint8_t> live((size_t)n_groups, 0);
+    for (size_t r = 0; r < w->robots.size(); r++)
+        if (!w->robots[r].removed && !w->robots[r].ghost) live[w->sets.group[r]] = 1;
+    uint32_t first = n_groups;
+    *rc = MGX_OK;
+    const bool sharded = std::find(w->sets.ghost.begin(), w->sets.ghost.end(), (uint8_t)1) != w->sets.ghost.end() || w->xres.connected ||
+                         w->direct.connected || w->rccl.connected;
+    if (sharded) {  // (every robot is in group 0 there: only a call whose groups ALL have the same steps says what the world runs)
+        const std::vector<uint8_t> all((size_t)n_groups, 1);
+        if (!group_steps_equal(n_groups, steps, step_first, all.data(), &first)) {
+            *rc = fail(MGX_ERR_STATE, "groups with different schedules on a sharded world: ghosts have no group");
+            return false;
+        }
+    }
+    if (group_steps_equal(n_groups, steps, step_first, live.data(), &first)) {
+        *eq_steps = first < n_groups && steps ? steps + step_first[first] : nullptr;
+        *eq_n = first < n_groups ? step_first[first + 1] - step_first[first] : 0u;
+        return true;
+    }
+    if (w->frozen_live || w->ir_frozen_live || w->thaw_kinds || w->ir_thaw_active || w->n_keyless > 0)
+        *rc = fail(MGX_ERR_STATE, "groups with different schedules on a world that has switched a factor kind (mgx_set_enabled): the thaw kernels are world-wide");
+    return false;
+}
+// The launches of a MIXED call: launch k carries segment k of every group (GroupPlan, mgx_resident.h), launch by launch in the
+// segments form — never recorded, posted or resident.  The caller has ended a lingering launch and submitted what was recorded
+// (MGX_ENTER).  The robots' groups by device index go up only when the layout has changed them; the call's segment records travel
+// through the pinned ring into device memory, ONE copy for all its launches.
+static int run_group_plan(mgx_world *w, const GroupPlan &gp) {
+    int rc = commit(w);
+    if (rc != MGX_OK) return rc;
+    if ((rc = check_device_error(w)) != MGX_OK) return rc;
+    mgx_world::GroupSchedules &gs = w->gsched;
+    gs.mixed_calls++;
+    const size_t RL = (size_t)w->d.R_local;
+    if (gp.n_launches == 0 || RL == 0) return MGX_OK;
+    // (a robot that has left keeps its group: every group on the device has a record, all-zero — sits out — beyond n_groups)
+    std::vector<uint32_t> now(RL);
+    size_t top = gp.n_groups;
+    for (size_t dr = 0; dr < RL; dr++) {
+        now[dr] = w->sets.group[(size_t)w->robot_of[dr]];
+        top = std::max(top, (size_t)now[dr] + 1);
+    }
+    if (now != gs.group_of || !gs.group_of_d.p) {
+        gs.group_of.swap(now);
+        HIP_TRY(gs.group_of_d.upload(gs.group_of, w->stream, (size_t)std::max(w->R_cap, 0)));
+        HIP_TRY(hipStreamSynchronize(w->stream));  // (pageable memory: the copy has left it)
+    }
+    std::vector<uint32_t> members(top, 0u);
+    for (size_t dr = 0; dr < RL; dr++) members[gs.group_of[dr]]++;
+    const size_t n_rec = gp.n_launches * top;
+    {
+        void *hp = nullptr;
+        int slot = 0;
+        HIP_TRY(w->stage.acquire(sizeof(GroupSeg) * n_rec, &hp, &slot));
+        GroupSeg *rec = (GroupSeg *)hp;
+        std::fill(rec, rec + n_rec, GroupSeg{0u, 0u, 0, 0u});
+        for (size_t k = 0; k < gp.n_launches; k++) std::copy(gp.launch(k), gp.launch(k) + gp.n_groups, rec + k * top);
+        if (n_rec > gs.seg_d.cap) HIP_TRY(hipStreamSynchronize(w->stream));  // (an array that has to grow is freed first: nothing may still read it)
+        HIP_TRY(gs.seg_d.reserve(n_rec));
+        HIP_TRY(hipMemcpyAsync(gs.seg_d.p, hp, sizeof(GroupSeg) * n_rec, hipMemcpyHostToDevice, w->stream));
+        HIP_TRY(w->stage.release(slot, w->stream));
+    }
+    w->stale_kinds |= ~w->p.enable_mask & 15u;  // disabled factors miss what these sweeps deliver
+    for (size_t k = 0; k < gp.n_launches; k++) {
+        const bool writes_snap = gp.writes_snap[k] != 0;
+        if (gp.any_ext[k]) w->res.backoff.external_iteration();
+        w->d.group_of = gs.group_of_d.p;
+        w->d.group_seg = gs.seg_d.p + k * top;
+        const hipError_t e = launch_robot_sweep(w->d, 0, w->d.R_local, 0u, 0u, 0, writes_snap ? 1 - w->d.cur : -1, 0u, w->stream, &w->last_sweep);
+        w->d.group_of = nullptr;
+        w->d.group_seg = nullptr;
+        HIP_TRY(e);
+        w->last_sweep_form = MGX_SWEEP_FORM_SEGMENTS;
+        w->last_sweep_launches++;
+        gs.mixed_launches++;
+        if (writes_snap) w->d.cur ^= 1;
+        for (size_t g = 0; g < top; g++) {  // the counters' log, scoped by group; the workgroups that sat the launch out, from the plan
+            const GroupSeg none{0u, 0u, 0, 0u};
+            const GroupSeg &sg = g < gp.n_groups ? gp.launch(k)[g] : none;
+            if (sits_out(sg)) gs.sat_out += members[g];
+            else if (members[g]) log_launch(w, -2 - (int)g, sg.ext_mask, sg.int_mask, sg.n_int);
+        }
+    }
+    return MGX_OK;
+}

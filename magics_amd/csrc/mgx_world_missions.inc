@@ -2,7 +2,6 @@
 // Part of ONE translation unit: included by mgx_world.hip (which says in which order, and why one unit).
 extern "C" {
 // ---- missions on the device (SURVEY §8 f1) ---------------------------------------------------------------------------
-static std::vector<Launch> plan_launches(const uint8_t *steps, uint32_t n);
 static int mission_download(mgx_world *w) {  // device -> host copies of what the device advances (before the arrays are laid out again)
     mgx_world::Mission &ms = w->mission;
     if (!ms.uploaded) return MGX_OK;
@@ -250,9 +249,28 @@ static int observers_tick_end(mgx_world *w, const float *pos_d, const uint8_t *a
     return MGX_OK;
 }
 
+static int mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed, double delta_t, const uint8_t *steps, uint32_t n_steps, const GroupPlan *mixed);
 int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed, double delta_t, const uint8_t *steps, uint32_t n_steps) {
     MGX_ENTER(w);
     if (!w || (!steps && n_steps)) return fail(MGX_ERR_INVALID, "null argument");
+    return mission_tick_end(w, antennas, max_speed, delta_t, steps, n_steps, nullptr);
+}
+// ... with one schedule per robot group (include/mgx.h, ROBOT GROUPS): equal schedules are the call above; a mixed one runs the
+// prior updates as the kernel of their own and then the groups' segments launch by launch (run_group_plan)
+int mgx_mission_tick_end_groups(mgx_world *w, const uint8_t *antennas, double max_speed, double delta_t, uint32_t n_groups, const uint8_t *steps,
+                                const uint32_t *step_first) {
+    int rc = group_schedule_arguments(w, n_groups, steps, step_first);
+    if (rc != MGX_OK) return rc;
+    const uint8_t *eq_steps = nullptr;
+    uint32_t eq_n = 0;
+    if (group_schedule_is_plain(w, n_groups, steps, step_first, &eq_steps, &eq_n, &rc)) return mgx_mission_tick_end(w, antennas, max_speed, delta_t, eq_steps, eq_n);
+    if (rc != MGX_OK) return rc;
+    MGX_ENTER(w);
+    const GroupPlan gp = plan_group_launches(n_groups, steps, step_first);
+    return mission_tick_end(w, antennas, max_speed, delta_t, nullptr, 0, &gp);
+}
+// mixed (may be null): the groups' own segments in place of the one schedule `steps`
+static int mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed, double delta_t, const uint8_t *steps, uint32_t n_steps, const GroupPlan *mixed) {
     mgx_world::Mission &ms = w->mission;
     if (!ms.in_tick) return fail(MGX_ERR_STATE, "mgx_mission_tick_end without mgx_mission_tick_begin");
     ms.in_tick = false;
@@ -322,8 +340,11 @@ int mgx_mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_speed
     w->last_sweep_launches = 0;
     w->last_sweep = SweepRan{};
     w->last_sweep_form = -1;
-    const bool fuse = !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0;
-    if (!fuse) {
+    const bool fuse = !mixed && !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0;
+    if (mixed) {
+        HIP_TRY(launch_update_priors(w->d, R, ms.robots_d.p, ms.waypoints_d.p, ms.ts_list_d.p, ms.what_d.p, max_speed, delta_t, s));
+        rc = run_group_plan(w, *mixed);
+    } else if (!fuse) {
         HIP_TRY(launch_update_priors(w->d, R, ms.robots_d.p, ms.waypoints_d.p, ms.ts_list_d.p, ms.what_d.p, max_speed, delta_t, s));
         rc = iterate_now(w, steps, n_steps);
     } else {
@@ -456,30 +477,6 @@ int mgx_sweep(mgx_world *w, int32_t robot, uint32_t external_phases, uint32_t in
     if (n_internal > 1 && internal_phases != 3u) return fail(MGX_ERR_INVALID, "fused iterations need both internal phases");
     const uint32_t h = ((hints & MGX_HINT_NEXT_STARTS_EXTERNAL) && (external_phases & 1u)) ? HINT_IR_DEAD : 0u;
     return sweep(w, robot, external_phases, internal_phases << 2, internal_phases ? (int)n_internal : 0, h);
-}
-
-// the launches of a schedule: phases I / E flattened (robot.rs:1787-1860: internal first, then external, per
-// step) and grouped into launches of the form [E] I* (one workgroup-resident pass each)
-static std::vector<Launch> plan_launches(const uint8_t *steps, uint32_t n) {
-    std::vector<uint8_t> ph;
-    for (uint32_t i = 0; i < n; i++) {
-        if (steps[i] & MGX_STEP_INTERNAL) ph.push_back('I');
-        if (steps[i] & MGX_STEP_EXTERNAL) ph.push_back('E');
-    }
-    std::vector<Launch> out;
-    size_t i = 0;
-    while (i < ph.size()) {
-        Launch l{0u, 0, 0u};
-        if (ph[i] == 'E') { l.ext = PH_EXT_FACTOR | PH_EXT_VARIABLE; i++; }
-        while (i < ph.size() && ph[i] == 'I') { l.n_int++; i++; }
-        // the next launch of this call (if any) starts with an external phase: the inter-robot messages
-        // this launch computes are recomputed before anything reads their HBM copy
-        l.hints = (l.ext && i < ph.size()) ? HINT_IR_DEAD : 0u;
-        // later launches of this call that run a variable sweep rewrite the belief images (nothing reads them in between)
-        for (size_t j = i; j < ph.size(); j++) l.hints |= (ph[j] == 'E') ? HINT_LATER_EXT_VARIABLE : HINT_LATER_INT_VARIABLE;
-        out.push_back(l);
-    }
-    return out;
 }
 
 }  // extern "C" (continued in the next part)

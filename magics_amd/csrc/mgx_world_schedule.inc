@@ -130,6 +130,31 @@ int mgx_iterate(mgx_world *w, const uint8_t *steps, uint32_t n) {
     return MGX_OK;
 }
 
+// One schedule per robot group (include/mgx.h, ROBOT GROUPS).  Equal schedules are mgx_iterate itself — the same door, so resident
+// launches, lingering, post merging and batches are as ever; a mixed call runs launch by launch (run_group_plan).
+int mgx_iterate_groups(mgx_world *w, uint32_t n_groups, const uint8_t *steps, const uint32_t *step_first) {
+    int rc = group_schedule_arguments(w, n_groups, steps, step_first);
+    if (rc != MGX_OK) return rc;
+    const uint8_t *eq_steps = nullptr;
+    uint32_t eq_n = 0;
+    if (group_schedule_is_plain(w, n_groups, steps, step_first, &eq_steps, &eq_n, &rc)) return mgx_iterate(w, eq_steps, eq_n);
+    if (rc != MGX_OK) return rc;
+    MGX_ENTER(w);  // (ends a lingering launch and submits what was recorded, an open batch's schedules included)
+    if ((rc = check_device_error(w)) != MGX_OK) return rc;
+    MGX_CONFIRM(w);  // (a declined launch is run again here: not this call's launches)
+    w->last_sweep_launches = 0;
+    w->last_sweep = SweepRan{};
+    w->last_sweep_form = -1;
+    return run_group_plan(w, plan_group_launches(n_groups, steps, step_first));
+}
+int mgx_group_schedule_stats(mgx_world *w, uint64_t *mixed_calls, uint64_t *mixed_launches, uint64_t *sat_out) {
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (mixed_calls) *mixed_calls = w->gsched.mixed_calls;
+    if (mixed_launches) *mixed_launches = w->gsched.mixed_launches;
+    if (sat_out) *sat_out = w->gsched.sat_out;
+    return MGX_OK;
+}
+
 static int iterate_now(mgx_world *w, const uint8_t *steps, uint32_t n) { return iterate_plan(w, plan_launches(steps, n)); }
 static int iterate_plan(mgx_world *w, const std::vector<Launch> &plan) {
     const int rcc = confirm_held(w);  // (a declined launch is run again here: not this call's launches)

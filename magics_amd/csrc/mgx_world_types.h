@@ -694,7 +694,15 @@ struct mgx_world {
         uint32_t schedules = 0, submissions = 0, launches = 0;
         uint32_t implicit = 0;  // schedules in `steps` that mgx_iterate recorded by itself, outside a batch (post merging)
     } batch;
-    ResidentLaunches res;  // resident and lingering schedule launches: their words and tables, the launch not yet decided, the open launch and its post
+    // One schedule per robot group (mgx_iterate_groups): the robots' groups by device index as they were uploaded last (again only
+    // when the layout has changed them), the segment records of a mixed call's launches, and what mgx_group_schedule_stats reports
+    struct GroupSchedules {
+        std::vector<uint32_t> group_of;  // [R_local] what group_of_d holds
+        DevBuf<uint32_t> group_of_d;
+        DevBuf<GroupSeg> seg_d;          // [launches of the call][groups]
+        uint64_t mixed_calls = 0, mixed_launches = 0, sat_out = 0;
+    } gsched;
+    ResidentLaunches res;// resident and lingering schedule launches: their words and tables, the launch not yet decided, the open launch and its post
     int sticky_rc = 0;       // a declined launch whose re-run failed inside a call that cannot report it (flush_counts): every
                              // later sweep, read-back and mgx_synchronize reports it (check_device_error)
     // what the per-tick table rebuild reads of EVERY connection, 16 bytes apiece beside the connections themselves (168 bytes and
@@ -918,7 +926,7 @@ struct mgx_world {
     SweepRan last_sweep;               // the sweep instantiation it launched last (mgx_last_sweep) ...
     int32_t last_sweep_form = -1;      // ... and in which form (MGX_SWEEP_FORM_*; -1: none)
     // message counters are advanced lazily: launches and prior changes are only logged here
-    struct CountEntry { uint8_t ext, in; int n_int, robot; uint64_t times; };
+    struct CountEntry { uint8_t ext, in; int n_int, robot; uint64_t times; };  // robot: an id; -1: every robot; -2 - g: the robots of group g
     std::vector<CountEntry> clog;
     int n_keyless = 0;  // connections whose factors still lack inbox keys (IrConn::keys)
     std::vector<uint32_t> cp_pending;  // [robot * K + variable] change_prior calls not yet counted

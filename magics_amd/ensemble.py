@@ -11,7 +11,8 @@ once (mission_tick_begin_groups, mission_tick_end) and runs the parts of `Simula
 device's collision logs and tracker sample log are drained once and their records routed to the members by robot id.
 
 Per member (per group of the world): the seed, the comms failure rate, the formations, max-time — and the comms radius, which the
-grouped search holds per group (mission_tick_begin_groups with one radius per member).  The per-robot observers — environment
+grouped search holds per group (mission_tick_begin_groups with one radius per member), and the GBP iteration schedule
+(mission_tick_end with one schedule per member: mgx_mission_tick_end_groups).  The per-robot observers — environment
 collisions, goal areas, the run metrics — do not look at the group: the first member switches them on for the world, and every
 member reads its own robots' part."""
 import copy
@@ -21,6 +22,7 @@ import numpy as np
 from . import config as _config
 from . import hostlib
 from .sim import Simulation
+from .world import group_steps
 
 UNSUPPORTED = ("global_planner",)
 # the observers an Ensemble runs on the device, and what the world has to offer for each
@@ -33,7 +35,7 @@ def _shared_settings(sc):
     """everything the world holds once, as (key, value) in the order it is compared"""
     cfg = sc["config"]
     out = [("params." + k, v) for k, v in _config.world_params(cfg).items()]
-    out += [("gbp.iteration-schedule", cfg["gbp"]["iteration-schedule"]), ("gbp.lookahead-multiple", cfg["gbp"]["lookahead-multiple"]),
+    out += [("gbp.lookahead-multiple", cfg["gbp"]["lookahead-multiple"]),
             ("robot.target-speed", cfg["robot"]["target-speed"]),
             ("robot.planning-horizon", cfg["robot"]["planning-horizon"]), ("simulation.hz", cfg["simulation"]["hz"]),
             ("simulation.despawn-robot-when-final-waypoint-reached", cfg["simulation"]["despawn-robot-when-final-waypoint-reached"]),
@@ -199,9 +201,9 @@ class Ensemble:
     def __init__(self, scenarios, world, **simulation_options):
         """scenarios: one scenario dict per member (config.load_scenario, tests/golden/scenarios.json); member m's robots are in
         group m of `world`, a fresh World made with config.world_params of any of them.  The members may differ in
-        simulation.prng-seed, robot.communication.failure-rate, robot.communication.radius (and max-time) and in their formations;
-        everything the world holds once must be equal (ValueError names the first key that differs; a world that takes no radius
-        per group holds the radius once, too).  simulation_options go to every member's Simulation, so the members share them —
+        simulation.prng-seed, robot.communication.failure-rate, robot.communication.radius, gbp.iteration-schedule (and max-time) and
+        in their formations; everything the world holds once must be equal (ValueError names the first key that differs; a world
+        that takes no radius or no schedule per group holds that once, too).  simulation_options go to every member's Simulation, so the members share them —
         goal_areas among them.  An Ensemble runs device missions with device robot-robot collisions and device trackers, and on
         request the device's other observers: environment_collisions=True, goal_areas, device_metrics (with sample_log=False if
         asked).  Still refused, with NotImplementedError: global_planner (and so rrt-star formations) — a per-group many-tick run
@@ -230,9 +232,11 @@ class Ensemble:
             if any(f["planning-strategy"] != "only-local" for f in sc["formation"]["formations"]):
                 raise NotImplementedError(f"Ensemble: member {m} has an rrt-star formation; the global planner is not supported in this version")
         per_group_radius = hasattr(world, "neighbours_groups")   # (the engine's grouped search: one comms radius per group)
+        per_group_steps = hasattr(world, "group_schedule_stats")  # (mgx_mission_tick_end_groups: one iteration schedule per group)
 
         def shared(sc):
-            return _shared_settings(sc) + ([] if per_group_radius else [("robot.communication.radius", sc["config"]["robot"]["communication"]["radius"])])
+            return (_shared_settings(sc) + ([] if per_group_steps else [("gbp.iteration-schedule", sc["config"]["gbp"]["iteration-schedule"])]) +
+                    ([] if per_group_radius else [("robot.communication.radius", sc["config"]["robot"]["communication"]["radius"])]))
         first = shared(scenarios[0])
         for m, sc in enumerate(scenarios[1:], 1):
             for (key, a), (_, b) in zip(first, shared(sc)):
@@ -248,6 +252,8 @@ class Ensemble:
         self._logging = True      # the device appends the trackers' samples to its log (sample_log)
         self._goals = False       # goal areas are on: their clock is the ensemble's
         self._per_group_radius = per_group_radius
+        self._per_group_steps = per_group_steps
+        self._steps_for = self._steps = None   # the tick's schedule(s) as handed to the world, and the retired flags they were packed for
         self._log_room = 0        # room of the device's sample log (what the first member enabled the trackers with)
         self._log_bound = 0       # samples the log holds at the most since it was last drained
         self._dist = np.zeros(0)
@@ -327,11 +333,24 @@ class Ensemble:
                     if antennas is None:
                         antennas = np.ones(len(self._owner), dtype=np.uint8)
                     antennas[m._view.ids] = ant
-            w.mission_tick_end(s0.steps, float(s0.max_speed), float(s0.dt32), antennas=antennas)
+            w.mission_tick_end(self._tick_steps(s0), float(s0.max_speed), float(s0.dt32), antennas=antennas)
             self._clock = self.tick_no + 1
         for m in active:
             m.sim.tick_no += 1
         self.tick_no += 1
+
+    def _tick_steps(self, s0):
+        """the tick's schedule: one per member where the world takes that and the members differ in it — a retired member's group
+        holds no robot any more and gets an empty range — packed once for as long as nobody retires; else the one schedule"""
+        if not self._per_group_steps:
+            return s0.steps
+        retired = tuple(m.retired for m in self.members)
+        if retired != self._steps_for:
+            per = [[] if m.retired else list(m.sim.steps) for m in self.members]
+            live = [s for s in per if s]
+            self._steps = live[0] if all(s == live[0] for s in live) else group_steps(per)
+            self._steps_for = retired
+        return self._steps
 
     def _retire(self, m):
         """the member's run is over: trackers flushed, export and metrics frozen, its remaining robots out of the world"""

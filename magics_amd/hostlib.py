@@ -152,6 +152,8 @@ SYMBOLS = {
                                         C.POINTER(C.c_uint64)]),
     "mgx_connections": (C.c_int, [_V, C.c_int32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_iterate": (C.c_int, [_V, C.c_char_p, C.c_uint32]),
+    "mgx_iterate_groups": (C.c_int, [_V, C.c_uint32, C.c_char_p, C.c_void_p]),
+    "mgx_group_schedule_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mgx_batch_begin": (C.c_int, [_V]),
     "mgx_batch_end": (C.c_int, [_V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mgx_sweep": (C.c_int, [_V, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -210,6 +212,7 @@ SYMBOLS = {
     "mgx_mission_tick_begin_groups_radii": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p]),
     "mgx_mission_run": (C.c_int, [_V, C.c_void_p]),
     "mgx_mission_tick_end": (C.c_int, [_V, C.c_void_p, C.c_double, C.c_double, C.c_char_p, C.c_uint32]),
+    "mgx_mission_tick_end_groups": (C.c_int, [_V, C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_char_p, C.c_void_p]),
     "mgx_mission_finished": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_mission_translations": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_mission_read": (C.c_int, [_V, C.c_void_p, C.c_void_p, C.c_void_p]),

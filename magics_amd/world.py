@@ -5,6 +5,7 @@ crates/magics/src/factorgraph/factorgraph.rs and crates/magics/src/planner/robot
 (``internal_factor_iteration``, ``change_prior`` ...).  ``FactorGraph`` is the per-robot
 handle a reference user would hold (a Bevy component there, ``(world, robot_id)`` here).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -34,6 +35,50 @@ def group_radii(radius, n_groups):
     if radii.ndim != 1 or len(radii) != n_groups:
         raise ValueError(f"one comms radius per group: got shape {radii.shape} for {n_groups} groups")
     return radii
+
+
+GroupSteps = collections.namedtuple("GroupSteps", "steps first")   # one schedule per group, packed (group_steps)
+_SEQUENCES = (list, tuple, bytes, bytearray, np.ndarray)
+
+
+def _per_group(steps):
+    """the cheap look World.iterate / mission_tick_end take at every call's schedule — it is issued every tick: one schedule per
+    group when its first entry is itself a schedule (group_steps then checks all of it), or when it has been packed already"""
+    if type(steps) is GroupSteps:
+        return steps
+    if isinstance(steps, (bytes, bytearray)) or len(steps) == 0 or not isinstance(steps[0], _SEQUENCES):
+        return None
+    return group_steps(steps)
+
+
+def group_steps(steps):
+    """the schedule of an iterate / mission_tick_end call as the engine takes it: None for ONE schedule (bytes, or a sequence of
+    MGX_STEP_* values: the plain call), else one schedule per group, by group id, packed as GroupSteps(steps bytes, first
+    [n_groups + 1] u32) for mgx_iterate_groups — group g runs steps[first[g]:first[g + 1]], an empty one sits the call out.
+    ValueError for a sequence that mixes the two, or that nests deeper.  A caller that issues the same schedules tick after tick
+    packs them once and hands the GroupSteps in."""
+    if type(steps) is GroupSteps:
+        return steps
+    if isinstance(steps, (bytes, bytearray)):
+        return None
+    items = list(steps)
+    def depth(x):   # 0: a step value; 1: a schedule (bytes, or a flat sequence of step values); -1: anything else
+        if isinstance(x, (bytes, bytearray)):
+            return 1
+        if isinstance(x, (list, tuple)):
+            return 1 if all(not isinstance(v, (bytes, bytearray, list, tuple)) and np.ndim(v) == 0 for v in x) else -1
+        return {0: 0, 1: 1}.get(np.ndim(x), -1)
+    depths = [depth(x) for x in items]
+    if -1 in depths:
+        raise ValueError("one schedule per group: every schedule is a flat sequence of step values")
+    if 1 not in depths:
+        return None
+    if 0 in depths:
+        raise ValueError("one schedule per group: got step values and schedules in one sequence")
+    packed = [bytes(x) if isinstance(x, (bytes, bytearray)) else bytes(bytearray(int(v) for v in x)) for x in items]
+    first = np.zeros(len(packed) + 1, dtype=np.uint32)
+    first[1:] = np.cumsum([len(b) for b in packed], dtype=np.uint64)
+    return GroupSteps(b"".join(packed), first)
 
 
 def make_params(p):
@@ -247,6 +292,12 @@ class World:
 
     # -- hot path ----------------------------------------------------------------------------
     def iterate(self, steps):
+        """steps: one schedule, or one schedule per robot group (group_steps above: mgx_iterate_groups)"""
+        per_group = _per_group(steps)
+        if per_group is not None:
+            b, first = per_group
+            self._chk(self._L.mgx_iterate_groups(self._w, len(first) - 1, b, first.ctypes.data))
+            return
         # (a tick's schedule is issued over and over: its byte string is made once — building it costs more host time than the call)
         key = steps if isinstance(steps, (bytes, tuple)) else tuple(steps)
         b = _STEP_BYTES.get(key)
@@ -462,7 +513,14 @@ class World:
         return nxt, stats[:n_groups], fin
 
     def mission_tick_end(self, steps, max_speed, delta_t, antennas=None):
+        """steps: one schedule, or one schedule per robot group (group_steps above: mgx_mission_tick_end_groups)"""
         ant = None if antennas is None else np.ascontiguousarray(antennas, dtype=np.uint8)
+        per_group = _per_group(steps)
+        if per_group is not None:
+            b, first = per_group
+            self._chk(self._L.mgx_mission_tick_end_groups(self._w, None if ant is None else ant.ctypes.data, float(max_speed), float(delta_t),
+                                                          len(first) - 1, b, first.ctypes.data))
+            return
         self._chk(self._L.mgx_mission_tick_end(self._w, None if ant is None else ant.ctypes.data, float(max_speed), float(delta_t),
                                                bytes(bytearray(steps)), len(steps)))
 
@@ -798,6 +856,13 @@ class World:
         """(resident launches so far, declined ones, what is left of the back-off after the last declined one)"""
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint32()
         self._chk(self._L.mgx_resident_stats(self._w, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def group_schedule_stats(self):
+        """(iterate / mission_tick_end calls that ran MIXED — groups with different schedules —, the sweep-kernel launches of those
+        calls, workgroups that sat such a launch out): mgx_group_schedule_stats"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self._L.mgx_group_schedule_stats(self._w, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
     def is_thawing(self):

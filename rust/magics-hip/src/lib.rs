@@ -129,6 +129,27 @@ impl World {
     pub fn iterate(&self, steps: &[u8]) -> Result<(), MgxError> {
         check(unsafe { sys::mgx_iterate(self.raw, steps.as_ptr(), steps.len() as u32) })
     }
+    /// `iterate` with one schedule per robot group (`mgx_iterate_groups`): group g runs `steps[step_first[g] .. step_first[g + 1]]`,
+    /// `step_first` ascending from 0, one entry more than there are groups; an empty range sits the call out.
+    pub fn iterate_groups(&self, steps: &[u8], step_first: &[u32]) -> Result<(), MgxError> {
+        assert!(!step_first.is_empty() && *step_first.last().unwrap() as usize <= steps.len());
+        check(unsafe { sys::mgx_iterate_groups(self.raw, (step_first.len() - 1) as u32, steps.as_ptr(), step_first.as_ptr()) })
+    }
+    /// The second half of a mission tick with one schedule per robot group (`mgx_mission_tick_end_groups`); `antennas`: one byte
+    /// per robot of the world, or none.
+    pub fn mission_tick_end_groups(&self, antennas: Option<&[u8]>, max_speed: f64, delta_t: f64, steps: &[u8], step_first: &[u32]) -> Result<(), MgxError> {
+        assert!(!step_first.is_empty() && *step_first.last().unwrap() as usize <= steps.len());
+        let ant = antennas.map_or(std::ptr::null(), |a| a.as_ptr());
+        check(unsafe {
+            sys::mgx_mission_tick_end_groups(self.raw, ant, max_speed, delta_t, (step_first.len() - 1) as u32, steps.as_ptr(), step_first.as_ptr())
+        })
+    }
+    /// (calls that ran mixed — groups with different schedules —, the sweep-kernel launches of those calls, workgroups that sat one out)
+    pub fn group_schedule_stats(&self) -> Result<(u64, u64, u64), MgxError> {
+        let (mut calls, mut launches, mut sat_out) = (0u64, 0u64, 0u64);
+        check(unsafe { sys::mgx_group_schedule_stats(self.raw, &mut calls, &mut launches, &mut sat_out) })?;
+        Ok((calls, launches, sat_out))
+    }
     /// Several `iterate` calls, one submission (`mgx_batch_begin` / `mgx_batch_end`): the schedules issued inside `f` are recorded and
     /// submitted together, merged into as few resident launches as their segments fit; same results, bit for bit.
     /// Returns (schedules recorded, sweep-kernel launches they were submitted as).

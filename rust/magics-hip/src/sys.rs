@@ -282,6 +282,8 @@ extern "C" {
     pub fn mgx_neighbours_groups(w: *mut mgx_world, positions_xyz: *const f32, radii: *const f32, n_groups: u32, method: u32, row_ptr: *mut i32, neighbours_out: *mut i32, capacity: u64, needed: *mut u64) -> c_int;
     pub fn mgx_connections(w: *mut mgx_world, robot: i32, others: *mut i32, capacity: u32, n: *mut u32) -> c_int;
     pub fn mgx_iterate(w: *mut mgx_world, steps: *const u8, n: u32) -> c_int;
+    pub fn mgx_iterate_groups(w: *mut mgx_world, n_groups: u32, steps: *const u8, step_first: *const u32) -> c_int;
+    pub fn mgx_group_schedule_stats(w: *mut mgx_world, mixed_calls: *mut u64, mixed_launches: *mut u64, sat_out: *mut u64) -> c_int;
     pub fn mgx_batch_begin(w: *mut mgx_world) -> c_int;
     pub fn mgx_batch_end(w: *mut mgx_world, n_schedules: *mut u32, n_launches: *mut u32) -> c_int;
     pub fn mgx_last_launch_count(w: *mut mgx_world, n_launches: *mut u32) -> c_int;
@@ -316,6 +318,7 @@ extern "C" {
     pub fn mgx_mission_tick_end(w: *mut mgx_world, antennas: *const u8, max_speed: f64, delta_t: f64, steps: *const u8, n_steps: u32) -> c_int;
     pub fn mgx_mission_tick_begin_groups(w: *mut mgx_world, comms_radius: f32, method: u32, n_groups: u32, number_next: *mut u64, despawn_finished: i32, stats: *mut u32) -> c_int;
     pub fn mgx_mission_tick_begin_groups_radii(w: *mut mgx_world, comms_radii: *const f32, method: u32, n_groups: u32, number_next: *mut u64, despawn_finished: i32, stats: *mut u32) -> c_int;
+    pub fn mgx_mission_tick_end_groups(w: *mut mgx_world, antennas: *const u8, max_speed: f64, delta_t: f64, n_groups: u32, steps: *const u8, step_first: *const u32) -> c_int;
     pub fn mgx_mission_finished(w: *mut mgx_world, robots: *mut i32, capacity: u32, n: *mut u32) -> c_int;
     pub fn mgx_mission_run(w: *mut mgx_world, desc: *mut mgx_mission_run_desc) -> c_int;
     pub fn mgx_mission_translations(w: *mut mgx_world, translations: *mut f32, capacity_robots: u32, n_robots: *mut u32) -> c_int;

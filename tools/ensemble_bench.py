@@ -1,9 +1,11 @@
 """Many scenario runs as ONE Ensemble against the same runs one after another (profiles/ensemble.md).
 
-Three workloads, all from tests/golden/scenarios.json: the reference's communications-failure experiment as its script runs it — 5
+Four workloads, all from tests/golden/scenarios.json: the reference's communications-failure experiment as its script runs it — 5
 seeds x 8 failure rates, 21 robots per run: 40 members —, the Environment Obstacles Experiment with 32 seeds, and the Varying Network
 Connectivity Experiment as its script runs it — 5 seeds x comms radii 20 / 40 / 60 / 80, 30 robots per run: 20 members that differ in
-their comms radius.  For each:
+their comms radius —, and a subset of the Iteration Amount Experiment as its script runs it — the script's 5 seeds x internal 1 / 5 / 21
+x external 1 / 5 / 21 of its 1, 2, 3, 5, 8, 13, 21, 34 each, 25 robots per run: 45 members that differ in their GBP iteration
+schedule, so the ensemble's ticks run MIXED (launches per tick and the workgroups that sat launches out are reported).  For each:
   ensemble   the members as robot groups of one world (magics_amd/ensemble.py): wall time, member ticks per second, the kernel the
              neighbour search ran, the resident schedule launches (ran / declined);
   solo       the same members one after another, each a Simulation on a world of its own: run(chunk=1) and run(chunk=256).
@@ -46,18 +48,21 @@ with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") a
     known = json.load(f)
 
 
-def members(name, seeds, rates, radii=(None,)):
+def members(name, seeds, rates, radii=(None,), amounts=(None,)):
     out = []
-    for radius in radii:
-        for rate in rates:
-            for seed in seeds:
-                sc = copy.deepcopy(known[name])
-                sc["config"]["simulation"]["prng-seed"] = seed
-                if rate is not None:
-                    sc["config"]["robot"]["communication"]["failure-rate"] = rate
-                if radius is not None:
-                    sc["config"]["robot"]["communication"]["radius"] = radius
-                out.append(sc)
+    for amount in amounts:
+        for radius in radii:
+            for rate in rates:
+                for seed in seeds:
+                    sc = copy.deepcopy(known[name])
+                    sc["config"]["simulation"]["prng-seed"] = seed
+                    if rate is not None:
+                        sc["config"]["robot"]["communication"]["failure-rate"] = rate
+                    if radius is not None:
+                        sc["config"]["robot"]["communication"]["radius"] = radius
+                    if amount is not None:
+                        sc["config"]["gbp"]["iteration-schedule"].update({"internal": amount[0], "external": amount[1]})
+                    out.append(sc)
     return out
 
 
@@ -66,6 +71,8 @@ WORKLOADS = {
     "environment-obstacles 32 seeds": lambda: members("Environment Obstacles Experiment", list(range(100, 132)), [None]),
     "network-connectivity 5 seeds x 4 radii": lambda: members("Varying Network Connectivity Experiment", [0, 31, 227, 252, 805], [None],
                                                               [20.0, 40.0, 60.0, 80.0]),
+    "iteration-amount 5 seeds x 3 internal x 3 external": lambda: members("Iteration Amount Experiment", [0, 31, 227, 252, 805], [None],
+                                                                          amounts=[(i, e) for i in (1, 5, 21) for e in (1, 5, 21)]),
 }
 
 
@@ -93,10 +100,17 @@ def run_ensemble(scs):
     wall = time.perf_counter() - t0
     ran, declined, _ = e.world.resident_stats()
     lingered, posted = e.world.linger_stats()[:2]
+    mixed = {}
+    if hasattr(e.world, "group_schedule_stats"):
+        calls, launches, sat_out = e.world.group_schedule_stats()
+        if calls:   # (workgroup launches: one per robot on the device and launch — the world's robots at the end stand for all of them)
+            most = launches * e.world.num_robots()[0]
+            mixed = {"mixed_calls": calls, "mixed_launches": launches, "launches_per_mixed_call": round(launches / calls, 2), "sat_out": sat_out,
+                     "workgroup_launches_at_most": most, "sat_out_share_at_least": round(sat_out / max(most, 1), 4)}
     # (mgx_last_search names the kernel of the last search that launched one: the last tick with robots alive)
     return wall, sum(m.tick_no for m in e.members), {"world_ticks": e.tick_no, "robots": e.world.num_robots()[0], "search_kernel": e.world.last_search()[0],
                                                       "resident_launches": ran, "resident_declined": declined, "lingered_launches": lingered,
-                                                      "schedules_posted": posted}
+                                                      "schedules_posted": posted, **mixed}
 
 
 result = {"max_time": max_time, "reps": reps, "observers": observers, "workloads": {}}

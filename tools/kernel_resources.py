@@ -1,4 +1,4 @@
-"""Diagnostics: registers, spills and scratch of every k_robot_sweep instantiation (hipcc -Rpass-analysis=kernel-resource-usage).
+"""Diagnostics: registers, spills, scratch and static LDS of every k_robot_sweep instantiation (hipcc -Rpass-analysis=kernel-resource-usage).
 usage: python tools/kernel_resources.py [extra hipcc flags ...]"""
 import os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
@@ -25,7 +25,7 @@ for line in out.splitlines():
     m = re.search(r"remark:\s+([A-Za-z ]+?)(?: \[[^\]]*\])?: (\d+)", line)
     if m and cur:
         rows[cur][m.group(1).strip()] = int(m.group(2))
-print(f"{'kernel':44s} {'VGPR':>5s} {'AGPR':>5s} {'v-spill':>8s} {'s-spill':>8s} {'scratch':>8s} {'occ':>4s}")
+print(f"{'kernel':44s} {'VGPR':>5s} {'AGPR':>5s} {'SGPR':>5s} {'v-spill':>8s} {'s-spill':>8s} {'scratch':>8s} {'LDS':>6s} {'occ':>4s}")
 table = []
 for name, r in rows.items():
     m = re.match(r"_ZN3mgx13k_robot_sweepILi(n?\d+)ELi(\d)ELb(\d)ELb(\d)EE", name)
@@ -35,5 +35,5 @@ for name, r in rows.items():
     table.append((k, int(m.group(2)), int(m.group(3)), int(m.group(4)), r))
 for k, irm, per, sh, r in sorted(table, key=lambda t: (t[0] <= 0, t[0], t[1], t[2], t[3])):
     label = f"k_robot_sweep<{k:>3d}, {irm}, {'true ' if per else 'false'}{', shard' if sh else ''}>"
-    print(f"{label:44s} {r.get('VGPRs', 0):5d} {r.get('AGPRs', 0):5d} "
-          f"{r.get('VGPRs Spill', 0):8d} {r.get('SGPRs Spill', 0):8d} {r.get('ScratchSize', 0):8d} {r.get('Occupancy', 0):4d}")
+    print(f"{label:44s} {r.get('VGPRs', 0):5d} {r.get('AGPRs', 0):5d} {r.get('TotalSGPRs', 0):5d} "
+          f"{r.get('VGPRs Spill', 0):8d} {r.get('SGPRs Spill', 0):8d} {r.get('ScratchSize', 0):8d} {r.get('LDS Size', 0):6d} {r.get('Occupancy', 0):4d}")

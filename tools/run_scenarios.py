@@ -14,15 +14,18 @@ sample is logged on the device and the robots' positions / velocities lists stay
 "junction" is the two exits of the reference's junction scenario, FILE.json holds a list of boxes [[x0, z0], [x1, z1]]; each
 scenario's line then carries the arrivals per area and the throughput the reference's analyse-junction-scenario.py reads out of an
 export (robots that started within 50 s and arrived, per second).  --export DIR writes each scenario's export to DIR/<name>.json.
---ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] runs the cross product of ONE scenario —
-every seed with every failure rate and every comms radius (default: the scenario's own) — as one Ensemble (magics_amd/ensemble.py):
+--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:INTERNAL:EXTERNAL,..]
+runs the cross product of ONE scenario — every seed with every failure rate, every comms radius and every GBP iteration schedule
+(KIND: centered, soon-as-possible, late-as-possible, interleave-evenly, half-beginning-half-end; default each: the scenario's own)
+— as one Ensemble (magics_amd/ensemble.py):
 the members are robot groups of one world, one launch per schedule and one synchronisation per tick for all of them, each member
 identical to the same run alone.  One line per member — with --environment-collisions, --goal-areas and --metrics (with or
 without --no-sample-log) it carries the member's contacts, arrivals and the means of its run metrics; with --export DIR one
-export per member, DIR/<name>.seed<A>.rate<X>.radius<R>.json.  The global planner and host trackers do not run in an Ensemble.
+export per member, DIR/<name>.seed<A>.rate<X>.radius<R>[.<kind>-<internal>-<external>].json.  The global planner and host trackers do not run in an Ensemble.
 usage: python tools/run_scenarios.py [--max-time S] [--goal-areas junction|FILE.json] [--export DIR] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
            [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N]
-           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..]] [scenario-dir | name ...]"""
+           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..]]
+           [scenario-dir | name ...]"""
 import copy
 import json
 import os
@@ -94,8 +97,18 @@ if "--ensemble-comms-radii" in args:
     i = args.index("--ensemble-comms-radii")
     ensemble_radii = [float(x) for x in args[i + 1].split(",")]
     del args[i:i + 2]
-if (ensemble_rates or ensemble_radii) and not ensemble_seeds:
-    sys.exit("--ensemble-failure-rates and --ensemble-comms-radii need --ensemble-seeds")
+ensemble_schedules = None
+if "--ensemble-schedules" in args:
+    i = args.index("--ensemble-schedules")
+    ensemble_schedules = []
+    for word in args[i + 1].split(","):
+        kind, internal, external = word.split(":")
+        if kind not in config.SCHEDULE_KINDS:
+            sys.exit(f"--ensemble-schedules: {kind!r} is none of {sorted(config.SCHEDULE_KINDS)}")
+        ensemble_schedules.append({"schedule": kind, "internal": int(internal), "external": int(external)})
+    del args[i:i + 2]
+if (ensemble_rates or ensemble_radii or ensemble_schedules) and not ensemble_seeds:
+    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii and --ensemble-schedules need --ensemble-seeds")
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 if ensemble_seeds:
@@ -106,14 +119,17 @@ if ensemble_seeds:
         sys.exit("--ensemble-seeds: the global planner and host trackers do not run in an Ensemble (magics_amd/ensemble.py says why)")
     base = config.load_scenario(args[0]) if os.path.isdir(args[0]) else known[args[0]]
     members = []
-    for radius in ensemble_radii or [base["config"]["robot"]["communication"]["radius"]]:
-        for rate in ensemble_rates or [base["config"]["robot"]["communication"]["failure-rate"]]:
-            for seed in ensemble_seeds:
-                sc = copy.deepcopy(base)
-                sc["config"]["simulation"]["prng-seed"] = seed
-                sc["config"]["robot"]["communication"]["failure-rate"] = rate
-                sc["config"]["robot"]["communication"]["radius"] = radius
-                members.append((seed, rate, radius, sc))
+    for schedule in ensemble_schedules or [None]:
+        for radius in ensemble_radii or [base["config"]["robot"]["communication"]["radius"]]:
+            for rate in ensemble_rates or [base["config"]["robot"]["communication"]["failure-rate"]]:
+                for seed in ensemble_seeds:
+                    sc = copy.deepcopy(base)
+                    sc["config"]["simulation"]["prng-seed"] = seed
+                    sc["config"]["robot"]["communication"]["failure-rate"] = rate
+                    sc["config"]["robot"]["communication"]["radius"] = radius
+                    if schedule is not None:
+                        sc["config"]["gbp"]["iteration-schedule"].update(schedule)
+                    members.append((seed, rate, radius, sc))
     t0 = time.perf_counter()
     e = ensemble.Ensemble([sc for *_, sc in members], World(config.world_params(base["config"])), environment_collisions=env_collisions,
                           device_metrics=metrics, sample_log=not no_sample_log, goal_areas=goal_areas)
@@ -125,7 +141,9 @@ if ensemble_seeds:
         done = [r for r in s.robots if r["completed"]]
         trav = [r["travelled"] for r in s.robots]
         figures = m.metrics() if metrics or env_collisions or goal_areas else None
+        sch = sc["config"]["gbp"]["iteration-schedule"]
         print(json.dumps({"scenario": sc.get("name", args[0]), "seed": seed, "failure_rate": rate, "comms_radius": radius,
+                          **({"schedule": f"{sch['schedule']}:{sch['internal']}:{sch['external']}"} if ensemble_schedules else {}),
                           "simulated_s": round(s.elapsed(), 1),
                           "robots": len(s.robots), "finished": len(done), "all_finished": s.finished(), "K": s.K,
                           "mean_distance": round(sum(trav) / max(1, len(trav)), 1),
@@ -137,9 +155,11 @@ if ensemble_seeds:
                              if metrics else {})}), flush=True)
         if export_dir:
             os.makedirs(export_dir, exist_ok=True)
-            with open(os.path.join(export_dir, f"{stem}.seed{seed}.rate{rate:g}.radius{radius:g}.json"), "w", encoding="utf-8") as f:
+            tail = f".{sch['schedule']}-{sch['internal']}-{sch['external']}" if ensemble_schedules else ""
+            with open(os.path.join(export_dir, f"{stem}.seed{seed}.rate{rate:g}.radius{radius:g}{tail}.json"), "w", encoding="utf-8") as f:
                 json.dump(m.export(), f)
-    print(json.dumps({"ensemble": len(members), "ticks": e.tick_no, "member_ticks": sum(m.tick_no for m in e.members), "wall_s": round(wall, 2),
+    mixed_calls, mixed_launches, sat_out = e.world.group_schedule_stats()
+    print(json.dumps({"ensemble": len(members), "ticks": e.tick_no, "mixed_calls": mixed_calls, "mixed_launches": mixed_launches, "sat_out": sat_out, "member_ticks": sum(m.tick_no for m in e.members), "wall_s": round(wall, 2),
                       "member_ticks_per_s": round(sum(m.tick_no for m in e.members) / wall, 1)}), flush=True)
     sys.exit(0)
 names = args or [n for n, sc in sorted(known.items())
