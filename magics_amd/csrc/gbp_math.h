@@ -157,7 +157,9 @@ MGX_HD bool belief_update(const double (&eta)[4], const double (&lam)[16], doubl
     if (fin) {
 #pragma unroll
         for (int r = 0; r < 4; r++)
-            mu[r] = ((cov[r * 4 + 0] * eta[0] + cov[r * 4 + 1] * eta[1]) + cov[r * 4 + 2] * eta[2]) + cov[r * 4 + 3] * eta[3];
+            // (variable.rs:284 is ndarray's dot: a sum that STARTS at +0.0 — it shows only in the sign of a zero: products that are
+            // all -0.0 sum to +0.0 there, and to -0.0 without the leading term)
+            mu[r] = (((0.0 + cov[r * 4 + 0] * eta[0]) + cov[r * 4 + 1] * eta[1]) + cov[r * 4 + 2] * eta[2]) + cov[r * 4 + 3] * eta[3];
     }
     return true;
 }

@@ -1355,7 +1355,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                 double cq[4];
 #pragma unroll
                 for (int c = 0; c < 4; c++) cq[c] = cov_img[(q * 4 + c) * K + i];
-                mu_q = ((cq[0] * eta[0] + cq[1] * eta[1]) + cq[2] * eta[2]) + cq[3] * eta[3];
+                mu_q = (((0.0 + cq[0] * eta[0]) + cq[1] * eta[1]) + cq[2] * eta[2]) + cq[3] * eta[3];  // (from +0.0: belief_update)
             }
         }
     };

@@ -139,12 +139,15 @@ def _grid(K, n, seed, tracking):
             del S.HORIZON_FOR_K[K]
 
 
-def make_script(seed, n_ops=20):
+def make_script(seed, n_ops=20, K=None, tracking=None):
+    """K, tracking: None for the seed's own; given, they replace it and nothing else — the draws are the same (tests/group_fuzz.py:
+    the scripts that share a world share the horizon and the kinds of factors)"""
     rng = np.random.default_rng(seed)
     sp = Script(seed)
-    K = int(KS[int(rng.integers(0, len(KS)))])
+    own_K = int(KS[int(rng.integers(0, len(KS)))])
+    K = own_K if K is None else int(K)
     n = int(rng.integers(6, 13))
-    tracking = seed % 2 == 0
+    tracking = seed % 2 == 0 if tracking is None else bool(tracking)
     sc = _grid(K, n, seed, tracking)
     n0 = n - HELD_BACK
     # the held-back robots' order keys run against their ids: whatever sorts by key must not get away with sorting by id
@@ -487,10 +490,11 @@ def _compare(script, step, eng, ref):
     assert got == want, f"{what}: message counts of robots {live}: {got} != {want}"
 
 
-def run(script, eng, ref, upto=None):
+def run(script, eng, ref, upto=None, at_compare=None):
     """the script (its operations 0 .. upto) on both sides, compared at its compare points and at the end; eng None: the oracle
     alone.  Returns a Result: whether the oracle's beliefs were finite at every compare point, its final beliefs, the engine's
-    trace.  A failed comparison carries the seed, the step and every operation up to it."""
+    trace.  A failed comparison carries the seed, the step and every operation up to it.  at_compare(step, ref): called at every
+    compare point (tests/group_fuzz.py takes the oracle's state there)."""
     res = Result()
     last = len(script.ops) - 1 if upto is None else min(upto, len(script.ops) - 1)
     script.reset("oracle")
@@ -514,6 +518,8 @@ def run(script, eng, ref, upto=None):
                                  f"{script.reserve}, scenario {script.scenario['name']}): {type(e).__name__}: {e}\n"
                                  f"{script.describe(step)}") from e
         res.finite.append(all(np.isfinite(x).all() for x in ref.read_beliefs()))
+        if at_compare is not None:
+            at_compare(step, ref)
         first = step + 1
     res.final = ref.read_beliefs()
     if eng is not None:

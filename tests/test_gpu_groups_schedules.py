@@ -63,28 +63,40 @@ def scenario_of(g):
 
 
 class Pair:
-    """the shared world and the groups' own worlds, driven alike; ids[g][i]: the shared world's id of robot i of group g"""
+    """the shared world and the groups' own worlds, driven alike; ids[g][i]: the shared world's id of robot i of group g.
 
-    def __init__(self, reserve=0):
-        self.scs = [scenario_of(g) for g in range(GROUPS)]
+    The defaults are this file's world.  scs: one scenario per group (its last robot is held back for a spawn where sizes[g] leaves
+    it out); sizes: robots per group; alone: what makes a group's own world from the scenario's params (tests/
+    test_gpu_groups_kernel_matrix.py hands in the CPU oracle); radius: the comms radius of topology(); group_ids: the shared
+    world's group id of every group here, n_groups: how many groups the per-group calls name (the ones in between hold no robot)"""
+
+    def __init__(self, reserve=0, scs=None, sizes=None, alone=World, radius=RADIUS, spawn_group=SPAWN_GROUP, group_ids=None, n_groups=None):
+        self.scs = scs if scs is not None else [scenario_of(g) for g in range(GROUPS)]
+        self.n, self.K, self.radius = len(self.scs), self.scs[0]["K"], radius
+        self.sizes = list(sizes) if sizes is not None else [PER_GROUP] * self.n
+        self.gid = list(group_ids) if group_ids is not None else list(range(self.n))
+        self.n_groups = n_groups if n_groups is not None else max(self.gid) + 1
         sdf = self.scs[0]["sdf"]
-        self.shared, self.alone = World(self.scs[0]["params"]), [World(sc["params"]) for sc in self.scs]
+        self.shared, self.alone = World(self.scs[0]["params"]), [alone(sc["params"]) for sc in self.scs]
         for w in [self.shared] + self.alone:
             w.set_sdf(sdf["rgb"], sdf["world_w"], sdf["world_h"])
         if reserve:
-            self.shared.reserve(GROUPS * PER_GROUP + reserve)
-            self.alone[SPAWN_GROUP].reserve(PER_GROUP + reserve)
-        self.ids = [[] for _ in range(GROUPS)]
+            self.shared.reserve(sum(self.sizes) + reserve)
+            if hasattr(self.alone[spawn_group], "reserve"):
+                self.alone[spawn_group].reserve(self.sizes[spawn_group] + reserve)
+        self.ids = [[] for _ in range(self.n)]
+        self.gone = set()                     # (g, i) of the robots that have been removed
         self.key = 0
-        for i in range(PER_GROUP):            # ids interleaved across the groups
-            for g in range(GROUPS):
-                self.add(g, i)
-        self.nxt, self.nxt_alone = np.ones(GROUPS, np.uint64), [1] * GROUPS
+        for i in range(max(self.sizes)):      # ids interleaved across the groups
+            for g in range(self.n):
+                if i < self.sizes[g]:
+                    self.add(g, i)
+        self.nxt, self.nxt_alone = np.ones(self.n_groups, np.uint64), [1] * self.n
         self.created = self.deleted = 0
 
     def add(self, g, i):
         rb = self.scs[g]["robots"][i]
-        self.ids[g].append(self.shared.add_robot(rb["mean0"], rb["prior_diag"], rb["dt"], rb["radius"], path=rb["path"], order_key=self.key, group=g))
+        self.ids[g].append(self.shared.add_robot(rb["mean0"], rb["prior_diag"], rb["dt"], rb["radius"], path=rb["path"], order_key=self.key, group=self.gid[g]))
         assert self.alone[g].add_robot(rb["mean0"], rb["prior_diag"], rb["dt"], rb["radius"], path=rb["path"], order_key=self.key) == i
         self.key += 1
 
@@ -95,46 +107,62 @@ class Pair:
         """one pass over the robots' start positions; robot i of every group with i in `far` is out of everybody's range"""
         n = sum(len(x) for x in self.ids)
         pos_shared = np.zeros((n, 3), dtype=F)
-        for g in range(GROUPS):
+        for g in range(self.n):
             pos = np.array([[rb["pos"][0] + (5000.0 * (i + 1) if i in far else 0.0), 0.5, rb["pos"][1]] for i, rb in enumerate(self.robots(g))], dtype=F)
             pos_shared[self.ids[g]] = pos
-            self.nxt_alone[g], c, d = self.alone[g].update_topology(pos, RADIUS, self.nxt_alone[g])
+            self.nxt_alone[g], c, d = self.alone[g].update_topology(pos, self.radius, self.nxt_alone[g])
             self.created, self.deleted = self.created + c, self.deleted + d
-        self.nxt, stats = self.shared.update_topology_groups(pos_shared, RADIUS, self.nxt)
-        assert [int(x) for x in self.nxt] == self.nxt_alone
+        self.nxt, stats = self.shared.update_topology_groups(pos_shared, self.radius, self.nxt)
+        assert [int(self.nxt[q]) for q in self.gid] == self.nxt_alone
 
     def prior_changes(self):
-        by_id = {self.ids[g][i]: rb for g in range(GROUPS) for i, rb in enumerate(self.robots(g))}
+        by_id = {self.ids[g][i]: rb for g in range(self.n) for i, rb in enumerate(self.robots(g)) if (g, i) not in self.gone}
         every = {"robots": [by_id[r] for r in sorted(by_id)], "target_speed": self.scs[0]["target_speed"]}
-        self.shared.update_priors(**S.tick_inputs(every, HZ))
+        self.shared.update_priors(**dict(S.tick_inputs(every, HZ), robots=np.array(sorted(by_id), dtype=np.int32)))
         for g, w in enumerate(self.alone):
-            w.update_priors(**S.tick_inputs({"robots": self.robots(g), "target_speed": self.scs[g]["target_speed"]}, HZ))
+            live = [i for i in range(len(self.ids[g])) if (g, i) not in self.gone]
+            if live:
+                w.update_priors(**dict(S.tick_inputs({"robots": [self.robots(g)[i] for i in live], "target_speed": self.scs[g]["target_speed"]}, HZ),
+                                       robots=np.array(live, dtype=np.int32)))
 
     def flags(self, antenna_off=None, idle=None):
         for g, w in enumerate(self.alone):
             for i, rid in enumerate(self.ids[g]):
+                if (g, i) in self.gone:
+                    continue
                 for world, r in ((self.shared, rid), (w, i)):
                     world.set_antenna(r, i != antenna_off)
                     world.set_idle(r, i == idle)
 
+    def per_group_of_world(self, per_group):
+        """one schedule per group of the SHARED world: the groups here by their group id there, an empty one for every other id"""
+        if self.gid == list(range(self.n_groups)):
+            return per_group
+        out = [[] for _ in range(self.n_groups)]
+        for g, steps in enumerate(per_group):
+            out[self.gid[g]] = steps
+        return out
+
     def iterate(self, per_group):
-        self.shared.iterate(per_group)
+        self.shared.iterate(self.per_group_of_world(per_group))
         for g, w in enumerate(self.alone):
-            if len(per_group[g]):
+            if len(per_group[g]) and len(self.gone & {(g, i) for i in range(len(self.ids[g]))}) < len(self.ids[g]):
                 w.iterate(per_group[g])
 
     def beliefs(self):
         n = sum(len(x) for x in self.ids)
-        return [a.reshape((n, K) + a.shape[1:]) for a in self.shared.read_beliefs()]
+        return [a.reshape((n, self.K) + a.shape[1:]) for a in self.shared.read_beliefs()]
 
     def same(self, what):
         bs = self.beliefs()
         for g, w in enumerate(self.alone):
             sel = np.array(self.ids[g])
             for name, a, b in zip(("eta", "lam", "mean"), bs, w.read_beliefs()):
-                b = b.reshape((len(sel), K) + b.shape[1:])
+                b = b.reshape((len(sel), self.K) + b.shape[1:])
                 assert np.array_equal(a[sel].view(np.uint64), b.view(np.uint64)), (what, g, name)
             for i, rid in enumerate(self.ids[g]):
+                if (g, i) in self.gone:
+                    continue
                 assert self.shared.message_counts(rid) == w.message_counts(i), (what, g, i)
                 assert self.shared.connections(rid) == [self.ids[g][j] for j in w.connections(i)], (what, g, i)
 

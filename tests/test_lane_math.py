@@ -187,6 +187,30 @@ def test_belief_update_rules(H):
     assert (mu2 == 7).all() and (cov2 == 7).all()
 
 
+def test_belief_mean_sums_from_plus_zero(H):
+    """variable.rs:284 computes the mean with ndarray's dot (numeric_util::unrolled_dot, as the oracle restates it): a sum that
+    STARTS at +0.0.  It shows only in the sign of a zero — four products that are all -0.0 sum to +0.0 there and to -0.0 when the
+    sum starts at the first product — and the beliefs are compared as bit patterns (tests/test_gpu_groups_kernel_matrix.py)."""
+    import itertools
+    lam = 2.0 * np.eye(4)
+    all_negative_zero = 0
+    for eta in itertools.product((0.0, -0.0, 1.5, -1.5), repeat=4):
+        eta = np.array(eta)
+        mu, cov, valid = np.full(4, 7.0), np.full((4, 4), 7.0), C.c_int(0)
+        H.h_belief(dp(eta), dp(lam), dp(mu), dp(cov), C.byref(valid))
+        assert valid.value == 1
+        want = np.zeros(4)
+        for r in range(4):
+            s = 0.0
+            products = [float(cov[r, c]) * float(eta[c]) for c in range(4)]
+            for x in products:
+                s = s + x
+            want[r] = s
+            all_negative_zero += all(x == 0.0 and np.signbit(x) for x in products)
+        assert np.array_equal(mu.view(np.uint64), want.view(np.uint64)), (eta, mu, want)
+    assert all_negative_zero > 0
+
+
 def test_tracking_message_vs_oracle_world(H):
     # drive the oracle's tracking factor through a one-robot world and the lane function with the
     # same linearisation points; state (record, last measurement) must evolve identically
