@@ -146,7 +146,32 @@ typedef struct mgx_robot_desc {
  *     MGX_ERR_STATE, nothing changes: a mixed schedule on a sharded world (ghosts have no group, and every robot there is in group
  *     0: a call whose groups do not ALL have byte-equal steps is refused, whichever of them hold robots), and on a world that has
  *     ever switched a factor kind with mgx_set_enabled (the thaw kernels in front of a sweep are world-wide).
- *     The open end: a mixed call is never recorded, posted or run resident.
+ *     The open end: a mixed call is never recorded, posted or run resident;
+ *   * the enabled factor kinds (gbp.factors-enabled) are per group with mgx_set_group_enabled: every factor of a robot of group g
+ *     is enabled iff its kind's bit is set in group g's mask.  A group that was never given a mask has the world's
+ *     (mgx_params.enable_mask, or what mgx_set_enabled made of it), and a mask equal to the world's is no mask at all: the group
+ *     follows the world as if the call had not been made.  The INTERNAL kinds may differ from the world's (MGX_FACTOR_DYNAMIC,
+ *     _OBSTACLE, _TRACKING: bits 1, 4, 8).  The inter-robot bit must equal the world's — it decides residency, keyless factors and
+ *     the inter-robot freeze world-wide — MGX_ERR_INVALID otherwise.
+ *     A group's kinds are fixed for the life of the group: the call is accepted only while no robot of that group has ever been
+ *     added (group 0 counts like any other), MGX_ERR_STATE afterwards.  So a factor of a switched-off kind is off FROM ITS
+ *     CREATION and never switched on: it receives nothing, not even the empty message of add_internal_edge
+ *     (factorgraph.rs:304-330, mgx_message_counts); it sends nothing; its variable does not deliver to it
+ *     (factorgraph.rs:695,781) — what the same robots do in a world of their own created with that mask in mgx_params, bit for
+ *     bit, as everything else of a group.
+ *     A world is MASKED while some group's mask differs from the world's.  A masked world runs EVERY schedule launch by launch,
+ *     as mixed schedules run: mgx_iterate, mgx_iterate_groups, mgx_tick, mgx_mission_tick_end(_groups), open batches and the
+ *     world-wide mgx_sweep / mgx_*_iteration calls become launches in which every workgroup reads its group's kinds from a table
+ *     beside the group's segment record (equal schedules: every group the same segments); a per-robot fine-grained call hands
+ *     the kinds of that robot's group to its launch.  Prior updates go as the kernel of their own, as in mixed calls.  Never
+ *     recorded, posted or resident: mgx_last_sweep reports MGX_SWEEP_FORM_SEGMENTS.  mgx_group_enabled_stats counts the schedules
+ *     (and world-wide sweeps) that ran this way BECAUSE of the masks; mixed calls keep counting in mgx_group_schedule_stats.
+ *     An unmasked world, grouped or not, takes exactly the code paths it took before the call existed.
+ *     MGX_ERR_STATE, nothing changes: a world that has switched a factor kind at run time (mgx_set_enabled with robots: freeze
+ *     and thaw are world-wide), a world with ghosts or an engine-side exchange.  On a masked world mgx_set_enabled with a mask
+ *     other than the world's and mgx_mission_run (one generator, one schedule: one group's) are MGX_ERR_STATE.
+ *     The arguments are checked first and need no device: unknown kind bits, then group >= MGX_GROUPS_MAX (both
+ *     MGX_ERR_INVALID), a NULL world or out-pointer last.
  * Everything else is per robot and does not look at the group: prior updates, missions, trackers, run metrics, environment
  * collisions, goal areas, the planner, the message counters.
  * Ghosts have no group: mgx_robot_add of a ghost with a non-zero group is MGX_ERR_INVALID; a ghost added to a grouped world, a
@@ -273,6 +298,13 @@ int mgx_iterate_groups(mgx_world *w, uint32_t n_groups, const uint8_t *steps, co
  * calls, and the workgroups that sat such a launch out (counted on the host, from the plan).  Equal schedules count nowhere here:
  * they are the plain calls.  Host bookkeeping only: no synchronisation; any pointer may be NULL. */
 int mgx_group_schedule_stats(mgx_world *w, uint64_t *mixed_calls, uint64_t *mixed_launches, uint64_t *sat_out);
+/* The enabled factor kinds of ONE robot group (ROBOT GROUPS above): kind_mask of MGX_FACTOR_* bits, set before the group's first
+ * robot is added.  _get answers what a robot added to the group now would run under. */
+int mgx_set_group_enabled(mgx_world *w, uint32_t group, uint32_t kind_mask);
+int mgx_get_group_enabled(mgx_world *w, uint32_t group, uint32_t *kind_mask);
+/* What the masks have cost so far: schedules (and world-wide fine-grained sweeps) that ran as group plans only because the world
+ * is masked, and the sweep-kernel launches of those.  Host bookkeeping only: no synchronisation; either pointer may be NULL. */
+int mgx_group_enabled_stats(mgx_world *w, uint64_t *masked_plans, uint64_t *masked_launches);
 /* Batches: several schedules, one submission.  A resident schedule launch pays for itself once — the robots' graphs go
  * HBM -> LDS when it starts and back when it ends, a sixth of a ten-iteration launch at 1000 x 16 — so a caller that issues
  * schedule after schedule with nothing in between (the reference's `iterate_gbp_v2` loop run ahead of the renderer, a planner

@@ -250,6 +250,19 @@ public:
         check(mgx_group_schedule_stats(w_, &s[0], &s[1], &s[2]));
         return s;
     }
+    /// gbp.factors-enabled of ONE robot group (mgx_set_group_enabled): before the group's first robot is added; the inter-robot bit is the world's
+    void set_group_enabled(uint32_t group, uint32_t kind_mask) { check(mgx_set_group_enabled(w_, group, kind_mask)); }
+    uint32_t group_enabled(uint32_t group) {
+        uint32_t m = 0;
+        check(mgx_get_group_enabled(w_, group, &m));
+        return m;
+    }
+    /// schedules that ran as group plans only because the world is masked, and the sweep-kernel launches of those
+    std::array<uint64_t, 2> group_enabled_stats() {
+        std::array<uint64_t, 2> s{};
+        check(mgx_group_enabled_stats(w_, &s[0], &s[1]));
+        return s;
+    }
     /// several iterate_gbp_v2 calls, one submission (mgx_batch_begin / mgx_batch_end): `{ auto b = world.batch(); for (...) world.iterate_gbp_v2(s); }`
     struct Batch {
         mgx_world *w;

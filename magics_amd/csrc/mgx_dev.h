@@ -271,6 +271,10 @@ struct DevWorld {
     // launches of a mixed call.
     const uint32_t *group_of;   // [R_local]
     const GroupSeg *group_seg;  // [groups]: every group a local robot is in has a record
+    // Enabled factor kinds per robot group (mgx_set_group_enabled): the INTERNAL kinds (bits 1, 4, 8) of every group, read beside
+    // the group's segment record where `enable` is read otherwise — `enable & 2u` stays the world's.  Null unless the world is
+    // MASKED (some group's kinds differ from the world's); a masked world's launches all carry segment records.
+    const uint32_t *group_enable;  // [groups], as group_seg
 };
 
 // An inter-robot factor created WHILE its kind was switched off dropped the two messages that would have filled its inbox

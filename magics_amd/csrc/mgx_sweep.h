@@ -576,9 +576,19 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     // snapshots for others carries its records of buffer `cur` over unchanged — the full path's write-back does (the external
     // sweeps leave s_snap and s_epoch alone), and a workgroup with nothing to run at all copies them and leaves without staging
     // its graph: what the full path leaves for an idle robot (no prior updates ride in a mixed launch).
+    // The enabled INTERNAL kinds are the group's as well where the world is masked (mgx_set_group_enabled: DevWorld::group_enable),
+    // one more scalar of the same kind; `kinds()` is what every read of bits 1, 4 and 8 goes through.  Resident launches never
+    // read the table (a masked world runs none): theirs is the kernel argument itself, as ever.
+    uint32_t group_kinds = w.enable;
+    auto kinds = [&]() __attribute__((always_inline)) -> uint32_t {
+        if constexpr (PERSIST) return w.enable;
+        else return group_kinds;
+    };
     if constexpr (!PERSIST) {
         if (w.group_seg) {
-            const GroupSeg *gs = w.group_seg + __builtin_amdgcn_readfirstlane((int)w.group_of[r]);
+            const int g = __builtin_amdgcn_readfirstlane((int)w.group_of[r]);
+            const GroupSeg *gs = w.group_seg + g;
+            if (w.group_enable) group_kinds = (uint32_t)__builtin_amdgcn_readfirstlane((int)w.group_enable[g]);
             ext_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs->ext_mask);
             int_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs->int_mask);
             n_int = __builtin_amdgcn_readfirstlane(gs->n_int);
@@ -650,7 +660,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
         dyn_other_edge = (1 - slot) * (K - 1) + f;
     }
     // obstacle factors: four lanes per factor when they fit one wave and no tracking lanes are needed
-    const bool obs_rows = (4 * (K - 2) <= 64) && !(w.enable & 8u);
+    const bool obs_rows = (4 * (K - 2) <= 64) && !(kinds() & 8u);
     // UV wave, factor phase (otherwise): obstacle lanes [0, K-2), tracking lanes [K-2, 2(K-2))
     const int uvar = (is_trk ? lane - (K - 2) : lane) + 1;  // variable of the unary factor
     const int uedge = n_dyn + lane;                         // its internal-edge column
@@ -1475,7 +1485,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     auto unary_messages = [&](uint32_t skip, double *s_out, int itf_gate) __attribute__((always_inline)) {
         if (obs_rows) {
             // four lanes per obstacle factor: lane q samples tap q and writes row q of the message
-            if (role == ROLE_UF && lane < 4 * (K - 2) && (w.enable & 4u) && !(skip & 4u)) {
+            if (role == ROLE_UF && lane < 4 * (K - 2) && (kinds() & 4u) && !(skip & 4u)) {
                 const int j = lane >> 2, q = lane & 3, var = j + 1, col = n_dyn + j;
                 double x0[4];
                 const bool pres = s_epoch[var] > 0;
@@ -1492,7 +1502,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
 #pragma unroll
                 for (int c = 0; c < 4; c++) s_out[(4 + q * 4 + c) * E1 + col] = lam_q[c];
             }
-        } else if (is_obs && (w.enable & 4u) && !(skip & 4u)) {
+        } else if (is_obs && (kinds() & 4u) && !(skip & 4u)) {
             double x0[4], oe[4], ol[16];
             const bool pres = s_epoch[uvar] > 0;
 #pragma unroll
@@ -1508,7 +1518,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
 #pragma unroll
             for (int c = 0; c < 16; c++) s_out[(4 + c) * E1 + uedge] = ol[c];
         }
-        if (is_trk && (w.enable & 8u) && itf_gate >= 10 && !(skip & 8u)) {  // factorgraph.rs:701
+        if (is_trk && (kinds() & 8u) && itf_gate >= 10 && !(skip & 8u)) {  // factorgraph.rs:701
             double x0[4], oe[4], ol[16];
 #pragma unroll
             for (int c = 0; c < 4; c++) x0[c] = s_snap[(20 + c) * K + uvar];
@@ -1527,7 +1537,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
         }
         // horizons beyond 33 variables: tracking factors K-2+64 .. 2(K-2)-1 have no lane of their own; lanes
         // 0 .. of the UV wave take them on, with their state in HBM (BIG instantiations only)
-        if (BIG && role == ROLE_UF && lane + 64 >= K - 2 && lane + 64 < 2 * (K - 2) && (w.enable & 8u) && itf_gate >= 10 &&
+        if (BIG && role == ROLE_UF && lane + 64 >= K - 2 && lane + 64 < 2 * (K - 2) && (kinds() & 8u) && itf_gate >= 10 &&
             !(skip & 8u)) {
             const int j2 = lane + 64 - (K - 2), var2 = j2 + 1, col2 = n_dyn + (K - 2) + j2, item2 = r * (K - 2) + j2;
             double x0[4], oe[4], ol[16];
@@ -1946,7 +1956,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                 // (the unary factors linearise at the means of the last INTERNAL sweep, which this external one does not touch:
                 // with four waves they run beside it)
                 if (prefired && (NW == 4 || role == ROLE_UV)) unary_messages(0u, s_sh, itf);
-                if (prefired && is_dyn && (w.enable & 1u)) dynamic_messages(s_sh);
+                if (prefired && is_dyn && (kinds() & 1u)) dynamic_messages(s_sh);
                 QSTAMP(6, qt);
                 if (keep_means) have_xmu = true;
                 if (ir_on && is_last_ext_seg) {  // the plan's last external iteration: the means go to HBM (robot.rs:1842-1858)
@@ -1990,7 +2000,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
             // The unary factors do not either (they linearise at the means of the last INTERNAL sweep): the UV wave
             // runs them right after its finish instead of idling until the DYN wave is done.
             prefired = !early && radio && n_int_k > 0 && !idle && (int_k & PH_INT_FACTOR) && skip0 == 0u;  // same for the whole workgroup
-            if (prefired && is_dyn && (w.enable & 1u)) dynamic_messages(s_fv);
+            if (prefired && is_dyn && (kinds() & 1u)) dynamic_messages(s_fv);
             if (PERSIST && early && radio && role == ROLE_DYN) adopt_early(lane, 64);  // the sums above were the last readers of the old messages
             if (radio && is_var) variable_finish(s_sum, false);
             if (prefired) unary_messages(0u, s_fv, itf);
@@ -2041,7 +2051,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
             if ((int_k & PH_INT_FACTOR) && it == 0 && prefired) {
                 itf += 1;  // this sweep ran next to the external variable sweep, in front of that block's last barrier
             } else if (int_k & PH_INT_FACTOR) {
-                if (is_dyn && (w.enable & 1u) && !(it == 0 && (skip0 & 1u))) dynamic_messages(s_fv);
+                if (is_dyn && (kinds() & 1u) && !(it == 0 && (skip0 & 1u))) dynamic_messages(s_fv);
                 // UV wave: first the belief of the previous sweep (mean, covariance) that the unary
                 // factors linearise at — same wave, so its LDS writes precede their LDS reads
                 if (pending) {
@@ -2222,7 +2232,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
             early = (seg_b >> 24) > 0u && !idle && skip0 == 0u;
             DELAY_AT(3, role == ROLE_DYN);
             if (early) {
-                if (is_dyn && (w.enable & 1u)) dynamic_messages(s_sh);
+                if (is_dyn && (kinds() & 1u)) dynamic_messages(s_sh);
                 unary_messages(0u, s_sh, itf + ((((seg_b >> 16) & 1u) && radio) ? 1 : 0));
             }
             QSTAMP(13, qt);

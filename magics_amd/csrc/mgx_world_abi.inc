@@ -143,8 +143,8 @@ int mgx_robot_add(mgx_world *w, const mgx_robot_desc *d, int32_t *robot_id) {
     rb.n_nodes = K + (K - 1) + 2 * (K - 2);
     flush_counts(w);  // launches logged so far do not concern the new robot
     {   // add_internal_edge (factorgraph.rs:304-330): the variable receives an (empty) message, the factor one if enabled
-        const uint32_t en = w->p.enable_mask;
-        rb.cnt[2] = (uint64_t)(2 * (K - 1) + 2 * (K - 2)) + ((en & 1u) ? 2 * (K - 1) : 0) + ((en & 4u) ? K - 2 : 0) + ((en & 8u) ? K - 2 : 0);
+        const uint32_t en = w->kinds_of_group(d->group);  // (the group's own kinds where it was given some: mgx_set_group_enabled)
+        rb.cnt[2] =(uint64_t)(2 * (K - 1) + 2 * (K - 2)) + ((en & 1u) ? 2 * (K - 1) : 0) + ((en & 4u) ? K - 2 : 0) + ((en & 8u) ? K - 2 : 0);
         // a robot that joins a world that has iterated: its switched-off factors stay without inbox keys, and switching the kind
         // on has something to thaw even if no sweep runs in between
         if (w->n_layouts > 0) {
@@ -199,6 +199,8 @@ int mgx_robot_add(mgx_world *w, const mgx_robot_desc *d, int32_t *robot_id) {
     w->sets.removed.push_back(0);
     w->sets.group.push_back(d->group);
     w->sets.n_grouped += d->group ? 1 : 0;
+    if (w->gkinds.populated.size() <= d->group) w->gkinds.populated.resize((size_t)d->group + 1, 0);
+    w->gkinds.populated[d->group] = 1;  // (from here on the group's kinds are fixed)
     w->robots.push_back(std::move(rb));
     w->sets.ensure(w->robots.size());
     w->K = K;
@@ -391,6 +393,8 @@ int mgx_set_enabled(mgx_world *w, uint32_t kind_mask) {
     if (kind_mask & ~15u) return fail(MGX_ERR_INVALID, "unknown factor kind bits 0x%x", kind_mask);
     const uint32_t on = kind_mask & ~w->p.enable_mask, off = w->p.enable_mask & ~kind_mask;
     if (kind_mask == w->p.enable_mask) return MGX_OK;
+    if (w->gkinds.masked())
+        return fail(MGX_ERR_STATE, "mgx_set_enabled on a world whose groups have enabled kinds of their own (mgx_set_group_enabled): freeze and thaw are world-wide");
     flush_counts(w);  // what was logged so far was sent under the old flags
     // Internal kinds (dynamic, obstacle, tracking): a factor switched off keeps the inbox it has now and
     // resumes from it when it is switched on again (FactorNode::receive_message_from drops everything in
@@ -455,6 +459,46 @@ int mgx_set_enabled(mgx_world *w, uint32_t kind_mask) {
     w->d.enable = kind_mask;
     if (kind_mask & 8u) { w->trk_ever_on = true; w->d.trk_cols = 1; }
     w->stale_kinds &= ~kind_mask;
+    return MGX_OK;
+}
+
+// The enabled kinds of ONE robot group (include/mgx.h, ROBOT GROUPS): fixed before the group's first robot joins, so a factor of a
+// switched-off kind is off from its creation — nothing to freeze, nothing to thaw, no inbox keys ever.  Only the internal kinds
+// may differ from the world's; a mask equal to the world's is no mask at all (the group follows the world, as if never set).
+int mgx_set_group_enabled(mgx_world *w, uint32_t group, uint32_t kind_mask) {
+    // (what the arguments alone say comes first: it needs no world and no device)
+    if (kind_mask & ~15u) return fail(MGX_ERR_INVALID, "unknown factor kind bits 0x%x", kind_mask);
+    if (group >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "group %u is not below MGX_GROUPS_MAX (%u)", group, MGX_GROUPS_MAX);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    MGX_ENTER(w);
+    mgx_world::GroupKinds &gk = w->gkinds;
+    if ((kind_mask ^ w->p.enable_mask) & 2u)
+        return fail(MGX_ERR_INVALID, "group %u: the inter-robot kind (bit 2) must equal the world's (%s): residency, keyless factors and the inter-robot "
+                                     "freeze are world-wide", group, (w->p.enable_mask & 2u) ? "on" : "off");
+    if (group < gk.populated.size() && gk.populated[group])
+        return fail(MGX_ERR_STATE, "group %u has had robots: a group's enabled kinds are fixed before its first robot is added", group);
+    if (w->frozen_live || w->ir_frozen_live || w->thaw_kinds || w->ir_thaw_active || w->n_keyless > 0)
+        return fail(MGX_ERR_STATE, "enabled kinds per group on a world that has switched a factor kind (mgx_set_enabled): freeze and thaw are world-wide");
+    if (w->obs.n_ghosts || w->xres.connected || w->direct.connected || w->rccl.connected)
+        return fail(MGX_ERR_STATE, "enabled kinds per group on a sharded world: ghosts have no group");
+    if (gk.has.size() <= group) { gk.has.resize((size_t)group + 1, 0); gk.mask.resize((size_t)group + 1, 0u); }
+    const bool own = kind_mask != w->p.enable_mask;
+    gk.n_masked += (own ? 1u : 0u) - (gk.has[group] ? 1u : 0u);
+    gk.has[group] = own ? 1 : 0;
+    gk.mask[group] = kind_mask;
+    if (own && (kind_mask & 8u)) { w->trk_ever_on = true; w->d.trk_cols = 1; }  // (on if ANY group has tracking on)
+    return MGX_OK;
+}
+int mgx_get_group_enabled(mgx_world *w, uint32_t group, uint32_t *kind_mask) {
+    if (group >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "group %u is not below MGX_GROUPS_MAX (%u)", group, MGX_GROUPS_MAX);
+    if (!w || !kind_mask) return fail(MGX_ERR_INVALID, "null argument");
+    *kind_mask = w->kinds_of_group(group);
+    return MGX_OK;
+}
+int mgx_group_enabled_stats(mgx_world *w, uint64_t *masked_plans, uint64_t *masked_launches) {
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (masked_plans) *masked_plans = w->gkinds.masked_plans;
+    if (masked_launches) *masked_launches = w->gkinds.masked_launches;
     return MGX_OK;
 }
 

@@ -48,8 +48,8 @@ static void flush_counts(mgx_world *w, bool lazy) {
         return;
     }
     const int K = w->K;
-    const uint32_t en = w->p.enable_mask;
-    const uint64_t dynf = (en & 1u) ? 2ull * (K - 1) : 0, obsf = (en & 4u) ? (uint64_t)(K - 2) : 0, trkf = (en & 8u) ? (uint64_t)(K - 2) : 0;
+    // (the enabled kinds are the robot's GROUP's where the world is masked — mgx_set_group_enabled; the inter-robot bit is the world's)
+    const uint32_t en_ir = w->p.enable_mask & 2u;
     // The robots (what each one's sweeps were, from the log: their own counters, and the cumulative counts the connections are
     // settled against), then — in full — the connections.  What the passes need of a robot sits in compact arrays: a Robot is a
     // dozen vectors wide.
@@ -144,6 +144,7 @@ static void flush_counts(mgx_world *w, bool lazy) {
             const uint64_t c = w->cp_pending[key];
             w->cp_pending[key] = 0;
             Robot &rb = w->robots[r];
+            const uint32_t en = w->kinds_of_robot(r);
             const uint64_t dyn_here = (uint64_t)((i >= 1) + (i <= K - 2));
             rb.cnt[2] += c * (((en & 1u) ? dyn_here : 0) + ((i >= 1 && i <= K - 2) ? (uint64_t)(((en & 4u) != 0) + ((en & 8u) != 0)) : 0));
             if (i >= 1) cu.on_ir[r] += c;  // one inter-robot factor per connection hangs on this variable
@@ -156,7 +157,7 @@ static void flush_counts(mgx_world *w, bool lazy) {
         // their keys are settled as ever, against the cumulative counts BEFORE this log joins them — their share of it is added here).
         for (IrConn &c : w->conns) {
             settle_conn(w, c);  // (prior changes up to now; sweeps up to the last flush)
-            if (!(en & 2u) || !log_any) continue;
+            if (!en_ir || !log_any) continue;
             const size_t o = (size_t)c.owner, t = (size_t)c.other;
             const bool radio_a = (flags[o] & 1u) != 0, radio_b = (flags[t] & 1u) != 0;
             c.cnt[2] += nIv[o] * (uint64_t)(K - 1);
@@ -192,6 +193,8 @@ static void flush_counts(mgx_world *w, bool lazy) {
             Robot &rb = w->robots[r];
             if (rb.ghost) continue;
             const uint64_t own = w->cidx.out[r].size(), foreign = w->cidx.in[r].size();
+            const uint32_t en = w->kinds_of_robot(r);
+            const uint64_t dynf = (en & 1u) ? 2ull * (K - 1) : 0, obsf = (en & 4u) ? (uint64_t)(K - 2) : 0, trkf = (en & 8u) ? (uint64_t)(K - 2) : 0;
             const uint64_t s_int = 2ull * (K - 1) + 2ull * (K - 2) + (uint64_t)(K - 1) * own, s_ext = (uint64_t)(K - 1) * foreign;
             // internal factor sweeps: one message per inbox key of every updated factor, received by the variables
             rb.cnt[0] += nIfv[r] * (dynf + obsf) + trkv[r] * trkf;

@@ -99,7 +99,10 @@ static int commit_held(mgx_world *w) {  // mgx_tick: a lingering launch stays â€
     w->res.linger.hold = false;
     return rc;
 }
+static int run_masked_launch(mgx_world *w, uint32_t ext_mask, uint32_t int_mask, int n_int, uint32_t hints);
 static int sweep(mgx_world *w, int32_t robot, uint32_t ext_mask, uint32_t int_mask, int n_int, uint32_t hints) {
+    // A masked world (mgx_set_group_enabled): a world-wide sweep is a group plan of one launch, every group the same segment
+    if (robot < 0 && w->gkinds.masked()) return run_masked_launch(w, ext_mask, int_mask, n_int, hints);
     int rc = commit(w);
     if (rc != MGX_OK) return rc;
     if ((rc = check_device_error(w)) != MGX_OK) return rc;
@@ -179,8 +182,12 @@ static int sweep(mgx_world *w, int32_t robot, uint32_t ext_mask, uint32_t int_ma
         // single workgroup: nobody else reads the snapshot buffer concurrently => update in place
         const bool thawing = w->thaw_kinds && (int_mask & PH_INT_FACTOR) && n_int > 0;
         if (thawing) HIP_TRY(launch_thaw(w->d, w->dev_of[(size_t)robot], 1, 0, w->stream));
-        HIP_TRY(launch_robot_sweep(w->d, w->dev_of[(size_t)robot], 1, 0, int_mask, n_int, writes_snap ? w->d.cur : -1, 0, w->stream,
-                                   &w->last_sweep));
+        // (one robot, one group: its kinds are the launch's own scalar â€” mgx_set_group_enabled)
+        w->d.enable = w->kinds_of_robot((size_t)robot);
+        const hipError_t le = launch_robot_sweep(w->d, w->dev_of[(size_t)robot], 1, 0, int_mask, n_int, writes_snap ? w->d.cur : -1, 0, w->stream,
+                                                 &w->last_sweep);
+        w->d.enable = w->p.enable_mask;
+        HIP_TRY(le);
         w->last_sweep_form = MGX_SWEEP_FORM_SEGMENTS;
         if (w->thaw_kinds && (thawing || writes_snap)) HIP_TRY(launch_thaw_done(w->d, w->dev_of[(size_t)robot], 1, writes_snap ? 1 : 0, w->stream));
         log_launch(w, robot, 0, int_mask, n_int);
@@ -303,6 +310,7 @@ static int ensure_resident_tables(mgx_world *w) {
 static bool resident_gate(const mgx_world *w, const std::vector<Launch> &plan) {
     if (!resident_enabled() || w->res.mode == ResidentLaunches::OFF || plan.size() < 2) return false;
     if (w->res.backoff.left > 0) return false;  // a recent launch found the GPU shared (residency census): launch by launch for a while
+    if (w->gkinds.masked()) return false;       // enabled kinds per group (mgx_set_group_enabled): the resident kernel reads the world's only
     const DevWorld &d = w->d;
     const bool sharded = w->xres.connected;  // the ranks have agreed (mgx_halo_resident_connect_peers) that ghost records travel inside the launches
     if ((d.R_total != d.R_local && !sharded) || !(w->p.enable_mask & 2u)) return false;
@@ -381,7 +389,12 @@ static void linger_confirm(mgx_world *w) {
 }
 // Submits `plan` with `upd` riding in it: posted or as resident launches where the world qualifies, launch by launch where not.
 // The one place where a schedule's prior updates are set on the world, and cleared.  lap: the caller's stage clock (mgx_tick).
+static int run_masked_plan(mgx_world *w, const std::vector<Launch> &plan);
 static int run_schedule(mgx_world *w, const std::vector<Launch> &plan, const RidingUpdates &upd, StageTimer *lap = nullptr) {
+    if (w->gkinds.masked()) {  // (never posted, never resident; its callers send the prior updates as the kernel of their own)
+        if (upd.any()) return fail(MGX_ERR_STATE, "internal: prior updates riding in a masked world's schedule");
+        return run_masked_plan(w, plan);
+    }
     const RidingUpdates outer = w->res.riding;  // (none â€” unless this is a post taken back on the way to the schedule that follows it)
     w->res.riding = upd;
     const int resident = run_resident(w, plan);
@@ -729,12 +742,16 @@ static bool group_schedule_is_plain(mgx_world *w, uint32_t n_groups, const uint8
 // segments form â€” never recorded, posted or resident.  The caller has ended a lingering launch and submitted what was recorded
 // (MGX_ENTER).  The robots' groups by device index go up only when the layout has changed them; the call's segment records travel
 // through the pinned ring into device memory, ONE copy for all its launches.
-static int run_group_plan(mgx_world *w, const GroupPlan &gp) {
+// by_masks: the plan is ONE schedule (or one sweep) for every group, run this way because the world is masked
+// (mgx_set_group_enabled) â€” counted apart (mgx_group_enabled_stats), and none of its workgroups sits out.
+static int run_group_plan(mgx_world *w, const GroupPlan &gp, bool by_masks = false) {
     int rc = commit(w);
     if (rc != MGX_OK) return rc;
     if ((rc = check_device_error(w)) != MGX_OK) return rc;
     mgx_world::GroupSchedules &gs = w->gsched;
-    gs.mixed_calls++;
+    mgx_world::GroupKinds &gk = w->gkinds;
+    if (by_masks) gk.masked_plans++;
+    else gs.mixed_calls++;
     const size_t RL = (size_t)w->d.R_local;
     if (gp.n_launches == 0 || RL == 0) return MGX_OK;
     // (a robot that has left keeps its group: every group on the device has a record, all-zero â€” sits out â€” beyond n_groups)
@@ -764,26 +781,74 @@ static int run_group_plan(mgx_world *w, const GroupPlan &gp) {
         HIP_TRY(hipMemcpyAsync(gs.seg_d.p, hp, sizeof(GroupSeg) * n_rec, hipMemcpyHostToDevice, w->stream));
         HIP_TRY(w->stage.release(slot, w->stream));
     }
+    // A masked world: the groups' enabled kinds by group id, beside the records.  They are fixed once a group has robots, so the
+    // table goes up again only when a group joined or was given its kinds (an unmasked world has none: the kernel's scalar serves)
+    if (gk.masked()) {
+        std::vector<uint32_t> kinds(top);
+        for (size_t g = 0; g < top; g++) kinds[g] = w->kinds_of_group((uint32_t)g);
+        if (kinds != gk.table || !gk.table_d.p) {
+            if (top > gk.table_d.cap) HIP_TRY(hipStreamSynchronize(w->stream));  // (an array that has to grow is freed first: nothing may still read it)
+            gk.table.swap(kinds);
+            HIP_TRY(gk.table_d.upload(gk.table, w->stream, (size_t)MGX_GROUPS_MAX));
+            HIP_TRY(hipStreamSynchronize(w->stream));  // (pageable memory: the copy has left it)
+        }
+    }
     w->stale_kinds |= ~w->p.enable_mask & 15u;  // disabled factors miss what these sweeps deliver
     for (size_t k = 0; k < gp.n_launches; k++) {
         const bool writes_snap = gp.writes_snap[k] != 0;
         if (gp.any_ext[k]) w->res.backoff.external_iteration();
         w->d.group_of = gs.group_of_d.p;
         w->d.group_seg = gs.seg_d.p + k * top;
+        w->d.group_enable = gk.masked() ? gk.table_d.p : nullptr;
         const hipError_t e = launch_robot_sweep(w->d, 0, w->d.R_local, 0u, 0u, 0, writes_snap ? 1 - w->d.cur : -1, 0u, w->stream, &w->last_sweep);
         w->d.group_of = nullptr;
         w->d.group_seg = nullptr;
+        w->d.group_enable = nullptr;
         HIP_TRY(e);
         w->last_sweep_form = MGX_SWEEP_FORM_SEGMENTS;
         w->last_sweep_launches++;
-        gs.mixed_launches++;
+        if (by_masks) gk.masked_launches++;
+        else gs.mixed_launches++;
         if (writes_snap) w->d.cur ^= 1;
         for (size_t g = 0; g < top; g++) {  // the counters' log, scoped by group; the workgroups that sat the launch out, from the plan
             const GroupSeg none{0u, 0u, 0, 0u};
             const GroupSeg &sg = g < gp.n_groups ? gp.launch(k)[g] : none;
-            if (sits_out(sg)) gs.sat_out += members[g];
+            if (sits_out(sg)) gs.sat_out += by_masks ? 0u : members[g];
             else if (members[g]) log_launch(w, -2 - (int)g, sg.ext_mask, sg.int_mask, sg.n_int);
         }
     }
     return MGX_OK;
+}
+static uint32_t groups_in_use(const mgx_world *w) {  // 1 + the highest group id a robot of the world has (had)
+    uint32_t top = 1;
+    for (const uint32_t g : w->sets.group) top = std::max(top, g + 1);
+    return top;
+}
+// A masked world's schedules (mgx_set_group_enabled): the plan every group shares as a group plan in which every group has the
+// same segments â€” the launches of run_segments, each reading its robots' kinds beside the segment record.
+static int run_masked_plan(mgx_world *w, const std::vector<Launch> &plan) {
+    GroupPlan gp;
+    const uint32_t top = groups_in_use(w);
+    gp.n_groups = top;
+    gp.n_launches = plan.size();
+    gp.n_segments.assign(top, (uint32_t)plan.size());
+    gp.recs.reserve(plan.size() * (size_t)top);
+    for (const Launch &l : plan) {
+        gp.recs.insert(gp.recs.end(), (size_t)top, GroupSeg{l.ext, int_phases(l), l.n_int, l.hints});
+        gp.writes_snap.push_back(l.n_int > 0 ? 1 : 0);
+        gp.any_ext.push_back(l.ext ? 1 : 0);
+    }
+    return run_group_plan(w, gp, true);
+}
+// ... and its world-wide fine-grained sweeps (mgx_sweep, mgx_*_iteration with robot = -1): one launch of that form
+static int run_masked_launch(mgx_world *w, uint32_t ext_mask, uint32_t int_mask, int n_int, uint32_t hints) {
+    GroupPlan gp;
+    const uint32_t top = groups_in_use(w);
+    gp.n_groups = top;
+    gp.n_launches = 1;
+    gp.n_segments.assign(top, 1u);
+    gp.recs.assign((size_t)top, GroupSeg{ext_mask, int_mask, n_int, hints});
+    gp.writes_snap.assign(1, (int_mask & PH_INT_VARIABLE) && n_int > 0 ? 1 : 0);
+    gp.any_ext.assign(1, ext_mask ? 1 : 0);
+    return run_group_plan(w, gp, true);
 }

@@ -340,7 +340,8 @@ static int mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_sp
     w->last_sweep_launches = 0;
     w->last_sweep = SweepRan{};
     w->last_sweep_form = -1;
-    const bool fuse = !mixed && !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0;
+    // (a masked world — mgx_set_group_enabled — sends its prior updates as mixed calls do: no launch of a group plan carries them)
+    const bool fuse = !mixed && !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0 && !w->gkinds.masked();
     if (mixed) {
         HIP_TRY(launch_update_priors(w->d, R, ms.robots_d.p, ms.waypoints_d.p, ms.ts_list_d.p, ms.what_d.p, max_speed, delta_t, s));
         rc = run_group_plan(w, *mixed);
@@ -370,6 +371,8 @@ int mgx_mission_run(mgx_world *w, mgx_mission_run_desc *d) {
         (d->finished_capacity && !d->finished))
         return fail(MGX_ERR_INVALID, "null argument");
     if (!(d->failure_rate >= 0.0 && d->failure_rate <= 1.0)) return fail(MGX_ERR_INVALID, "failure_rate is outside [0, 1]");
+    if (w->gkinds.masked())
+        return fail(MGX_ERR_STATE, "mgx_mission_run on a world whose groups have enabled kinds of their own (mgx_set_group_enabled): one generator and one schedule are one group's");
     mgx_world::Mission &ms = w->mission;
     const size_t R = w->robots.size();
     d->ticks_done = 0;

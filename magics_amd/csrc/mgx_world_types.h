@@ -702,6 +702,22 @@ struct mgx_world {
         DevBuf<GroupSeg> seg_d;          // [launches of the call][groups]
         uint64_t mixed_calls = 0, mixed_launches = 0, sat_out = 0;
     } gsched;
+    // Enabled factor kinds per robot group (mgx_set_group_enabled).  A group has a mask of its own only where it was given one that
+    // differs from the world's in an INTERNAL kind (bits 1, 4, 8); every other group follows w->p.enable_mask.  The world is MASKED
+    // while there is such a group: its schedules all run as group plans (run_group_plan), whose launches read the table.
+    struct GroupKinds {
+        std::vector<uint8_t> has;       // [groups given a mask] 1: `mask` holds the group's own
+        std::vector<uint32_t> mask;
+        std::vector<uint8_t> populated; // [groups] a robot of the group has been added at some point: the kinds are fixed
+        uint32_t n_masked = 0;          // groups with a mask of their own: the world is masked when there are any
+        DevBuf<uint32_t> table_d;       // [groups of the last upload] the kinds by group id
+        std::vector<uint32_t> table;    // what table_d holds
+        uint64_t masked_plans = 0, masked_launches = 0;  // mgx_group_enabled_stats
+        bool masked() const { return n_masked != 0; }
+    } gkinds;
+    // the enabled kinds of group g / of robot r (an id): the group's own internal kinds, the world's inter-robot bit
+    uint32_t kinds_of_group(uint32_t g) const { return g < gkinds.has.size() && gkinds.has[g] ? ((gkinds.mask[g] & 13u) | (p.enable_mask & 2u)) : p.enable_mask; }
+    uint32_t kinds_of_robot(size_t r) const { return gkinds.n_masked ? kinds_of_group(sets.group[r]) : p.enable_mask; }
     ResidentLaunches res;// resident and lingering schedule launches: their words and tables, the launch not yet decided, the open launch and its post
     int sticky_rc = 0;       // a declined launch whose re-run failed inside a call that cannot report it (flush_counts): every
                              // later sweep, read-back and mgx_synchronize reports it (check_device_error)

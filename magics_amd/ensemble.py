@@ -11,8 +11,9 @@ once (mission_tick_begin_groups, mission_tick_end) and runs the parts of `Simula
 device's collision logs and tracker sample log are drained once and their records routed to the members by robot id.
 
 Per member (per group of the world): the seed, the comms failure rate, the formations, max-time — and the comms radius, which the
-grouped search holds per group (mission_tick_begin_groups with one radius per member), and the GBP iteration schedule
-(mission_tick_end with one schedule per member: mgx_mission_tick_end_groups).  The per-robot observers — environment
+grouped search holds per group (mission_tick_begin_groups with one radius per member), the GBP iteration schedule
+(mission_tick_end with one schedule per member: mgx_mission_tick_end_groups) and the enabled factor kinds but the inter-robot one
+(set_group_enabled before the member's first robot: mgx_set_group_enabled).  The per-robot observers — environment
 collisions, goal areas, the run metrics — do not look at the group: the first member switches them on for the world, and every
 member reads its own robots' part."""
 import copy
@@ -31,10 +32,13 @@ ENV_EVENTS_PER_MEMBER = 262144   # the room a run of its own has for environment
 ENV_EVENTS_MOST = 1 << 24        # ... and where an ensemble's log stops growing with its members (24 bytes a record)
 
 
-def _shared_settings(sc):
-    """everything the world holds once, as (key, value) in the order it is compared"""
+def _shared_settings(sc, per_group_kinds=False):
+    """everything the world holds once, as (key, value) in the order it is compared.  per_group_kinds: the world takes
+    gbp.factors-enabled per group (mgx_set_group_enabled) — all of it but the inter-robot kind, which stays the world's"""
     cfg = sc["config"]
-    out = [("params." + k, v) for k, v in _config.world_params(cfg).items()]
+    out = [("params." + k, v) for k, v in _config.world_params(cfg).items() if not (per_group_kinds and k == "enable_mask")]
+    if per_group_kinds:
+        out.append(("gbp.factors-enabled.interrobot", cfg["gbp"]["factors-enabled"]["interrobot"]))
     out += [("gbp.lookahead-multiple", cfg["gbp"]["lookahead-multiple"]),
             ("robot.target-speed", cfg["robot"]["target-speed"]),
             ("robot.planning-horizon", cfg["robot"]["planning-horizon"]), ("simulation.hz", cfg["simulation"]["hz"]),
@@ -201,9 +205,10 @@ class Ensemble:
     def __init__(self, scenarios, world, **simulation_options):
         """scenarios: one scenario dict per member (config.load_scenario, tests/golden/scenarios.json); member m's robots are in
         group m of `world`, a fresh World made with config.world_params of any of them.  The members may differ in
-        simulation.prng-seed, robot.communication.failure-rate, robot.communication.radius, gbp.iteration-schedule (and max-time) and
-        in their formations; everything the world holds once must be equal (ValueError names the first key that differs; a world
-        that takes no radius or no schedule per group holds that once, too).  simulation_options go to every member's Simulation, so the members share them —
+        simulation.prng-seed, robot.communication.failure-rate, robot.communication.radius, gbp.iteration-schedule,
+        gbp.factors-enabled.{dynamic, obstacle, tracking} (and max-time) and in their formations; everything the world holds once must be equal (ValueError names the first key that differs; a world
+        that takes no radius, no schedule or no enabled kinds per group holds that once, too; gbp.factors-enabled.interrobot is the
+        world's always).  simulation_options go to every member's Simulation, so the members share them —
         goal_areas among them.  An Ensemble runs device missions with device robot-robot collisions and device trackers, and on
         request the device's other observers: environment_collisions=True, goal_areas, device_metrics (with sample_log=False if
         asked).  Still refused, with NotImplementedError: global_planner (and so rrt-star formations) — a per-group many-tick run
@@ -233,9 +238,10 @@ class Ensemble:
                 raise NotImplementedError(f"Ensemble: member {m} has an rrt-star formation; the global planner is not supported in this version")
         per_group_radius = hasattr(world, "neighbours_groups")   # (the engine's grouped search: one comms radius per group)
         per_group_steps = hasattr(world, "group_schedule_stats")  # (mgx_mission_tick_end_groups: one iteration schedule per group)
+        per_group_kinds = hasattr(world, "set_group_enabled")     # (mgx_set_group_enabled: dynamic, obstacle and tracking per group)
 
         def shared(sc):
-            return (_shared_settings(sc) + ([] if per_group_steps else [("gbp.iteration-schedule", sc["config"]["gbp"]["iteration-schedule"])]) +
+            return (_shared_settings(sc, per_group_kinds) + ([] if per_group_steps else [("gbp.iteration-schedule", sc["config"]["gbp"]["iteration-schedule"])]) +
                     ([] if per_group_radius else [("robot.communication.radius", sc["config"]["robot"]["communication"]["radius"])]))
         first = shared(scenarios[0])
         for m, sc in enumerate(scenarios[1:], 1):
@@ -259,6 +265,12 @@ class Ensemble:
         self._dist = np.zeros(0)
         self._clock = None        # the tick the device's tracker clock names
         self.tick_no = 0
+        # every member's enabled kinds, before its first robot is added (a mask equal to the world's is none: an ensemble whose
+        # members agree stays the unmasked world it was)
+        masks = [_config.enable_mask(sc["config"]) for sc in scenarios]
+        if per_group_kinds and any(k != masks[0] for k in masks):
+            for m, k in enumerate(masks):
+                world.set_group_enabled(m, k)
         self.members_worlds = [_MemberWorld(self, m) for m in range(len(scenarios))]
         self.members = [Member(Simulation(sc, view, **simulation_options), view) for sc, view in zip(scenarios, self.members_worlds)]
         s0 = self.members[0].sim

@@ -865,6 +865,24 @@ class World:
         self._chk(self._L.mgx_group_schedule_stats(self._w, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
 
+    def set_group_enabled(self, group, kind_mask):
+        """gbp.factors-enabled of ONE robot group (mgx_set_group_enabled): kind_mask of the MGX_FACTOR_* bits, before the group's
+        first robot is added.  Dynamic, obstacle and tracking may differ from the world's; the inter-robot bit may not."""
+        self._chk(self._L.mgx_set_group_enabled(self._w, int(group), int(kind_mask)))
+
+    def group_enabled(self, group):
+        """the kinds a robot added to `group` runs under (mgx_get_group_enabled)"""
+        m = C.c_uint32()
+        self._chk(self._L.mgx_get_group_enabled(self._w, int(group), C.byref(m)))
+        return m.value
+
+    def group_enabled_stats(self):
+        """(schedules and world-wide sweeps that ran as group plans only because the world is masked, the sweep-kernel launches of
+        those): mgx_group_enabled_stats"""
+        a, b = C.c_uint64(), C.c_uint64()
+        self._chk(self._L.mgx_group_enabled_stats(self._w, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def is_thawing(self):
         """factors switched back on are still resuming from their frozen inboxes (mgx_is_thawing)"""
         t = C.c_int32()

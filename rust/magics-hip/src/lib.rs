@@ -150,6 +150,23 @@ impl World {
         check(unsafe { sys::mgx_group_schedule_stats(self.raw, &mut calls, &mut launches, &mut sat_out) })?;
         Ok((calls, launches, sat_out))
     }
+    /// `gbp.factors-enabled` of ONE robot group (`mgx_set_group_enabled`): before the group's first robot is added; dynamic, obstacle
+    /// and tracking may differ from the world's, the inter-robot bit may not.
+    pub fn set_group_enabled(&self, group: u32, kind_mask: u32) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_set_group_enabled(self.raw, group, kind_mask) })
+    }
+    /// The kinds a robot added to `group` runs under (`mgx_get_group_enabled`).
+    pub fn group_enabled(&self, group: u32) -> Result<u32, MgxError> {
+        let mut mask = 0u32;
+        check(unsafe { sys::mgx_get_group_enabled(self.raw, group, &mut mask) })?;
+        Ok(mask)
+    }
+    /// (schedules that ran as group plans only because the world is masked, the sweep-kernel launches of those)
+    pub fn group_enabled_stats(&self) -> Result<(u64, u64), MgxError> {
+        let (mut plans, mut launches) = (0u64, 0u64);
+        check(unsafe { sys::mgx_group_enabled_stats(self.raw, &mut plans, &mut launches) })?;
+        Ok((plans, launches))
+    }
     /// Several `iterate` calls, one submission (`mgx_batch_begin` / `mgx_batch_end`): the schedules issued inside `f` are recorded and
     /// submitted together, merged into as few resident launches as their segments fit; same results, bit for bit.
     /// Returns (schedules recorded, sweep-kernel launches they were submitted as).

@@ -1,11 +1,13 @@
 """Many scenario runs as ONE Ensemble against the same runs one after another (profiles/ensemble.md).
 
-Four workloads, all from tests/golden/scenarios.json: the reference's communications-failure experiment as its script runs it — 5
+Five workloads, all from tests/golden/scenarios.json: the reference's communications-failure experiment as its script runs it — 5
 seeds x 8 failure rates, 21 robots per run: 40 members —, the Environment Obstacles Experiment with 32 seeds, and the Varying Network
 Connectivity Experiment as its script runs it — 5 seeds x comms radii 20 / 40 / 60 / 80, 30 robots per run: 20 members that differ in
 their comms radius —, and a subset of the Iteration Amount Experiment as its script runs it — the script's 5 seeds x internal 1 / 5 / 21
 x external 1 / 5 / 21 of its 1, 2, 3, 5, 8, 13, 21, 34 each, 25 robots per run: 45 members that differ in their GBP iteration
-schedule, so the ensemble's ticks run MIXED (launches per tick and the workgroups that sat launches out are reported).  For each:
+schedule, so the ensemble's ticks run MIXED (launches per tick and the workgroups that sat launches out are reported) —, and the
+Structured Junction Twoway experiment as its script runs it — seed 0, tracking factors on and off x failure rates 0.0 .. 0.7: 16
+members that differ in gbp.factors-enabled, so the world is MASKED and every tick a group plan (mgx_group_enabled_stats).  For each:
   ensemble   the members as robot groups of one world (magics_amd/ensemble.py): wall time, member ticks per second, the kernel the
              neighbour search ran, the resident schedule launches (ran / declined);
   solo       the same members one after another, each a Simulation on a world of its own: run(chunk=1) and run(chunk=256).
@@ -48,14 +50,16 @@ with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") a
     known = json.load(f)
 
 
-def members(name, seeds, rates, radii=(None,), amounts=(None,)):
+def members(name, seeds, rates, radii=(None,), amounts=(None,), tracking=(None,)):
     out = []
-    for amount in amounts:
+    for trk, amount in [(t, a) for t in tracking for a in amounts]:
         for radius in radii:
             for rate in rates:
                 for seed in seeds:
                     sc = copy.deepcopy(known[name])
                     sc["config"]["simulation"]["prng-seed"] = seed
+                    if trk is not None:
+                        sc["config"]["gbp"]["factors-enabled"]["tracking"] = trk
                     if rate is not None:
                         sc["config"]["robot"]["communication"]["failure-rate"] = rate
                     if radius is not None:
@@ -73,6 +77,8 @@ WORKLOADS = {
                                                               [20.0, 40.0, 60.0, 80.0]),
     "iteration-amount 5 seeds x 3 internal x 3 external": lambda: members("Iteration Amount Experiment", [0, 31, 227, 252, 805], [None],
                                                                           amounts=[(i, e) for i in (1, 5, 21) for e in (1, 5, 21)]),
+    "structured-junction-twoway tracking on / off x 8 rates": lambda: members("Structured Junction Twoway", [0], [0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7],
+                                                                              tracking=[True, False]),
 }
 
 
@@ -101,11 +107,15 @@ def run_ensemble(scs):
     ran, declined, _ = e.world.resident_stats()
     lingered, posted = e.world.linger_stats()[:2]
     mixed = {}
+    if hasattr(e.world, "group_enabled_stats"):
+        plans, launches = e.world.group_enabled_stats()
+        if plans:   # (a masked world: every tick's schedule a group plan, launch by launch)
+            mixed = {"masked_plans": plans, "masked_launches": launches, "launches_per_masked_plan": round(launches / plans, 2)}
     if hasattr(e.world, "group_schedule_stats"):
         calls, launches, sat_out = e.world.group_schedule_stats()
         if calls:   # (workgroup launches: one per robot on the device and launch — the world's robots at the end stand for all of them)
             most = launches * e.world.num_robots()[0]
-            mixed = {"mixed_calls": calls, "mixed_launches": launches, "launches_per_mixed_call": round(launches / calls, 2), "sat_out": sat_out,
+            mixed = {**mixed, "mixed_calls": calls, "mixed_launches": launches, "launches_per_mixed_call": round(launches / calls, 2), "sat_out": sat_out,
                      "workgroup_launches_at_most": most, "sat_out_share_at_least": round(sat_out / max(most, 1), 4)}
     # (mgx_last_search names the kernel of the last search that launched one: the last tick with robots alive)
     return wall, sum(m.tick_no for m in e.members), {"world_ticks": e.tick_no, "robots": e.world.num_robots()[0], "search_kernel": e.world.last_search()[0],

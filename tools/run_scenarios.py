@@ -15,16 +15,17 @@ sample is logged on the device and the robots' positions / velocities lists stay
 scenario's line then carries the arrivals per area and the throughput the reference's analyse-junction-scenario.py reads out of an
 export (robots that started within 50 s and arrived, per second).  --export DIR writes each scenario's export to DIR/<name>.json.
 --ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:INTERNAL:EXTERNAL,..]
-runs the cross product of ONE scenario — every seed with every failure rate, every comms radius and every GBP iteration schedule
-(KIND: centered, soon-as-possible, late-as-possible, interleave-evenly, half-beginning-half-end; default each: the scenario's own)
-— as one Ensemble (magics_amd/ensemble.py):
+[--ensemble-tracking on,off]
+runs the cross product of ONE scenario — every seed with every failure rate, every comms radius, every GBP iteration schedule
+(KIND: centered, soon-as-possible, late-as-possible, interleave-evenly, half-beginning-half-end) and gbp.factors-enabled.tracking
+on / off (default each: the scenario's own) — as one Ensemble (magics_amd/ensemble.py):
 the members are robot groups of one world, one launch per schedule and one synchronisation per tick for all of them, each member
 identical to the same run alone.  One line per member — with --environment-collisions, --goal-areas and --metrics (with or
 without --no-sample-log) it carries the member's contacts, arrivals and the means of its run metrics; with --export DIR one
-export per member, DIR/<name>.seed<A>.rate<X>.radius<R>[.<kind>-<internal>-<external>].json.  The global planner and host trackers do not run in an Ensemble.
+export per member, DIR/<name>.seed<A>.rate<X>.radius<R>[.<kind>-<internal>-<external>][.tracking-<on|off>].json.  The global planner and host trackers do not run in an Ensemble.
 usage: python tools/run_scenarios.py [--max-time S] [--goal-areas junction|FILE.json] [--export DIR] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
            [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N]
-           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..]]
+           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..] [--ensemble-tracking on,off]]
            [scenario-dir | name ...]"""
 import copy
 import json
@@ -107,8 +108,16 @@ if "--ensemble-schedules" in args:
             sys.exit(f"--ensemble-schedules: {kind!r} is none of {sorted(config.SCHEDULE_KINDS)}")
         ensemble_schedules.append({"schedule": kind, "internal": int(internal), "external": int(external)})
     del args[i:i + 2]
-if (ensemble_rates or ensemble_radii or ensemble_schedules) and not ensemble_seeds:
-    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii and --ensemble-schedules need --ensemble-seeds")
+ensemble_tracking = None
+if "--ensemble-tracking" in args:
+    i = args.index("--ensemble-tracking")
+    words = args[i + 1].split(",")
+    if not words or any(x not in ("on", "off") for x in words):
+        sys.exit("--ensemble-tracking: a list of on / off")
+    ensemble_tracking = [x == "on" for x in words]
+    del args[i:i + 2]
+if (ensemble_rates or ensemble_radii or ensemble_schedules or ensemble_tracking) and not ensemble_seeds:
+    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii, --ensemble-schedules and --ensemble-tracking need --ensemble-seeds")
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 if ensemble_seeds:
@@ -119,17 +128,20 @@ if ensemble_seeds:
         sys.exit("--ensemble-seeds: the global planner and host trackers do not run in an Ensemble (magics_amd/ensemble.py says why)")
     base = config.load_scenario(args[0]) if os.path.isdir(args[0]) else known[args[0]]
     members = []
-    for schedule in ensemble_schedules or [None]:
-        for radius in ensemble_radii or [base["config"]["robot"]["communication"]["radius"]]:
-            for rate in ensemble_rates or [base["config"]["robot"]["communication"]["failure-rate"]]:
-                for seed in ensemble_seeds:
-                    sc = copy.deepcopy(base)
-                    sc["config"]["simulation"]["prng-seed"] = seed
-                    sc["config"]["robot"]["communication"]["failure-rate"] = rate
-                    sc["config"]["robot"]["communication"]["radius"] = radius
-                    if schedule is not None:
-                        sc["config"]["gbp"]["iteration-schedule"].update(schedule)
-                    members.append((seed, rate, radius, sc))
+    for tracking in ensemble_tracking or [None]:
+        for schedule in ensemble_schedules or [None]:
+            for radius in ensemble_radii or [base["config"]["robot"]["communication"]["radius"]]:
+                for rate in ensemble_rates or [base["config"]["robot"]["communication"]["failure-rate"]]:
+                    for seed in ensemble_seeds:
+                        sc = copy.deepcopy(base)
+                        sc["config"]["simulation"]["prng-seed"] = seed
+                        sc["config"]["robot"]["communication"]["failure-rate"] = rate
+                        sc["config"]["robot"]["communication"]["radius"] = radius
+                        if schedule is not None:
+                            sc["config"]["gbp"]["iteration-schedule"].update(schedule)
+                        if tracking is not None:
+                            sc["config"]["gbp"]["factors-enabled"]["tracking"] = tracking
+                        members.append((seed, rate, radius, sc))
     t0 = time.perf_counter()
     e = ensemble.Ensemble([sc for *_, sc in members], World(config.world_params(base["config"])), environment_collisions=env_collisions,
                           device_metrics=metrics, sample_log=not no_sample_log, goal_areas=goal_areas)
@@ -144,6 +156,7 @@ if ensemble_seeds:
         sch = sc["config"]["gbp"]["iteration-schedule"]
         print(json.dumps({"scenario": sc.get("name", args[0]), "seed": seed, "failure_rate": rate, "comms_radius": radius,
                           **({"schedule": f"{sch['schedule']}:{sch['internal']}:{sch['external']}"} if ensemble_schedules else {}),
+                          **({"tracking": sc["config"]["gbp"]["factors-enabled"]["tracking"]} if ensemble_tracking else {}),
                           "simulated_s": round(s.elapsed(), 1),
                           "robots": len(s.robots), "finished": len(done), "all_finished": s.finished(), "K": s.K,
                           "mean_distance": round(sum(trav) / max(1, len(trav)), 1),
@@ -156,10 +169,14 @@ if ensemble_seeds:
         if export_dir:
             os.makedirs(export_dir, exist_ok=True)
             tail = f".{sch['schedule']}-{sch['internal']}-{sch['external']}" if ensemble_schedules else ""
+            if ensemble_tracking:
+                tail += ".tracking-on" if sc["config"]["gbp"]["factors-enabled"]["tracking"] else ".tracking-off"
             with open(os.path.join(export_dir, f"{stem}.seed{seed}.rate{rate:g}.radius{radius:g}{tail}.json"), "w", encoding="utf-8") as f:
                 json.dump(m.export(), f)
     mixed_calls, mixed_launches, sat_out = e.world.group_schedule_stats()
-    print(json.dumps({"ensemble": len(members), "ticks": e.tick_no, "mixed_calls": mixed_calls, "mixed_launches": mixed_launches, "sat_out": sat_out, "member_ticks": sum(m.tick_no for m in e.members), "wall_s": round(wall, 2),
+    masked_plans, masked_launches = e.world.group_enabled_stats()
+    print(json.dumps({"ensemble": len(members), "ticks": e.tick_no, "mixed_calls": mixed_calls, "mixed_launches": mixed_launches, "sat_out": sat_out,
+                      "masked_plans": masked_plans, "masked_launches": masked_launches, "member_ticks": sum(m.tick_no for m in e.members), "wall_s": round(wall, 2),
                       "member_ticks_per_s": round(sum(m.tick_no for m in e.members) / wall, 1)}), flush=True)
     sys.exit(0)
 names = args or [n for n, sc in sorted(known.items())
