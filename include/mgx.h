@@ -341,6 +341,18 @@ int mgx_last_launch_count(mgx_world *w, uint32_t *n_launches);
 #define MGX_SWEEP_FORM_POSTED 2    /* posted into a lingering resident launch */
 #define MGX_SWEEP_FORM_SHARDED 3   /* one resident launch on a sharded world */
 int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *form, int32_t *resident_capacity);
+/* FORMS OF THE RESIDENT KERNEL.  A resident launch runs the smallest instantiation that covers it: without the tracking
+ * factors' code where the world's tracking factors are off (MGX_SWEEP_F_TRACKING), without the path of mgx_tick's prior updates
+ * where its own schedule carries none and the world has issued no mgx_tick so far (MGX_SWEEP_F_UPDATES).  A lingering launch
+ * keeps its form: an mgx_tick that meets a launch without MGX_SWEEP_F_UPDATES ends it and runs as a launch of the covering
+ * form, and the world's launches keep that form from then on.  Results are the same bit for bit in every form.
+ * mgx_last_sweep_features: the form of the sweep mgx_last_sweep reports (launch-per-segment kernels: always both bits; 0 as well
+ * when no sweep ran).  mgx_set_specialize: 0 = every resident launch of this world in the full form (MGX_SPECIALIZE=0 in the
+ * environment does it for the process), 1 = the smallest form, < 0: as the environment says.  For measuring one against the other. */
+#define MGX_SWEEP_F_TRACKING 1u
+#define MGX_SWEEP_F_UPDATES 2u
+int mgx_last_sweep_features(mgx_world *w, uint32_t *features);
+int mgx_set_specialize(mgx_world *w, int32_t enabled);
 /* How the last neighbour search of this world (mgx_neighbours, mgx_update_topology, a mission tick's) ran, as the branch that
  * launched it chose: the kernel it launched LAST (MGX_SEARCH_*), the row capacity it launched it with (the one-pass kernels write
  * rows of a fixed capacity that the world doubles when a row outgrows it; 0 for the two-pass forms), and how many search launches

@@ -185,6 +185,9 @@ public:
     /// everything issued so far is enqueued: a lingering launch is told to end (no wait); how long launches linger (us, 0: never)
     void flush() { check(mgx_flush(w_)); }
     void set_linger(int32_t microseconds) { check(mgx_set_linger(w_, microseconds)); }
+    /// 0: every resident launch in the full form of the kernel; 1: the smallest form that covers it (default); which one ran last
+    void set_specialize(int32_t enabled) { check(mgx_set_specialize(w_, enabled)); }
+    uint32_t last_sweep_features() { uint32_t f = 0; check(mgx_last_sweep_features(w_, &f)); return f; }
     /// back-to-back schedules merged into one post: 0 off, 1 while the launch is behind (default), 2 whenever they fit
     void set_post_merge(int32_t mode) { check(mgx_set_post_merge(w_, mode)); }
     /// FactorGraph::change_factor_enabled (factorgraph.rs:1529-1539) for every graph: MGX_FACTOR_* bits

@@ -541,9 +541,15 @@ struct LingerBox {  // host-mapped
 };
 
 // Which instantiation of k_robot_sweep a launcher enqueued (mgx_last_sweep): written by the branch that launched it
+// What a resident schedule launch may meet (k_robot_sweep's FEAT, mgx_sweep.h; mgx_last_sweep_features).  The host picks the
+// smallest form that covers the launch: lean (0), SWEEP_F_UPD, or full.  Launch-per-segment kernels exist in the full form only.
+constexpr uint32_t SWEEP_F_TRK = 1u;  // the world's tracking factors are enabled
+constexpr uint32_t SWEEP_F_UPD = 2u;  // plans may carry mgx_tick's prior updates
+constexpr uint32_t SWEEP_F_ALL = SWEEP_F_TRK | SWEEP_F_UPD;
 struct SweepRan {
     int32_t variant = 0;   // KT of the template: a constant horizon, or 0 / -1 for the run-time-K kernels
     int32_t ir_mode = -1;  // IR_NONE / IR_GLOBAL / IR_STAGED (mgx_sweep.h); -1: nothing launched
+    uint32_t features = SWEEP_F_ALL;  // SWEEP_F_* of the instantiation
 };
 
 struct SegPlan {

@@ -808,15 +808,19 @@ static int sweep_variant_of(int K) {
 #define MGX_DECLARE_SET(N)                                                                                                          \
     bool sweep_plain_set##N(int kt, const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,   \
                             int snap_out, uint32_t hints, hipStream_t stream, SweepRan *ran);                                       \
-    int resident_capacity_set##N(int kt, const DevWorld &w);                                                                        \
-    bool resident_launch_set##N(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream, \
-                                hipError_t *err, SweepRan *ran);                                                                    \
-    int sharded_capacity_set##N(int kt, const DevWorld &w);                                                                         \
-    bool sharded_launch_set##N(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream,  \
-                               hipError_t *err, SweepRan *ran);
+    MGX_DECLARE_FORM(N, 0) MGX_DECLARE_FORM(N, 2) MGX_DECLARE_FORM(N, 3)
+// (one object per flavour, horizon set and form: lean, with prior updates, full — SWEEP_F_*, mgx_dev.h)
+#define MGX_DECLARE_FORM(N, F)                                                                                                          \
+    int resident_capacity_set##N##_f##F(int kt, const DevWorld &w);                                                                     \
+    bool resident_launch_set##N##_f##F(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream, \
+                                       hipError_t *err, SweepRan *ran);                                                                 \
+    int sharded_capacity_set##N##_f##F(int kt, const DevWorld &w);                                                                      \
+    bool sharded_launch_set##N##_f##F(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream,  \
+                                      hipError_t *err, SweepRan *ran);
 MGX_DECLARE_SET(0)
 MGX_DECLARE_SET(1)
 MGX_DECLARE_SET(2)
+#undef MGX_DECLARE_FORM
 #undef MGX_DECLARE_SET
 
 hipError_t launch_robot_sweep(const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,
@@ -833,26 +837,39 @@ hipError_t launch_robot_sweep(const DevWorld &w, int robot0, int n_robots, uint3
 // ---- resident schedule launches ------------------------------------------------------------------------
 constexpr size_t RESIDENT_LDS_MAX = 160 * 1024;
 size_t sweep_resident_lds_max() { return RESIDENT_LDS_MAX; }
-// workgroups of the resident kernel the device holds at once (sharded: of the instantiation that takes ghost records in-launch)
-int sweep_resident_capacity(const DevWorld &w, bool sharded) {
+// The form a launch of these features runs in: the smallest instantiated one that covers them (lean, SWEEP_F_UPD, full); the
+// run-time-K kernels have the full form only.
+uint32_t sweep_resident_form(int K, uint32_t features) {
+    if (sweep_variant_of(K) <= 0 || (features & SWEEP_F_TRK)) return SWEEP_F_ALL;
+    return features & SWEEP_F_UPD;
+}
+typedef int (*CapacityFn)(int, const DevWorld &);
+typedef bool (*LaunchFn)(int, const DevWorld &, int, const SegPlan &, bool, hipStream_t, hipError_t *, SweepRan *);
+struct ResidentForm { CapacityFn capacity[3]; LaunchFn launch[3]; };  // per horizon set
+#define MGX_FORM(flav, F) {{flav##_capacity_set0_f##F, flav##_capacity_set1_f##F, flav##_capacity_set2_f##F}, {flav##_launch_set0_f##F, flav##_launch_set1_f##F, flav##_launch_set2_f##F}}
+static const ResidentForm &resident_form(bool sharded, uint32_t form) {
+    static const ResidentForm forms[2][3] = {{MGX_FORM(resident, 0), MGX_FORM(resident, 2), MGX_FORM(resident, 3)},
+                                             {MGX_FORM(sharded, 0), MGX_FORM(sharded, 2), MGX_FORM(sharded, 3)}};
+    return forms[sharded ? 1 : 0][form == 0u ? 0 : form == SWEEP_F_UPD ? 1 : 2];
+}
+#undef MGX_FORM
+// workgroups of the resident kernel the device holds at once (sharded: of the instantiation that takes ghost records in-launch):
+// asked of the instantiation that `features` runs in
+int sweep_resident_capacity(const DevWorld &w, bool sharded, uint32_t features) {
     const int kt = sweep_variant_of(w.K);
-    int cap = sharded ? sharded_capacity_set0(kt, w) : resident_capacity_set0(kt, w);
-    if (cap < 0) cap = sharded ? sharded_capacity_set1(kt, w) : resident_capacity_set1(kt, w);
-    if (cap < 0) cap = sharded ? sharded_capacity_set2(kt, w) : resident_capacity_set2(kt, w);
+    const ResidentForm &f = resident_form(sharded, sweep_resident_form(w.K, features));
+    int cap = -1;
+    for (int s = 0; s < 3 && cap < 0; s++) cap = f.capacity[s](kt, w);
     return cap < 0 ? 0 : cap;
 }
-hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, bool cooperative, hipStream_t stream,
-                                 SweepRan *ran) {
+hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, uint32_t features, bool cooperative,
+                                 hipStream_t stream, SweepRan *ran) {
     if (n_robots <= 0 || plan.n <= 0) return hipSuccess;
     const int kt = sweep_variant_of(w.K);
+    const ResidentForm &f = resident_form(sharded, sweep_resident_form(w.K, features));
     hipError_t e = hipErrorInvalidValue;
-    if (sharded) {
-        if (!sharded_launch_set0(kt, w, n_robots, plan, cooperative, stream, &e, ran) && !sharded_launch_set1(kt, w, n_robots, plan, cooperative, stream, &e, ran))
-            (void)sharded_launch_set2(kt, w, n_robots, plan, cooperative, stream, &e, ran);
-    } else {
-        if (!resident_launch_set0(kt, w, n_robots, plan, cooperative, stream, &e, ran) && !resident_launch_set1(kt, w, n_robots, plan, cooperative, stream, &e, ran))
-            (void)resident_launch_set2(kt, w, n_robots, plan, cooperative, stream, &e, ran);
-    }
+    for (int s = 0; s < 3; s++)
+        if (f.launch[s](kt, w, n_robots, plan, cooperative, stream, &e, ran)) break;
     return e;
 }
 

@@ -291,12 +291,19 @@ __device__ __forceinline__ void quad_transpose4(unsigned (&x)[4], int lane) {
 }
 
 // PERSIST: the launch runs a whole schedule (SegPlan, mgx_dev.h) instead of one segment.
+// FEAT (resident launches only; mgx_dev.h: SWEEP_F_*): what the launch may meet, decided by the host where it launches
+// (mgx_world_launch.inc: resident_features) — a world whose tracking factors are off needs none of their code, state or lanes
+// (F_TRK), a launch no mgx_tick will post into needs no prior-update path (F_UPD).  What the mask leaves out is compiled out:
+// the code, and the launch-wide values it kept alive across the segment loop.  Launch-per-segment kernels are always full.
 // SHARD (resident launches of a sharded world): the snapshot records of ghost robots arrive INSIDE the launch — their owners'
 // ranks store them into this rank's peer-mapped ghost area and this rank's boundary robots store theirs into the peers'.
-template <int KT, int IRM, bool PERSIST, bool SHARD = false>
+template <int KT, int IRM, bool PERSIST, bool SHARD = false, uint32_t FEAT = SWEEP_F_ALL>
 __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_sweep(DevWorld w, int robot0, uint32_t ext_mask, uint32_t int_mask,
                                                              int n_int, int snap_out, uint32_t hints, const SegPlan plan) {
     constexpr bool HAS_IR = IRM != IR_NONE, STAGE_IR = IRM == IR_STAGED;
+    static_assert(PERSIST || FEAT == SWEEP_F_ALL, "only resident schedule launches have lean forms");
+    static_assert(!(FEAT & SWEEP_F_TRK) || (FEAT & SWEEP_F_UPD), "forms: lean, F_UPD, full");
+    constexpr bool TRK = (FEAT & SWEEP_F_TRK) != 0u, UPD = (FEAT & SWEEP_F_UPD) != 0u;
     constexpr int NW = sweep_waves<KT, PERSIST>(), NT = 64 * NW;  // waves / threads of a workgroup
     constexpr int ROLE_DF = NW == 4 ? 2 : ROLE_DYN, ROLE_UF = NW == 4 ? 3 : ROLE_UV;  // who computes the dynamic / the unary factors' messages
     static_assert(!PERSIST || IRM == IR_STAGED, "resident schedule launches exist for worlds with staged inter-robot messages");
@@ -368,7 +375,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     };
     if (PLDS && threadIdx.x == 0) {  // the launch's own plan, as a posted one would arrive (read behind the staging barrier)
         s_plan[0] = (uint32_t)plan.n;
-        s_plan[1] = w.upd ? 1u : 0u;
+        s_plan[1] = (UPD && w.upd) ? 1u : 0u;
 #pragma unroll
         for (int i = 0; i < MAX_SEGS / 4; i++) {
             s_plan[2 + i] = reinterpret_cast<const uint32_t *>(plan.ext)[i];
@@ -581,7 +588,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     // read the table (a masked world runs none): theirs is the kernel argument itself, as ever.
     uint32_t group_kinds = w.enable;
     auto kinds = [&]() __attribute__((always_inline)) -> uint32_t {
-        if constexpr (PERSIST) return w.enable;
+        if constexpr (PERSIST) return TRK ? w.enable : (w.enable & 7u);
         else return group_kinds;
     };
     if constexpr (!PERSIST) {
@@ -609,7 +616,10 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     const int n_dyn = 2 * (K - 1);
     // kinds whose first internal factor sweep of this launch has already been computed from the inbox they
     // froze with (k_thaw, mgx_set_enabled); the pointer is null unless some robot is thawing
-    const uint32_t skip0 = w.skip0 ? (uint32_t)w.skip0[r] : 0u;
+    // (resident launches: the host starts none while anything thaws — resident_fits, linger_world_qualifies — and says so where it
+    // launches, so it is 0 in all of them; a CONSTANT 0 in the lean and F_UPD forms.  The full forms keep the read: written as a
+    // constant there it moved their register allocation, and four of them spilled more than before.)
+    const uint32_t skip0 = (FEAT == SWEEP_F_ALL && w.skip0) ? (uint32_t)w.skip0[r] : 0u;
     const bool idle = w.idle[r] != 0;
     const bool radio = (w.antenna[r] != 0) && !idle;
 
@@ -618,7 +628,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     // ---- roles ------------------------------------------------------------------------------------
     const bool is_dyn = role == ROLE_DF && lane < n_dyn;
     const bool is_obs = role == ROLE_UF && lane < K - 2;
-    const bool is_trk = role == ROLE_UF && lane >= K - 2 && lane < 2 * (K - 2);
+    const bool is_trk = TRK && role == ROLE_UF && lane >= K - 2 && lane < 2 * (K - 2);
     const bool is_var = role == ROLE_UV && lane < K;
     // Horizons of at most 16 variables: the belief finish runs on FOUR lanes per variable (lane (q, i) computes cofactor row q of
     // variable i, variable_finish_quad), and in resident launches the whole variable sweep — inbox sums and finish — stays on the
@@ -762,7 +772,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     // mgx_tick: this robot's prior updates (waypoint, time scale, what) and, lane c < 20 of each wave, entry c of
     // the belief (eta, lam) the variable it updates holds in HBM — wave 0: the horizon variable, wave 1: variable 0
     double u_rec[4] = {0.0, 0.0, 0.0, 0.0}, u_bel = 0.0;
-    if (w.upd) {
+    if (UPD && w.upd) {
 #pragma unroll
         for (int c = 0; c < 4; c++) u_rec[c] = w.upd[(size_t)r * 4 + c];
         if (lane < 20 && role < 2) u_bel = blob[L.bel() + lane * K + (role == 0 ? K - 1 : 0)];
@@ -895,7 +905,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
         return __syncthreads_or(abort_launch) != 0;
     };
     if (census && CENSUS_EARLY && census_says_abort(early_decision)) return;  // nothing has been written: the world is as it was
-    if (PLDS && w.upd) {  // mgx_tick's prior updates of the launch's own plan: parked where a posted plan's would be (see where a plan begins)
+    if (PLDS && UPD && w.upd) {  // mgx_tick's prior updates of the launch's own plan: parked where a posted plan's would be (see where a plan begins)
         if (tid < 4) s_urec[tid] = tid == 0 ? u_rec[0] : (tid == 1 ? u_rec[1] : (tid == 2 ? u_rec[2] : u_rec[3]));
         if (lane < 20 && role < 2) s_tmp[4 * K + role * 20 + lane] = u_bel;
         __syncthreads();
@@ -936,7 +946,14 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
         ld16_unset(R);
         constexpr bool IMM_OFF = KT > 0 && (XREC_CHUNKS - 1) * 16 * KT < 4096;
         const unsigned cstride = 16u * (unsigned)K;
-        const unsigned off = off_mine & ~GHOST_BIT, sb_x = buf ? xrec_bytes : 0u, sb_gx = buf ? gx_bytes : 0u;
+        // (the parity offsets are scalar operands of hand-written loads: said to be uniform in the lean and F_UPD forms, where the
+        // compiler otherwise selects them into a vector register, which the instruction does not take)
+        const unsigned off = off_mine & ~GHOST_BIT;
+        unsigned sb_x = buf ? xrec_bytes : 0u, sb_gx = buf ? gx_bytes : 0u;
+        if constexpr (FEAT != SWEEP_F_ALL) {
+            sb_x = (unsigned)__builtin_amdgcn_readfirstlane((int)sb_x);
+            sb_gx = (unsigned)__builtin_amdgcn_readfirstlane((int)sb_gx);
+        }
         // (ghost records crossed the fabric: their sequence word carries a mix of the payload it arrived with, mgx_dev.h — undone
         // ONCE, where a chunk is fetched, and only in waves that gather a ghost record at all: fifteen mixes per look of every lane
         // of every robot were 0.7 us of a sharded world's iteration)
@@ -1665,7 +1682,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     for (int k = 0; PLDS || k < nseg; k++) {
         if (k == 0) {  // ======================= a plan begins: the launch's own, or (LINGER) one the host posted into the running launch
             const int plans_done = PLDS ? (int)ps_word(0) : 0;
-            const bool upd_now = PLDS ? plan_dword(1) != 0u : w.upd != nullptr;  // the plan carries mgx_tick's prior updates (u_rec, u_bel)
+            const bool upd_now = UPD && (PLDS ? plan_dword(1) != 0u : w.upd != nullptr);  // the plan carries mgx_tick's prior updates (u_rec, u_bel)
             // ---- mgx_tick: update_prior_of_horizon_state (wave 0, variable K-1) and update_prior_of_current_state_v3
             // (wave 1, variable 0) on the staged image, each ending in change_prior of that variable
             // (robot.rs:2182-2338, variable.rs:203-230; same arithmetic as k_update_priors / apply_change_prior).  For
@@ -2282,7 +2299,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                         if (lane < 11) c = ld16_agent_raw(rs_s, my_off);
                         else if (lane == 11) gw = __hip_atomic_load(go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         const unsigned long long ok = __ballot(lane < 11 && c.w == seq);
-                        const uint32_t has_upd = (uint32_t)__builtin_amdgcn_readlane((int)c.y, 0);
+                        const uint32_t has_upd = UPD ? (uint32_t)__builtin_amdgcn_readlane((int)c.y, 0) : 0u;  // (!UPD: the host posts none)
                         unsigned long long g = ((unsigned long long)(uint32_t)__builtin_amdgcn_readlane((int)(gw >> 32), 11) << 32) |
                                                (uint32_t)__builtin_amdgcn_readlane((int)(gw & 0xffffffffull), 11);
                         if ((ok & 0xffull) == 0xffull && (!has_upd || (ok & 0x700ull) == 0x700ull)) { verdict = 1; break; }
@@ -2300,7 +2317,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                     }
                     if (verdict == 1) {  // payload: three dwords per chunk
                         if (lane < 8) { s_plan[3 * lane] = c.x; s_plan[3 * lane + 1] = c.y; s_plan[3 * lane + 2] = c.z; }
-                        else if (lane < 11) {
+                        else if (UPD && lane < 11) {
                             uint32_t *u = reinterpret_cast<uint32_t *>(s_urec) + 3 * (lane - 8);
                             u[0] = c.x; u[1] = c.y;
                             if (lane < 10) u[2] = c.z;
@@ -2313,7 +2330,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                 __syncthreads();
                 const int iu = role == 0 ? K - 1 : 0;
                 // (parked behind the response means in the scratch sums' block, idle between the plans)
-                if (lane < 20 && role < 2) s_tmp[4 * K + role * 20 + lane] = any_sweep ? s_prior[lane * K + iu] : blob[L.bel() + lane * K + iu];
+                if (UPD && lane < 20 && role < 2) s_tmp[4 * K + role * 20 + lane] = any_sweep ? s_prior[lane * K + iu] : blob[L.bel() + lane * K + iu];
                 if (role == ROLE_DYN && any_sweep) copy_words_wave(blob + L.bel(), s_prior, 20 * K, lane);
                 StageRegs<(KT > 0 ? 20 * KT : 2), NT> r_prior;
                 if constexpr (KT > 0) r_prior.load(blob + L.prior(), tid);

@@ -73,6 +73,12 @@ int mgx_set_linger(mgx_world *w, int32_t microseconds) {
     w->res.set_linger(microseconds);
     return MGX_OK;
 }
+int mgx_set_specialize(mgx_world *w, int32_t enabled) {
+    MGX_ENTER(w);  // (a launch that lingers ends: the next one takes the form asked for here)
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    w->res.specialize = enabled < 0 ? -1 : (enabled ? 1 : 0);
+    return MGX_OK;
+}
 int mgx_linger_stats(mgx_world *w, uint64_t *launches, uint64_t *posts, uint64_t *reruns, uint64_t *ended_by_device) {
     MGX_ENTER_SCHEDULE(w);
     if (!w) return fail(MGX_ERR_INVALID, "null world");

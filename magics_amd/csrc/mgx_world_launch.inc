@@ -214,6 +214,7 @@ struct ResidentKnobs {
         const char *e = getenv("MGX_POST_MERGE");
         return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : POST_MERGE_AUTO;
     }
+    static int32_t specialize() { const char *e = getenv("MGX_SPECIALIZE"); return !(e && e[0] == '0'); }  // 0: every resident launch in the full form
     static long long linger_ticks() {  // microseconds a workgroup waits for the next schedule before it ends the launch
         const char *off = getenv("MGX_LINGER"), *us = getenv("MGX_LINGER_US");
         const long long v = off && off[0] == '0' ? 0 : us ? atoll(us) : 300;
@@ -324,12 +325,25 @@ static bool resident_gate(const mgx_world *w, const std::vector<Launch> &plan) {
 // keys, not told to decline, the workgroup's LDS footprint, and every workgroup — with the residency census' decider, for which
 // one slot is kept free — on the device at once.  The callers draw their own consequences.
 enum ResidentFit { FITS, UNFIT_NOW, UNFIT_LDS, UNFIT_CAPACITY };
-static ResidentFit resident_fits(mgx_world *w, bool sharded) {
+// The form of the world's next resident launch (SWEEP_F_*, mgx_dev.h): tracking code only where tracking factors are enabled,
+// the prior-update path only where the launch's own schedule carries updates or the world has seen some (ResidentLaunches).
+static uint32_t resident_features(mgx_world *w, bool carries_updates) {
+    ResidentLaunches &rl = w->res;
+    if (rl.specialize < 0) rl.specialize = ResidentKnobs::specialize();
+    if (!rl.specialize) return SWEEP_F_ALL;
+    const uint32_t f = ((w->p.enable_mask & 8u) ? SWEEP_F_TRK : 0u) | ((carries_updates || rl.upd_seen) ? SWEEP_F_UPD : 0u);
+    return sweep_resident_form(w->K, f);
+}
+// The resident kernels take "nothing thaws" for granted (mgx_sweep.h: skip0 is a constant 0 there): every door to them —
+// resident_fits for a launch, linger_world_qualifies for a post — is shut while a kind thaws, and this says so once more where
+// the launch is made.
+static bool resident_launch_allowed(const mgx_world *w) { return !w->thaw_kinds && !w->ir_thaw_active && w->d.skip0 == nullptr; }
+static ResidentFit resident_fits(mgx_world *w, bool sharded, uint32_t form) {
     const DevWorld &d = w->d;
     if (!(d.ir_max_edges > 0 && !w->conns.empty() && !w->thaw_kinds && !w->ir_thaw_active && w->n_keyless == 0 && w->res.mode != ResidentLaunches::DECLINE))
         return UNFIT_NOW;
     if (sweep_lds_bytes(w->K, d.ir_max_edges, true) > sweep_resident_lds_max()) return UNFIT_LDS;
-    return d.R_local + 1 > w->res.capacity_for(d, sharded) ? UNFIT_CAPACITY : FITS;
+    return d.R_local + 1 > w->res.capacity_for(d, sharded, form) ? UNFIT_CAPACITY : FITS;
 }
 
 // ---- lingering resident launches: the host's side (mgx_dev.h; the device's side is in mgx_sweep.h) --------------------------
@@ -473,7 +487,9 @@ static bool linger_world_qualifies(const mgx_world *w) {
     return !w->dirty && !w->conns_dirty && !w->flags_dirty && !w->thaw_kinds && !w->ir_thaw_active && w->n_keyless == 0 &&
            rl.mode == ResidentLaunches::ON && (w->p.enable_mask & 2u) && rl.backoff.left == 0;
 }
-static int linger_prepare_post(mgx_world *w, const std::vector<Launch> &plan) {
+// needs_upd: the post carries prior updates — a launch of a form without them (SWEEP_F_UPD) is ended like one the plan does not
+// fit, and the schedule becomes a launch of the covering form; from then on the world's launches keep it (upd_seen).
+static int linger_prepare_post(mgx_world *w, const std::vector<Launch> &plan, bool needs_upd) {
     ResidentLaunches &rl = w->res;
     ResidentLaunches::Linger &lg = rl.linger;
     if (!lg.open) return 0;
@@ -487,7 +503,9 @@ static int linger_prepare_post(mgx_world *w, const std::vector<Launch> &plan) {
         if (rc != MGX_OK) return rc;
         if (!lg.open) return 0;
     }
-    const bool fits = linger_plan_fits(plan) && linger_world_qualifies(w);
+    const bool covered = !needs_upd || (lg.ran.features & SWEEP_F_UPD) != 0u;
+    if (needs_upd) rl.upd_seen = true;
+    const bool fits = covered && linger_plan_fits(plan) && linger_world_qualifies(w);
     if (!fits) {
         const int rc = linger_close(w);
         return rc != MGX_OK ? rc : 0;
@@ -559,7 +577,7 @@ static int post_into_open_launch(mgx_world *w, const std::vector<Launch> &plan) 
         const int rc = linger_close(w);
         return rc != MGX_OK ? rc : 0;
     }
-    const int r = linger_prepare_post(w, plan);
+    const int r = linger_prepare_post(w, plan, w->res.riding.any());
     if (r == 1) linger_post(w, plan, w->res.riding);
     return r;
 }
@@ -642,13 +660,15 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
     // What follows is this rank's own: where the ranks agree on every schedule (xres.agree) a rank
     // that cannot take part says so THERE — its launch is a single vote, and everybody takes the launch-by-launch path.
     const bool ranks_agree = sharded && w->xres.agree != nullptr;
-    const ResidentFit fit = resident_fits(w, sharded);
+    if (rl.riding.any()) rl.upd_seen = true;
+    const uint32_t form = resident_features(w, rl.riding.any());
+    const ResidentFit fit = resident_fits(w, sharded, form);
     if (fit != FITS && !ranks_agree) {
         if (fit == UNFIT_NOW || !sharded) return 0;
         if (fit == UNFIT_LDS) return fail(MGX_ERR_STATE, "resident launches were agreed on with the other ranks, but this rank's robots no longer fit LDS");
-        if (d.R_local > rl.cap_sharded)  // (no census without the ranks' agreement, so no decider workgroup either)
+        if (d.R_local > rl.capacity_for(d, true, form))  // (no census without the ranks' agreement, so no decider workgroup either)
             return fail(MGX_ERR_STATE, "resident launches were agreed on with the other ranks, but only %d of this rank's %d workgroups "
-                                       "are resident at once", rl.cap_sharded, d.R_local);
+                                       "are resident at once", rl.capacity_for(d, true, form), d.R_local);
     }
     const bool can = fit == FITS || !ranks_agree;
     tr.lap("gate + capacity");
@@ -679,13 +699,14 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
         w->d.upd = rode.dev; w->d.upd_max_speed = rode.max_speed; w->d.upd_delta_t = rode.delta_t;
         SweepRan ran;
         const bool cooperative = ResidentKnobs::cooperative();
-        const hipError_t le = can ? launch_robot_schedule(w->d, w->d.R_local, sp, sharded, cooperative, w->stream, &ran)
+        if (can && !resident_launch_allowed(w)) return fail(MGX_ERR_STATE, "internal: a resident launch while factors thaw");
+        const hipError_t le = can ? launch_robot_schedule(w->d, w->d.R_local, sp, sharded, form, cooperative, w->stream, &ran)
                                   : launch_agree_abort(w->d, sp, w->stream);
         w->d.upd = nullptr;
         if (le != hipSuccess) {
             (void)hipGetLastError();
             if (cooperative && le == hipErrorCooperativeLaunchTooLarge && i0 == 0 && !sharded) {
-                rl.cap = 0;  // until the topology (hence the workgroup's LDS) changes
+                for (int &c : rl.cap[0]) c = 0;  // until the topology (hence the workgroup's LDS) changes
                 return 0;
             }
             return fail(MGX_ERR_HIP, "resident schedule launch: %s", hipGetErrorString(le));

@@ -283,7 +283,7 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
     // a launch lingers and takes this tick: the records go straight into the coming number's slot of its box (the pinned ring's
     // slots are guarded by events, and an event behind a launch that lingers does not complete)
     int posting = 0;
-    if (w->res.linger.open && (posting = linger_prepare_post(w, plan)) < 0) return posting;
+    if (w->res.linger.open && (posting = linger_prepare_post(w, plan, true)) < 0) return posting;
     double *rec = nullptr;
     if (posting) {
         rec = linger_upd_slot(w, w->res.launch_seq + 1ull);
@@ -645,11 +645,20 @@ int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *fo
     if (form) *form = w->last_sweep_form;
     if (resident_capacity) {
         const bool sharded = w->xres.connected;
-        int cap = sharded ? w->res.cap_sharded : w->res.cap;
-        // (not asked by a launch yet: asked here, for the topology on the device — no commit, which would end a lingering launch)
-        if (cap < 0) cap = device_ok() ? sweep_resident_capacity(w->d, sharded) : 0;
+        // (of the form that ran last, or that the next launch would take; not asked by a launch yet: asked here, for the topology on
+        // the device — no commit, which would end a lingering launch)
+        const uint32_t form = w->last_sweep.ir_mode >= 0 && w->last_sweep_form != MGX_SWEEP_FORM_SEGMENTS ? w->last_sweep.features : resident_features(w, false);
+        int cap = w->res.cap[sharded ? 1 : 0][form & 3u];
+        if (cap < 0) cap = device_ok() ? sweep_resident_capacity(w->d, sharded, form) : 0;
         *resident_capacity = cap;
     }
+    return MGX_OK;
+}
+int mgx_last_sweep_features(mgx_world *w, uint32_t *features) {
+    MGX_ENTER_SCHEDULE(w);
+    if (!w || !features) return fail(MGX_ERR_INVALID, "null argument");
+    MGX_CONFIRM(w);
+    *features = w->last_sweep.ir_mode >= 0 ? w->last_sweep.features : 0u;
     return MGX_OK;
 }
 int mgx_last_search(mgx_world *w, int32_t *kernel, int32_t *row_cap, int32_t *n_launches, int32_t *n_changed, uint8_t *changed,

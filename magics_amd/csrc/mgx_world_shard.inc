@@ -594,7 +594,7 @@ int mgx_halo_resident_setup(mgx_world *w, void **area_base, uint32_t *n_ghost_sl
     const bool has_factors = d.ir_max_edges > 0 && !w->conns.empty();
     bool ok = resident_enabled() && (w->p.enable_mask & 2u) && sweep_lds_bytes(w->K, d.ir_max_edges, true) <= sweep_resident_lds_max();
     if (ok && has_factors) {
-        ok = d.R_local + 1 <= w->res.capacity_for(d, true);  // (+ the launch's decider workgroup)
+        ok = d.R_local + 1 <= w->res.capacity_for(d, true, SWEEP_F_ALL);  // (+ the launch's decider workgroup; every launch asks its own form again)
     }
     rc = ensure_resident_tables(w);  // settles this rank's segment count (progress words are created here)
     if (rc != MGX_OK) return rc;
@@ -728,7 +728,7 @@ int mgx_resident_ready(mgx_world *w, const uint8_t *steps, uint32_t n, int32_t *
     if (rc != MGX_OK) return rc;
     *ready = resident_gate(w, plan_launches(steps, n)) ? 1 : 0;
     if (*ready && !(w->xres.connected && w->xres.agree)) {  // nobody to agree with: what this world's own launch needs
-        *ready = resident_fits(w, w->xres.connected) == FITS ? 1 : 0;
+        *ready = resident_fits(w, w->xres.connected, resident_features(w, false)) == FITS ? 1 : 0;
     }
     return MGX_OK;
 }

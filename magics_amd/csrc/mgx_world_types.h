@@ -31,10 +31,11 @@ int blob_words(int K);
 bool sweep_supports(int K);
 hipError_t launch_robot_sweep(const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,
                               int snap_out, uint32_t hints, hipStream_t stream, SweepRan *ran);
-int sweep_resident_capacity(const DevWorld &w, bool sharded);
+int sweep_resident_capacity(const DevWorld &w, bool sharded, uint32_t features);
+uint32_t sweep_resident_form(int K, uint32_t features);
 size_t sweep_resident_lds_max();
-hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, bool cooperative, hipStream_t stream,
-                                 SweepRan *ran);
+hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, uint32_t features, bool cooperative,
+                                 hipStream_t stream, SweepRan *ran);
 hipError_t launch_agree_abort(const DevWorld &w, const SegPlan &plan, hipStream_t stream);
 hipError_t launch_change_prior(const DevWorld &w, int n, const int32_t *robots, const uint32_t *vars, const double *means,
                                hipStream_t stream);
@@ -529,12 +530,21 @@ struct ResidentLaunches {
     unsigned long long launch_seq = 0;  // the number of the last launch or post
     enum Mode : int32_t { OFF = 0, ON = 1, DECLINE = 2 } mode = ON;  // mgx_set_resident_launches
     Backoff backoff;
-    int cap = -1, cap_sharded = -1;  // workgroups of the resident kernel (of its sharded instantiation) the device holds at once; -1: not asked yet
-    int capacity_for(const DevWorld &d, bool sharded) {  // (asked of the runtime once per topology)
-        int &c = sharded ? cap_sharded : cap;
-        if (c < 0) c = sweep_resident_capacity(d, sharded);
+    // workgroups of the resident kernel the device holds at once, per flavour (unsharded, sharded) and form (SWEEP_F_* mask): asked
+    // of the instantiation that will run; -1: not asked yet
+    int cap[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
+    void forget_capacity() { for (auto &f : cap) for (int &c : f) c = -1; }
+    int capacity_for(const DevWorld &d, bool sharded, uint32_t form) {  // (asked of the runtime once per topology)
+        int &c = cap[sharded ? 1 : 0][form & 3u];
+        if (c < 0) c = sweep_resident_capacity(d, sharded, form);
         return c;
     }
+    // The form the world's resident launches take (mgx_dev.h, SWEEP_F_*).  specialize: 1 = the smallest form that covers the launch,
+    // 0 = always the full one (mgx_set_specialize, MGX_SPECIALIZE; -1: not asked yet).  upd_seen: a schedule with prior updates has
+    // come this way — from then on every launch can take them, so a caller who alternates mgx_iterate and mgx_tick ends a
+    // lingering launch for it once, not at every tick.
+    int32_t specialize = -1;
+    bool upd_seen = false;
     uint64_t aborts = 0, launches = 0;
     Submitted pending;      // the launch the host has enqueued but not yet seen decided (go / abort)
     RidingUpdates riding;   // the prior updates of the schedule being submitted (run_schedule sets and clears them)
@@ -569,7 +579,7 @@ struct ResidentLaunches {
         peers_valid = false;
         sweep_flag_buf.n = 0;
         flag_base = 0;
-        cap = cap_sharded = -1;
+        forget_capacity();
     }
     // commit appended robots behind the ones on the device (append_robots): progress words and exchange records are re-created
     // for the new count (a launch's first segment reads snapshots, not records) and the peer table is built again — row pointers
@@ -582,7 +592,7 @@ struct ResidentLaunches {
     }
     // the resident kernel's LDS per workgroup (hence workgroups per CU) follows the largest number of edges on one robot: a
     // capacity asked for a sparser topology says nothing about this one
-    void lds_footprint_changed() { cap = cap_sharded = -1; }
+    void lds_footprint_changed() { forget_capacity(); }
     // retopo built the peer table of the new topology beside the edge tables (or could not: no resident launches on this world now)
     void peers_rebuilt(bool built, size_t R, DevWorld &d) {
         if (built) {

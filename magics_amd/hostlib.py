@@ -240,6 +240,8 @@ SYMBOLS = {
     "mgx_num_robots": (C.c_int, [_V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mgx_last_launch_count": (C.c_int, [_V, C.POINTER(C.c_uint32)]),
     "mgx_last_sweep": (C.c_int, [_V, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mgx_last_sweep_features": (C.c_int, [_V, C.POINTER(C.c_uint32)]),
+    "mgx_set_specialize": (C.c_int, [_V, C.c_int32]),
     "mgx_last_search": (C.c_int, [_V, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _V, C.c_uint32]),
     "mgx_flush": (C.c_int, [_V]),
     "mgx_set_linger": (C.c_int, [_V, C.c_int32]),

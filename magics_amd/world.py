@@ -904,6 +904,18 @@ class World:
         self._chk(self._L.mgx_last_sweep(self._w, *[C.byref(x) for x in v]))
         return tuple(int(x.value) for x in v)
 
+    def last_sweep_features(self):
+        """the form of the sweep kernel last_sweep reports (mgx_last_sweep_features): bit 0 tracking factors, bit 1 mgx_tick's
+        prior updates; 0: the lean resident form (or no sweep ran), 3: the full form (every launch-per-segment kernel)"""
+        f = C.c_uint32()
+        self._chk(self._L.mgx_last_sweep_features(self._w, C.byref(f)))
+        return int(f.value)
+
+    def set_specialize(self, enabled):
+        """False: every resident launch in the full form of the kernel; True: the smallest form that covers it; None: the
+        default (MGX_SPECIALIZE) — mgx_set_specialize"""
+        self._chk(self._L.mgx_set_specialize(self._w, -1 if enabled is None else int(bool(enabled))))
+
     def last_search(self):
         """how the last neighbour search ran (mgx_last_search): (kernel, row_cap, n_launches, n_changed, changed) — the kernel it
         launched last (hostlib.SEARCH_*), with which row capacity (0: the two-pass forms), in how many launches, how many robots'

@@ -291,6 +291,8 @@ extern "C" {
     pub fn mgx_batch_end(w: *mut mgx_world, n_schedules: *mut u32, n_launches: *mut u32) -> c_int;
     pub fn mgx_last_launch_count(w: *mut mgx_world, n_launches: *mut u32) -> c_int;
     pub fn mgx_last_sweep(w: *mut mgx_world, variant: *mut i32, ir_mode: *mut i32, form: *mut i32, resident_capacity: *mut i32) -> c_int;
+    pub fn mgx_last_sweep_features(w: *mut mgx_world, features: *mut u32) -> c_int;
+    pub fn mgx_set_specialize(w: *mut mgx_world, enabled: i32) -> c_int;
     pub fn mgx_last_search(w: *mut mgx_world, kernel: *mut i32, row_cap: *mut i32, n_launches: *mut i32, n_changed: *mut i32, changed: *mut u8, capacity: u32) -> c_int;
     pub fn mgx_flush(w: *mut mgx_world) -> c_int;
     pub fn mgx_set_linger(w: *mut mgx_world, microseconds: i32) -> c_int;

@@ -1,5 +1,5 @@
 """Diagnostics: what the compiler made of gather_records (mgx_sweep.h) in ONE sweep-kernel instantiation, from its listing.
-usage: python tools/gather_listing.py [--flavor 1|2] [--kset 0|1|2] [-K 16] [--listing FILE.s] [extra hipcc flags ...]
+usage: python tools/gather_listing.py [--flavor 1|2] [--kset 0|1|2] [-K 16] [--features 0|2|3] [--listing FILE.s] [extra hipcc flags ...]
 Compiles magics_amd/csrc/mgx_sweep_inst.hip for that instantiation (or reads a listing made the same way), finds the gather's
 spin loop (the innermost loop around its `s_sleep 32`) and prints, per part of the gather, the instructions that are bookkeeping:
   front       the six blocks in front of the loop (addresses, first requests)
@@ -22,9 +22,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 COUNTED = ("v_mov_b64", "v_mov_b32", "v_add_u32", "v_cmp_ne_u32", "buffer_load_dwordx4", "s_waitcnt")
 
 
-def listing(flavor, kset, k, extra):
-    out = os.path.join(tempfile.mkdtemp(prefix="mgx_listing_"), f"sweep_f{flavor}_k{k}.s")
-    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-DMGX_FLAVOR={flavor}", f"-DMGX_KSET={kset}",
+def listing(flavor, kset, k, extra, features=3):
+    out = os.path.join(tempfile.mkdtemp(prefix="mgx_listing_"), f"sweep_f{flavor}_k{k}_feat{features}.s")
+    subprocess.run(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", f"-DMGX_FLAVOR={flavor}", f"-DMGX_KSET={kset}", f"-DMGX_FEAT={features}",
                     f"-DMGX_ONLY_K={k}", "-S", "--cuda-device-only", *extra, os.path.join(ROOT, "magics_amd", "csrc", "mgx_sweep_inst.hip"), "-o", out],
                    check=True, stderr=subprocess.DEVNULL)
     return out
@@ -68,9 +68,10 @@ def main():
     ap.add_argument("--flavor", type=int, default=1)
     ap.add_argument("--kset", type=int, default=1)
     ap.add_argument("-K", type=int, default=16)
+    ap.add_argument("--features", type=int, default=3, choices=(0, 2, 3), help="the form: 0 lean, 2 with prior updates, 3 full")
     ap.add_argument("--listing")
     args, extra = ap.parse_known_args()
-    path = args.listing or listing(args.flavor, args.kset, args.K, extra)
+    path = args.listing or listing(args.flavor, args.kset, args.K, extra, args.features)
     lines = open(path).read().splitlines()
     bl = blocks_of(lines)
     sleep = next((i for i, l in enumerate(lines) if re.match(r"\s+s_sleep 32\b", l)), None)

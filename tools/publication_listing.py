@@ -1,6 +1,6 @@
 """Diagnostics: what the compiler made of the publication of the exchange records (mgx_sweep.h, end of a segment of a resident
 launch) in ONE sweep-kernel instantiation, from its listing.
-usage: python tools/publication_listing.py [--flavor 1|2] [--kset 0|1|2] [-K 16] [--listing FILE.s] [extra hipcc flags ...]
+usage: python tools/publication_listing.py [--flavor 1|2] [--kset 0|1|2] [-K 16] [--features 0|2|3] [--listing FILE.s] [extra hipcc flags ...]
 Compiles magics_amd/csrc/mgx_sweep_inst.hip for that instantiation (or reads a listing made the same way) and finds the LOCAL
 publication: the first run of agent-scope 16-byte buffer stores (`buffer_store_dwordx4 ... offen ... sc1`, not `sc0 sc1`) behind a
 `; wave barrier`.  Its span runs from that barrier to the last of those stores — to the end of the innermost loop around them
@@ -78,9 +78,10 @@ def main():
     ap.add_argument("--flavor", type=int, default=1)
     ap.add_argument("--kset", type=int, default=1)
     ap.add_argument("-K", type=int, default=16)
+    ap.add_argument("--features", type=int, default=3, choices=(0, 2, 3), help="the form: 0 lean, 2 with prior updates, 3 full")
     ap.add_argument("--listing")
     args, extra = ap.parse_known_args()
-    path = args.listing or listing(args.flavor, args.kset, args.K, extra)
+    path = args.listing or listing(args.flavor, args.kset, args.K, extra, args.features)
     lines = open(path).read().splitlines()
     bl = blocks_of(lines)
     barriers = [i for i, l in enumerate(lines) if l.strip() == "; wave barrier"]
