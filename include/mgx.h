@@ -166,6 +166,15 @@ typedef struct mgx_robot_desc {
  *     the kinds of that robot's group to its launch.  Prior updates go as the kernel of their own, as in mixed calls.  Never
  *     recorded, posted or resident: mgx_last_sweep reports MGX_SWEEP_FORM_SEGMENTS.  mgx_group_enabled_stats counts the schedules
  *     (and world-wide sweeps) that ran this way BECAUSE of the masks; mixed calls keep counting in mgx_group_schedule_stats.
+ *     mgx_set_group_resident(w, 1) changes that for the world's EQUAL schedules (off by default): mgx_iterate, mgx_iterate_groups
+ *     and mgx_mission_tick_end_groups with equal schedules, mgx_tick, mgx_mission_tick_end and batches then run as on an unmasked
+ *     world — one resident launch of the masked form of the kernel (MGX_SWEEP_F_GROUP_KINDS: each workgroup reads its group's
+ *     kinds once, from the table that is uploaded in front of the launch and never written while one lingers), lingering, posts,
+ *     post merging, the residency census, prior updates riding in the launch or the post.  Mixed schedules and the world-wide
+ *     fine-grained sweeps stay group plans.  A schedule that cannot run resident (no connection yet, mgx_set_resident_launches 0,
+ *     a launch the census declined, the rest of a plan after a back-off, a post taken back) sends its prior updates as the
+ *     kernel of their own and runs as ONE group plan: mgx_group_enabled_stats counts it, and so does `fallbacks` of
+ *     mgx_group_resident_stats.  Results are the same bit for bit either way.  On an unmasked world the switch does nothing.
  *     An unmasked world, grouped or not, takes exactly the code paths it took before the call existed.
  *     MGX_ERR_STATE, nothing changes: a world that has switched a factor kind at run time (mgx_set_enabled with robots: freeze
  *     and thaw are world-wide), a world with ghosts or an engine-side exchange.  On a masked world mgx_set_enabled with a mask
@@ -305,6 +314,13 @@ int mgx_get_group_enabled(mgx_world *w, uint32_t group, uint32_t *kind_mask);
 /* What the masks have cost so far: schedules (and world-wide fine-grained sweeps) that ran as group plans only because the world
  * is masked, and the sweep-kernel launches of those.  Host bookkeeping only: no synchronisation; either pointer may be NULL. */
 int mgx_group_enabled_stats(mgx_world *w, uint64_t *masked_plans, uint64_t *masked_launches);
+/* Resident launches for a MASKED world's equal schedules (ROBOT GROUPS above): enabled != 0 switches them on for this world, 0
+ * (the default) off.  An ordinary call: it ends a lingering launch first.  _stats: resident launches of the masked form made so
+ * far (a launch the residency census declined counts, as in mgx_resident_stats), schedules posted into one (a post taken back
+ * does not count), and schedules of the switched-on masked world that ran as group plans all the same.  Host bookkeeping only: no
+ * synchronisation; any pointer may be NULL. */
+int mgx_set_group_resident(mgx_world *w, int32_t enabled);
+int mgx_group_resident_stats(mgx_world *w, uint64_t *launches, uint64_t *posts, uint64_t *fallbacks);
 /* Batches: several schedules, one submission.  A resident schedule launch pays for itself once — the robots' graphs go
  * HBM -> LDS when it starts and back when it ends, a sixth of a ten-iteration launch at 1000 x 16 — so a caller that issues
  * schedule after schedule with nothing in between (the reference's `iterate_gbp_v2` loop run ahead of the renderer, a planner
@@ -346,11 +362,14 @@ int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *fo
  * where its own schedule carries none and the world has issued no mgx_tick so far (MGX_SWEEP_F_UPDATES).  A lingering launch
  * keeps its form: an mgx_tick that meets a launch without MGX_SWEEP_F_UPDATES ends it and runs as a launch of the covering
  * form, and the world's launches keep that form from then on.  Results are the same bit for bit in every form.
+ * A masked world with mgx_set_group_resident on has ONE form, whatever mgx_set_specialize says: the full one with the enabled
+ * internal kinds read per robot group (MGX_SWEEP_F_GROUP_KINDS | MGX_SWEEP_F_TRACKING | MGX_SWEEP_F_UPDATES = 7).
  * mgx_last_sweep_features: the form of the sweep mgx_last_sweep reports (launch-per-segment kernels: always both bits; 0 as well
  * when no sweep ran).  mgx_set_specialize: 0 = every resident launch of this world in the full form (MGX_SPECIALIZE=0 in the
  * environment does it for the process), 1 = the smallest form, < 0: as the environment says.  For measuring one against the other. */
 #define MGX_SWEEP_F_TRACKING 1u
 #define MGX_SWEEP_F_UPDATES 2u
+#define MGX_SWEEP_F_GROUP_KINDS 4u
 int mgx_last_sweep_features(mgx_world *w, uint32_t *features);
 int mgx_set_specialize(mgx_world *w, int32_t enabled);
 /* How the last neighbour search of this world (mgx_neighbours, mgx_update_topology, a mission tick's) ran, as the branch that

@@ -266,6 +266,14 @@ public:
         check(mgx_group_enabled_stats(w_, &s[0], &s[1]));
         return s;
     }
+    /// a masked world's equal schedules as resident launches of the masked form (mgx_set_group_resident; off by default)
+    void set_group_resident(bool enabled) { check(mgx_set_group_resident(w_, enabled ? 1 : 0)); }
+    /// resident launches of the masked form, schedules posted into one, schedules that ran as group plans all the same
+    std::array<uint64_t, 3> group_resident_stats() {
+        std::array<uint64_t, 3> s{};
+        check(mgx_group_resident_stats(w_, &s[0], &s[1], &s[2]));
+        return s;
+    }
     /// several iterate_gbp_v2 calls, one submission (mgx_batch_begin / mgx_batch_end): `{ auto b = world.batch(); for (...) world.iterate_gbp_v2(s); }`
     struct Batch {
         mgx_world *w;

@@ -273,7 +273,8 @@ struct DevWorld {
     const GroupSeg *group_seg;  // [groups]: every group a local robot is in has a record
     // Enabled factor kinds per robot group (mgx_set_group_enabled): the INTERNAL kinds (bits 1, 4, 8) of every group, read beside
     // the group's segment record where `enable` is read otherwise — `enable & 2u` stays the world's.  Null unless the world is
-    // MASKED (some group's kinds differ from the world's); a masked world's launches all carry segment records.
+    // MASKED (some group's kinds differ from the world's); a masked world's launches all carry segment records — but for its
+    // resident launches (SWEEP_F_GRP), which read group_of and this table and have no segment records (group_seg is null).
     const uint32_t *group_enable;  // [groups], as group_seg
 };
 
@@ -546,6 +547,9 @@ struct LingerBox {  // host-mapped
 constexpr uint32_t SWEEP_F_TRK = 1u;  // the world's tracking factors are enabled
 constexpr uint32_t SWEEP_F_UPD = 2u;  // plans may carry mgx_tick's prior updates
 constexpr uint32_t SWEEP_F_ALL = SWEEP_F_TRK | SWEEP_F_UPD;
+// ... and the MASKED form (mgx_set_group_resident): the internal kinds are the robot's GROUP's, read from DevWorld::group_enable
+// once per workgroup.  One instantiation, SWEEP_F_GRP | SWEEP_F_ALL, of the unsharded resident kernel.
+constexpr uint32_t SWEEP_F_GRP = 4u;
 struct SweepRan {
     int32_t variant = 0;   // KT of the template: a constant horizon, or 0 / -1 for the run-time-K kernels
     int32_t ir_mode = -1;  // IR_NONE / IR_GLOBAL / IR_STAGED (mgx_sweep.h); -1: nothing launched

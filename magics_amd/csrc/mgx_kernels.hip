@@ -808,8 +808,13 @@ static int sweep_variant_of(int K) {
 #define MGX_DECLARE_SET(N)                                                                                                          \
     bool sweep_plain_set##N(int kt, const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,   \
                             int snap_out, uint32_t hints, hipStream_t stream, SweepRan *ran);                                       \
-    MGX_DECLARE_FORM(N, 0) MGX_DECLARE_FORM(N, 2) MGX_DECLARE_FORM(N, 3)
-// (one object per flavour, horizon set and form: lean, with prior updates, full — SWEEP_F_*, mgx_dev.h)
+    MGX_DECLARE_FORM(N, 0) MGX_DECLARE_FORM(N, 2) MGX_DECLARE_FORM(N, 3) MGX_DECLARE_MASKED(N)
+// (one object per flavour, horizon set and form: lean, with prior updates, full — SWEEP_F_*, mgx_dev.h; the masked form,
+// SWEEP_F_GRP | SWEEP_F_ALL, is unsharded only)
+#define MGX_DECLARE_MASKED(N)                                                                                                           \
+    int resident_capacity_set##N##_f7(int kt, const DevWorld &w);                                                                       \
+    bool resident_launch_set##N##_f7(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream, \
+                                     hipError_t *err, SweepRan *ran);
 #define MGX_DECLARE_FORM(N, F)                                                                                                          \
     int resident_capacity_set##N##_f##F(int kt, const DevWorld &w);                                                                     \
     bool resident_launch_set##N##_f##F(int kt, const DevWorld &w, int n_robots, const SegPlan &plan, bool cooperative, hipStream_t stream, \
@@ -821,6 +826,7 @@ MGX_DECLARE_SET(0)
 MGX_DECLARE_SET(1)
 MGX_DECLARE_SET(2)
 #undef MGX_DECLARE_FORM
+#undef MGX_DECLARE_MASKED
 #undef MGX_DECLARE_SET
 
 hipError_t launch_robot_sweep(const DevWorld &w, int robot0, int n_robots, uint32_t ext_mask, uint32_t int_mask, int n_int,
@@ -838,8 +844,9 @@ hipError_t launch_robot_sweep(const DevWorld &w, int robot0, int n_robots, uint3
 constexpr size_t RESIDENT_LDS_MAX = 160 * 1024;
 size_t sweep_resident_lds_max() { return RESIDENT_LDS_MAX; }
 // The form a launch of these features runs in: the smallest instantiated one that covers them (lean, SWEEP_F_UPD, full); the
-// run-time-K kernels have the full form only.
+// run-time-K kernels have the full form only.  Kinds per robot group (SWEEP_F_GRP): the masked form, whatever else is asked.
 uint32_t sweep_resident_form(int K, uint32_t features) {
+    if (features & SWEEP_F_GRP) return SWEEP_F_GRP | SWEEP_F_ALL;
     if (sweep_variant_of(K) <= 0 || (features & SWEEP_F_TRK)) return SWEEP_F_ALL;
     return features & SWEEP_F_UPD;
 }
@@ -850,12 +857,15 @@ struct ResidentForm { CapacityFn capacity[3]; LaunchFn launch[3]; };  // per hor
 static const ResidentForm &resident_form(bool sharded, uint32_t form) {
     static const ResidentForm forms[2][3] = {{MGX_FORM(resident, 0), MGX_FORM(resident, 2), MGX_FORM(resident, 3)},
                                              {MGX_FORM(sharded, 0), MGX_FORM(sharded, 2), MGX_FORM(sharded, 3)}};
+    static const ResidentForm masked = MGX_FORM(resident, 7);
+    if (form & SWEEP_F_GRP) return masked;  // (the callers refuse it on sharded worlds)
     return forms[sharded ? 1 : 0][form == 0u ? 0 : form == SWEEP_F_UPD ? 1 : 2];
 }
 #undef MGX_FORM
 // workgroups of the resident kernel the device holds at once (sharded: of the instantiation that takes ghost records in-launch):
 // asked of the instantiation that `features` runs in
 int sweep_resident_capacity(const DevWorld &w, bool sharded, uint32_t features) {
+    if ((features & SWEEP_F_GRP) && sharded) return 0;
     const int kt = sweep_variant_of(w.K);
     const ResidentForm &f = resident_form(sharded, sweep_resident_form(w.K, features));
     int cap = -1;
@@ -865,6 +875,8 @@ int sweep_resident_capacity(const DevWorld &w, bool sharded, uint32_t features) 
 hipError_t launch_robot_schedule(const DevWorld &w, int n_robots, const SegPlan &plan, bool sharded, uint32_t features, bool cooperative,
                                  hipStream_t stream, SweepRan *ran) {
     if (n_robots <= 0 || plan.n <= 0) return hipSuccess;
+    // the masked form reads the robots' groups and the groups' kinds: unsharded worlds only, and both tables there
+    if ((features & SWEEP_F_GRP) && (sharded || !w.group_of || !w.group_enable)) return hipErrorInvalidValue;
     const int kt = sweep_variant_of(w.K);
     const ResidentForm &f = resident_form(sharded, sweep_resident_form(w.K, features));
     hipError_t e = hipErrorInvalidValue;

@@ -303,7 +303,8 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     constexpr bool HAS_IR = IRM != IR_NONE, STAGE_IR = IRM == IR_STAGED;
     static_assert(PERSIST || FEAT == SWEEP_F_ALL, "only resident schedule launches have lean forms");
     static_assert(!(FEAT & SWEEP_F_TRK) || (FEAT & SWEEP_F_UPD), "forms: lean, F_UPD, full");
-    constexpr bool TRK = (FEAT & SWEEP_F_TRK) != 0u, UPD = (FEAT & SWEEP_F_UPD) != 0u;
+    static_assert(!(FEAT & SWEEP_F_GRP) || (PERSIST && !SHARD && (FEAT & SWEEP_F_ALL) == SWEEP_F_ALL), "the masked form: full, unsharded, resident");
+    constexpr bool TRK = (FEAT & SWEEP_F_TRK) != 0u, UPD = (FEAT & SWEEP_F_UPD) != 0u, GRP = (FEAT & SWEEP_F_GRP) != 0u;
     constexpr int NW = sweep_waves<KT, PERSIST>(), NT = 64 * NW;  // waves / threads of a workgroup
     constexpr int ROLE_DF = NW == 4 ? 2 : ROLE_DYN, ROLE_UF = NW == 4 ? 3 : ROLE_UV;  // who computes the dynamic / the unary factors' messages
     static_assert(!PERSIST || IRM == IR_STAGED, "resident schedule launches exist for worlds with staged inter-robot messages");
@@ -584,13 +585,18 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     // sweeps leave s_snap and s_epoch alone), and a workgroup with nothing to run at all copies them and leaves without staging
     // its graph: what the full path leaves for an idle robot (no prior updates ride in a mixed launch).
     // The enabled INTERNAL kinds are the group's as well where the world is masked (mgx_set_group_enabled: DevWorld::group_enable),
-    // one more scalar of the same kind; `kinds()` is what every read of bits 1, 4 and 8 goes through.  Resident launches never
-    // read the table (a masked world runs none): theirs is the kernel argument itself, as ever.
+    // one more scalar of the same kind; `kinds()` is what every read of bits 1, 4 and 8 goes through.  Resident launches read
+    // the kernel argument itself — but for the masked form (GRP: mgx_set_group_resident), whose workgroup reads its group's kinds
+    // from the table ONCE, here, for the launch and every plan posted into it (the table is never written while a launch lingers).
     uint32_t group_kinds = w.enable;
     auto kinds = [&]() __attribute__((always_inline)) -> uint32_t {
-        if constexpr (PERSIST) return TRK ? w.enable : (w.enable & 7u);
+        if constexpr (PERSIST && !GRP) return TRK ? w.enable : (w.enable & 7u);
         else return group_kinds;
     };
+    if constexpr (GRP) {
+        const int g = __builtin_amdgcn_readfirstlane((int)w.group_of[r]);
+        group_kinds = (uint32_t)__builtin_amdgcn_readfirstlane((int)w.group_enable[g]);
+    }
     if constexpr (!PERSIST) {
         if (w.group_seg) {
             const int g = __builtin_amdgcn_readfirstlane((int)w.group_of[r]);
@@ -619,7 +625,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
     // (resident launches: the host starts none while anything thaws — resident_fits, linger_world_qualifies — and says so where it
     // launches, so it is 0 in all of them; a CONSTANT 0 in the lean and F_UPD forms.  The full forms keep the read: written as a
     // constant there it moved their register allocation, and four of them spilled more than before.)
-    const uint32_t skip0 = (FEAT == SWEEP_F_ALL && w.skip0) ? (uint32_t)w.skip0[r] : 0u;
+    const uint32_t skip0 = ((FEAT & SWEEP_F_ALL) == SWEEP_F_ALL && w.skip0) ? (uint32_t)w.skip0[r] : 0u;
     const bool idle = w.idle[r] != 0;
     const bool radio = (w.antenna[r] != 0) && !idle;
 

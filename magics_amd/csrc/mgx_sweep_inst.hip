@@ -10,18 +10,22 @@
 //                       scenarios; 0 / -1 = the run-time-K fallbacks
 //   MGX_FEAT 0 | 2 | 3  (resident flavours) the form, SWEEP_F_* of mgx_dev.h: lean, with prior updates, full.  The run-time-K
 //                       kernels exist in the full form only.
+//   MGX_FEAT 7          (MGX_FLAVOR 1 only) the masked form: full, the internal kinds per robot group (SWEEP_F_GRP); every horizon
 // Every object exports `..._set<KSET>` functions that answer "not mine" (false / -1) for a horizon variant of another
 // set; mgx_kernels.hip asks them in turn.
 #include "mgx_sweep.h"
 
 #ifndef MGX_FLAVOR
-#error "compile with -DMGX_FLAVOR=0|1|2 -DMGX_KSET=0|1|2 [-DMGX_FEAT=0|2|3]"
+#error "compile with -DMGX_FLAVOR=0|1|2 -DMGX_KSET=0|1|2 [-DMGX_FEAT=0|2|3|7]"
 #endif
 #ifndef MGX_FEAT
 #define MGX_FEAT 3
 #endif
-#if MGX_FEAT != 0 && MGX_FEAT != 2 && MGX_FEAT != 3
-#error "MGX_FEAT: 0 (lean), 2 (prior updates) or 3 (full)"
+#if MGX_FEAT != 0 && MGX_FEAT != 2 && MGX_FEAT != 3 && MGX_FEAT != 7
+#error "MGX_FEAT: 0 (lean), 2 (prior updates), 3 (full) or 7 (masked: full, kinds per robot group)"
+#endif
+#if MGX_FEAT == 7 && MGX_FLAVOR != 1
+#error "the masked form exists for unsharded resident launches only"
 #endif
 #if MGX_FLAVOR == 0 && MGX_FEAT != 3
 #error "launch-per-segment kernels have the full form only"
@@ -48,7 +52,7 @@
 #define MGX_K_LIST(DO) DO(MGX_ONLY_K)
 #define MGX_K_CONST(DO) DO(MGX_ONLY_K)
 #endif
-#if MGX_FEAT == 3
+#if MGX_FEAT == 3 || MGX_FEAT == 7
 #define MGX_FORM_K_LIST(DO) MGX_K_LIST(DO)
 #else
 #define MGX_FORM_K_LIST(DO) MGX_K_CONST(DO)

@@ -507,6 +507,23 @@ int mgx_group_enabled_stats(mgx_world *w, uint64_t *masked_plans, uint64_t *mask
     if (masked_launches) *masked_launches = w->gkinds.masked_launches;
     return MGX_OK;
 }
+// A masked world's equal schedules as resident launches of the masked form (include/mgx.h, ROBOT GROUPS).  A switch of the world,
+// off by default; like every call that is no schedule it ends a lingering launch first, so no launch outlives the form it was
+// chosen under.
+int mgx_set_group_resident(mgx_world *w, int32_t enabled) {
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    MGX_ENTER(w);
+    MGX_CONFIRM(w);  // (a launch the census declined is run again under the setting it was issued with)
+    w->gkinds.resident = enabled != 0;
+    return MGX_OK;
+}
+int mgx_group_resident_stats(mgx_world *w, uint64_t *launches, uint64_t *posts, uint64_t *fallbacks) {
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    if (launches) *launches = w->gkinds.res_launches;
+    if (posts) *posts = w->gkinds.res_posts;
+    if (fallbacks) *fallbacks = w->gkinds.res_fallbacks;
+    return MGX_OK;
+}
 
 // FactorGraph::update_inter_robot_safety_distance_multiplier for every graph + the config entry new factors read
 // (factorgraph.rs:892-910, interrobot.rs:87-89, ui/settings.rs:586-590).  The multiplier lives in w->p: every record the host

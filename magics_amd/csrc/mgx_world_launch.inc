@@ -9,9 +9,66 @@ static void log_launch(mgx_world *w, int robot, uint32_t ext_mask, uint32_t int_
 static void log_plan(mgx_world *w, const std::vector<Launch> &plan, size_t from = 0, size_t n = ~(size_t)0) {
     for (size_t k = from; k < plan.size() && k - from < n; k++) log_launch(w, -1, plan[k].ext, int_phases(plan[k]), plan[k].n_int);
 }
+// A masked world whose schedules may run resident (mgx_set_group_enabled + mgx_set_group_resident): the form of its launches reads
+// the robots' groups and the groups' kinds (SWEEP_F_GRP, mgx_dev.h)
+static bool masked_resident(const mgx_world *w) { return w->gkinds.masked() && w->gkinds.resident; }
+static int run_masked_plan(mgx_world *w, const std::vector<Launch> &plan);
+// Prior updates that were to ride in a schedule, sent as the kernel of their own instead (no launch of a group plan carries
+// them): mgx_tick's records — one per device robot, (waypoint, time scale, what) — become mgx_update_priors' lists; the
+// mission's are in device memory, where launch_mission_prepare wrote the lists beside them.
+static int send_riding_updates(mgx_world *w, const RidingUpdates &upd) {
+    if (!upd.any()) return MGX_OK;
+    if (!upd.host) {
+        const mgx_world::Mission &ms = w->mission;
+        if (upd.dev != ms.rec_d.p) return fail(MGX_ERR_STATE, "internal: riding prior updates in device memory that are not the mission's");
+        HIP_TRY(launch_update_priors(w->d, (int)w->robots.size(), ms.robots_d.p, ms.waypoints_d.p, ms.ts_list_d.p, ms.what_d.p, upd.max_speed, upd.delta_t, w->stream));
+        return MGX_OK;
+    }
+    // (copied out first: the records may sit in a ring slot already released, which the acquire below could hand out again)
+    const size_t RL = (size_t)w->d.R_local;
+    const std::vector<double> rec(upd.host, upd.host + 4 * RL);
+    std::vector<int32_t> who;
+    for (size_t dr = 0; dr < RL; dr++)
+        if (rec[4 * dr + 3] != 0.0) who.push_back((int32_t)dr);
+    const size_t n = who.size();
+    if (n == 0) return MGX_OK;
+    // packed arguments, f64 words: waypoints[2n] | time_scale[n] | device robot (int32)[n] | what (u8)[n]
+    const size_t w_r = (n + 1) / 2, w_w = (n + 7) / 8, words = 3 * n + w_r + w_w;
+    void *hp = nullptr, *dp = nullptr;
+    int slot = 0;
+    HIP_TRY(w->stage.acquire(words * sizeof(double), &hp, &slot));
+    double *hw = (double *)hp;
+    int32_t *hr = (int32_t *)(hw + 3 * n);
+    uint8_t *hh = (uint8_t *)(hw + 3 * n + w_r);
+    for (size_t i = 0; i < n; i++) {
+        const double *q = &rec[4 * (size_t)who[i]];
+        hw[2 * i] = q[0]; hw[2 * i + 1] = q[1]; hw[2 * n + i] = q[2];
+        hr[i] = who[i];
+        hh[i] = (uint8_t)q[3];
+    }
+    HIP_TRY(hipHostGetDevicePointer(&dp, hp, 0));
+    const double *dw = (const double *)dp;
+    HIP_TRY(launch_update_priors(w->d, (int)n, (const int32_t *)(dw + 3 * n), dw, dw + 2 * n, (const uint8_t *)(dw + 3 * n + w_r), upd.max_speed,
+                                 upd.delta_t, w->stream));
+    HIP_TRY(w->stage.release(slot, w->stream));
+    return MGX_OK;
+}
 // Runs `plan` from segment `from` on launch by launch.  Prior updates ride in the first of these launches only, and the pinned
 // ring slot they sit in is released behind it (an event-record error is reported only if the sweep itself succeeded).
+// A masked world comes here only with mgx_set_group_resident on, from a schedule that could not run (or go on) resident: the
+// riding updates go out as the kernel of their own, then the segments left are ONE group plan (run_masked_plan).
 static int run_segments(mgx_world *w, const std::vector<Launch> &plan, size_t from, const RidingUpdates &upd) {
+    if (w->gkinds.masked()) {
+        int rc = send_riding_updates(w, upd);
+        if (upd.slot >= 0) {
+            const hipError_t e = w->stage.release(upd.slot, w->stream);
+            if (rc == MGX_OK && e != hipSuccess) rc = fail(MGX_ERR_HIP, "event record: %s", hipGetErrorString(e));
+        }
+        if (rc != MGX_OK) return rc;
+        w->gkinds.res_fallbacks++;
+        if (from == 0) return run_masked_plan(w, plan);
+        return run_masked_plan(w, std::vector<Launch>(plan.begin() + (long)std::min(from, plan.size()), plan.end()));
+    }
     for (size_t k = from; k < plan.size(); k++) {
         const bool rides = k == from && upd.dev;
         if (rides) { w->d.upd = upd.dev; w->d.upd_max_speed = upd.max_speed; w->d.upd_delta_t = upd.delta_t; }
@@ -311,7 +368,9 @@ static int ensure_resident_tables(mgx_world *w) {
 static bool resident_gate(const mgx_world *w, const std::vector<Launch> &plan) {
     if (!resident_enabled() || w->res.mode == ResidentLaunches::OFF || plan.size() < 2) return false;
     if (w->res.backoff.left > 0) return false;  // a recent launch found the GPU shared (residency census): launch by launch for a while
-    if (w->gkinds.masked()) return false;       // enabled kinds per group (mgx_set_group_enabled): the resident kernel reads the world's only
+    // enabled kinds per group (mgx_set_group_enabled): the resident kernel reads the world's only — but for its masked form, which
+    // the world has to ask for (mgx_set_group_resident)
+    if (w->gkinds.masked() && (!w->gkinds.resident || w->xres.connected)) return false;
     const DevWorld &d = w->d;
     const bool sharded = w->xres.connected;  // the ranks have agreed (mgx_halo_resident_connect_peers) that ghost records travel inside the launches
     if ((d.R_total != d.R_local && !sharded) || !(w->p.enable_mask & 2u)) return false;
@@ -329,6 +388,7 @@ enum ResidentFit { FITS, UNFIT_NOW, UNFIT_LDS, UNFIT_CAPACITY };
 // the prior-update path only where the launch's own schedule carries updates or the world has seen some (ResidentLaunches).
 static uint32_t resident_features(mgx_world *w, bool carries_updates) {
     ResidentLaunches &rl = w->res;
+    if (masked_resident(w)) return SWEEP_F_GRP | SWEEP_F_ALL;  // (the one masked form, whatever mgx_set_specialize says)
     if (rl.specialize < 0) rl.specialize = ResidentKnobs::specialize();
     if (!rl.specialize) return SWEEP_F_ALL;
     const uint32_t f = ((w->p.enable_mask & 8u) ? SWEEP_F_TRK : 0u) | ((carries_updates || rl.upd_seen) ? SWEEP_F_UPD : 0u);
@@ -403,9 +463,10 @@ static void linger_confirm(mgx_world *w) {
 }
 // Submits `plan` with `upd` riding in it: posted or as resident launches where the world qualifies, launch by launch where not.
 // The one place where a schedule's prior updates are set on the world, and cleared.  lap: the caller's stage clock (mgx_tick).
-static int run_masked_plan(mgx_world *w, const std::vector<Launch> &plan);
 static int run_schedule(mgx_world *w, const std::vector<Launch> &plan, const RidingUpdates &upd, StageTimer *lap = nullptr) {
-    if (w->gkinds.masked()) {  // (never posted, never resident; its callers send the prior updates as the kernel of their own)
+    // (a masked world: never posted, never resident — its callers send the prior updates as the kernel of their own — unless it
+    // asked for the masked form: mgx_set_group_resident.  Then it goes the way of every world, and run_segments is its fall-back.)
+    if (w->gkinds.masked() && !w->gkinds.resident) {
         if (upd.any()) return fail(MGX_ERR_STATE, "internal: prior updates riding in a masked world's schedule");
         return run_masked_plan(w, plan);
     }
@@ -433,6 +494,7 @@ static int linger_settle(mgx_world *w, bool nested = false) {  // nested: on the
         Submitted un = std::move(lg.un);
         lg.un = Submitted{};
         lg.reruns += un.schedules;
+        if (lg.ran.features & SWEEP_F_GRP) w->gkinds.res_posts -= std::min<uint64_t>(w->gkinds.res_posts, un.schedules);  // (not posted after all)
         un.take_back(w);
         RidingUpdates upd;
         if (un.upd.any()) {  // (a copy in the pinned ring: the box's slot belongs to the posts of the launch that follows)
@@ -503,7 +565,9 @@ static int linger_prepare_post(mgx_world *w, const std::vector<Launch> &plan, bo
         if (rc != MGX_OK) return rc;
         if (!lg.open) return 0;
     }
-    const bool covered = !needs_upd || (lg.ran.features & SWEEP_F_UPD) != 0u;
+    // (... and a launch whose form reads the world's kinds takes no plan of a world that needs its groups', or the other way
+    // round: whoever masks a world or moves the switch has ended the launch already — MGX_ENTER — so this only says it again)
+    const bool covered = (!needs_upd || (lg.ran.features & SWEEP_F_UPD) != 0u) && ((lg.ran.features & SWEEP_F_GRP) != 0u) == masked_resident(w);
     if (needs_upd) rl.upd_seen = true;
     const bool fits = covered && linger_plan_fits(plan) && linger_world_qualifies(w);
     if (!fits) {
@@ -550,6 +614,7 @@ static void linger_post(mgx_world *w, const std::vector<Launch> &plan, const Rid
     lg.plans_posted++;
     lg.schedules_in_plans += un.schedules;
     lg.largest_plan = std::max<uint64_t>(lg.largest_plan, un.schedules);
+    if (lg.ran.features & SWEEP_F_GRP) w->gkinds.res_posts += un.schedules;
     un.upd = RidingUpdates{};
     if (upd.any()) {
         double *slot = linger_upd_slot(w, P);
@@ -564,6 +629,43 @@ static void linger_post(mgx_world *w, const std::vector<Launch> &plan, const Rid
     w->last_sweep_launches++;  // (one submission: the schedule runs inside the launch that is there)
     w->last_sweep = lg.ran;
     w->last_sweep_form = MGX_SWEEP_FORM_POSTED;
+}
+
+static uint32_t groups_in_use(const mgx_world *w);
+// The robots' groups by device index, as they are now: uploaded again only when the layout has changed them.
+static int ensure_group_of(mgx_world *w) {
+    mgx_world::GroupSchedules &gs = w->gsched;
+    const size_t RL = (size_t)w->d.R_local;
+    std::vector<uint32_t> now(RL);
+    for (size_t dr = 0; dr < RL; dr++) now[dr] = w->sets.group[(size_t)w->robot_of[dr]];
+    if (now != gs.group_of || !gs.group_of_d.p) {
+        gs.group_of.swap(now);
+        HIP_TRY(gs.group_of_d.upload(gs.group_of, w->stream, (size_t)std::max(w->R_cap, 0)));
+        HIP_TRY(hipStreamSynchronize(w->stream));  // (pageable memory: the copy has left it)
+    }
+    return MGX_OK;
+}
+// What a masked world's resident launch reads (SWEEP_F_GRP): the robots' groups and the groups' kinds by group id, under the
+// rule of run_group_plan — the kinds are fixed once a group has robots, so the table goes up again only when a group joined or was
+// given its kinds (a table that a mixed call left longer than the groups in use serves as it is).  Never while a launch lingers:
+// run_resident comes here behind its commit, which has ended one.
+static int ensure_group_kinds(mgx_world *w) {
+    const int rc = ensure_group_of(w);
+    if (rc != MGX_OK) return rc;
+    mgx_world::GroupKinds &gk = w->gkinds;
+    if (w->res.linger.open) return fail(MGX_ERR_STATE, "internal: the groups' kinds written while a launch lingers");
+    const size_t top = std::max((size_t)groups_in_use(w), gk.table.size());
+    std::vector<uint32_t> kinds(top);
+    for (size_t g = 0; g < top; g++) kinds[g] = w->kinds_of_group((uint32_t)g);
+    if (kinds != gk.table || !gk.table_d.p) {
+        if (top > gk.table_d.cap) HIP_TRY(hipStreamSynchronize(w->stream));  // (an array that has to grow is freed first: nothing may still read it)
+        gk.table.swap(kinds);
+        HIP_TRY(gk.table_d.upload(gk.table, w->stream, (size_t)MGX_GROUPS_MAX));
+        HIP_TRY(hipStreamSynchronize(w->stream));  // (pageable memory: the copy has left it)
+    }
+    for (const uint32_t g : w->gsched.group_of)
+        if ((size_t)g >= gk.table.size()) return fail(MGX_ERR_STATE, "internal: robot group %u beyond the kinds table", g);
+    return MGX_OK;
 }
 
 // ---- run_resident, step by step -------------------------------------------------------------------------------------------
@@ -617,6 +719,7 @@ static void part_launched(mgx_world *w, const std::vector<Launch> &plan, size_t 
     ResidentLaunches &rl = w->res;
     w->last_sweep_launches++;
     rl.launches++;
+    if (can && (ran.features & SWEEP_F_GRP)) w->gkinds.res_launches++;
     if (can) {  // (a rank that voted no launched no sweep)
         w->last_sweep = ran;
         w->last_sweep_form = sharded ? MGX_SWEEP_FORM_SHARDED : MGX_SWEEP_FORM_RESIDENT;
@@ -674,6 +777,8 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
     tr.lap("gate + capacity");
     if ((rc = ensure_resident_tables(w)) != MGX_OK) return rc;
     tr.lap("peer tables");
+    const bool by_groups = (form & SWEEP_F_GRP) != 0u;  // the masked form: the robots' groups and the groups' kinds, in front of the launch
+    if (by_groups && (rc = ensure_group_kinds(w)) != MGX_OK) return rc;
     w->stale_kinds |= ~w->p.enable_mask & 15u;  // disabled factors miss what these sweeps deliver
     const bool census = sharded ? ranks_agree : ResidentKnobs::census();
     for (size_t i0 = 0; i0 < plan.size(); i0 += MAX_SEGS) {
@@ -697,12 +802,15 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
         }
         const RidingUpdates rode = i0 == 0 ? rl.riding : RidingUpdates{};
         w->d.upd = rode.dev; w->d.upd_max_speed = rode.max_speed; w->d.upd_delta_t = rode.delta_t;
+        if (by_groups) { w->d.group_of = w->gsched.group_of_d.p; w->d.group_enable = w->gkinds.table_d.p; }  // (group_seg stays null)
         SweepRan ran;
         const bool cooperative = ResidentKnobs::cooperative();
         if (can && !resident_launch_allowed(w)) return fail(MGX_ERR_STATE, "internal: a resident launch while factors thaw");
         const hipError_t le = can ? launch_robot_schedule(w->d, w->d.R_local, sp, sharded, form, cooperative, w->stream, &ran)
                                   : launch_agree_abort(w->d, sp, w->stream);
         w->d.upd = nullptr;
+        w->d.group_of = nullptr;
+        w->d.group_enable = nullptr;
         if (le != hipSuccess) {
             (void)hipGetLastError();
             if (cooperative && le == hipErrorCooperativeLaunchTooLarge && i0 == 0 && !sharded) {
@@ -776,17 +884,9 @@ static int run_group_plan(mgx_world *w, const GroupPlan &gp, bool by_masks = fal
     const size_t RL = (size_t)w->d.R_local;
     if (gp.n_launches == 0 || RL == 0) return MGX_OK;
     // (a robot that has left keeps its group: every group on the device has a record, all-zero — sits out — beyond n_groups)
-    std::vector<uint32_t> now(RL);
+    if ((rc = ensure_group_of(w)) != MGX_OK) return rc;
     size_t top = gp.n_groups;
-    for (size_t dr = 0; dr < RL; dr++) {
-        now[dr] = w->sets.group[(size_t)w->robot_of[dr]];
-        top = std::max(top, (size_t)now[dr] + 1);
-    }
-    if (now != gs.group_of || !gs.group_of_d.p) {
-        gs.group_of.swap(now);
-        HIP_TRY(gs.group_of_d.upload(gs.group_of, w->stream, (size_t)std::max(w->R_cap, 0)));
-        HIP_TRY(hipStreamSynchronize(w->stream));  // (pageable memory: the copy has left it)
-    }
+    for (const uint32_t g : gs.group_of) top = std::max(top, (size_t)g + 1);
     std::vector<uint32_t> members(top, 0u);
     for (size_t dr = 0; dr < RL; dr++) members[gs.group_of[dr]]++;
     const size_t n_rec = gp.n_launches * top;

@@ -340,8 +340,10 @@ static int mission_tick_end(mgx_world *w, const uint8_t *antennas, double max_sp
     w->last_sweep_launches = 0;
     w->last_sweep = SweepRan{};
     w->last_sweep_form = -1;
-    // (a masked world — mgx_set_group_enabled — sends its prior updates as mixed calls do: no launch of a group plan carries them)
-    const bool fuse = !mixed && !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0 && !w->gkinds.masked();
+    // (a masked world — mgx_set_group_enabled — sends its prior updates as mixed calls do: no launch of a group plan carries them;
+    // with mgx_set_group_resident they ride, and every fall-back to a group plan sends them first: run_segments)
+    const bool fuse = !mixed && !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0 &&
+                      (!w->gkinds.masked() || w->gkinds.resident);
     if (mixed) {
         HIP_TRY(launch_update_priors(w->d, R, ms.robots_d.p, ms.waypoints_d.p, ms.ts_list_d.p, ms.what_d.p, max_speed, delta_t, s));
         rc = run_group_plan(w, *mixed);

@@ -264,8 +264,10 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
     w->last_sweep_launches = 0;
     w->last_sweep = SweepRan{};
     w->last_sweep_form = -1;
-    // (a masked world — mgx_set_group_enabled — sends its prior updates as mixed calls do: no launch of a group plan carries them)
-    const bool fuse = n > 0 && !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0 && w->K >= 3 && !w->gkinds.masked();
+    // (a masked world — mgx_set_group_enabled — sends its prior updates as mixed calls do: no launch of a group plan carries them;
+    // with mgx_set_group_resident they ride, and every fall-back to a group plan sends them first: run_segments)
+    const bool fuse = n > 0 && !plan.empty() && plan[0].ext == 0 && plan[0].n_int > 0 && w->thaw_kinds == 0 && w->K >= 3 &&
+                      (!w->gkinds.masked() || w->gkinds.resident);
     if (!fuse) {
         const int rc = n ? mgx_update_priors(w, n, robots, waypoints_xy, time_scale, what, max_speed, delta_t) : MGX_OK;
         return rc != MGX_OK ? rc : iterate_now(w, steps, n_steps);
@@ -648,7 +650,7 @@ int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *fo
         // (of the form that ran last, or that the next launch would take; not asked by a launch yet: asked here, for the topology on
         // the device — no commit, which would end a lingering launch)
         const uint32_t form = w->last_sweep.ir_mode >= 0 && w->last_sweep_form != MGX_SWEEP_FORM_SEGMENTS ? w->last_sweep.features : resident_features(w, false);
-        int cap = w->res.cap[sharded ? 1 : 0][form & 3u];
+        int cap = w->res.cap[sharded ? 1 : 0][form & 7u];
         if (cap < 0) cap = device_ok() ? sweep_resident_capacity(w->d, sharded, form) : 0;
         *resident_capacity = cap;
     }

@@ -532,10 +532,10 @@ struct ResidentLaunches {
     Backoff backoff;
     // workgroups of the resident kernel the device holds at once, per flavour (unsharded, sharded) and form (SWEEP_F_* mask): asked
     // of the instantiation that will run; -1: not asked yet
-    int cap[2][4] = {{-1, -1, -1, -1}, {-1, -1, -1, -1}};
+    int cap[2][8] = {{-1, -1, -1, -1, -1, -1, -1, -1}, {-1, -1, -1, -1, -1, -1, -1, -1}};
     void forget_capacity() { for (auto &f : cap) for (int &c : f) c = -1; }
     int capacity_for(const DevWorld &d, bool sharded, uint32_t form) {  // (asked of the runtime once per topology)
-        int &c = cap[sharded ? 1 : 0][form & 3u];
+        int &c = cap[sharded ? 1 : 0][form & 7u];
         if (c < 0) c = sweep_resident_capacity(d, sharded, form);
         return c;
     }
@@ -723,6 +723,10 @@ struct mgx_world {
         DevBuf<uint32_t> table_d;       // [groups of the last upload] the kinds by group id
         std::vector<uint32_t> table;    // what table_d holds
         uint64_t masked_plans = 0, masked_launches = 0;  // mgx_group_enabled_stats
+        // mgx_set_group_resident: the world's equal schedules take the resident kernel's masked form (SWEEP_F_GRP) — launches of
+        // that form, schedules posted into one, schedules that ran as group plans all the same (mgx_group_resident_stats)
+        bool resident = false;
+        uint64_t res_launches = 0, res_posts = 0, res_fallbacks = 0;
         bool masked() const { return n_masked != 0; }
     } gkinds;
     // the enabled kinds of group g / of robot r (an id): the group's own internal kinds, the world's inter-robot bit

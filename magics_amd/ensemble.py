@@ -202,7 +202,7 @@ class Member:
 
 
 class Ensemble:
-    def __init__(self, scenarios, world, **simulation_options):
+    def __init__(self, scenarios, world, masked_resident=False, **simulation_options):
         """scenarios: one scenario dict per member (config.load_scenario, tests/golden/scenarios.json); member m's robots are in
         group m of `world`, a fresh World made with config.world_params of any of them.  The members may differ in
         simulation.prng-seed, robot.communication.failure-rate, robot.communication.radius, gbp.iteration-schedule,
@@ -213,7 +213,10 @@ class Ensemble:
         request the device's other observers: environment_collisions=True, goal_areas, device_metrics (with sample_log=False if
         asked).  Still refused, with NotImplementedError: global_planner (and so rrt-star formations) — a per-group many-tick run
         and per-group planning are not part of the engine — and every option that needs each tick's Transforms on the host:
-        environment_collisions="host", device_goal_areas=False, device_missions / device_collisions / device_trackers = False."""
+        environment_collisions="host", device_goal_areas=False, device_missions / device_collisions / device_trackers = False.
+        masked_resident is the Ensemble's own (no Simulation sees it): True lets a world whose members differ in
+        gbp.factors-enabled run the ticks they share a schedule in as resident launches (World.set_group_resident) — same
+        results, bit for bit; it changes nothing where the members' kinds agree."""
         scenarios = list(scenarios)
         if not scenarios:
             raise ValueError("an Ensemble needs at least one scenario")
@@ -267,6 +270,10 @@ class Ensemble:
         self.tick_no = 0
         # every member's enabled kinds, before its first robot is added (a mask equal to the world's is none: an ensemble whose
         # members agree stays the unmasked world it was)
+        if masked_resident:   # (the world's switch, before the first robot)
+            if not hasattr(world, "set_group_resident"):
+                raise NotImplementedError("Ensemble: masked_resident needs an engine world that offers set_group_resident")
+            world.set_group_resident(True)
         masks = [_config.enable_mask(sc["config"]) for sc in scenarios]
         if per_group_kinds and any(k != masks[0] for k in masks):
             for m, k in enumerate(masks):

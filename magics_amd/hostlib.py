@@ -157,6 +157,8 @@ SYMBOLS = {
     "mgx_set_group_enabled": (C.c_int, [_V, C.c_uint32, C.c_uint32]),
     "mgx_get_group_enabled": (C.c_int, [_V, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_group_enabled_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mgx_set_group_resident": (C.c_int, [_V, C.c_int32]),
+    "mgx_group_resident_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mgx_batch_begin": (C.c_int, [_V]),
     "mgx_batch_end": (C.c_int, [_V, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mgx_sweep": (C.c_int, [_V, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),

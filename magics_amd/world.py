@@ -883,6 +883,19 @@ class World:
         self._chk(self._L.mgx_group_enabled_stats(self._w, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_group_resident(self, enabled):
+        """True: a masked world's equal schedules (iterate, tick, mission ticks, batches) run as resident launches of the masked
+        form of the kernel, lingering and posts included (mgx_set_group_resident); False, the default: as group plans.  Same
+        results bit for bit; nothing changes on an unmasked world."""
+        self._chk(self._L.mgx_set_group_resident(self._w, 1 if enabled else 0))
+
+    def group_resident_stats(self):
+        """(resident launches of the masked form, schedules posted into one, schedules of the switched-on masked world that ran
+        as group plans all the same): mgx_group_resident_stats"""
+        a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._chk(self._L.mgx_group_resident_stats(self._w, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def is_thawing(self):
         """factors switched back on are still resuming from their frozen inboxes (mgx_is_thawing)"""
         t = C.c_int32()
@@ -906,7 +919,8 @@ class World:
 
     def last_sweep_features(self):
         """the form of the sweep kernel last_sweep reports (mgx_last_sweep_features): bit 0 tracking factors, bit 1 mgx_tick's
-        prior updates; 0: the lean resident form (or no sweep ran), 3: the full form (every launch-per-segment kernel)"""
+        prior updates, bit 2 the kinds per robot group; 0: the lean resident form (or no sweep ran), 3: the full form (every
+        launch-per-segment kernel), 7: the masked form (set_group_resident)"""
         f = C.c_uint32()
         self._chk(self._L.mgx_last_sweep_features(self._w, C.byref(f)))
         return int(f.value)

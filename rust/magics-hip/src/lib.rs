@@ -167,6 +167,16 @@ impl World {
         check(unsafe { sys::mgx_group_enabled_stats(self.raw, &mut plans, &mut launches) })?;
         Ok((plans, launches))
     }
+    /// A masked world's equal schedules as resident launches of the masked form (`mgx_set_group_resident`; off by default).
+    pub fn set_group_resident(&self, enabled: bool) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_set_group_resident(self.raw, enabled as i32) })
+    }
+    /// (resident launches of the masked form, schedules posted into one, schedules that ran as group plans all the same)
+    pub fn group_resident_stats(&self) -> Result<(u64, u64, u64), MgxError> {
+        let (mut launches, mut posts, mut fallbacks) = (0u64, 0u64, 0u64);
+        check(unsafe { sys::mgx_group_resident_stats(self.raw, &mut launches, &mut posts, &mut fallbacks) })?;
+        Ok((launches, posts, fallbacks))
+    }
     /// Several `iterate` calls, one submission (`mgx_batch_begin` / `mgx_batch_end`): the schedules issued inside `f` are recorded and
     /// submitted together, merged into as few resident launches as their segments fit; same results, bit for bit.
     /// Returns (schedules recorded, sweep-kernel launches they were submitted as).

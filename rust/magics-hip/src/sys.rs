@@ -287,6 +287,8 @@ extern "C" {
     pub fn mgx_set_group_enabled(w: *mut mgx_world, group: u32, kind_mask: u32) -> c_int;
     pub fn mgx_get_group_enabled(w: *mut mgx_world, group: u32, kind_mask: *mut u32) -> c_int;
     pub fn mgx_group_enabled_stats(w: *mut mgx_world, masked_plans: *mut u64, masked_launches: *mut u64) -> c_int;
+    pub fn mgx_set_group_resident(w: *mut mgx_world, enabled: i32) -> c_int;
+    pub fn mgx_group_resident_stats(w: *mut mgx_world, launches: *mut u64, posts: *mut u64, fallbacks: *mut u64) -> c_int;
     pub fn mgx_batch_begin(w: *mut mgx_world) -> c_int;
     pub fn mgx_batch_end(w: *mut mgx_world, n_schedules: *mut u32, n_launches: *mut u32) -> c_int;
     pub fn mgx_last_launch_count(w: *mut mgx_world, n_launches: *mut u32) -> c_int;

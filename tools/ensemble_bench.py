@@ -19,8 +19,15 @@ The solo part needs nothing of the ensemble: `--solo` runs it alone, also from t
 --only WORD keeps the workloads whose name contains WORD.  --observers runs the ensemble with environment_collisions=True,
 device_metrics=True, sample_log=False (the figures the Environment Obstacles analysis reads), for a run against the same without.
 
-usage: python tools/ensemble_bench.py [--solo | --ensemble] [--only WORD] [--observers] [--reps N] [--max-time S] [--out FILE.json]"""
+--ensemble-masked-resident adds the form `ensemble_masked_resident`: the ensemble with masked_resident=True, whose masked world runs
+the ticks its members share a schedule in as resident launches (mgx_set_group_resident); its row reports the launches of the masked
+form, the schedules posted into them and the fall-backs.  --by-turns runs the timed repetitions of all forms by turns (one of each,
+then the next of each) instead of form after form.
+
+usage: python tools/ensemble_bench.py [--solo | --ensemble] [--ensemble-masked-resident] [--by-turns] [--only WORD] [--observers] [--reps N]
+       [--max-time S] [--out FILE.json]"""
 import copy
+import gc
 import json
 import os
 import statistics
@@ -45,6 +52,7 @@ def option(flag, kind, default):
 reps, max_time, out_file = option("--reps", int, 5), option("--max-time", float, 30.0), option("--out", str, None)
 only, observers = option("--only", str, ""), "--observers" in args
 only_solo, only_ensemble = "--solo" in args, "--ensemble" in args
+masked_resident, by_turns = "--ensemble-masked-resident" in args, "--by-turns" in args
 OBSERVERS = {"environment_collisions": True, "device_metrics": True, "sample_log": False} if observers else {}
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
@@ -97,10 +105,11 @@ def run_solo(scs, chunk):
     return time.perf_counter() - t0, ticks, {}
 
 
-def run_ensemble(scs):
+def run_ensemble(scs, knob=False):
     from magics_amd import ensemble
     t0 = time.perf_counter()
-    e = ensemble.Ensemble([copy.deepcopy(sc) for sc in scs], World(config.world_params(scs[0]["config"])), **OBSERVERS)
+    e = ensemble.Ensemble([copy.deepcopy(sc) for sc in scs], World(config.world_params(scs[0]["config"])), **({"masked_resident": True} if knob else {}),
+                          **OBSERVERS)
     e.run(max_time=max_time)
     e.world.synchronize()
     wall = time.perf_counter() - t0
@@ -111,6 +120,9 @@ def run_ensemble(scs):
         plans, launches = e.world.group_enabled_stats()
         if plans:   # (a masked world: every tick's schedule a group plan, launch by launch)
             mixed = {"masked_plans": plans, "masked_launches": launches, "launches_per_masked_plan": round(launches / plans, 2)}
+    if knob:
+        launches, posts, fallbacks = e.world.group_resident_stats()
+        mixed = {**mixed, "masked_resident_launches": launches, "masked_resident_posts": posts, "masked_resident_fallbacks": fallbacks}
     if hasattr(e.world, "group_schedule_stats"):
         calls, launches, sat_out = e.world.group_schedule_stats()
         if calls:   # (workgroup launches: one per robot on the device and launch — the world's robots at the end stand for all of them)
@@ -132,15 +144,25 @@ for name, make in WORKLOADS.items():
     forms = []
     if not only_solo:
         forms.append(("ensemble", lambda: run_ensemble(scs)))
+        if masked_resident:
+            forms.append(("ensemble_masked_resident", lambda: run_ensemble(scs, True)))
     if not only_ensemble:
         forms += [("solo_chunk1", lambda: run_solo(scs, 1)), ("solo_chunk256", lambda: run_solo(scs, 256))]
-    for form, run in forms:
+    taken = {form: ([], [], {}, 0) for form, _ in forms}
+    for form, run in ([] if not by_turns else forms):
         run()   # warm-up: code objects, the environment's rasteriser, the allocator
-        walls, rates, extra, ticks = [], [], {}, 0
-        for _ in range(reps):
+    for form, run in (forms if not by_turns else forms * reps):
+        if not by_turns:
+            run()   # warm-up, as above
+        walls, rates, _, _ = taken[form]
+        for _ in range(1 if by_turns else reps):
+            gc.collect()   # (untimed: the run before leaves cycles behind, and the run that follows would pay for collecting them)
             wall, ticks, extra = run()
             walls.append(wall)
             rates.append(ticks / wall)
+            taken[form] = (walls, rates, extra, ticks)
+    for form, _ in forms:
+        walls, rates, extra, ticks = taken[form]
         row[form] = {"wall_s": spread(walls), "member_ticks_per_s": spread(rates), "member_ticks": ticks, **extra}
         print(json.dumps({name: {form: row[form]}}), flush=True)
     result["workloads"][name] = row

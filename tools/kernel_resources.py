@@ -1,5 +1,5 @@
 """Diagnostics: registers, spills, scratch and static LDS of every k_robot_sweep instantiation, every form of the resident ones
-included (feat: 0 lean, 2 with prior updates, 3 full) (hipcc -Rpass-analysis=kernel-resource-usage).
+included (feat: 0 lean, 2 with prior updates, 3 full, 7 masked: full with the kinds per robot group) (hipcc -Rpass-analysis=kernel-resource-usage).
 usage: python tools/kernel_resources.py [extra hipcc flags ...]"""
 import os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
@@ -15,7 +15,7 @@ def remarks(fk):
 
 
 with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 2)) as ex:
-    out = "\n".join(ex.map(remarks, [(f, k, ft) for f in range(3) for k in range(3) for ft in ((3, 2, 0) if f else (3,))]))
+    out = "\n".join(ex.map(remarks, [(f, k, ft) for f in range(3) for k in range(3) for ft in (((7, 3, 2, 0) if f == 1 else (3, 2, 0)) if f else (3,))]))
 cur, rows = None, {}
 for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)

@@ -15,7 +15,7 @@ sample is logged on the device and the robots' positions / velocities lists stay
 scenario's line then carries the arrivals per area and the throughput the reference's analyse-junction-scenario.py reads out of an
 export (robots that started within 50 s and arrived, per second).  --export DIR writes each scenario's export to DIR/<name>.json.
 --ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:INTERNAL:EXTERNAL,..]
-[--ensemble-tracking on,off]
+[--ensemble-tracking on,off] [--ensemble-masked-resident]
 runs the cross product of ONE scenario — every seed with every failure rate, every comms radius, every GBP iteration schedule
 (KIND: centered, soon-as-possible, late-as-possible, interleave-evenly, half-beginning-half-end) and gbp.factors-enabled.tracking
 on / off (default each: the scenario's own) — as one Ensemble (magics_amd/ensemble.py):
@@ -23,9 +23,11 @@ the members are robot groups of one world, one launch per schedule and one synch
 identical to the same run alone.  One line per member — with --environment-collisions, --goal-areas and --metrics (with or
 without --no-sample-log) it carries the member's contacts, arrivals and the means of its run metrics; with --export DIR one
 export per member, DIR/<name>.seed<A>.rate<X>.radius<R>[.<kind>-<internal>-<external>][.tracking-<on|off>].json.  The global planner and host trackers do not run in an Ensemble.
+--ensemble-masked-resident: members that differ in tracking on / off make the world masked; with this switch its ticks run as resident
+launches all the same (Ensemble(masked_resident=True), mgx_set_group_resident) — same results.
 usage: python tools/run_scenarios.py [--max-time S] [--goal-areas junction|FILE.json] [--export DIR] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
            [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N]
-           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..] [--ensemble-tracking on,off]]
+           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..] [--ensemble-tracking on,off] [--ensemble-masked-resident]]
            [scenario-dir | name ...]"""
 import copy
 import json
@@ -116,8 +118,11 @@ if "--ensemble-tracking" in args:
         sys.exit("--ensemble-tracking: a list of on / off")
     ensemble_tracking = [x == "on" for x in words]
     del args[i:i + 2]
-if (ensemble_rates or ensemble_radii or ensemble_schedules or ensemble_tracking) and not ensemble_seeds:
-    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii, --ensemble-schedules and --ensemble-tracking need --ensemble-seeds")
+ensemble_masked_resident = "--ensemble-masked-resident" in args
+if ensemble_masked_resident:
+    args.remove("--ensemble-masked-resident")
+if (ensemble_rates or ensemble_radii or ensemble_schedules or ensemble_tracking or ensemble_masked_resident) and not ensemble_seeds:
+    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii, --ensemble-schedules, --ensemble-tracking and --ensemble-masked-resident need --ensemble-seeds")
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 if ensemble_seeds:
@@ -144,7 +149,7 @@ if ensemble_seeds:
                         members.append((seed, rate, radius, sc))
     t0 = time.perf_counter()
     e = ensemble.Ensemble([sc for *_, sc in members], World(config.world_params(base["config"])), environment_collisions=env_collisions,
-                          device_metrics=metrics, sample_log=not no_sample_log, goal_areas=goal_areas)
+                          device_metrics=metrics, sample_log=not no_sample_log, goal_areas=goal_areas, masked_resident=ensemble_masked_resident)
     e.run(max_time=max_time)
     wall = time.perf_counter() - t0
     stem = os.path.basename(os.path.normpath(base.get("name", args[0])))
