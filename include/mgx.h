@@ -180,7 +180,24 @@ typedef struct mgx_robot_desc {
  *     and thaw are world-wide), a world with ghosts or an engine-side exchange.  On a masked world mgx_set_enabled with a mask
  *     other than the world's and mgx_mission_run (one generator, one schedule: one group's) are MGX_ERR_STATE.
  *     The arguments are checked first and need no device: unknown kind bits, then group >= MGX_GROUPS_MAX (both
- *     MGX_ERR_INVALID), a NULL world or out-pointer last.
+ *     MGX_ERR_INVALID), a NULL world or out-pointer last;
+ *   * the four factor sigmas (gbp.sigma-factor-{dynamics, interrobot, obstacle, tracking}) are per group with
+ *     mgx_set_group_sigmas, under the rules of mgx_set_group_enabled: before the group's first robot (MGX_ERR_STATE afterwards), a
+ *     group never given sigmas has the world's (mgx_params.sigma_*), and a set equal to the world's is none at all.  Every robot
+ *     of group g then runs under g's sigmas — its dynamic factors' potentials are formed with g's sigma_dynamics when it is added
+ *     (spawned in place included), its obstacle, tracking and inter-robot factors (which only ever join robots of one group) are
+ *     evaluated with g's 1 / sigma^2, the double a world created with those mgx_params holds — bit for bit what the same robots
+ *     do in a world of their own created with those sigmas.  A group may have both a mask and sigmas.
+ *     A world in which some group's sigmas differ from the world's is run exactly as a MASKED world is (above): group plans
+ *     launch by launch, each workgroup reading its group's three 1 / sigma^2 from a second table beside the kinds'; a
+ *     per-robot fine-grained call hands its launch that robot's group's; with mgx_set_group_resident(w, 1) resident launches
+ *     and posts of the masked form, which reads the table once per workgroup.  mgx_group_enabled_stats and
+ *     mgx_group_resident_stats count its plans and launches as a masked world's; mgx_set_enabled with another mask and
+ *     mgx_mission_run are MGX_ERR_STATE there (the freeze and thaw kernels evaluate factors with the world's sigmas).
+ *     MGX_ERR_INVALID: a NULL struct, then a value that is not finite and > 0, then group >= MGX_GROUPS_MAX — checked before the
+ *     world is looked at, a NULL world last.  MGX_ERR_STATE, nothing changes: a world that has switched a factor kind at run
+ *     time, a world with ghosts or an engine-side exchange.  Not per group: sigmas changed once the group has robots,
+ *     tracking.switch-padding and attraction-distance, the safety multiplier.
  * Everything else is per robot and does not look at the group: prior updates, missions, trackers, run metrics, environment
  * collisions, goal areas, the planner, the message counters.
  * Ghosts have no group: mgx_robot_add of a ghost with a non-zero group is MGX_ERR_INVALID; a ghost added to a grouped world, a
@@ -321,6 +338,12 @@ int mgx_group_enabled_stats(mgx_world *w, uint64_t *masked_plans, uint64_t *mask
  * synchronisation; any pointer may be NULL. */
 int mgx_set_group_resident(mgx_world *w, int32_t enabled);
 int mgx_group_resident_stats(mgx_world *w, uint64_t *launches, uint64_t *posts, uint64_t *fallbacks);
+/* The four factor sigmas of ONE robot group (ROBOT GROUPS above), as mgx_params holds the world's: every value finite and > 0, set
+ * before the group's first robot is added.  _get answers what a robot added to the group now would run under: the group's own,
+ * else the world's. */
+typedef struct { double dynamics, interrobot, obstacle, tracking; } mgx_group_sigmas;
+int mgx_set_group_sigmas(mgx_world *w, uint32_t group, const mgx_group_sigmas *s);
+int mgx_get_group_sigmas(mgx_world *w, uint32_t group, mgx_group_sigmas *out);
 /* Batches: several schedules, one submission.  A resident schedule launch pays for itself once — the robots' graphs go
  * HBM -> LDS when it starts and back when it ends, a sixth of a ten-iteration launch at 1000 x 16 — so a caller that issues
  * schedule after schedule with nothing in between (the reference's `iterate_gbp_v2` loop run ahead of the renderer, a planner
@@ -363,7 +386,8 @@ int mgx_last_sweep(mgx_world *w, int32_t *variant, int32_t *ir_mode, int32_t *fo
  * keeps its form: an mgx_tick that meets a launch without MGX_SWEEP_F_UPDATES ends it and runs as a launch of the covering
  * form, and the world's launches keep that form from then on.  Results are the same bit for bit in every form.
  * A masked world with mgx_set_group_resident on has ONE form, whatever mgx_set_specialize says: the full one with the enabled
- * internal kinds read per robot group (MGX_SWEEP_F_GROUP_KINDS | MGX_SWEEP_F_TRACKING | MGX_SWEEP_F_UPDATES = 7).
+ * internal kinds — and, where some group has its own, the factor sigmas (mgx_set_group_sigmas) — read per robot group
+ * (MGX_SWEEP_F_GROUP_KINDS | MGX_SWEEP_F_TRACKING | MGX_SWEEP_F_UPDATES = 7).
  * mgx_last_sweep_features: the form of the sweep mgx_last_sweep reports (launch-per-segment kernels: always both bits; 0 as well
  * when no sweep ran).  mgx_set_specialize: 0 = every resident launch of this world in the full form (MGX_SPECIALIZE=0 in the
  * environment does it for the process), 1 = the smallest form, < 0: as the environment says.  For measuring one against the other. */

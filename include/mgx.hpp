@@ -274,6 +274,13 @@ public:
         check(mgx_group_resident_stats(w_, &s[0], &s[1], &s[2]));
         return s;
     }
+    /// gbp.sigma-factor-* of ONE robot group (mgx_set_group_sigmas): before the group's first robot is added; equal to the world's is none
+    void set_group_sigmas(uint32_t group, const mgx_group_sigmas &s) { check(mgx_set_group_sigmas(w_, group, &s)); }
+    mgx_group_sigmas group_sigmas(uint32_t group) {
+        mgx_group_sigmas s{};
+        check(mgx_get_group_sigmas(w_, group, &s));
+        return s;
+    }
     /// several iterate_gbp_v2 calls, one submission (mgx_batch_begin / mgx_batch_end): `{ auto b = world.batch(); for (...) world.iterate_gbp_v2(s); }`
     struct Batch {
         mgx_world *w;

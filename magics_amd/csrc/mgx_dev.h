@@ -276,7 +276,13 @@ struct DevWorld {
     // MASKED (some group's kinds differ from the world's); a masked world's launches all carry segment records — but for its
     // resident launches (SWEEP_F_GRP), which read group_of and this table and have no segment records (group_seg is null).
     const uint32_t *group_enable;  // [groups], as group_seg
+    // Factor sigmas per robot group (mgx_set_group_sigmas): {inv_s2_obs, inv_s2_ir, inv_s2_trk} of every group, the very doubles
+    // a world created with the group's sigmas holds above, read where group_enable is read and taken in place of those three
+    // (sigma_dynamics is in the robots' own dyn_m).  Null unless some group's sigmas differ from the world's; such a world is
+    // masked, so its launches carry group_enable as well.
+    const double *group_sigma;  // [groups][GROUP_SIGMA_W]
 };
+constexpr int GROUP_SIGMA_W = 3;  // DevWorld::group_sigma: obstacle, inter-robot, tracking
 
 // An inter-robot factor created WHILE its kind was switched off dropped the two messages that would have filled its inbox
 // (factor/mod.rs:307-310): once enabled it has no inbox KEYS until its variables deliver again, and FactorNode::update answers

@@ -290,6 +290,8 @@ __global__ void k_thaw(DevWorld w, int robot0, int n_robots, uint32_t ext_mask) 
             double h[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) h[q] = (idx[q] >= 0) ? sdf_value(w.sdf[idx[q]]) : 0.0;
+            // (launch-wide sigma: unreachable where groups have sigmas of their own — k_thaw runs only while kinds thaw, which takes
+            // mgx_set_enabled with another mask, refused there; and mgx_set_group_sigmas is refused on a world that has switched a kind)
             obstacle_message(h, w.obs_delta, w.obs_inv_delta, w.inv_s2_obs, x0, oe, ol);
         } else {
             const bool radio = (w.antenna[r] != 0) && !idle;
@@ -300,6 +302,7 @@ __global__ void k_thaw(DevWorld w, int robot0, int n_robots, uint32_t ext_mask) 
             float lp[2] = {w.trk_last_pos[item], w.trk_last_pos[(size_t)w.NT + item]};
             double lv = w.trk_last_val[item];
             const int p0 = w.path_ptr[r], np = w.path_ptr[r + 1] - p0;
+            // (launch-wide sigma: unreachable on a world with sigmas per group, as the obstacle branch above)
             ok = tracking_update(w.path_xy + 2 * (size_t)p0, np, w.trk_pad, w.trk_attr, w.inv_s2_trk, x0, rec, lp, lv, oe, ol);
             w.trk_record[item] = rec;
             w.trk_last_pos[item] = lp[0];
@@ -372,6 +375,8 @@ __global__ void k_thaw_ir(DevWorld w, uint8_t *gate) {
             x_lo[c] = dslot ? a_mu[c] : b_mu[c];
             x_hi[c] = dslot ? b_mu[c] : a_mu[c];
         }
+        // (launch-wide sigma: unreachable on a world with sigmas per group — k_thaw_ir runs only after the inter-robot kind was switched
+        // off and on again, and both mgx_set_enabled there and mgx_set_group_sigmas after a switch are refused)
         const bool ok = interrobot_message_compact(x_lo, x_hi, er.d_safe, reciprocal_for_division(er.d_safe), er.offset, w.inv_s2_ir, dslot, ao_eta, ao_lam, o6);
         w.ir_fv_eta[0 * (size_t)w.NI + e] = ok ? o6[0] : 0.0;
         w.ir_fv_eta[1 * (size_t)w.NI + e] = ok ? o6[1] : 0.0;
@@ -405,6 +410,9 @@ __global__ void k_keyless_ir(DevWorld w, uint8_t *gate, int n, const KeylessRec 
 #pragma unroll
         for (int c = 0; c < 16; c++) zero16[c] = 0.0;
         ld_soa4(w.ir_bmu, w.NI, e, b_mu);
+        // (launch-wide sigma: unreachable on a world with sigmas per group — keyless factors are created only while the inter-robot
+        // kind is off and evaluated only once it is on again, a switch that mgx_set_enabled refuses there; and a world that has
+        // keyless factors already is refused by mgx_set_group_sigmas)
         const bool ok = interrobot_message(b_mu, zero4, er.d_safe, er.offset, w.inv_s2_ir, 0, zero4, zero16, oe, ol);
         w.ir_fv_eta[0 * (size_t)w.NI + e] = ok ? oe[0] : 0.0;
         w.ir_fv_eta[1 * (size_t)w.NI + e] = ok ? oe[1] : 0.0;

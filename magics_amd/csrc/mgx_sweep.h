@@ -593,15 +593,40 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
         if constexpr (PERSIST && !GRP) return TRK ? w.enable : (w.enable & 7u);
         else return group_kinds;
     };
+    // The factor sigmas are the group's in the same places (mgx_set_group_sigmas: DevWorld::group_sigma, null unless some group
+    // has sigmas of its own): three doubles at a wave-uniform address — the group index is in a scalar register — in place of
+    // the launch-wide inv_s2_*; every other resident form reads the kernel arguments, as ever.
+    double group_s2_obs = w.inv_s2_obs, group_s2_ir = w.inv_s2_ir, group_s2_trk = w.inv_s2_trk;
+    auto group_sigmas = [&](int g) __attribute__((always_inline)) {
+        if (!w.group_sigma) return;
+        const double *s = w.group_sigma + (size_t)GROUP_SIGMA_W * (size_t)g;
+        group_s2_obs = s[0];
+        group_s2_ir = s[1];
+        group_s2_trk = s[2];
+    };
+    auto inv_s2_obs = [&]() __attribute__((always_inline)) -> double {
+        if constexpr (PERSIST && !GRP) return w.inv_s2_obs;
+        else return group_s2_obs;
+    };
+    auto inv_s2_ir = [&]() __attribute__((always_inline)) -> double {
+        if constexpr (PERSIST && !GRP) return w.inv_s2_ir;
+        else return group_s2_ir;
+    };
+    auto inv_s2_trk = [&]() __attribute__((always_inline)) -> double {
+        if constexpr (PERSIST && !GRP) return w.inv_s2_trk;
+        else return group_s2_trk;
+    };
     if constexpr (GRP) {
         const int g = __builtin_amdgcn_readfirstlane((int)w.group_of[r]);
         group_kinds = (uint32_t)__builtin_amdgcn_readfirstlane((int)w.group_enable[g]);
+        group_sigmas(g);
     }
     if constexpr (!PERSIST) {
         if (w.group_seg) {
             const int g = __builtin_amdgcn_readfirstlane((int)w.group_of[r]);
             const GroupSeg *gs = w.group_seg + g;
             if (w.group_enable) group_kinds = (uint32_t)__builtin_amdgcn_readfirstlane((int)w.group_enable[g]);
+            group_sigmas(g);
             ext_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs->ext_mask);
             int_mask = (uint32_t)__builtin_amdgcn_readfirstlane((int)gs->int_mask);
             n_int = __builtin_amdgcn_readfirstlane(gs->n_int);
@@ -1167,7 +1192,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
                     x_lo[c] = dslot ? a_mu[c] : b_mu[c];
                     x_hi[c] = dslot ? b_mu[c] : a_mu[c];
                 }
-                const bool live_msg = interrobot_message_compact(x_lo, x_hi, er_d_safe, er_inv_d_safe, er_offset, w.inv_s2_ir, dslot, ao_eta, ao_lam, o6);
+                const bool live_msg = interrobot_message_compact(x_lo, x_hi, er_d_safe, er_inv_d_safe, er_offset, inv_s2_ir(), dslot, ao_eta, ao_lam, o6);
                 if (!live_msg) {
 #pragma unroll
                     for (int c = 0; c < 6; c++) o6[c] = 0.0;
@@ -1520,7 +1545,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
 #pragma unroll
                 for (int t = 0; t < 4; t++) h[t] = __shfl(hq, (lane & ~3) + t, 64);
                 double eta_q, lam_q[4];
-                obstacle_message_row(h, w.obs_delta, obs_inv_delta_here(), w.inv_s2_obs, x0, q, eta_q, lam_q);
+                obstacle_message_row(h, w.obs_delta, obs_inv_delta_here(), inv_s2_obs(), x0, q, eta_q, lam_q);
                 s_out[q * E1 + col] = eta_q;
 #pragma unroll
                 for (int c = 0; c < 4; c++) s_out[(4 + q * 4 + c) * E1 + col] = lam_q[c];
@@ -1535,7 +1560,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
             double h[4];
 #pragma unroll
             for (int q = 0; q < 4; q++) h[q] = (idx[q] >= 0) ? sdf_value(w.sdf[idx[q]]) : 0.0;
-            obstacle_message(h, w.obs_delta, obs_inv_delta_here(), w.inv_s2_obs, x0, oe, ol);
+            obstacle_message(h, w.obs_delta, obs_inv_delta_here(), inv_s2_obs(), x0, oe, ol);
 #pragma unroll
             for (int c = 0; c < 4; c++) s_out[c * E1 + uedge] = oe[c];
 #pragma unroll
@@ -1546,7 +1571,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
 #pragma unroll
             for (int c = 0; c < 4; c++) x0[c] = s_snap[(20 + c) * K + uvar];
             const int p0 = w.path_ptr[r], np = w.path_ptr[r + 1] - p0;
-            if (!tracking_update(w.path_xy + 2 * (size_t)p0, np, trk_pad_here(), w.trk_attr, w.inv_s2_trk, x0, trk_rec,
+            if (!tracking_update(w.path_xy + 2 * (size_t)p0, np, trk_pad_here(), w.trk_attr, inv_s2_trk(), x0, trk_rec,
                                   trk_lp, trk_lv, oe, ol)) {
 #pragma unroll
                 for (int c = 0; c < 4; c++) oe[c] = 0.0;
@@ -1570,7 +1595,7 @@ __global__ void __launch_bounds__((sweep_threads<KT, PERSIST>()), 2) k_robot_swe
             float lp2[2] = {w.trk_last_pos[item2], w.trk_last_pos[(size_t)w.NT + item2]};
             double lv2 = w.trk_last_val[item2];
             const int p0 = w.path_ptr[r], np = w.path_ptr[r + 1] - p0;
-            if (!tracking_update(w.path_xy + 2 * (size_t)p0, np, trk_pad_here(), w.trk_attr, w.inv_s2_trk, x0, rec2, lp2, lv2, oe, ol)) {
+            if (!tracking_update(w.path_xy + 2 * (size_t)p0, np, trk_pad_here(), w.trk_attr, inv_s2_trk(), x0, rec2, lp2, lv2, oe, ol)) {
 #pragma unroll
                 for (int c = 0; c < 4; c++) oe[c] = 0.0;
 #pragma unroll

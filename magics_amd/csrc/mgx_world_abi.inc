@@ -189,9 +189,10 @@ int mgx_robot_add(mgx_world *w, const mgx_robot_desc *d, int32_t *robot_id) {
         memcpy(&rb.snap[24 * i + 4], lam, sizeof lam);
         memcpy(&rb.snap[24 * i + 20], m, 4 * sizeof(double));
     }
+    const double sigma_dynamics = w->sigmas_of_group(d->group).dynamics;  // (the group's own where it was given sigmas: mgx_set_group_sigmas)
     for (int f = 0; f < K - 1; f++) {
         if (!(d->dt[f] > 0)) return fail(MGX_ERR_INVALID, "dt must be positive");
-        dynamic_potential(d->dt[f], w->p.sigma_dynamics, &rb.dyn_m[16 * f]);
+        dynamic_potential(d->dt[f], sigma_dynamics, &rb.dyn_m[16 * f]);
     }
     for (int j = 0; j < K - 2; j++) {  // new_tracking_factor, factor/mod.rs:269-274
         rb.trk_last_pos[2 * j] = (float)d->mean0[4 * (j + 1)];
@@ -400,7 +401,8 @@ int mgx_set_enabled(mgx_world *w, uint32_t kind_mask) {
     const uint32_t on = kind_mask & ~w->p.enable_mask, off = w->p.enable_mask & ~kind_mask;
     if (kind_mask == w->p.enable_mask) return MGX_OK;
     if (w->gkinds.masked())
-        return fail(MGX_ERR_STATE, "mgx_set_enabled on a world whose groups have enabled kinds of their own (mgx_set_group_enabled): freeze and thaw are world-wide");
+        return fail(MGX_ERR_STATE, "mgx_set_enabled on a world whose groups have enabled kinds or sigmas of their own (mgx_set_group_enabled, mgx_set_group_sigmas): "
+                                   "freeze and thaw are world-wide");
     flush_counts(w);  // what was logged so far was sent under the old flags
     // Internal kinds (dynamic, obstacle, tracking): a factor switched off keeps the inbox it has now and
     // resumes from it when it is switched on again (FactorNode::receive_message_from drops everything in
@@ -505,6 +507,38 @@ int mgx_group_enabled_stats(mgx_world *w, uint64_t *masked_plans, uint64_t *mask
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     if (masked_plans) *masked_plans = w->gkinds.masked_plans;
     if (masked_launches) *masked_launches = w->gkinds.masked_launches;
+    return MGX_OK;
+}
+// The factor sigmas of ONE robot group (include/mgx.h, ROBOT GROUPS), under the rules of mgx_set_group_enabled: fixed before the
+// group's first robot joins, a set equal to the world's is none at all.  sigma_dynamics goes into the dyn_m of the group's robots
+// as they are added (mgx_robot_add); the other three reach the kernels as 1 / sigma^2 by group id (ensure_group_kinds).
+int mgx_set_group_sigmas(mgx_world *w, uint32_t group, const mgx_group_sigmas *s) {
+    // (what the arguments alone say comes first: it needs no world and no device)
+    if (!s) return fail(MGX_ERR_INVALID, "null sigmas");
+    for (const double v : {s->dynamics, s->interrobot, s->obstacle, s->tracking})
+        if (!(std::isfinite(v) && v > 0)) return fail(MGX_ERR_INVALID, "sigmas must be finite and positive");
+    if (group >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "group %u is not below MGX_GROUPS_MAX (%u)", group, MGX_GROUPS_MAX);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    MGX_ENTER(w);
+    mgx_world::GroupKinds &gk = w->gkinds;
+    if (group < gk.populated.size() && gk.populated[group])
+        return fail(MGX_ERR_STATE, "group %u has had robots: a group's sigmas are fixed before its first robot is added", group);
+    if (w->frozen_live || w->ir_frozen_live || w->thaw_kinds || w->ir_thaw_active || w->n_keyless > 0)
+        return fail(MGX_ERR_STATE, "sigmas per group on a world that has switched a factor kind (mgx_set_enabled): freeze and thaw evaluate factors with the world's sigmas");
+    if (w->obs.n_ghosts || w->xres.connected || w->direct.connected || w->rccl.connected)
+        return fail(MGX_ERR_STATE, "sigmas per group on a sharded world: ghosts have no group");
+    if (gk.sig_has.size() <= group) { gk.sig_has.resize((size_t)group + 1, 0); gk.sig.resize((size_t)group + 1, mgx_group_sigmas{0.0, 0.0, 0.0, 0.0}); }
+    const bool own = s->dynamics != w->p.sigma_dynamics || s->interrobot != w->p.sigma_interrobot || s->obstacle != w->p.sigma_obstacle ||
+                     s->tracking != w->p.sigma_tracking;
+    gk.n_sigma += (own ? 1u : 0u) - (gk.sig_has[group] ? 1u : 0u);
+    gk.sig_has[group] = own ? 1 : 0;
+    gk.sig[group] = *s;
+    return MGX_OK;
+}
+int mgx_get_group_sigmas(mgx_world *w, uint32_t group, mgx_group_sigmas *out) {
+    if (group >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "group %u is not below MGX_GROUPS_MAX (%u)", group, MGX_GROUPS_MAX);
+    if (!w || !out) return fail(MGX_ERR_INVALID, "null argument");
+    *out = w->sigmas_of_group(group);
     return MGX_OK;
 }
 // A masked world's equal schedules as resident launches of the masked form (include/mgx.h, ROBOT GROUPS).  A switch of the world,

@@ -240,10 +240,19 @@ static int sweep(mgx_world *w, int32_t robot, uint32_t ext_mask, uint32_t int_ma
         const bool thawing = w->thaw_kinds && (int_mask & PH_INT_FACTOR) && n_int > 0;
         if (thawing) HIP_TRY(launch_thaw(w->d, w->dev_of[(size_t)robot], 1, 0, w->stream));
         // (one robot, one group: its kinds are the launch's own scalar — mgx_set_group_enabled)
+        // (... and so are its sigmas — mgx_set_group_sigmas: the launch's three 1 / sigma^2, formed as commit forms the world's)
         w->d.enable = w->kinds_of_robot((size_t)robot);
+        const double world_s2[3] = {w->d.inv_s2_obs, w->d.inv_s2_ir, w->d.inv_s2_trk};
+        if (w->gkinds.n_sigma) {
+            const mgx_group_sigmas gsg = w->sigmas_of_group(w->sets.group[(size_t)robot]);
+            w->d.inv_s2_obs = 1.0 / (gsg.obstacle * gsg.obstacle);
+            w->d.inv_s2_ir = 1.0 / (gsg.interrobot * gsg.interrobot);
+            w->d.inv_s2_trk = 1.0 / (gsg.tracking * gsg.tracking);
+        }
         const hipError_t le = launch_robot_sweep(w->d, w->dev_of[(size_t)robot], 1, 0, int_mask, n_int, writes_snap ? w->d.cur : -1, 0, w->stream,
                                                  &w->last_sweep);
         w->d.enable = w->p.enable_mask;
+        w->d.inv_s2_obs = world_s2[0]; w->d.inv_s2_ir = world_s2[1]; w->d.inv_s2_trk = world_s2[2];
         HIP_TRY(le);
         w->last_sweep_form = MGX_SWEEP_FORM_SEGMENTS;
         if (w->thaw_kinds && (thawing || writes_snap)) HIP_TRY(launch_thaw_done(w->d, w->dev_of[(size_t)robot], 1, writes_snap ? 1 : 0, w->stream));
@@ -645,6 +654,30 @@ static int ensure_group_of(mgx_world *w) {
     }
     return MGX_OK;
 }
+// The groups' {inv_s2_obs, inv_s2_ir, inv_s2_trk} by group id, `top` groups of them (mgx_set_group_sigmas; DevWorld::group_sigma):
+// each 1.0 / (s * s) as commit forms the world's, so a group's value is the very double a world created with its sigmas holds.
+// Under the rule of the kinds' table beside it: fixed once a group has robots, so it goes up again only when a group joined or
+// was given values — and the callers come here with no launch lingering.  No group with sigmas of its own: no table at all.
+static int ensure_group_sigmas(mgx_world *w, size_t top) {
+    mgx_world::GroupKinds &gk = w->gkinds;
+    if (gk.n_sigma == 0) return MGX_OK;
+    std::vector<double> now(top * (size_t)GROUP_SIGMA_W);
+    for (size_t g = 0; g < top; g++) {
+        const mgx_group_sigmas s = w->sigmas_of_group((uint32_t)g);
+        now[g * GROUP_SIGMA_W + 0] = 1.0 / (s.obstacle * s.obstacle);
+        now[g * GROUP_SIGMA_W + 1] = 1.0 / (s.interrobot * s.interrobot);
+        now[g * GROUP_SIGMA_W + 2] = 1.0 / (s.tracking * s.tracking);
+    }
+    if (now != gk.sig_table || !gk.sig_d.p) {
+        if (now.size() > gk.sig_d.cap) HIP_TRY(hipStreamSynchronize(w->stream));  // (an array that has to grow is freed first: nothing may still read it)
+        gk.sig_table.swap(now);
+        HIP_TRY(gk.sig_d.upload(gk.sig_table, w->stream, (size_t)MGX_GROUPS_MAX * (size_t)GROUP_SIGMA_W));
+        HIP_TRY(hipStreamSynchronize(w->stream));  // (pageable memory: the copy has left it)
+    }
+    return MGX_OK;
+}
+// (what a launch of a world whose groups differ carries in DevWorld::group_sigma: the table, or null where no group has sigmas)
+static const double *group_sigma_table(const mgx_world *w) { return w->gkinds.n_sigma ? w->gkinds.sig_d.p : nullptr; }
 // What a masked world's resident launch reads (SWEEP_F_GRP): the robots' groups and the groups' kinds by group id, under the
 // rule of run_group_plan — the kinds are fixed once a group has robots, so the table goes up again only when a group joined or was
 // given its kinds (a table that a mixed call left longer than the groups in use serves as it is).  Never while a launch lingers:
@@ -665,7 +698,7 @@ static int ensure_group_kinds(mgx_world *w) {
     }
     for (const uint32_t g : w->gsched.group_of)
         if ((size_t)g >= gk.table.size()) return fail(MGX_ERR_STATE, "internal: robot group %u beyond the kinds table", g);
-    return MGX_OK;
+    return ensure_group_sigmas(w, gk.table.size());  // (the groups' sigmas, as many rows)
 }
 
 // ---- run_resident, step by step -------------------------------------------------------------------------------------------
@@ -802,7 +835,9 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
         }
         const RidingUpdates rode = i0 == 0 ? rl.riding : RidingUpdates{};
         w->d.upd = rode.dev; w->d.upd_max_speed = rode.max_speed; w->d.upd_delta_t = rode.delta_t;
-        if (by_groups) { w->d.group_of = w->gsched.group_of_d.p; w->d.group_enable = w->gkinds.table_d.p; }  // (group_seg stays null)
+        if (by_groups) {  // (group_seg stays null)
+            w->d.group_of = w->gsched.group_of_d.p; w->d.group_enable = w->gkinds.table_d.p; w->d.group_sigma = group_sigma_table(w);
+        }
         SweepRan ran;
         const bool cooperative = ResidentKnobs::cooperative();
         if (can && !resident_launch_allowed(w)) return fail(MGX_ERR_STATE, "internal: a resident launch while factors thaw");
@@ -811,6 +846,7 @@ static int run_resident(mgx_world *w, const std::vector<Launch> &plan) {
         w->d.upd = nullptr;
         w->d.group_of = nullptr;
         w->d.group_enable = nullptr;
+        w->d.group_sigma = nullptr;
         if (le != hipSuccess) {
             (void)hipGetLastError();
             if (cooperative && le == hipErrorCooperativeLaunchTooLarge && i0 == 0 && !sharded) {
@@ -913,6 +949,7 @@ static int run_group_plan(mgx_world *w, const GroupPlan &gp, bool by_masks = fal
             HIP_TRY(gk.table_d.upload(gk.table, w->stream, (size_t)MGX_GROUPS_MAX));
             HIP_TRY(hipStreamSynchronize(w->stream));  // (pageable memory: the copy has left it)
         }
+        if ((rc = ensure_group_sigmas(w, top)) != MGX_OK) return rc;  // (... and their sigmas, where some group has its own)
     }
     w->stale_kinds |= ~w->p.enable_mask & 15u;  // disabled factors miss what these sweeps deliver
     for (size_t k = 0; k < gp.n_launches; k++) {
@@ -921,10 +958,12 @@ static int run_group_plan(mgx_world *w, const GroupPlan &gp, bool by_masks = fal
         w->d.group_of = gs.group_of_d.p;
         w->d.group_seg = gs.seg_d.p + k * top;
         w->d.group_enable = gk.masked() ? gk.table_d.p : nullptr;
+        w->d.group_sigma = group_sigma_table(w);
         const hipError_t e = launch_robot_sweep(w->d, 0, w->d.R_local, 0u, 0u, 0, writes_snap ? 1 - w->d.cur : -1, 0u, w->stream, &w->last_sweep);
         w->d.group_of = nullptr;
         w->d.group_seg = nullptr;
         w->d.group_enable = nullptr;
+        w->d.group_sigma = nullptr;
         HIP_TRY(e);
         w->last_sweep_form = MGX_SWEEP_FORM_SEGMENTS;
         w->last_sweep_launches++;

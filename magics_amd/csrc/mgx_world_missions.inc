@@ -374,7 +374,8 @@ int mgx_mission_run(mgx_world *w, mgx_mission_run_desc *d) {
         return fail(MGX_ERR_INVALID, "null argument");
     if (!(d->failure_rate >= 0.0 && d->failure_rate <= 1.0)) return fail(MGX_ERR_INVALID, "failure_rate is outside [0, 1]");
     if (w->gkinds.masked())
-        return fail(MGX_ERR_STATE, "mgx_mission_run on a world whose groups have enabled kinds of their own (mgx_set_group_enabled): one generator and one schedule are one group's");
+        return fail(MGX_ERR_STATE, "mgx_mission_run on a world whose groups have enabled kinds or sigmas of their own (mgx_set_group_enabled, mgx_set_group_sigmas): "
+                                   "one generator and one schedule are one group's");
     mgx_world::Mission &ms = w->mission;
     const size_t R = w->robots.size();
     d->ticks_done = 0;

@@ -727,8 +727,22 @@ struct mgx_world {
         // that form, schedules posted into one, schedules that ran as group plans all the same (mgx_group_resident_stats)
         bool resident = false;
         uint64_t res_launches = 0, res_posts = 0, res_fallbacks = 0;
-        bool masked() const { return n_masked != 0; }
+        // Factor sigmas per robot group (mgx_set_group_sigmas): a group has sigmas of its own only where it was given a set that
+        // differs from the world's.  Fixed before the group's first robot, as the kinds are (`populated`); a world with such a
+        // group counts as masked — ONE predicate for "the groups differ, in kinds or in sigmas" — and its launches read a second
+        // table beside the kinds': {inv_s2_obs, inv_s2_ir, inv_s2_trk} by group id (sigma_dynamics is baked into the robots' dyn_m)
+        std::vector<uint8_t> sig_has;   // [groups given sigmas] 1: `sig` holds the group's own
+        std::vector<mgx_group_sigmas> sig;
+        uint32_t n_sigma = 0;           // groups with sigmas of their own
+        DevBuf<double> sig_d;           // [groups of the last upload][GROUP_SIGMA_W]
+        std::vector<double> sig_table;  // what sig_d holds
+        bool masked() const { return n_masked != 0 || n_sigma != 0; }
     } gkinds;
+    // the factor sigmas of group g: the group's own, else the world's
+    mgx_group_sigmas sigmas_of_group(uint32_t g) const {
+        if (g < gkinds.sig_has.size() && gkinds.sig_has[g]) return gkinds.sig[g];
+        return mgx_group_sigmas{p.sigma_dynamics, p.sigma_interrobot, p.sigma_obstacle, p.sigma_tracking};
+    }
     // the enabled kinds of group g / of robot r (an id): the group's own internal kinds, the world's inter-robot bit
     uint32_t kinds_of_group(uint32_t g) const { return g < gkinds.has.size() && gkinds.has[g] ? ((gkinds.mask[g] & 13u) | (p.enable_mask & 2u)) : p.enable_mask; }
     uint32_t kinds_of_robot(size_t r) const { return gkinds.n_masked ? kinds_of_group(sets.group[r]) : p.enable_mask; }

@@ -12,8 +12,9 @@ device's collision logs and tracker sample log are drained once and their record
 
 Per member (per group of the world): the seed, the comms failure rate, the formations, max-time — and the comms radius, which the
 grouped search holds per group (mission_tick_begin_groups with one radius per member), the GBP iteration schedule
-(mission_tick_end with one schedule per member: mgx_mission_tick_end_groups) and the enabled factor kinds but the inter-robot one
-(set_group_enabled before the member's first robot: mgx_set_group_enabled).  The per-robot observers — environment
+(mission_tick_end with one schedule per member: mgx_mission_tick_end_groups), the enabled factor kinds but the inter-robot one
+(set_group_enabled before the member's first robot: mgx_set_group_enabled) and the four factor sigmas (set_group_sigmas, likewise:
+mgx_set_group_sigmas).  The per-robot observers — environment
 collisions, goal areas, the run metrics — do not look at the group: the first member switches them on for the world, and every
 member reads its own robots' part."""
 import copy
@@ -32,11 +33,22 @@ ENV_EVENTS_PER_MEMBER = 262144   # the room a run of its own has for environment
 ENV_EVENTS_MOST = 1 << 24        # ... and where an ensemble's log stops growing with its members (24 bytes a record)
 
 
-def _shared_settings(sc, per_group_kinds=False):
+SIGMAS = ("dynamics", "interrobot", "obstacle", "tracking")   # gbp.sigma-factor-*: params.sigma_* of the world, mgx_group_sigmas of a group
+
+
+def _member_sigmas(sc):
+    """a member's four factor sigmas as its world's params hold them"""
+    p = _config.world_params(sc["config"])
+    return {k: p["sigma_" + k] for k in SIGMAS}
+
+
+def _shared_settings(sc, per_group_kinds=False, per_group_sigmas=False):
     """everything the world holds once, as (key, value) in the order it is compared.  per_group_kinds: the world takes
-    gbp.factors-enabled per group (mgx_set_group_enabled) — all of it but the inter-robot kind, which stays the world's"""
+    gbp.factors-enabled per group (mgx_set_group_enabled) — all of it but the inter-robot kind, which stays the world's.
+    per_group_sigmas: it takes the four gbp.sigma-factor-* per group as well (mgx_set_group_sigmas)"""
     cfg = sc["config"]
-    out = [("params." + k, v) for k, v in _config.world_params(cfg).items() if not (per_group_kinds and k == "enable_mask")]
+    out = [("params." + k, v) for k, v in _config.world_params(cfg).items()
+           if not (per_group_kinds and k == "enable_mask") and not (per_group_sigmas and k in tuple("sigma_" + n for n in SIGMAS))]
     if per_group_kinds:
         out.append(("gbp.factors-enabled.interrobot", cfg["gbp"]["factors-enabled"]["interrobot"]))
     out += [("gbp.lookahead-multiple", cfg["gbp"]["lookahead-multiple"]),
@@ -206,8 +218,8 @@ class Ensemble:
         """scenarios: one scenario dict per member (config.load_scenario, tests/golden/scenarios.json); member m's robots are in
         group m of `world`, a fresh World made with config.world_params of any of them.  The members may differ in
         simulation.prng-seed, robot.communication.failure-rate, robot.communication.radius, gbp.iteration-schedule,
-        gbp.factors-enabled.{dynamic, obstacle, tracking} (and max-time) and in their formations; everything the world holds once must be equal (ValueError names the first key that differs; a world
-        that takes no radius, no schedule or no enabled kinds per group holds that once, too; gbp.factors-enabled.interrobot is the
+        gbp.factors-enabled.{dynamic, obstacle, tracking}, gbp.sigma-factor-{dynamics, interrobot, obstacle, tracking} (and max-time) and in their formations; everything the world holds once must be equal (ValueError names the first key that differs; a world
+        that takes no radius, no schedule, no enabled kinds or no sigmas per group holds that once, too; gbp.factors-enabled.interrobot is the
         world's always).  simulation_options go to every member's Simulation, so the members share them —
         goal_areas among them.  An Ensemble runs device missions with device robot-robot collisions and device trackers, and on
         request the device's other observers: environment_collisions=True, goal_areas, device_metrics (with sample_log=False if
@@ -215,8 +227,8 @@ class Ensemble:
         and per-group planning are not part of the engine — and every option that needs each tick's Transforms on the host:
         environment_collisions="host", device_goal_areas=False, device_missions / device_collisions / device_trackers = False.
         masked_resident is the Ensemble's own (no Simulation sees it): True lets a world whose members differ in
-        gbp.factors-enabled run the ticks they share a schedule in as resident launches (World.set_group_resident) — same
-        results, bit for bit; it changes nothing where the members' kinds agree."""
+        gbp.factors-enabled or in their sigmas run the ticks they share a schedule in as resident launches (World.set_group_resident) — same
+        results, bit for bit; it changes nothing where the members' kinds and sigmas agree."""
         scenarios = list(scenarios)
         if not scenarios:
             raise ValueError("an Ensemble needs at least one scenario")
@@ -242,9 +254,10 @@ class Ensemble:
         per_group_radius = hasattr(world, "neighbours_groups")   # (the engine's grouped search: one comms radius per group)
         per_group_steps = hasattr(world, "group_schedule_stats")  # (mgx_mission_tick_end_groups: one iteration schedule per group)
         per_group_kinds = hasattr(world, "set_group_enabled")     # (mgx_set_group_enabled: dynamic, obstacle and tracking per group)
+        per_group_sigmas = hasattr(world, "set_group_sigmas")     # (mgx_set_group_sigmas: the four factor sigmas per group)
 
         def shared(sc):
-            return (_shared_settings(sc, per_group_kinds) + ([] if per_group_steps else [("gbp.iteration-schedule", sc["config"]["gbp"]["iteration-schedule"])]) +
+            return (_shared_settings(sc, per_group_kinds, per_group_sigmas) + ([] if per_group_steps else [("gbp.iteration-schedule", sc["config"]["gbp"]["iteration-schedule"])]) +
                     ([] if per_group_radius else [("robot.communication.radius", sc["config"]["robot"]["communication"]["radius"])]))
         first = shared(scenarios[0])
         for m, sc in enumerate(scenarios[1:], 1):
@@ -278,6 +291,11 @@ class Ensemble:
         if per_group_kinds and any(k != masks[0] for k in masks):
             for m, k in enumerate(masks):
                 world.set_group_enabled(m, k)
+        # ... and its sigmas, under the same rule (equal to the world's is none: members that agree leave the world as it was)
+        sigmas = [_member_sigmas(sc) for sc in scenarios]
+        if per_group_sigmas and any(s != sigmas[0] for s in sigmas):
+            for m, s in enumerate(sigmas):
+                world.set_group_sigmas(m, **s)
         self.members_worlds = [_MemberWorld(self, m) for m in range(len(scenarios))]
         self.members = [Member(Simulation(sc, view, **simulation_options), view) for sc, view in zip(scenarios, self.members_worlds)]
         s0 = self.members[0].sim

@@ -55,6 +55,10 @@ class Params(C.Structure):
     ]
 
 
+class GroupSigmas(C.Structure):  # mgx_group_sigmas
+    _fields_ = [("dynamics", C.c_double), ("interrobot", C.c_double), ("obstacle", C.c_double), ("tracking", C.c_double)]
+
+
 class RobotDesc(C.Structure):
     _fields_ = [
         ("K", C.c_uint32),
@@ -157,6 +161,8 @@ SYMBOLS = {
     "mgx_set_group_enabled": (C.c_int, [_V, C.c_uint32, C.c_uint32]),
     "mgx_get_group_enabled": (C.c_int, [_V, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_group_enabled_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "mgx_set_group_sigmas": (C.c_int, [_V, C.c_uint32, C.POINTER(GroupSigmas)]),
+    "mgx_get_group_sigmas": (C.c_int, [_V, C.c_uint32, C.POINTER(GroupSigmas)]),
     "mgx_set_group_resident": (C.c_int, [_V, C.c_int32]),
     "mgx_group_resident_stats": (C.c_int, [_V, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "mgx_batch_begin": (C.c_int, [_V]),

@@ -883,6 +883,24 @@ class World:
         self._chk(self._L.mgx_group_enabled_stats(self._w, C.byref(a), C.byref(b)))
         return a.value, b.value
 
+    def set_group_sigmas(self, group, dynamics=None, interrobot=None, obstacle=None, tracking=None):
+        """gbp.sigma-factor-{dynamics, interrobot, obstacle, tracking} of ONE robot group (mgx_set_group_sigmas), before the group's
+        first robot is added: every value finite and positive; one left out keeps what the group has (the world's unless set
+        before).  A set equal to the world's is none; a world whose groups differ in their sigmas runs as a masked world does."""
+        s = hostlib.GroupSigmas()
+        self._chk(self._L.mgx_get_group_sigmas(self._w, int(group), C.byref(s)))
+        for name, v in (("dynamics", dynamics), ("interrobot", interrobot), ("obstacle", obstacle), ("tracking", tracking)):
+            if v is not None:
+                setattr(s, name, float(v))
+        self._chk(self._L.mgx_set_group_sigmas(self._w, int(group), C.byref(s)))
+
+    def group_sigmas(self, group):
+        """the sigmas a robot added to `group` runs under, {dynamics, interrobot, obstacle, tracking}: the group's own, else the
+        world's (mgx_get_group_sigmas)"""
+        s = hostlib.GroupSigmas()
+        self._chk(self._L.mgx_get_group_sigmas(self._w, int(group), C.byref(s)))
+        return {"dynamics": s.dynamics, "interrobot": s.interrobot, "obstacle": s.obstacle, "tracking": s.tracking}
+
     def set_group_resident(self, enabled):
         """True: a masked world's equal schedules (iterate, tick, mission ticks, batches) run as resident launches of the masked
         form of the kernel, lingering and posts included (mgx_set_group_resident); False, the default: as group plans.  Same

@@ -177,6 +177,17 @@ impl World {
         check(unsafe { sys::mgx_group_resident_stats(self.raw, &mut launches, &mut posts, &mut fallbacks) })?;
         Ok((launches, posts, fallbacks))
     }
+    /// `gbp.sigma-factor-*` of ONE robot group (`mgx_set_group_sigmas`): before the group's first robot is added, every value finite
+    /// and positive; a set equal to the world's is none.  A world whose groups differ in their sigmas runs as a masked world does.
+    pub fn set_group_sigmas(&self, group: u32, sigmas: &sys::mgx_group_sigmas) -> Result<(), MgxError> {
+        check(unsafe { sys::mgx_set_group_sigmas(self.raw, group, sigmas) })
+    }
+    /// The sigmas a robot added to `group` runs under (`mgx_get_group_sigmas`): the group's own, else the world's.
+    pub fn group_sigmas(&self, group: u32) -> Result<sys::mgx_group_sigmas, MgxError> {
+        let mut s = sys::mgx_group_sigmas { dynamics: 0.0, interrobot: 0.0, obstacle: 0.0, tracking: 0.0 };
+        check(unsafe { sys::mgx_get_group_sigmas(self.raw, group, &mut s) })?;
+        Ok(s)
+    }
     /// Several `iterate` calls, one submission (`mgx_batch_begin` / `mgx_batch_end`): the schedules issued inside `f` are recorded and
     /// submitted together, merged into as few resident launches as their segments fit; same results, bit for bit.
     /// Returns (schedules recorded, sweep-kernel launches they were submitted as).

@@ -253,6 +253,16 @@ pub struct mgx_plan_done {
     pub result: mgx_plan_result,
 }
 
+/// the four factor sigmas of one robot group (mgx_set_group_sigmas / mgx_get_group_sigmas)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, PartialEq)]
+pub struct mgx_group_sigmas {
+    pub dynamics: f64,
+    pub interrobot: f64,
+    pub obstacle: f64,
+    pub tracking: f64,
+}
+
 #[repr(C)]
 pub struct mgx_mvn { _private: [u8; 0] }
 #[repr(C)]
@@ -289,6 +299,8 @@ extern "C" {
     pub fn mgx_group_enabled_stats(w: *mut mgx_world, masked_plans: *mut u64, masked_launches: *mut u64) -> c_int;
     pub fn mgx_set_group_resident(w: *mut mgx_world, enabled: i32) -> c_int;
     pub fn mgx_group_resident_stats(w: *mut mgx_world, launches: *mut u64, posts: *mut u64, fallbacks: *mut u64) -> c_int;
+    pub fn mgx_set_group_sigmas(w: *mut mgx_world, group: u32, s: *const mgx_group_sigmas) -> c_int;
+    pub fn mgx_get_group_sigmas(w: *mut mgx_world, group: u32, out: *mut mgx_group_sigmas) -> c_int;
     pub fn mgx_batch_begin(w: *mut mgx_world) -> c_int;
     pub fn mgx_batch_end(w: *mut mgx_world, n_schedules: *mut u32, n_launches: *mut u32) -> c_int;
     pub fn mgx_last_launch_count(w: *mut mgx_world, n_launches: *mut u32) -> c_int;

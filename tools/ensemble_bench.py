@@ -19,12 +19,16 @@ The solo part needs nothing of the ensemble: `--solo` runs it alone, also from t
 --only WORD keeps the workloads whose name contains WORD.  --observers runs the ensemble with environment_collisions=True,
 device_metrics=True, sample_log=False (the figures the Environment Obstacles analysis reads), for a run against the same without.
 
+--ensemble-sigma-tracking S1,S2,.. adds a sixth workload: Structured Junction Twoway, every gbp.sigma-factor-tracking of the list x
+5 seeds (the sigma sweep of the reference's Collaborative GP experiment on a scenario without the global planner) — members that
+differ in a factor sigma, so the world runs as a masked one does (mgx_set_group_sigmas).
+
 --ensemble-masked-resident adds the form `ensemble_masked_resident`: the ensemble with masked_resident=True, whose masked world runs
 the ticks its members share a schedule in as resident launches (mgx_set_group_resident); its row reports the launches of the masked
 form, the schedules posted into them and the fall-backs.  --by-turns runs the timed repetitions of all forms by turns (one of each,
 then the next of each) instead of form after form.
 
-usage: python tools/ensemble_bench.py [--solo | --ensemble] [--ensemble-masked-resident] [--by-turns] [--only WORD] [--observers] [--reps N]
+usage: python tools/ensemble_bench.py [--solo | --ensemble] [--ensemble-masked-resident] [--ensemble-sigma-tracking S1,S2,..] [--by-turns] [--only WORD] [--observers] [--reps N]
        [--max-time S] [--out FILE.json]"""
 import copy
 import gc
@@ -53,14 +57,15 @@ reps, max_time, out_file = option("--reps", int, 5), option("--max-time", float,
 only, observers = option("--only", str, ""), "--observers" in args
 only_solo, only_ensemble = "--solo" in args, "--ensemble" in args
 masked_resident, by_turns = "--ensemble-masked-resident" in args, "--by-turns" in args
+sigma_tracking = option("--ensemble-sigma-tracking", lambda text: [config.f32(float(x)) for x in text.split(",")], None)   # (f32 as the config file's own)
 OBSERVERS = {"environment_collisions": True, "device_metrics": True, "sample_log": False} if observers else {}
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 
 
-def members(name, seeds, rates, radii=(None,), amounts=(None,), tracking=(None,)):
+def members(name, seeds, rates, radii=(None,), amounts=(None,), tracking=(None,), sigma_trk=(None,)):
     out = []
-    for trk, amount in [(t, a) for t in tracking for a in amounts]:
+    for sig, trk, amount in [(s, t, a) for s in sigma_trk for t in tracking for a in amounts]:
         for radius in radii:
             for rate in rates:
                 for seed in seeds:
@@ -68,6 +73,8 @@ def members(name, seeds, rates, radii=(None,), amounts=(None,), tracking=(None,)
                     sc["config"]["simulation"]["prng-seed"] = seed
                     if trk is not None:
                         sc["config"]["gbp"]["factors-enabled"]["tracking"] = trk
+                    if sig is not None:
+                        sc["config"]["gbp"]["sigma-factor-tracking"] = sig
                     if rate is not None:
                         sc["config"]["robot"]["communication"]["failure-rate"] = rate
                     if radius is not None:
@@ -88,6 +95,11 @@ WORKLOADS = {
     "structured-junction-twoway tracking on / off x 8 rates": lambda: members("Structured Junction Twoway", [0], [0.0, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7],
                                                                               tracking=[True, False]),
 }
+
+
+if sigma_tracking:
+    WORKLOADS["structured-junction-twoway sigma-tracking " + " / ".join(f"{x:g}" for x in sigma_tracking) + " x 5 seeds"] = lambda: members(
+        "Structured Junction Twoway", [0, 31, 227, 252, 805], [None], sigma_trk=sigma_tracking)
 
 
 def spread(xs):

@@ -18,7 +18,7 @@ BEGIN, END = "// BEGIN generated from include/mgx.h (tools/gen_rust_sys.py)", "/
 SCALARS = {"int": "c_int", "int32_t": "i32", "uint32_t": "u32", "int64_t": "i64", "uint64_t": "u64", "uint8_t": "u8", "double": "f64",
            "float": "f32", "char": "c_char", "void": "c_void"}
 STRUCTS = {"mgx_world", "mgx_params", "mgx_robot_desc", "mgx_env_desc", "mgx_env_obstacle", "mgx_mvn", "mgx_shard_plan", "mgx_mission_desc", "mgx_mission_run_desc", "mgx_collision_event", "mgx_env_collider",
-           "mgx_env_collision_event", "mgx_goal_area", "mgx_goal_arrival", "mgx_track_sample", "mgx_track_metrics", "mgx_plan_params", "mgx_plan_request", "mgx_plan_result", "mgx_plan_done"}
+           "mgx_env_collision_event", "mgx_goal_area", "mgx_goal_arrival", "mgx_track_sample", "mgx_track_metrics", "mgx_plan_params", "mgx_plan_request", "mgx_plan_result", "mgx_plan_done", "mgx_group_sigmas"}
 RUST_KEYWORDS = {"type", "ref", "in", "fn", "mod", "use", "where", "self", "move", "box", "loop", "match"}
 
 

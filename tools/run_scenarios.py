@@ -15,19 +15,19 @@ sample is logged on the device and the robots' positions / velocities lists stay
 scenario's line then carries the arrivals per area and the throughput the reference's analyse-junction-scenario.py reads out of an
 export (robots that started within 50 s and arrived, per second).  --export DIR writes each scenario's export to DIR/<name>.json.
 --ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:INTERNAL:EXTERNAL,..]
-[--ensemble-tracking on,off] [--ensemble-masked-resident]
+[--ensemble-tracking on,off] [--ensemble-sigma-tracking S1,S2,..] [--ensemble-masked-resident]
 runs the cross product of ONE scenario — every seed with every failure rate, every comms radius, every GBP iteration schedule
-(KIND: centered, soon-as-possible, late-as-possible, interleave-evenly, half-beginning-half-end) and gbp.factors-enabled.tracking
-on / off (default each: the scenario's own) — as one Ensemble (magics_amd/ensemble.py):
+(KIND: centered, soon-as-possible, late-as-possible, interleave-evenly, half-beginning-half-end), gbp.factors-enabled.tracking
+on / off and every gbp.sigma-factor-tracking (default each: the scenario's own) — as one Ensemble (magics_amd/ensemble.py):
 the members are robot groups of one world, one launch per schedule and one synchronisation per tick for all of them, each member
 identical to the same run alone.  One line per member — with --environment-collisions, --goal-areas and --metrics (with or
 without --no-sample-log) it carries the member's contacts, arrivals and the means of its run metrics; with --export DIR one
-export per member, DIR/<name>.seed<A>.rate<X>.radius<R>[.<kind>-<internal>-<external>][.tracking-<on|off>].json.  The global planner and host trackers do not run in an Ensemble.
---ensemble-masked-resident: members that differ in tracking on / off make the world masked; with this switch its ticks run as resident
+export per member, DIR/<name>.seed<A>.rate<X>.radius<R>[.<kind>-<internal>-<external>][.tracking-<on|off>][.sigma-tracking<S>].json.  The global planner and host trackers do not run in an Ensemble.
+--ensemble-masked-resident: members that differ in tracking on / off or in sigma-factor-tracking make the world masked; with this switch its ticks run as resident
 launches all the same (Ensemble(masked_resident=True), mgx_set_group_resident) — same results.
 usage: python tools/run_scenarios.py [--max-time S] [--goal-areas junction|FILE.json] [--export DIR] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
            [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N]
-           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..] [--ensemble-tracking on,off] [--ensemble-masked-resident]]
+           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..] [--ensemble-tracking on,off] [--ensemble-sigma-tracking S1,S2,..] [--ensemble-masked-resident]]
            [scenario-dir | name ...]"""
 import copy
 import json
@@ -118,11 +118,18 @@ if "--ensemble-tracking" in args:
         sys.exit("--ensemble-tracking: a list of on / off")
     ensemble_tracking = [x == "on" for x in words]
     del args[i:i + 2]
+ensemble_sigma_tracking = None
+if "--ensemble-sigma-tracking" in args:
+    i = args.index("--ensemble-sigma-tracking")
+    ensemble_sigma_tracking = [config.f32(float(x)) for x in args[i + 1].split(",")]   # (f32 as the config file's own, parse_config)
+    if any(not (0.0 < x < float("inf")) for x in ensemble_sigma_tracking):
+        sys.exit("--ensemble-sigma-tracking: a list of positive finite sigmas")
+    del args[i:i + 2]
 ensemble_masked_resident = "--ensemble-masked-resident" in args
 if ensemble_masked_resident:
     args.remove("--ensemble-masked-resident")
-if (ensemble_rates or ensemble_radii or ensemble_schedules or ensemble_tracking or ensemble_masked_resident) and not ensemble_seeds:
-    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii, --ensemble-schedules, --ensemble-tracking and --ensemble-masked-resident need --ensemble-seeds")
+if (ensemble_rates or ensemble_radii or ensemble_schedules or ensemble_tracking or ensemble_sigma_tracking or ensemble_masked_resident) and not ensemble_seeds:
+    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii, --ensemble-schedules, --ensemble-tracking, --ensemble-sigma-tracking and --ensemble-masked-resident need --ensemble-seeds")
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 if ensemble_seeds:
@@ -133,7 +140,7 @@ if ensemble_seeds:
         sys.exit("--ensemble-seeds: the global planner and host trackers do not run in an Ensemble (magics_amd/ensemble.py says why)")
     base = config.load_scenario(args[0]) if os.path.isdir(args[0]) else known[args[0]]
     members = []
-    for tracking in ensemble_tracking or [None]:
+    for sigma_trk, tracking in [(s, t) for s in ensemble_sigma_tracking or [None] for t in ensemble_tracking or [None]]:
         for schedule in ensemble_schedules or [None]:
             for radius in ensemble_radii or [base["config"]["robot"]["communication"]["radius"]]:
                 for rate in ensemble_rates or [base["config"]["robot"]["communication"]["failure-rate"]]:
@@ -146,6 +153,8 @@ if ensemble_seeds:
                             sc["config"]["gbp"]["iteration-schedule"].update(schedule)
                         if tracking is not None:
                             sc["config"]["gbp"]["factors-enabled"]["tracking"] = tracking
+                        if sigma_trk is not None:
+                            sc["config"]["gbp"]["sigma-factor-tracking"] = sigma_trk
                         members.append((seed, rate, radius, sc))
     t0 = time.perf_counter()
     e = ensemble.Ensemble([sc for *_, sc in members], World(config.world_params(base["config"])), environment_collisions=env_collisions,
@@ -162,6 +171,7 @@ if ensemble_seeds:
         print(json.dumps({"scenario": sc.get("name", args[0]), "seed": seed, "failure_rate": rate, "comms_radius": radius,
                           **({"schedule": f"{sch['schedule']}:{sch['internal']}:{sch['external']}"} if ensemble_schedules else {}),
                           **({"tracking": sc["config"]["gbp"]["factors-enabled"]["tracking"]} if ensemble_tracking else {}),
+                          **({"sigma_tracking": sc["config"]["gbp"]["sigma-factor-tracking"]} if ensemble_sigma_tracking else {}),
                           "simulated_s": round(s.elapsed(), 1),
                           "robots": len(s.robots), "finished": len(done), "all_finished": s.finished(), "K": s.K,
                           "mean_distance": round(sum(trav) / max(1, len(trav)), 1),
@@ -176,6 +186,8 @@ if ensemble_seeds:
             tail = f".{sch['schedule']}-{sch['internal']}-{sch['external']}" if ensemble_schedules else ""
             if ensemble_tracking:
                 tail += ".tracking-on" if sc["config"]["gbp"]["factors-enabled"]["tracking"] else ".tracking-off"
+            if ensemble_sigma_tracking:
+                tail += f".sigma-tracking{sc['config']['gbp']['sigma-factor-tracking']:g}"
             with open(os.path.join(export_dir, f"{stem}.seed{seed}.rate{rate:g}.radius{radius:g}{tail}.json"), "w", encoding="utf-8") as f:
                 json.dump(m.export(), f)
     mixed_calls, mixed_launches, sat_out = e.world.group_schedule_stats()
