@@ -1407,7 +1407,29 @@ int mgx_track_metrics_read(mgx_world *w, mgx_track_metrics *out, uint64_t capaci
  * mgx_plan_pending(w, n): requests submitted and neither collected nor cancelled.
  * mgx_planner_enable while requests are pending: env == NULL drops them with everything else; a new map is MGX_ERR_STATE and
  *   changes nothing.  mgx_plan_paths and mgx_plan_tree work beside pending requests (they wait for the slices enqueued, and
- *   advance none of them). */
+ *   advance none of them).
+ *
+ * A PARAMETER SET PER GROUP.  A launch runs many requests, and the runs of a parameter sweep that share a world (ROBOT GROUPS)
+ *   differ in `rrt.*` as they differ in seed or sigmas.  A group here is only the index of a parameter set, 0 ..
+ *   MGX_GROUPS_MAX - 1: no robot of that group need exist.  The sets live in one table in device memory, uploaded on the
+ *   world's stream when one changes; a request carries the index of its set from submit on, and its workgroup reads the row once
+ *   per launch.  A launch none of whose requests names a set is handed no table and runs the code it ran before there were sets.
+ * mgx_planner_set_group_params(w, group, params): from the next submit on, requests of `group` run under *params.  params ==
+ *   NULL puts the group back on the world's parameters.  Checked in this order, with nothing changed on failure: planner off,
+ *   MGX_ERR_STATE; group >= MGX_GROUPS_MAX, MGX_ERR_INVALID; the value checks mgx_planner_enable makes on a parameter struct,
+ *   MGX_ERR_INVALID; max_nodes or iterations_per_launch neither 0 nor equal to what the world runs with, MGX_ERR_INVALID — these
+ *   two belong to the launch (they fix the LDS size, the arrays' strides and the budget), and a set is stored with the world's;
+ *   requests pending (mgx_plan_pending > 0), MGX_ERR_STATE: a set does not change under a request that is running.
+ *   sample_half_extent 0 is 2000, as in mgx_planner_enable.  mgx_planner_enable in either form (a new map, or NULL) forgets every
+ *   group's set.
+ * mgx_planner_group_params(w, group, out): what a request of the group would run under — its own set, or the world's as
+ *   mgx_planner_enable took it (defaults filled in).  MGX_ERR_STATE: planner off.  MGX_ERR_INVALID: NULL, group >= MGX_GROUPS_MAX.
+ * mgx_plan_paths_groups, mgx_plan_submit_groups: mgx_plan_paths and mgx_plan_submit with one group per request; groups == NULL
+ *   is group 0 for every request, and that is what mgx_plan_paths and mgx_plan_submit are.  A group >= MGX_GROUPS_MAX is
+ *   MGX_ERR_INVALID and nothing is queued.  On a world that has never set a group's parameters they compute what the plain calls
+ *   compute, bit for bit.  Everything else keeps its statement per request: mgx_plan_tree, the collect order (slice number,
+ *   ticket), cancel, pending, and HOW MANY SLICES A REQUEST TAKES with the max_iterations of the request's own group.
+ *   mgx_plan_done.group is the group a request was submitted under. */
 #define MGX_PLAN_OK 0
 #define MGX_PLAN_MAX_ITERATIONS 1
 #define MGX_PLAN_TREE_FULL 2
@@ -1442,7 +1464,7 @@ int mgx_plan_tree(mgx_world *w, uint32_t request, uint32_t capacity, double *xy,
 typedef struct mgx_plan_done {
     uint64_t ticket;
     uint32_t slices;                /* the slice number it ended in                                          */
-    uint32_t reserved;
+    uint32_t group;                 /* the group it was submitted under (a word that was reserved and 0)     */
     mgx_plan_result result;
 } mgx_plan_done;
 int mgx_plan_submit(mgx_world *w, uint32_t n, const mgx_plan_request *requests, uint64_t *tickets);
@@ -1452,6 +1474,12 @@ int mgx_plan_collect(mgx_world *w, uint32_t flags, uint32_t capacity, mgx_plan_d
                      uint32_t point_capacity, uint32_t *n_done, uint32_t *n_points);
 int mgx_plan_cancel(mgx_world *w, uint64_t ticket);
 int mgx_plan_pending(mgx_world *w, uint32_t *n);
+int mgx_planner_set_group_params(mgx_world *w, uint32_t group, const mgx_plan_params *params);
+int mgx_planner_group_params(mgx_world *w, uint32_t group, mgx_plan_params *out);
+int mgx_plan_paths_groups(mgx_world *w, uint32_t n, const mgx_plan_request *requests, const uint32_t *groups,
+                          mgx_plan_result *results, float *path_xy, uint32_t point_capacity, uint32_t *n_points);
+int mgx_plan_submit_groups(mgx_world *w, uint32_t n, const mgx_plan_request *requests, const uint32_t *groups,
+                           uint64_t *tickets);
 
 /* ---- host helpers (no device needed) --------------------------------------------------- */
 /* gbp_schedule: fills steps[max(n_int,n_ext)] with MGX_STEP_* bits. Returns the count

@@ -458,15 +458,18 @@ public:
         std::vector<mgx_plan_result> results;     ///< one per request; its points are path_xy[first_point .. + n_points)
         std::vector<std::array<float, 2>> path_xy;
     };
-    Plans plan_paths(const std::vector<mgx_plan_request> &requests) {
+    /// groups: one group per request (empty: group 0 for all) — the parameter set each runs under (planner_set_group_params)
+    Plans plan_paths(const std::vector<mgx_plan_request> &requests, const std::vector<uint32_t> &groups = {}) {
+        if (!groups.empty() && groups.size() != requests.size()) throw std::invalid_argument("plan_paths: one group per request");
+        const uint32_t *g = groups.empty() ? nullptr : groups.data();
         Plans out;
         out.results.resize(requests.size());
         out.path_xy.resize(256 * requests.size() + 1);
         uint32_t total = 0;
-        int rc = mgx_plan_paths(w_, (uint32_t)requests.size(), requests.data(), out.results.data(), out.path_xy[0].data(), (uint32_t)out.path_xy.size(), &total);
+        int rc = mgx_plan_paths_groups(w_, (uint32_t)requests.size(), requests.data(), g, out.results.data(), out.path_xy[0].data(), (uint32_t)out.path_xy.size(), &total);
         if (rc == MGX_ERR_INVALID && total > out.path_xy.size()) {  // (the counts came back: once more with room for them)
             out.path_xy.resize(total);
-            rc = mgx_plan_paths(w_, (uint32_t)requests.size(), requests.data(), out.results.data(), out.path_xy[0].data(), total, &total);
+            rc = mgx_plan_paths_groups(w_, (uint32_t)requests.size(), requests.data(), g, out.results.data(), out.path_xy[0].data(), total, &total);
         }
         check(rc);
         out.path_xy.resize(total);
@@ -474,10 +477,18 @@ public:
     }
     /// plans that ride the stream (mgx.h): submit returns tickets at once, advance enqueues one slice for every pending request,
     /// collect hands out what has ended — in the order of (slice number, ticket), each once; wait = false never blocks
-    std::vector<uint64_t> plan_submit(const std::vector<mgx_plan_request> &requests) {
+    std::vector<uint64_t> plan_submit(const std::vector<mgx_plan_request> &requests, const std::vector<uint32_t> &groups = {}) {
+        if (!groups.empty() && groups.size() != requests.size()) throw std::invalid_argument("plan_submit: one group per request");
         std::vector<uint64_t> tickets(requests.size());
-        check(mgx_plan_submit(w_, (uint32_t)requests.size(), requests.data(), tickets.data()));
+        check(mgx_plan_submit_groups(w_, (uint32_t)requests.size(), requests.data(), groups.empty() ? nullptr : groups.data(), tickets.data()));
         return tickets;
+    }
+    /// a parameter set per group (mgx.h): requests of `group` run under `params` from the next submit on; nullptr: the world's again
+    void planner_set_group_params(uint32_t group, const mgx_plan_params *params) { check(mgx_planner_set_group_params(w_, group, params)); }
+    mgx_plan_params planner_group_params(uint32_t group) {
+        mgx_plan_params out{};
+        check(mgx_planner_group_params(w_, group, &out));
+        return out;
     }
     void plan_advance(uint32_t iterations) { check(mgx_plan_advance(w_, iterations)); }
     void planner_set_tick_budget(uint32_t iterations) { check(mgx_planner_set_tick_budget(w_, iterations)); }

@@ -449,7 +449,8 @@ struct PlanState {             // 64 bytes
     uint32_t path_len;         // points of the path (the tree's nodes on it, then `end`)
     uint32_t smooth_done;      // smoothing iterations so far
     int32_t goal;              // the node that reached the goal
-    uint32_t reserved;
+    uint32_t set;              // the parameter set the request runs under: 0 the launch's own (PlanDev), k > 0 row k - 1 of PlanPoolDev::sets;
+                               // written by the host at submit, carried through every launch
 };
 static_assert(sizeof(PlanState) == 64, "one request's state is one 64-byte record");
 struct PlanDev {
@@ -460,6 +461,15 @@ struct PlanDev {
     uint32_t budget;           // iterations (growth and smoothing together) one launch runs per request at the most
     int32_t smoothing;
 };
+// One group's parameter set (mgx_planner_set_group_params): the fields of PlanDev a request may have of its own.  max_nodes and
+// budget fix the launch's LDS, the arrays' strides and the slice: they stay the launch's.
+struct PlanSetDev {            // 48 bytes
+    double step, radius2, half_extent, smoothing_step;
+    float collision_radius;
+    uint32_t max_iterations, smoothing_max;
+    int32_t smoothing;
+};
+static_assert(sizeof(PlanSetDev) == 48, "a row of the table of sets");
 // A pool of requests (k_plan_pool; the host's side: mgx_plan_pool.h, mgx_world_planner.inc): the one that rides the world's
 // stream, or the one of a mgx_plan_paths call.  Slots are allocated a block at a time and never move: a launch finds a slot's
 // arrays through its block's base pointers.
@@ -489,6 +499,7 @@ struct PlanPoolDev {
     uint32_t slots_per_block;
     uint32_t seq;                // the number of this advance (low word): slice number = seq - first_seq
     uint32_t reserved;
+    const PlanSetDev *sets;      // device memory, the groups' parameter sets; NULL: no request of this launch names one
 };
 
 __host__ __device__ constexpr int frozen_words(int K) { return 40 * (K - 1) + 8 * (K - 2); }

@@ -17,7 +17,9 @@
 // global memory — tree, counters, stream state, phase — so the host launches again until every request is done, and where the
 // slices fall does not show in the result.  One kernel runs the slice (plan_slice): k_plan_pool, over the active slots of a pool
 // of requests — the pool whose requests ride the world's stream (mgx_plan_submit / _advance / _collect), or the pool that
-// mgx_plan_paths fills, drives to the end and empties within one call.
+// mgx_plan_paths fills, drives to the end and empties within one call.  A request may run under its robot group's own parameter set
+// (mgx_planner_set_group_params): a row of one device table, read once per launch; k_plan_pool<true> is the launch that carries
+// the table, k_plan_pool<false> the launch none of whose requests names a set.
 // All planner arithmetic is f64 with every operation rounded on its own: contraction is switched off for this file whatever
 // the command line says, so libmgx.so and libmgx_fma.so hold the same code here.
 #include <hip/hip_runtime.h>
@@ -111,13 +113,23 @@ struct PlanSlot {
 };
 
 // One slice of one request by one workgroup.  True (in every lane) when the request ENDED in this slice.
-__device__ __forceinline__ bool plan_slice(const PlanDev &c, const PlanSlot &slot) {
+// `sets`: the groups' parameter sets (mgx_planner_set_group_params), NULL when no request of the launch names one.  A request
+// that names one (PlanState::set) reads its row once and runs under a copy of the launch's constants with the row's fields in
+// place: every value is the same in all lanes, as the launch's own are.
+__device__ __forceinline__ bool plan_slice(const PlanDev &launch, const PlanSetDev *__restrict__ sets, const PlanSlot &slot) {
     extern __shared__ double plan_lds[];  // X [max_nodes], Y [max_nodes]
     __shared__ PlanScratch sc;
     __shared__ uint32_t s_len;
     const int tid = (int)threadIdx.x;
     PlanState st = *slot.state;  // (the same in every lane, and kept so)
     if (st.phase == PLAN_PHASE_DONE) return false;
+    PlanDev c = launch;
+    if (sets && st.set) {
+        const PlanSetDev g = sets[st.set - 1u];
+        c.step = g.step; c.radius2 = g.radius2; c.half_extent = g.half_extent; c.smoothing_step = g.smoothing_step;
+        c.collision_radius = g.collision_radius;
+        c.max_iterations = g.max_iterations; c.smoothing_max = g.smoothing_max; c.smoothing = g.smoothing;
+    }
     const uint32_t cap = c.max_nodes;
     double *const X = plan_lds, *const Y = plan_lds + cap;
     double *const gx = slot.x, *const gy = slot.y, *const gcost = slot.cost;
@@ -269,6 +281,8 @@ __device__ __forceinline__ bool plan_slice(const PlanDev &c, const PlanSlot &slo
 // visible to the host, then claims the next log entry (the one atomic, on a counter in device memory: the host never reads it)
 // and fills it with one 16-byte store.  The host takes an entry once its ticket is not 0 (tickets count from 1) and zeroes it
 // again, so a counter that is ahead of an entry's store only delays that entry to the next look.
+// SETS: the launch carries the table of parameter sets.  A launch without one runs the instantiation that knows nothing of sets.
+template <bool SETS>
 __global__ void __launch_bounds__(PLAN_BLOCK) k_plan_pool(PlanDev c, PlanPoolDev pool) {
     const PlanActive a = pool.active[blockIdx.x];
     const PlanBlockDev b = pool.blocks[a.slot / pool.slots_per_block];
@@ -279,7 +293,7 @@ __global__ void __launch_bounds__(PLAN_BLOCK) k_plan_pool(PlanDev c, PlanPoolDev
     slot.parent = b.parent + i * cap;
     slot.path = b.path + i * (cap + 1);
     slot.out = b.out + 2 * i * (cap + 1);
-    if (!plan_slice(c, slot)) return;
+    if (!plan_slice(c, SETS ? pool.sets : nullptr, slot)) return;
     __threadfence_system();  // every lane: its points; lane 0: the state
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the fence's own wait is not relied on)
     __syncthreads();
@@ -295,17 +309,22 @@ __global__ void __launch_bounds__(PLAN_BLOCK) k_plan_pool(PlanDev c, PlanPoolDev
     }
 }
 
-hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s) {
-    if (n_active <= 0) return hipSuccess;
+template <bool SETS>
+static hipError_t launch_plan_pool_as(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s) {
     static size_t granted = 0;
     const size_t lds = sizeof(double) * 2 * (size_t)c.max_nodes;
     if (lds > granted) {  // dynamic LDS beyond 64 KiB has to be asked for once per size
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_plan_pool), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_plan_pool<SETS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
         granted = lds;
     }
-    hipLaunchKernelGGL(k_plan_pool, dim3((unsigned)n_active), dim3(PLAN_BLOCK), lds, s, c, pool);
+    hipLaunchKernelGGL(k_plan_pool<SETS>, dim3((unsigned)n_active), dim3(PLAN_BLOCK), lds, s, c, pool);
     return hipGetLastError();
+}
+
+hipError_t launch_plan_pool(const PlanDev &c, const PlanPoolDev &pool, int n_active, hipStream_t s) {
+    if (n_active <= 0) return hipSuccess;
+    return pool.sets ? launch_plan_pool_as<true>(c, pool, n_active, s) : launch_plan_pool_as<false>(c, pool, n_active, s);
 }
 
 }  // namespace mgx

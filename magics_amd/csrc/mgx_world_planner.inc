@@ -1,5 +1,6 @@
 // mgx_world_planner.inc — C ABI: the global planner (mgx_planner_enable, mgx_plan_paths, mgx_plan_tree; mgx_plan_submit, _advance,
-// _collect, _cancel, _pending and mgx_planner_set_tick_budget for plans that ride the stream).
+// _collect, _cancel, _pending and mgx_planner_set_tick_budget for plans that ride the stream; mgx_planner_set_group_params,
+// mgx_planner_group_params and the _groups forms of paths and submit for a parameter set per robot group).
 // Part of ONE translation unit: included by mgx_world.hip (which says in which order, and why one unit).
 // What a plan is: include/mgx.h; how a launch computes it: mgx_planner.hip.  The host's side here: the map goes up once
 // (env_map_upload, shared with the robot-environment pass), and every request lives in a slot of a pool (mgx_world::Planner::Pool;
@@ -24,30 +25,59 @@ static void planner_drop(mgx_world *w) {
     p.enabled = false;
     p.map.release();
     p.pool.release();
+    p.sets.release();
     plan_call_drop(p);
 }
 
+// the fields a request may have of its own, as the device reads them: a row of the table of sets, and the same fields of a launch
+static PlanSetDev plan_set_dev(const mgx_plan_params &q) {
+    PlanSetDev g{};
+    g.step = (double)q.step_size;
+    g.radius2 = (double)q.neighbourhood_radius * (double)q.neighbourhood_radius;
+    g.half_extent = (double)q.sample_half_extent;
+    g.smoothing_step = (double)q.smoothing_step;
+    g.collision_radius = q.collision_radius;
+    g.max_iterations = q.max_iterations;
+    g.smoothing_max = q.smoothing_max_iterations;
+    g.smoothing = q.smoothing_enabled ? 1 : 0;
+    return g;
+}
 // what a launch is handed apart from its arrays and its budget
 static PlanDev plan_dev_params(const mgx_world::Planner &p) {
-    const mgx_plan_params &q = p.params;
+    const PlanSetDev g = plan_set_dev(p.params);
     PlanDev d{};
     d.map = p.map.d;
-    d.step = (double)q.step_size;
-    d.radius2 = (double)q.neighbourhood_radius * (double)q.neighbourhood_radius;
-    d.half_extent = (double)q.sample_half_extent;
-    d.smoothing_step = (double)q.smoothing_step;
-    d.collision_radius = q.collision_radius;
-    d.max_iterations = q.max_iterations; d.max_nodes = q.max_nodes;
-    d.smoothing = q.smoothing_enabled ? 1 : 0;
-    d.smoothing_max = q.smoothing_max_iterations;
+    d.step = g.step; d.radius2 = g.radius2; d.half_extent = g.half_extent; d.smoothing_step = g.smoothing_step;
+    d.collision_radius = g.collision_radius;
+    d.max_iterations = g.max_iterations; d.max_nodes = p.params.max_nodes;
+    d.smoothing = g.smoothing;
+    d.smoothing_max = g.smoothing_max;
     return d;
+}
+// the parameters a request of `group` runs under: its own set, or the world's
+static const mgx_plan_params &plan_params_of(const mgx_world::Planner &p, uint32_t group) {
+    const uint32_t k = p.sets.of(group);
+    return k ? p.sets.params[k - 1] : p.params;
+}
+
+// the value checks of a parameter struct (mgx_planner_enable, mgx_planner_set_group_params)
+static int plan_params_check(const mgx_plan_params &q) {
+    const auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
+    const auto not_negative = [](float v) { return std::isfinite(v) && v >= 0.f; };
+    if (!positive(q.step_size) || !positive(q.neighbourhood_radius) || (q.smoothing_enabled && !positive(q.smoothing_step)))
+        return fail(MGX_ERR_INVALID, "step_size, neighbourhood_radius and smoothing_step must be positive and finite");
+    if (!not_negative(q.collision_radius) || !not_negative(q.sample_half_extent))
+        return fail(MGX_ERR_INVALID, "collision_radius and sample_half_extent must be finite and not negative");
+    if (q.max_nodes > PLAN_MAX_NODES) return fail(MGX_ERR_INVALID, "max_nodes beyond %u", PLAN_MAX_NODES);
+    return MGX_OK;
 }
 
 static bool plan_request_finite(const mgx_plan_request &r) {
     return std::isfinite(r.start[0]) && std::isfinite(r.start[1]) && std::isfinite(r.end[0]) && std::isfinite(r.end[1]);
 }
-static PlanState plan_initial_state(const mgx_plan_request &r) {
+static PlanState plan_initial_state(const mgx_plan_request &r, uint32_t set) {
     PlanState st{};
+    st.set = set;
     st.rng = r.wyrand_state;
     for (int k = 0; k < 2; k++) { st.start[k] = r.start[k]; st.end[k] = r.end[k]; }
     st.phase = PLAN_PHASE_INIT;
@@ -138,8 +168,9 @@ static int plan_pool_add_block(PlanPool &pl, const mgx_plan_params &q, hipStream
 
 // n requests into n slots that nothing in flight can touch (blocks are added as needed; on failure what was taken goes back): each
 // slot gets its request's initial state and a ticket (book.slots[slot].ticket)
-static int plan_pool_submit(PlanPool &pl, const mgx_plan_params &q, hipStream_t stream, uint32_t n, const mgx_plan_request *requests,
-                            std::vector<uint32_t> &slots) {
+static int plan_pool_submit(PlanPool &pl, const mgx_world::Planner &p, hipStream_t stream, uint32_t n, const mgx_plan_request *requests,
+                            const uint32_t *groups, std::vector<uint32_t> &slots) {
+    const mgx_plan_params &q = p.params;
     (void)plan_pool_poll(pl);  // (before a slot changes its tenant: what the log says of the one before is taken)
     slots.clear();
     slots.reserve(n);
@@ -153,8 +184,13 @@ static int plan_pool_submit(PlanPool &pl, const mgx_plan_params &q, hipStream_t 
             return rc;
         }
     }
+    if (pl.slot_group.size() < pl.book.slots.size()) { pl.slot_group.resize(pl.book.slots.size(), 0u); pl.slot_set.resize(pl.book.slots.size(), 0u); }
     for (uint32_t i = 0; i < n; i++) {
-        pl.blocks[slots[i] / pl.book.slots_per_block].state[slots[i] % pl.book.slots_per_block] = plan_initial_state(requests[i]);
+        const uint32_t group = groups ? groups[i] : 0u;
+        const uint32_t set = p.sets.of(group);
+        pl.blocks[slots[i] / pl.book.slots_per_block].state[slots[i] % pl.book.slots_per_block] = plan_initial_state(requests[i], set);
+        pl.slot_group[slots[i]] = group;
+        pl.slot_set[slots[i]] = set;
         (void)pl.book.submit(slots[i]);
     }
     return MGX_OK;
@@ -186,11 +222,14 @@ static int plan_pool_write_list(PlanPool &pl) {
     }
     PlanActive *out = pl.lists[(size_t)k].p;
     size_t m = 0;
+    bool sets = false;
     pl.book.for_running([&](uint32_t s, const PlanPoolBook::Slot &q) {
         PlanActive a{};
         a.ticket = q.ticket; a.slot = s; a.first_seq = (uint32_t)q.first_seq;
         if (m < n) out[m++] = a;
+        sets = sets || pl.slot_set[s] != 0;
     });
+    pl.cur_sets = sets;
     pl.cur = k;
     pl.cur_n = (uint32_t)m;
     pl.book.list_dirty = false;
@@ -214,6 +253,7 @@ static int plan_pool_advance(PlanPool &pl, const mgx_world::Planner &p, hipStrea
     pd.log_count = pl.log_count;
     pd.log_cap = pl.log_cap;
     pd.slots_per_block = pl.book.slots_per_block;
+    pd.sets = pl.cur_sets ? p.sets.dev : nullptr;
     const uint64_t seq = pl.book.seq + 1;
     pd.seq = (uint32_t)seq;
     HIP_TRY(launch_plan_pool(d, pd, (int)pl.cur_n, stream));
@@ -238,13 +278,8 @@ int mgx_planner_enable(mgx_world *w, const mgx_env_desc *env, const mgx_plan_par
     if (!params) return fail(MGX_ERR_INVALID, "null params");
     if (p.pool.book.pending()) return fail(MGX_ERR_STATE, "%u requests are pending (mgx_plan_collect, mgx_plan_cancel)", p.pool.book.pending());
     mgx_plan_params q = *params;
-    const auto positive = [](float v) { return std::isfinite(v) && v > 0.f; };
-    const auto not_negative = [](float v) { return std::isfinite(v) && v >= 0.f; };
-    if (!positive(q.step_size) || !positive(q.neighbourhood_radius) || (q.smoothing_enabled && !positive(q.smoothing_step)))
-        return fail(MGX_ERR_INVALID, "step_size, neighbourhood_radius and smoothing_step must be positive and finite");
-    if (!not_negative(q.collision_radius) || !not_negative(q.sample_half_extent))
-        return fail(MGX_ERR_INVALID, "collision_radius and sample_half_extent must be finite and not negative");
-    if (q.max_nodes > PLAN_MAX_NODES) return fail(MGX_ERR_INVALID, "max_nodes beyond %u", PLAN_MAX_NODES);
+    const int rc_check = plan_params_check(q);
+    if (rc_check != MGX_OK) return rc_check;
     if (q.sample_half_extent == 0.f) q.sample_half_extent = PLAN_DEFAULT_HALF_EXTENT;
     if (q.max_nodes == 0) q.max_nodes = PLAN_DEFAULT_NODES;
     if (q.iterations_per_launch == 0) q.iterations_per_launch = PLAN_DEFAULT_SLICE;
@@ -260,6 +295,11 @@ int mgx_planner_enable(mgx_world *w, const mgx_env_desc *env, const mgx_plan_par
 
 int mgx_plan_paths(mgx_world *w, uint32_t n, const mgx_plan_request *requests, mgx_plan_result *results, float *path_xy,
                    uint32_t point_capacity, uint32_t *n_points) {
+    return mgx_plan_paths_groups(w, n, requests, nullptr, results, path_xy, point_capacity, n_points);
+}
+
+int mgx_plan_paths_groups(mgx_world *w, uint32_t n, const mgx_plan_request *requests, const uint32_t *groups, mgx_plan_result *results,
+                          float *path_xy, uint32_t point_capacity, uint32_t *n_points) {
     MGX_ENTER(w);
     if (!w || !n_points || (n && (!requests || !results)) || (!path_xy && point_capacity)) return fail(MGX_ERR_INVALID, "null argument");
     mgx_world::Planner &p = w->planner;
@@ -267,6 +307,8 @@ int mgx_plan_paths(mgx_world *w, uint32_t n, const mgx_plan_request *requests, m
     if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the global planner runs on unsharded worlds");
     for (uint32_t i = 0; i < n; i++)
         if (!plan_request_finite(requests[i])) return fail(MGX_ERR_INVALID, "request %u: a coordinate is not finite", i);
+    for (uint32_t i = 0; groups && i < n; i++)
+        if (groups[i] >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "request %u: group %u beyond %u", i, groups[i], MGX_GROUPS_MAX - 1);
     if (n > (1u << 20)) return fail(MGX_ERR_INVALID, "more than 2^20 requests");
     if (n == 0) { *n_points = 0; p.call_slots.clear(); return MGX_OK; }
     MGX_CONFIRM(w);
@@ -278,9 +320,15 @@ int mgx_plan_paths(mgx_world *w, uint32_t n, const mgx_plan_request *requests, m
         plan_call_drop(p);
         pl.book.reset(n + n / 4, 1);
     }
-    int rc = plan_pool_submit(pl, q, w->stream, n, requests, p.call_slots);
-    // every launch takes `budget` off what a request has left (growth, then smoothing), and one more finishes it
-    const uint64_t most = ((uint64_t)q.max_iterations + q.smoothing_max_iterations) / q.iterations_per_launch + 3;
+    int rc = plan_pool_submit(pl, p, w->stream, n, requests, groups, p.call_slots);
+    // every launch takes `budget` off what a request has left (growth, then smoothing), and one more finishes it: the longest a
+    // request of these groups can take
+    uint64_t longest = (uint64_t)q.max_iterations + q.smoothing_max_iterations;
+    for (uint32_t i = 0; groups && i < n; i++) {
+        const mgx_plan_params &g = plan_params_of(p, groups[i]);
+        longest = std::max(longest, (uint64_t)g.max_iterations + g.smoothing_max_iterations);
+    }
+    const uint64_t most = longest / q.iterations_per_launch + 3;
     for (uint64_t l = 0; l < most && rc == MGX_OK && pl.book.n_running; l++) {
         rc = plan_pool_advance(pl, p, w->stream, q.iterations_per_launch);
         if (rc == MGX_OK) rc = plan_pool_poll(pl, true);
@@ -336,6 +384,10 @@ int mgx_plan_tree(mgx_world *w, uint32_t request, uint32_t capacity, double *xy,
 }
 
 int mgx_plan_submit(mgx_world *w, uint32_t n, const mgx_plan_request *requests, uint64_t *tickets) {
+    return mgx_plan_submit_groups(w, n, requests, nullptr, tickets);
+}
+
+int mgx_plan_submit_groups(mgx_world *w, uint32_t n, const mgx_plan_request *requests, const uint32_t *groups, uint64_t *tickets) {
     MGX_ENTER(w);
     if (!w || (n && (!requests || !tickets))) return fail(MGX_ERR_INVALID, "null argument");
     mgx_world::Planner &p = w->planner;
@@ -343,10 +395,12 @@ int mgx_plan_submit(mgx_world *w, uint32_t n, const mgx_plan_request *requests, 
     if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "the global planner runs on unsharded worlds");
     for (uint32_t i = 0; i < n; i++)
         if (!plan_request_finite(requests[i])) return fail(MGX_ERR_INVALID, "request %u: a coordinate is not finite", i);
+    for (uint32_t i = 0; groups && i < n; i++)
+        if (groups[i] >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "request %u: group %u beyond %u", i, groups[i], MGX_GROUPS_MAX - 1);
     PlanPool &pl = p.pool;
     if ((uint64_t)pl.book.pending() + n > pl.book.max_slots()) return fail(MGX_ERR_INVALID, "more than %u requests pending", pl.book.max_slots());
     std::vector<uint32_t> slots;
-    const int rc = plan_pool_submit(pl, p.params, w->stream, n, requests, slots);
+    const int rc = plan_pool_submit(pl, p, w->stream, n, requests, groups, slots);
     if (rc != MGX_OK) return rc;
     for (uint32_t i = 0; i < n; i++) tickets[i] = pl.book.slots[slots[i]].ticket;
     return MGX_OK;
@@ -387,6 +441,7 @@ int mgx_plan_collect(mgx_world *w, uint32_t flags, uint32_t capacity, mgx_plan_d
         if (d.result.n_points > point_capacity - np) break;  // (it stays for the next call)
         d.ticket = ticket;
         d.slices = slices;
+        d.group = pl.slot_group[slot];
         plan_pool_points(pl, slot, cap, d.result, path_xy);
         np += d.result.n_points;
         done[nd++] = d;
@@ -402,6 +457,69 @@ int mgx_plan_cancel(mgx_world *w, uint64_t ticket) {
     if (!w) return fail(MGX_ERR_INVALID, "null world");
     (void)plan_pool_poll(w->planner.pool);
     if (!w->planner.pool.book.cancel(ticket)) return fail(MGX_ERR_INVALID, "ticket %llu is not pending", (unsigned long long)ticket);
+    return MGX_OK;
+}
+
+int mgx_planner_set_group_params(mgx_world *w, uint32_t group, const mgx_plan_params *params) {
+    MGX_ENTER(w);
+    if (!w) return fail(MGX_ERR_INVALID, "null world");
+    mgx_world::Planner &p = w->planner;
+    if (!p.enabled) return fail(MGX_ERR_STATE, "%s", PLAN_OFF);
+    if (group >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "group %u beyond %u", group, MGX_GROUPS_MAX - 1);
+    mgx_plan_params q = params ? *params : p.params;
+    if (params) {
+        const int rc = plan_params_check(q);
+        if (rc != MGX_OK) return rc;
+        if ((q.max_nodes && q.max_nodes != p.params.max_nodes) || (q.iterations_per_launch && q.iterations_per_launch != p.params.iterations_per_launch))
+            return fail(MGX_ERR_INVALID, "max_nodes and iterations_per_launch are the launch's: 0, or the world's %u and %u", p.params.max_nodes,
+                        p.params.iterations_per_launch);
+        if (q.sample_half_extent == 0.f) q.sample_half_extent = PLAN_DEFAULT_HALF_EXTENT;
+        q.max_nodes = p.params.max_nodes;
+        q.iterations_per_launch = p.params.iterations_per_launch;
+    }
+    if (p.pool.book.pending())
+        return fail(MGX_ERR_STATE, "%u requests are pending (mgx_plan_collect, mgx_plan_cancel): a set does not change under them", p.pool.book.pending());
+    mgx_world::Planner::Sets &s = p.sets;
+    if (!params) {
+        if (s.of(group)) s.set_of[group] = 0;
+        return MGX_OK;
+    }
+    // the group's row: the one it had, or a new one — in a table that grows by doubling (nothing in flight reads it: no request
+    // pends, and mgx_plan_paths leaves none running)
+    const bool fresh = s.row_of.empty() || s.row_of[group] == 0;
+    const size_t rows = s.params.size() + (fresh ? 1 : 0);
+    if (rows > s.dev_cap) {
+        size_t cap = std::max<size_t>(16, s.dev_cap);
+        while (cap < rows) cap *= 2;
+        PlanSetDev *grown = nullptr;
+        HIP_TRY(hipStreamSynchronize(w->stream));
+        HIP_TRY(hipMalloc((void **)&grown, sizeof(PlanSetDev) * cap));
+        if (s.dev) {
+            const hipError_t e = hipMemcpyAsync(grown, s.dev, sizeof(PlanSetDev) * s.params.size(), hipMemcpyDeviceToDevice, w->stream);
+            if (e != hipSuccess) { (void)hipFree(grown); HIP_TRY(e); }
+            HIP_TRY(hipStreamSynchronize(w->stream));
+            (void)hipFree(s.dev);
+        }
+        s.dev = grown;
+        s.dev_cap = cap;
+    }
+    const size_t row = fresh ? s.params.size() : s.row_of[group] - 1;
+    const PlanSetDev g = plan_set_dev(q);
+    HIP_TRY(hipMemcpyAsync(s.dev + row, &g, sizeof(g), hipMemcpyHostToDevice, w->stream));
+    HIP_TRY(hipStreamSynchronize(w->stream));  // (the row is read from this frame)
+    if (s.row_of.empty()) { s.row_of.assign(MGX_GROUPS_MAX, 0u); s.set_of.assign(MGX_GROUPS_MAX, 0u); }
+    if (fresh) { s.params.push_back(q); s.row_of[group] = (uint32_t)s.params.size(); }
+    else s.params[row] = q;
+    s.set_of[group] = s.row_of[group];
+    return MGX_OK;
+}
+
+int mgx_planner_group_params(mgx_world *w, uint32_t group, mgx_plan_params *out) {
+    MGX_ENTER_SCHEDULE(w);
+    if (!w || !out) return fail(MGX_ERR_INVALID, "null argument");
+    if (!w->planner.enabled) return fail(MGX_ERR_STATE, "%s", PLAN_OFF);
+    if (group >= MGX_GROUPS_MAX) return fail(MGX_ERR_INVALID, "group %u beyond %u", group, MGX_GROUPS_MAX - 1);
+    *out = plan_params_of(w->planner, group);
     return MGX_OK;
 }
 

@@ -927,6 +927,25 @@ struct mgx_world {
         mgx_plan_params params{};  // defaults filled in
         EnvMap map;
         uint32_t tick_budget = 0;  // mgx_planner_set_tick_budget (a setting of the world: mgx_planner_enable keeps it)
+        // the groups' parameter sets (mgx_planner_set_group_params): a group that has ever had one keeps its row of the device
+        // table; set_of[group] is the index its requests carry (row + 1), 0 while it runs under the world's parameters
+        struct Sets {
+            std::vector<uint32_t> set_of;           // [MGX_GROUPS_MAX] once a set exists; empty: no group has one
+            std::vector<uint32_t> row_of;           // [MGX_GROUPS_MAX] the group's row + 1, kept when its set is taken back
+            std::vector<mgx_plan_params> params;    // per row, defaults filled in
+            PlanSetDev *dev = nullptr;              // device memory, [dev_cap] rows
+            size_t dev_cap = 0;
+            Sets() = default;
+            Sets(const Sets &) = delete;
+            Sets &operator=(const Sets &) = delete;
+            ~Sets() { release(); }
+            void release() {  // (the caller has synchronised the stream)
+                if (dev) (void)hipFree(dev);
+                dev = nullptr; dev_cap = 0;
+                set_of.clear(); row_of.clear(); params.clear();
+            }
+            uint32_t of(uint32_t group) const { return group < set_of.size() ? set_of[group] : 0u; }
+        } sets;
         // a pool: bookkeeping in `book` (mgx_plan_pool.h), the slots' arrays a block at a time — trees and node paths in device
         // memory, states and points host-mapped — so that nothing a pending request uses ever moves; the table of blocks, the
         // completion log and the launches' active lists are host-mapped
@@ -943,6 +962,9 @@ struct mgx_world {
             std::vector<List> lists;
             int cur = -1;                    // the list the running slots were last written to
             uint32_t cur_n = 0;
+            bool cur_sets = false;           // a slot of that list names a parameter set: its launches take the table of sets
+            std::vector<uint32_t> slot_group, slot_set;  // per slot: the group its request was submitted under (mgx_plan_done::group),
+                                                         // and the parameter set it names (PlanState::set)
             hipEvent_t ev = nullptr;         // behind the last slice
             uint64_t ev_seq = 0;
             Pool(uint32_t slots_per_block, uint32_t max_blocks) : book(slots_per_block, max_blocks) {}
@@ -959,7 +981,8 @@ struct mgx_world {
                 if (log_count) (void)hipFree(log_count);
                 if (ev) (void)hipEventDestroy(ev);
                 table = nullptr; log = nullptr; log_count = nullptr; ev = nullptr;
-                log_cap = 0; log_taken = 0; cur = -1; cur_n = 0; ev_seq = 0;
+                log_cap = 0; log_taken = 0; cur = -1; cur_n = 0; ev_seq = 0; cur_sets = false;
+                slot_group.clear(); slot_set.clear();
                 book.drop();
             }
         };

@@ -16,7 +16,15 @@ grouped search holds per group (mission_tick_begin_groups with one radius per me
 (set_group_enabled before the member's first robot: mgx_set_group_enabled) and the four factor sigmas (set_group_sigmas, likewise:
 mgx_set_group_sigmas).  The per-robot observers — environment
 collisions, goal areas, the run metrics — do not look at the group: the first member switches them on for the world, and every
-member reads its own robots' part."""
+member reads its own robots' part.
+
+The global planner (global_planner="sliced"): the world has ONE pool of requests, and a launch runs every request of it.  Each
+member's `rrt.*` is a parameter set of its group (planner_set_group_params: mgx_planner_set_group_params — member 0's is the
+world's, a member that agrees with it sets nothing); a member submits its requests under its group, and per tick the ensemble
+drains the pool ONCE (one plan_collect that waits), routes what has ended to the members by group and ticket, and applies every
+member's new paths in ONE apply_global_paths over the union of their robots; the mission tick's one slice advances them all.
+global_planner="host" plans every member's requests with the host restatement under the member's own parameters and shares only
+that one apply."""
 import copy
 
 import numpy as np
@@ -26,7 +34,12 @@ from . import hostlib
 from .sim import Simulation
 from .world import group_steps
 
-UNSUPPORTED = ("global_planner",)
+UNSUPPORTED = ("global_planner",)   # the options whose value True (the synchronous form) an Ensemble refuses
+# what a member's Simulation may ask of the world's planner; the view offers each only where the world does
+PLANNER_CALLS = ("planner_enable", "planner_set_tick_budget", "plan_submit", "plan_collect", "plan_cancel", "plan_pending", "set_idle",
+                 "apply_global_paths")
+# rrt.* of a member's config: a parameter set of its group where the world takes one per group
+RRT_KEYS = ("step-size", "neighbourhood-radius", "collision-radius", "max-iterations", "smoothing.enabled", "smoothing.max-iterations")
 # the observers an Ensemble runs on the device, and what the world has to offer for each
 OBSERVERS = (("environment_collisions", "env_collisions_enable"), ("goal_areas", "goal_areas_enable"), ("device_metrics", "track_metrics_enable"))
 ENV_EVENTS_PER_MEMBER = 262144   # the room a run of its own has for environment-collision events (mgx_env_collisions_enable's default)
@@ -42,10 +55,22 @@ def _member_sigmas(sc):
     return {k: p["sigma_" + k] for k in SIGMAS}
 
 
-def _shared_settings(sc, per_group_kinds=False, per_group_sigmas=False):
+def _rrt_settings(cfg):
+    """rrt.* as (key, value), in the order of RRT_KEYS"""
+    out = []
+    for key in RRT_KEYS:
+        v = cfg["rrt"]
+        for part in key.split("."):
+            v = v[part]
+        out.append(("rrt." + key, v))
+    return out
+
+
+def _shared_settings(sc, per_group_kinds=False, per_group_sigmas=False, rrt_once=False):
     """everything the world holds once, as (key, value) in the order it is compared.  per_group_kinds: the world takes
     gbp.factors-enabled per group (mgx_set_group_enabled) — all of it but the inter-robot kind, which stays the world's.
-    per_group_sigmas: it takes the four gbp.sigma-factor-* per group as well (mgx_set_group_sigmas)"""
+    per_group_sigmas: it takes the four gbp.sigma-factor-* per group as well (mgx_set_group_sigmas).  rrt_once: the engine's
+    planner runs the members' requests and takes no parameter set per group, so rrt.* is held once as well"""
     cfg = sc["config"]
     out = [("params." + k, v) for k, v in _config.world_params(cfg).items()
            if not (per_group_kinds and k == "enable_mask") and not (per_group_sigmas and k in tuple("sigma_" + n for n in SIGMAS))]
@@ -56,6 +81,8 @@ def _shared_settings(sc, per_group_kinds=False, per_group_sigmas=False):
             ("robot.planning-horizon", cfg["robot"]["planning-horizon"]), ("simulation.hz", cfg["simulation"]["hz"]),
             ("simulation.despawn-robot-when-final-waypoint-reached", cfg["simulation"]["despawn-robot-when-final-waypoint-reached"]),
             ("environment", sc["environment"])]
+    if rrt_once:
+        out += _rrt_settings(cfg)
     return out
 
 
@@ -70,7 +97,14 @@ class _MemberWorld:
         self.coll_events = []    # this member's collision events so far, member ids, in (pass, a, b) order
         self.env_events = []     # ... and its environment-collision events, in (pass, robot, collider) order
         self.samples = []        # this member's tracker samples not taken yet
+        self.plans_done = []     # this member's requests that have ended and are not taken yet, in the world's order
         self.reserved = 0
+
+    def __getattr__(self, name):
+        # the planner's side of the world, offered only where the world offers it (Simulation asks with hasattr)
+        if name in PLANNER_CALLS and hasattr(self._e.world, name):
+            return getattr(self, "_" + name)
+        raise AttributeError(name)
 
     # -- set up once for the world -------------------------------------------------------------------------------------------
     def set_environment(self, env):
@@ -183,6 +217,54 @@ class _MemberWorld:
             out[k] = s
         return out, len(mine), dropped, (dist[self.ids] if len(self.ids) else np.zeros(0))
 
+    # -- the global planner: one pool and one apply for the world, in member ids and the member's group ---------------------------
+    def _planner_enable(self, env, params=None):
+        """member 0 enables the world's planner with its parameters; a member whose parameters differ from member 0's sets its
+        group's set (members that agree leave the world as it was)"""
+        e = self._e
+        if self._group == 0:
+            e.world.planner_enable(env, params)
+            e._plan_params = None if env is None else dict(params)
+        elif env is not None and dict(params) != e._plan_params:
+            if not hasattr(e.world, "planner_set_group_params"):
+                raise NotImplementedError("Ensemble: members that differ in their planner's parameters need an engine world that offers "
+                                          "planner_set_group_params")
+            e.world.planner_set_group_params(self._group, params)
+
+    def _planner_set_tick_budget(self, iterations):
+        if self._group == 0:
+            self._e.world.planner_set_tick_budget(iterations)
+
+    def _plan_submit(self, requests):
+        tickets = self._e.world.plan_submit(requests, groups=[self._group] * len(requests))
+        self._e._plan_owner.update((t, self._group) for t in tickets)
+        return tickets
+
+    def _plan_collect(self, wait=False, capacity=64, point_capacity=None):
+        """this member's requests that have ended (the ensemble drains the world's pool and routes by group and ticket)"""
+        self._e._drain_plans(wait)
+        out, self.plans_done = self.plans_done[:int(capacity)], self.plans_done[int(capacity):]
+        return out
+
+    def _plan_cancel(self, ticket):
+        if self._e._plan_owner.get(ticket) != self._group:
+            raise hostlib.MgxError(f"ticket {ticket} is not pending in member {self._group}")
+        held = [r for r in self.plans_done if r["ticket"] == ticket]
+        if held:   # (drained already: the world has handed it out)
+            self.plans_done.remove(held[0])
+        else:
+            self._e.world.plan_cancel(ticket)
+        del self._e._plan_owner[ticket]
+
+    def _plan_pending(self):
+        return sum(1 for g in self._e._plan_owner.values() if g == self._group)
+
+    def _set_idle(self, robot, idle):
+        self._e.world.set_idle(self.ids[robot], idle)
+
+    def _apply_global_paths(self, robots, paths, means, **kwargs):
+        self._e.world.apply_global_paths([self.ids[int(r)] for r in robots], paths, means, **kwargs)
+
     # -- the ensemble's -----------------------------------------------------------------------------------------------------------
     def mission_tick_begin(self, *args, **kwargs):
         raise RuntimeError("a member of an Ensemble does not tick on its own: Ensemble.tick()")
@@ -218,13 +300,17 @@ class Ensemble:
         """scenarios: one scenario dict per member (config.load_scenario, tests/golden/scenarios.json); member m's robots are in
         group m of `world`, a fresh World made with config.world_params of any of them.  The members may differ in
         simulation.prng-seed, robot.communication.failure-rate, robot.communication.radius, gbp.iteration-schedule,
-        gbp.factors-enabled.{dynamic, obstacle, tracking}, gbp.sigma-factor-{dynamics, interrobot, obstacle, tracking} (and max-time) and in their formations; everything the world holds once must be equal (ValueError names the first key that differs; a world
-        that takes no radius, no schedule, no enabled kinds or no sigmas per group holds that once, too; gbp.factors-enabled.interrobot is the
-        world's always).  simulation_options go to every member's Simulation, so the members share them —
+        gbp.factors-enabled.{dynamic, obstacle, tracking}, gbp.sigma-factor-{dynamics, interrobot, obstacle, tracking},
+        rrt.* (and max-time) and in their formations; everything the world holds once must be equal (ValueError names the first key that differs; a world
+        that takes no radius, no schedule, no enabled kinds, no sigmas or — under global_planner="sliced" — no planner parameters
+        per group holds that once, too; gbp.factors-enabled.interrobot is the world's always).  simulation_options go to every member's Simulation, so the members share them —
         goal_areas among them.  An Ensemble runs device missions with device robot-robot collisions and device trackers, and on
         request the device's other observers: environment_collisions=True, goal_areas, device_metrics (with sample_log=False if
-        asked).  Still refused, with NotImplementedError: global_planner (and so rrt-star formations) — a per-group many-tick run
-        and per-group planning are not part of the engine — and every option that needs each tick's Transforms on the host:
+        asked).  global_planner="sliced" (with plan_budget and planner_overrides, shared like the rest) runs rrt-star formations on
+        the engine's planner — one pool, one collect, one apply and one slice per tick for all members — and "host" on the
+        restatement.  Still refused, with NotImplementedError: global_planner=True (a synchronous mgx_plan_paths per member would
+        hold every member's ticks for the slowest plan), rrt-star formations without a planner, and every option that needs each
+        tick's Transforms on the host:
         environment_collisions="host", device_goal_areas=False, device_missions / device_collisions / device_trackers = False.
         masked_resident is the Ensemble's own (no Simulation sees it): True lets a world whose members differ in
         gbp.factors-enabled or in their sigmas run the ticks they share a schedule in as resident launches (World.set_group_resident) — same
@@ -234,10 +320,16 @@ class Ensemble:
             raise ValueError("an Ensemble needs at least one scenario")
         if len(scenarios) > hostlib.GROUPS_MAX:
             raise ValueError(f"an Ensemble has at most {hostlib.GROUPS_MAX} members")
+        planner = simulation_options.get("global_planner")
         for opt in UNSUPPORTED:
-            if simulation_options.get(opt):
-                raise NotImplementedError(f"Ensemble: {opt} is not supported (the engine plans and runs many ticks for ONE group: mgx_mission_run, "
-                                          "mgx_plan_paths)")
+            if simulation_options.get(opt) is True:
+                raise NotImplementedError(f"Ensemble: {opt}=True is not supported (a synchronous mgx_plan_paths per member would hold every "
+                                          f'member\'s ticks for the length of the slowest plan); {opt}="sliced" lets the plans ride the ticks')
+        if planner == "sliced":
+            for needs in ("planner_enable", "plan_submit", "plan_collect", "planner_set_tick_budget", "apply_global_paths"):
+                if not hasattr(world, needs):
+                    raise NotImplementedError(f'Ensemble: global_planner "sliced" needs an engine world that offers {needs} (the plans ride the '
+                                              "device's ticks)")
         for opt in ("device_missions", "device_collisions", "device_trackers", "device_goal_areas"):
             if simulation_options.get(opt) is False:
                 raise NotImplementedError(f"Ensemble: {opt}=False is not supported (the members share the device's passes; a host pass needs every "
@@ -249,15 +341,18 @@ class Ensemble:
             if simulation_options.get(opt) and not hasattr(world, needs):
                 raise NotImplementedError(f"Ensemble: {opt} needs an engine world that offers {needs} (the pass runs on the device)")
         for m, sc in enumerate(scenarios):
-            if any(f["planning-strategy"] != "only-local" for f in sc["formation"]["formations"]):
-                raise NotImplementedError(f"Ensemble: member {m} has an rrt-star formation; the global planner is not supported in this version")
+            if planner is None and any(f["planning-strategy"] != "only-local" for f in sc["formation"]["formations"]):
+                raise NotImplementedError(f'Ensemble: member {m} has an rrt-star formation and no global planner was asked for (global_planner='
+                                          '"sliced" or "host")')
         per_group_radius = hasattr(world, "neighbours_groups")   # (the engine's grouped search: one comms radius per group)
         per_group_steps = hasattr(world, "group_schedule_stats")  # (mgx_mission_tick_end_groups: one iteration schedule per group)
         per_group_kinds = hasattr(world, "set_group_enabled")     # (mgx_set_group_enabled: dynamic, obstacle and tracking per group)
         per_group_sigmas = hasattr(world, "set_group_sigmas")     # (mgx_set_group_sigmas: the four factor sigmas per group)
+        # (mgx_planner_set_group_params: rrt.* per group; the host restatement plans each member under its own anyway)
+        rrt_once = planner == "sliced" and not hasattr(world, "planner_set_group_params")
 
         def shared(sc):
-            return (_shared_settings(sc, per_group_kinds, per_group_sigmas) + ([] if per_group_steps else [("gbp.iteration-schedule", sc["config"]["gbp"]["iteration-schedule"])]) +
+            return (_shared_settings(sc, per_group_kinds, per_group_sigmas, rrt_once) + ([] if per_group_steps else [("gbp.iteration-schedule", sc["config"]["gbp"]["iteration-schedule"])]) +
                     ([] if per_group_radius else [("robot.communication.radius", sc["config"]["robot"]["communication"]["radius"])]))
         first = shared(scenarios[0])
         for m, sc in enumerate(scenarios[1:], 1):
@@ -280,6 +375,8 @@ class Ensemble:
         self._log_bound = 0       # samples the log holds at the most since it was last drained
         self._dist = np.zeros(0)
         self._clock = None        # the tick the device's tracker clock names
+        self._plan_params = None  # the planner's parameters as member 0 enabled it with: the world's
+        self._plan_owner = {}     # ticket -> member, of the requests submitted and neither taken by their member nor cancelled
         self.tick_no = 0
         # every member's enabled kinds, before its first robot is added (a mask equal to the world's is none: an ensemble whose
         # members agree stays the unmasked world it was)
@@ -332,11 +429,50 @@ class Ensemble:
             self.members_worlds[m].samples.append((s["tick"], r, s["span_ticks"], s["position"], s["velocity"]))
         return dropped, dist
 
+    def _drain_plans(self, wait):
+        """every request of the world's pool that has ended, to its member's list, in the world's order (slice number, ticket): at
+        most one collect that waits, whatever the pool holds"""
+        while self._plan_owner:
+            done = self.world.plan_collect(wait=wait, capacity=len(self._plan_owner))
+            wait = False          # (what the first look left behind for want of room has ended already)
+            for r in done:
+                g = self._plan_owner[r["ticket"]]
+                assert g == r["group"], "a request came back under another group than it was submitted under"
+                self.members_worlds[g].plans_done.append(r)
+            if not done:
+                break
+
+    def _apply_members_plans(self, active):
+        """the first pass of a tick: what the planner has finished for every member, and ONE apply_global_paths over the union of
+        the members' robots (the call synchronises the stream and repacks every path on the host: once, not once per member)"""
+        sliced = [m for m in active if m.sim._plan_tickets]
+        for m in sliced:
+            m.sim._cancel_dead_plans()
+        if any(m.sim._plan_tickets for m in sliced):
+            self._drain_plans(wait=True)
+        for m in sliced:
+            done, m._view.plans_done = m._view.plans_done, []
+            for r in done:
+                del self._plan_owner[r["ticket"]]
+            m.sim._take_plans(done)
+        ids, paths, means, per = [], [], [], []
+        for m in active:
+            mine, p, mu = m.sim._gather_plans()
+            if mine:
+                ids += [m._view.ids[r] for r in mine]
+                paths += p
+                means += mu
+                per.append((m, mine))
+        if ids:
+            self.world.apply_global_paths(ids, paths, np.stack(means), reset_tracking=True, route=True, activate=True)
+            for m, mine in per:
+                m.sim._plans_applied(mine)
+
     # -- a tick: the existing tick with the world-wide calls made once ---------------------------------------------------------------
     def tick(self):
         active = [m for m in self.members if not m.retired]
-        for m in active:          # every member applies its spawns, in member order
-            m.sim._apply_plans()
+        self._apply_members_plans(active)
+        for m in active:          # every member applies its spawns, in member order, and asks for its new robots' plans
             m.sim._spawn()
             m.sim._plan()
         ticking = [m for m in active if m.sim.robots]
@@ -395,6 +531,9 @@ class Ensemble:
         m.sim._tracks()
         m._export, m._metrics = m.sim.export(), m.sim.metrics()
         m.retired = True
+        for t in list(m.sim._plan_tickets):   # (its requests are never handed out: ended or not, their slots are free again)
+            m._view.plan_cancel(t)
+        m.sim._plan_tickets.clear()
         for r in m.sim.robots:
             if r["alive"]:
                 self.world.remove_robot(m._view.ids[r["id"]])

@@ -138,6 +138,10 @@ SYMBOLS = {
     "mgx_plan_collect": (C.c_int, [_V, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "mgx_plan_cancel": (C.c_int, [_V, C.c_uint64]),
     "mgx_plan_pending": (C.c_int, [_V, C.POINTER(C.c_uint32)]),
+    "mgx_planner_set_group_params": (C.c_int, [_V, C.c_uint32, C.c_void_p]),
+    "mgx_planner_group_params": (C.c_int, [_V, C.c_uint32, C.c_void_p]),
+    "mgx_plan_paths_groups": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "mgx_plan_submit_groups": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_robot_add": (C.c_int, [_V, C.POINTER(RobotDesc), C.POINTER(C.c_int32)]),
     "mgx_robot_remove": (C.c_int, [_V, C.c_int32]),
     "mgx_ir_connect": (C.c_int, [_V, C.c_int32, C.c_int32, C.c_uint64]),
@@ -540,7 +544,7 @@ PLAN_WAIT = 1  # MGX_PLAN_WAIT
 def plan_done_dtype():
     """numpy view of an array of mgx_plan_done"""
     import numpy as np
-    return np.dtype([("ticket", np.uint64), ("slices", np.uint32), ("reserved", np.uint32), ("result", plan_result_dtype())])
+    return np.dtype([("ticket", np.uint64), ("slices", np.uint32), ("group", np.uint32), ("result", plan_result_dtype())])
 
 
 def env_colliders(env, fma=None):

@@ -392,9 +392,17 @@ class Simulation:
         every robot whose request succeeded, in one call"""
         if self._plan_tickets:
             self._collect_plans()
+        ids, paths, means = self._gather_plans()
+        if ids:
+            self.w.apply_global_paths(ids, paths, np.stack(means), reset_tracking=True, route=True, activate=True)
+            self._plans_applied(ids)
+
+    def _gather_plans(self):
+        """what is ready goes into the request log, and the plans that succeeded for robots still alive come back as (robot ids,
+        paths, means): the arguments of ONE apply_global_paths — this run's own (_apply_plans), or an Ensemble's for all its members"""
         ready, self._plans_ready = self._plans_ready, []
         if not ready:
-            return
+            return [], [], []
         from .driver import global_path_plan
         rb = self.cfg["robot"]
         ids, paths, means = [], [], []
@@ -409,29 +417,36 @@ class Simulation:
             paths.append(np.ascontiguousarray(wps[:, :2]))
             means.append(m)
             me["waypoints"], me["target"], me["idle"] = [w.copy() for w in wps], 1, False
-        if ids:
-            self.w.apply_global_paths(ids, paths, np.stack(means), reset_tracking=True, route=True, activate=True)
-            if self._dev_metrics:  # (the robots were Idle so far: no sample was measured against the route this one replaces)
-                for rid in ids:
-                    self.w.track_metrics_set_route(rid, self._route(self.robots[rid]))
+        return ids, paths, means
+
+    def _plans_applied(self, ids):
+        """behind the apply_global_paths that took these robots' plans"""
+        if self._dev_metrics:  # (the robots were Idle so far: no sample was measured against the route this one replaces)
+            for rid in ids:
+                self.w.track_metrics_set_route(rid, self._route(self.robots[rid]))
 
     def _collect_plans(self):
         """sliced: the requests that have ended by the slices enqueued so far -> _plans_ready; a robot that is gone has its
         request cancelled, a request that failed goes in again with the stream where the attempt left it"""
-        for t in [t for t, q in self._plan_tickets.items() if not self.robots[q[0]]["alive"]]:
-            self.w.plan_cancel(t)
-            del self._plan_tickets[t]
-        again = []
+        self._cancel_dead_plans()
         while self._plan_tickets:
             done = self.w.plan_collect(wait=True, capacity=len(self._plan_tickets))
             if not done:
                 break
-            for r in done:
-                rid, start, end = self._plan_tickets.pop(r["ticket"])
-                self._plans_ready.append((rid, r))
-                if r["status"] != 0:
-                    again.append((rid, start, end, r["wyrand_state"]))
-        self._plan_requests += again  # (submitted by this tick's _plan, with the robots that spawn in it)
+            self._take_plans(done)
+
+    def _cancel_dead_plans(self):
+        for t in [t for t, q in self._plan_tickets.items() if not self.robots[q[0]]["alive"]]:
+            self.w.plan_cancel(t)
+            del self._plan_tickets[t]
+
+    def _take_plans(self, done):
+        """requests of this run that have ended, in the order the world handed them out"""
+        for r in done:
+            rid, start, end = self._plan_tickets.pop(r["ticket"])
+            self._plans_ready.append((rid, r))
+            if r["status"] != 0:  # (submitted again by this tick's _plan, with the robots that spawn in it)
+                self._plan_requests.append((rid, start, end, r["wyrand_state"]))
 
     def _spawn(self):
         for sp in self.spawners:

@@ -745,34 +745,70 @@ class World:
             return
         from .environment import _Desc
         d = _Desc(env)
-        p = hostlib.PlanParams(float(params["step_size"]), float(params["neighbourhood_radius"]), float(params["collision_radius"]),
-                               int(params["max_iterations"]), 1 if params.get("smoothing_enabled") else 0,
-                               int(params.get("smoothing_max_iterations", 0)), float(params.get("smoothing_step", 0.0)),
-                               float(params.get("sample_half_extent", 0.0)), int(params.get("max_nodes", 0)),
-                               int(params.get("iterations_per_launch", 0)))
+        p = self._plan_params(params)
         self._chk(self._L.mgx_planner_enable(self._w, C.byref(d.desc), C.byref(p)))
 
-    def plan_paths_raw(self, requests, point_capacity):
-        """mgx_plan_paths as it is: requests a structured array (hostlib.plan_request_dtype) -> (status code, results, points
-        [point_capacity, 2] f32, all points); nothing is raised"""
+    @staticmethod
+    def _plan_params(params):
+        """a dict as global_planner.params makes it -> mgx_plan_params"""
+        return hostlib.PlanParams(float(params["step_size"]), float(params["neighbourhood_radius"]), float(params["collision_radius"]),
+                                  int(params["max_iterations"]), 1 if params.get("smoothing_enabled") else 0,
+                                  int(params.get("smoothing_max_iterations", 0)), float(params.get("smoothing_step", 0.0)),
+                                  float(params.get("sample_half_extent", 0.0)), int(params.get("max_nodes", 0)),
+                                  int(params.get("iterations_per_launch", 0)))
+
+    def planner_set_group_params(self, group, params):
+        """from the next submit on, requests of `group` run under `params` (a dict as planner_enable takes it; max_nodes and
+        iterations_per_launch absent, 0 or the world's); None: the world's parameters again.  Raises while requests are pending
+        (mgx_planner_set_group_params)"""
+        p = None if params is None else self._plan_params(params)
+        self._chk(self._L.mgx_planner_set_group_params(self._w, int(group), None if p is None else C.addressof(p)))
+
+    def planner_group_params(self, group):
+        """what a request of `group` would run under — its own set, or the world's with the defaults filled in — as a dict of the
+        fields of mgx_plan_params (mgx_planner_group_params)"""
+        p = hostlib.PlanParams()
+        self._chk(self._L.mgx_planner_group_params(self._w, int(group), C.addressof(p)))
+        out = {name: getattr(p, name) for name, _ in hostlib.PlanParams._fields_}
+        out["smoothing_enabled"] = bool(out["smoothing_enabled"])
+        return out
+
+    @staticmethod
+    def _plan_groups(groups, n):
+        """one group per request as the engine reads it; None stays None (group 0 for every request)"""
+        if groups is None:
+            return None
+        g = np.ascontiguousarray(groups, dtype=np.int64)
+        if g.shape != (n,):
+            raise ValueError("groups: one group per request")
+        if n and (g.min() < 0 or g.max() > 0xffffffff):
+            raise ValueError("groups: a group index is not a 32-bit count")
+        return g.astype(np.uint32)
+
+    def plan_paths_raw(self, requests, point_capacity, groups=None):
+        """mgx_plan_paths_groups as it is: requests a structured array (hostlib.plan_request_dtype), groups None or one per request
+        -> (status code, results, points [point_capacity, 2] f32, all points); nothing is raised"""
         req = np.ascontiguousarray(requests, dtype=hostlib.plan_request_dtype())
+        g = self._plan_groups(groups, len(req))
         res = np.zeros(len(req), hostlib.plan_result_dtype())
         xy = np.full((max(int(point_capacity), 1), 2), np.nan, np.float32)
         total = C.c_uint32(0)
-        rc = self._L.mgx_plan_paths(self._w, len(req), req.ctypes.data, res.ctypes.data, xy.ctypes.data, int(point_capacity), C.byref(total))
+        rc = self._L.mgx_plan_paths_groups(self._w, len(req), req.ctypes.data, None if g is None else g.ctypes.data, res.ctypes.data,
+                                           xy.ctypes.data, int(point_capacity), C.byref(total))
         return rc, res, xy[:int(point_capacity)], int(total.value)
 
-    def plan_paths(self, requests):
+    def plan_paths(self, requests, groups=None):
         """requests: [(start (x, y), end (x, y), wyrand_state)] -> one dict per request (status, n_nodes, iterations, cost,
         wyrand_state, path [n, 2] f32 — empty unless the status is hostlib.PLAN_OK), as global_planner.plan_paths gives them.
-        One call, synchronous (mgx_plan_paths)."""
+        groups: one group per request — the parameter set it runs under (planner_set_group_params); None: group 0 for all.
+        One call, synchronous (mgx_plan_paths_groups)."""
         req = np.zeros(len(requests), hostlib.plan_request_dtype())
         for i, (s, e, state) in enumerate(requests):
             req["start"][i], req["end"][i], req["wyrand_state"][i] = s, e, int(state)
         room = 256 * max(len(req), 1)
-        rc, res, xy, total = self.plan_paths_raw(req, room)
+        rc, res, xy, total = self.plan_paths_raw(req, room, groups)
         if rc < 0 and total > room:  # (the counts came back: once more with room for them)
-            rc, res, xy, total = self.plan_paths_raw(req, total)
+            rc, res, xy, total = self.plan_paths_raw(req, total, groups)
         self._chk(rc)
         return [{"status": int(r["status"]), "n_nodes": int(r["n_nodes"]), "iterations": int(r["iterations"]),
                  "smoothing_iterations": int(r["smoothing_iterations"]), "cost": float(r["cost"]),
@@ -780,13 +816,15 @@ class World:
                 for r in res]
 
     # plans that ride the stream (include/mgx.h): submit returns at once, advance enqueues one slice, collect hands out what ended
-    def plan_submit(self, requests):
-        """requests: [(start (x, y), end (x, y), wyrand_state)] -> their tickets (mgx_plan_submit: nothing is launched or waited for)"""
+    def plan_submit(self, requests, groups=None):
+        """requests: [(start (x, y), end (x, y), wyrand_state)] -> their tickets; groups: one group per request, None: group 0 for
+        all (mgx_plan_submit_groups: nothing is launched or waited for)"""
         req = np.zeros(len(requests), hostlib.plan_request_dtype())
         for i, (s, e, state) in enumerate(requests):
             req["start"][i], req["end"][i], req["wyrand_state"][i] = s, e, int(state)
+        g = self._plan_groups(groups, len(req))
         tickets = np.zeros(len(req), np.uint64)
-        self._chk(self._L.mgx_plan_submit(self._w, len(req), req.ctypes.data, tickets.ctypes.data))
+        self._chk(self._L.mgx_plan_submit_groups(self._w, len(req), req.ctypes.data, None if g is None else g.ctypes.data, tickets.ctypes.data))
         return [int(t) for t in tickets]
 
     def plan_advance(self, iterations):
@@ -799,7 +837,7 @@ class World:
 
     def plan_collect(self, wait=False, capacity=64, point_capacity=None):
         """The requests that have ended, in the order of (slice number, ticket), each once: one dict per request as plan_paths gives
-        them, with `ticket`, `slices` and `smoothing_iterations` beside.  wait: first wait for the slices enqueued so far
+        them, with `ticket`, `slices`, `group` (the one it was submitted under) and `smoothing_iterations` beside.  wait: first wait for the slices enqueued so far
         (MGX_PLAN_WAIT); otherwise the call never blocks.  What does not fit into capacity / point_capacity stays for the next call."""
         capacity = int(capacity)
         room = 256 * max(capacity, 1) if point_capacity is None else int(point_capacity)
@@ -811,7 +849,7 @@ class World:
         out = []
         for d in done[:nd.value]:
             r = d["result"]
-            out.append({"ticket": int(d["ticket"]), "slices": int(d["slices"]), "status": int(r["status"]), "n_nodes": int(r["n_nodes"]),
+            out.append({"ticket": int(d["ticket"]), "slices": int(d["slices"]), "group": int(d["group"]), "status": int(r["status"]), "n_nodes": int(r["n_nodes"]),
                         "iterations": int(r["iterations"]), "smoothing_iterations": int(r["smoothing_iterations"]), "cost": float(r["cost"]),
                         "wyrand_state": int(r["wyrand_state"]),
                         "path": xy[int(r["first_point"]):int(r["first_point"]) + int(r["n_points"])].copy()})

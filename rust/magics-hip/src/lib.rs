@@ -313,6 +313,40 @@ impl World {
         check(unsafe { sys::mgx_plan_pending(self.raw, &mut n) })?;
         Ok(n)
     }
+    /// A parameter set per group (include/mgx.h): from the next submit on, requests of `group` run under `params`; `None` puts
+    /// the group back on the world's parameters.  Refused while requests are pending.
+    pub fn planner_set_group_params(&self, group: u32, params: Option<&sys::mgx_plan_params>) -> Result<(), MgxError> {
+        let p = params.map_or(std::ptr::null(), |q| q as *const sys::mgx_plan_params);
+        check(unsafe { sys::mgx_planner_set_group_params(self.raw, group, p) })
+    }
+    /// What a request of the group would run under: its own set, or the world's.
+    pub fn planner_group_params(&self, group: u32) -> Result<sys::mgx_plan_params, MgxError> {
+        let mut out = std::mem::MaybeUninit::<sys::mgx_plan_params>::zeroed();
+        check(unsafe { sys::mgx_planner_group_params(self.raw, group, out.as_mut_ptr()) })?;
+        Ok(unsafe { out.assume_init() })
+    }
+    /// `plan_submit` with one group per request (`mgx_plan_done.group` names it again).
+    pub fn plan_submit_groups(&self, requests: &[sys::mgx_plan_request], groups: &[u32]) -> Result<Vec<u64>, MgxError> {
+        assert!(requests.len() == groups.len());
+        let mut tickets = vec![0u64; requests.len()];
+        check(unsafe { sys::mgx_plan_submit_groups(self.raw, requests.len() as u32, requests.as_ptr(), groups.as_ptr(), tickets.as_mut_ptr()) })?;
+        Ok(tickets)
+    }
+    /// `mgx_plan_paths` with one group per request: (results, points); synchronous.
+    pub fn plan_paths_groups(&self, requests: &[sys::mgx_plan_request], groups: &[u32], point_capacity: u32)
+                             -> Result<(Vec<sys::mgx_plan_result>, Vec<[f32; 2]>), MgxError> {
+        assert!(requests.len() == groups.len());
+        let mut results: Vec<sys::mgx_plan_result> = Vec::with_capacity(requests.len());
+        let mut xy = vec![[0f32; 2]; point_capacity as usize];
+        let mut n_points = 0u32;
+        check(unsafe {
+            sys::mgx_plan_paths_groups(self.raw, requests.len() as u32, requests.as_ptr(), groups.as_ptr(), results.as_mut_ptr(),
+                                       xy.as_mut_ptr().cast(), point_capacity, &mut n_points)
+        })?;
+        unsafe { results.set_len(requests.len()) };
+        xy.truncate(n_points as usize);
+        Ok((results, xy))
+    }
 }
 
 /// Owner rank of every robot for a node of `n_ranks` GPUs (`mgx_shard_partition`: equal-count strips in (y, x) order).

@@ -249,7 +249,7 @@ pub const MGX_PLAN_WAIT: u32 = 1;
 pub struct mgx_plan_done {
     pub ticket: u64,
     pub slices: u32,
-    pub reserved: u32,
+    pub group: u32,
     pub result: mgx_plan_result,
 }
 
@@ -438,6 +438,10 @@ extern "C" {
     pub fn mgx_plan_collect(w: *mut mgx_world, flags: u32, capacity: u32, done: *mut mgx_plan_done, path_xy: *mut f32, point_capacity: u32, n_done: *mut u32, n_points: *mut u32) -> c_int;
     pub fn mgx_plan_cancel(w: *mut mgx_world, ticket: u64) -> c_int;
     pub fn mgx_plan_pending(w: *mut mgx_world, n: *mut u32) -> c_int;
+    pub fn mgx_planner_set_group_params(w: *mut mgx_world, group: u32, params: *const mgx_plan_params) -> c_int;
+    pub fn mgx_planner_group_params(w: *mut mgx_world, group: u32, out: *mut mgx_plan_params) -> c_int;
+    pub fn mgx_plan_paths_groups(w: *mut mgx_world, n: u32, requests: *const mgx_plan_request, groups: *const u32, results: *mut mgx_plan_result, path_xy: *mut f32, point_capacity: u32, n_points: *mut u32) -> c_int;
+    pub fn mgx_plan_submit_groups(w: *mut mgx_world, n: u32, requests: *const mgx_plan_request, groups: *const u32, tickets: *mut u64) -> c_int;
     pub fn mgx_schedule(kind: i32, n_internal: u8, n_external: u8, steps: *mut u8, capacity: u32) -> c_int;
     pub fn mgx_variable_timesteps(lookahead_horizon: u32, lookahead_multiple: u32, timesteps: *mut u32, capacity: u32) -> c_int;
 }

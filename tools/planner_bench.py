@@ -3,6 +3,7 @@
 (magics_amd/global_planner.py), on the Solo GP map.
 
     python tools/planner_bench.py [--requests 1,8,64] [--iterations 500,2000,8000] [--half-extent 125] [--reps 5] [--host-requests 2]
+                                  [--group-set]
 
     python tools/planner_bench.py --sliced [--ticks 120] [--pending 1,8,64] [--budgets 16,64,256]
 
@@ -16,7 +17,9 @@ of the same requests.
 Every request plans from the scenario's start to a goal no tree reaches (far outside the map), so each one runs exactly
 `--iterations` iterations and the tree size is what the sampler grows in them; seeds differ per request.  The device figure is the
 median wall time of `--reps` calls after one warm-up call; the restatement is timed on `--host-requests` of the requests and
-scaled to the burst (it plans one request after the other).  One JSON line per cell, then the table of the profile."""
+scaled to the burst (it plans one request after the other).  One JSON line per cell, then the table of the profile.
+--group-set (profiles/ensemble_planner.md): every request goes in under group 1, whose parameter set EQUALS the world's
+(mgx_planner_set_group_params), so the launch carries the table of sets and every workgroup reads its row: what the sets cost."""
 import argparse
 import json
 import os
@@ -36,6 +39,7 @@ ap.add_argument("--half-extent", type=float, default=125.0)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--host-requests", type=int, default=2)
 ap.add_argument("--slice", type=int, default=0, help="iterations_per_launch (0: the default, 1024)")
+ap.add_argument("--group-set", action="store_true", help="every request under a group set equal to the world's parameters")
 ap.add_argument("--sliced", action="store_true", help="the cost of a tick while plans ride it")
 ap.add_argument("--ticks", type=int, default=120)
 ap.add_argument("--pending", default="1,8,64")
@@ -129,13 +133,16 @@ rows = []
 for iters in [int(x) for x in a.iterations.split(",")]:
     p = gp.params_from_config(sc["config"], sample_half_extent=a.half_extent, max_iterations=iters, iterations_per_launch=a.slice)
     w.planner_enable(env, p)
+    if a.group_set:
+        w.planner_set_group_params(1, p)
     for n in [int(x) for x in a.requests.split(",")]:
         reqs = [(START, NOWHERE, 1000 + i) for i in range(n)]
-        res = w.plan_paths(reqs)  # warm-up (sizes the trees, grants the LDS)
+        groups = {"groups": [1] * n} if a.group_set else {}
+        res = w.plan_paths(reqs, **groups)  # warm-up (sizes the trees, grants the LDS)
         times = []
         for _ in range(a.reps):
             t0 = time.perf_counter()
-            res = w.plan_paths(reqs)
+            res = w.plan_paths(reqs, **groups)
             times.append(time.perf_counter() - t0)
         assert all(r["status"] == gp.PLAN_MAX_ITERATIONS and r["iterations"] == iters for r in res)
         nodes = statistics.mean(r["n_nodes"] for r in res)
@@ -144,7 +151,7 @@ for iters in [int(x) for x in a.iterations.split(",")]:
         ref = gp.plan_paths(env, reqs[:k], p)
         host = (time.perf_counter() - t0) / k * n
         assert all(r["n_nodes"] == d["n_nodes"] and r["wyrand_state"] == d["wyrand_state"] for r, d in zip(ref, res))
-        row = {"requests": n, "iterations": iters, "mean_nodes": round(nodes, 1), "device_ms": round(1e3 * statistics.median(times), 3),
+        row = {**({"group_set": True} if a.group_set else {}), "requests": n, "iterations": iters, "mean_nodes": round(nodes, 1), "device_ms": round(1e3 * statistics.median(times), 3),
                "device_us_per_iteration": round(1e6 * statistics.median(times) / iters, 3), "host_ms": round(1e3 * host, 1)}
         rows.append(row)
         print(json.dumps(row), flush=True)

@@ -15,19 +15,23 @@ sample is logged on the device and the robots' positions / velocities lists stay
 scenario's line then carries the arrivals per area and the throughput the reference's analyse-junction-scenario.py reads out of an
 export (robots that started within 50 s and arrived, per second).  --export DIR writes each scenario's export to DIR/<name>.json.
 --ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:INTERNAL:EXTERNAL,..]
-[--ensemble-tracking on,off] [--ensemble-sigma-tracking S1,S2,..] [--ensemble-masked-resident]
+[--ensemble-tracking on,off] [--ensemble-sigma-tracking S1,S2,..] [--ensemble-rrt-collision-radii R1,R2,..] [--ensemble-masked-resident]
 runs the cross product of ONE scenario — every seed with every failure rate, every comms radius, every GBP iteration schedule
 (KIND: centered, soon-as-possible, late-as-possible, interleave-evenly, half-beginning-half-end), gbp.factors-enabled.tracking
-on / off and every gbp.sigma-factor-tracking (default each: the scenario's own) — as one Ensemble (magics_amd/ensemble.py):
+on / off, every gbp.sigma-factor-tracking and every rrt.collision-radius (default each: the scenario's own) — as one Ensemble (magics_amd/ensemble.py):
 the members are robot groups of one world, one launch per schedule and one synchronisation per tick for all of them, each member
 identical to the same run alone.  One line per member — with --environment-collisions, --goal-areas and --metrics (with or
 without --no-sample-log) it carries the member's contacts, arrivals and the means of its run metrics; with --export DIR one
-export per member, DIR/<name>.seed<A>.rate<X>.radius<R>[.<kind>-<internal>-<external>][.tracking-<on|off>][.sigma-tracking<S>].json.  The global planner and host trackers do not run in an Ensemble.
+export per member, DIR/<name>.seed<A>.rate<X>.radius<R>[.<kind>-<internal>-<external>][.tracking-<on|off>][.sigma-tracking<S>][.rrt-collision-radius<R>].json.
+An Ensemble runs `planning-strategy: rrt-star` scenarios with --global-planner sliced (the members' plans ride the world's ticks,
+each member's rrt.* a parameter set of its group) or --global-planner host; the synchronous `device` mode and host trackers do
+not run in an Ensemble.
 --ensemble-masked-resident: members that differ in tracking on / off or in sigma-factor-tracking make the world masked; with this switch its ticks run as resident
 launches all the same (Ensemble(masked_resident=True), mgx_set_group_resident) — same results.
 usage: python tools/run_scenarios.py [--max-time S] [--goal-areas junction|FILE.json] [--export DIR] [--environment-collisions] [--host-trackers] [--metrics [--no-sample-log]] [--global-planner [device|host|sliced]]
            [--plan-budget N] [--planner-half-extent H] [--planner-max-iterations N]
-           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..] [--ensemble-tracking on,off] [--ensemble-sigma-tracking S1,S2,..] [--ensemble-masked-resident]]
+           [--ensemble-seeds A,B,.. [--ensemble-failure-rates X,Y,..] [--ensemble-comms-radii R1,R2,..] [--ensemble-schedules KIND:I:E,..] [--ensemble-tracking on,off] [--ensemble-sigma-tracking S1,S2,..] [--ensemble-rrt-collision-radii R1,R2,..]
+            [--ensemble-masked-resident]]
            [scenario-dir | name ...]"""
 import copy
 import json
@@ -71,7 +75,7 @@ if "--export" in args:
     i = args.index("--export")
     export_dir = args[i + 1]
     del args[i:i + 2]
-global_planner, overrides = None, {}
+global_planner, overrides, mode = None, {}, None
 if "--global-planner" in args:
     i = args.index("--global-planner")
     mode = args[i + 1] if i + 1 < len(args) and args[i + 1] in ("device", "host", "sliced") else None
@@ -125,22 +129,36 @@ if "--ensemble-sigma-tracking" in args:
     if any(not (0.0 < x < float("inf")) for x in ensemble_sigma_tracking):
         sys.exit("--ensemble-sigma-tracking: a list of positive finite sigmas")
     del args[i:i + 2]
+ensemble_rrt_radii = None
+if "--ensemble-rrt-collision-radii" in args:
+    i = args.index("--ensemble-rrt-collision-radii")
+    ensemble_rrt_radii = [config.f32(float(x)) for x in args[i + 1].split(",")]   # (f32 as the config file's own, parse_config)
+    if any(not (0.0 <= x < float("inf")) for x in ensemble_rrt_radii):
+        sys.exit("--ensemble-rrt-collision-radii: a list of finite radii, none negative")
+    del args[i:i + 2]
 ensemble_masked_resident = "--ensemble-masked-resident" in args
 if ensemble_masked_resident:
     args.remove("--ensemble-masked-resident")
-if (ensemble_rates or ensemble_radii or ensemble_schedules or ensemble_tracking or ensemble_sigma_tracking or ensemble_masked_resident) and not ensemble_seeds:
-    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii, --ensemble-schedules, --ensemble-tracking, --ensemble-sigma-tracking and --ensemble-masked-resident need --ensemble-seeds")
+if (ensemble_rates or ensemble_radii or ensemble_schedules or ensemble_tracking or ensemble_sigma_tracking or ensemble_rrt_radii or ensemble_masked_resident) and not ensemble_seeds:
+    sys.exit("--ensemble-failure-rates, --ensemble-comms-radii, --ensemble-schedules, --ensemble-tracking, --ensemble-sigma-tracking, "
+             "--ensemble-rrt-collision-radii and --ensemble-masked-resident need --ensemble-seeds")
+if ensemble_seeds and global_planner is True:
+    sys.exit("--ensemble-seeds: --global-planner " + ("device" if mode else "without a mode") + " plans synchronously, which would hold every member's "
+             "ticks for the slowest plan: it does not run in an Ensemble; --global-planner sliced does (or host, the restatement)")
+if ensemble_rrt_radii and not global_planner:
+    sys.exit("--ensemble-rrt-collision-radii needs --global-planner sliced or host")
+if ensemble_seeds and host_trackers:
+    sys.exit("--ensemble-seeds: host trackers do not run in an Ensemble (magics_amd/ensemble.py says why)")
 with open(os.path.join("tests", "golden", "scenarios.json"), encoding="utf-8") as f:
     known = json.load(f)
 if ensemble_seeds:
     from magics_amd import ensemble  # noqa: E402
     if len(args) != 1:
         sys.exit("--ensemble-seeds runs ONE scenario: name it")
-    if global_planner or host_trackers:
-        sys.exit("--ensemble-seeds: the global planner and host trackers do not run in an Ensemble (magics_amd/ensemble.py says why)")
     base = config.load_scenario(args[0]) if os.path.isdir(args[0]) else known[args[0]]
     members = []
-    for sigma_trk, tracking in [(s, t) for s in ensemble_sigma_tracking or [None] for t in ensemble_tracking or [None]]:
+    for rrt_radius, sigma_trk, tracking in [(c, s, t) for c in ensemble_rrt_radii or [None] for s in ensemble_sigma_tracking or [None]
+                                            for t in ensemble_tracking or [None]]:
         for schedule in ensemble_schedules or [None]:
             for radius in ensemble_radii or [base["config"]["robot"]["communication"]["radius"]]:
                 for rate in ensemble_rates or [base["config"]["robot"]["communication"]["failure-rate"]]:
@@ -155,10 +173,13 @@ if ensemble_seeds:
                             sc["config"]["gbp"]["factors-enabled"]["tracking"] = tracking
                         if sigma_trk is not None:
                             sc["config"]["gbp"]["sigma-factor-tracking"] = sigma_trk
+                        if rrt_radius is not None:
+                            sc["config"]["rrt"]["collision-radius"] = rrt_radius
                         members.append((seed, rate, radius, sc))
     t0 = time.perf_counter()
     e = ensemble.Ensemble([sc for *_, sc in members], World(config.world_params(base["config"])), environment_collisions=env_collisions,
-                          device_metrics=metrics, sample_log=not no_sample_log, goal_areas=goal_areas, masked_resident=ensemble_masked_resident)
+                          device_metrics=metrics, sample_log=not no_sample_log, goal_areas=goal_areas, masked_resident=ensemble_masked_resident,
+                          **({"global_planner": global_planner, "planner_overrides": overrides, "plan_budget": plan_budget} if global_planner else {}))
     e.run(max_time=max_time)
     wall = time.perf_counter() - t0
     stem = os.path.basename(os.path.normpath(base.get("name", args[0])))
@@ -172,6 +193,8 @@ if ensemble_seeds:
                           **({"schedule": f"{sch['schedule']}:{sch['internal']}:{sch['external']}"} if ensemble_schedules else {}),
                           **({"tracking": sc["config"]["gbp"]["factors-enabled"]["tracking"]} if ensemble_tracking else {}),
                           **({"sigma_tracking": sc["config"]["gbp"]["sigma-factor-tracking"]} if ensemble_sigma_tracking else {}),
+                          **({"rrt_collision_radius": sc["config"]["rrt"]["collision-radius"]} if ensemble_rrt_radii else {}),
+                          **({"plans": len(s._plan_log), "plans_failed": sum(q["status"] != 0 for q in s._plan_log)} if global_planner else {}),
                           "simulated_s": round(s.elapsed(), 1),
                           "robots": len(s.robots), "finished": len(done), "all_finished": s.finished(), "K": s.K,
                           "mean_distance": round(sum(trav) / max(1, len(trav)), 1),
@@ -188,6 +211,8 @@ if ensemble_seeds:
                 tail += ".tracking-on" if sc["config"]["gbp"]["factors-enabled"]["tracking"] else ".tracking-off"
             if ensemble_sigma_tracking:
                 tail += f".sigma-tracking{sc['config']['gbp']['sigma-factor-tracking']:g}"
+            if ensemble_rrt_radii:
+                tail += f".rrt-collision-radius{sc['config']['rrt']['collision-radius']:g}"
             with open(os.path.join(export_dir, f"{stem}.seed{seed}.rate{rate:g}.radius{radius:g}{tail}.json"), "w", encoding="utf-8") as f:
                 json.dump(m.export(), f)
     mixed_calls, mixed_launches, sat_out = e.world.group_schedule_stats()
