@@ -263,6 +263,9 @@ int mgx_set_enabled(mgx_world *w, uint32_t kind_mask);
 int mgx_set_safety_multiplier(mgx_world *w, double multiplier);
 int mgx_set_antenna(mgx_world *w, int32_t robot, int32_t active);
 int mgx_set_idle(mgx_world *w, int32_t robot, int32_t idle);
+/* The idle flag as the world holds it — set by mgx_set_idle, cleared by mgx_apply_global_paths' ACTIVATE, set by a mission
+ * tick's first half for a robot that ended a leg (MISSIONS OF SEVERAL LEGS): *idle = 0 / 1.  Host state: no synchronisation. */
+int mgx_get_idle(mgx_world *w, int32_t robot, int32_t *idle);
 
 /* update_failed_comms (robot.rs:1593-1601) writes every antenna once per tick: bulk form.
  * The Bernoulli draws stay with the caller (the reference uses Bevy's GlobalEntropy<WyRand>). */
@@ -539,7 +542,8 @@ int mgx_set_tracking_path(mgx_world *w, int32_t robot, const float *path_xy, uin
  * device mission (mgx_mission_set) takes the route path_i[1:] widened to f64 — target_index = 1 skips the first point — and its
  * next waypoint is that route's first; reach rules, Transform and time scale stay.
  * Refused as a whole, nothing changed: null arrays, a path outside 2 .. 65535 points, a robot that is not a live local one or
- * is listed twice (MGX_ERR_INVALID); ROUTE on a robot without a mission or whose mission is complete (MGX_ERR_STATE).
+ * is listed twice (MGX_ERR_INVALID); ROUTE on a robot without a mission or whose mission is complete (MGX_ERR_STATE) — a robot
+ * that waits between two legs (mgx_mission_legs_ended) is not complete: this call is its hand-over.
  * Which worlds take which path:
  *   - laid out (launched at least once, no robot / obstacle change pending), unsharded, and in none of the switching states
  *     (no factor kind ever switched at run time, no factors that still lack inbox keys): applied IN PLACE on the device by one
@@ -610,10 +614,33 @@ int mgx_tick(mgx_world *w, uint32_t n, const int32_t *robots, const double *wayp
  * advance (Mission::advance_to_next_waypoint, robot.rs:995-1005), it gets no prior update and its Transform does not move
  * (both systems skip it, robot.rs:2212, 2303); it still takes part in the neighbour search, the topology pass and the collision
  * passes, and sits out the sweeps.  mgx_apply_global_paths with MGX_GLOBAL_PATH_ROUTE | MGX_GLOBAL_PATH_ACTIVATE hands it its
- * route and wakes it up. */
+ * route and wakes it up.
+ *
+ * MISSIONS OF SEVERAL LEGS.  The reference's global-planner mission keeps all its taskpoints (Mission::global, robot.rs:862-908)
+ * and follows one planned route per pair of them: when a route ends with taskpoints left, Mission::next_route (robot.rs:966-993)
+ * does not complete the mission — it opens the route [taskpoint k, taskpoint k+1] and sets MissionState::Idle, progress_missions
+ * (robot.rs:578-633) plans it, and the completion handler (robot.rs:643-799) wakes the robot on the new path.  Here the device
+ * knows how many legs follow the route it holds (mgx_mission_desc.legs_after -> legs_left, an int32 per robot that the device
+ * counts down) and the HOST plans and hands over, as it does at spawn:
+ *   - a robot reaches the last waypoint of its route under the FINISH rule on every leg (Mission::next_waypoint_is_last is true
+ *     on the last waypoint of the newest route, robot.rs:943-948, 2119-2123);
+ *   - with legs_left > 0 that ends a LEG: legs_left -= 1, the mission is NOT complete (finished_tick stays -1), the next
+ *     waypoint index stays == the route's length — so the robot gets no prior update and its Transform does not move — and
+ *     the robot is reported beside the completions at the tick's one synchronisation;
+ *   - mgx_mission_tick_begin (every form) makes it idle (as mgx_set_idle(robot, 1): the flags and edge gates travel ahead of
+ *     this tick's sweeps and of its message counters) and lists it in mgx_mission_legs_ended, ascending ids, until the next
+ *     _begin.  It is not despawned, not counted in stats[2] and not listed by mgx_mission_finished; the grouped forms need
+ *     nothing more — the robot ids say which group;
+ *   - mgx_apply_global_paths with MGX_GLOBAL_PATH_ROUTE | MGX_GLOBAL_PATH_ACTIVATE is the hand-over of the next leg, exactly as
+ *     at spawn and in place where the world allows (mgx_layout_stats does not move): the route becomes path[1:], the next
+ *     waypoint its first, the robot Active; legs_left is not touched;
+ *   - with legs_left == 0 the route's end completes the mission: everything as without legs.
+ * While it waits the robot is idle and therefore not evaluated by reached_waypoint.  Missions do not migrate and sharded worlds
+ * have none, as before. */
 typedef struct mgx_mission_desc {
     uint32_t n_waypoints;         /* waypoints still to visit; the first one is the next target (>= 1)                 */
-    uint32_t reserved;
+    uint32_t legs_after;          /* further legs that follow this route (MISSIONS OF SEVERAL LEGS below); 0: the route's
+                                     last waypoint completes the mission (a word that was reserved and 0)              */
     const double *waypoints_xy;   /* [n][2]; compared as f32 (the reference's Vec2), used as f64 by the horizon prior   */
     uint32_t reach_var, finish_var;   /* variable tested against an intermediate / the final waypoint: 0 = current,
                                          K-1 = horizon (waypoint-reached-when-intersects / finished-when-intersects)   */
@@ -649,6 +676,9 @@ int mgx_mission_tick_begin_groups_radii(mgx_world *w, const float *comms_radii, 
 int mgx_mission_tick_end_groups(mgx_world *w, const uint8_t *antennas, double max_speed, double delta_t,
                                 uint32_t n_groups, const uint8_t *steps, const uint32_t *step_first);
 int mgx_mission_finished(mgx_world *w, int32_t *robots, uint32_t capacity, uint32_t *n);
+/* The robots that ended a leg with legs left in the last _begin (MISSIONS OF SEVERAL LEGS above), ascending ids, all groups:
+ * *n = how many, the first min(*n, capacity) of them in `robots` (may be NULL).  No synchronisation: _begin's own lies behind. */
+int mgx_mission_legs_ended(mgx_world *w, int32_t *robots, uint32_t capacity, uint32_t *n);
 /* MANY ticks in one call: what a headless run does between two spawns (the reference's FixedUpdate chain tick after tick,
  * robot.rs:85-108, with update_failed_comms' draws in between) without the caller's interpreter in the loop —
  *   for each tick:  mgx_mission_tick_begin;  one Bernoulli(failure_rate) draw per robot alive after the tick's despawns, id
@@ -660,6 +690,9 @@ int mgx_mission_finished(mgx_world *w, int32_t *robots, uint32_t capacity, uint3
  * Transform::translation of EVERY robot after the tick's move ([n_ticks][n_robots][3], may be NULL) and the draws
  * ([n_ticks][n_robots], 1 = on air, may be NULL).  stop_when_all_finished: returns behind the tick that completed the last
  * mission.  No robot may join during the call.  Identical to the same ticks issued one by one (tests/test_gpu_sim.py).
+ * The call also returns behind the first tick in which a robot ended a leg with legs left (MISSIONS OF SEVERAL LEGS): ticks_done
+ * says where, mgx_mission_legs_ended whose — the caller plans the next leg and calls again.  Such a robot is unfinished for
+ * stop_when_all_finished.  A world without legs never sees this.
  * ONE generator and ONE draw stream, also on a grouped world (ROBOT GROUPS): per-group many-tick runs are not part of this call. */
 typedef struct mgx_mission_run_desc {
     uint32_t n_ticks;
@@ -688,6 +721,9 @@ int mgx_mission_translations(mgx_world *w, float *translations, uint32_t capacit
 /* Transform::translation [n][3], next waypoint index (== the route's length once complete; -1: no mission) and the tick
  * at which each mission completed (-1 before) of every robot, id order; any pointer may be NULL.  Synchronises. */
 int mgx_mission_read(mgx_world *w, float *translations, int32_t *targets, int64_t *finished_tick);
+/* legs_left [n] of every robot, id order (0: no mission, or none left), as the device has counted them down.  Synchronises
+ * as mgx_mission_read does. */
+int mgx_mission_legs_read(mgx_world *w, int32_t *legs_left);
 
 /* ---- robot-robot collision bookkeeping on the device -------------------------------------------------------
  * update_robot_robot_collisions with the Free / Colliding state machine of CollisionHistory (planner/collisions.rs:72-140,

@@ -298,6 +298,7 @@ struct KeylessRec {
 // Missions on the device (the driver's reached_waypoint and Transform increment, robot.rs:2080-2176,2309-2335):
 // per robot (device index == robot id: unsharded worlds) its route, the next waypoint, the reached-when rules of
 // formation.yaml and the Bevy Transform it moves.
+constexpr unsigned int MISSION_EVENT_LEG = 0x80000000u;  // event list: the robot ended a leg (otherwise: completed its mission)
 struct DevMission {
     const int32_t *wp_ptr;     // [R + 1] first waypoint of each robot in wp_xy
     const double *wp_xy;       // [.][2] waypoint positions (compared as f32 Vec2s by reached_waypoint, used as f64 by the prior update)
@@ -308,6 +309,8 @@ struct DevMission {
     const uint8_t *has;        // [R] the robot has a mission (and is not despawned)
     float *translation;        // [R][3] Transform::translation (x, height, y)
     long long *finished_tick;  // [R] tick at which the last waypoint was reached, -1 before
+    int32_t *legs_left;        // [R] further legs that follow the route (Mission::next_route, robot.rs:966-993): while > 0 the route's
+                               //     last waypoint ends a leg, not the mission
 };
 
 // Collision bookkeeping on the device (mgx_collisions.hip, which says what every array is for).  Both passes, robot-robot and

@@ -533,7 +533,8 @@ __global__ void k_gather_variable_means(DevWorld w, int var, double *__restrict_
 // ---- missions on the device (mgx_mission_tick) ---------------------------------------------------------------
 // reached_waypoint (robot.rs:2080-2176): the estimated position (belief mean of the rule's variable, as f32) against the
 // next waypoint, squared distance in f32 against the rule's limit; a robot that reaches its last waypoint is reported in
-// the host-mapped event list (ev[0] = count, ev[1 ..] = robot ids) that the host reads at the tick's one synchronisation.
+// the host-mapped event list (ev[0] = count, ev[1 ..] = robot ids, MISSION_EVENT_LEG set where a leg ended and not the mission)
+// that the host reads at the tick's one synchronisation.
 __global__ void k_mission_reached(DevWorld w, DevMission m, int n, long long tick, unsigned int *ev) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n || !m.has[r]) return;
@@ -550,9 +551,13 @@ __global__ void k_mission_reached(DevWorld w, DevMission m, int n, long long tic
     if (dx * dx + dy * dy < m.dist2[2 * r + (last ? 1 : 0)]) {
         m.target[r] = t + 1;
         if (last) {
-            m.finished_tick[r] = tick;
+            // Mission::next_route (robot.rs:966-993): with legs left the route's end is a leg's end — the mission is not complete,
+            // the robot waits where it is (target == n_wp) and the host hears of it in the same list, its id marked by the top bit
+            const int32_t legs = m.legs_left[r];
+            if (legs > 0) m.legs_left[r] = legs - 1;
+            else m.finished_tick[r] = tick;
             const unsigned slot = atomicAdd_system(&ev[0], 1u);
-            ev[1 + slot] = (unsigned)r;
+            ev[1 + slot] = (unsigned)r | (legs > 0 ? MISSION_EVENT_LEG : 0u);
         }
     }
 }

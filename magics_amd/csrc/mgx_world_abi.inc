@@ -604,6 +604,12 @@ int mgx_set_idle(mgx_world *w, int32_t robot, int32_t idle) {
     return MGX_OK;
 }
 
+int mgx_get_idle(mgx_world *w, int32_t robot, int32_t *idle) {
+    if (!w || !idle || robot < 0 || (size_t)robot >= w->robots.size()) return fail(MGX_ERR_INVALID, "bad argument");
+    *idle = w->robots[(size_t)robot].idle ? 1 : 0;
+    return MGX_OK;
+}
+
 int mgx_set_antennas(mgx_world *w, uint32_t n, const int32_t *robots, const uint8_t *active) {
     MGX_ENTER(w);
     if (!w || (n && (!robots || !active))) return fail(MGX_ERR_INVALID, "null argument");

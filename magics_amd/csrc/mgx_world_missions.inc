@@ -5,16 +5,18 @@ extern "C" {
 static int mission_download(mgx_world *w) {  // device -> host copies of what the device advances (before the arrays are laid out again)
     mgx_world::Mission &ms = w->mission;
     if (!ms.uploaded) return MGX_OK;
-    std::vector<int32_t> tg;
+    std::vector<int32_t> tg, lg;
     std::vector<float> tr;
     std::vector<long long> fin;
     HIP_TRY(ms.target_d.download(tg, w->stream));
     HIP_TRY(ms.translation_d.download(tr, w->stream));
     HIP_TRY(ms.finished_d.download(fin, w->stream));
+    HIP_TRY(ms.legs_d.download(lg, w->stream));
     HIP_TRY(hipStreamSynchronize(w->stream));
     for (size_t r = 0; r < tg.size() && r < ms.target.size(); r++) {
         ms.target[r] = tg[r];
         ms.finished_tick[r] = fin[r];
+        ms.legs_left[r] = lg[r];
         for (int c = 0; c < 3; c++) ms.translation[3 * r + c] = tr[3 * r + c];
     }
     return MGX_OK;
@@ -24,7 +26,7 @@ static int mission_upload(mgx_world *w) {
     const size_t R = w->robots.size();
     ms.wp.resize(R);
     ms.target.resize(R, 0); ms.vars.resize(2 * R, 0); ms.dist2.resize(2 * R, 0.f); ms.translation.resize(3 * R, 0.f);
-    ms.time_scale.resize(R, 0.0); ms.has.resize(R, 0); ms.finished_tick.resize(R, -1);
+    ms.time_scale.resize(R, 0.0); ms.has.resize(R, 0); ms.finished_tick.resize(R, -1); ms.legs_left.resize(R, 0);
     std::vector<int32_t> ptr(R + 1, 0);
     std::vector<double> xy;
     for (size_t r = 0; r < R; r++) {
@@ -42,6 +44,7 @@ static int mission_upload(mgx_world *w) {
     HIP_TRY(ms.time_scale_d.upload(ms.time_scale, s));
     HIP_TRY(ms.has_d.upload(ms.has, s));
     HIP_TRY(ms.finished_d.upload(ms.finished_tick, s));
+    HIP_TRY(ms.legs_d.upload(ms.legs_left, s));
     HIP_TRY(ms.rec_d.reserve(4 * R));
     HIP_TRY(ms.robots_d.reserve(R));
     HIP_TRY(ms.waypoints_d.reserve(2 * R));
@@ -58,7 +61,7 @@ static int mission_upload(mgx_world *w) {
     }
     DevMission &d = ms.d;
     d.wp_ptr = ms.wp_ptr_d.p; d.wp_xy = ms.wp_xy_d.p; d.target = ms.target_d.p; d.vars = ms.vars_d.p; d.dist2 = ms.dist2_d.p;
-    d.time_scale = ms.time_scale_d.p; d.has = ms.has_d.p; d.translation = ms.translation_d.p; d.finished_tick = ms.finished_d.p;
+    d.time_scale = ms.time_scale_d.p; d.has = ms.has_d.p; d.translation = ms.translation_d.p; d.finished_tick = ms.finished_d.p; d.legs_left = ms.legs_d.p;
     ms.uploaded = true;
     ms.dirty = false;
     ms.alive_dirty = true;
@@ -72,6 +75,7 @@ int mgx_mission_set(mgx_world *w, int32_t robot, const mgx_mission_desc *desc) {
     if (rb.ghost || rb.removed) return fail(MGX_ERR_INVALID, "robot %d is not a live local robot", robot);
     if (desc->n_waypoints == 0 || !desc->waypoints_xy) return fail(MGX_ERR_INVALID, "a mission needs at least one waypoint");
     if ((int)desc->reach_var >= rb.K || (int)desc->finish_var >= rb.K) return fail(MGX_ERR_INVALID, "rule names a variable beyond the horizon");
+    if (desc->legs_after > 0x7fffffffu) return fail(MGX_ERR_INVALID, "legs_after %u: more legs than a mission can count", desc->legs_after);
     if (collisions_sharded(w)) return fail(MGX_ERR_STATE, "missions run on unsharded worlds");
     mgx_world::Mission &ms = w->mission;
     if (ms.uploaded && !ms.dirty) {  // the device has advanced the missions it holds: fetch before the arrays are laid out again
@@ -81,7 +85,7 @@ int mgx_mission_set(mgx_world *w, int32_t robot, const mgx_mission_desc *desc) {
     const size_t R = w->robots.size(), r = (size_t)robot;
     ms.wp.resize(R);
     ms.target.resize(R, 0); ms.vars.resize(2 * R, 0); ms.dist2.resize(2 * R, 0.f); ms.translation.resize(3 * R, 0.f);
-    ms.time_scale.resize(R, 0.0); ms.has.resize(R, 0); ms.finished_tick.resize(R, -1);
+    ms.time_scale.resize(R, 0.0); ms.has.resize(R, 0); ms.finished_tick.resize(R, -1); ms.legs_left.resize(R, 0);
     ms.wp[r].assign(desc->waypoints_xy, desc->waypoints_xy + 2 * (size_t)desc->n_waypoints);
     ms.target[r] = 0;
     ms.vars[2 * r] = desc->reach_var; ms.vars[2 * r + 1] = desc->finish_var;
@@ -90,6 +94,7 @@ int mgx_mission_set(mgx_world *w, int32_t robot, const mgx_mission_desc *desc) {
     ms.time_scale[r] = desc->time_scale;
     ms.has[r] = 1;
     ms.finished_tick[r] = -1;
+    ms.legs_left[r] = (int32_t)desc->legs_after;
     ms.any = true;
     ms.dirty = true;
     return MGX_OK;
@@ -181,11 +186,27 @@ static int mission_tick_begin(mgx_world *w, float comms_radius, uint32_t method,
     tm.lap(prefetched ? "reached + rows of the search enqueued last tick" : "reached + search");
     // robots that reached their last waypoint this tick: despawned before the topology systems see them (robot.rs:2172) —
     // the search still looked at them, so they are taken out of its rows here
-    const unsigned n_fin = ms.ev_host[0];
+    // ... and the robots that ended a leg with legs left (the ids with MISSION_EVENT_LEG): MissionState::Idle from here on
+    // (Mission::next_route, robot.rs:987, inside reached_waypoint: ahead of the chain) — the flags and the edge gates travel with
+    // mission_tick_end's commit, ahead of the tick's sweeps and of its counter log.  They stay in the world and in the search's rows
+    const unsigned n_ev = ms.ev_host[0];
     std::vector<uint8_t> gone;
     ms.last_finished.clear();
+    ms.last_leg_ended.clear();
+    std::vector<int> fin;
+    for (unsigned e = 0; e < n_ev; e++) {
+        const unsigned int id = ms.ev_host[1 + e];
+        if (id & MISSION_EVENT_LEG) ms.last_leg_ended.push_back((int32_t)(id & ~MISSION_EVENT_LEG));
+        else fin.push_back((int)id);
+    }
+    if (!ms.last_leg_ended.empty()) {
+        std::sort(ms.last_leg_ended.begin(), ms.last_leg_ended.end());
+        flush_counts(w);
+        for (int32_t r : ms.last_leg_ended) w->robots[(size_t)r].idle = 1;
+        w->flags_dirty = true;
+    }
+    const unsigned n_fin = (unsigned)fin.size();
     if (n_fin) {
-        std::vector<int> fin(ms.ev_host + 1, ms.ev_host + 1 + n_fin);
         std::sort(fin.begin(), fin.end());
         ms.last_finished.assign(fin.begin(), fin.end());
         for (int r : fin) ms.finished_tick[(size_t)r] = ms.tick_no;
@@ -421,6 +442,7 @@ int mgx_mission_run(mgx_world *w, mgx_mission_run_desc *d) {
                                        d->n_steps)) != MGX_OK)
             return rc;
         d->ticks_done = t + 1;
+        if (!ms.last_leg_ended.empty()) break;  // a leg ended: the caller plans the next one (mgx_mission_legs_ended says whose)
         if (d->stop_when_all_finished) {
             bool all = true;
             for (size_t r = 0; r < R && all; r++) all = !ms.has[r] || ms.finished_tick[r] >= 0;
@@ -441,6 +463,15 @@ int mgx_mission_finished(mgx_world *w, int32_t *robots, uint32_t capacity, uint3
     MGX_ENTER(w);
     if (!w || !n) return fail(MGX_ERR_INVALID, "null argument");
     const std::vector<int32_t> &f = w->mission.last_finished;
+    *n = (uint32_t)f.size();
+    if (robots)
+        for (size_t i = 0; i < f.size() && i < capacity; i++) robots[i] = f[i];
+    return MGX_OK;
+}
+int mgx_mission_legs_ended(mgx_world *w, int32_t *robots, uint32_t capacity, uint32_t *n) {
+    MGX_ENTER(w);
+    if (!w || !n) return fail(MGX_ERR_INVALID, "null argument");
+    const std::vector<int32_t> &f = w->mission.last_leg_ended;
     *n = (uint32_t)f.size();
     if (robots)
         for (size_t i = 0; i < f.size() && i < capacity; i++) robots[i] = f[i];
@@ -471,6 +502,20 @@ int mgx_mission_read(mgx_world *w, float *translations, int32_t *targets, int64_
         if (targets) targets[r] = ms.has[r] ? ms.target[r] : -1;
         if (finished_tick) finished_tick[r] = ms.finished_tick[r];
     }
+    return check_device_error(w);
+}
+
+int mgx_mission_legs_read(mgx_world *w, int32_t *legs_left) {
+    MGX_ENTER(w);
+    if (!w || !legs_left) return fail(MGX_ERR_INVALID, "null argument");
+    mgx_world::Mission &ms = w->mission;
+    if (!ms.any) return fail(MGX_ERR_STATE, "no robot has a mission");
+    if (ms.uploaded && !ms.dirty) {
+        int rc = mission_download(w);
+        if (rc != MGX_OK) return rc;
+    }
+    const size_t R = std::min(w->robots.size(), ms.legs_left.size());
+    for (size_t r = 0; r < w->robots.size(); r++) legs_left[r] = (r < R && ms.has[r]) ? ms.legs_left[r] : 0;
     return check_device_error(w);
 }
 

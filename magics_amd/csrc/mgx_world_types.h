@@ -805,12 +805,13 @@ struct mgx_world {
         bool any = false, dirty = false, uploaded = false;
         std::vector<std::vector<double>> wp;  // per robot: [n][2]
         std::vector<int32_t> target;
+        std::vector<int32_t> legs_left;       // further legs behind the route (mgx_mission_desc.legs_after; the device counts it down)
         std::vector<uint32_t> vars;           // [R][2]
         std::vector<float> dist2, translation;  // [R][2], [R][3]
         std::vector<double> time_scale;
         std::vector<uint8_t> has;
         std::vector<long long> finished_tick;
-        DevBuf<int32_t> wp_ptr_d, target_d, alive_d, robots_d;
+        DevBuf<int32_t> wp_ptr_d, target_d, alive_d, robots_d, legs_d;
         DevBuf<double> wp_xy_d, time_scale_d, rec_d, waypoints_d, ts_list_d;
         DevBuf<uint32_t> vars_d;
         DevBuf<float> dist2_d, translation_d;
@@ -823,6 +824,7 @@ struct mgx_world {
         long long tick_no = 0;
         bool in_tick = false;                // between mgx_mission_tick_begin and _end
         std::vector<int32_t> last_finished;  // robots whose mission completed in the last begin, ascending
+        std::vector<int32_t> last_leg_ended; // robots that ended a leg with legs left in the last begin, ascending (Idle since)
         float search_radius = 0.f;           // what the last tick's topology pass searched with: the coming tick's search is enqueued
         uint32_t search_method = 0;          //   with the same (mgx_mission_tick_end), used if the next begin asks for the same
         std::vector<float> search_radii;     // ... per group where the last begin had one radius per group (else empty)

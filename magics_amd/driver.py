@@ -78,14 +78,18 @@ def _global_path(driver, robot, path_xy, planning_horizon, **flags):
 
 class Driver:
     def __init__(self, world, n_robots, K, waypoints, radii, t0, steps, comms_radius, target_speed, hz=10.0,
-                 height=0.5, despawn_when_finished=True, failure_draws=None, idle=()):
+                 height=0.5, despawn_when_finished=True, failure_draws=None, idle=(), legs=None):
         """waypoints[r]: list of (x, y) still to visit (the first one is the next waypoint);
         radii[r]: robot radius (reached-when-intersects distance, formation.yaml `robot-radius`);
         t0[r]: the robot's T0 component (f32); failure_draws: callable(tick, n) -> bool array of
         antennas that stay ON this tick (None: no comms failures); idle: robots that start in MissionState::Idle —
         they wait where they are (no waypoint advance, no prior update, no Transform move: robot.rs:995-1005, 2212, 2303)
-        until `global_path` hands them a route."""
+        until `global_path` hands them a route.  legs[r] (default none): further legs that follow robot r's route — a robot whose
+        route ends with legs left has ended a LEG (Mission::next_route, robot.rs:966-993): it goes Idle (not finished, not
+        despawned), is listed in `legs_ended` for that tick, and `global_path` wakes it on the next leg's route."""
         self.w, self.n, self.K = world, n_robots, K
+        self.legs_left = np.zeros(n_robots, dtype=np.int32) if legs is None else np.array(legs, dtype=np.int32)
+        self.legs_ended = []   # robots that ended a leg in the last tick, ascending
         self.idle = np.zeros(n_robots, dtype=bool)
         for r in idle:
             world.set_idle(int(r), True)
@@ -108,6 +112,7 @@ class Driver:
     # reached_waypoint (robot.rs:2080-2176): intermediate waypoints are checked against the horizon
     # variable, the last one against the current variable (formation.yaml of the Circle Experiment)
     def _reached_waypoint(self):
+        self.legs_ended = []
         todo = [r for r in range(self.n) if self.alive[r] and self.way[r] and not self.idle[r]]
         if not todo:
             return
@@ -119,7 +124,12 @@ class Driver:
             d = est - wp
             if F32(d[0] * d[0] + d[1] * d[1]) < F32(self.radii[r]) * F32(self.radii[r]):
                 self.way[r].pop(0)
-                if not self.way[r]:
+                if not self.way[r] and self.legs_left[r] > 0:   # a leg's end: Idle until the next leg's path (robot.rs:987)
+                    self.legs_left[r] -= 1
+                    self.w.set_idle(r, True)
+                    self.idle[r] = True
+                    self.legs_ended.append(r)
+                elif not self.way[r]:
                     self.finished_at[r] = self.tick_no
                     if self.despawn:
                         self.w.remove_robot(r)
@@ -183,8 +193,11 @@ class DeviceDriver:
     the position / velocity samples taken every 100 ms of simulated time collect in `track_samples`."""
 
     def __init__(self, world, n_robots, K, waypoints, radii, t0, steps, comms_radius, target_speed, hz=10.0,
-                 height=0.5, despawn_when_finished=True, failure_draws=None, idle=(), tracks=False):
+                 height=0.5, despawn_when_finished=True, failure_draws=None, idle=(), tracks=False, legs=None):
+        """legs[r] (default none): further legs behind robot r's route, as Driver takes them — handed to the device as legs_after;
+        `legs_ended` lists the robots that ended a leg in the last tick (mission_legs_ended), `completed` those whose mission did"""
         self.w, self.n, self.K = world, n_robots, K
+        self.legs_ended, self.completed = [], []
         self.tracks, self.track_samples, self.travelled = bool(tracks), [], np.zeros(n_robots)
         if self.tracks:
             world.tracks_enable(True, period_ns=100_000_000, tick_ns=int(round(1e9 / hz)), next_tick=0)
@@ -200,7 +213,8 @@ class DeviceDriver:
             # intermediate waypoints against the horizon variable, the last one against the current variable, both
             # within the robot's radius (the Circle Experiment's formation.yaml)
             world.mission_set(r, np.asarray(waypoints[r], dtype=np.float64), K - 1, 0, r2, r2,
-                              (F32(cur[r, 0]), F32(height), F32(cur[r, 1])), float(self.dt32 / F32(t0[r])))
+                              (F32(cur[r, 0]), F32(height), F32(cur[r, 1])), float(self.dt32 / F32(t0[r])),
+                              **({} if legs is None else {"legs_after": int(legs[r])}))
         self.n_way = np.array([len(wp) for wp in waypoints])
         self.next_number, self.tick_no = 1, 0
         self._alive = np.ones(n_robots, dtype=bool)
@@ -222,6 +236,8 @@ class DeviceDriver:
             ant = np.ones(self.n, dtype=np.uint8)
             ant[live] = d
             self.w.mission_tick_end(self.steps, self.max_speed, self.delta_t, antennas=ant)
+        if hasattr(self.w, "mission_legs_ended"):
+            self.legs_ended, self.completed = self.w.mission_legs_ended().tolist(), self.w.mission_finished().tolist()
         self.tick_no += 1
         self._finished_dirty = True
         return created, deleted

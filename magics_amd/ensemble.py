@@ -494,18 +494,25 @@ class Ensemble:
             # one comms radius per member (a retired member's is its own still: it changes nothing, so nothing is uploaded again)
             radius = np.array([m.sim.comms_radius for m in self.members], dtype=np.float32) if self._per_group_radius else s0.comms_radius
             numbers, stats, fin = w.mission_tick_begin_groups(radius, numbers, despawn_finished=s0.despawn, method=s0.method)
-            finished = [[] for _ in self.members]
+            finished, legs = [[] for _ in self.members], [[] for _ in self.members]
             for wid in fin:
                 g, r = self._owner[int(wid)]
                 finished[g].append(r)
+            # the robots that ended a leg of a global-planner mission in this tick: read once, routed like the completions
+            if any(m.sim._has_legs for m in ticking):
+                for wid in w.mission_legs_ended():
+                    g, r = self._owner[int(wid)]
+                    legs[g].append(r)
             antennas = None
             for m in ticking:     # every member makes its own draws from its own stream, in its own robot order
                 g = m._view._group
-                ant = m.sim._tick_device_between(int(numbers[g]), int(stats[g, 0]), int(stats[g, 1]), finished[g])
+                ant = m.sim._tick_device_between(int(numbers[g]), int(stats[g, 0]), int(stats[g, 1]), finished[g], legs=legs[g])
                 if ant is not None:
                     if antennas is None:
                         antennas = np.ones(len(self._owner), dtype=np.uint8)
                     antennas[m._view.ids] = ant
+            for m in ticking:     # the next legs' requests, under their members' groups: ahead of this tick's planner slice
+                m.sim._plan()
             w.mission_tick_end(self._tick_steps(s0), float(s0.max_speed), float(s0.dt32), antennas=antennas)
             self._clock = self.tick_no + 1
         for m in active:

@@ -150,6 +150,7 @@ SYMBOLS = {
     "mgx_set_safety_multiplier": (C.c_int, [_V, C.c_double]),
     "mgx_set_antenna": (C.c_int, [_V, C.c_int32, C.c_int32]),
     "mgx_set_idle": (C.c_int, [_V, C.c_int32, C.c_int32]),
+    "mgx_get_idle": (C.c_int, [_V, C.c_int32, C.POINTER(C.c_int32)]),
     "mgx_set_antennas": (C.c_int, [_V, C.c_uint32, C.c_void_p, C.c_void_p]),
     "mgx_neighbours": (C.c_int, [_V, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                  C.POINTER(C.c_uint64)]),
@@ -229,6 +230,8 @@ SYMBOLS = {
     "mgx_mission_tick_end": (C.c_int, [_V, C.c_void_p, C.c_double, C.c_double, C.c_char_p, C.c_uint32]),
     "mgx_mission_tick_end_groups": (C.c_int, [_V, C.c_void_p, C.c_double, C.c_double, C.c_uint32, C.c_char_p, C.c_void_p]),
     "mgx_mission_finished": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "mgx_mission_legs_ended": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "mgx_mission_legs_read": (C.c_int, [_V, C.c_void_p]),
     "mgx_mission_translations": (C.c_int, [_V, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]),
     "mgx_mission_read": (C.c_int, [_V, C.c_void_p, C.c_void_p, C.c_void_p]),
     "mgx_collisions_enable": (C.c_int, [_V, C.c_int32, C.c_uint32, C.c_uint64]),
@@ -410,7 +413,7 @@ class MissionRunDesc(C.Structure):
 
 class MissionDesc(C.Structure):
     """mgx_mission_desc (include/mgx.h)"""
-    _fields_ = [("n_waypoints", C.c_uint32), ("reserved", C.c_uint32), ("waypoints_xy", c_double_p), ("reach_var", C.c_uint32),
+    _fields_ = [("n_waypoints", C.c_uint32), ("legs_after", C.c_uint32), ("waypoints_xy", c_double_p), ("reach_var", C.c_uint32),
                 ("finish_var", C.c_uint32), ("reach_dist2", C.c_float), ("finish_dist2", C.c_float), ("translation", C.c_float * 3),
                 ("reserved2", C.c_float), ("time_scale", C.c_double)]
 

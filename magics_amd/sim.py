@@ -184,6 +184,10 @@ class Simulation:
         iteration was measured at outside a tick), and the start of a tick collects — waiting for the slices enqueued, so that
         the tick a path arrives in depends on the request and the budget and not on timing — and applies what has ended: a
         request that takes s slices activates its robot at the start of tick s after the one it spawned in (True: tick 1).
+        A mission of more than two taskpoints runs leg by leg (Mission::next_route, robot.rs:966-993): the robot keeps every
+        taskpoint, the device mission gets the first route and the number of legs behind it, and a robot the tick reports as
+        having ended a leg goes Idle, has its route closed and the next one opened, and asks for taskpoints[k] -> taskpoints[k+1]
+        in that tick (between its halves) — applied under the same rules as a spawn's request.
         A robot despawned while it waits has its request cancelled; a request that FAILS is submitted again with the stream
         state its result carries (the reference's "try again"), and every attempt is in the export.  While requests are pending
         run() goes tick by tick."""
@@ -232,6 +236,7 @@ class Simulation:
         self._plan_requests = []   # (robot id, start, end, stream state) of the robots spawned in this tick
         self._plans_ready = []     # (robot id, result) planned in the tick before: applied when the next one starts
         self._plan_log = []        # per request: {"robot", "status", "n_nodes", "iterations", "n_points"}
+        self._has_legs = False     # some robot's mission has more than one leg: the ticks ask the world who ended one
         self._pending_track = None
         self._trk_log = []  # what _track noted since _tracks last ran
         self.name = scenario.get("name", "")
@@ -316,11 +321,12 @@ class Simulation:
                 raise NotImplementedError("planning-strategy rrt-star: the global planner is outside the hot path")
             if not (self.dev and hasattr(self.w, "apply_global_paths") and (self._planner == "host" or hasattr(self.w, "planner_enable"))):
                 raise NotImplementedError("planning-strategy rrt-star: the global planner needs an engine world with device missions")
-            if len(desc["waypoints"]) > 2:
-                raise NotImplementedError("planning-strategy rrt-star: a mission of more than two taskpoints (its later legs are "
-                                          "planned when the earlier ones end) is not supported")
         rb = self.cfg["robot"]
-        states = desc["waypoints"]
+        taskpoints = desc["waypoints"]
+        # Mission::global keeps every taskpoint and opens with the route [taskpoint 0, taskpoint 1] (robot.rs:862-908); the later
+        # legs are planned when the earlier ones end (_legs_ended)
+        states = taskpoints[:2] if planned else taskpoints
+        legs_after = len(taskpoints) - 2 if planned else 0
         mean0, prior, dt = robot_initial_state(states[0], states[1], desc["timesteps"], desc["radius"], rb["target-speed"], rb["planning-horizon"])
         if planned:
             mean0[:] = np.asarray(states[0], dtype=F).astype(np.float64)  # horizon state = start (robot.rs:1195)
@@ -336,7 +342,12 @@ class Simulation:
                             "time_scale": float(self.dt32 / t0), "colour": desc["colour"], "rng": desc["rng"],
                             "strategy": desc["planning-strategy"], "reach": desc["waypoint-reached-when-intersects"],
                             "finish": desc["finished-when-intersects"], "positions": [], "velocities": [], "travelled": 0.0,
-                            "trk_elapsed": 0, "trk_prev": None, "entity": key, "idle": planned})
+                            "trk_elapsed": 0, "trk_prev": None, "entity": key, "idle": planned,
+                            # the legs of a global-planner mission: every taskpoint, the leg under way, the legs that ended (as
+                            # export() gives them, with the tick they ended in) and when the one under way was opened; the tick of
+                            # every entry of `positions` (metrics() measures a sample against the route of the leg it was taken in)
+                            "taskpoints": [s.copy() for s in taskpoints] if planned else None, "leg": 0, "routes": [],
+                            "route_started_at": self.elapsed(), "position_ticks": []})
         self._translation = np.vstack([self._translation, np.array([[states[0][0], -1.5, states[0][1]]], dtype=F)])  # spawner.rs:548
         if self.dev:
             me = self.robots[-1]
@@ -349,7 +360,8 @@ class Simulation:
                 return var, float(lim)
             (rv, rd), (fv, fd) = rule(me["reach"]), rule(me["finish"])
             self.w.mission_set(rid, np.array([s_[:2] for s_ in states[1:]], dtype=np.float64), rv, fv, rd, fd,
-                               self._translation[-1], me["time_scale"])
+                               self._translation[-1], me["time_scale"], **({"legs_after": legs_after} if legs_after else {}))
+            self._has_legs = self._has_legs or legs_after > 0
             if self._dev_metrics:
                 self.w.track_metrics_set_route(rid, self._route(me))
             if planned:  # Mission::global (robot.rs:1294): Idle until a path has been found
@@ -358,9 +370,13 @@ class Simulation:
                                             desc["rng"].state))
 
     @staticmethod
+    def _points(states):
+        return [[float(s[0]), float(s[1])] for s in states]
+
+    @staticmethod
     def _route(r):
-        """a robot's route as export() gives it: mission.routes[0].waypoints"""
-        return [[float(s[0]), float(s[1])] for s in r["waypoints"]]
+        """a robot's route as export() gives it: the waypoints of the last of mission.routes, the leg under way"""
+        return Simulation._points(r["waypoints"])
 
     @property
     def translation(self):
@@ -371,8 +387,23 @@ class Simulation:
         return self._translation
 
     # -- progress_missions (robot.rs:578-633) + the path-finding completion handler (robot.rs:643-799) ----------------------
+    def _legs_ended(self, ids):
+        """the device reported these robots at the last waypoint of a route with legs left (Mission::next_route, robot.rs:966-993):
+        the leg's route is closed, the next one [taskpoint k, taskpoint k+1] opened, the robot Idle (the engine has made it so), and
+        the path-finding request of progress_missions queued (robot.rs:578-633): between the TASKPOINTS' own positions (:601-602),
+        from the robot's forked stream as it stands (:622 clones the component; nothing in this runner draws from it)"""
+        for rid in ids:
+            r = self.robots[int(rid)]
+            now = self.elapsed()
+            r["routes"].append({"waypoints": self._route(r), "started_at": r["route_started_at"], "finished_at": now, "end_tick": self.tick_no})
+            r["leg"] += 1
+            a, b = r["taskpoints"][r["leg"]], r["taskpoints"][r["leg"] + 1]
+            r["waypoints"], r["target"], r["idle"], r["route_started_at"] = [a.copy(), b.copy()], 1, True, now
+            self._plan_requests.append((r["id"], tuple(float(v) for v in a[:2]), tuple(float(v) for v in b[:2]), r["rng"].state))
+
     def _plan(self):
-        """the requests of the robots that spawned in this tick, in one call; what comes back waits for the next tick"""
+        """the requests of the robots that spawned in this tick (before its FixedUpdate) or ended a leg in it (between the tick's
+        halves, ahead of its planner slice), in one call each; what comes back waits for the next tick"""
         reqs, self._plan_requests = self._plan_requests, []
         if not reqs:
             return
@@ -421,7 +452,8 @@ class Simulation:
 
     def _plans_applied(self, ids):
         """behind the apply_global_paths that took these robots' plans"""
-        if self._dev_metrics:  # (the robots were Idle so far: no sample was measured against the route this one replaces)
+        if self._dev_metrics:  # (the robots were Idle so far — since they spawned, or since their last leg ended: no sample was
+            #                      measured against the route this one replaces; from here on samples belong to this leg's path)
             for rid in ids:
                 self.w.track_metrics_set_route(rid, self._route(self.robots[rid]))
 
@@ -508,6 +540,7 @@ class Simulation:
             return
         log, self._trk_log = self._trk_log, []
         for ids, rows, now in log:
+            tick = int(round(now / (self.dt_ns * 1e-9))) - 1
             for k, rid in enumerate(ids):
                 r = self.robots[int(rid)]
                 r["trk_elapsed"] += self.dt_ns
@@ -516,6 +549,7 @@ class Simulation:
                 r["trk_elapsed"] %= 100_000_000
                 pos = rows[k]
                 r["positions"].append([float(pos[0]), float(pos[2])])
+                r.setdefault("position_ticks", []).append(tick)  # (a bare tracker record, as the trackers' checkers keep, has no legs)
                 if r["trk_prev"] is not None:
                     dt = now - r["trk_prev"][1]
                     v = (pos - r["trk_prev"][0]) / F(dt)
@@ -536,6 +570,7 @@ class Simulation:
                                              samples["position"].tolist(), samples["velocity"].tolist()):
             r = self.robots[rid]
             r["positions"].append([pos[0], pos[2]])
+            r.setdefault("position_ticks", []).append(tick)  # (a bare tracker record, as the trackers' checkers keep, has no legs)
             if span:
                 now = (tick + 1) * self.dt_ns * 1e-9
                 dt = now - (tick - span + 1) * self.dt_ns * 1e-9
@@ -687,9 +722,10 @@ class Simulation:
         self._tracks_room(1, sum(1 for r in self.robots if r["alive"]))
         self._goal_clock()
 
-    def _tick_device_between(self, next_number, created, deleted, fin):
-        """what mission_tick_begin gave -> the run's bookkeeping and this tick's comms draws; the antenna bytes for mission_tick_end
-        (one per robot of this run; None: nothing fails)"""
+    def _tick_device_between(self, next_number, created, deleted, fin, legs=()):
+        """what mission_tick_begin gave (legs: the robots of this run that ended a leg in it, mission_legs_ended) -> the run's
+        bookkeeping and this tick's comms draws; the antenna bytes for mission_tick_end (one per robot of this run; None: nothing
+        fails)"""
         self.next_number = next_number
         self._flush_trackers()
         if created or deleted:
@@ -701,6 +737,7 @@ class Simulation:
             if self.despawn:
                 r["alive"] = False
                 self.entities.free(r["entity"])
+        self._legs_ended(legs)
         live = [r for r in self.robots if r["alive"]]
         ant = None
         if live:
@@ -715,7 +752,9 @@ class Simulation:
     def _tick_device(self):
         w = self.w
         self._tick_device_before()
-        ant = self._tick_device_between(*w.mission_tick_begin(self.comms_radius, self.next_number, despawn_finished=self.despawn, method=self.method))
+        ant = self._tick_device_between(*w.mission_tick_begin(self.comms_radius, self.next_number, despawn_finished=self.despawn, method=self.method),
+                                        legs=w.mission_legs_ended() if self._has_legs else ())
+        self._plan()  # (the next legs of the robots that have just ended one: ahead of this tick's planner slice)
         w.mission_tick_end(self.steps, float(self.max_speed), float(self.dt32), antennas=ant)
 
     def tick(self):
@@ -785,12 +824,15 @@ class Simulation:
         if not self.robots:
             self.tick_no += 1
             return
+        if self._has_legs and self._plan_tickets:
+            # requests ride this tick's slice, and a robot that ends a leg in it must submit its next one AHEAD of that slice: the
+            # tick in its two halves (as tick() makes it)
+            self._tick_device()
+            self.tick_no += 1
+            return
         self._flush_trackers(synchronise=True)
         # (planned paths are applied one tick on; a pending plan is looked for at the start of every tick)
         m = 1 + (self._quiet_ticks(cap - 1) if cap > 1 and not self._plans_ready and not self._plan_tickets else 0)
-        for _ in range(m - 1):  # the real spawners live through the same frames (nothing happens in them)
-            for sp in self.spawners:
-                sp.tick(self.dt_ns)
         self._tracks_room(m, sum(1 for r in self.robots if r["alive"]))
         self._goal_clock()
         host_tr = self._host_needs_transforms()
@@ -799,6 +841,11 @@ class Simulation:
                                  wyrand_state=self.rng.state, stop_when_all_finished=all(sp.exhausted() for sp in self.spawners),
                                  want_translations=host_tr)
         self.next_number, self.rng.state = out["next_number"], out["wyrand_state"]
+        # the real spawners live through the same frames (nothing happens in them) — the frames the call made: it returns early
+        # behind a tick in which a leg ended
+        for _ in range(out["ticks"] - 1):
+            for sp in self.spawners:
+                sp.tick(self.dt_ns)
         for j in range(out["ticks"]):
             if out["created"][j] or out["deleted"][j]:
                 self.events.append((self.tick_no, int(out["created"][j]), int(out["deleted"][j])))
@@ -809,6 +856,7 @@ class Simulation:
                 if self.despawn:
                     r["alive"] = False
                     self.entities.free(r["entity"])
+            self._legs_ended(out["legs_ended"][j] if self._has_legs else ())
             if host_tr:
                 live = [r for r in self.robots if r["alive"]]
                 tr = out["translations"][j]
@@ -819,6 +867,10 @@ class Simulation:
                 self._collide_environment(live, tr)
                 self._goal_areas_host(live, tr, self.tick_no)
             self.tick_no += 1
+        if self._plan_requests:  # legs ended in the call's last tick: their requests go out as in tick(), and a sliced one takes
+            self._plan()         # that tick's slice, which the call enqueued when nothing was pending
+            if self._sliced:
+                self.w.plan_advance(self._plan_budget)
 
     def run(self, max_ticks=None, max_time=None, chunk=256):
         """chunk: device missions — up to that many ticks per engine call (mgx_mission_run) where no spawner acts; 1: tick by tick"""
@@ -858,8 +910,12 @@ class Simulation:
                 "collisions": {"robots": sum(h["times"] for k, h in collisions.items() if r["id"] in k),
                                "environment": env_count.get(r["id"], 0)},
                 "messages": {"sent": {"internal": sent_i, "external": sent_e}, "received": {"internal": recv_i, "external": recv_e}},
-                "mission": {"waypoints": [wps[0], wps[-1]], "started_at": r["started_at"], "finished_at": fin,
-                            "routes": [{"waypoints": wps, "started_at": r["started_at"], "finished_at": fin}]},
+                # mission.waypoints: the taskpoints (export.rs:391); routes: one entry per leg started (export.rs:400-415), the
+                # one under way with its planned path — or [taskpoint k, taskpoint k+1] while it waits for one
+                "mission": {"waypoints": [wps[0], wps[-1]] if not r["taskpoints"] or len(r["taskpoints"]) == 2 else self._points(r["taskpoints"]),
+                            "started_at": r["started_at"], "finished_at": fin,
+                            "routes": [{k: leg[k] for k in ("waypoints", "started_at", "finished_at")} for leg in r["routes"]] +
+                                      [{"waypoints": wps, "started_at": r["route_started_at"], "finished_at": fin}]},
                 "planning_strategy": r["strategy"], "color": r["colour"]}
         extra = {}
         if self._planner is not None:  # what became of every path-finding request; a failed one left its robot Idle
@@ -884,7 +940,11 @@ class Simulation:
         deviation_sum, n_positions, n_velocities, n_unrouted}}, "summary": {figure: track_metrics.summary}, "makespan",
         "collisions": {"robots", "environment"}}.  With device_metrics the records are the device's (one read that waits);
         otherwise the streaming restatement (track_metrics.Stream) over the robots' positions / velocities lists and the routes
-        export() gives — the same figures bit for bit, and the checker of the device."""
+        export() gives — the same figures bit for bit, and the checker of the device.
+        A mission of several legs: a sample is measured against the route of the leg it was taken in, in both forms (the device's
+        route is replaced at every hand-over; the host form switches at the same sample).  The reference's script measures every
+        position against all legs' lines concatenated (scripts/perpendicular-path-deviation.py:81-99); the streaming form does NOT —
+        a position is never measured against a leg the robot had not begun or had left."""
         if self.dev:
             self._flush_trackers(synchronise=True)
         self._tracks()
@@ -893,8 +953,7 @@ class Simulation:
             recs = [{k: rec[k].item() for k in rec.dtype.names} for rec in recs]
             recs += [_metrics.Stream().read() for _ in range(len(self.robots) - len(recs))]
         else:
-            recs = [_metrics.stream([(v["velocity"][0], v["velocity"][2]) for v in r["velocities"]], r["positions"], self._route(r))
-                    for r in self.robots]
+            recs = [self._stream_metrics(r) for r in self.robots]
         robots = {}
         for r, rec in zip(self.robots, recs):
             fin = r["finished_at"] if r["finished_at"] is not None else self.elapsed()
@@ -907,6 +966,20 @@ class Simulation:
                 "makespan": self.elapsed(),
                 "collisions": {"robots": sum(h["times"] for h in self.collisions.values()), "environment": sum(h["times"] for h in env_coll.values())},
                 **self._goal_metrics()}
+
+    def _stream_metrics(self, r):
+        """the host streaming form of one robot's record: every position against the route of the leg it was taken in"""
+        vel = [(v["velocity"][0], v["velocity"][2]) for v in r["velocities"]]
+        if not r["routes"]:
+            return _metrics.stream(vel, r["positions"], self._route(r))
+        s, k, legs = _metrics.Stream(), 0, r["routes"]
+        for u, w in vel:
+            s.velocity(u, w)
+        for (x, y), tick in zip(r["positions"], r["position_ticks"]):
+            while k < len(legs) and tick >= legs[k]["end_tick"]:  # (a leg's last sample lies before the tick it ended in)
+                k += 1
+            s.position(x, y, legs[k]["waypoints"] if k < len(legs) else self._route(r))
+        return s.read()
 
     def _goal_metrics(self, window=50.0):
         """{"goal_areas": {"arrivals": per area, "reached": robots in any history, "time_to_goal": {robot: first arrival minus

@@ -218,6 +218,15 @@ class World:
     def set_idle(self, robot, idle):
         self._chk(self._L.mgx_set_idle(self._w, robot, int(bool(idle))))
 
+    def idle_flags(self):
+        """the idle flag of every robot [n] bool, as the world holds them (mgx_get_idle)"""
+        n, _ = self.num_robots()
+        out, v = np.zeros(n, dtype=bool), C.c_int32()
+        for r in range(n):
+            self._chk(self._L.mgx_get_idle(self._w, r, C.byref(v)))
+            out[r] = bool(v.value)
+        return out
+
     def set_antennas(self, robots, active):
         """update_failed_comms (robot.rs:1593-1601): one write per antenna per tick."""
         robots = np.ascontiguousarray(robots, dtype=np.int32)
@@ -459,9 +468,12 @@ class World:
         return a.value, b.value
 
     # -- whole driver ticks on the device (include/mgx.h, mgx_mission_*) ---------------------------------------------
-    def mission_set(self, robot, waypoints_xy, reach_var, finish_var, reach_dist2, finish_dist2, translation, time_scale):
+    def mission_set(self, robot, waypoints_xy, reach_var, finish_var, reach_dist2, finish_dist2, translation, time_scale, legs_after=0):
+        """legs_after: further legs that follow this route (include/mgx.h, MISSIONS OF SEVERAL LEGS); 0: the route is the mission"""
         wp = _f64(waypoints_xy).reshape(-1, 2)
-        d = hostlib.MissionDesc(len(wp), 0, _dp(wp), int(reach_var), int(finish_var), float(reach_dist2), float(finish_dist2),
+        if int(legs_after) < 0:
+            raise ValueError("legs_after: a count of legs")
+        d = hostlib.MissionDesc(len(wp), int(legs_after), _dp(wp), int(reach_var), int(finish_var), float(reach_dist2), float(finish_dist2),
                                 (C.c_float * 3)(*[float(x) for x in translation]), 0.0, float(time_scale))
         self._chk(self._L.mgx_mission_set(self._w, int(robot), C.byref(d)))
 
@@ -512,6 +524,32 @@ class World:
             self._chk(self._L.mgx_mission_finished(self._w, fin.ctypes.data, n_fin, C.byref(k)))
         return nxt, stats[:n_groups], fin
 
+    def mission_finished(self):
+        """ids of the robots whose mission completed in the last mission_tick_begin (any form), ascending (mgx_mission_finished)"""
+        k = C.c_uint32()
+        self._chk(self._L.mgx_mission_finished(self._w, None, 0, C.byref(k)))
+        out = np.zeros(k.value, dtype=np.int32)
+        if k.value:
+            self._chk(self._L.mgx_mission_finished(self._w, out.ctypes.data, k.value, C.byref(k)))
+        return out
+
+    def mission_legs_ended(self):
+        """ids of the robots that ended a leg with legs left in the last mission_tick_begin (any form), ascending: idle since, waiting
+        for apply_global_paths(route=True, activate=True) (mgx_mission_legs_ended)"""
+        k = C.c_uint32()
+        self._chk(self._L.mgx_mission_legs_ended(self._w, None, 0, C.byref(k)))
+        out = np.zeros(k.value, dtype=np.int32)
+        if k.value:
+            self._chk(self._L.mgx_mission_legs_ended(self._w, out.ctypes.data, k.value, C.byref(k)))
+        return out
+
+    def mission_legs_read(self):
+        """legs left per robot as the device has counted them down [n] int32 (mgx_mission_legs_read; synchronises)"""
+        n, _ = self.num_robots()
+        out = np.zeros(n, np.int32)
+        self._chk(self._L.mgx_mission_legs_read(self._w, out.ctypes.data))
+        return out
+
     def mission_tick_end(self, steps, max_speed, delta_t, antennas=None):
         """steps: one schedule, or one schedule per robot group (group_steps above: mgx_mission_tick_end_groups)"""
         ant = None if antennas is None else np.ascontiguousarray(antennas, dtype=np.uint8)
@@ -528,6 +566,7 @@ class World:
                     failure_rate=0.0, wyrand_state=None, stop_when_all_finished=False, want_translations=True, want_antennas=False):
         """Up to n_ticks whole driver ticks in ONE call (mgx_mission_run): per tick what mission_tick_begin / _end would have
         given.  Returns dict(ticks, next_number, wyrand_state, created [t], deleted [t], finished (list of id arrays per tick),
+        legs_ended (likewise: the call returns behind the first tick in which a robot ended a leg, so only the last may hold any),
         translations [t, n, 3] f32, antennas [t, n] u8)."""
         n, _ = self.num_robots()
         T = int(n_ticks)
@@ -553,6 +592,9 @@ class World:
         cuts = np.concatenate([[0], np.cumsum(nfin[:t])]).astype(int)
         return dict(ticks=t, next_number=int(nn.value), wyrand_state=None if wyrand_state is None else int(ws.value), created=created[:t],
                     deleted=deleted[:t], finished=[fin[cuts[i]:cuts[i + 1]].copy() for i in range(t)],
+                    # (an older build named by MGX_LIB knows no legs: nobody ever ends one there)
+                    legs_ended=[np.zeros(0, np.int32) for _ in range(t - 1)] +
+                               ([self.mission_legs_ended() if hasattr(self._L, "mgx_mission_legs_ended") else np.zeros(0, np.int32)] if t else []),
                     translations=None if tr is None else tr[:t], antennas=None if ant is None else ant[:t])
 
     def mission_translations(self):

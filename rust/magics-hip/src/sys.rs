@@ -79,7 +79,7 @@ pub struct mgx_env_desc {
 #[repr(C)]
 pub struct mgx_mission_desc {
     pub n_waypoints: u32,
-    pub reserved: u32,
+    pub legs_after: u32,
     pub waypoints_xy: *const f64,
     pub reach_var: u32,
     pub finish_var: u32,
@@ -284,6 +284,7 @@ extern "C" {
     pub fn mgx_set_safety_multiplier(w: *mut mgx_world, multiplier: f64) -> c_int;
     pub fn mgx_set_antenna(w: *mut mgx_world, robot: i32, active: i32) -> c_int;
     pub fn mgx_set_idle(w: *mut mgx_world, robot: i32, idle: i32) -> c_int;
+    pub fn mgx_get_idle(w: *mut mgx_world, robot: i32, idle: *mut i32) -> c_int;
     pub fn mgx_set_antennas(w: *mut mgx_world, n: u32, robots: *const i32, active: *const u8) -> c_int;
     pub fn mgx_neighbours(w: *mut mgx_world, positions_xyz: *const f32, radius: f32, method: u32, row_ptr: *mut i32, neighbours_out: *mut i32, capacity: u64, needed: *mut u64) -> c_int;
     pub fn mgx_update_topology(w: *mut mgx_world, positions_xyz: *const f32, radius: f32, method: u32, robot_number_next: *mut u64, stats: *mut u32) -> c_int;
@@ -339,9 +340,11 @@ extern "C" {
     pub fn mgx_mission_tick_begin_groups_radii(w: *mut mgx_world, comms_radii: *const f32, method: u32, n_groups: u32, number_next: *mut u64, despawn_finished: i32, stats: *mut u32) -> c_int;
     pub fn mgx_mission_tick_end_groups(w: *mut mgx_world, antennas: *const u8, max_speed: f64, delta_t: f64, n_groups: u32, steps: *const u8, step_first: *const u32) -> c_int;
     pub fn mgx_mission_finished(w: *mut mgx_world, robots: *mut i32, capacity: u32, n: *mut u32) -> c_int;
+    pub fn mgx_mission_legs_ended(w: *mut mgx_world, robots: *mut i32, capacity: u32, n: *mut u32) -> c_int;
     pub fn mgx_mission_run(w: *mut mgx_world, desc: *mut mgx_mission_run_desc) -> c_int;
     pub fn mgx_mission_translations(w: *mut mgx_world, translations: *mut f32, capacity_robots: u32, n_robots: *mut u32) -> c_int;
     pub fn mgx_mission_read(w: *mut mgx_world, translations: *mut f32, targets: *mut i32, finished_tick: *mut i64) -> c_int;
+    pub fn mgx_mission_legs_read(w: *mut mgx_world, legs_left: *mut i32) -> c_int;
     pub fn mgx_collisions_enable(w: *mut mgx_world, enabled: i32, method: u32, event_capacity: u64) -> c_int;
     pub fn mgx_collisions_update(w: *mut mgx_world, positions_xyz: *const f32) -> c_int;
     pub fn mgx_collisions_read(w: *mut mgx_world, first: u64, events: *mut mgx_collision_event, capacity: u64, n_total: *mut u64, dropped: *mut u64, per_robot: *mut u32) -> c_int;
